@@ -11,6 +11,11 @@ same steps with one launch per kernel (bev_set_lanes(ctx, 1)).  N > 1: one proce
 nccl = RCCL), frames sharded contiguously, the only collective on the path is
 the broadcast of the frame-range table; weak scaling (1000 frames per GPU).
 
+A plain run sets up, warms up, times --steps steps and prints the headline (`value`, `ms_per_step`); `--full` adds
+what takes passes or work of its own: the fenced median step, the per-kernel profile passes and the roofline, the
+CPU baseline and the routes of the last sub-batch.  `--dump-outputs DIR` writes what the last timed step computed for
+a fixed sample of frames.
+
 Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
@@ -33,12 +38,39 @@ HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 # geometry (a 64-row loop over 8 KiB row pieces, whole-line stores) as a pure copy.
 COPY_CEILING_GBPS = 6610.0
 WALK_SHAPE_CEILING_GBPS = 5010.0
+DUMP_BYTES = 60_000_000  # --dump-outputs: at most this much in all (whole frames of a seeded sample)
+ORDERED_FIELDS = ("x", "y", "z", "intensity", "row", "col", "t", "label")  # the ordered cloud's fields, padding left out
+
+
+def dump_outputs(out_dir, first, count, S, L, M, read_frame):
+    """What a caller of the timed path receives — the ordered, labelled clouds and the multi- and single-layer BEVs —
+    for a fixed, seeded sample of this rank's frames, as DIR/<name>.npy: ordered_cloud (n, S, 8) float64 (columns
+    ORDERED_FIELDS), multi_bev (n, L, M, M) and single_bev (n, M, M) float32, sample_frames (n,) float64 (frame ids).
+    read_frame(i) -> (ordered records, multi, single) of local frame i."""
+    import numpy as np
+
+    per_frame = S * len(ORDERED_FIELDS) * 8 + (L * M * M + M * M) * 4
+    n = max(1, min(count, 8, DUMP_BYTES // per_frame))
+    pick = np.sort(np.random.default_rng(0xD0D0).choice(count, n, replace=False))
+    ordered = np.empty((n, S, len(ORDERED_FIELDS)), np.float64)
+    multi = np.empty((n, L, M, M), np.float32)
+    single = np.empty((n, M, M), np.float32)
+    for j, i in enumerate(pick):
+        o, m, s_ = read_frame(int(i))
+        for c, f in enumerate(ORDERED_FIELDS):
+            ordered[j, :, c] = o[f]
+        multi[j] = m.reshape(L, M, M)
+        single[j] = s_.reshape(M, M)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in (("ordered_cloud", ordered), ("multi_bev", multi), ("single_bev", single),
+                    ("sample_frames", (first + pick).astype(np.float64))):
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20, help="timed steps (a step = the whole path over the frames; 20 x 2.5 ms: the bench is mostly set-up and the CPU baseline)")
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (a step = the whole path over the frames; 20 x 2.5 ms: the bench is mostly set-up)")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--frames", type=int, default=1000, help="frames per GPU (BASELINE config: 1000)")
     ap.add_argument("--sensor", default=None)
@@ -53,20 +85,28 @@ def main() -> int:
                          "fails its checks; not the graded metric)")
     ap.add_argument("--sub-batch", type=int, default=int(os.environ.get("BEV_SUB_BATCH", "500")),
                     help="frames per sub-batch (= per fused launch: a sub-batch's walk beside the later stages of earlier ones; 500: two per "
-                         "1000-frame step; 125 / 250 / 334 / 1000 measured 2-3 % behind 500, profiles/r06_experiments.txt)")
+                         "1000-frame step; 125 / 250 / 334 / 1000 measured 2-3 %% behind 500, profiles/r06_experiments.txt)")
     ap.add_argument("--n-dup", type=int, default=int(os.environ.get("BEV_BENCH_NDUP", "5000")),
                     help="duplicates appended to every hdl64_sweep frame (BASELINE config 2: 5000; anything else is a "
                          "developer experiment and is named in config.workload)")
     ap.add_argument("--layout-hint", default="none", choices=["none", "structured", "firing"],
                     help="bev_set_layout_hint: the caller says how its clouds are laid out and k_probe does not look (verified by the "
                          "walk like any guess); named in config.workload")
-    ap.add_argument("--cpu-sample", type=int, default=400, help="frames timed on the CPU oracle (rank 0, N=1)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-profile", action="store_true", help="do not bracket kernels with HIP events")
+    ap.add_argument("--full", action="store_true",
+                    help="also the fenced median step, the per-kernel profile passes and roofline, the CPU baseline and the "
+                         "routes of the last sub-batch (a plain run does only the timed steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (ordered clouds, multi and single BEVs) for "
+                         "a fixed seeded sample of frames as DIR/<name>.npy, float32/float64, under 64 MB (rank 0's frames)")
+    ap.add_argument("--cpu-sample", type=int, default=400, help="frames timed on the CPU oracle (rank 0, N=1; --full)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-profile", action="store_true", help="--full without the passes that bracket kernels with HIP events")
     ap.add_argument("--no-build", action="store_true",
                     help="do not run __graft_entry__.build() first (profiling scripts build once, then run "
                          "`rocprofv3 ... -- python3 bench.py --no-build`: no child process under the profiler)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import numpy as np
     import torch  # before the HIP library: one HIP runtime per process (bev_amd.load_lib)
@@ -227,16 +267,6 @@ def main() -> int:
     elapsed = time.perf_counter() - t0
     local_elapsed = elapsed
     elapsed = shard.max_over_ranks(elapsed, world, device=dev, force_collective=use_dist)
-    # the same steps once more, each one fenced by itself: the median step next to the mean of the timed region
-    # (SURVEY.md 8(d) asks for the median; a fence per step costs the pipeline its overlap across steps)
-    per_step = []
-    for _ in range(args.steps):
-        ts = time.perf_counter()
-        step()
-        fence()
-        per_step.append(time.perf_counter() - ts)
-    per_step.sort()
-    median_step = per_step[len(per_step) // 2] if len(per_step) % 2 else 0.5 * (per_step[len(per_step) // 2 - 1] + per_step[len(per_step) // 2])
     total_frames = shard.sum_over_ranks(float(count * args.steps), world, device=dev, force_collective=use_dist)
     # what every rank measured by itself (its shard of the table, its own wall time of the timed region, its device): the
     # line shows that the collectives ran over `ranks_seen` ranks without anyone reading logs
@@ -244,12 +274,31 @@ def main() -> int:
     per_rank = shard.gather_per_rank([rank, local_rank, first, count, local_elapsed, count * args.steps / local_elapsed],
                                      world, device=dev, force_collective=use_dist)
 
+    if args.dump_outputs and rank == 0:
+        def read_frame(i):
+            return (d_ordered[i * S * 32:(i + 1) * S * 32].cpu().numpy().view(bev_amd.POINT_DTYPE),
+                    d_multi[i * L * M * M:(i + 1) * L * M * M].cpu().numpy(), d_single[i * M * M:(i + 1) * M * M].cpu().numpy())
+        dump_outputs(args.dump_outputs, first, count, S, L, M, read_frame)
+
+    # the same steps once more, each one fenced by itself: the median step next to the mean of the timed region
+    # (SURVEY.md 8(d) asks for the median; a fence per step costs the pipeline its overlap across steps)
+    median_step = None
+    if args.full:
+        per_step = []
+        for _ in range(args.steps):
+            ts = time.perf_counter()
+            step()
+            fence()
+            per_step.append(time.perf_counter() - ts)
+        per_step.sort()
+        median_step = per_step[len(per_step) // 2] if len(per_step) % 2 else 0.5 * (per_step[len(per_step) // 2 - 1] + per_step[len(per_step) // 2])
+
     # ---- profile passes (after the timed region, which carries no events): (1) the same steps again, still pipelined,
     # every launch bracketed by HIP events on its own stream: what each kernel costs UNDER OVERLAP, i.e. in the
     # configuration the headline number comes from; (2) the same steps with ONE lane, launches back to back: a
     # launch's duration is then its own, which is what the roofline of the dominant kernel is computed from.
     stats, stats_pipe = [], []
-    if not args.no_profile:
+    if args.full and not args.no_profile:
         ctx.profile_enable(True)
         ctx.profile_reset()
         for _ in range(args.steps):
@@ -267,7 +316,7 @@ def main() -> int:
         ctx.profile_enable(False)
 
     n_last = count - ((count - 1) // args.sub_batch) * args.sub_batch
-    routes = {str(k): int(v) for k, v in zip(*np.unique(ctx.frame_info(0, n_last)[:, 1], return_counts=True))}
+    routes = {str(k): int(v) for k, v in zip(*np.unique(ctx.frame_info(0, n_last)[:, 1], return_counts=True))} if args.full else None
     # ---- per-kernel HIP-event durations of the roofline pass (this rank)
     mean_pts = total_pts / count
     b_frame = bev_amd.algorithmic_bytes_per_frame(p, mean_pts)  # 32P + 32S + L*M*M + M*M
@@ -347,7 +396,7 @@ def main() -> int:
 
     # ---- CPU baseline: the oracle (a port of the reference algorithm), 1 thread, bounded sample
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         import oracle_lib as orc
 
         sp = orc.sensor_from_params(p)
@@ -428,12 +477,13 @@ def main() -> int:
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": elapsed / args.steps * 1e3,
-            "ms_per_step_median_fenced": median_step * 1e3,
+            "ms_per_step_median_fenced": median_step * 1e3 if median_step is not None else None,
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
             "dtype": "f32",
             "data": "synthetic",
+            "full": args.full,  # whether the fields below that need passes of their own (fenced median, roofline, kernels, cpu_baseline, routes) were measured
             "config": {"workload": f"{F} synthetic {args.workload} {args.sensor} clouds per GPU (mean {mean_pts:.0f} input pts, "
                                    f"{S} slots), single+multi BEV, device-resident" +
                                    (f" [developer run: {n_dup} appended duplicates instead of 5000]" if args.workload == "hdl64_sweep" and n_dup != 5000 else "") +

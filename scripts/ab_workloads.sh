@@ -6,7 +6,7 @@ R=$GRAFT_REPO_ROOT; cd $R
 A=$1; B=$2; shift 2
 python3 -c "import __graft_entry__ as g; g.build()" || exit 1
 for wl in "$@"; do for rep in 1 2 3; do for lib in $A $B; do
-BEV_AMD_LIB=$R/point-cloud-preprocessing-tools_amd/csrc/libbev_$lib.so timeout 300 python3 bench.py --no-build --steps 20 --warmup 5 --no-cpu --no-profile --workload $wl 2>/dev/null | tail -1 > /tmp/b.json || exit 1
+BEV_AMD_LIB=$R/point-cloud-preprocessing-tools_amd/csrc/libbev_$lib.so timeout 300 python3 bench.py --full --no-build --steps 20 --warmup 5 --no-cpu --no-profile --workload $wl 2>/dev/null | tail -1 > /tmp/b.json || exit 1
 python3 - $lib $wl <<'PY'
 import json, sys
 d = json.loads(open("/tmp/b.json").read())

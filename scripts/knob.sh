@@ -3,7 +3,7 @@
 R=$GRAFT_REPO_ROOT; cd $R
 for rep in 1 2 3; do
 for setting in "$@"; do
-  env $setting timeout -k 10 300 python3 bench.py --no-build --steps 8 --warmup 3 --no-cpu $(for kv in $setting; do case $kv in BENCH_ARGS=*) echo ${kv#BENCH_ARGS=} | tr , " ";; esac; done) 2>/dev/null | tail -1 > /tmp/knob.json || exit 1
+  env $setting timeout -k 10 300 python3 bench.py --full --no-build --steps 8 --warmup 3 --no-cpu $(for kv in $setting; do case $kv in BENCH_ARGS=*) echo ${kv#BENCH_ARGS=} | tr , " ";; esac; done) 2>/dev/null | tail -1 > /tmp/knob.json || exit 1
   python3 - "$setting" <<'PY'
 import json,sys
 d=json.loads(open("/tmp/knob.json").read()); F=d["config"]["frames_per_gpu"]

@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; cd $R
 TAG=${1:-pmc}; OUT=$R/gpurun_out/$TAG; mkdir -p $OUT
 for kv in $3; do export "$kv"; done
-BEV_LANES=1 timeout -k 10 300 rocprofv3 --pmc $2 --output-format csv -d $OUT/pmc -- python3 bench.py --no-build --steps 1 --warmup 1 --no-cpu --no-profile > $OUT/pmc.log 2>&1 || { tail -5 $OUT/pmc.log; exit 1; }
+BEV_LANES=1 timeout -k 10 300 rocprofv3 --pmc $2 --output-format csv -d $OUT/pmc -- python3 bench.py --full --no-build --steps 1 --warmup 1 --no-cpu --no-profile > $OUT/pmc.log 2>&1 || { tail -5 $OUT/pmc.log; exit 1; }
 python3 - $OUT <<'PY'
 import csv,glob,collections,sys
 agg=collections.defaultdict(lambda: collections.defaultdict(float))

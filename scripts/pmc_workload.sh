@@ -2,7 +2,7 @@
 export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; cd $R
 TAG=$1; WL=$2; F=$3; OUT=$R/gpurun_out/$TAG; rm -rf $OUT; mkdir -p $OUT
-BEV_LANES=1 timeout -k 10 300 rocprofv3 --pmc $4 --output-format csv -d $OUT/pmc -- python3 bench.py --no-build --steps 1 --warmup 1 --no-cpu --no-profile --workload $WL --frames $F > $OUT/pmc.log 2>&1 || { tail -5 $OUT/pmc.log; exit 1; }
+BEV_LANES=1 timeout -k 10 300 rocprofv3 --pmc $4 --output-format csv -d $OUT/pmc -- python3 bench.py --full --no-build --steps 1 --warmup 1 --no-cpu --no-profile --workload $WL --frames $F > $OUT/pmc.log 2>&1 || { tail -5 $OUT/pmc.log; exit 1; }
 python3 - $OUT $F <<'PY'
 import csv,glob,collections,sys
 agg=collections.defaultdict(lambda: collections.defaultdict(float))

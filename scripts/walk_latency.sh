@@ -3,7 +3,7 @@
 R=$GRAFT_REPO_ROOT; cd $R
 for kv in $1; do export "$kv"; done
 for F in 32 64 96 128 256; do
-  BEV_LANES=1 timeout -k 10 300 python3 bench.py --no-build --steps 10 --warmup 3 --no-cpu --frames $F --sub-batch $F 2>/dev/null | tail -1 > /tmp/wl.json || exit 1
+  BEV_LANES=1 timeout -k 10 300 python3 bench.py --full --no-build --steps 10 --warmup 3 --no-cpu --frames $F --sub-batch $F 2>/dev/null | tail -1 > /tmp/wl.json || exit 1
   python3 - $F <<'PY'
 import json,sys
 d=json.loads(open("/tmp/wl.json").read()); F=int(sys.argv[1])

@@ -1,14 +1,16 @@
 """CPU: SURVEY §8(f) row N1 — the label step (host/LabelStep.cpp) against the reference's OWN k-NN.
 
-oracle/_ref/libref_knn.so is built (oracle/Makefile, `make ref`) from the reference's include/nanoflann.hpp and
-include/KDTreeVectorOfVectorsAdaptor.h where they lie under /root/reference, and called like
-BatchMultiBevGen.cpp:534-550 / :594-613 call it.  The loops around the searches (selectMajorFrames :502-566,
-getKeyFrameLabel :575-636) are restated below in Python, float32 like the reference; the product implementation
-(exhaustive scan in nanoflann's distance evaluation order) must give the same major frames and the same labels,
-bit for bit.  The .so is prebuilt where /root/reference is absent; without it the tests are skipped."""
+The reference's k-NN (its include/nanoflann.hpp + include/KDTreeVectorOfVectorsAdaptor.h, called like
+BatchMultiBevGen.cpp:534-550 / :594-613) answered every query these tests make once; its answers are stored in
+tests/golden/ref_knn_calls.npz (tests/golden/make_ref_knn_calls.py, from oracle/_ref/libref_knn.so, which
+`make -C oracle ref` builds where the reference sources are at hand).  The loops around the searches (selectMajorFrames
+:502-566, getKeyFrameLabel :575-636) are restated below in Python, float32 like the reference; the product
+implementation (exhaustive scan in nanoflann's distance evaluation order) must give the same major frames and the same
+labels, bit for bit.  Where oracle/_ref/libref_knn.so exists, every stored answer is also checked against it."""
 import ctypes as C
+import hashlib
 import pathlib
-import subprocess
+import struct
 
 import numpy as np
 import pytest
@@ -17,14 +19,16 @@ import hostcheck_lib as hc
 
 ROOT = pathlib.Path(__file__).resolve().parents[1]
 REF_SO = ROOT / "oracle" / "_ref" / "libref_knn.so"
+CALLS = ROOT / "tests" / "golden" / "ref_knn_calls.npz"
 
 
-@pytest.fixture(scope="module")
-def ref_knn():
-    if pathlib.Path("/root/reference/include/nanoflann.hpp").exists():
-        subprocess.run(["make", "-C", str(ROOT / "oracle"), "ref"], check=True, capture_output=True)
-    if not REF_SO.exists():
-        pytest.skip("oracle/_ref/libref_knn.so not built (needs /root/reference)")
+def call_key(pts, q, k):
+    """What identifies one query: the searched points, the query point (always 3 floats) and k."""
+    return hashlib.sha1(pts.tobytes() + q.tobytes() + struct.pack("<Q", k)).digest()
+
+
+def live_knn():
+    """The reference's k-NN itself, through oracle/_ref/libref_knn.so."""
     lib = C.CDLL(str(REF_SO))
     lib.ref_knn.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
     lib.ref_knn.restype = C.c_int
@@ -36,6 +40,26 @@ def ref_knn():
         d2 = np.zeros(k, np.float32)
         found = lib.ref_knn(pts.ctypes.data, len(pts), q.ctypes.data, k, idx.ctypes.data, d2.ctypes.data)
         return idx.astype(np.int64), d2, found
+
+    return knn
+
+
+@pytest.fixture(scope="module")
+def ref_knn():
+    rec = dict(np.load(CALLS))
+    row = {bytes(key): i for i, key in enumerate(rec["key"])}
+    live = live_knn() if REF_SO.exists() else None
+
+    def knn(pts, q, k):
+        pts = np.ascontiguousarray(pts, np.float32)
+        q = np.ascontiguousarray(q, np.float32)
+        i = row.get(call_key(pts, q, k))
+        assert i is not None, f"a k-NN query that {CALLS.name} does not hold (tests/golden/make_ref_knn_calls.py records them)"
+        idx, d2, found = rec["idx"][i, :k].astype(np.int64), rec["d2"][i, :k].copy(), int(rec["found"][i])
+        if live is not None:
+            l_idx, l_d2, l_found = live(pts, q, k)
+            assert (l_idx.tolist(), l_d2.tobytes(), l_found) == (idx.tolist(), d2.tobytes(), found), "stored answer != libref_knn.so"
+        return idx, d2, found
 
     return knn
 
