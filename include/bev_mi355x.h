@@ -218,6 +218,46 @@ void bev_yaw_translate_matrix(float tx, float ty, float tz, float yaw_deg, float
 int bev_project_xyzi(bev_ctx_t *ctx, int kind, const float *xyzi, uint32_t n, bev_point_t *out);
 size_t bev_project_out_points(int kind, uint32_t n); /* 0 for an unknown kind */
 
+/* ---- registration front end ----------------------------------------------------------------------------------------
+ * What the reference's registration tools (top_part_registration, batch_top_part_registration, batch_whole_registration)
+ * do to every cloud before ICP.  The contract — restated from PCL / FLANN / Eigen's published sources, parity with the
+ * reference UNPINNED, the points the reference leaves open fixed — is DESIGN.md "Registration front end".  Layouts:
+ * PointXYZ = 4 floats (x y z pad), pcl::Normal = 8 floats (nx ny nz pad curvature pad pad pad), pcl::PointNormal = 12
+ * floats (x y z pad nx ny nz pad curvature pad pad pad); every pad the library writes is 0, every NaN it writes is
+ * 0x7fc00000.  Clouds of up to max(max_points, S) points (bev_create); each entry first launches whatever the BEV path
+ * has pending. */
+
+/* extractTopAndFlatten (TopPartRegistration.cpp:79-136 = BatchTopPartRegistration.cpp:90-147 =
+ * BatchWholeRegistration.cpp:90-147): label-0 and non-finite points are skipped; cell gx = round((x + 100) / 20), gy the
+ * same from y, 0 <= gx, gy < 10; a cell of >= 20 points emits its round(0.2f * n) highest points (equal z: lower index
+ * first) as (x, y, 0), cells in gx-major order.  out: capacity bev_regfront_max_out(n) PointXYZ. */
+int bev_top_part_flatten(bev_ctx_t *ctx, const bev_point_t *cloud, uint32_t n, float *out, uint32_t *n_out);
+/* pcl::VoxelGrid<pcl::PointXYZ> with one leaf size for x, y, z (BatchTopPartRegistration.cpp:342-343,405-409; PCL >= 1.10
+ * defaults): voxels in ascending index order, centroids summed in input order.  Non-finite points are dropped.  When the
+ * grid would have more than INT32_MAX voxels the output is the input.  out: capacity n PointXYZ. */
+int bev_voxel_grid_xyz(bev_ctx_t *ctx, const float *xyz, uint32_t n, float leaf, float *out, uint32_t *n_out);
+/* Normal2dEstimation::compute(PointCloud<Normal>) in radius mode with setViewPoint (src/Normal2dEstimation.cpp,
+ * src/PCA2D.cpp; addNormal, BatchTopPartRegistration.cpp:155-172, uses radius 2 and the viewpoint (0, 0, 0)).
+ * k_search != 0 (setKSearch) -> BEV_ERR_UNSUPPORTED.  viewpoint: 3 floats or NULL (origin; z is not used).  Every point
+ * is scanned for every query (O(n^2) work: meant for clouds up to ~10^5 points).  out: n pcl::Normal records. */
+int bev_normals_2d(bev_ctx_t *ctx, const float *xyz, uint32_t n, int k_search, float radius, const float *viewpoint,
+                   float *out);
+/* The three steps for a batch of clouds, device-resident: top part -> voxel grid (leaf) -> normals (radius, viewpoint)
+ * -> pcl::concatenateFields into PointNormal (addNormal, BatchTopPartRegistration.cpp:155-172).
+ * d_clouds   : h_offsets == NULL: the d_ordered output of bev_process_device_resident (n_frames * S points);
+ *              else packed clouds, frame f = [h_offsets[f], h_offsets[f+1]) (HOST array of n_frames + 1 offsets).
+ * d_out      : n_frames * out_stride PointNormal records (device); out_stride >= bev_regfront_max_out(largest cloud).
+ * d_counts   : n_frames uint32 (device): records of frame f.
+ * Asynchronous like bev_process_device_resident: bev_synchronize() before reading the results.  It starts behind every
+ * BEV call made before it (including their pending stages) and behind the caller's default-stream work; the next
+ * bev_process_device_resident starts behind it. */
+int bev_registration_front_device_resident(bev_ctx_t *ctx, int n_frames, const bev_point_t *d_clouds,
+                                           const uint64_t *h_offsets, float leaf, float radius, const float *viewpoint,
+                                           void *d_out, size_t out_stride, uint32_t *d_counts);
+/* Records the top part (and so the chain) can emit for a cloud of n points: sum of round(0.2f * n_cell) <= n / 5 + 51.
+ * Host only. */
+size_t bev_regfront_max_out(size_t n);
+
 /* ---- layout hint -------------------------------------------------------
  * What the caller knows about how its clouds are laid out, so that the library need not look (k_probe reads every 63rd
  * record of a frame to find out: 0.36 MB and 0.07 us of an HDL_64E frame).  Sticky per context; applies to frames of

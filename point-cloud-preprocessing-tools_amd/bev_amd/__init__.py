@@ -77,7 +77,12 @@ ABI_SYMBOLS = [
     "bev_float_bev", "bev_float_bev_size", "bev_transform_cloud", "bev_yaw_translate_matrix", "bev_project_xyzi", "bev_project_out_points", "bev_host_alloc", "bev_host_free",
     "bev_set_lanes", "bev_set_layout_hint", "bev_profile_enable", "bev_profile_reset", "bev_profile_get",
     "bev_debug_get_cell_avg", "bev_debug_get_frame_info", "bev_debug_get_code_overflow", "bev_debug_angle_predicate", "bev_abi_version",
+    "bev_top_part_flatten", "bev_voxel_grid_xyz", "bev_normals_2d", "bev_registration_front_device_resident",
+    "bev_regfront_max_out",
 ]
+
+# registration front end (include/bev_mi355x.h): pcl::PointXYZ, pcl::Normal, pcl::PointNormal as float rows
+XYZ_FLOATS, NORMAL_FLOATS, POINT_NORMAL_FLOATS = 4, 8, 12
 
 
 def load_lib() -> C.CDLL:
@@ -149,6 +154,14 @@ def load_lib() -> C.CDLL:
         lib.bev_debug_get_code_overflow.argtypes = [vp, i32, i32, vp]
     lib.bev_debug_angle_predicate.argtypes = [vp, vp, vp, vp, vp, sz]
     lib.bev_abi_version.restype = i32
+    if hasattr(lib, "bev_registration_front_device_resident"):  # (absent from older builds selected through BEV_AMD_LIB)
+        lib.bev_top_part_flatten.argtypes = [vp, vp, u32, vp, C.POINTER(u32)]
+        lib.bev_voxel_grid_xyz.argtypes = [vp, vp, u32, C.c_float, vp, C.POINTER(u32)]
+        lib.bev_normals_2d.argtypes = [vp, vp, u32, i32, C.c_float, vp, vp]
+        lib.bev_registration_front_device_resident.argtypes = [vp, i32, vp, C.POINTER(C.c_uint64), C.c_float, C.c_float,
+                                                               vp, vp, sz, vp]
+        lib.bev_regfront_max_out.argtypes = [sz]
+        lib.bev_regfront_max_out.restype = sz
     _lib = lib
     return lib
 
@@ -285,6 +298,72 @@ class BevContext:
                     "bev_project_xyzi")
         return out
 
+    # ---- registration front end (DESIGN.md "Registration front end") ------------------------------------------
+    def top_part_flatten(self, cloud):
+        """extractTopAndFlatten: (m, 4) float32 PointXYZ rows (x, y, 0, 0)."""
+        cloud = np.ascontiguousarray(cloud, dtype=POINT_DTYPE)
+        out = np.zeros((regfront_max_out(len(cloud)), XYZ_FLOATS), dtype=np.float32)
+        m = C.c_uint32(0)
+        self._check(self.lib.bev_top_part_flatten(self._h, _ptr(cloud) if len(cloud) else None, len(cloud), _ptr(out),
+                                                  C.byref(m)), "bev_top_part_flatten")
+        return out[: m.value].copy()
+
+    def voxel_grid(self, xyz, leaf=0.2):
+        """pcl::VoxelGrid<PointXYZ> with one leaf size: xyz is (n, 4) or (n, 3) float32; returns (v, 4) centroids."""
+        xyz = _xyz4(xyz)
+        out = np.zeros((max(len(xyz), 1), XYZ_FLOATS), dtype=np.float32)
+        m = C.c_uint32(0)
+        self._check(self.lib.bev_voxel_grid_xyz(self._h, _ptr(xyz) if len(xyz) else None, len(xyz), leaf, _ptr(out),
+                                                C.byref(m)), "bev_voxel_grid_xyz")
+        return out[: m.value].copy()
+
+    def normals_2d(self, xyz, radius=2.0, viewpoint=(0.0, 0.0, 0.0), k_search=0):
+        """Normal2dEstimation::compute(PointCloud<Normal>), radius mode: (n, 8) float32 pcl::Normal rows."""
+        xyz = _xyz4(xyz)
+        out = np.zeros((len(xyz), NORMAL_FLOATS), dtype=np.float32)
+        vp = np.asarray(viewpoint, dtype=np.float32).reshape(3)
+        self._check(self.lib.bev_normals_2d(self._h, _ptr(xyz) if len(xyz) else None, len(xyz), k_search, radius,
+                                            _ptr(vp), _ptr(out) if len(xyz) else None), "bev_normals_2d")
+        return out
+
+    def registration_front_device(self, n_frames, d_clouds, offsets, d_out, out_stride, d_counts, leaf=0.2, radius=2.0,
+                                  viewpoint=(0.0, 0.0, 0.0)):
+        """The chain on device pointers (bev_registration_front_device_resident); offsets None: d_clouds is the d_ordered
+        layout (n_frames * S points).  Asynchronous: synchronize() before reading d_out / d_counts."""
+        offs = None
+        if offsets is not None:
+            offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+            assert offsets.shape[0] == n_frames + 1
+            offs = offsets.ctypes.data_as(C.POINTER(C.c_uint64))
+        vp = np.asarray(viewpoint, dtype=np.float32).reshape(3)
+        self._check(self.lib.bev_registration_front_device_resident(
+            self._h, n_frames, C.c_void_p(d_clouds), offs, leaf, radius, _ptr(vp), C.c_void_p(d_out), out_stride,
+            C.c_void_p(d_counts)), "bev_registration_front_device_resident")
+
+    def registration_front(self, clouds, leaf=0.2, radius=2.0, viewpoint=(0.0, 0.0, 0.0)):
+        """The chain on host clouds (uploaded through torch): a list of (k, 12) float32 pcl::PointNormal arrays."""
+        import torch
+
+        clouds = [np.ascontiguousarray(c_, dtype=POINT_DTYPE) for c_ in clouds]
+        n = len(clouds)
+        if n == 0:
+            return []
+        offs = np.zeros(n + 1, dtype=np.uint64)
+        offs[1:] = np.cumsum([len(c_) for c_ in clouds])
+        stride = regfront_max_out(max(len(c_) for c_ in clouds))
+        dev = torch.device("cuda", torch.cuda.current_device())
+        packed = np.concatenate(clouds) if offs[-1] else np.zeros(1, dtype=POINT_DTYPE)
+        d_in = torch.from_numpy(packed.view(np.uint8).reshape(-1).copy()).to(dev)
+        d_out = torch.zeros(n * stride * POINT_NORMAL_FLOATS, dtype=torch.float32, device=dev)
+        d_cnt = torch.zeros(n, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize()
+        self.registration_front_device(n, d_in.data_ptr(), offs, d_out.data_ptr(), stride, d_cnt.data_ptr(), leaf, radius,
+                                       viewpoint)
+        self.synchronize()
+        out = d_out.cpu().numpy().reshape(n, stride, POINT_NORMAL_FLOATS)
+        cnt = d_cnt.cpu().numpy().astype(np.int64)
+        return [out[f, : cnt[f]].copy() for f in range(n)]
+
     def set_layout_hint(self, layout: int):
         """LAYOUT_UNKNOWN (the library looks), LAYOUT_STRUCTURED, LAYOUT_FIRING_ORDER: include/bev_mi355x.h"""
         self._check(self.lib.bev_set_layout_hint(self._h, layout), "bev_set_layout_hint")
@@ -343,6 +422,18 @@ class BevContext:
         self._check(self.lib.bev_debug_angle_predicate(self._h, _ptr(dx), _ptr(dy), _ptr(dz), _ptr(out), dx.shape[0]),
                     "bev_debug_angle_predicate")
         return out
+
+
+def regfront_max_out(n: int) -> int:
+    """Records the registration front end can emit for a cloud of n points (host only)."""
+    return int(load_lib().bev_regfront_max_out(n))
+
+
+def _xyz4(xyz) -> np.ndarray:
+    a = np.asarray(xyz, dtype=np.float32)
+    if a.ndim == 2 and a.shape[1] == 3:
+        a = np.concatenate([a, np.zeros((len(a), 1), np.float32)], axis=1)
+    return np.ascontiguousarray(a.reshape(-1, XYZ_FLOATS))
 
 
 def yaw_translate_matrix(tx: float, ty: float, tz: float, yaw_deg: float) -> np.ndarray:

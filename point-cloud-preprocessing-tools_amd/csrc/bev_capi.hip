@@ -6,6 +6,7 @@
  * HIP cannot give us a device, bev_create() fails.
  */
 #include <algorithm>
+#include <cmath>
 #include <condition_variable>
 #include <deque>
 #include <mutex>
@@ -189,6 +190,18 @@ struct bev_ctx {
     /* KITTI projection workspace, one allocation made on first use and grown on demand */
     void *kitti_buf = nullptr;
     size_t kitti_points = 0;
+
+    /* registration front end (bev_registration_front_device_resident & co.): one allocation on first use, max_batch frames
+     * of max(max_points, S) points; the offsets of packed clouds go up through a pinned array, reused once rf_offs_ev has
+     * passed */
+    void *rf_buf = nullptr;
+    RfWork rf{};
+    float *rf_nrm = nullptr; /* P pcl::Normal records: bev_normals_2d's output */
+    uint64_t *rf_h_offs = nullptr, *rf_d_offs = nullptr;
+    size_t rf_offs_cap = 0;
+    hipEvent_t rf_offs_ev = nullptr;
+    hipEvent_t rf_tail_ev = nullptr; /* recorded behind the last chain: the next BEV call's stage streams wait for it */
+    bool rf_tail_pending = false;
 
     /* profiling */
     bool prof_on = false;
@@ -513,6 +526,10 @@ int run_pipeline(bev_ctx *c, int n_frames, const bev_point_t *d_pts, const uint6
         HIPCK(c, hipEventRecord(c->fork_ev, c->stream));
         for (int q = 0; q < kMaxStageStreams; ++q) HIPCK(c, hipStreamWaitEvent(c->stage_st[q], c->fork_ev, 0));
     }
+    if (c->rf_tail_pending) { /* a registration front end still reading a cloud this call may overwrite */
+        for (int q = 0; q < kMaxStageStreams; ++q) HIPCK(c, hipStreamWaitEvent(c->stage_st[q], c->rf_tail_ev, 0));
+        c->rf_tail_pending = false;
+    }
     if (!fork && !identity) {
         /* device pointers from the caller: whatever it has queued on the default stream up to now — the upload or the fill of
          * these very buffers, typically — comes first (the library's streams are non-blocking: nothing else orders them behind
@@ -734,6 +751,56 @@ int ensure_staging(bev_ctx *c)
     return BEV_OK;
 }
 
+/* workspace of the registration front end (RfWork, bev_internal.h), allocated on first use; the BEV path's is untouched */
+int ensure_rf(bev_ctx *c)
+{
+    if (c->rf_buf) return BEV_OK;
+    const size_t B = (size_t)c->max_batch, P = std::max(c->max_points, (size_t)c->geo.S), Q = P;
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t sz[] = {B * P * 8, B * 2 * P * 8, B * kRfCells * 4, B * (kRfCells + 1) * 4, B * (kRfCells + 1) * 4,
+                         B * Q * 16, B * Q * 16, B * Q * 4, B * (Q + 1) * 4, B * sizeof(RfFrameMeta), P * 32};
+    size_t total = 0;
+    for (size_t b : sz) total += al(b);
+    HIPCK(c, hipMalloc(&c->rf_buf, total));
+    char *p = static_cast<char *>(c->rf_buf);
+    void **dst[] = {(void **)&c->rf.keys, (void **)&c->rf.scr, (void **)&c->rf.cell_cnt, (void **)&c->rf.cell_off,
+                    (void **)&c->rf.out_off, (void **)&c->rf.flat, (void **)&c->rf.vpts, (void **)&c->rf.vidx,
+                    (void **)&c->rf.vstart, (void **)&c->rf.meta, (void **)&c->rf_nrm};
+    for (size_t i = 0; i < sizeof(sz) / sizeof(sz[0]); ++i) {
+        *dst[i] = p;
+        p += al(sz[i]);
+    }
+    c->rf.P = P;
+    c->rf.Q = Q;
+    HIPCK(c, hipEventCreateWithFlags(&c->rf_offs_ev, hipEventDisableTiming));
+    HIPCK(c, hipEventCreateWithFlags(&c->rf_tail_ev, hipEventDisableTiming));
+    return BEV_OK;
+}
+
+/* the chain on nf <= max_batch frames of the workspace: top part -> voxel grid -> normals (PointNormal at out) */
+int rf_chain(bev_ctx *c, const RfIn &in, int nf, float leaf, float radius, const float vp[2], uint32_t n_max, float *out,
+             size_t out_stride, uint32_t *counts)
+{
+    {
+        ProfScope ps(c, K_RF_CELLS, nf);
+        launch_rf_top(in, c->rf, nf, c->stream, 0);
+    }
+    {
+        ProfScope ps(c, K_RF_TOP, nf);
+        launch_rf_top(in, c->rf, nf, c->stream, 1);
+    }
+    {
+        ProfScope ps(c, K_RF_VOXEL, nf);
+        launch_rf_voxel(c->rf, nf, leaf, counts, c->stream);
+    }
+    {
+        ProfScope ps(c, K_RF_NORMALS, nf);
+        launch_rf_normals(c->rf, nf, bev_regfront_max_out(n_max), radius, leaf, vp, true, out, out_stride, c->stream);
+    }
+    HIPCK(c, hipGetLastError());
+    return BEV_OK;
+}
+
 } // namespace
 
 /* ======================================================================== */
@@ -940,13 +1007,16 @@ void bev_destroy(bev_ctx_t *c)
     if (c->dl_stream) (void)hipStreamDestroy(c->dl_stream);
     for (auto e : c->out_ready)
         if (e) (void)hipEventDestroy(e);
-    void *dev[] = {c->st_in, c->st_ordered, c->st_multi, c->st_single, c->st_gm, c->kitti_buf, c->codes, c->ctx_tab};
+    void *dev[] = {c->st_in, c->st_ordered, c->st_multi, c->st_single, c->st_gm, c->kitti_buf, c->codes, c->ctx_tab, c->rf_buf, c->rf_d_offs};
     for (void *p : dev)
         if (p) (void)hipFree(p);
     for (int k = 0; k < kDescRing; ++k) {
         if (c->h_desc[k]) (void)hipHostFree(c->h_desc[k]);
         if (c->desc_done[k]) (void)hipEventDestroy(c->desc_done[k]);
     }
+    if (c->rf_h_offs) (void)hipHostFree(c->rf_h_offs);
+    if (c->rf_offs_ev) (void)hipEventDestroy(c->rf_offs_ev);
+    if (c->rf_tail_ev) (void)hipEventDestroy(c->rf_tail_ev);
     for (auto &s : c->prof_pool) {
         if (s.a) (void)hipEventDestroy(s.a);
         if (s.b) (void)hipEventDestroy(s.b);
@@ -1324,6 +1394,157 @@ void bev_yaw_translate_matrix(float tx, float ty, float tz, float yaw_deg, float
     m[4] = s;    m[5] = c;        m[6] = 0.0f;  m[7] = ty;
     m[8] = 0.0f; m[9] = 0.0f;     m[10] = one_minus_c + c; m[11] = tz;
 }
+
+/* ---- registration front end ------------------------------------------------------------------------------------------ */
+size_t bev_regfront_max_out(size_t n) { return n / 5 + 51; }
+
+#define RF_PROLOGUE(c)                                                                                                   \
+    do {                                                                                                                 \
+        HIPCK(c, hipSetDevice(c->device));                                                                               \
+        const int rc_ = flush_pending(c); /* (joins both stage streams into the context's stream) */                    \
+        if (rc_ != BEV_OK) return rc_;                                                                                   \
+        const int rc2_ = ensure_rf(c);                                                                                   \
+        if (rc2_ != BEV_OK) return rc2_;                                                                                 \
+    } while (0)
+
+static bool rf_positive(float v) { return std::isfinite(v) && v > 0.0f; }
+
+int bev_top_part_flatten(bev_ctx_t *c, const bev_point_t *cloud, uint32_t n, float *out, uint32_t *n_out)
+{
+    if (!c || !n_out || (n && (!cloud || !out))) return BEV_ERR_INVALID_ARG;
+    if ((size_t)n > std::max(c->max_points, (size_t)c->geo.S)) return BEV_ERR_TOO_LARGE;
+    *n_out = 0;
+    RF_PROLOGUE(c);
+    if (n == 0) return BEV_OK;
+    int rc = ensure_staging(c);
+    if (rc != BEV_OK) return rc;
+    HIPCK(c, hipMemcpyAsync(c->st_in, cloud, (size_t)n * sizeof(bev_point_t), hipMemcpyHostToDevice, c->stream));
+    RfIn in{c->st_in, nullptr, n, n};
+    {
+        ProfScope ps(c, K_RF_CELLS, 1);
+        launch_rf_top(in, c->rf, 1, c->stream, 0);
+    }
+    {
+        ProfScope ps(c, K_RF_TOP, 1);
+        launch_rf_top(in, c->rf, 1, c->stream, 1);
+    }
+    HIPCK(c, hipGetLastError());
+    RfFrameMeta meta{};
+    HIPCK(c, hipMemcpyAsync(&meta, c->rf.meta, sizeof(meta), hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    if (meta.m) HIPCK(c, hipMemcpy(out, c->rf.flat, (size_t)meta.m * 16, hipMemcpyDeviceToHost));
+    *n_out = meta.m;
+    return BEV_OK;
+}
+
+int bev_voxel_grid_xyz(bev_ctx_t *c, const float *xyz, uint32_t n, float leaf, float *out, uint32_t *n_out)
+{
+    if (!c || !n_out || (n && (!xyz || !out)) || !rf_positive(leaf)) return BEV_ERR_INVALID_ARG;
+    if ((size_t)n > std::max(c->max_points, (size_t)c->geo.S)) return BEV_ERR_TOO_LARGE;
+    *n_out = 0;
+    RF_PROLOGUE(c);
+    if (n == 0) return BEV_OK;
+    RfFrameMeta meta{};
+    meta.m = n;
+    HIPCK(c, hipMemcpyAsync(c->rf.flat, xyz, (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, hipMemcpyAsync(c->rf.meta, &meta, sizeof(meta), hipMemcpyHostToDevice, c->stream));
+    {
+        ProfScope ps(c, K_RF_VOXEL, 1);
+        launch_rf_voxel(c->rf, 1, leaf, nullptr, c->stream);
+    }
+    HIPCK(c, hipGetLastError());
+    HIPCK(c, hipMemcpyAsync(&meta, c->rf.meta, sizeof(meta), hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    if (meta.nv) HIPCK(c, hipMemcpy(out, c->rf.vpts, (size_t)meta.nv * 16, hipMemcpyDeviceToHost));
+    *n_out = meta.nv;
+    return BEV_OK;
+}
+
+int bev_normals_2d(bev_ctx_t *c, const float *xyz, uint32_t n, int k_search, float radius, const float *viewpoint,
+                   float *out)
+{
+    if (!c || (n && (!xyz || !out))) return BEV_ERR_INVALID_ARG;
+    if (k_search != 0) return BEV_ERR_UNSUPPORTED;
+    if (!rf_positive(radius)) return BEV_ERR_INVALID_ARG;
+    if ((size_t)n > std::max(c->max_points, (size_t)c->geo.S)) return BEV_ERR_TOO_LARGE;
+    RF_PROLOGUE(c);
+    if (n == 0) return BEV_OK;
+    const float vp[2] = {viewpoint ? viewpoint[0] : 0.0f, viewpoint ? viewpoint[1] : 0.0f};
+    RfFrameMeta meta{};
+    meta.m = meta.nv = n;
+    meta.windowed = 0; /* any order: every point is scanned */
+    HIPCK(c, hipMemcpyAsync(c->rf.vpts, xyz, (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, hipMemcpyAsync(c->rf.meta, &meta, sizeof(meta), hipMemcpyHostToDevice, c->stream));
+    {
+        ProfScope ps(c, K_RF_NORMALS, 1);
+        launch_rf_normals(c->rf, 1, n, radius, 0.0f, vp, false, c->rf_nrm, 0, c->stream);
+    }
+    HIPCK(c, hipGetLastError());
+    HIPCK(c, hipMemcpyAsync(out, c->rf_nrm, (size_t)n * 32, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    return BEV_OK;
+}
+
+int bev_registration_front_device_resident(bev_ctx_t *c, int n_frames, const bev_point_t *d_clouds,
+                                           const uint64_t *h_offsets, float leaf, float radius, const float *viewpoint,
+                                           void *d_out, size_t out_stride, uint32_t *d_counts)
+{
+    if (!c || n_frames < 0 || !rf_positive(leaf) || !rf_positive(radius)) return BEV_ERR_INVALID_ARG;
+    if (n_frames > 0 && (!d_clouds || !d_out || !d_counts)) return BEV_ERR_INVALID_ARG;
+    const size_t P = std::max(c->max_points, (size_t)c->geo.S);
+    uint32_t n_max = (uint32_t)c->geo.S;
+    if (h_offsets) {
+        n_max = 0;
+        for (int f = 0; f < n_frames; ++f) {
+            if (h_offsets[f + 1] < h_offsets[f] || h_offsets[f + 1] - h_offsets[f] > P) return BEV_ERR_TOO_LARGE;
+            n_max = std::max(n_max, (uint32_t)(h_offsets[f + 1] - h_offsets[f]));
+        }
+    }
+    if (n_frames > 0 && out_stride < bev_regfront_max_out(n_max)) return BEV_ERR_INVALID_ARG;
+    RF_PROLOGUE(c);
+    if (n_frames == 0) return BEV_OK;
+    /* the caller's default-stream work (the upload of packed clouds, typically) comes first */
+    HIPCK(c, hipEventRecord(c->null_ev, nullptr));
+    HIPCK(c, hipStreamWaitEvent(c->stream, c->null_ev, 0));
+    if (h_offsets) {
+        HIPCK(c, hipEventSynchronize(c->rf_offs_ev)); /* the last call's offsets have gone up */
+        if (c->rf_offs_cap < (size_t)n_frames + 1) {
+            HIPCK(c, hipStreamSynchronize(c->stream)); /* (kernels of the last call may still read rf_d_offs) */
+            if (c->rf_h_offs) HIPCK(c, hipHostFree(c->rf_h_offs));
+            if (c->rf_d_offs) HIPCK(c, hipFree(c->rf_d_offs));
+            c->rf_h_offs = nullptr;
+            c->rf_d_offs = nullptr;
+            c->rf_offs_cap = 0;
+            const size_t cap = std::max((size_t)n_frames + 1, (size_t)1024);
+            HIPCK(c, hipHostMalloc((void **)&c->rf_h_offs, cap * 8, hipHostMallocDefault));
+            HIPCK(c, hipMalloc((void **)&c->rf_d_offs, cap * 8));
+            c->rf_offs_cap = cap;
+        }
+        std::memcpy(c->rf_h_offs, h_offsets, ((size_t)n_frames + 1) * 8);
+        HIPCK(c, hipMemcpyAsync(c->rf_d_offs, c->rf_h_offs, ((size_t)n_frames + 1) * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCK(c, hipEventRecord(c->rf_offs_ev, c->stream));
+    }
+    const float vp[2] = {viewpoint ? viewpoint[0] : 0.0f, viewpoint ? viewpoint[1] : 0.0f};
+    for (int f0 = 0; f0 < n_frames; f0 += c->max_batch) {
+        const int nf = std::min(c->max_batch, n_frames - f0);
+        RfIn in{};
+        if (h_offsets) {
+            in.pts = d_clouds;
+            in.offs = c->rf_d_offs + f0;
+        } else {
+            in.pts = d_clouds + (size_t)f0 * c->geo.S;
+            in.stride = (size_t)c->geo.S;
+            in.n_uniform = (uint32_t)c->geo.S;
+        }
+        int rc = rf_chain(c, in, nf, leaf, radius, vp, n_max, static_cast<float *>(d_out) + (size_t)f0 * out_stride * 12,
+                          out_stride, d_counts + f0);
+        if (rc != BEV_OK) return rc;
+    }
+    HIPCK(c, hipEventRecord(c->rf_tail_ev, c->stream));
+    c->rf_tail_pending = true;
+    return BEV_OK;
+}
+#undef RF_PROLOGUE
 
 int bev_set_layout_hint(bev_ctx_t *c, int layout)
 {

@@ -205,6 +205,10 @@ enum KernelId {
     K_WALK_COLMAJOR_GEN, /* ... any start azimuth, direction, staggered beams, no-return records (kFrameColMajorGen) */
     K_VERDICT,
     K_STAGE, /* the fused launch: a sub-batch's walk beside the later stages of the sub-batches before it (k_stage) */
+    K_RF_CELLS,   /* registration front end (bev_regfront.h): cells of the top-part flatten */
+    K_RF_TOP,     /* ... each cell's highest points */
+    K_RF_VOXEL,   /* ... voxel grid */
+    K_RF_NORMALS, /* ... 2-D normals */
     K_COUNT
 };
 const char *kernel_name(int id);
@@ -270,6 +274,45 @@ struct KittiWork {
 };
 void launch_project_kitti(const float *xyzi, uint32_t n, const KittiWork &w, bev_point_t *out, hipStream_t st);
 void launch_angle_debug(const float *dx, const float *dy, const float *dz, uint8_t *out, size_t n, hipStream_t st);
+/* ---- registration front end (bev_regfront.h; DESIGN.md "Registration front end") ---- */
+constexpr int kRfThreads = 256;
+constexpr int kRfGrid = 10;                  /* NUM_GRID_X / NUM_GRID_Y of extractTopAndFlatten (TopPartRegistration.cpp:83-84) */
+constexpr int kRfCells = kRfGrid * kRfGrid;
+constexpr int kRfMinCellPoints = 20;         /* MIN_GRID_POINTS_SIZE (:90) */
+constexpr int kRfLdsKeys = 8192;             /* keys a workgroup sorts in LDS (64 KiB); more: in its global scratch region */
+struct RfFrameMeta {
+    uint32_t m;        /* top-part points of the frame (the voxel stage's input count) */
+    uint32_t nv;       /* voxels (the normal stage's point count) */
+    uint32_t windowed; /* the voxels are sorted by index i + j * div_x: neighbours lie in a contiguous window of rows */
+    uint32_t div_x, div_y;
+    uint32_t _pad[3];
+};
+/* per frame: P = max(max_points, S) input points, Q = P points between the stages */
+struct RfWork {
+    uint64_t *keys;      /* [nf][P]        top-part sort keys, bucketed by cell */
+    uint64_t *scr;       /* [nf][2P]       global sort scratch (cells / voxel sorts too large for LDS) */
+    uint32_t *cell_cnt;  /* [nf][100] */
+    uint32_t *cell_off;  /* [nf][101]      bucket offsets */
+    uint32_t *out_off;   /* [nf][101]      output offsets of the cells' top points */
+    float4 *flat;        /* [nf][Q]        flattened top points (PointXYZ, pad 0) */
+    float4 *vpts;        /* [nf][Q]        voxel centroids */
+    uint32_t *vidx;      /* [nf][Q]        voxel index of each centroid */
+    uint32_t *vstart;    /* [nf][Q + 1]    first sorted key of each voxel */
+    RfFrameMeta *meta;   /* [nf] */
+    size_t P, Q;
+};
+struct RfIn {
+    const bev_point_t *pts;
+    const uint64_t *offs; /* [nf + 1] element offsets (device), or nullptr: frame f = pts + f * stride, n_uniform points */
+    size_t stride;
+    uint32_t n_uniform;
+};
+/* phase 0: k_rf_cells, 1: k_rf_top */
+void launch_rf_top(const RfIn &in, const RfWork &w, int nf, hipStream_t st, int phase);
+void launch_rf_voxel(const RfWork &w, int nf, float leaf, uint32_t *counts, hipStream_t st);
+void launch_rf_normals(const RfWork &w, int nf, uint32_t max_points, float radius, float leaf, const float vp[2],
+                       bool point_normal, float *out, size_t out_stride, hipStream_t st);
+
 /* opt in to > 64 KiB of dynamic LDS for the kernels that need it */
 hipError_t configure_kernels(const Geometry &g);
 size_t cell_sums_lds_bytes();

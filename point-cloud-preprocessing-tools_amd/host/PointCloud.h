@@ -28,6 +28,21 @@ struct alignas(16) PointXYZIRCT {
 };
 static_assert(sizeof(PointXYZIRCT) == sizeof(bev_point_t), "PointXYZIRCT must match bev_point_t");
 
+/* the registration front end's types (Registration.h), PCL's layouts: every pad is written as 0 by the library */
+struct alignas(16) PointXYZ {
+    float x, y, z, _pad;
+};
+struct alignas(16) Normal {
+    float normal_x, normal_y, normal_z, _pad0;
+    float curvature, _pad1[3];
+};
+struct alignas(16) PointNormal {
+    float x, y, z, _pad0;
+    float normal_x, normal_y, normal_z, _pad1;
+    float curvature, _pad2[3];
+};
+static_assert(sizeof(PointXYZ) == 16 && sizeof(Normal) == 32 && sizeof(PointNormal) == 48, "PCL layouts");
+
 template <class PointT>
 class PointCloud {
 public:
