@@ -258,6 +258,69 @@ int bev_registration_front_device_resident(bev_ctx_t *ctx, int n_frames, const b
  * Host only. */
 size_t bev_regfront_max_out(size_t n);
 
+/* ---- coarse point-to-plane ICP ---------------------------------------------------------------------------------------
+ * pcl::IterativeClosestPointWithNormals<PointNormal, PointNormal> as the registration tools' performCoarseIcp runs it
+ * (BatchTopPartRegistration.cpp:192-221; the tool's two yaw guesses and its choice, :415-466).  The contract — restated
+ * from PCL's published sources, parity with the reference UNPINNED, exact 1-NN with the lowest index on ties, every sum
+ * in a fixed order — is DESIGN.md §6c.  Clouds are pcl::PointNormal records (12 floats, as above); source normals are
+ * never read.  Coarse stage only: the fine stage (VoxelGrid + point-to-point ICP) is not built. */
+typedef struct {
+    double max_correspondence_distance; /* D: a correspondence needs (double)dist <= D * D */
+    double transformation_epsilon;
+    double euclidean_fitness_epsilon;
+    int32_t max_iterations;             /* 1 ... 1000 */
+    int32_t _pad;                       /* 0 */
+} bev_icp_params_t;
+/* PCL's defaults plus the tool's two settings: D = 10, 10 iterations, transformation_epsilon 0,
+ * euclidean_fitness_epsilon -DBL_MAX.  Host only. */
+bev_icp_params_t bev_icp_coarse_defaults(void);
+
+enum {
+    BEV_ICP_NOT_CONVERGED = 0,
+    BEV_ICP_ITERATIONS = 1,
+    BEV_ICP_TRANSFORM = 2,
+    BEV_ICP_ABS_MSE = 3,
+    BEV_ICP_REL_MSE = 4,
+    BEV_ICP_NO_CORRESPONDENCES = 5 /* fewer than 3 correspondences: converged 0 */
+};
+typedef struct {
+    float T[16];        /* getFinalTransformation(), row-major; a NaN entry is 0x7fc00000 */
+    double fitness;     /* getFitnessScore(): DBL_MAX when no source point has a finite nearest distance */
+    int32_t converged;  /* hasConverged() */
+    int32_t iterations;
+    int32_t state;      /* BEV_ICP_* (DefaultConvergenceCriteria's enum) */
+    int32_t _pad;       /* 0 */
+} bev_icp_result_t;
+
+/* the reference's MatchResult (BatchTopPartRegistration.cpp:83-88): query_idx is the source frame, match_idx the target */
+typedef struct {
+    int32_t query_idx;
+    int32_t match_idx;
+    float angle_guess; /* degrees */
+} bev_match_t;
+
+/* One problem on host clouds (synchronous).  guess16: row-major 4 x 4 initial guess (NULL: identity).  params NULL: the
+ * coarse defaults.  Invalid parameters (max_iterations outside 1 ... 1000, D <= 0 or non-finite) -> BEV_ERR_INVALID_ARG. */
+int bev_icp_point_to_plane(bev_ctx_t *ctx, const float *src, uint32_t n_src, const float *tgt, uint32_t n_tgt,
+                           const float *guess16, const bev_icp_params_t *params, bev_icp_result_t *result);
+/* The tool's coarse loop for a list of matches, device-resident: for match m, ICP of frame query_idx onto frame match_idx
+ * from the guesses theta and theta + 180 (yaw about z, theta = angle_guess), and the better of the two.
+ * d_pn, stride, d_counts : bev_registration_front_device_resident's output (n_frames * stride PointNormal records,
+ *                          n_frames uint32 counts; a count above stride is read as stride)
+ * h_matches              : n_matches HOST records; every index in 0 ... n_frames - 1
+ * d_results              : 2 * n_matches results (device): [2m] guess theta, [2m + 1] guess theta + 180
+ * d_best                 : n_matches int32 (device): 0 iff fitness[2m] < fitness[2m + 1], else 1 (ties, NaN)
+ * Asynchronous like bev_process_device_resident: bev_synchronize() before reading the results.  It starts behind every
+ * call made on the context before it and behind the caller's default-stream work; the next BEV call starts behind it.
+ * Workspace, allocated on first use (grown when a call needs more) and freed by bev_destroy:
+ *   U * (32 + 4 * 4097 + 16 * stride) + min(2 * n_matches, 1024) * 16 * stride + 80 * 2 * n_matches + 4 * U bytes,
+ * U the number of distinct target frames; the problems run in launches of 1024 (the results do not depend on it).
+ * Nothing is launched when an argument is invalid (BEV_ERR_INVALID_ARG). */
+int bev_coarse_registration_device_resident(bev_ctx_t *ctx, int n_frames, const void *d_pn, size_t stride,
+                                            const uint32_t *d_counts, int n_matches, const bev_match_t *h_matches,
+                                            const bev_icp_params_t *params, bev_icp_result_t *d_results,
+                                            int32_t *d_best);
+
 /* ---- layout hint -------------------------------------------------------
  * What the caller knows about how its clouds are laid out, so that the library need not look (k_probe reads every 63rd
  * record of a frame to find out: 0.36 MB and 0.07 us of an HDL_64E frame).  Sticky per context; applies to frames of

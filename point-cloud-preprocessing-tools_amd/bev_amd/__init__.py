@@ -79,10 +79,29 @@ ABI_SYMBOLS = [
     "bev_debug_get_cell_avg", "bev_debug_get_frame_info", "bev_debug_get_code_overflow", "bev_debug_angle_predicate", "bev_abi_version",
     "bev_top_part_flatten", "bev_voxel_grid_xyz", "bev_normals_2d", "bev_registration_front_device_resident",
     "bev_regfront_max_out",
+    "bev_icp_coarse_defaults", "bev_icp_point_to_plane", "bev_coarse_registration_device_resident",
 ]
 
 # registration front end (include/bev_mi355x.h): pcl::PointXYZ, pcl::Normal, pcl::PointNormal as float rows
 XYZ_FLOATS, NORMAL_FLOATS, POINT_NORMAL_FLOATS = 4, 8, 12
+
+# coarse ICP (include/bev_mi355x.h): bev_icp_result_t, bev_match_t and the convergence states
+ICP_RESULT_DTYPE = np.dtype([("T", "<f4", (16,)), ("fitness", "<f8"), ("converged", "<i4"), ("iterations", "<i4"),
+                             ("state", "<i4"), ("_pad", "<i4")])
+MATCH_DTYPE = np.dtype([("query_idx", "<i4"), ("match_idx", "<i4"), ("angle_guess", "<f4")])
+ICP_NOT_CONVERGED, ICP_ITERATIONS, ICP_TRANSFORM, ICP_ABS_MSE, ICP_REL_MSE, ICP_NO_CORRESPONDENCES = range(6)
+
+
+class IcpParams(C.Structure):
+    """bev_icp_params_t"""
+    _fields_ = [("max_correspondence_distance", C.c_double), ("transformation_epsilon", C.c_double),
+                ("euclidean_fitness_epsilon", C.c_double), ("max_iterations", C.c_int32), ("_pad", C.c_int32)]
+
+
+def icp_params(max_correspondence_distance=10.0, max_iterations=10, transformation_epsilon=0.0,
+               euclidean_fitness_epsilon=-1.7976931348623157e308) -> IcpParams:
+    """The coarse defaults of the registration tools (bev_icp_coarse_defaults), any of them overridden."""
+    return IcpParams(max_correspondence_distance, transformation_epsilon, euclidean_fitness_epsilon, max_iterations, 0)
 
 
 def load_lib() -> C.CDLL:
@@ -162,6 +181,11 @@ def load_lib() -> C.CDLL:
                                                                vp, vp, sz, vp]
         lib.bev_regfront_max_out.argtypes = [sz]
         lib.bev_regfront_max_out.restype = sz
+    if hasattr(lib, "bev_coarse_registration_device_resident"):
+        lib.bev_icp_coarse_defaults.argtypes = []
+        lib.bev_icp_coarse_defaults.restype = IcpParams
+        lib.bev_icp_point_to_plane.argtypes = [vp, vp, u32, vp, u32, vp, C.POINTER(IcpParams), vp]
+        lib.bev_coarse_registration_device_resident.argtypes = [vp, i32, vp, sz, vp, i32, vp, C.POINTER(IcpParams), vp, vp]
     _lib = lib
     return lib
 
@@ -364,6 +388,63 @@ class BevContext:
         cnt = d_cnt.cpu().numpy().astype(np.int64)
         return [out[f, : cnt[f]].copy() for f in range(n)]
 
+    # ---- coarse point-to-plane ICP ---------------------------------------------------------------
+    def icp_point_to_plane(self, src, tgt, guess=None, params: IcpParams | None = None):
+        """One problem: src / tgt are (n, 12) float32 pcl::PointNormal rows, guess a 4 x 4 (None: identity).  Returns one
+        ICP_RESULT_DTYPE record."""
+        src = _pn12(src)
+        tgt = _pn12(tgt)
+        g = None if guess is None else np.ascontiguousarray(np.asarray(guess, dtype=np.float32).reshape(16))
+        prm = params if params is not None else icp_params()
+        out = np.zeros(1, dtype=ICP_RESULT_DTYPE)
+        self._check(self.lib.bev_icp_point_to_plane(self._h, _ptr(src) if len(src) else None, len(src),
+                                                    _ptr(tgt) if len(tgt) else None, len(tgt),
+                                                    _ptr(g) if g is not None else None, C.byref(prm), _ptr(out)),
+                    "bev_icp_point_to_plane")
+        return out[0]
+
+    def coarse_registration_device(self, n_frames, d_pn, stride, d_counts, matches, d_results, d_best,
+                                   params: IcpParams | None = None):
+        """bev_coarse_registration_device_resident on device pointers; matches: MATCH_DTYPE records (host).
+        Asynchronous: synchronize() before reading d_results (2 ICP_RESULT_DTYPE per match) and d_best (int32)."""
+        m = np.ascontiguousarray(matches, dtype=MATCH_DTYPE)
+        prm = params if params is not None else icp_params()
+        self._check(self.lib.bev_coarse_registration_device_resident(
+            self._h, n_frames, C.c_void_p(d_pn), stride, C.c_void_p(d_counts), len(m), _ptr(m) if len(m) else None,
+            C.byref(prm), C.c_void_p(d_results), C.c_void_p(d_best)), "bev_coarse_registration_device_resident")
+
+    def coarse_registration(self, pn_clouds, matches, params: IcpParams | None = None):
+        """The tool's coarse loop on host clouds (uploaded through torch): pn_clouds is a list of (k, 12) float32
+        PointNormal arrays, matches MATCH_DTYPE records or (query_idx, match_idx, angle_guess) tuples.  Returns
+        (results (n_matches, 2) ICP_RESULT_DTYPE, best (n_matches,) int32)."""
+        import torch
+
+        m = np.array([tuple(r) for r in matches], dtype=MATCH_DTYPE) if not isinstance(matches, np.ndarray) else \
+            np.ascontiguousarray(matches, dtype=MATCH_DTYPE)
+        n = len(m)
+        res = np.zeros((n, 2), dtype=ICP_RESULT_DTYPE)
+        best = np.zeros(n, dtype=np.int32)
+        if n == 0:
+            return res, best
+        clouds = [_pn12(c_) for c_ in pn_clouds]
+        F = len(clouds)
+        stride = max([len(c_) for c_ in clouds] + [1])
+        packed = np.zeros((F, stride, POINT_NORMAL_FLOATS), dtype=np.float32)
+        for f, c_ in enumerate(clouds):
+            packed[f, : len(c_)] = c_
+        dev = torch.device("cuda", torch.cuda.current_device())
+        d_pn = torch.from_numpy(packed.reshape(-1)).to(dev)
+        d_cnt = torch.from_numpy(np.array([len(c_) for c_ in clouds], dtype=np.int32)).to(dev)
+        d_res = torch.zeros(n * 2 * ICP_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        d_best = torch.zeros(n, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize()
+        self.coarse_registration_device(F, d_pn.data_ptr(), stride, d_cnt.data_ptr(), m, d_res.data_ptr(),
+                                        d_best.data_ptr(), params)
+        self.synchronize()
+        res[:] = d_res.cpu().numpy().view(ICP_RESULT_DTYPE).reshape(n, 2)
+        best[:] = d_best.cpu().numpy()
+        return res, best
+
     def set_layout_hint(self, layout: int):
         """LAYOUT_UNKNOWN (the library looks), LAYOUT_STRUCTURED, LAYOUT_FIRING_ORDER: include/bev_mi355x.h"""
         self._check(self.lib.bev_set_layout_hint(self._h, layout), "bev_set_layout_hint")
@@ -427,6 +508,15 @@ class BevContext:
 def regfront_max_out(n: int) -> int:
     """Records the registration front end can emit for a cloud of n points (host only)."""
     return int(load_lib().bev_regfront_max_out(n))
+
+
+def _pn12(a) -> np.ndarray:
+    return np.ascontiguousarray(np.asarray(a, dtype=np.float32).reshape(-1, POINT_NORMAL_FLOATS))
+
+
+def icp_coarse_defaults() -> IcpParams:
+    """bev_icp_coarse_defaults(): D = 10, 10 iterations, transformation_epsilon 0, euclidean_fitness_epsilon -DBL_MAX."""
+    return load_lib().bev_icp_coarse_defaults()
 
 
 def _xyz4(xyz) -> np.ndarray:

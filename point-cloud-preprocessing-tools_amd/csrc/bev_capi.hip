@@ -6,6 +6,7 @@
  * HIP cannot give us a device, bev_create() fails.
  */
 #include <algorithm>
+#include <cfloat>
 #include <cmath>
 #include <condition_variable>
 #include <deque>
@@ -22,6 +23,7 @@
 
 #include "bev_internal.h"
 #include "bev_libm.h"
+#include "bev_libm_f64.h"
 
 using namespace bevk;
 
@@ -202,6 +204,18 @@ struct bev_ctx {
     hipEvent_t rf_offs_ev = nullptr;
     hipEvent_t rf_tail_ev = nullptr; /* recorded behind the last chain: the next BEV call's stage streams wait for it */
     bool rf_tail_pending = false;
+
+    /* coarse ICP (bev_coarse_registration_device_resident & co.): one device allocation for the grids and the transformed
+     * clouds, grown on demand; the problem tables go up through a pinned array, reused once icp_tab_ev has passed */
+    void *icp_buf = nullptr;
+    size_t icp_cap = 0;
+    void *icp_tab = nullptr, *icp_h_tab = nullptr;
+    size_t icp_tab_cap = 0;
+    hipEvent_t icp_tab_ev = nullptr;
+    void *icp_one = nullptr; /* bev_icp_point_to_plane: both clouds, their counts, the result */
+    size_t icp_one_cap = 0;
+    hipEvent_t icp_tail_ev = nullptr; /* recorded behind the last batched ICP: the next BEV call waits for it */
+    bool icp_tail_pending = false;
 
     /* profiling */
     bool prof_on = false;
@@ -525,6 +539,10 @@ int run_pipeline(bev_ctx *c, int n_frames, const bev_point_t *d_pts, const uint6
     } else if (fork) {
         HIPCK(c, hipEventRecord(c->fork_ev, c->stream));
         for (int q = 0; q < kMaxStageStreams; ++q) HIPCK(c, hipStreamWaitEvent(c->stage_st[q], c->fork_ev, 0));
+    }
+    if (c->icp_tail_pending) { /* a coarse ICP still running */
+        for (int q = 0; q < kMaxStageStreams; ++q) HIPCK(c, hipStreamWaitEvent(c->stage_st[q], c->icp_tail_ev, 0));
+        c->icp_tail_pending = false;
     }
     if (c->rf_tail_pending) { /* a registration front end still reading a cloud this call may overwrite */
         for (int q = 0; q < kMaxStageStreams; ++q) HIPCK(c, hipStreamWaitEvent(c->stage_st[q], c->rf_tail_ev, 0));
@@ -1007,7 +1025,8 @@ void bev_destroy(bev_ctx_t *c)
     if (c->dl_stream) (void)hipStreamDestroy(c->dl_stream);
     for (auto e : c->out_ready)
         if (e) (void)hipEventDestroy(e);
-    void *dev[] = {c->st_in, c->st_ordered, c->st_multi, c->st_single, c->st_gm, c->kitti_buf, c->codes, c->ctx_tab, c->rf_buf, c->rf_d_offs};
+    void *dev[] = {c->st_in, c->st_ordered, c->st_multi, c->st_single, c->st_gm, c->kitti_buf, c->codes, c->ctx_tab, c->rf_buf, c->rf_d_offs,
+                   c->icp_buf, c->icp_tab, c->icp_one};
     for (void *p : dev)
         if (p) (void)hipFree(p);
     for (int k = 0; k < kDescRing; ++k) {
@@ -1017,6 +1036,9 @@ void bev_destroy(bev_ctx_t *c)
     if (c->rf_h_offs) (void)hipHostFree(c->rf_h_offs);
     if (c->rf_offs_ev) (void)hipEventDestroy(c->rf_offs_ev);
     if (c->rf_tail_ev) (void)hipEventDestroy(c->rf_tail_ev);
+    if (c->icp_h_tab) (void)hipHostFree(c->icp_h_tab);
+    if (c->icp_tab_ev) (void)hipEventDestroy(c->icp_tab_ev);
+    if (c->icp_tail_ev) (void)hipEventDestroy(c->icp_tail_ev);
     for (auto &s : c->prof_pool) {
         if (s.a) (void)hipEventDestroy(s.a);
         if (s.b) (void)hipEventDestroy(s.b);
@@ -1545,6 +1567,179 @@ int bev_registration_front_device_resident(bev_ctx_t *c, int n_frames, const bev
     return BEV_OK;
 }
 #undef RF_PROLOGUE
+
+/* ---- coarse point-to-plane ICP --------------------------------------------------------------------------------------- */
+bev_icp_params_t bev_icp_coarse_defaults(void)
+{
+    bev_icp_params_t p{};
+    p.max_correspondence_distance = 10.0; /* icp.setMaxCorrespondenceDistance(10.0f) */
+    p.max_iterations = 10;                /* icp.setMaximumIterations(10) */
+    p.transformation_epsilon = 0.0;
+    p.euclidean_fitness_epsilon = -DBL_MAX;
+    return p;
+}
+
+static bool icp_params_ok(const bev_icp_params_t &p)
+{
+    return p.max_iterations >= 1 && p.max_iterations <= 1000 && std::isfinite(p.max_correspondence_distance) &&
+           p.max_correspondence_distance > 0.0;
+}
+
+namespace {
+
+/* the grids of the target frames slot_frames, then every problem (launches of kIcpProblemsPerLaunch), then, when d_best is
+ * set, the better guess of each of the n_best matches; all on the context's stream */
+int icp_launch(bev_ctx *c, const float *d_pn, size_t stride, const uint32_t *d_counts,
+               const std::vector<IcpProblem> &probs, const std::vector<uint32_t> &slot_frames,
+               const bev_icp_params_t &prm, bev_icp_result_t *d_res, int n_best, int32_t *d_best)
+{
+    const size_t U = slot_frames.size(), P = probs.size(), L = std::min(P, (size_t)kIcpProblemsPerLaunch);
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t sz[] = {U * sizeof(IcpGridHdr), U * 4 * (size_t)(kIcpCells + 1), U * 16 * stride, L * 16 * stride};
+    size_t need = 0;
+    for (size_t b : sz) need += al(b);
+    if (need > c->icp_cap) {
+        HIPCK(c, hipStreamSynchronize(c->stream)); /* (the last call's kernels may still use it) */
+        if (c->icp_buf) HIPCK(c, hipFree(c->icp_buf));
+        c->icp_buf = nullptr;
+        c->icp_cap = 0;
+        HIPCK(c, hipMalloc(&c->icp_buf, need));
+        c->icp_cap = need;
+    }
+    IcpWork w{};
+    char *p = static_cast<char *>(c->icp_buf);
+    void **dst[] = {(void **)&w.hdr, (void **)&w.cell_off, (void **)&w.sorted, (void **)&w.cur};
+    for (size_t i = 0; i < 4; ++i) {
+        *dst[i] = p;
+        p += al(sz[i]);
+    }
+    const size_t tab = al(P * sizeof(IcpProblem)) + U * 4;
+    if (!c->icp_tab_ev) HIPCK(c, hipEventCreateWithFlags(&c->icp_tab_ev, hipEventDisableTiming));
+    else HIPCK(c, hipEventSynchronize(c->icp_tab_ev)); /* the last call's tables have gone up */
+    if (tab > c->icp_tab_cap) {
+        HIPCK(c, hipStreamSynchronize(c->stream));
+        if (c->icp_h_tab) HIPCK(c, hipHostFree(c->icp_h_tab));
+        if (c->icp_tab) HIPCK(c, hipFree(c->icp_tab));
+        c->icp_h_tab = c->icp_tab = nullptr;
+        c->icp_tab_cap = 0;
+        const size_t cap = std::max(tab, (size_t)1 << 16);
+        HIPCK(c, hipHostMalloc(&c->icp_h_tab, cap, hipHostMallocDefault));
+        HIPCK(c, hipMalloc(&c->icp_tab, cap));
+        c->icp_tab_cap = cap;
+    }
+    char *h = static_cast<char *>(c->icp_h_tab);
+    std::memcpy(h, probs.data(), P * sizeof(IcpProblem));
+    std::memcpy(h + al(P * sizeof(IcpProblem)), slot_frames.data(), U * 4);
+    HIPCK(c, hipMemcpyAsync(c->icp_tab, c->icp_h_tab, tab, hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, hipEventRecord(c->icp_tab_ev, c->stream));
+    const IcpProblem *d_probs = static_cast<const IcpProblem *>(c->icp_tab);
+    const uint32_t *d_slots = reinterpret_cast<const uint32_t *>(static_cast<char *>(c->icp_tab) + al(P * sizeof(IcpProblem)));
+    {
+        ProfScope ps(c, K_ICP_GRID, (int)U);
+        launch_icp_grid(d_pn, stride, d_counts, d_slots, (int)U, w, c->stream);
+    }
+    for (size_t p0 = 0; p0 < P; p0 += kIcpProblemsPerLaunch) {
+        const int n = (int)std::min((size_t)kIcpProblemsPerLaunch, P - p0);
+        ProfScope ps(c, K_ICP, n);
+        launch_icp(d_pn, stride, d_counts, d_probs + p0, n, w, prm, d_res, c->stream);
+    }
+    if (d_best) {
+        ProfScope ps(c, K_ICP_BEST, n_best);
+        launch_icp_best(d_res, n_best, d_best, c->stream);
+    }
+    HIPCK(c, hipGetLastError());
+    return BEV_OK;
+}
+
+} // namespace
+
+int bev_icp_point_to_plane(bev_ctx_t *c, const float *src, uint32_t n_src, const float *tgt, uint32_t n_tgt,
+                           const float *guess16, const bev_icp_params_t *params, bev_icp_result_t *result)
+{
+    const bev_icp_params_t prm = params ? *params : bev_icp_coarse_defaults();
+    if (!c || !result || (n_src && !src) || (n_tgt && !tgt) || !icp_params_ok(prm)) return BEV_ERR_INVALID_ARG;
+    HIPCK(c, hipSetDevice(c->device));
+    int rc = flush_pending(c);
+    if (rc != BEV_OK) return rc;
+    const size_t stride = std::max<size_t>(std::max(n_src, n_tgt), 1);
+    const size_t need = 2 * stride * 48 + 256 + sizeof(bev_icp_result_t);
+    if (need > c->icp_one_cap) {
+        HIPCK(c, hipStreamSynchronize(c->stream));
+        if (c->icp_one) HIPCK(c, hipFree(c->icp_one));
+        c->icp_one = nullptr;
+        c->icp_one_cap = 0;
+        HIPCK(c, hipMalloc(&c->icp_one, need));
+        c->icp_one_cap = need;
+    }
+    char *d = static_cast<char *>(c->icp_one);
+    float *d_pn = reinterpret_cast<float *>(d);
+    uint32_t *d_counts = reinterpret_cast<uint32_t *>(d + 2 * stride * 48);
+    bev_icp_result_t *d_res = reinterpret_cast<bev_icp_result_t *>(d + 2 * stride * 48 + 256);
+    const uint32_t counts[2] = {n_src, n_tgt};
+    if (n_src) HIPCK(c, hipMemcpyAsync(d_pn, src, (size_t)n_src * 48, hipMemcpyHostToDevice, c->stream));
+    if (n_tgt) HIPCK(c, hipMemcpyAsync(d_pn + stride * 12, tgt, (size_t)n_tgt * 48, hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, hipMemcpyAsync(d_counts, counts, sizeof(counts), hipMemcpyHostToDevice, c->stream));
+    std::vector<IcpProblem> probs(1);
+    probs[0].src_frame = 0;
+    probs[0].tgt_frame = 1;
+    probs[0].tgt_slot = 0;
+    probs[0].result = 0;
+    for (int k = 0; k < 16; ++k) probs[0].guess[k] = guess16 ? guess16[k] : (k % 5 == 0 ? 1.0f : 0.0f);
+    rc = icp_launch(c, d_pn, stride, d_counts, probs, std::vector<uint32_t>{1u}, prm, d_res, 0, nullptr);
+    if (rc != BEV_OK) return rc;
+    HIPCK(c, hipMemcpyAsync(result, d_res, sizeof(bev_icp_result_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    return BEV_OK;
+}
+
+int bev_coarse_registration_device_resident(bev_ctx_t *c, int n_frames, const void *d_pn, size_t stride,
+                                            const uint32_t *d_counts, int n_matches, const bev_match_t *h_matches,
+                                            const bev_icp_params_t *params, bev_icp_result_t *d_results,
+                                            int32_t *d_best)
+{
+    const bev_icp_params_t prm = params ? *params : bev_icp_coarse_defaults();
+    if (!c || n_frames < 0 || n_matches < 0 || !icp_params_ok(prm)) return BEV_ERR_INVALID_ARG;
+    if (n_matches > 0) {
+        if (!d_pn || !d_counts || !h_matches || !d_results || !d_best || stride == 0) return BEV_ERR_INVALID_ARG;
+        for (int m = 0; m < n_matches; ++m) {
+            const bev_match_t &mt = h_matches[m];
+            if (mt.query_idx < 0 || mt.query_idx >= n_frames || mt.match_idx < 0 || mt.match_idx >= n_frames)
+                return BEV_ERR_INVALID_ARG;
+        }
+    }
+    HIPCK(c, hipSetDevice(c->device));
+    int rc = flush_pending(c); /* (joins both stage streams into the context's stream) */
+    if (rc != BEV_OK) return rc;
+    if (n_matches == 0) return BEV_OK;
+    /* the caller's default-stream work comes first */
+    HIPCK(c, hipEventRecord(c->null_ev, nullptr));
+    HIPCK(c, hipStreamWaitEvent(c->stream, c->null_ev, 0));
+    std::vector<int32_t> slot_of((size_t)n_frames, -1);
+    std::vector<uint32_t> slot_frames;
+    std::vector<IcpProblem> probs((size_t)n_matches * 2);
+    for (int m = 0; m < n_matches; ++m) {
+        const bev_match_t &mt = h_matches[m];
+        if (slot_of[mt.match_idx] < 0) {
+            slot_of[mt.match_idx] = (int32_t)slot_frames.size();
+            slot_frames.push_back((uint32_t)mt.match_idx);
+        }
+        for (int g = 0; g < 2; ++g) {
+            IcpProblem &pb = probs[(size_t)m * 2 + g];
+            pb.src_frame = (uint32_t)mt.query_idx;
+            pb.tgt_frame = (uint32_t)mt.match_idx;
+            pb.tgt_slot = (uint32_t)slot_of[mt.match_idx];
+            pb.result = (uint32_t)(m * 2 + g);
+            bevx::icp_tool_guess(mt.angle_guess, g, pb.guess);
+        }
+    }
+    rc = icp_launch(c, static_cast<const float *>(d_pn), stride, d_counts, probs, slot_frames, prm, d_results, n_matches,
+                    d_best);
+    if (rc != BEV_OK) return rc;
+    if (!c->icp_tail_ev) HIPCK(c, hipEventCreateWithFlags(&c->icp_tail_ev, hipEventDisableTiming));
+    HIPCK(c, hipEventRecord(c->icp_tail_ev, c->stream));
+    c->icp_tail_pending = true;
+    return BEV_OK;
+}
 
 int bev_set_layout_hint(bev_ctx_t *c, int layout)
 {

@@ -209,6 +209,9 @@ enum KernelId {
     K_RF_TOP,     /* ... each cell's highest points */
     K_RF_VOXEL,   /* ... voxel grid */
     K_RF_NORMALS, /* ... 2-D normals */
+    K_ICP_GRID,   /* coarse ICP (bev_icp.h): the target frames' grids */
+    K_ICP,        /* ... one workgroup per (match, guess): the whole loop and the fitness */
+    K_ICP_BEST,   /* ... the better guess of every match */
     K_COUNT
 };
 const char *kernel_name(int id);
@@ -312,6 +315,36 @@ void launch_rf_top(const RfIn &in, const RfWork &w, int nf, hipStream_t st, int 
 void launch_rf_voxel(const RfWork &w, int nf, float leaf, uint32_t *counts, hipStream_t st);
 void launch_rf_normals(const RfWork &w, int nf, uint32_t max_points, float radius, float leaf, const float vp[2],
                        bool point_normal, float *out, size_t out_stride, hipStream_t st);
+
+/* ---- coarse point-to-plane ICP (bev_icp.h) ---- */
+constexpr int kIcpThreads = 256;
+constexpr int kIcpGridMax = 64;                       /* cells per axis of a target frame's grid */
+constexpr int kIcpCells = kIcpGridMax * kIcpGridMax;
+constexpr int kIcpChunkSlots = 32;                    /* 64-point chunk sums a workgroup holds in LDS at once */
+constexpr int kIcpProblemsPerLaunch = 1024;           /* problems of one k_icp launch (= transformed clouds in scratch) */
+struct IcpGridHdr {
+    float minx, miny, inv_s, s; /* cell (floor((x - minx) * inv_s), ...) clamped; square cells of side s */
+    int32_t nx, ny;
+    float mag;                  /* largest |coordinate| of the bounds (the ring bound's rounding margin) */
+    uint32_t n;                 /* searchable points */
+};
+struct IcpProblem {
+    uint32_t src_frame, tgt_frame, tgt_slot, result;
+    float guess[16]; /* row-major */
+};
+/* per target slot: header, nx * ny + 1 cell offsets, the searchable points (x, y, z, index bits) by cell; per problem of
+ * a launch: the transformed source */
+struct IcpWork {
+    IcpGridHdr *hdr;    /* [slots] */
+    uint32_t *cell_off; /* [slots][kIcpCells + 1] */
+    float4 *sorted;     /* [slots][stride] */
+    float4 *cur;        /* [kIcpProblemsPerLaunch][stride] */
+};
+void launch_icp_grid(const float *pn, size_t stride, const uint32_t *counts, const uint32_t *slot_frame, int n_slots,
+                     const IcpWork &w, hipStream_t st);
+void launch_icp(const float *pn, size_t stride, const uint32_t *counts, const IcpProblem *probs, int n,
+                const IcpWork &w, const bev_icp_params_t &prm, bev_icp_result_t *results, hipStream_t st);
+void launch_icp_best(const bev_icp_result_t *res, int n_matches, int32_t *best, hipStream_t st);
 
 /* opt in to > 64 KiB of dynamic LDS for the kernels that need it */
 hipError_t configure_kernels(const Geometry &g);

@@ -1,0 +1,23 @@
+/* MatchResults.cpp — loadMatchResults (BatchTopPartRegistration.cpp:250-272): plain C++, no device code. */
+#include <fstream>
+#include <sstream>
+
+#include "Registration.h"
+
+std::vector<MatchResult> loadMatchResults(std::string match_results_filename)
+{
+    std::ifstream f_list(match_results_filename);
+    if (!f_list.is_open()) throw std::runtime_error("Failed to open file: " + match_results_filename);
+    std::vector<MatchResult> matches;
+    std::string line;
+    for (size_t line_no = 1; std::getline(f_list, line); ++line_no) {
+        if (line.find_first_not_of(" \t\r") == std::string::npos) continue;
+        std::stringstream ss(line);
+        MatchResult m{};
+        if (!(ss >> m.query_idx >> m.match_idx >> m.angle_guess))
+            throw std::runtime_error(match_results_filename + ":" + std::to_string(line_no) +
+                                     ": expected \"query_idx match_idx angle_guess\"");
+        matches.push_back(m);
+    }
+    return matches;
+}

@@ -1,8 +1,11 @@
-/* Registration.cpp — see Registration.h.  Every computation happens behind the C ABI (bev_regfront.h on the GPU). */
+/* Registration.cpp — see Registration.h.  Every computation happens behind the C ABI (bev_regfront.h, bev_icp.h on the
+ * GPU); only performCoarseIcp's aligned copy of the source is moved on the host. */
 #include "Registration.h"
 
 #include <algorithm>
 #include <string>
+
+#include <hip/hip_runtime_api.h>
 
 bev_ctx_t *bevhost_context(); /* BatchMultiBevGen.cpp (host): the lazily created context of the free functions */
 
@@ -78,4 +81,102 @@ void addNormal(pcl::PointCloud<pcl::PointXYZ>::Ptr cloud, pcl::PointCloud<pcl::P
         o.normal_z = normals->points[i].normal_z;
         o.curvature = normals->points[i].curvature;
     }
+}
+
+/* ---- coarse ICP ------------------------------------------------------------------------------------------------------ */
+static IcpAlignResult to_align_result(const bev_icp_result_t &r)
+{
+    IcpAlignResult a;
+    a.is_converged = r.converged != 0;
+    a.fitness_score = r.fitness;
+    std::copy(r.T, r.T + 16, a.final_transformation.begin());
+    a.iterations = r.iterations;
+    a.state = r.state;
+    return a;
+}
+
+IcpAlignResult performCoarseIcp(pcl::PointCloud<pcl::PointNormal>::Ptr &points_with_normals_src,
+                                pcl::PointCloud<pcl::PointNormal>::Ptr &points_with_normals_tgt,
+                                pcl::PointCloud<pcl::PointNormal>::Ptr points_with_normals_src_aligned,
+                                const std::array<float, 16> &initial_guess)
+{
+    const bev_icp_params_t prm = bev_icp_coarse_defaults();
+    bev_icp_result_t r{};
+    const auto &src = points_with_normals_src->points;
+    const auto &tgt = points_with_normals_tgt->points;
+    check(bev_icp_point_to_plane(bevhost_context(), reinterpret_cast<const float *>(src.data()), (uint32_t)src.size(),
+                                 reinterpret_cast<const float *>(tgt.data()), (uint32_t)tgt.size(), initial_guess.data(),
+                                 &prm, &r),
+          "performCoarseIcp");
+    if (points_with_normals_src_aligned) {
+        const float *T = r.T;
+        points_with_normals_src_aligned->resize(src.size());
+        for (size_t i = 0; i < src.size(); ++i) {
+            pcl::PointNormal o = src[i];
+            const float x = o.x, y = o.y, z = o.z, nx = o.normal_x, ny = o.normal_y, nz = o.normal_z;
+            o.x = T[0] * x + (T[1] * y + (T[2] * z + T[3]));
+            o.y = T[4] * x + (T[5] * y + (T[6] * z + T[7]));
+            o.z = T[8] * x + (T[9] * y + (T[10] * z + T[11]));
+            o.normal_x = (T[0] * nx + T[1] * ny) + T[2] * nz;
+            o.normal_y = (T[4] * nx + T[5] * ny) + T[6] * nz;
+            o.normal_z = (T[8] * nx + T[9] * ny) + T[10] * nz;
+            points_with_normals_src_aligned->points[i] = o;
+        }
+    }
+    return to_align_result(r);
+}
+
+std::vector<CoarseMatch> coarseRegisterMatches(const std::vector<pcl::PointCloud<pcl::PointNormal>::Ptr> &clouds,
+                                               const std::vector<MatchResult> &matches)
+{
+    std::vector<CoarseMatch> out(matches.size());
+    if (matches.empty()) return out;
+    size_t stride = 1;
+    for (const auto &cl : clouds) stride = std::max(stride, cl ? cl->points.size() : (size_t)0);
+    const size_t F = clouds.size();
+    std::vector<pcl::PointNormal> packed(F * stride);
+    std::vector<uint32_t> counts(F, 0);
+    for (size_t f = 0; f < F; ++f) {
+        if (!clouds[f]) continue;
+        std::copy(clouds[f]->points.begin(), clouds[f]->points.end(), packed.begin() + f * stride);
+        counts[f] = (uint32_t)clouds[f]->points.size();
+    }
+    void *d_pn = nullptr, *d_counts = nullptr, *d_res = nullptr, *d_best = nullptr;
+    auto release = [&]() {
+        for (void *p : {d_pn, d_counts, d_res, d_best})
+            if (p) (void)hipFree(p);
+    };
+    auto hip = [&](hipError_t e, const char *what) {
+        if (e != hipSuccess) {
+            release();
+            throw std::runtime_error(std::string("coarseRegisterMatches: ") + what + ": " + hipGetErrorString(e));
+        }
+    };
+    bev_ctx_t *ctx = bevhost_context();
+    hip(hipMalloc(&d_pn, packed.size() * sizeof(pcl::PointNormal)), "hipMalloc");
+    hip(hipMalloc(&d_counts, F * 4), "hipMalloc");
+    hip(hipMalloc(&d_res, matches.size() * 2 * sizeof(bev_icp_result_t)), "hipMalloc");
+    hip(hipMalloc(&d_best, matches.size() * 4), "hipMalloc");
+    hip(hipMemcpy(d_pn, packed.data(), packed.size() * sizeof(pcl::PointNormal), hipMemcpyHostToDevice), "hipMemcpy");
+    hip(hipMemcpy(d_counts, counts.data(), F * 4, hipMemcpyHostToDevice), "hipMemcpy");
+    int rc = bev_coarse_registration_device_resident(ctx, (int)F, d_pn, stride, static_cast<uint32_t *>(d_counts),
+                                                     (int)matches.size(),
+                                                     reinterpret_cast<const bev_match_t *>(matches.data()), nullptr,
+                                                     static_cast<bev_icp_result_t *>(d_res), static_cast<int32_t *>(d_best));
+    if (rc == BEV_OK) rc = bev_synchronize(ctx);
+    if (rc != BEV_OK) {
+        release();
+        check(rc, "coarseRegisterMatches");
+    }
+    std::vector<bev_icp_result_t> res(matches.size() * 2);
+    std::vector<int32_t> best(matches.size());
+    hip(hipMemcpy(res.data(), d_res, res.size() * sizeof(bev_icp_result_t), hipMemcpyDeviceToHost), "hipMemcpy");
+    hip(hipMemcpy(best.data(), d_best, best.size() * 4, hipMemcpyDeviceToHost), "hipMemcpy");
+    release();
+    for (size_t m = 0; m < matches.size(); ++m) {
+        out[m].results[0] = to_align_result(res[2 * m]);
+        out[m].results[1] = to_align_result(res[2 * m + 1]);
+        out[m].best = best[m];
+    }
+    return out;
 }

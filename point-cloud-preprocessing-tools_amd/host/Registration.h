@@ -5,12 +5,19 @@
  *   VoxelGridXYZ           pcl::VoxelGrid<pcl::PointXYZ> (BatchTopPartRegistration.cpp:342-343,405-409)
  *   Normal2dEstimation     src/Normal2dEstimation.cpp (radius mode), src/PCA2D.cpp
  *   addNormal              BatchTopPartRegistration.cpp:155-172 (radius 2, viewpoint at the origin, concatenateFields)
- * The contract is DESIGN.md "Registration front end".  ICP is not here.
+ * and the coarse registration the front end feeds:
+ *   MatchResult, IcpAlignResult, loadMatchResults   BatchTopPartRegistration.cpp:76-88, 250-272 (MatchResults.cpp: no
+ *                                                   device code, so a plain g++ build can use it)
+ *   performCoarseIcp       :192-221 (IterativeClosestPointWithNormals, D = 10, 10 iterations)
+ *   coarseRegisterMatches  the tool's loop (:415-466): both yaw guesses of every match and the better one, in one batch
+ * The contracts are DESIGN.md "Registration front end" (§6b) and "Coarse ICP" (§6c).  The fine stage is not here.
  */
 #ifndef BEV_HOST_REGISTRATION_H
 #define BEV_HOST_REGISTRATION_H
 
+#include <array>
 #include <stdexcept>
+#include <string>
 
 #include "PointCloud.h"
 
@@ -51,5 +58,40 @@ private:
 };
 
 void addNormal(pcl::PointCloud<pcl::PointXYZ>::Ptr cloud, pcl::PointCloud<pcl::PointNormal>::Ptr cloud_with_normals);
+
+struct MatchResult {
+    int32_t query_idx; /* the source frame */
+    int32_t match_idx; /* the target frame */
+    float angle_guess; /* degrees */
+};
+static_assert(sizeof(MatchResult) == sizeof(bev_match_t), "MatchResult must match bev_match_t");
+
+struct IcpAlignResult {
+    bool is_converged = false;
+    double fitness_score = 0.0;
+    std::array<float, 16> final_transformation{}; /* row-major 4 x 4 (Eigen::Matrix4f in the reference) */
+    int iterations = 0;
+    int state = 0; /* BEV_ICP_* */
+};
+
+/* one "query match angle" triple per line (whitespace separated); a blank line is skipped (the reference would push an
+ * uninitialised entry), a line that does not hold the three numbers throws std::runtime_error, as does a file that cannot
+ * be opened (the reference exits) */
+std::vector<MatchResult> loadMatchResults(std::string match_results_filename);
+
+/* IterativeClosestPointWithNormals with D = 10 and 10 iterations from initial_guess (row-major); src_aligned (may be
+ * null) receives the source moved by the final transformation (points by Transformer::se3, normals by its rotation) */
+IcpAlignResult performCoarseIcp(pcl::PointCloud<pcl::PointNormal>::Ptr &points_with_normals_src,
+                                pcl::PointCloud<pcl::PointNormal>::Ptr &points_with_normals_tgt,
+                                pcl::PointCloud<pcl::PointNormal>::Ptr points_with_normals_src_aligned,
+                                const std::array<float, 16> &initial_guess);
+
+struct CoarseMatch {
+    IcpAlignResult results[2]; /* from angle_guess and angle_guess + 180 */
+    int best = 1;              /* 0 iff results[0].fitness_score < results[1].fitness_score */
+};
+/* the tool's coarse loop over every match at once: clouds[f] is frame f's PointNormal cloud (addNormal's output) */
+std::vector<CoarseMatch> coarseRegisterMatches(const std::vector<pcl::PointCloud<pcl::PointNormal>::Ptr> &clouds,
+                                               const std::vector<MatchResult> &matches);
 
 #endif
