@@ -263,7 +263,7 @@ size_t bev_regfront_max_out(size_t n);
  * (BatchTopPartRegistration.cpp:192-221; the tool's two yaw guesses and its choice, :415-466).  The contract — restated
  * from PCL's published sources, parity with the reference UNPINNED, exact 1-NN with the lowest index on ties, every sum
  * in a fixed order — is DESIGN.md §6c.  Clouds are pcl::PointNormal records (12 floats, as above); source normals are
- * never read.  Coarse stage only: the fine stage (VoxelGrid + point-to-point ICP) is not built. */
+ * never read.  The fine stage (VoxelGrid<PointXYZIRCT> + point-to-point ICP) is below. */
 typedef struct {
     double max_correspondence_distance; /* D: a correspondence needs (double)dist <= D * D */
     double transformation_epsilon;
@@ -320,6 +320,49 @@ int bev_coarse_registration_device_resident(bev_ctx_t *ctx, int n_frames, const 
                                             const uint32_t *d_counts, int n_matches, const bev_match_t *h_matches,
                                             const bev_icp_params_t *params, bev_icp_result_t *d_results,
                                             int32_t *d_best);
+
+/* ---- fine stage: VoxelGrid<PointXYZIRCT> and point-to-point ICP ------------------------------------------------------
+ * performFineIcp of the registration tools (BatchTopPartRegistration.cpp:224-247, 480-497; BatchWholeRegistration.cpp:
+ * 222-245, 372-389): pcl::VoxelGrid<PointXYZIRCT> (leaf 0.2) on the full labelled clouds, then
+ * pcl::IterativeClosestPoint<PointXYZIRCT, PointXYZIRCT> (TransformationEstimationSVD, Umeyama without scaling).  The
+ * contract — restated from PCL's and Eigen's published sources, parity with the reference UNPINNED, §6c's loop, exact
+ * 1-NN and summation order — is DESIGN.md §6d. */
+/* pcl::VoxelGrid<pcl::PointXYZIRCT> (BatchTopPartRegistration.cpp:345-346,483-487): x, y, z as bev_voxel_grid_xyz;
+ * intensity the float sum in input order / float(n); label the majority (a tie: the smallest as uint32); row, col, t and
+ * the pads 0.  out: capacity n records. */
+int bev_voxel_grid_irct(bev_ctx_t *ctx, const bev_point_t *cloud, uint32_t n, float leaf, bev_point_t *out,
+                        uint32_t *n_out);
+/* the top-part tool's settings: D 1, transformation_epsilon 1e-6, euclidean_fitness_epsilon 0.01, 100 iterations.
+ * Host only. */
+bev_icp_params_t bev_icp_fine_defaults(void);
+/* the whole tool's settings: D 4, 1e-6, 0.001, 200 iterations.  Host only. */
+bev_icp_params_t bev_icp_whole_defaults(void);
+/* One problem on host clouds (synchronous); only x, y, z are read.  guess16: row-major 4 x 4 (NULL: identity); params
+ * NULL: the fine defaults.  Invalid parameters (as bev_icp_point_to_plane) -> BEV_ERR_INVALID_ARG. */
+int bev_icp_point_to_point(bev_ctx_t *ctx, const bev_point_t *src, uint32_t n_src, const bev_point_t *tgt,
+                           uint32_t n_tgt, const float *guess16, const bev_icp_params_t *params,
+                           bev_icp_result_t *result);
+/* The tools' fine stage for a list of matches, device-resident: the voxel grid (leaf) of every distinct frame the
+ * matches name (once each), then ICP of frame query_idx onto frame match_idx per match.
+ * d_clouds, h_offsets : as bev_registration_front_device_resident (h_offsets NULL: the d_ordered output of
+ *                       bev_process_device_resident, S records per frame; else HOST offsets of packed clouds)
+ * d_coarse, d_best    : bev_coarse_registration_device_resident's outputs: the guess of match m is
+ *                       d_coarse[2m + d_best[m]].T (the top-part tool); both NULL: the yaw guess theta = angle_guess
+ *                       (guess 0 of §6c; the whole tool).  One NULL and the other not: BEV_ERR_INVALID_ARG.
+ * d_results           : n_matches results (device).  params NULL: the fine defaults.
+ * Asynchronous like bev_process_device_resident: bev_synchronize() before reading the results.  It starts behind every
+ * call made on the context before it and behind the caller's default-stream work; the next BEV call starts behind it.
+ * Workspace, allocated on first use (grown when a call needs more) and freed by bev_destroy, with U the distinct frames
+ * of the call, N the largest of their record counts and K the smallest power of two >= N:
+ *   U * (48 N + 4 * 16385 + 36) + min(U, 256) * (8 K + 4 N + 4) + min(n_matches, 1024) * 20 N bytes,
+ * i.e. per frame 48 N bytes of voxel records and the searchable points plus a 64 KiB grid (at most 128 x 128 cells);
+ * plus the tables (16 bytes per frame, 80 per match).  Frames run in voxel launches of 256 and matches in ICP launches of
+ * 1024 (the results do not depend on either).  Nothing is launched when an argument is invalid (BEV_ERR_INVALID_ARG). */
+int bev_fine_registration_device_resident(bev_ctx_t *ctx, int n_frames, const bev_point_t *d_clouds,
+                                          const uint64_t *h_offsets, float leaf, int n_matches,
+                                          const bev_match_t *h_matches, const bev_icp_result_t *d_coarse,
+                                          const int32_t *d_best, const bev_icp_params_t *params,
+                                          bev_icp_result_t *d_results);
 
 /* ---- layout hint -------------------------------------------------------
  * What the caller knows about how its clouds are laid out, so that the library need not look (k_probe reads every 63rd

@@ -80,6 +80,8 @@ ABI_SYMBOLS = [
     "bev_top_part_flatten", "bev_voxel_grid_xyz", "bev_normals_2d", "bev_registration_front_device_resident",
     "bev_regfront_max_out",
     "bev_icp_coarse_defaults", "bev_icp_point_to_plane", "bev_coarse_registration_device_resident",
+    "bev_voxel_grid_irct", "bev_icp_fine_defaults", "bev_icp_whole_defaults", "bev_icp_point_to_point",
+    "bev_fine_registration_device_resident",
 ]
 
 # registration front end (include/bev_mi355x.h): pcl::PointXYZ, pcl::Normal, pcl::PointNormal as float rows
@@ -186,6 +188,13 @@ def load_lib() -> C.CDLL:
         lib.bev_icp_coarse_defaults.restype = IcpParams
         lib.bev_icp_point_to_plane.argtypes = [vp, vp, u32, vp, u32, vp, C.POINTER(IcpParams), vp]
         lib.bev_coarse_registration_device_resident.argtypes = [vp, i32, vp, sz, vp, i32, vp, C.POINTER(IcpParams), vp, vp]
+    if hasattr(lib, "bev_fine_registration_device_resident"):
+        lib.bev_voxel_grid_irct.argtypes = [vp, vp, u32, C.c_float, vp, C.POINTER(u32)]
+        lib.bev_icp_fine_defaults.argtypes = lib.bev_icp_whole_defaults.argtypes = []
+        lib.bev_icp_fine_defaults.restype = lib.bev_icp_whole_defaults.restype = IcpParams
+        lib.bev_icp_point_to_point.argtypes = [vp, vp, u32, vp, u32, vp, C.POINTER(IcpParams), vp]
+        lib.bev_fine_registration_device_resident.argtypes = [vp, i32, vp, C.POINTER(C.c_uint64), C.c_float, i32, vp, vp,
+                                                              vp, C.POINTER(IcpParams), vp]
     _lib = lib
     return lib
 
@@ -445,6 +454,79 @@ class BevContext:
         best[:] = d_best.cpu().numpy()
         return res, best
 
+    # ---- fine stage: VoxelGrid<PointXYZIRCT> and point-to-point ICP ---------------------------------
+    def voxel_grid_irct(self, cloud, leaf=0.2):
+        """pcl::VoxelGrid<PointXYZIRCT> with one leaf size: POINT_DTYPE records in, POINT_DTYPE voxels out."""
+        cloud = np.ascontiguousarray(cloud, dtype=POINT_DTYPE)
+        out = np.zeros(max(len(cloud), 1), dtype=POINT_DTYPE)
+        m = C.c_uint32(0)
+        self._check(self.lib.bev_voxel_grid_irct(self._h, _ptr(cloud) if len(cloud) else None, len(cloud), leaf,
+                                                 _ptr(out), C.byref(m)), "bev_voxel_grid_irct")
+        return out[: m.value].copy()
+
+    def icp_point_to_point(self, src, tgt, guess=None, params: IcpParams | None = None):
+        """One problem: src / tgt are POINT_DTYPE records (or (n, 3) / (n, 4) float rows: x, y, z), guess a 4 x 4 (None:
+        identity), params None: the fine defaults.  Returns one ICP_RESULT_DTYPE record."""
+        src, tgt = as_points(src), as_points(tgt)
+        g = None if guess is None else np.ascontiguousarray(np.asarray(guess, dtype=np.float32).reshape(16))
+        prm = params if params is not None else icp_fine_defaults()
+        out = np.zeros(1, dtype=ICP_RESULT_DTYPE)
+        self._check(self.lib.bev_icp_point_to_point(self._h, _ptr(src) if len(src) else None, len(src),
+                                                    _ptr(tgt) if len(tgt) else None, len(tgt),
+                                                    _ptr(g) if g is not None else None, C.byref(prm), _ptr(out)),
+                    "bev_icp_point_to_point")
+        return out[0]
+
+    def fine_registration_device(self, n_frames, d_clouds, offsets, matches, d_results, d_coarse=None, d_best=None,
+                                 leaf=0.2, params: IcpParams | None = None):
+        """bev_fine_registration_device_resident on device pointers; offsets None: d_clouds is the d_ordered layout
+        (n_frames * S records); d_coarse / d_best: the coarse entry's outputs (top-part tool) or None (whole tool).
+        Asynchronous: synchronize() before reading d_results (one ICP_RESULT_DTYPE per match)."""
+        offs = None
+        if offsets is not None:
+            offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+            assert offsets.shape[0] == n_frames + 1
+            offs = offsets.ctypes.data_as(C.POINTER(C.c_uint64))
+        m = np.ascontiguousarray(matches, dtype=MATCH_DTYPE)
+        prm = params if params is not None else icp_fine_defaults()
+        self._check(self.lib.bev_fine_registration_device_resident(
+            self._h, n_frames, C.c_void_p(d_clouds), offs, leaf, len(m), _ptr(m) if len(m) else None,
+            C.c_void_p(d_coarse) if d_coarse else None, C.c_void_p(d_best) if d_best else None, C.byref(prm),
+            C.c_void_p(d_results)), "bev_fine_registration_device_resident")
+
+    def fine_registration(self, clouds, matches, coarse=None, best=None, leaf=0.2, params: IcpParams | None = None):
+        """The fine stage on host clouds (uploaded through torch): clouds is a list of POINT_DTYPE arrays, matches
+        MATCH_DTYPE records or (query_idx, match_idx, angle_guess) tuples; coarse / best: the coarse results
+        ((n, 2) ICP_RESULT_DTYPE, (n,) int32) whose better transform is the guess, or None (the yaw guess).  Returns
+        (n_matches,) ICP_RESULT_DTYPE."""
+        import torch
+
+        m = np.array([tuple(r) for r in matches], dtype=MATCH_DTYPE) if not isinstance(matches, np.ndarray) else \
+            np.ascontiguousarray(matches, dtype=MATCH_DTYPE)
+        n = len(m)
+        res = np.zeros(n, dtype=ICP_RESULT_DTYPE)
+        if n == 0:
+            return res
+        clouds = [np.ascontiguousarray(c_, dtype=POINT_DTYPE) for c_ in clouds]
+        offs = np.zeros(len(clouds) + 1, dtype=np.uint64)
+        offs[1:] = np.cumsum([len(c_) for c_ in clouds])
+        dev = torch.device("cuda", torch.cuda.current_device())
+        packed = np.concatenate(clouds) if offs[-1] else np.zeros(1, dtype=POINT_DTYPE)
+        d_in = torch.from_numpy(packed.view(np.uint8).reshape(-1).copy()).to(dev)
+        d_res = torch.zeros(n * ICP_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        d_coarse = d_best = None
+        if coarse is not None:
+            cr = np.ascontiguousarray(coarse, dtype=ICP_RESULT_DTYPE).reshape(-1)
+            d_coarse = torch.from_numpy(cr.view(np.uint8).copy()).to(dev)
+            d_best = torch.from_numpy(np.ascontiguousarray(best, dtype=np.int32).copy()).to(dev)
+        torch.cuda.synchronize()
+        self.fine_registration_device(len(clouds), d_in.data_ptr(), offs, m, d_res.data_ptr(),
+                                      d_coarse.data_ptr() if d_coarse is not None else None,
+                                      d_best.data_ptr() if d_best is not None else None, leaf, params)
+        self.synchronize()
+        res[:] = d_res.cpu().numpy().view(ICP_RESULT_DTYPE)
+        return res
+
     def set_layout_hint(self, layout: int):
         """LAYOUT_UNKNOWN (the library looks), LAYOUT_STRUCTURED, LAYOUT_FIRING_ORDER: include/bev_mi355x.h"""
         self._check(self.lib.bev_set_layout_hint(self._h, layout), "bev_set_layout_hint")
@@ -517,6 +599,27 @@ def _pn12(a) -> np.ndarray:
 def icp_coarse_defaults() -> IcpParams:
     """bev_icp_coarse_defaults(): D = 10, 10 iterations, transformation_epsilon 0, euclidean_fitness_epsilon -DBL_MAX."""
     return load_lib().bev_icp_coarse_defaults()
+
+
+def icp_fine_defaults() -> IcpParams:
+    """bev_icp_fine_defaults(): the top-part tool's fine ICP — D = 1, transformation_epsilon 1e-6,
+    euclidean_fitness_epsilon 0.01, 100 iterations."""
+    return load_lib().bev_icp_fine_defaults()
+
+
+def icp_whole_defaults() -> IcpParams:
+    """bev_icp_whole_defaults(): the whole tool's ICP — D = 4, 1e-6, 0.001, 200 iterations."""
+    return load_lib().bev_icp_whole_defaults()
+
+
+def as_points(a) -> np.ndarray:
+    """POINT_DTYPE records as they are, or (n, 3) / (n, 4) float rows as records with x, y, z set (every other field 0)."""
+    if isinstance(a, np.ndarray) and a.dtype == POINT_DTYPE:
+        return np.ascontiguousarray(a)
+    f = np.asarray(a, dtype=np.float32).reshape(len(a), -1) if len(a) else np.zeros((0, 3), np.float32)
+    out = np.zeros(len(f), dtype=POINT_DTYPE)
+    out["x"], out["y"], out["z"] = f[:, 0], f[:, 1], f[:, 2]
+    return out
 
 
 def _xyz4(xyz) -> np.ndarray:

@@ -217,6 +217,17 @@ struct bev_ctx {
     hipEvent_t icp_tail_ev = nullptr; /* recorded behind the last batched ICP: the next BEV call waits for it */
     bool icp_tail_pending = false;
 
+    /* fine stage (bev_fine_registration_device_resident & co.): one device allocation for the voxel clouds, grids and
+     * transformed clouds, grown on demand; host clouds of the per-cloud entries go through fine_in; the tables go up
+     * through a pinned array, reused once fine_tab_ev has passed.  The batched entry's tail is icp_tail_ev. */
+    void *fine_buf = nullptr;
+    size_t fine_cap = 0;
+    void *fine_in = nullptr;
+    size_t fine_in_cap = 0;
+    void *fine_tab = nullptr, *fine_h_tab = nullptr;
+    size_t fine_tab_cap = 0;
+    hipEvent_t fine_tab_ev = nullptr;
+
     /* profiling */
     bool prof_on = false;
     std::vector<ProfSlot> prof_pool;
@@ -1026,7 +1037,7 @@ void bev_destroy(bev_ctx_t *c)
     for (auto e : c->out_ready)
         if (e) (void)hipEventDestroy(e);
     void *dev[] = {c->st_in, c->st_ordered, c->st_multi, c->st_single, c->st_gm, c->kitti_buf, c->codes, c->ctx_tab, c->rf_buf, c->rf_d_offs,
-                   c->icp_buf, c->icp_tab, c->icp_one};
+                   c->icp_buf, c->icp_tab, c->icp_one, c->fine_buf, c->fine_in, c->fine_tab};
     for (void *p : dev)
         if (p) (void)hipFree(p);
     for (int k = 0; k < kDescRing; ++k) {
@@ -1039,6 +1050,8 @@ void bev_destroy(bev_ctx_t *c)
     if (c->icp_h_tab) (void)hipHostFree(c->icp_h_tab);
     if (c->icp_tab_ev) (void)hipEventDestroy(c->icp_tab_ev);
     if (c->icp_tail_ev) (void)hipEventDestroy(c->icp_tail_ev);
+    if (c->fine_h_tab) (void)hipHostFree(c->fine_h_tab);
+    if (c->fine_tab_ev) (void)hipEventDestroy(c->fine_tab_ev);
     for (auto &s : c->prof_pool) {
         if (s.a) (void)hipEventDestroy(s.a);
         if (s.b) (void)hipEventDestroy(s.b);
@@ -1734,6 +1747,276 @@ int bev_coarse_registration_device_resident(bev_ctx_t *c, int n_frames, const vo
     }
     rc = icp_launch(c, static_cast<const float *>(d_pn), stride, d_counts, probs, slot_frames, prm, d_results, n_matches,
                     d_best);
+    if (rc != BEV_OK) return rc;
+    if (!c->icp_tail_ev) HIPCK(c, hipEventCreateWithFlags(&c->icp_tail_ev, hipEventDisableTiming));
+    HIPCK(c, hipEventRecord(c->icp_tail_ev, c->stream));
+    c->icp_tail_pending = true;
+    return BEV_OK;
+}
+
+/* ---- fine stage: VoxelGrid<PointXYZIRCT> and point-to-point ICP ------------------------------------------------------ */
+bev_icp_params_t bev_icp_fine_defaults(void)
+{
+    bev_icp_params_t p{};
+    p.max_correspondence_distance = 1.0; /* icp_full.setMaxCorrespondenceDistance(1.0f) (BatchTopPartRegistration.cpp:232) */
+    p.transformation_epsilon = 1e-6;     /* setTransformationEpsilon(1e-6) */
+    p.euclidean_fitness_epsilon = 0.01;  /* setEuclideanFitnessEpsilon(0.01) */
+    p.max_iterations = 100;              /* setMaximumIterations(100) */
+    return p;
+}
+
+bev_icp_params_t bev_icp_whole_defaults(void)
+{
+    bev_icp_params_t p{};
+    p.max_correspondence_distance = 4.0; /* BatchWholeRegistration.cpp:232-235 */
+    p.transformation_epsilon = 1e-6;
+    p.euclidean_fitness_epsilon = 0.001;
+    p.max_iterations = 200;
+    return p;
+}
+
+namespace {
+
+size_t pow2_at_least(size_t n)
+{
+    size_t p = 1;
+    while (p < n) p <<= 1;
+    return p;
+}
+
+/* the device workspace for U slots of at most Pn records and P problems (grown when a call needs more), the slot and
+ * problem tables uploaded behind everything on the context's stream */
+int fine_setup(bev_ctx *c, size_t U, size_t Pn, const std::vector<FineSlot> &slots, const std::vector<FineProblem> &probs,
+               FineWork &w, const FineSlot **d_slots, const FineProblem **d_probs)
+{
+    const size_t P = probs.size(), G = std::min(U, (size_t)kFineVoxelGroup), L = std::min(P, (size_t)kFineProblemsPerLaunch);
+    const size_t Kn = pow2_at_least(Pn);
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t sz[] = {U * Pn * sizeof(bev_point_t), U * 4, G * Kn * 8, G * (Pn + 1) * 4, U * sizeof(IcpGridHdr),
+                         U * 4 * (size_t)(kFineCells + 1), U * Pn * 16, L * Pn * 16, L * Pn * 4};
+    constexpr size_t kParts = sizeof(sz) / sizeof(sz[0]);
+    size_t need = 0;
+    for (size_t b : sz) need += al(b);
+    if (need > c->fine_cap) {
+        HIPCK(c, hipStreamSynchronize(c->stream)); /* (the last call's kernels may still use it) */
+        if (c->fine_buf) HIPCK(c, hipFree(c->fine_buf));
+        c->fine_buf = nullptr;
+        c->fine_cap = 0;
+        HIPCK(c, hipMalloc(&c->fine_buf, need));
+        c->fine_cap = need;
+    }
+    w = FineWork{};
+    char *p = static_cast<char *>(c->fine_buf);
+    void **dst[kParts] = {(void **)&w.vox, (void **)&w.vox_n, (void **)&w.keys, (void **)&w.vstart, (void **)&w.hdr,
+                          (void **)&w.cell_off, (void **)&w.sorted, (void **)&w.cur, (void **)&w.corr};
+    for (size_t i = 0; i < kParts; ++i) {
+        *dst[i] = p;
+        p += al(sz[i]);
+    }
+    w.Pn = Pn;
+    w.Kn = Kn;
+    const size_t tab = al(slots.size() * sizeof(FineSlot)) + P * sizeof(FineProblem);
+    if (!c->fine_tab_ev) HIPCK(c, hipEventCreateWithFlags(&c->fine_tab_ev, hipEventDisableTiming));
+    else HIPCK(c, hipEventSynchronize(c->fine_tab_ev)); /* the last call's tables have gone up */
+    if (tab > c->fine_tab_cap) {
+        HIPCK(c, hipStreamSynchronize(c->stream));
+        if (c->fine_h_tab) HIPCK(c, hipHostFree(c->fine_h_tab));
+        if (c->fine_tab) HIPCK(c, hipFree(c->fine_tab));
+        c->fine_h_tab = c->fine_tab = nullptr;
+        c->fine_tab_cap = 0;
+        const size_t cap = std::max(tab, (size_t)1 << 16);
+        HIPCK(c, hipHostMalloc(&c->fine_h_tab, cap, hipHostMallocDefault));
+        HIPCK(c, hipMalloc(&c->fine_tab, cap));
+        c->fine_tab_cap = cap;
+    }
+    char *h = static_cast<char *>(c->fine_h_tab);
+    if (!slots.empty()) std::memcpy(h, slots.data(), slots.size() * sizeof(FineSlot));
+    if (P) std::memcpy(h + al(slots.size() * sizeof(FineSlot)), probs.data(), P * sizeof(FineProblem));
+    if (tab) HIPCK(c, hipMemcpyAsync(c->fine_tab, c->fine_h_tab, tab, hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, hipEventRecord(c->fine_tab_ev, c->stream));
+    *d_slots = static_cast<const FineSlot *>(c->fine_tab);
+    *d_probs = reinterpret_cast<const FineProblem *>(static_cast<char *>(c->fine_tab) + al(slots.size() * sizeof(FineSlot)));
+    return BEV_OK;
+}
+
+int fine_voxel(bev_ctx *c, const bev_point_t *d_pts, const FineSlot *d_slots, int U, const FineWork &w, float leaf)
+{
+    for (int s0 = 0; s0 < U; s0 += kFineVoxelGroup) {
+        const int n = std::min(kFineVoxelGroup, U - s0);
+        ProfScope ps(c, K_FINE_VOXEL, n);
+        launch_fine_voxel(d_pts, d_slots, s0, n, w, leaf, c->stream);
+    }
+    HIPCK(c, hipGetLastError());
+    return BEV_OK;
+}
+
+int fine_icp(bev_ctx *c, int U, const FineProblem *d_probs, size_t P, const FineWork &w, const bev_icp_result_t *d_coarse,
+             const int32_t *d_best, const bev_icp_params_t &prm, bev_icp_result_t *d_res)
+{
+    {
+        ProfScope ps(c, K_FINE_GRID, U);
+        launch_fine_grid(U, w, c->stream);
+    }
+    for (size_t p0 = 0; p0 < P; p0 += kFineProblemsPerLaunch) {
+        const int n = (int)std::min((size_t)kFineProblemsPerLaunch, P - p0);
+        ProfScope ps(c, K_FINE_ICP, n);
+        launch_fine_icp(d_probs + p0, n, w, d_coarse, d_best, prm, d_res, c->stream);
+    }
+    HIPCK(c, hipGetLastError());
+    return BEV_OK;
+}
+
+/* host records -> c->fine_in (grown on demand) */
+int fine_upload(bev_ctx *c, const bev_point_t *const *clouds, const uint32_t *n, int k, size_t *offs)
+{
+    size_t total = 0;
+    for (int i = 0; i < k; ++i) {
+        offs[i] = total;
+        total += n[i];
+    }
+    const size_t need = std::max<size_t>(total, 1) * sizeof(bev_point_t);
+    if (need > c->fine_in_cap) {
+        HIPCK(c, hipStreamSynchronize(c->stream));
+        if (c->fine_in) HIPCK(c, hipFree(c->fine_in));
+        c->fine_in = nullptr;
+        c->fine_in_cap = 0;
+        HIPCK(c, hipMalloc(&c->fine_in, need));
+        c->fine_in_cap = need;
+    }
+    for (int i = 0; i < k; ++i)
+        if (n[i])
+            HIPCK(c, hipMemcpyAsync(static_cast<bev_point_t *>(c->fine_in) + offs[i], clouds[i], (size_t)n[i] * sizeof(bev_point_t),
+                                    hipMemcpyHostToDevice, c->stream));
+    return BEV_OK;
+}
+
+} // namespace
+
+int bev_voxel_grid_irct(bev_ctx_t *c, const bev_point_t *cloud, uint32_t n, float leaf, bev_point_t *out, uint32_t *n_out)
+{
+    if (!c || !n_out || (n && (!cloud || !out)) || !(std::isfinite(leaf) && leaf > 0.0f)) return BEV_ERR_INVALID_ARG;
+    *n_out = 0;
+    HIPCK(c, hipSetDevice(c->device));
+    int rc = flush_pending(c);
+    if (rc != BEV_OK) return rc;
+    if (n == 0) return BEV_OK;
+    size_t off = 0;
+    rc = fine_upload(c, &cloud, &n, 1, &off);
+    if (rc != BEV_OK) return rc;
+    FineWork w;
+    const FineSlot *d_slots;
+    const FineProblem *d_probs;
+    rc = fine_setup(c, 1, n, std::vector<FineSlot>{FineSlot{0, n, 0}}, std::vector<FineProblem>{}, w, &d_slots, &d_probs);
+    if (rc != BEV_OK) return rc;
+    rc = fine_voxel(c, static_cast<const bev_point_t *>(c->fine_in), d_slots, 1, w, leaf);
+    if (rc != BEV_OK) return rc;
+    uint32_t nv = 0;
+    HIPCK(c, hipMemcpyAsync(&nv, w.vox_n, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    if (nv) HIPCK(c, hipMemcpy(out, w.vox, (size_t)nv * sizeof(bev_point_t), hipMemcpyDeviceToHost));
+    *n_out = nv;
+    return BEV_OK;
+}
+
+int bev_icp_point_to_point(bev_ctx_t *c, const bev_point_t *src, uint32_t n_src, const bev_point_t *tgt, uint32_t n_tgt,
+                           const float *guess16, const bev_icp_params_t *params, bev_icp_result_t *result)
+{
+    const bev_icp_params_t prm = params ? *params : bev_icp_fine_defaults();
+    if (!c || !result || (n_src && !src) || (n_tgt && !tgt) || !icp_params_ok(prm)) return BEV_ERR_INVALID_ARG;
+    HIPCK(c, hipSetDevice(c->device));
+    int rc = flush_pending(c);
+    if (rc != BEV_OK) return rc;
+    const size_t Pn = std::max<size_t>(std::max(n_src, n_tgt), 1);
+    std::vector<FineProblem> probs(1);
+    probs[0].src_slot = 0;
+    probs[0].tgt_slot = 1;
+    probs[0].result = 0;
+    probs[0].coarse_match = 0xffffffffu;
+    for (int k = 0; k < 16; ++k) probs[0].guess[k] = guess16 ? guess16[k] : (k % 5 == 0 ? 1.0f : 0.0f);
+    FineWork w;
+    const FineSlot *d_slots;
+    const FineProblem *d_probs;
+    rc = fine_setup(c, 2, Pn, std::vector<FineSlot>{}, probs, w, &d_slots, &d_probs);
+    if (rc != BEV_OK) return rc;
+    /* the clouds are the "voxel clouds" of slots 0 and 1; the result goes behind them in the sort scratch */
+    const uint32_t counts[2] = {n_src, n_tgt};
+    if (n_src) HIPCK(c, hipMemcpyAsync(w.vox, src, (size_t)n_src * sizeof(bev_point_t), hipMemcpyHostToDevice, c->stream));
+    if (n_tgt) HIPCK(c, hipMemcpyAsync(w.vox + Pn, tgt, (size_t)n_tgt * sizeof(bev_point_t), hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, hipMemcpyAsync(w.vox_n, counts, sizeof(counts), hipMemcpyHostToDevice, c->stream));
+    bev_icp_result_t *d_res = reinterpret_cast<bev_icp_result_t *>(w.keys);
+    rc = fine_icp(c, 2, d_probs, 1, w, nullptr, nullptr, prm, d_res);
+    if (rc != BEV_OK) return rc;
+    HIPCK(c, hipMemcpyAsync(result, d_res, sizeof(bev_icp_result_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    return BEV_OK;
+}
+
+int bev_fine_registration_device_resident(bev_ctx_t *c, int n_frames, const bev_point_t *d_clouds,
+                                          const uint64_t *h_offsets, float leaf, int n_matches,
+                                          const bev_match_t *h_matches, const bev_icp_result_t *d_coarse,
+                                          const int32_t *d_best, const bev_icp_params_t *params,
+                                          bev_icp_result_t *d_results)
+{
+    const bev_icp_params_t prm = params ? *params : bev_icp_fine_defaults();
+    if (!c || n_frames < 0 || n_matches < 0 || !icp_params_ok(prm) || !(std::isfinite(leaf) && leaf > 0.0f) ||
+        (d_coarse == nullptr) != (d_best == nullptr))
+        return BEV_ERR_INVALID_ARG;
+    if (n_matches > 0) {
+        if (!d_clouds || !h_matches || !d_results) return BEV_ERR_INVALID_ARG;
+        for (int m = 0; m < n_matches; ++m) {
+            const bev_match_t &mt = h_matches[m];
+            if (mt.query_idx < 0 || mt.query_idx >= n_frames || mt.match_idx < 0 || mt.match_idx >= n_frames)
+                return BEV_ERR_INVALID_ARG;
+        }
+        if (h_offsets)
+            for (int f = 0; f < n_frames; ++f)
+                if (h_offsets[f + 1] < h_offsets[f] || h_offsets[f + 1] - h_offsets[f] > 0xffffffffull) return BEV_ERR_INVALID_ARG;
+    }
+    HIPCK(c, hipSetDevice(c->device));
+    int rc = flush_pending(c); /* (joins both stage streams into the context's stream) */
+    if (rc != BEV_OK) return rc;
+    if (n_matches == 0) return BEV_OK;
+    /* the caller's default-stream work comes first */
+    HIPCK(c, hipEventRecord(c->null_ev, nullptr));
+    HIPCK(c, hipStreamWaitEvent(c->stream, c->null_ev, 0));
+    std::vector<int32_t> slot_of((size_t)n_frames, -1);
+    std::vector<FineSlot> slots;
+    size_t Pn = 1;
+    auto slot = [&](int f) -> uint32_t {
+        if (slot_of[f] < 0) {
+            slot_of[f] = (int32_t)slots.size();
+            FineSlot s{};
+            if (h_offsets) {
+                s.off = h_offsets[f];
+                s.n = (uint32_t)(h_offsets[f + 1] - h_offsets[f]);
+            } else {
+                s.off = (uint64_t)f * c->geo.S;
+                s.n = (uint32_t)c->geo.S;
+            }
+            Pn = std::max(Pn, (size_t)s.n);
+            slots.push_back(s);
+        }
+        return (uint32_t)slot_of[f];
+    };
+    std::vector<FineProblem> probs((size_t)n_matches);
+    for (int m = 0; m < n_matches; ++m) {
+        const bev_match_t &mt = h_matches[m];
+        FineProblem &pb = probs[(size_t)m];
+        pb.src_slot = slot(mt.query_idx);
+        pb.tgt_slot = slot(mt.match_idx);
+        pb.result = (uint32_t)m;
+        pb.coarse_match = d_coarse ? (uint32_t)m : 0xffffffffu;
+        bevx::icp_tool_guess(mt.angle_guess, 0, pb.guess);
+    }
+    const int U = (int)slots.size();
+    FineWork w;
+    const FineSlot *d_slots;
+    const FineProblem *d_probs;
+    rc = fine_setup(c, (size_t)U, Pn, slots, probs, w, &d_slots, &d_probs);
+    if (rc != BEV_OK) return rc;
+    rc = fine_voxel(c, d_clouds, d_slots, U, w, leaf);
+    if (rc != BEV_OK) return rc;
+    rc = fine_icp(c, U, d_probs, probs.size(), w, d_coarse, d_best, prm, d_results);
     if (rc != BEV_OK) return rc;
     if (!c->icp_tail_ev) HIPCK(c, hipEventCreateWithFlags(&c->icp_tail_ev, hipEventDisableTiming));
     HIPCK(c, hipEventRecord(c->icp_tail_ev, c->stream));

@@ -212,6 +212,9 @@ enum KernelId {
     K_ICP_GRID,   /* coarse ICP (bev_icp.h): the target frames' grids */
     K_ICP,        /* ... one workgroup per (match, guess): the whole loop and the fitness */
     K_ICP_BEST,   /* ... the better guess of every match */
+    K_FINE_VOXEL, /* fine stage (bev_fine.h): VoxelGrid<PointXYZIRCT> of the full clouds */
+    K_FINE_GRID,  /* ... the target frames' grids */
+    K_FINE_ICP,   /* ... one workgroup per match: the point-to-point loop and the fitness */
     K_COUNT
 };
 const char *kernel_name(int id);
@@ -345,6 +348,44 @@ void launch_icp_grid(const float *pn, size_t stride, const uint32_t *counts, con
 void launch_icp(const float *pn, size_t stride, const uint32_t *counts, const IcpProblem *probs, int n,
                 const IcpWork &w, const bev_icp_params_t &prm, bev_icp_result_t *results, hipStream_t st);
 void launch_icp_best(const bev_icp_result_t *res, int n_matches, int32_t *best, hipStream_t st);
+
+/* ---- fine stage: VoxelGrid<PointXYZIRCT> and point-to-point ICP (bev_fine.h) ---- */
+constexpr int kFineThreads = 256;
+constexpr int kFineGridMax = 128;                     /* cells per axis of a target frame's grid (counts: 64 KiB of LDS) */
+constexpr int kFineCells = kFineGridMax * kFineGridMax;
+constexpr int kFineSvdSweeps = 64;                    /* Jacobi sweeps of the 3 x 3 SVD at most (never reached on finite input) */
+constexpr int kFineProblemsPerLaunch = 1024;          /* problems of one k_fine_icp launch (= transformed clouds in scratch) */
+constexpr int kFineVoxelGroup = 256;                  /* frames of one k_fine_voxel launch (= sort scratch regions) */
+/* a frame of the call: its records are pts + off, n of them (n <= Pn) */
+struct FineSlot {
+    uint64_t off;
+    uint32_t n, _pad;
+};
+/* src / tgt: slots; coarse_match != ~0: the guess is coarse[2 m + best[m]].T, else guess */
+struct FineProblem {
+    uint32_t src_slot, tgt_slot, result, coarse_match;
+    float guess[16]; /* row-major */
+};
+/* per slot: the voxel grid's records and count, the grid (header, offsets, the searchable points by cell); per frame of a
+ * voxel launch: the sort keys and voxel starts; per problem of an ICP launch: the transformed source, its correspondences */
+struct FineWork {
+    bev_point_t *vox;   /* [slots][Pn] */
+    uint32_t *vox_n;    /* [slots] */
+    uint64_t *keys;     /* [kFineVoxelGroup][Kn] */
+    uint32_t *vstart;   /* [kFineVoxelGroup][Pn + 1] */
+    IcpGridHdr *hdr;    /* [slots] */
+    uint32_t *cell_off; /* [slots][kFineCells + 1] */
+    float4 *sorted;     /* [slots][Pn] */
+    float4 *cur;        /* [kFineProblemsPerLaunch][Pn] */
+    uint32_t *corr;     /* [kFineProblemsPerLaunch][Pn] */
+    size_t Pn, Kn;      /* Kn: the smallest power of two >= Pn */
+};
+/* slots slot0 ... slot0 + n - 1 (n <= kFineVoxelGroup) */
+void launch_fine_voxel(const bev_point_t *pts, const FineSlot *slots, int slot0, int n, const FineWork &w, float leaf,
+                       hipStream_t st);
+void launch_fine_grid(int n_slots, const FineWork &w, hipStream_t st);
+void launch_fine_icp(const FineProblem *probs, int n, const FineWork &w, const bev_icp_result_t *coarse,
+                     const int32_t *best, const bev_icp_params_t &prm, bev_icp_result_t *results, hipStream_t st);
 
 /* opt in to > 64 KiB of dynamic LDS for the kernels that need it */
 hipError_t configure_kernels(const Geometry &g);

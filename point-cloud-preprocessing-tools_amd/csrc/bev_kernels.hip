@@ -38,6 +38,7 @@
 #include "bev_misc.h"
 #include "bev_regfront.h"
 #include "bev_icp.h"
+#include "bev_fine.h"
 
 using namespace bevx;
 
@@ -48,6 +49,7 @@ static const char *const kNames[K_COUNT] = {
     "k_gather_only", "k_ground_mat", "k_cloud_codes", "k_angle_debug", "k_float_bev", "k_project", "k_transform",
     "k_probe", "k_walk_general", "k_walk_structured", "k_walk_colmajor", "k_walk_colmajor_gen", "k_verdict", "k_stage",
     "k_rf_cells", "k_rf_top", "k_rf_voxel", "k_rf_normals", "k_icp_grid", "k_icp", "k_icp_best",
+    "k_fine_voxel", "k_fine_grid", "k_fine_icp",
 };
 const char *kernel_name(int id) { return (id >= 0 && id < K_COUNT) ? kNames[id] : "?"; }
 

@@ -1,4 +1,5 @@
 /* MatchResults.cpp — loadMatchResults (BatchTopPartRegistration.cpp:250-272): plain C++, no device code. */
+#include <cmath>
 #include <fstream>
 #include <sstream>
 
@@ -20,4 +21,12 @@ std::vector<MatchResult> loadMatchResults(std::string match_results_filename)
         matches.push_back(m);
     }
     return matches;
+}
+
+/* rotationMatrixToEulerAngles (BatchTopPartRegistration.cpp:290-309): float, the host libm */
+std::array<float, 3> rotationMatrixToEulerAngles(const std::array<float, 9> &R)
+{
+    const float sy = std::sqrt(R[0] * R[0] + R[3] * R[3]);
+    if (!(sy < 1e-6)) return {std::atan2(R[7], R[8]), std::atan2(-R[6], sy), std::atan2(R[3], R[0])};
+    return {std::atan2(-R[5], R[4]), std::atan2(-R[6], sy), 0.0f};
 }

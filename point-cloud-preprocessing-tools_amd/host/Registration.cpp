@@ -180,3 +180,111 @@ std::vector<CoarseMatch> coarseRegisterMatches(const std::vector<pcl::PointCloud
     }
     return out;
 }
+
+/* ---- fine stage ------------------------------------------------------------------------------------------------------ */
+void VoxelGridXYZIRCT::setLeafSize(float lx, float ly, float lz)
+{
+    if (lx != ly || ly != lz) throw std::runtime_error("VoxelGridXYZIRCT: one leaf size for x, y and z");
+    m_leaf = lx;
+}
+
+void VoxelGridXYZIRCT::filter(pcl::PointCloud<pcl::PointXYZIRCT> &output) const
+{
+    const uint32_t n = m_in ? (uint32_t)m_in->points.size() : 0u;
+    std::vector<pcl::PointXYZIRCT> out(std::max<uint32_t>(n, 1));
+    uint32_t m = 0;
+    check(bev_voxel_grid_irct(bevhost_context(), n ? reinterpret_cast<const bev_point_t *>(m_in->points.data()) : nullptr,
+                              n, m_leaf, reinterpret_cast<bev_point_t *>(out.data()), &m),
+          "VoxelGridXYZIRCT::filter");
+    output.points.assign(out.begin(), out.begin() + m);
+    output.width = m;
+    output.height = 1;
+}
+
+IcpAlignResult performFineIcp(pcl::PointCloud<pcl::PointXYZIRCT>::Ptr &full_cloud_1_ds,
+                              pcl::PointCloud<pcl::PointXYZIRCT>::Ptr &full_cloud_2_ds,
+                              pcl::PointCloud<pcl::PointXYZIRCT>::Ptr full_cloud_1_ds_aligned,
+                              const std::array<float, 16> &initial_guess, const bev_icp_params_t &params)
+{
+    bev_icp_result_t r{};
+    const auto &src = full_cloud_1_ds->points;
+    const auto &tgt = full_cloud_2_ds->points;
+    check(bev_icp_point_to_point(bevhost_context(), reinterpret_cast<const bev_point_t *>(src.data()), (uint32_t)src.size(),
+                                 reinterpret_cast<const bev_point_t *>(tgt.data()), (uint32_t)tgt.size(),
+                                 initial_guess.data(), &params, &r),
+          "performFineIcp");
+    if (full_cloud_1_ds_aligned) {
+        const float *T = r.T;
+        full_cloud_1_ds_aligned->points.resize(src.size());
+        for (size_t i = 0; i < src.size(); ++i) {
+            pcl::PointXYZIRCT o = src[i];
+            const float x = o.x, y = o.y, z = o.z;
+            o.x = T[0] * x + (T[1] * y + (T[2] * z + T[3]));
+            o.y = T[4] * x + (T[5] * y + (T[6] * z + T[7]));
+            o.z = T[8] * x + (T[9] * y + (T[10] * z + T[11]));
+            full_cloud_1_ds_aligned->points[i] = o;
+        }
+    }
+    return to_align_result(r);
+}
+
+std::vector<IcpAlignResult> fineRegisterMatches(const std::vector<pcl::PointCloud<pcl::PointXYZIRCT>::Ptr> &clouds,
+                                                const std::vector<MatchResult> &matches,
+                                                const std::vector<CoarseMatch> *coarse, const bev_icp_params_t &params,
+                                                float leaf)
+{
+    std::vector<IcpAlignResult> out(matches.size());
+    if (matches.empty()) return out;
+    if (coarse && coarse->size() != matches.size()) throw std::runtime_error("fineRegisterMatches: one coarse result per match");
+    const size_t F = clouds.size();
+    std::vector<uint64_t> offs(F + 1, 0);
+    for (size_t f = 0; f < F; ++f) offs[f + 1] = offs[f] + (clouds[f] ? clouds[f]->points.size() : 0);
+    void *d_pts = nullptr, *d_coarse = nullptr, *d_best = nullptr, *d_res = nullptr;
+    auto release = [&]() {
+        for (void *p : {d_pts, d_coarse, d_best, d_res})
+            if (p) (void)hipFree(p);
+    };
+    auto hip = [&](hipError_t e, const char *what) {
+        if (e != hipSuccess) {
+            release();
+            throw std::runtime_error(std::string("fineRegisterMatches: ") + what + ": " + hipGetErrorString(e));
+        }
+    };
+    bev_ctx_t *ctx = bevhost_context();
+    hip(hipMalloc(&d_pts, std::max<size_t>(offs[F], 1) * sizeof(bev_point_t)), "hipMalloc");
+    for (size_t f = 0; f < F; ++f)
+        if (offs[f + 1] > offs[f])
+            hip(hipMemcpy(static_cast<bev_point_t *>(d_pts) + offs[f], clouds[f]->points.data(),
+                          (offs[f + 1] - offs[f]) * sizeof(bev_point_t), hipMemcpyHostToDevice),
+                "hipMemcpy");
+    if (coarse) {
+        std::vector<bev_icp_result_t> cr(matches.size() * 2);
+        std::vector<int32_t> best(matches.size());
+        for (size_t m = 0; m < matches.size(); ++m) {
+            for (int g = 0; g < 2; ++g)
+                std::copy((*coarse)[m].results[g].final_transformation.begin(),
+                          (*coarse)[m].results[g].final_transformation.end(), cr[2 * m + g].T);
+            best[m] = (*coarse)[m].best;
+        }
+        hip(hipMalloc(&d_coarse, cr.size() * sizeof(bev_icp_result_t)), "hipMalloc");
+        hip(hipMalloc(&d_best, best.size() * 4), "hipMalloc");
+        hip(hipMemcpy(d_coarse, cr.data(), cr.size() * sizeof(bev_icp_result_t), hipMemcpyHostToDevice), "hipMemcpy");
+        hip(hipMemcpy(d_best, best.data(), best.size() * 4, hipMemcpyHostToDevice), "hipMemcpy");
+    }
+    hip(hipMalloc(&d_res, matches.size() * sizeof(bev_icp_result_t)), "hipMalloc");
+    int rc = bev_fine_registration_device_resident(ctx, (int)F, static_cast<const bev_point_t *>(d_pts), offs.data(), leaf,
+                                                   (int)matches.size(), reinterpret_cast<const bev_match_t *>(matches.data()),
+                                                   static_cast<const bev_icp_result_t *>(d_coarse),
+                                                   static_cast<const int32_t *>(d_best), &params,
+                                                   static_cast<bev_icp_result_t *>(d_res));
+    if (rc == BEV_OK) rc = bev_synchronize(ctx);
+    if (rc != BEV_OK) {
+        release();
+        check(rc, "fineRegisterMatches");
+    }
+    std::vector<bev_icp_result_t> res(matches.size());
+    hip(hipMemcpy(res.data(), d_res, res.size() * sizeof(bev_icp_result_t), hipMemcpyDeviceToHost), "hipMemcpy");
+    release();
+    for (size_t m = 0; m < matches.size(); ++m) out[m] = to_align_result(res[m]);
+    return out;
+}

@@ -10,7 +10,14 @@
  *                                                   device code, so a plain g++ build can use it)
  *   performCoarseIcp       :192-221 (IterativeClosestPointWithNormals, D = 10, 10 iterations)
  *   coarseRegisterMatches  the tool's loop (:415-466): both yaw guesses of every match and the better one, in one batch
- * The contracts are DESIGN.md "Registration front end" (§6b) and "Coarse ICP" (§6c).  The fine stage is not here.
+ * and the fine stage both batch tools end with:
+ *   VoxelGridXYZIRCT       pcl::VoxelGrid<pcl::PointXYZIRCT> (:345-346, 483-487)
+ *   performFineIcp         :224-247 (IterativeClosestPoint<PointXYZIRCT, PointXYZIRCT>, SVD; the top-part tool's
+ *                          settings by default, the whole tool's through bev_icp_whole_defaults())
+ *   fineRegisterMatches    the voxel grids and the fine ICP of every match in one batch (:480-497; the whole tool,
+ *                          BatchWholeRegistration.cpp:372-389, from the yaw guess)
+ *   rotationMatrixToEulerAngles  :290-309
+ * The contracts are DESIGN.md "Registration front end" (§6b), "Coarse ICP" (§6c) and "Fine ICP" (§6d).
  */
 #ifndef BEV_HOST_REGISTRATION_H
 #define BEV_HOST_REGISTRATION_H
@@ -93,5 +100,37 @@ struct CoarseMatch {
 /* the tool's coarse loop over every match at once: clouds[f] is frame f's PointNormal cloud (addNormal's output) */
 std::vector<CoarseMatch> coarseRegisterMatches(const std::vector<pcl::PointCloud<pcl::PointNormal>::Ptr> &clouds,
                                                const std::vector<MatchResult> &matches);
+
+/* pcl::VoxelGrid<pcl::PointXYZIRCT>: setInputCloud, setLeafSize (one size for x, y, z), filter */
+class VoxelGridXYZIRCT {
+public:
+    void setInputCloud(const pcl::PointCloud<pcl::PointXYZIRCT>::Ptr &cloud) { m_in = cloud; }
+    void setLeafSize(float lx, float ly, float lz);
+    void filter(pcl::PointCloud<pcl::PointXYZIRCT> &output) const;
+
+private:
+    pcl::PointCloud<pcl::PointXYZIRCT>::Ptr m_in;
+    float m_leaf = 0.0f;
+};
+
+/* IterativeClosestPoint<PointXYZIRCT, PointXYZIRCT> from initial_guess (row-major) with params (the top-part tool's: D 1,
+ * 1e-6, 0.01, 100 iterations); full_cloud_1_ds_aligned (may be null) receives the source moved by the final
+ * transformation (Transformer::se3) */
+IcpAlignResult performFineIcp(pcl::PointCloud<pcl::PointXYZIRCT>::Ptr &full_cloud_1_ds,
+                              pcl::PointCloud<pcl::PointXYZIRCT>::Ptr &full_cloud_2_ds,
+                              pcl::PointCloud<pcl::PointXYZIRCT>::Ptr full_cloud_1_ds_aligned,
+                              const std::array<float, 16> &initial_guess,
+                              const bev_icp_params_t &params = bev_icp_fine_defaults());
+
+/* the fine stage of every match at once: clouds[f] is frame f's full labelled cloud (null: empty); the voxel grid (leaf)
+ * of every frame named, then ICP from coarse[m]'s better result (the top-part tool) or, with coarse null, from the yaw
+ * guess angle_guess (the whole tool) */
+std::vector<IcpAlignResult> fineRegisterMatches(const std::vector<pcl::PointCloud<pcl::PointXYZIRCT>::Ptr> &clouds,
+                                                const std::vector<MatchResult> &matches,
+                                                const std::vector<CoarseMatch> *coarse, const bev_icp_params_t &params,
+                                                float leaf = 0.2f);
+
+/* rotationMatrixToEulerAngles (:290-309) on a row-major 3 x 3, in float with the host libm: (x, y, z) */
+std::array<float, 3> rotationMatrixToEulerAngles(const std::array<float, 9> &R);
 
 #endif
