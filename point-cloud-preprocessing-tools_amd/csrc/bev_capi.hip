@@ -1,6 +1,6 @@
 /*
- * bev_capi.hip — context, workspace and the extern "C" boundary declared in
- * include/bev_mi355x.h.  Host-side only; the kernels are in bev_kernels.hip.
+ * bev_capi.hip — context (bev_ctx.h), workspace and the extern "C" boundary declared in include/bev_mi355x.h, but for
+ * the registration entry points (bev_capi_reg.hip).  Host-side only; the kernels are in bev_kernels.hip.
  *
  * There is deliberately no CPU implementation behind these entry points: if
  * HIP cannot give us a device, bev_create() fails.
@@ -8,239 +8,21 @@
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
-#include <condition_variable>
-#include <deque>
-#include <mutex>
-#include <thread>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <new>
-#include <string>
-#include <vector>
 
 #include <roctracer/roctx.h>
 
-#include "bev_internal.h"
+#include "bev_ctx.h"
 #include "bev_libm.h"
 #include "bev_libm_f64.h"
 
 using namespace bevk;
+using namespace bevh;
 
-namespace {
-
-constexpr int kDescRing = 4; /* calls the host may run ahead of the device (2 and 12 measured the same) */
-constexpr int kEventPairs = 2048;
-
-struct ProfSlot {
-    hipEvent_t a, b;
-    int kid;
-    int frames;
-};
-
-/* A sub-batch's workspace lives from its column walk to its rasters: four launches of its stream, and two streams take
- * sub-batches in turn (k_stage, see run_pipeline), so eight workspace sets ("lanes", the name rounds 2-5 gave them when
- * each also had a stream) go round.  Lane 0 doubles as
- * the workspace of the single-cloud entry points. */
-constexpr int kMaxStageStreams = 4;
-constexpr int kMaxLanes = 4 * kMaxStageStreams;
-struct Lane {
-    FrameInfo *info = nullptr;  /* per frame: how its points reach their slots (k_probe / k_verdict) */
-    FrameDesc *desc = nullptr;  /* per frame: k_probe's device copy of the caller's descriptor */
-    uint32_t *est = nullptr;    /* stream frames: estimated input position of every (row, strip)'s first slot */
-    uint32_t *tail_list = nullptr, *tail_cnt = nullptr; /* ... and their tail points per (row, strip) (stream mode only) */
-    int32_t *cm_par = nullptr;   /* firing-order frames: direction and row bases (k_probe) */
-    uint32_t *cm_sync = nullptr; /* ... and what their strips tell each other and k_verdict about column 0 */
-    uint32_t *winner = nullptr;
-    uint32_t win_gen = 0; /* generation tag of the last sub-batch that used this set's winner table */
-    uint2 *cand = nullptr; /* candidate key | height */
-    uint32_t *ncand = nullptr;
-    uint32_t *code_main = nullptr, *ncode = nullptr; /* per-(strip, band) lists of final BEV codes */
-    float *avg = nullptr;
-    int8_t *gm = nullptr; /* lazily allocated */
-};
-
-} // namespace
-
-/* Device -> host side of bev_process_batch.  Copies into pageable host memory block the calling thread, so the
- * downloads of chunk k run on their own thread and stream while the main thread uploads and launches chunk k + 1:
- * PCIe is used in both directions at once.  The thread lives as long as the context (it used to be created and joined
- * by every call). */
-struct bev_ctx;
-namespace {
-struct Downloader {
-    struct Task {
-        int f0, nb, half;
-        bev_point_t *const *ordered_out;
-        uint8_t *const *multi_out;
-        uint8_t *const *single_out;
-        int8_t *const *gm_out;
-        int half_frames;
-    };
-    bev_ctx *c = nullptr;
-    std::mutex mu;
-    std::condition_variable cv;
-    std::deque<Task> queue;
-    bool closing = false;
-    int finished = 0; /* chunks of the current call whose outputs are in the caller's buffers */
-    hipError_t err = hipSuccess;
-    std::thread th;
-
-    void run();
-    void start(bev_ctx *ctx)
-    {
-        c = ctx;
-        th = std::thread([this] { run(); });
-    }
-    void begin_call()
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        finished = 0;
-        err = hipSuccess;
-    }
-    void push(Task t)
-    {
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            queue.push_back(t);
-        }
-        cv.notify_all();
-    }
-    void wait_finished(int n)
-    {
-        std::unique_lock<std::mutex> lk(mu);
-        cv.wait(lk, [&] { return finished >= n; });
-    }
-    void close()
-    {
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            closing = true;
-        }
-        cv.notify_all();
-        if (th.joinable()) th.join();
-    }
-};
-} // namespace
-
-struct bev_ctx {
-    int device = -1;
-    bev_params_t params{};
-    Geometry geo{};
-    int max_batch = 0;
-    size_t max_points = 0;
-    int win_shift = 32;  /* bits an input index + 1 needs; the rest of a winner entry is the generation tag */
-    size_t multi_bytes = 0, single_bytes = 0;
-    hipStream_t stream = nullptr;
-
-    /* sub-batch workspace sets; the aliases below are lane 0's */
-    Lane lanes[kMaxLanes];
-    int n_lanes = 8; /* 4 * n_stage_streams */
-    /* fused launches alternate between two streams: sub-batch s on stage_st[s % 2], its workspace set s % 8 (always the
-     * same stream's), its later stages in that stream's next three launches — a launch's tail is filled by the other
-     * stream's launch, and nothing but the order of launches on ONE stream ever orders two stages of one sub-batch */
-    hipStream_t stage_st[kMaxStageStreams] = {};
-    hipEvent_t stage_ev[kMaxStageStreams] = {};
-    hipEvent_t fork_ev = nullptr, null_ev = nullptr;
-    int n_stage_streams = 2;   /* BEV_STAGE_STREAMS=1 .. 4 (1: a launch's tail stands empty; 3, 4: measured like 2, with 12 / 16 workspace sets) */
-    unsigned sub_seq = 0;      /* sub-batches so far */
-    /* fused: a sub-batch's stages ride in consecutive k_stage launches beside the stages of its neighbours (run_pipeline);
-     * serial (BEV_LANES=1, bev_set_lanes(ctx, 1)): every kernel a launch of its own, back to back — per-kernel durations */
-    bool fused = true;
-    int stage_lead = 0;        /* group slots by which a launch's walk workgroups precede its other stages' (0, 4, 12, 24, 32 measured the same) */
-    uint32_t *hint = nullptr;  /* mapped host words (k_verdict): [0] frames of the last verdict's sub-batch that were NOT read in place, [1] the modes k_probe gave its frames (bit = mode) */
-    int mode_absent[8] = {0, 0, 0, 0, 0, 0, 0, 0}; /* looks at hint[1] since it last showed the mode (see run_pipeline) */
-    int mode_ttl = 8;          /* a mode's in-place walk stays launched for this many sub-batches after a verdict last showed the mode (BEV_MODE_TTL) */
-    int layout_hint = 0;       /* bev_set_layout_hint: 0, kFrameStructured or kFrameColMajor */
-    bool allow_stream = true;  /* sorted-prefix frames are read in place (k_probe); BEV_STREAM=0 turns it off, see bev_create */
-    /* sub-batches whose later stages have not been launched yet, oldest first (see run_pipeline / flush_pending) */
-    struct Pending {
-        BatchPtrs b;
-        int nf;
-        bool want_multi, want_single;
-        int8_t *gm_out; /* final ground_mat wanted (device), or nullptr */
-        int next;       /* 1 phase B, 2 phase C, 3 rasters */
-        int q;          /* which of the two streams its stages ride on */
-    };
-    std::deque<Pending> pending;
-    uint32_t *winner = nullptr;
-    uint32_t *codes = nullptr;
-    size_t codes_elems = 0;
-    uint32_t *ctx_tab = nullptr; /* per-context tables (BatchPtrs::ctx_tab) */
-    float *last_avg = nullptr;
-    uint32_t *last_ncode = nullptr;
-    FrameInfo *last_info = nullptr;
-
-    /* frame descriptors: ring of pinned host + device arrays */
-    FrameDesc *h_desc[kDescRing] = {nullptr, nullptr, nullptr, nullptr};
-    FrameDesc *d_desc[kDescRing] = {nullptr, nullptr, nullptr, nullptr}; /* the device's address of h_desc (mapped host memory) */
-    size_t desc_cap[kDescRing] = {0, 0, 0, 0};
-    hipEvent_t desc_done[kDescRing]{};
-    bool desc_used[kDescRing] = {false, false, false, false};
-    int desc_next = 0;
-
-    /* staging for the host-buffer entry points (lazily allocated) */
-    bev_point_t *st_in = nullptr;
-    size_t st_in_elems = 0;
-    bev_point_t *st_ordered = nullptr;
-    uint8_t *st_multi = nullptr, *st_single = nullptr;
-    int8_t *st_gm = nullptr;
-    bool staging_ready = false;
-    hipStream_t dl_stream = nullptr;             /* device -> host copies of bev_process_batch (own host thread) */
-    Downloader *downloader = nullptr;            /* that thread, started with the staging buffers */
-    hipEvent_t out_ready[2] = {nullptr, nullptr}; /* per half of the output staging: its chunk has been computed */
-    /* KITTI projection workspace, one allocation made on first use and grown on demand */
-    void *kitti_buf = nullptr;
-    size_t kitti_points = 0;
-
-    /* registration front end (bev_registration_front_device_resident & co.): one allocation on first use, max_batch frames
-     * of max(max_points, S) points; the offsets of packed clouds go up through a pinned array, reused once rf_offs_ev has
-     * passed */
-    void *rf_buf = nullptr;
-    RfWork rf{};
-    float *rf_nrm = nullptr; /* P pcl::Normal records: bev_normals_2d's output */
-    uint64_t *rf_h_offs = nullptr, *rf_d_offs = nullptr;
-    size_t rf_offs_cap = 0;
-    hipEvent_t rf_offs_ev = nullptr;
-    hipEvent_t rf_tail_ev = nullptr; /* recorded behind the last chain: the next BEV call's stage streams wait for it */
-    bool rf_tail_pending = false;
-
-    /* coarse ICP (bev_coarse_registration_device_resident & co.): one device allocation for the grids and the transformed
-     * clouds, grown on demand; the problem tables go up through a pinned array, reused once icp_tab_ev has passed */
-    void *icp_buf = nullptr;
-    size_t icp_cap = 0;
-    void *icp_tab = nullptr, *icp_h_tab = nullptr;
-    size_t icp_tab_cap = 0;
-    hipEvent_t icp_tab_ev = nullptr;
-    void *icp_one = nullptr; /* bev_icp_point_to_plane: both clouds, their counts, the result */
-    size_t icp_one_cap = 0;
-    hipEvent_t icp_tail_ev = nullptr; /* recorded behind the last batched ICP: the next BEV call waits for it */
-    bool icp_tail_pending = false;
-
-    /* fine stage (bev_fine_registration_device_resident & co.): one device allocation for the voxel clouds, grids and
-     * transformed clouds, grown on demand; host clouds of the per-cloud entries go through fine_in; the tables go up
-     * through a pinned array, reused once fine_tab_ev has passed.  The batched entry's tail is icp_tail_ev. */
-    void *fine_buf = nullptr;
-    size_t fine_cap = 0;
-    void *fine_in = nullptr;
-    size_t fine_in_cap = 0;
-    void *fine_tab = nullptr, *fine_h_tab = nullptr;
-    size_t fine_tab_cap = 0;
-    hipEvent_t fine_tab_ev = nullptr;
-
-    /* profiling */
-    bool prof_on = false;
-    std::vector<ProfSlot> prof_pool;
-    size_t prof_used = 0;
-    double prof_ms[K_COUNT]{};
-    uint64_t prof_launches[K_COUNT]{};
-    uint64_t prof_frames[K_COUNT]{};
-
-    int last_sub_frames = 0;
-    std::string last_error;
-};
-
-namespace {
+namespace bevh {
 void Downloader::run()
 {
     (void)hipSetDevice(c->device);
@@ -284,23 +66,18 @@ void Downloader::run()
         cv.notify_all();
     }
 }
-} // namespace
 
-namespace {
-
-int hip_fail(bev_ctx *c, hipError_t e, const char *what, int line)
+int hip_fail(bev_ctx *c, hipError_t e, const char *what, int line, const char *file)
 {
+    const char *base = strrchr(file, '/');
     char buf[256];
-    snprintf(buf, sizeof buf, "%s failed at bev_capi.hip:%d: %s", what, line, hipGetErrorString(e));
+    snprintf(buf, sizeof buf, "%s failed at %s:%d: %s", what, base ? base + 1 : file, line, hipGetErrorString(e));
     if (c) c->last_error = buf;
     return e == hipErrorOutOfMemory ? BEV_ERR_OOM : BEV_ERR_HIP;
 }
+} // namespace bevh
 
-#define HIPCK(ctx, expr)                                                   \
-    do {                                                                   \
-        hipError_t e_ = (expr);                                            \
-        if (e_ != hipSuccess) return hip_fail((ctx), e_, #expr, __LINE__); \
-    } while (0)
+namespace {
 
 int mat_size_of(const bev_params_t *p)
 {
@@ -391,26 +168,25 @@ struct RoctxRange {
     ~RoctxRange() { roctxRangePop(); }
 };
 
-struct ProfScope {
-    bev_ctx *c;
-    ProfSlot *s = nullptr;
-    hipStream_t st;
-    ProfScope(bev_ctx *ctx, int kid, int frames, hipStream_t stream = nullptr) : c(ctx), st(stream ? stream : ctx->stream)
-    {
-        if (!c->prof_on) return;
-        if (c->prof_used == c->prof_pool.size()) {
-            if (prof_flush(c) != BEV_OK) return;
-        }
-        s = &c->prof_pool[c->prof_used++];
-        s->kid = kid;
-        s->frames = frames;
-        (void)hipEventRecord(s->a, st);
+} // namespace
+
+bevh::ProfScope::ProfScope(bev_ctx *ctx, int kid, int frames, hipStream_t stream) : c(ctx), st(stream ? stream : ctx->stream)
+{
+    if (!c->prof_on) return;
+    if (c->prof_used == c->prof_pool.size()) {
+        if (prof_flush(c) != BEV_OK) return;
     }
-    ~ProfScope()
-    {
-        if (s) (void)hipEventRecord(s->b, st);
-    }
-};
+    s = &c->prof_pool[c->prof_used++];
+    s->kid = kid;
+    s->frames = frames;
+    (void)hipEventRecord(s->a, st);
+}
+bevh::ProfScope::~ProfScope()
+{
+    if (s) (void)hipEventRecord(s->b, st);
+}
+
+namespace {
 
 /* ---- frame descriptors -------------------------------------------------- */
 int acquire_desc(bev_ctx *c, size_t n, int *slot_out)
@@ -498,8 +274,10 @@ int join_stage_streams(bev_ctx *c)
     }
     return BEV_OK;
 }
+} // namespace
+
 /* launches what is left of every pending sub-batch: up to three launches without a walk per stream; then joins */
-int flush_pending(bev_ctx *c)
+int bevh::flush_pending(bev_ctx *c)
 {
     while (!c->pending.empty()) {
         for (int q = 0; q < kMaxStageStreams; ++q) {
@@ -520,6 +298,8 @@ int flush_pending(bev_ctx *c)
     }
     return join_stage_streams(c);
 }
+
+namespace {
 
 /* The whole pipeline on device pointers.  `identity`: d_pts already holds ordered
  * clouds (n_frames * S points) and the order stage is skipped.
@@ -551,13 +331,9 @@ int run_pipeline(bev_ctx *c, int n_frames, const bev_point_t *d_pts, const uint6
         HIPCK(c, hipEventRecord(c->fork_ev, c->stream));
         for (int q = 0; q < kMaxStageStreams; ++q) HIPCK(c, hipStreamWaitEvent(c->stage_st[q], c->fork_ev, 0));
     }
-    if (c->icp_tail_pending) { /* a coarse ICP still running */
-        for (int q = 0; q < kMaxStageStreams; ++q) HIPCK(c, hipStreamWaitEvent(c->stage_st[q], c->icp_tail_ev, 0));
-        c->icp_tail_pending = false;
-    }
-    if (c->rf_tail_pending) { /* a registration front end still reading a cloud this call may overwrite */
-        for (int q = 0; q < kMaxStageStreams; ++q) HIPCK(c, hipStreamWaitEvent(c->stage_st[q], c->rf_tail_ev, 0));
-        c->rf_tail_pending = false;
+    if (c->reg.tail_pending) { /* a batched registration call still running: it may read a cloud this call overwrites */
+        for (int q = 0; q < kMaxStageStreams; ++q) HIPCK(c, hipStreamWaitEvent(c->stage_st[q], c->reg.tail_ev, 0));
+        c->reg.tail_pending = false;
     }
     if (!fork && !identity) {
         /* device pointers from the caller: whatever it has queued on the default stream up to now — the upload or the fill of
@@ -759,8 +535,9 @@ int run_pipeline(bev_ctx *c, int n_frames, const bev_point_t *d_pts, const uint6
     }
     return BEV_OK;
 }
+} // namespace
 
-int ensure_staging(bev_ctx *c)
+int bevh::ensure_staging(bev_ctx *c)
 {
     if (c->staging_ready) return BEV_OK;
     const size_t S = (size_t)c->geo.S;
@@ -779,58 +556,6 @@ int ensure_staging(bev_ctx *c)
     c->staging_ready = true;
     return BEV_OK;
 }
-
-/* workspace of the registration front end (RfWork, bev_internal.h), allocated on first use; the BEV path's is untouched */
-int ensure_rf(bev_ctx *c)
-{
-    if (c->rf_buf) return BEV_OK;
-    const size_t B = (size_t)c->max_batch, P = std::max(c->max_points, (size_t)c->geo.S), Q = P;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t sz[] = {B * P * 8, B * 2 * P * 8, B * kRfCells * 4, B * (kRfCells + 1) * 4, B * (kRfCells + 1) * 4,
-                         B * Q * 16, B * Q * 16, B * Q * 4, B * (Q + 1) * 4, B * sizeof(RfFrameMeta), P * 32};
-    size_t total = 0;
-    for (size_t b : sz) total += al(b);
-    HIPCK(c, hipMalloc(&c->rf_buf, total));
-    char *p = static_cast<char *>(c->rf_buf);
-    void **dst[] = {(void **)&c->rf.keys, (void **)&c->rf.scr, (void **)&c->rf.cell_cnt, (void **)&c->rf.cell_off,
-                    (void **)&c->rf.out_off, (void **)&c->rf.flat, (void **)&c->rf.vpts, (void **)&c->rf.vidx,
-                    (void **)&c->rf.vstart, (void **)&c->rf.meta, (void **)&c->rf_nrm};
-    for (size_t i = 0; i < sizeof(sz) / sizeof(sz[0]); ++i) {
-        *dst[i] = p;
-        p += al(sz[i]);
-    }
-    c->rf.P = P;
-    c->rf.Q = Q;
-    HIPCK(c, hipEventCreateWithFlags(&c->rf_offs_ev, hipEventDisableTiming));
-    HIPCK(c, hipEventCreateWithFlags(&c->rf_tail_ev, hipEventDisableTiming));
-    return BEV_OK;
-}
-
-/* the chain on nf <= max_batch frames of the workspace: top part -> voxel grid -> normals (PointNormal at out) */
-int rf_chain(bev_ctx *c, const RfIn &in, int nf, float leaf, float radius, const float vp[2], uint32_t n_max, float *out,
-             size_t out_stride, uint32_t *counts)
-{
-    {
-        ProfScope ps(c, K_RF_CELLS, nf);
-        launch_rf_top(in, c->rf, nf, c->stream, 0);
-    }
-    {
-        ProfScope ps(c, K_RF_TOP, nf);
-        launch_rf_top(in, c->rf, nf, c->stream, 1);
-    }
-    {
-        ProfScope ps(c, K_RF_VOXEL, nf);
-        launch_rf_voxel(c->rf, nf, leaf, counts, c->stream);
-    }
-    {
-        ProfScope ps(c, K_RF_NORMALS, nf);
-        launch_rf_normals(c->rf, nf, bev_regfront_max_out(n_max), radius, leaf, vp, true, out, out_stride, c->stream);
-    }
-    HIPCK(c, hipGetLastError());
-    return BEV_OK;
-}
-
-} // namespace
 
 /* ======================================================================== */
 extern "C" {
@@ -1036,22 +761,14 @@ void bev_destroy(bev_ctx_t *c)
     if (c->dl_stream) (void)hipStreamDestroy(c->dl_stream);
     for (auto e : c->out_ready)
         if (e) (void)hipEventDestroy(e);
-    void *dev[] = {c->st_in, c->st_ordered, c->st_multi, c->st_single, c->st_gm, c->kitti_buf, c->codes, c->ctx_tab, c->rf_buf, c->rf_d_offs,
-                   c->icp_buf, c->icp_tab, c->icp_one, c->fine_buf, c->fine_in, c->fine_tab};
+    void *dev[] = {c->st_in, c->st_ordered, c->st_multi, c->st_single, c->st_gm, c->kitti_buf, c->codes, c->ctx_tab};
     for (void *p : dev)
         if (p) (void)hipFree(p);
     for (int k = 0; k < kDescRing; ++k) {
         if (c->h_desc[k]) (void)hipHostFree(c->h_desc[k]);
         if (c->desc_done[k]) (void)hipEventDestroy(c->desc_done[k]);
     }
-    if (c->rf_h_offs) (void)hipHostFree(c->rf_h_offs);
-    if (c->rf_offs_ev) (void)hipEventDestroy(c->rf_offs_ev);
-    if (c->rf_tail_ev) (void)hipEventDestroy(c->rf_tail_ev);
-    if (c->icp_h_tab) (void)hipHostFree(c->icp_h_tab);
-    if (c->icp_tab_ev) (void)hipEventDestroy(c->icp_tab_ev);
-    if (c->icp_tail_ev) (void)hipEventDestroy(c->icp_tail_ev);
-    if (c->fine_h_tab) (void)hipHostFree(c->fine_h_tab);
-    if (c->fine_tab_ev) (void)hipEventDestroy(c->fine_tab_ev);
+    c->reg.release();
     for (auto &s : c->prof_pool) {
         if (s.a) (void)hipEventDestroy(s.a);
         if (s.b) (void)hipEventDestroy(s.b);
@@ -1288,10 +1005,10 @@ namespace {
 int kitti_workspace(bev_ctx *c, uint32_t n, KittiWork &w)
 {
     const size_t blocks = ((size_t)n + bevx::kKittiBlock - 1) / bevx::kKittiBlock;
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o_col = up(sizeof(KittiHeader)), o_cnt = o_col + up((size_t)n * 4), o_pos = o_cnt + up(blocks * 4),
-                 o_win = o_pos + up(blocks * bevx::kKittiListCap * 4),
-                 total = o_win + up((size_t)bevx::kKittiRows * bevx::kKittiCols * 4);
+    const size_t sz[] = {sizeof(KittiHeader), (size_t)n * 4, blocks * 4, blocks * bevx::kKittiListCap * 4,
+                         (size_t)bevx::kKittiRows * bevx::kKittiCols * 4};
+    void **const dst[] = {(void **)&w.hdr, (void **)&w.col, (void **)&w.cnt, (void **)&w.pos, (void **)&w.winner};
+    const size_t total = carve(nullptr, sz, dst);
     if (n > c->kitti_points || !c->kitti_buf) {
         if (c->kitti_buf) HIPCK(c, hipFree(c->kitti_buf));
         c->kitti_buf = nullptr;
@@ -1305,12 +1022,7 @@ int kitti_workspace(bev_ctx *c, uint32_t n, KittiWork &w)
         HIPCK(c, e);
         c->kitti_points = n;
     }
-    char *base = static_cast<char *>(c->kitti_buf);
-    w.hdr = reinterpret_cast<KittiHeader *>(base);
-    w.col = reinterpret_cast<int32_t *>(base + o_col);
-    w.cnt = reinterpret_cast<uint32_t *>(base + o_cnt);
-    w.pos = reinterpret_cast<uint32_t *>(base + o_pos);
-    w.winner = reinterpret_cast<uint32_t *>(base + o_win);
+    carve(c->kitti_buf, sz, dst);
     return BEV_OK;
 }
 } // namespace
@@ -1428,600 +1140,6 @@ void bev_yaw_translate_matrix(float tx, float ty, float tz, float yaw_deg, float
     m[0] = c;    m[1] = 0.0f - s; m[2] = 0.0f;  m[3] = tx;
     m[4] = s;    m[5] = c;        m[6] = 0.0f;  m[7] = ty;
     m[8] = 0.0f; m[9] = 0.0f;     m[10] = one_minus_c + c; m[11] = tz;
-}
-
-/* ---- registration front end ------------------------------------------------------------------------------------------ */
-size_t bev_regfront_max_out(size_t n) { return n / 5 + 51; }
-
-#define RF_PROLOGUE(c)                                                                                                   \
-    do {                                                                                                                 \
-        HIPCK(c, hipSetDevice(c->device));                                                                               \
-        const int rc_ = flush_pending(c); /* (joins both stage streams into the context's stream) */                    \
-        if (rc_ != BEV_OK) return rc_;                                                                                   \
-        const int rc2_ = ensure_rf(c);                                                                                   \
-        if (rc2_ != BEV_OK) return rc2_;                                                                                 \
-    } while (0)
-
-static bool rf_positive(float v) { return std::isfinite(v) && v > 0.0f; }
-
-int bev_top_part_flatten(bev_ctx_t *c, const bev_point_t *cloud, uint32_t n, float *out, uint32_t *n_out)
-{
-    if (!c || !n_out || (n && (!cloud || !out))) return BEV_ERR_INVALID_ARG;
-    if ((size_t)n > std::max(c->max_points, (size_t)c->geo.S)) return BEV_ERR_TOO_LARGE;
-    *n_out = 0;
-    RF_PROLOGUE(c);
-    if (n == 0) return BEV_OK;
-    int rc = ensure_staging(c);
-    if (rc != BEV_OK) return rc;
-    HIPCK(c, hipMemcpyAsync(c->st_in, cloud, (size_t)n * sizeof(bev_point_t), hipMemcpyHostToDevice, c->stream));
-    RfIn in{c->st_in, nullptr, n, n};
-    {
-        ProfScope ps(c, K_RF_CELLS, 1);
-        launch_rf_top(in, c->rf, 1, c->stream, 0);
-    }
-    {
-        ProfScope ps(c, K_RF_TOP, 1);
-        launch_rf_top(in, c->rf, 1, c->stream, 1);
-    }
-    HIPCK(c, hipGetLastError());
-    RfFrameMeta meta{};
-    HIPCK(c, hipMemcpyAsync(&meta, c->rf.meta, sizeof(meta), hipMemcpyDeviceToHost, c->stream));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    if (meta.m) HIPCK(c, hipMemcpy(out, c->rf.flat, (size_t)meta.m * 16, hipMemcpyDeviceToHost));
-    *n_out = meta.m;
-    return BEV_OK;
-}
-
-int bev_voxel_grid_xyz(bev_ctx_t *c, const float *xyz, uint32_t n, float leaf, float *out, uint32_t *n_out)
-{
-    if (!c || !n_out || (n && (!xyz || !out)) || !rf_positive(leaf)) return BEV_ERR_INVALID_ARG;
-    if ((size_t)n > std::max(c->max_points, (size_t)c->geo.S)) return BEV_ERR_TOO_LARGE;
-    *n_out = 0;
-    RF_PROLOGUE(c);
-    if (n == 0) return BEV_OK;
-    RfFrameMeta meta{};
-    meta.m = n;
-    HIPCK(c, hipMemcpyAsync(c->rf.flat, xyz, (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
-    HIPCK(c, hipMemcpyAsync(c->rf.meta, &meta, sizeof(meta), hipMemcpyHostToDevice, c->stream));
-    {
-        ProfScope ps(c, K_RF_VOXEL, 1);
-        launch_rf_voxel(c->rf, 1, leaf, nullptr, c->stream);
-    }
-    HIPCK(c, hipGetLastError());
-    HIPCK(c, hipMemcpyAsync(&meta, c->rf.meta, sizeof(meta), hipMemcpyDeviceToHost, c->stream));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    if (meta.nv) HIPCK(c, hipMemcpy(out, c->rf.vpts, (size_t)meta.nv * 16, hipMemcpyDeviceToHost));
-    *n_out = meta.nv;
-    return BEV_OK;
-}
-
-int bev_normals_2d(bev_ctx_t *c, const float *xyz, uint32_t n, int k_search, float radius, const float *viewpoint,
-                   float *out)
-{
-    if (!c || (n && (!xyz || !out))) return BEV_ERR_INVALID_ARG;
-    if (k_search != 0) return BEV_ERR_UNSUPPORTED;
-    if (!rf_positive(radius)) return BEV_ERR_INVALID_ARG;
-    if ((size_t)n > std::max(c->max_points, (size_t)c->geo.S)) return BEV_ERR_TOO_LARGE;
-    RF_PROLOGUE(c);
-    if (n == 0) return BEV_OK;
-    const float vp[2] = {viewpoint ? viewpoint[0] : 0.0f, viewpoint ? viewpoint[1] : 0.0f};
-    RfFrameMeta meta{};
-    meta.m = meta.nv = n;
-    meta.windowed = 0; /* any order: every point is scanned */
-    HIPCK(c, hipMemcpyAsync(c->rf.vpts, xyz, (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
-    HIPCK(c, hipMemcpyAsync(c->rf.meta, &meta, sizeof(meta), hipMemcpyHostToDevice, c->stream));
-    {
-        ProfScope ps(c, K_RF_NORMALS, 1);
-        launch_rf_normals(c->rf, 1, n, radius, 0.0f, vp, false, c->rf_nrm, 0, c->stream);
-    }
-    HIPCK(c, hipGetLastError());
-    HIPCK(c, hipMemcpyAsync(out, c->rf_nrm, (size_t)n * 32, hipMemcpyDeviceToHost, c->stream));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    return BEV_OK;
-}
-
-int bev_registration_front_device_resident(bev_ctx_t *c, int n_frames, const bev_point_t *d_clouds,
-                                           const uint64_t *h_offsets, float leaf, float radius, const float *viewpoint,
-                                           void *d_out, size_t out_stride, uint32_t *d_counts)
-{
-    if (!c || n_frames < 0 || !rf_positive(leaf) || !rf_positive(radius)) return BEV_ERR_INVALID_ARG;
-    if (n_frames > 0 && (!d_clouds || !d_out || !d_counts)) return BEV_ERR_INVALID_ARG;
-    const size_t P = std::max(c->max_points, (size_t)c->geo.S);
-    uint32_t n_max = (uint32_t)c->geo.S;
-    if (h_offsets) {
-        n_max = 0;
-        for (int f = 0; f < n_frames; ++f) {
-            if (h_offsets[f + 1] < h_offsets[f] || h_offsets[f + 1] - h_offsets[f] > P) return BEV_ERR_TOO_LARGE;
-            n_max = std::max(n_max, (uint32_t)(h_offsets[f + 1] - h_offsets[f]));
-        }
-    }
-    if (n_frames > 0 && out_stride < bev_regfront_max_out(n_max)) return BEV_ERR_INVALID_ARG;
-    RF_PROLOGUE(c);
-    if (n_frames == 0) return BEV_OK;
-    /* the caller's default-stream work (the upload of packed clouds, typically) comes first */
-    HIPCK(c, hipEventRecord(c->null_ev, nullptr));
-    HIPCK(c, hipStreamWaitEvent(c->stream, c->null_ev, 0));
-    if (h_offsets) {
-        HIPCK(c, hipEventSynchronize(c->rf_offs_ev)); /* the last call's offsets have gone up */
-        if (c->rf_offs_cap < (size_t)n_frames + 1) {
-            HIPCK(c, hipStreamSynchronize(c->stream)); /* (kernels of the last call may still read rf_d_offs) */
-            if (c->rf_h_offs) HIPCK(c, hipHostFree(c->rf_h_offs));
-            if (c->rf_d_offs) HIPCK(c, hipFree(c->rf_d_offs));
-            c->rf_h_offs = nullptr;
-            c->rf_d_offs = nullptr;
-            c->rf_offs_cap = 0;
-            const size_t cap = std::max((size_t)n_frames + 1, (size_t)1024);
-            HIPCK(c, hipHostMalloc((void **)&c->rf_h_offs, cap * 8, hipHostMallocDefault));
-            HIPCK(c, hipMalloc((void **)&c->rf_d_offs, cap * 8));
-            c->rf_offs_cap = cap;
-        }
-        std::memcpy(c->rf_h_offs, h_offsets, ((size_t)n_frames + 1) * 8);
-        HIPCK(c, hipMemcpyAsync(c->rf_d_offs, c->rf_h_offs, ((size_t)n_frames + 1) * 8, hipMemcpyHostToDevice, c->stream));
-        HIPCK(c, hipEventRecord(c->rf_offs_ev, c->stream));
-    }
-    const float vp[2] = {viewpoint ? viewpoint[0] : 0.0f, viewpoint ? viewpoint[1] : 0.0f};
-    for (int f0 = 0; f0 < n_frames; f0 += c->max_batch) {
-        const int nf = std::min(c->max_batch, n_frames - f0);
-        RfIn in{};
-        if (h_offsets) {
-            in.pts = d_clouds;
-            in.offs = c->rf_d_offs + f0;
-        } else {
-            in.pts = d_clouds + (size_t)f0 * c->geo.S;
-            in.stride = (size_t)c->geo.S;
-            in.n_uniform = (uint32_t)c->geo.S;
-        }
-        int rc = rf_chain(c, in, nf, leaf, radius, vp, n_max, static_cast<float *>(d_out) + (size_t)f0 * out_stride * 12,
-                          out_stride, d_counts + f0);
-        if (rc != BEV_OK) return rc;
-    }
-    HIPCK(c, hipEventRecord(c->rf_tail_ev, c->stream));
-    c->rf_tail_pending = true;
-    return BEV_OK;
-}
-#undef RF_PROLOGUE
-
-/* ---- coarse point-to-plane ICP --------------------------------------------------------------------------------------- */
-bev_icp_params_t bev_icp_coarse_defaults(void)
-{
-    bev_icp_params_t p{};
-    p.max_correspondence_distance = 10.0; /* icp.setMaxCorrespondenceDistance(10.0f) */
-    p.max_iterations = 10;                /* icp.setMaximumIterations(10) */
-    p.transformation_epsilon = 0.0;
-    p.euclidean_fitness_epsilon = -DBL_MAX;
-    return p;
-}
-
-static bool icp_params_ok(const bev_icp_params_t &p)
-{
-    return p.max_iterations >= 1 && p.max_iterations <= 1000 && std::isfinite(p.max_correspondence_distance) &&
-           p.max_correspondence_distance > 0.0;
-}
-
-namespace {
-
-/* the grids of the target frames slot_frames, then every problem (launches of kIcpProblemsPerLaunch), then, when d_best is
- * set, the better guess of each of the n_best matches; all on the context's stream */
-int icp_launch(bev_ctx *c, const float *d_pn, size_t stride, const uint32_t *d_counts,
-               const std::vector<IcpProblem> &probs, const std::vector<uint32_t> &slot_frames,
-               const bev_icp_params_t &prm, bev_icp_result_t *d_res, int n_best, int32_t *d_best)
-{
-    const size_t U = slot_frames.size(), P = probs.size(), L = std::min(P, (size_t)kIcpProblemsPerLaunch);
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t sz[] = {U * sizeof(IcpGridHdr), U * 4 * (size_t)(kIcpCells + 1), U * 16 * stride, L * 16 * stride};
-    size_t need = 0;
-    for (size_t b : sz) need += al(b);
-    if (need > c->icp_cap) {
-        HIPCK(c, hipStreamSynchronize(c->stream)); /* (the last call's kernels may still use it) */
-        if (c->icp_buf) HIPCK(c, hipFree(c->icp_buf));
-        c->icp_buf = nullptr;
-        c->icp_cap = 0;
-        HIPCK(c, hipMalloc(&c->icp_buf, need));
-        c->icp_cap = need;
-    }
-    IcpWork w{};
-    char *p = static_cast<char *>(c->icp_buf);
-    void **dst[] = {(void **)&w.hdr, (void **)&w.cell_off, (void **)&w.sorted, (void **)&w.cur};
-    for (size_t i = 0; i < 4; ++i) {
-        *dst[i] = p;
-        p += al(sz[i]);
-    }
-    const size_t tab = al(P * sizeof(IcpProblem)) + U * 4;
-    if (!c->icp_tab_ev) HIPCK(c, hipEventCreateWithFlags(&c->icp_tab_ev, hipEventDisableTiming));
-    else HIPCK(c, hipEventSynchronize(c->icp_tab_ev)); /* the last call's tables have gone up */
-    if (tab > c->icp_tab_cap) {
-        HIPCK(c, hipStreamSynchronize(c->stream));
-        if (c->icp_h_tab) HIPCK(c, hipHostFree(c->icp_h_tab));
-        if (c->icp_tab) HIPCK(c, hipFree(c->icp_tab));
-        c->icp_h_tab = c->icp_tab = nullptr;
-        c->icp_tab_cap = 0;
-        const size_t cap = std::max(tab, (size_t)1 << 16);
-        HIPCK(c, hipHostMalloc(&c->icp_h_tab, cap, hipHostMallocDefault));
-        HIPCK(c, hipMalloc(&c->icp_tab, cap));
-        c->icp_tab_cap = cap;
-    }
-    char *h = static_cast<char *>(c->icp_h_tab);
-    std::memcpy(h, probs.data(), P * sizeof(IcpProblem));
-    std::memcpy(h + al(P * sizeof(IcpProblem)), slot_frames.data(), U * 4);
-    HIPCK(c, hipMemcpyAsync(c->icp_tab, c->icp_h_tab, tab, hipMemcpyHostToDevice, c->stream));
-    HIPCK(c, hipEventRecord(c->icp_tab_ev, c->stream));
-    const IcpProblem *d_probs = static_cast<const IcpProblem *>(c->icp_tab);
-    const uint32_t *d_slots = reinterpret_cast<const uint32_t *>(static_cast<char *>(c->icp_tab) + al(P * sizeof(IcpProblem)));
-    {
-        ProfScope ps(c, K_ICP_GRID, (int)U);
-        launch_icp_grid(d_pn, stride, d_counts, d_slots, (int)U, w, c->stream);
-    }
-    for (size_t p0 = 0; p0 < P; p0 += kIcpProblemsPerLaunch) {
-        const int n = (int)std::min((size_t)kIcpProblemsPerLaunch, P - p0);
-        ProfScope ps(c, K_ICP, n);
-        launch_icp(d_pn, stride, d_counts, d_probs + p0, n, w, prm, d_res, c->stream);
-    }
-    if (d_best) {
-        ProfScope ps(c, K_ICP_BEST, n_best);
-        launch_icp_best(d_res, n_best, d_best, c->stream);
-    }
-    HIPCK(c, hipGetLastError());
-    return BEV_OK;
-}
-
-} // namespace
-
-int bev_icp_point_to_plane(bev_ctx_t *c, const float *src, uint32_t n_src, const float *tgt, uint32_t n_tgt,
-                           const float *guess16, const bev_icp_params_t *params, bev_icp_result_t *result)
-{
-    const bev_icp_params_t prm = params ? *params : bev_icp_coarse_defaults();
-    if (!c || !result || (n_src && !src) || (n_tgt && !tgt) || !icp_params_ok(prm)) return BEV_ERR_INVALID_ARG;
-    HIPCK(c, hipSetDevice(c->device));
-    int rc = flush_pending(c);
-    if (rc != BEV_OK) return rc;
-    const size_t stride = std::max<size_t>(std::max(n_src, n_tgt), 1);
-    const size_t need = 2 * stride * 48 + 256 + sizeof(bev_icp_result_t);
-    if (need > c->icp_one_cap) {
-        HIPCK(c, hipStreamSynchronize(c->stream));
-        if (c->icp_one) HIPCK(c, hipFree(c->icp_one));
-        c->icp_one = nullptr;
-        c->icp_one_cap = 0;
-        HIPCK(c, hipMalloc(&c->icp_one, need));
-        c->icp_one_cap = need;
-    }
-    char *d = static_cast<char *>(c->icp_one);
-    float *d_pn = reinterpret_cast<float *>(d);
-    uint32_t *d_counts = reinterpret_cast<uint32_t *>(d + 2 * stride * 48);
-    bev_icp_result_t *d_res = reinterpret_cast<bev_icp_result_t *>(d + 2 * stride * 48 + 256);
-    const uint32_t counts[2] = {n_src, n_tgt};
-    if (n_src) HIPCK(c, hipMemcpyAsync(d_pn, src, (size_t)n_src * 48, hipMemcpyHostToDevice, c->stream));
-    if (n_tgt) HIPCK(c, hipMemcpyAsync(d_pn + stride * 12, tgt, (size_t)n_tgt * 48, hipMemcpyHostToDevice, c->stream));
-    HIPCK(c, hipMemcpyAsync(d_counts, counts, sizeof(counts), hipMemcpyHostToDevice, c->stream));
-    std::vector<IcpProblem> probs(1);
-    probs[0].src_frame = 0;
-    probs[0].tgt_frame = 1;
-    probs[0].tgt_slot = 0;
-    probs[0].result = 0;
-    for (int k = 0; k < 16; ++k) probs[0].guess[k] = guess16 ? guess16[k] : (k % 5 == 0 ? 1.0f : 0.0f);
-    rc = icp_launch(c, d_pn, stride, d_counts, probs, std::vector<uint32_t>{1u}, prm, d_res, 0, nullptr);
-    if (rc != BEV_OK) return rc;
-    HIPCK(c, hipMemcpyAsync(result, d_res, sizeof(bev_icp_result_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    return BEV_OK;
-}
-
-int bev_coarse_registration_device_resident(bev_ctx_t *c, int n_frames, const void *d_pn, size_t stride,
-                                            const uint32_t *d_counts, int n_matches, const bev_match_t *h_matches,
-                                            const bev_icp_params_t *params, bev_icp_result_t *d_results,
-                                            int32_t *d_best)
-{
-    const bev_icp_params_t prm = params ? *params : bev_icp_coarse_defaults();
-    if (!c || n_frames < 0 || n_matches < 0 || !icp_params_ok(prm)) return BEV_ERR_INVALID_ARG;
-    if (n_matches > 0) {
-        if (!d_pn || !d_counts || !h_matches || !d_results || !d_best || stride == 0) return BEV_ERR_INVALID_ARG;
-        for (int m = 0; m < n_matches; ++m) {
-            const bev_match_t &mt = h_matches[m];
-            if (mt.query_idx < 0 || mt.query_idx >= n_frames || mt.match_idx < 0 || mt.match_idx >= n_frames)
-                return BEV_ERR_INVALID_ARG;
-        }
-    }
-    HIPCK(c, hipSetDevice(c->device));
-    int rc = flush_pending(c); /* (joins both stage streams into the context's stream) */
-    if (rc != BEV_OK) return rc;
-    if (n_matches == 0) return BEV_OK;
-    /* the caller's default-stream work comes first */
-    HIPCK(c, hipEventRecord(c->null_ev, nullptr));
-    HIPCK(c, hipStreamWaitEvent(c->stream, c->null_ev, 0));
-    std::vector<int32_t> slot_of((size_t)n_frames, -1);
-    std::vector<uint32_t> slot_frames;
-    std::vector<IcpProblem> probs((size_t)n_matches * 2);
-    for (int m = 0; m < n_matches; ++m) {
-        const bev_match_t &mt = h_matches[m];
-        if (slot_of[mt.match_idx] < 0) {
-            slot_of[mt.match_idx] = (int32_t)slot_frames.size();
-            slot_frames.push_back((uint32_t)mt.match_idx);
-        }
-        for (int g = 0; g < 2; ++g) {
-            IcpProblem &pb = probs[(size_t)m * 2 + g];
-            pb.src_frame = (uint32_t)mt.query_idx;
-            pb.tgt_frame = (uint32_t)mt.match_idx;
-            pb.tgt_slot = (uint32_t)slot_of[mt.match_idx];
-            pb.result = (uint32_t)(m * 2 + g);
-            bevx::icp_tool_guess(mt.angle_guess, g, pb.guess);
-        }
-    }
-    rc = icp_launch(c, static_cast<const float *>(d_pn), stride, d_counts, probs, slot_frames, prm, d_results, n_matches,
-                    d_best);
-    if (rc != BEV_OK) return rc;
-    if (!c->icp_tail_ev) HIPCK(c, hipEventCreateWithFlags(&c->icp_tail_ev, hipEventDisableTiming));
-    HIPCK(c, hipEventRecord(c->icp_tail_ev, c->stream));
-    c->icp_tail_pending = true;
-    return BEV_OK;
-}
-
-/* ---- fine stage: VoxelGrid<PointXYZIRCT> and point-to-point ICP ------------------------------------------------------ */
-bev_icp_params_t bev_icp_fine_defaults(void)
-{
-    bev_icp_params_t p{};
-    p.max_correspondence_distance = 1.0; /* icp_full.setMaxCorrespondenceDistance(1.0f) (BatchTopPartRegistration.cpp:232) */
-    p.transformation_epsilon = 1e-6;     /* setTransformationEpsilon(1e-6) */
-    p.euclidean_fitness_epsilon = 0.01;  /* setEuclideanFitnessEpsilon(0.01) */
-    p.max_iterations = 100;              /* setMaximumIterations(100) */
-    return p;
-}
-
-bev_icp_params_t bev_icp_whole_defaults(void)
-{
-    bev_icp_params_t p{};
-    p.max_correspondence_distance = 4.0; /* BatchWholeRegistration.cpp:232-235 */
-    p.transformation_epsilon = 1e-6;
-    p.euclidean_fitness_epsilon = 0.001;
-    p.max_iterations = 200;
-    return p;
-}
-
-namespace {
-
-size_t pow2_at_least(size_t n)
-{
-    size_t p = 1;
-    while (p < n) p <<= 1;
-    return p;
-}
-
-/* the device workspace for U slots of at most Pn records and P problems (grown when a call needs more), the slot and
- * problem tables uploaded behind everything on the context's stream */
-int fine_setup(bev_ctx *c, size_t U, size_t Pn, const std::vector<FineSlot> &slots, const std::vector<FineProblem> &probs,
-               FineWork &w, const FineSlot **d_slots, const FineProblem **d_probs)
-{
-    const size_t P = probs.size(), G = std::min(U, (size_t)kFineVoxelGroup), L = std::min(P, (size_t)kFineProblemsPerLaunch);
-    const size_t Kn = pow2_at_least(Pn);
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t sz[] = {U * Pn * sizeof(bev_point_t), U * 4, G * Kn * 8, G * (Pn + 1) * 4, U * sizeof(IcpGridHdr),
-                         U * 4 * (size_t)(kFineCells + 1), U * Pn * 16, L * Pn * 16, L * Pn * 4};
-    constexpr size_t kParts = sizeof(sz) / sizeof(sz[0]);
-    size_t need = 0;
-    for (size_t b : sz) need += al(b);
-    if (need > c->fine_cap) {
-        HIPCK(c, hipStreamSynchronize(c->stream)); /* (the last call's kernels may still use it) */
-        if (c->fine_buf) HIPCK(c, hipFree(c->fine_buf));
-        c->fine_buf = nullptr;
-        c->fine_cap = 0;
-        HIPCK(c, hipMalloc(&c->fine_buf, need));
-        c->fine_cap = need;
-    }
-    w = FineWork{};
-    char *p = static_cast<char *>(c->fine_buf);
-    void **dst[kParts] = {(void **)&w.vox, (void **)&w.vox_n, (void **)&w.keys, (void **)&w.vstart, (void **)&w.hdr,
-                          (void **)&w.cell_off, (void **)&w.sorted, (void **)&w.cur, (void **)&w.corr};
-    for (size_t i = 0; i < kParts; ++i) {
-        *dst[i] = p;
-        p += al(sz[i]);
-    }
-    w.Pn = Pn;
-    w.Kn = Kn;
-    const size_t tab = al(slots.size() * sizeof(FineSlot)) + P * sizeof(FineProblem);
-    if (!c->fine_tab_ev) HIPCK(c, hipEventCreateWithFlags(&c->fine_tab_ev, hipEventDisableTiming));
-    else HIPCK(c, hipEventSynchronize(c->fine_tab_ev)); /* the last call's tables have gone up */
-    if (tab > c->fine_tab_cap) {
-        HIPCK(c, hipStreamSynchronize(c->stream));
-        if (c->fine_h_tab) HIPCK(c, hipHostFree(c->fine_h_tab));
-        if (c->fine_tab) HIPCK(c, hipFree(c->fine_tab));
-        c->fine_h_tab = c->fine_tab = nullptr;
-        c->fine_tab_cap = 0;
-        const size_t cap = std::max(tab, (size_t)1 << 16);
-        HIPCK(c, hipHostMalloc(&c->fine_h_tab, cap, hipHostMallocDefault));
-        HIPCK(c, hipMalloc(&c->fine_tab, cap));
-        c->fine_tab_cap = cap;
-    }
-    char *h = static_cast<char *>(c->fine_h_tab);
-    if (!slots.empty()) std::memcpy(h, slots.data(), slots.size() * sizeof(FineSlot));
-    if (P) std::memcpy(h + al(slots.size() * sizeof(FineSlot)), probs.data(), P * sizeof(FineProblem));
-    if (tab) HIPCK(c, hipMemcpyAsync(c->fine_tab, c->fine_h_tab, tab, hipMemcpyHostToDevice, c->stream));
-    HIPCK(c, hipEventRecord(c->fine_tab_ev, c->stream));
-    *d_slots = static_cast<const FineSlot *>(c->fine_tab);
-    *d_probs = reinterpret_cast<const FineProblem *>(static_cast<char *>(c->fine_tab) + al(slots.size() * sizeof(FineSlot)));
-    return BEV_OK;
-}
-
-int fine_voxel(bev_ctx *c, const bev_point_t *d_pts, const FineSlot *d_slots, int U, const FineWork &w, float leaf)
-{
-    for (int s0 = 0; s0 < U; s0 += kFineVoxelGroup) {
-        const int n = std::min(kFineVoxelGroup, U - s0);
-        ProfScope ps(c, K_FINE_VOXEL, n);
-        launch_fine_voxel(d_pts, d_slots, s0, n, w, leaf, c->stream);
-    }
-    HIPCK(c, hipGetLastError());
-    return BEV_OK;
-}
-
-int fine_icp(bev_ctx *c, int U, const FineProblem *d_probs, size_t P, const FineWork &w, const bev_icp_result_t *d_coarse,
-             const int32_t *d_best, const bev_icp_params_t &prm, bev_icp_result_t *d_res)
-{
-    {
-        ProfScope ps(c, K_FINE_GRID, U);
-        launch_fine_grid(U, w, c->stream);
-    }
-    for (size_t p0 = 0; p0 < P; p0 += kFineProblemsPerLaunch) {
-        const int n = (int)std::min((size_t)kFineProblemsPerLaunch, P - p0);
-        ProfScope ps(c, K_FINE_ICP, n);
-        launch_fine_icp(d_probs + p0, n, w, d_coarse, d_best, prm, d_res, c->stream);
-    }
-    HIPCK(c, hipGetLastError());
-    return BEV_OK;
-}
-
-/* host records -> c->fine_in (grown on demand) */
-int fine_upload(bev_ctx *c, const bev_point_t *const *clouds, const uint32_t *n, int k, size_t *offs)
-{
-    size_t total = 0;
-    for (int i = 0; i < k; ++i) {
-        offs[i] = total;
-        total += n[i];
-    }
-    const size_t need = std::max<size_t>(total, 1) * sizeof(bev_point_t);
-    if (need > c->fine_in_cap) {
-        HIPCK(c, hipStreamSynchronize(c->stream));
-        if (c->fine_in) HIPCK(c, hipFree(c->fine_in));
-        c->fine_in = nullptr;
-        c->fine_in_cap = 0;
-        HIPCK(c, hipMalloc(&c->fine_in, need));
-        c->fine_in_cap = need;
-    }
-    for (int i = 0; i < k; ++i)
-        if (n[i])
-            HIPCK(c, hipMemcpyAsync(static_cast<bev_point_t *>(c->fine_in) + offs[i], clouds[i], (size_t)n[i] * sizeof(bev_point_t),
-                                    hipMemcpyHostToDevice, c->stream));
-    return BEV_OK;
-}
-
-} // namespace
-
-int bev_voxel_grid_irct(bev_ctx_t *c, const bev_point_t *cloud, uint32_t n, float leaf, bev_point_t *out, uint32_t *n_out)
-{
-    if (!c || !n_out || (n && (!cloud || !out)) || !(std::isfinite(leaf) && leaf > 0.0f)) return BEV_ERR_INVALID_ARG;
-    *n_out = 0;
-    HIPCK(c, hipSetDevice(c->device));
-    int rc = flush_pending(c);
-    if (rc != BEV_OK) return rc;
-    if (n == 0) return BEV_OK;
-    size_t off = 0;
-    rc = fine_upload(c, &cloud, &n, 1, &off);
-    if (rc != BEV_OK) return rc;
-    FineWork w;
-    const FineSlot *d_slots;
-    const FineProblem *d_probs;
-    rc = fine_setup(c, 1, n, std::vector<FineSlot>{FineSlot{0, n, 0}}, std::vector<FineProblem>{}, w, &d_slots, &d_probs);
-    if (rc != BEV_OK) return rc;
-    rc = fine_voxel(c, static_cast<const bev_point_t *>(c->fine_in), d_slots, 1, w, leaf);
-    if (rc != BEV_OK) return rc;
-    uint32_t nv = 0;
-    HIPCK(c, hipMemcpyAsync(&nv, w.vox_n, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    if (nv) HIPCK(c, hipMemcpy(out, w.vox, (size_t)nv * sizeof(bev_point_t), hipMemcpyDeviceToHost));
-    *n_out = nv;
-    return BEV_OK;
-}
-
-int bev_icp_point_to_point(bev_ctx_t *c, const bev_point_t *src, uint32_t n_src, const bev_point_t *tgt, uint32_t n_tgt,
-                           const float *guess16, const bev_icp_params_t *params, bev_icp_result_t *result)
-{
-    const bev_icp_params_t prm = params ? *params : bev_icp_fine_defaults();
-    if (!c || !result || (n_src && !src) || (n_tgt && !tgt) || !icp_params_ok(prm)) return BEV_ERR_INVALID_ARG;
-    HIPCK(c, hipSetDevice(c->device));
-    int rc = flush_pending(c);
-    if (rc != BEV_OK) return rc;
-    const size_t Pn = std::max<size_t>(std::max(n_src, n_tgt), 1);
-    std::vector<FineProblem> probs(1);
-    probs[0].src_slot = 0;
-    probs[0].tgt_slot = 1;
-    probs[0].result = 0;
-    probs[0].coarse_match = 0xffffffffu;
-    for (int k = 0; k < 16; ++k) probs[0].guess[k] = guess16 ? guess16[k] : (k % 5 == 0 ? 1.0f : 0.0f);
-    FineWork w;
-    const FineSlot *d_slots;
-    const FineProblem *d_probs;
-    rc = fine_setup(c, 2, Pn, std::vector<FineSlot>{}, probs, w, &d_slots, &d_probs);
-    if (rc != BEV_OK) return rc;
-    /* the clouds are the "voxel clouds" of slots 0 and 1; the result goes behind them in the sort scratch */
-    const uint32_t counts[2] = {n_src, n_tgt};
-    if (n_src) HIPCK(c, hipMemcpyAsync(w.vox, src, (size_t)n_src * sizeof(bev_point_t), hipMemcpyHostToDevice, c->stream));
-    if (n_tgt) HIPCK(c, hipMemcpyAsync(w.vox + Pn, tgt, (size_t)n_tgt * sizeof(bev_point_t), hipMemcpyHostToDevice, c->stream));
-    HIPCK(c, hipMemcpyAsync(w.vox_n, counts, sizeof(counts), hipMemcpyHostToDevice, c->stream));
-    bev_icp_result_t *d_res = reinterpret_cast<bev_icp_result_t *>(w.keys);
-    rc = fine_icp(c, 2, d_probs, 1, w, nullptr, nullptr, prm, d_res);
-    if (rc != BEV_OK) return rc;
-    HIPCK(c, hipMemcpyAsync(result, d_res, sizeof(bev_icp_result_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    return BEV_OK;
-}
-
-int bev_fine_registration_device_resident(bev_ctx_t *c, int n_frames, const bev_point_t *d_clouds,
-                                          const uint64_t *h_offsets, float leaf, int n_matches,
-                                          const bev_match_t *h_matches, const bev_icp_result_t *d_coarse,
-                                          const int32_t *d_best, const bev_icp_params_t *params,
-                                          bev_icp_result_t *d_results)
-{
-    const bev_icp_params_t prm = params ? *params : bev_icp_fine_defaults();
-    if (!c || n_frames < 0 || n_matches < 0 || !icp_params_ok(prm) || !(std::isfinite(leaf) && leaf > 0.0f) ||
-        (d_coarse == nullptr) != (d_best == nullptr))
-        return BEV_ERR_INVALID_ARG;
-    if (n_matches > 0) {
-        if (!d_clouds || !h_matches || !d_results) return BEV_ERR_INVALID_ARG;
-        for (int m = 0; m < n_matches; ++m) {
-            const bev_match_t &mt = h_matches[m];
-            if (mt.query_idx < 0 || mt.query_idx >= n_frames || mt.match_idx < 0 || mt.match_idx >= n_frames)
-                return BEV_ERR_INVALID_ARG;
-        }
-        if (h_offsets)
-            for (int f = 0; f < n_frames; ++f)
-                if (h_offsets[f + 1] < h_offsets[f] || h_offsets[f + 1] - h_offsets[f] > 0xffffffffull) return BEV_ERR_INVALID_ARG;
-    }
-    HIPCK(c, hipSetDevice(c->device));
-    int rc = flush_pending(c); /* (joins both stage streams into the context's stream) */
-    if (rc != BEV_OK) return rc;
-    if (n_matches == 0) return BEV_OK;
-    /* the caller's default-stream work comes first */
-    HIPCK(c, hipEventRecord(c->null_ev, nullptr));
-    HIPCK(c, hipStreamWaitEvent(c->stream, c->null_ev, 0));
-    std::vector<int32_t> slot_of((size_t)n_frames, -1);
-    std::vector<FineSlot> slots;
-    size_t Pn = 1;
-    auto slot = [&](int f) -> uint32_t {
-        if (slot_of[f] < 0) {
-            slot_of[f] = (int32_t)slots.size();
-            FineSlot s{};
-            if (h_offsets) {
-                s.off = h_offsets[f];
-                s.n = (uint32_t)(h_offsets[f + 1] - h_offsets[f]);
-            } else {
-                s.off = (uint64_t)f * c->geo.S;
-                s.n = (uint32_t)c->geo.S;
-            }
-            Pn = std::max(Pn, (size_t)s.n);
-            slots.push_back(s);
-        }
-        return (uint32_t)slot_of[f];
-    };
-    std::vector<FineProblem> probs((size_t)n_matches);
-    for (int m = 0; m < n_matches; ++m) {
-        const bev_match_t &mt = h_matches[m];
-        FineProblem &pb = probs[(size_t)m];
-        pb.src_slot = slot(mt.query_idx);
-        pb.tgt_slot = slot(mt.match_idx);
-        pb.result = (uint32_t)m;
-        pb.coarse_match = d_coarse ? (uint32_t)m : 0xffffffffu;
-        bevx::icp_tool_guess(mt.angle_guess, 0, pb.guess);
-    }
-    const int U = (int)slots.size();
-    FineWork w;
-    const FineSlot *d_slots;
-    const FineProblem *d_probs;
-    rc = fine_setup(c, (size_t)U, Pn, slots, probs, w, &d_slots, &d_probs);
-    if (rc != BEV_OK) return rc;
-    rc = fine_voxel(c, d_clouds, d_slots, U, w, leaf);
-    if (rc != BEV_OK) return rc;
-    rc = fine_icp(c, U, d_probs, probs.size(), w, d_coarse, d_best, prm, d_results);
-    if (rc != BEV_OK) return rc;
-    if (!c->icp_tail_ev) HIPCK(c, hipEventCreateWithFlags(&c->icp_tail_ev, hipEventDisableTiming));
-    HIPCK(c, hipEventRecord(c->icp_tail_ev, c->stream));
-    c->icp_tail_pending = true;
-    return BEV_OK;
 }
 
 int bev_set_layout_hint(bev_ctx_t *c, int layout)

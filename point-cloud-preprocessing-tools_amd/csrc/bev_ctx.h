@@ -1,0 +1,278 @@
+/*
+ * bev_ctx.h — the context behind bev_ctx_t and what the two files of the C ABI share: bev_capi.hip (the context, the BEV
+ * pipeline and the single-cloud entry points) and bev_capi_reg.hip (the registration entry points).  Private, like
+ * bev_internal.h.  The types live in a named namespace: struct bev_ctx is one type in both translation units.
+ */
+#ifndef BEV_CTX_H
+#define BEV_CTX_H
+
+#include <condition_variable>
+#include <cstring>
+#include <deque>
+#include <mutex>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "bev_internal.h"
+
+struct bev_ctx;
+
+namespace bevh {
+using namespace bevk;
+
+constexpr int kDescRing = 4; /* calls the host may run ahead of the device (2 and 12 measured the same) */
+constexpr int kEventPairs = 2048;
+
+struct ProfSlot {
+    hipEvent_t a, b;
+    int kid;
+    int frames;
+};
+
+/* A sub-batch's workspace lives from its column walk to its rasters: four launches of its stream, and two streams take
+ * sub-batches in turn (k_stage, see run_pipeline), so eight workspace sets ("lanes", the name rounds 2-5 gave them when
+ * each also had a stream) go round.  Lane 0 doubles as
+ * the workspace of the single-cloud entry points. */
+constexpr int kMaxStageStreams = 4;
+constexpr int kMaxLanes = 4 * kMaxStageStreams;
+struct Lane {
+    FrameInfo *info = nullptr;  /* per frame: how its points reach their slots (k_probe / k_verdict) */
+    FrameDesc *desc = nullptr;  /* per frame: k_probe's device copy of the caller's descriptor */
+    uint32_t *est = nullptr;    /* stream frames: estimated input position of every (row, strip)'s first slot */
+    uint32_t *tail_list = nullptr, *tail_cnt = nullptr; /* ... and their tail points per (row, strip) (stream mode only) */
+    int32_t *cm_par = nullptr;   /* firing-order frames: direction and row bases (k_probe) */
+    uint32_t *cm_sync = nullptr; /* ... and what their strips tell each other and k_verdict about column 0 */
+    uint32_t *winner = nullptr;
+    uint32_t win_gen = 0; /* generation tag of the last sub-batch that used this set's winner table */
+    uint2 *cand = nullptr; /* candidate key | height */
+    uint32_t *ncand = nullptr;
+    uint32_t *code_main = nullptr, *ncode = nullptr; /* per-(strip, band) lists of final BEV codes */
+    float *avg = nullptr;
+    int8_t *gm = nullptr; /* lazily allocated */
+};
+
+/* Device -> host side of bev_process_batch.  Copies into pageable host memory block the calling thread, so the
+ * downloads of chunk k run on their own thread and stream while the main thread uploads and launches chunk k + 1:
+ * PCIe is used in both directions at once.  The thread lives as long as the context (it used to be created and joined
+ * by every call). */
+struct Downloader {
+    struct Task {
+        int f0, nb, half;
+        bev_point_t *const *ordered_out;
+        uint8_t *const *multi_out;
+        uint8_t *const *single_out;
+        int8_t *const *gm_out;
+        int half_frames;
+    };
+    bev_ctx *c = nullptr;
+    std::mutex mu;
+    std::condition_variable cv;
+    std::deque<Task> queue;
+    bool closing = false;
+    int finished = 0; /* chunks of the current call whose outputs are in the caller's buffers */
+    hipError_t err = hipSuccess;
+    std::thread th;
+
+    void run();
+    void start(bev_ctx *ctx)
+    {
+        c = ctx;
+        th = std::thread([this] { run(); });
+    }
+    void begin_call()
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        finished = 0;
+        err = hipSuccess;
+    }
+    void push(Task t)
+    {
+        {
+            std::lock_guard<std::mutex> lk(mu);
+            queue.push_back(t);
+        }
+        cv.notify_all();
+    }
+    void wait_finished(int n)
+    {
+        std::unique_lock<std::mutex> lk(mu);
+        cv.wait(lk, [&] { return finished >= n; });
+    }
+    void close()
+    {
+        {
+            std::lock_guard<std::mutex> lk(mu);
+            closing = true;
+        }
+        cv.notify_all();
+        if (th.joinable()) th.join();
+    }
+};
+
+/* ---- what the registration entry points keep between calls (bev_capi_reg.hip) ---- */
+/* a device buffer that grows when a call needs more */
+struct DevBuf {
+    void *p = nullptr;
+    size_t cap = 0;
+    int grow(bev_ctx *c, size_t need); /* (waits for the context's stream first: the last call's kernels may still use it) */
+    void release();
+};
+/* a pinned host block and its device copy: begin() waits until the last call's table has gone up, grows both blocks to
+ * max(bytes, min_cap) where they are smaller and returns the host block to fill; push() sends it up the context's stream */
+struct UploadTable {
+    void *host = nullptr, *dev = nullptr;
+    size_t cap = 0;
+    hipEvent_t ev = nullptr;
+    int begin(bev_ctx *c, size_t bytes, size_t min_cap, void **host_out);
+    int push(bev_ctx *c, size_t bytes);
+    void release();
+};
+struct RegState {
+    /* front end (bev_registration_front_device_resident & co.): one allocation on first use, max_batch frames of
+     * max(max_points, S) points; the offsets of packed clouds go up through rf_offs */
+    DevBuf rf_buf;
+    RfWork rf{};
+    float *rf_nrm = nullptr; /* P pcl::Normal records: bev_normals_2d's output */
+    UploadTable rf_offs;
+    /* coarse ICP (bev_coarse_registration_device_resident & co.): the grids and the transformed clouds; the problem tables;
+     * bev_icp_point_to_plane's two clouds, their counts and the result */
+    DevBuf icp_buf, icp_one;
+    UploadTable icp_tab;
+    /* fine stage (bev_fine_registration_device_resident & co.): the voxel clouds, grids and transformed clouds; the host
+     * clouds of the per-cloud entries; the slot and problem tables */
+    DevBuf fine_buf, fine_in;
+    UploadTable fine_tab;
+    /* Recorded on the context's stream behind the last batched registration call (front end, coarse, fine): the next BEV
+     * call's stage streams wait for it.  One event serves all three: they record on the same stream, so the latest record
+     * covers the earlier ones. */
+    hipEvent_t tail_ev = nullptr;
+    bool tail_pending = false;
+    void release();
+};
+
+} // namespace bevh
+
+struct bev_ctx {
+    int device = -1;
+    bev_params_t params{};
+    bevk::Geometry geo{};
+    int max_batch = 0;
+    size_t max_points = 0;
+    int win_shift = 32;  /* bits an input index + 1 needs; the rest of a winner entry is the generation tag */
+    size_t multi_bytes = 0, single_bytes = 0;
+    hipStream_t stream = nullptr;
+
+    /* sub-batch workspace sets; the aliases below are lane 0's */
+    bevh::Lane lanes[bevh::kMaxLanes];
+    int n_lanes = 8; /* 4 * n_stage_streams */
+    /* fused launches alternate between two streams: sub-batch s on stage_st[s % 2], its workspace set s % 8 (always the
+     * same stream's), its later stages in that stream's next three launches — a launch's tail is filled by the other
+     * stream's launch, and nothing but the order of launches on ONE stream ever orders two stages of one sub-batch */
+    hipStream_t stage_st[bevh::kMaxStageStreams] = {};
+    hipEvent_t stage_ev[bevh::kMaxStageStreams] = {};
+    hipEvent_t fork_ev = nullptr, null_ev = nullptr;
+    int n_stage_streams = 2;   /* BEV_STAGE_STREAMS=1 .. 4 (1: a launch's tail stands empty; 3, 4: measured like 2, with 12 / 16 workspace sets) */
+    unsigned sub_seq = 0;      /* sub-batches so far */
+    /* fused: a sub-batch's stages ride in consecutive k_stage launches beside the stages of its neighbours (run_pipeline);
+     * serial (BEV_LANES=1, bev_set_lanes(ctx, 1)): every kernel a launch of its own, back to back — per-kernel durations */
+    bool fused = true;
+    int stage_lead = 0;        /* group slots by which a launch's walk workgroups precede its other stages' (0, 4, 12, 24, 32 measured the same) */
+    uint32_t *hint = nullptr;  /* mapped host words (k_verdict): [0] frames of the last verdict's sub-batch that were NOT read in place, [1] the modes k_probe gave its frames (bit = mode) */
+    int mode_absent[8] = {0, 0, 0, 0, 0, 0, 0, 0}; /* looks at hint[1] since it last showed the mode (see run_pipeline) */
+    int mode_ttl = 8;          /* a mode's in-place walk stays launched for this many sub-batches after a verdict last showed the mode (BEV_MODE_TTL) */
+    int layout_hint = 0;       /* bev_set_layout_hint: 0, kFrameStructured or kFrameColMajor */
+    bool allow_stream = true;  /* sorted-prefix frames are read in place (k_probe); BEV_STREAM=0 turns it off, see bev_create */
+    /* sub-batches whose later stages have not been launched yet, oldest first (see run_pipeline / flush_pending) */
+    struct Pending {
+        bevk::BatchPtrs b;
+        int nf;
+        bool want_multi, want_single;
+        int8_t *gm_out; /* final ground_mat wanted (device), or nullptr */
+        int next;       /* 1 phase B, 2 phase C, 3 rasters */
+        int q;          /* which of the two streams its stages ride on */
+    };
+    std::deque<Pending> pending;
+    uint32_t *winner = nullptr;
+    uint32_t *codes = nullptr;
+    size_t codes_elems = 0;
+    uint32_t *ctx_tab = nullptr; /* per-context tables (BatchPtrs::ctx_tab) */
+    float *last_avg = nullptr;
+    uint32_t *last_ncode = nullptr;
+    bevk::FrameInfo *last_info = nullptr;
+
+    /* frame descriptors: ring of pinned host + device arrays */
+    bevk::FrameDesc *h_desc[bevh::kDescRing] = {nullptr, nullptr, nullptr, nullptr};
+    bevk::FrameDesc *d_desc[bevh::kDescRing] = {nullptr, nullptr, nullptr, nullptr}; /* the device's address of h_desc (mapped host memory) */
+    size_t desc_cap[bevh::kDescRing] = {0, 0, 0, 0};
+    hipEvent_t desc_done[bevh::kDescRing]{};
+    bool desc_used[bevh::kDescRing] = {false, false, false, false};
+    int desc_next = 0;
+
+    /* staging for the host-buffer entry points (lazily allocated) */
+    bev_point_t *st_in = nullptr;
+    size_t st_in_elems = 0;
+    bev_point_t *st_ordered = nullptr;
+    uint8_t *st_multi = nullptr, *st_single = nullptr;
+    int8_t *st_gm = nullptr;
+    bool staging_ready = false;
+    hipStream_t dl_stream = nullptr;             /* device -> host copies of bev_process_batch (own host thread) */
+    bevh::Downloader *downloader = nullptr;            /* that thread, started with the staging buffers */
+    hipEvent_t out_ready[2] = {nullptr, nullptr}; /* per half of the output staging: its chunk has been computed */
+    /* KITTI projection workspace, one allocation made on first use and grown on demand */
+    void *kitti_buf = nullptr;
+    size_t kitti_points = 0;
+
+    bevh::RegState reg;
+
+    /* profiling */
+    bool prof_on = false;
+    std::vector<bevh::ProfSlot> prof_pool;
+    size_t prof_used = 0;
+    double prof_ms[bevk::K_COUNT]{};
+    uint64_t prof_launches[bevk::K_COUNT]{};
+    uint64_t prof_frames[bevk::K_COUNT]{};
+
+    int last_sub_frames = 0;
+    std::string last_error;
+};
+
+namespace bevh {
+
+/* (file: __FILE__ of the caller) */
+int hip_fail(bev_ctx *c, hipError_t e, const char *what, int line, const char *file = "bev_capi.hip");
+#define HIPCK(ctx, expr)                                                             \
+    do {                                                                             \
+        hipError_t e_ = (expr);                                                      \
+        if (e_ != hipSuccess) return bevh::hip_fail((ctx), e_, #expr, __LINE__, __FILE__); \
+    } while (0)
+
+/* a kernel's events where profiling is on (bev_profile_enable) */
+struct ProfScope {
+    bev_ctx *c;
+    ProfSlot *s = nullptr;
+    hipStream_t st;
+    ProfScope(bev_ctx *ctx, int kid, int frames, hipStream_t stream = nullptr);
+    ~ProfScope();
+};
+
+/* launches what is left of every pending sub-batch, then joins the stage streams into the context's stream */
+int flush_pending(bev_ctx *c);
+int ensure_staging(bev_ctx *c);
+
+inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+/* one allocation in 256-byte aligned pieces: *dst[i] = the piece of sz[i] bytes (base == nullptr: nothing is written);
+ * returns the bytes the pieces take */
+template <size_t N>
+size_t carve(void *base, const size_t (&sz)[N], void **const (&dst)[N])
+{
+    size_t off = 0;
+    for (size_t i = 0; i < N; ++i) {
+        if (base) *dst[i] = static_cast<char *>(base) + off;
+        off += align256(sz[i]);
+    }
+    return off;
+}
+
+} // namespace bevh
+#endif

@@ -1,15 +1,15 @@
 /*
- * bev_fine.h — the fine stage of the registration tools (included by bev_kernels.hip, after bev_regfront.h and
- * bev_icp.h): pcl::VoxelGrid<PointXYZIRCT> on the full labelled clouds and pcl::IterativeClosestPoint<PointXYZIRCT,
- * PointXYZIRCT> (point-to-point, TransformationEstimationSVD) as performFineIcp runs it (BatchTopPartRegistration.cpp:
- * 224-247, 480-497; BatchWholeRegistration.cpp:222-245, 372-389).  The contract every line follows (and
- * tests/fineicp/fine_icp_oracle.c restates) is DESIGN.md §6d.
+ * bev_fine.h — the fine stage of the registration tools (included by bev_kernels.hip after bev_reg_common.h, whose voxel
+ * steps, grid build, search, ordered pass and loop it uses): pcl::VoxelGrid<PointXYZIRCT> on the full labelled clouds and
+ * pcl::IterativeClosestPoint<PointXYZIRCT, PointXYZIRCT> (point-to-point, TransformationEstimationSVD) as performFineIcp
+ * runs it (BatchTopPartRegistration.cpp:224-247, 480-497; BatchWholeRegistration.cpp:222-245, 372-389).  The contract
+ * every line follows (and tests/fineicp/fine_icp_oracle.c restates) is DESIGN.md §6d.
  *
  *   k_fine_voxel  per frame        : bounds, voxel index, a bitonic sort of (voxel index, input index) keys in global
  *                                    scratch, voxel starts, then one lane per voxel: x, y, z, intensity summed in input
  *                                    order, the label vote of AccumulatorLabel
  *   k_fine_grid   per target frame : a uniform 2-D grid of at most kFineGridMax^2 cells over the voxel centroids, a
- *                                    counting sort of the searchable points by cell (the search of bev_icp.h, icp_nn)
+ *                                    counting sort of the searchable points by cell (the search is icp_nn)
  *   k_fine_icp    per match        : the whole loop in one workgroup — pass 1: correspondences, the six coordinate sums,
  *                                    the MSE; pass 2: the nine products of sigma; thread 0: Umeyama through a 3 x 3
  *                                    Jacobi SVD, the increment, convergence — then getFitnessScore
@@ -21,70 +21,29 @@
 
 namespace bevk {
 
+/* a record's position */
+struct FinePts {
+    const bev_point_t *pts;
+    __device__ float3 operator()(uint32_t i) const { return make_float3(pts[i].x, pts[i].y, pts[i].z); }
+};
+
 /* ---- voxel grid on PointXYZIRCT ---------------------------------------------------------------------------------- */
 __global__ __launch_bounds__(kFineThreads) void k_fine_voxel(const bev_point_t *pts, const FineSlot *slots, int slot0,
                                                              FineWork w, float leaf)
 {
-    __shared__ float red[7][kFineThreads / 64];
-    __shared__ uint32_t wave_cnt[kFineThreads / 64];
+    __shared__ float red[7 * kRegWaves];
+    __shared__ uint32_t wave_cnt[kRegWaves];
     __shared__ int s_par[8]; /* overflow, nfin, minb xyz, div xyz */
-    const int g = (int)blockIdx.x, s = slot0 + g, t = (int)threadIdx.x, lane = t & 63, wv = t >> 6;
+    const int g = (int)blockIdx.x, s = slot0 + g, t = (int)threadIdx.x;
     const FineSlot sl = slots[s];
     const bev_point_t *src = pts + sl.off;
     const uint32_t m = sl.n;
     bev_point_t *out = w.vox + (size_t)s * w.Pn;
     uint32_t *vstart = w.vstart + (size_t)g * (w.Pn + 1);
 
-    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-    uint32_t nfin = 0;
-    for (uint32_t i = t; i < m; i += kFineThreads) {
-        const bev_point_t &q = src[i];
-        if (!rf_finite3(q.x, q.y, q.z)) continue;
-        ++nfin;
-        mn[0] = fminf(mn[0], q.x), mn[1] = fminf(mn[1], q.y), mn[2] = fminf(mn[2], q.z);
-        mx[0] = fmaxf(mx[0], q.x), mx[1] = fmaxf(mx[1], q.y), mx[2] = fmaxf(mx[2], q.z);
-    }
-    for (int off = 32; off >= 1; off >>= 1) {
-        for (int d = 0; d < 3; ++d) {
-            mn[d] = fminf(mn[d], __shfl_xor(mn[d], off));
-            mx[d] = fmaxf(mx[d], __shfl_xor(mx[d], off));
-        }
-        nfin += __shfl_xor(nfin, off);
-    }
-    if (lane == 0) {
-        for (int d = 0; d < 3; ++d) {
-            red[d][wv] = mn[d];
-            red[3 + d][wv] = mx[d];
-        }
-        red[6][wv] = __uint_as_float(nfin);
-    }
-    __syncthreads();
+    const FinePts fetch{src};
     const float inv = 1.0f / leaf;
-    if (t == 0) {
-        uint32_t nf = 0;
-        for (int k = 0; k < kFineThreads / 64; ++k) {
-            for (int d = 0; d < 3; ++d) {
-                mn[d] = fminf(mn[d], red[d][k]);
-                mx[d] = fmaxf(mx[d], red[3 + d][k]);
-            }
-            nf += __float_as_uint(red[6][k]);
-        }
-        int overflow = 0;
-        double prod = 1.0;
-        for (int d = 0; d < 3; ++d) {
-            const float e = (mx[d] - mn[d]) * inv;
-            if (!(e < 9.0e18f)) overflow = 1;
-            else prod *= (double)((int64_t)e + 1);
-        }
-        overflow = overflow || prod > 2147483647.0;
-        s_par[0] = overflow;
-        s_par[1] = (int)nf;
-        for (int d = 0; d < 3 && nf && !overflow; ++d) {
-            s_par[2 + d] = (int)floorf(mn[d] * inv);
-            s_par[5 + d] = (int)floorf(mx[d] * inv) - s_par[2 + d] + 1;
-        }
-    }
-    __syncthreads();
+    rf_voxel_bounds(m, fetch, inv, red, s_par);
     const uint32_t nf = (uint32_t)s_par[1];
     if (nf == 0) {
         if (t == 0) w.vox_n[s] = 0;
@@ -95,45 +54,12 @@ __global__ __launch_bounds__(kFineThreads) void k_fine_voxel(const bev_point_t *
         if (t == 0) w.vox_n[s] = m;
         return;
     }
-    const int minb0 = s_par[2], minb1 = s_par[3], minb2 = s_par[4];
-    const uint32_t div0 = (uint32_t)s_par[5], div1 = (uint32_t)s_par[6];
-    const uint32_t mul2 = div0 * div1;
     const uint32_t np2 = rf_pow2(m);
     uint64_t *buf = w.keys + (size_t)g * w.Kn;
-    for (uint32_t i = t; i < np2; i += kFineThreads) {
-        uint64_t key = ~0ull;
-        if (i < m) {
-            const bev_point_t &q = src[i];
-            if (rf_finite3(q.x, q.y, q.z)) {
-                const uint32_t i0 = (uint32_t)(int)(floorf(q.x * inv) - (float)minb0);
-                const uint32_t i1 = (uint32_t)(int)(floorf(q.y * inv) - (float)minb1);
-                const uint32_t i2 = (uint32_t)(int)(floorf(q.z * inv) - (float)minb2);
-                key = ((uint64_t)(i0 + i1 * div0 + i2 * mul2) << 32) | i; /* voxel index modulo 2^32, then input index */
-            }
-        }
-        buf[i] = key;
-    }
-    __syncthreads();
+    rf_voxel_keys(m, np2, fetch, inv, s_par, buf);
     rf_bitonic(buf, np2);
-    uint32_t base = 0;
-    for (uint32_t c0 = 0; c0 < nf; c0 += kFineThreads) {
-        const uint32_t i = c0 + t;
-        const bool start = i < nf && (i == 0 || (buf[i] >> 32) != (buf[i - 1] >> 32));
-        const uint64_t bal = __ballot(start);
-        if (lane == 0) wave_cnt[wv] = (uint32_t)__popcll(bal);
-        __syncthreads();
-        uint32_t before = base;
-        for (int q = 0; q < wv; ++q) before += wave_cnt[q];
-        before += (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
-        if (start) vstart[before] = i;
-        for (int q = 0; q < kFineThreads / 64; ++q) base += wave_cnt[q];
-        __syncthreads();
-    }
-    const uint32_t nv = base;
-    if (t == 0) {
-        vstart[nv] = nf;
-        w.vox_n[s] = nv;
-    }
+    const uint32_t nv = rf_voxel_starts(buf, nf, wave_cnt, vstart, [](uint32_t, uint32_t) {});
+    if (t == 0) w.vox_n[s] = nv;
     __syncthreads();
     /* CentroidPoint<PointXYZIRCT>: AccumulatorXYZ, AccumulatorIntensity (float sums in input order / float(n)) and
      * AccumulatorLabel (std::map<uint32_t, size_t>: the most frequent label, on a tie the smallest as uint32 — the
@@ -185,111 +111,9 @@ __global__ __launch_bounds__(kFineThreads) void k_fine_voxel(const bev_point_t *
 /* ---- the target frames' grids ------------------------------------------------------------------------------------- */
 __global__ __launch_bounds__(kFineThreads) void k_fine_grid(FineWork w)
 {
-    __shared__ uint32_t cnt[kFineCells];
-    __shared__ float red[4][kFineThreads / 64];
-    __shared__ uint32_t part[kFineThreads];
-    __shared__ IcpGridHdr hdr;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int s = (int)blockIdx.x;
-    const uint32_t n = w.vox_n[s];
-    const bev_point_t *pts = w.vox + (size_t)s * w.Pn;
-    float mnx = INFINITY, mny = INFINITY, mxx = -INFINITY, mxy = -INFINITY;
-    for (uint32_t i = tid; i < n; i += kFineThreads) {
-        const bev_point_t &p = pts[i];
-        if (!icp_finite3(p.x, p.y, p.z)) continue;
-        mnx = fminf(mnx, p.x);
-        mny = fminf(mny, p.y);
-        mxx = fmaxf(mxx, p.x);
-        mxy = fmaxf(mxy, p.y);
-    }
-    for (int off = 32; off >= 1; off >>= 1) {
-        mnx = fminf(mnx, __shfl_xor(mnx, off));
-        mny = fminf(mny, __shfl_xor(mny, off));
-        mxx = fmaxf(mxx, __shfl_xor(mxx, off));
-        mxy = fmaxf(mxy, __shfl_xor(mxy, off));
-    }
-    if (lane == 0) {
-        red[0][wave] = mnx;
-        red[1][wave] = mny;
-        red[2][wave] = mxx;
-        red[3][wave] = mxy;
-    }
-    for (int c = tid; c < kFineCells; c += kFineThreads) cnt[c] = 0;
-    __syncthreads();
-    if (tid == 0) {
-        for (int k = 1; k < kFineThreads / 64; ++k) {
-            mnx = fminf(mnx, red[0][k]);
-            mny = fminf(mny, red[1][k]);
-            mxx = fmaxf(mxx, red[2][k]);
-            mxy = fmaxf(mxy, red[3][k]);
-        }
-        IcpGridHdr h{};
-        h.nx = h.ny = 1;
-        h.s = 1.0f;
-        h.inv_s = 0.0f;
-        if (mnx <= mxx) {
-            h.minx = mnx;
-            h.miny = mny;
-            h.mag = fmaxf(fmaxf(fabsf(mnx), fabsf(mxx)), fmaxf(fabsf(mny), fabsf(mxy)));
-            const float ex = mxx - mnx, ey = mxy - mny;
-            const int dim = min(kFineGridMax, max(1, (int)ceilf(sqrtf((float)n))));
-            const float sc = fmaxf(ex, ey) / (float)dim;
-            if (sc > 0.0f && isfinite(sc) && isfinite(1.0f / sc)) {
-                h.s = sc;
-                h.inv_s = 1.0f / sc;
-                h.nx = min(dim, (int)(ex * h.inv_s) + 1);
-                h.ny = min(dim, (int)(ey * h.inv_s) + 1);
-            }
-        }
-        hdr = h;
-    }
-    __syncthreads();
-    const IcpGridHdr h = hdr;
-    for (uint32_t i = tid; i < n; i += kFineThreads) {
-        const bev_point_t &p = pts[i];
-        if (!icp_finite3(p.x, p.y, p.z)) continue;
-        atomicAdd(&cnt[icp_cell(p.y, h.miny, h.inv_s, h.ny) * h.nx + icp_cell(p.x, h.minx, h.inv_s, h.nx)], 1u);
-    }
-    __syncthreads();
-    constexpr int kPer = kFineCells / kFineThreads;
-    const int nc = h.nx * h.ny;
-    uint32_t sum = 0;
-    for (int k = 0; k < kPer; ++k) sum += tid * kPer + k < nc ? cnt[tid * kPer + k] : 0u;
-    part[tid] = sum;
-    __syncthreads();
-    if (tid == 0) {
-        uint32_t run = 0;
-        for (int k = 0; k < kFineThreads; ++k) {
-            const uint32_t v = part[k];
-            part[k] = run;
-            run += v;
-        }
-        hdr.n = run;
-    }
-    __syncthreads();
-    uint32_t *off = w.cell_off + (size_t)s * (kFineCells + 1);
-    uint32_t run = part[tid];
-    for (int k = 0; k < kPer; ++k) {
-        const int c = tid * kPer + k;
-        if (c >= nc) break;
-        const uint32_t v = cnt[c];
-        off[c] = run;
-        cnt[c] = run; /* the cell's cursor */
-        run += v;
-    }
-    if (tid == 0) {
-        off[nc] = hdr.n;
-        w.hdr[s] = hdr;
-    }
-    __syncthreads();
-    float4 *sorted = w.sorted + (size_t)s * w.Pn;
-    for (uint32_t i = tid; i < n; i += kFineThreads) {
-        const bev_point_t &p = pts[i];
-        if (!icp_finite3(p.x, p.y, p.z)) continue;
-        const uint32_t pos =
-            atomicAdd(&cnt[icp_cell(p.y, h.miny, h.inv_s, h.ny) * h.nx + icp_cell(p.x, h.minx, h.inv_s, h.nx)], 1u);
-        sorted[pos] = make_float4(p.x, p.y, p.z, __uint_as_float(i));
-    }
+    reg_grid_build<kFineCells>(w.vox_n[s], FinePts{w.vox + (size_t)s * w.Pn}, w.hdr + s,
+                               w.cell_off + (size_t)s * (kFineCells + 1), w.sorted + (size_t)s * w.Pn);
 }
 
 /* ---- Umeyama through Eigen's JacobiSVD<Matrix3f> ------------------------------------------------ */
@@ -310,8 +134,9 @@ __device__ __forceinline__ float fine_det3(const float *M)
     return (h0 - h1) + h2;
 }
 
-/* sigma (row-major, finite) -> R (row-major): U S V^T with S = diag(1, 1, +-1) */
-__device__ void fine_svd_rotation(const float *sigma, float *R)
+/* sigma (row-major, finite) -> R (row-major): U S V^T with S = diag(1, 1, +-1).  (Inlined by force: left to the cost model,
+ * unrelated edits of k_fine_icp move its register count across the 128 of four waves per SIMD.) */
+__device__ __forceinline__ void fine_svd_rotation(const float *sigma, float *R)
 {
     const float kMin = 1.17549435e-38f, kPrec = 2.0f * 1.1920929e-7f;
     float scale = 0.0f;
@@ -407,76 +232,22 @@ __device__ void fine_svd_rotation(const float *sigma, float *R)
 
 /* ---- the loop ----------------------------------------------------------------------------------------------------- */
 struct FineShared {
-    float slotf[kIcpChunkSlots][9];
-    double slotd[kIcpChunkSlots];
-    uint32_t slot_cnt[kIcpChunkSlots];
-    float totf[9];
-    double totd;
-    uint32_t cnt;
-    int state, iters;
-    float fin[16], inc[16], mean[6];
+    RegSums<9, 1> sums;
+    RegLoop loop;
+    float mean[6];
 };
 
-/* one pass over the source: term(i, tf, td) fills NF floats and one double and returns whether point i counts; totals
- * in sh.totf / sh.totd / sh.cnt.  Chunk c of 64 points is reduced by wave c % 4, so point i is thread i % 256's. */
-template <int NF, class Term>
-__device__ void fine_pass(FineShared &sh, uint32_t n_src, Term term)
+/* thread 0: sigma, the rotation, the translation, then the shared tail */
+__device__ void fine_step(FineShared &sh, const bev_icp_params_t &prm, double mse_sum, double &prev)
 {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint32_t nchunks = (n_src + 63) / 64;
-    float accf = 0.0f;
-    double accd = 0.0;
-    uint32_t count = 0;
-    for (uint32_t base = 0; base < nchunks; base += kIcpChunkSlots) {
-        const uint32_t lim = min(nchunks - base, (uint32_t)kIcpChunkSlots);
-        for (uint32_t c = wave; c < lim; c += kFineThreads / 64) {
-            const uint32_t i = (base + c) * 64 + lane;
-            float tf[NF > 0 ? NF : 1];
-            double td = 0.0;
-#pragma unroll
-            for (int v = 0; v < NF; ++v) tf[v] = 0.0f;
-            const bool hit = i < n_src && term(i, tf, td);
-#pragma unroll
-            for (int off = 32; off >= 1; off >>= 1) {
-#pragma unroll
-                for (int v = 0; v < NF; ++v) tf[v] = tf[v] + __shfl_down(tf[v], off);
-                td = td + __shfl_down(td, off);
-            }
-            const uint32_t hits = (uint32_t)__popcll(__ballot(hit));
-            if (lane == 0) {
-#pragma unroll
-                for (int v = 0; v < NF; ++v) sh.slotf[c][v] = tf[v];
-                sh.slotd[c] = td;
-                sh.slot_cnt[c] = hits;
-            }
-        }
-        __syncthreads();
-        if (tid < NF) {
-            for (uint32_t c = 0; c < lim; ++c) accf = (base + c == 0) ? sh.slotf[c][tid] : accf + sh.slotf[c][tid];
-        } else if (tid == 32) {
-            for (uint32_t c = 0; c < lim; ++c) accd = (base + c == 0) ? sh.slotd[c] : accd + sh.slotd[c];
-        } else if (tid == 63) {
-            for (uint32_t c = 0; c < lim; ++c) count += sh.slot_cnt[c];
-        }
-        __syncthreads();
-    }
-    if (tid < NF) sh.totf[tid] = nchunks ? accf : 0.0f;
-    else if (tid == 32) sh.totd = nchunks ? accd : 0.0;
-    else if (tid == 63) sh.cnt = count;
-    __syncthreads();
-}
-
-/* thread 0: sigma, the rotation, the translation, final = inc * final, the convergence test */
-__device__ void fine_step(FineShared &sh, const bev_icp_params_t &prm, double &prev)
-{
-    const float oon = 1.0f / (float)sh.cnt;
+    const float oon = 1.0f / (float)sh.sums.cnt;
     float sigma[9];
     bool finite = true;
     for (int k = 0; k < 9; ++k) {
-        sigma[k] = oon * sh.totf[k];
+        sigma[k] = oon * sh.sums.totf[k];
         finite = finite && isfinite(sigma[k]);
     }
-    float *I = sh.inc;
+    float *I = sh.loop.inc;
     if (finite) {
         float R[9];
         fine_svd_rotation(sigma, R);
@@ -491,25 +262,7 @@ __device__ void fine_step(FineShared &sh, const bev_icp_params_t &prm, double &p
     I[13] = 0.0f;
     I[14] = 0.0f;
     I[15] = 1.0f;
-    float F[16];
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 4; ++j)
-            F[i * 4 + j] = ((I[i * 4] * sh.fin[j] + I[i * 4 + 1] * sh.fin[4 + j]) + I[i * 4 + 2] * sh.fin[8 + j]) +
-                           I[i * 4 + 3] * sh.fin[12 + j];
-    for (int k = 0; k < 16; ++k) sh.fin[k] = F[k];
-    const int it = ++sh.iters;
-    const double cos_angle = 0.5 * (double)(((I[0] + I[5]) + I[10]) - 1.0f);
-    const double trans2 = (double)((I[3] * I[3] + I[7] * I[7]) + I[11] * I[11]);
-    if (it >= prm.max_iterations) {
-        sh.state = 1; /* ITERATIONS */
-    } else if (cos_angle >= 1.0 - prm.transformation_epsilon && trans2 <= prm.transformation_epsilon) {
-        sh.state = 2; /* TRANSFORM */
-    } else {
-        const double mse = sh.totd / (double)sh.cnt;
-        if (fabs(mse - prev) < 1e-12) sh.state = 3;                                      /* ABS_MSE */
-        else if (fabs(mse - prev) / prev < prm.euclidean_fitness_epsilon) sh.state = 4; /* REL_MSE */
-        else prev = mse;
-    }
+    reg_converge(sh.loop, prm, mse_sum, sh.sums.cnt, prev);
 }
 
 __global__ __launch_bounds__(kFineThreads) void k_fine_icp(const FineProblem *probs, FineWork w,
@@ -535,28 +288,17 @@ __global__ __launch_bounds__(kFineThreads) void k_fine_icp(const FineProblem *pr
     } else {
         for (int k = 0; k < 16; ++k) G[k] = pb.guess[k];
     }
-    if (tid == 0) {
-        sh.state = 0;
-        sh.iters = 0;
-    }
-    if (tid < 16) sh.fin[tid] = G[tid];
-    bool identity = true;
-    for (int k = 0; k < 16; ++k) identity &= G[k] == ((k % 5 == 0) ? 1.0f : 0.0f);
-    for (uint32_t i = tid; i < n_src; i += kFineThreads) {
-        const bev_point_t &p = src[i];
-        const float3 q = identity ? make_float3(p.x, p.y, p.z) : icp_se3(G, p.x, p.y, p.z);
-        cur[i] = make_float4(q.x, q.y, q.z, 0.0f);
-    }
+    reg_start(sh.loop, G, n_src, FinePts{src}, cur);
     __syncthreads();
     const double D2 = prm.max_correspondence_distance * prm.max_correspondence_distance;
     double prev = 1.7976931348623157e308; /* DBL_MAX (thread 0's copy is the one used) */
     while (true) {
         /* pass 1: correspondences, the source and target coordinate sums (float), the MSE (double) */
-        fine_pass<6>(sh, n_src, [&](uint32_t i, float *t, double &td) -> bool {
+        reg_pass<6, 1>(sh.sums, n_src, [&](uint32_t i, float *t, double *td) -> bool {
             const float4 s = cur[i];
             uint32_t j = 0xffffffffu;
             float d;
-            if (!icp_finite3(s.x, s.y, s.z) || !icp_nn(h, toff, tpts, s.x, s.y, s.z, D2, d, j) || !((double)d <= D2)) {
+            if (!finite3(s.x, s.y, s.z) || !icp_nn(h, toff, tpts, s.x, s.y, s.z, D2, d, j) || !((double)d <= D2)) {
                 corr[i] = 0xffffffffu;
                 return false;
             }
@@ -568,24 +310,24 @@ __global__ __launch_bounds__(kFineThreads) void k_fine_icp(const FineProblem *pr
             t[3] = tp.x;
             t[4] = tp.y;
             t[5] = tp.z;
-            td = (double)d;
+            td[0] = (double)d;
             return true;
         });
         if (tid == 0) {
-            if (sh.cnt < 3) {
-                sh.state = 5; /* NO_CORRESPONDENCES */
+            if (sh.sums.cnt < 3) {
+                sh.loop.state = 5; /* NO_CORRESPONDENCES */
             } else {
-                const float oon = 1.0f / (float)sh.cnt;
-                for (int k = 0; k < 6; ++k) sh.mean[k] = sh.totf[k] * oon;
+                const float oon = 1.0f / (float)sh.sums.cnt;
+                for (int k = 0; k < 6; ++k) sh.mean[k] = sh.sums.totf[k] * oon;
             }
         }
         __syncthreads();
-        if (sh.state != 0) break;
-        const double mse_sum = sh.totd;
+        if (sh.loop.state != 0) break;
+        const double mse_sum = sh.sums.totd[0];
         float M[6];
         for (int k = 0; k < 6; ++k) M[k] = sh.mean[k];
-        /* pass 2: sigma's nine products dst_demean[a] * src_demean[b] (float) */
-        fine_pass<9>(sh, n_src, [&](uint32_t i, float *t, double &) -> bool {
+        /* pass 2: sigma's nine products dst_demean[a] * src_demean[b] (float); it counts the same correspondences */
+        reg_pass<9, 0>(sh.sums, n_src, [&](uint32_t i, float *t, double *) -> bool {
             const uint32_t j = corr[i];
             if (j == 0xffffffffu) return false;
             const float4 s = cur[i];
@@ -598,42 +340,12 @@ __global__ __launch_bounds__(kFineThreads) void k_fine_icp(const FineProblem *pr
                 for (int b = 0; b < 3; ++b) t[a * 3 + b] = dd[a] * sd[b];
             return true;
         });
-        if (tid == 0) {
-            sh.totd = mse_sum; /* (pass 2 counted the same correspondences) */
-            fine_step(sh, prm, prev);
-        }
+        if (tid == 0) fine_step(sh, prm, mse_sum, prev);
         __syncthreads();
-        if (sh.state != 0) break;
-        float I[12];
-        for (int k = 0; k < 12; ++k) I[k] = sh.inc[k];
-        for (uint32_t i = tid; i < n_src; i += kFineThreads) {
-            const float4 p = cur[i];
-            const float3 q = icp_se3(I, p.x, p.y, p.z);
-            cur[i] = make_float4(q.x, q.y, q.z, 0.0f);
-        }
+        if (sh.loop.state != 0) break;
+        reg_advance(sh.loop, n_src, cur);
     }
-    float F[16];
-    for (int k = 0; k < 16; ++k) F[k] = sh.fin[k];
-    fine_pass<0>(sh, n_src, [&](uint32_t i, float *, double &td) -> bool {
-        const bev_point_t &p = src[i];
-        const float3 q = icp_se3(F, p.x, p.y, p.z);
-        if (!icp_finite3(q.x, q.y, q.z)) return false;
-        float d;
-        uint32_t j;
-        if (!icp_nn(h, toff, tpts, q.x, q.y, q.z, INFINITY, d, j) || !isfinite(d)) return false;
-        td = (double)d;
-        return true;
-    });
-    if (tid == 0) {
-        bev_icp_result_t r{};
-        for (int k = 0; k < 16; ++k) r.T[k] = isnan(F[k]) ? __uint_as_float(0x7fc00000u) : F[k];
-        r.fitness = sh.cnt ? sh.totd / (double)sh.cnt : 1.7976931348623157e308;
-        if (isnan(r.fitness)) r.fitness = bevx::f64_qnan();
-        r.iterations = sh.iters;
-        r.state = sh.state;
-        r.converged = sh.state >= 1 && sh.state <= 4;
-        results[pb.result] = r;
-    }
+    reg_finish(sh.sums, sh.loop, n_src, FinePts{src}, h, toff, tpts, results + pb.result);
 }
 
 void launch_fine_voxel(const bev_point_t *pts, const FineSlot *slots, int slot0, int n, const FineWork &w, float leaf,

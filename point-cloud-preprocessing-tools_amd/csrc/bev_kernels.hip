@@ -36,6 +36,7 @@
 #include "bev_resolve.h"
 #include "bev_raster.h"
 #include "bev_misc.h"
+#include "bev_reg_common.h"
 #include "bev_regfront.h"
 #include "bev_icp.h"
 #include "bev_fine.h"

@@ -21,10 +21,6 @@
 
 namespace bevk {
 
-__device__ __forceinline__ bool rf_finite3(float x, float y, float z)
-{
-    return isfinite(x) && isfinite(y) && isfinite(z);
-}
 __device__ __forceinline__ float rf_canon(float f) { return isnan(f) ? __uint_as_float(0x7fc00000u) : f; }
 
 /* 32-bit key whose ascending order is DESCENDING z; -0 and +0 are one value */
@@ -41,39 +37,11 @@ __device__ __forceinline__ uint32_t rf_z_desc_key(float z)
 __device__ __forceinline__ int rf_top_cell(const bev_point_t &p)
 {
     if (p.label == 0) return -1;
-    if (!rf_finite3(p.x, p.y, p.z)) return -1;
+    if (!finite3(p.x, p.y, p.z)) return -1;
     const float gx = roundf((p.x + 100.0f) / 20.0f);
     const float gy = roundf((p.y + 100.0f) / 20.0f);
     if (!(gx >= 0.0f && gx < (float)kRfGrid && gy >= 0.0f && gy < (float)kRfGrid)) return -1;
     return (int)gx * kRfGrid + (int)gy;
-}
-
-__device__ __forceinline__ uint32_t rf_pow2(uint32_t n)
-{
-    uint32_t p = 1;
-    while (p < n) p <<= 1;
-    return p;
-}
-
-/* ascending bitonic sort of np2 (a power of two) keys by the whole workgroup; buf is LDS or global memory (a workgroup's
- * global writes are visible to its other waves after the barrier: they share the CU's vector cache) */
-__device__ void rf_bitonic(uint64_t *buf, uint32_t np2)
-{
-    for (uint32_t k = 2; k <= np2; k <<= 1) {
-        for (uint32_t j = k >> 1; j > 0; j >>= 1) {
-            for (uint32_t i = threadIdx.x; i < np2; i += blockDim.x) {
-                const uint32_t l = i ^ j;
-                if (l > i) {
-                    const uint64_t a = buf[i], b = buf[l];
-                    if ((a > b) == ((i & k) == 0)) {
-                        buf[i] = b;
-                        buf[l] = a;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-    }
 }
 
 __device__ __forceinline__ void rf_frame(const RfIn &in, int f, const bev_point_t **p, uint32_t *n)
@@ -173,49 +141,10 @@ __global__ __launch_bounds__(kRfThreads) void k_rf_voxel(RfWork w, float leaf, u
     uint32_t *vidx = w.vidx + (size_t)f * w.Q;
     uint32_t *vstart = w.vstart + (size_t)f * (w.Q + 1);
 
-    /* getMinMax3D over the finite points (min / max are exact: any order) */
-    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-    uint32_t nfin = 0;
-    for (uint32_t i = t; i < m; i += blockDim.x) {
-        const float4 q = src[i];
-        if (!rf_finite3(q.x, q.y, q.z)) continue;
-        ++nfin;
-        mn[0] = fminf(mn[0], q.x), mn[1] = fminf(mn[1], q.y), mn[2] = fminf(mn[2], q.z);
-        mx[0] = fmaxf(mx[0], q.x), mx[1] = fmaxf(mx[1], q.y), mx[2] = fmaxf(mx[2], q.z);
-    }
-    float *red = reinterpret_cast<float *>(lds);
-    for (int d = 0; d < 3; ++d) {
-        red[d * kRfThreads + t] = mn[d];
-        red[(3 + d) * kRfThreads + t] = mx[d];
-    }
-    reinterpret_cast<uint32_t *>(red + 6 * kRfThreads)[t] = nfin;
-    __syncthreads();
+    const auto fetch = [src](uint32_t i) { return make_float3(src[i].x, src[i].y, src[i].z); };
     const float inv = 1.0f / leaf;
-    if (t == 0) {
-        uint32_t nf = 0;
-        for (int i = 0; i < kRfThreads; ++i) {
-            for (int d = 0; d < 3; ++d) {
-                mn[d] = fminf(mn[d], red[d * kRfThreads + i]);
-                mx[d] = fmaxf(mx[d], red[(3 + d) * kRfThreads + i]);
-            }
-            nf += reinterpret_cast<uint32_t *>(red + 6 * kRfThreads)[i];
-        }
-        int overflow = 0;
-        double prod = 1.0;
-        for (int d = 0; d < 3; ++d) {
-            const float e = (mx[d] - mn[d]) * inv;
-            if (!(e < 9.0e18f)) overflow = 1;
-            else prod *= (double)((int64_t)e + 1);
-        }
-        overflow = overflow || prod > 2147483647.0;
-        s_par[0] = overflow;
-        s_par[1] = (int)nf;
-        for (int d = 0; d < 3 && nf && !overflow; ++d) {
-            s_par[2 + d] = (int)floorf(mn[d] * inv);
-            s_par[5 + d] = (int)floorf(mx[d] * inv) - s_par[2 + d] + 1;
-        }
-    }
-    __syncthreads();
+    /* (the reduction borrows the sort buffer: it is done with it before the keys are written) */
+    rf_voxel_bounds(m, fetch, inv, reinterpret_cast<float *>(lds), s_par);
     const uint32_t nf = (uint32_t)s_par[1];
     if (nf == 0) {
         if (t == 0) {
@@ -234,49 +163,14 @@ __global__ __launch_bounds__(kRfThreads) void k_rf_voxel(RfWork w, float leaf, u
         }
         return;
     }
-    const int minb0 = s_par[2], minb1 = s_par[3], minb2 = s_par[4];
     const uint32_t div0 = (uint32_t)s_par[5], div1 = (uint32_t)s_par[6], div2 = (uint32_t)s_par[7];
-    const uint32_t mul2 = div0 * div1;
     const uint32_t np2 = rf_pow2(m);
     uint64_t *buf = np2 <= (uint32_t)kRfLdsKeys ? lds : w.scr + (size_t)f * 2 * w.P;
-    __syncthreads(); /* (the reduction above lived in lds) */
-    for (uint32_t i = t; i < np2; i += blockDim.x) {
-        uint64_t key = ~0ull;
-        if (i < m) {
-            const float4 q = src[i];
-            if (rf_finite3(q.x, q.y, q.z)) {
-                const uint32_t i0 = (uint32_t)(int)(floorf(q.x * inv) - (float)minb0);
-                const uint32_t i1 = (uint32_t)(int)(floorf(q.y * inv) - (float)minb1);
-                const uint32_t i2 = (uint32_t)(int)(floorf(q.z * inv) - (float)minb2);
-                key = ((uint64_t)(i0 + i1 * div0 + i2 * mul2) << 32) | i; /* voxel index modulo 2^32, then input index */
-            }
-        }
-        buf[i] = key;
-    }
-    __syncthreads();
+    rf_voxel_keys(m, np2, fetch, inv, s_par, buf);
     rf_bitonic(buf, np2);
-    /* voxel starts: an exclusive scan of "first key of its voxel" over the nf sorted keys, 256 at a time */
-    uint32_t base = 0;
-    const int lane = t & 63, wv = t >> 6;
-    for (uint32_t c0 = 0; c0 < nf; c0 += blockDim.x) {
-        const uint32_t i = c0 + t;
-        const bool start = i < nf && (i == 0 || (buf[i] >> 32) != (buf[i - 1] >> 32));
-        const uint64_t bal = __ballot(start);
-        if (lane == 0) wave_cnt[wv] = (uint32_t)__popcll(bal);
-        __syncthreads();
-        uint32_t before = base;
-        for (int q = 0; q < wv; ++q) before += wave_cnt[q];
-        before += (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
-        if (start) {
-            vstart[before] = i;
-            vidx[before] = (uint32_t)(buf[i] >> 32);
-        }
-        for (int q = 0; q < kRfThreads / 64; ++q) base += wave_cnt[q];
-        __syncthreads();
-    }
-    const uint32_t nv = base;
+    const uint32_t nv = rf_voxel_starts(buf, nf, wave_cnt, vstart,
+                                        [=](uint32_t v, uint32_t i) { vidx[v] = (uint32_t)(buf[i] >> 32); });
     if (t == 0) {
-        vstart[nv] = nf;
         meta->nv = nv;
         meta->div_x = div0;
         meta->div_y = div1;

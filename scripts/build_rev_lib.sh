@@ -9,7 +9,8 @@ mkdir -p $T/pkg/csrc $T/include
 for f in $(git -C $R ls-tree --name-only $REV point-cloud-preprocessing-tools_amd/csrc/ | grep -E '\.(hip|h)$'); do git -C $R show $REV:$f > $T/pkg/csrc/$(basename $f); done
 git -C $R show $REV:include/bev_mi355x.h > $T/include/bev_mi355x.h
 FLAGS="$EXTRA -O3 -std=c++17 --offload-arch=gfx950 -fPIC -ffp-contract=off -fno-fast-math -fhip-fp32-correctly-rounded-divide-sqrt -Wno-unused-function"
-(cd $T/pkg && /opt/rocm/bin/hipcc $FLAGS -c csrc/bev_kernels.hip -o k.o && /opt/rocm/bin/hipcc $FLAGS -c csrc/bev_capi.hip -o c.o &&
- /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o $R/point-cloud-preprocessing-tools_amd/csrc/libbev_$NAME.so k.o c.o -L/opt/rocm/lib -lroctx64 -Wl,-rpath,/opt/rocm/lib)
+# (whichever translation units that revision has: bev_kernels.hip and one or two files of the C ABI)
+(cd $T/pkg && for s in csrc/*.hip; do /opt/rocm/bin/hipcc $FLAGS -c $s -o $(basename $s .hip).o; done &&
+ /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o $R/point-cloud-preprocessing-tools_amd/csrc/libbev_$NAME.so *.o -L/opt/rocm/lib -lroctx64 -Wl,-rpath,/opt/rocm/lib)
 rm -rf $T
 echo built csrc/libbev_$NAME.so from $REV
