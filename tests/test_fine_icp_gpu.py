@@ -2,7 +2,9 @@
 VoxelGrid<PointXYZIRCT> on edge clouds and HDL_64E frames, point-to-point ICP on edge cases, and the batched
 device-resident entry with both tools' settings over the BEV path's ordered clouds (half the pairs a frame against a
 moved copy of the same sweep), its top-part guesses read from the coarse entry's device output, also between
-unsynchronised BEV calls."""
+unsynchronised BEV calls.  Covered here: uniform frames of S records, at most 200 matches and 200 distinct frames, so
+one voxel group and one launch.  Ragged packed frames, more than 256 slots and 1024 problems, guesses from an uploaded
+coarse table, skewed geometry and chunk-boundary sources are in test_registration_batch_gpu.py."""
 import os
 from concurrent.futures import ThreadPoolExecutor
 
