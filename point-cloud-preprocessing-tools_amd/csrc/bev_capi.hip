@@ -409,7 +409,7 @@ int run_pipeline(bev_ctx *c, int n_frames, const bev_point_t *d_pts, const uint6
                     if (rc_ != BEV_OK) return rc_;
                 }
                 take_pending(c, &a, q);
-                if (source == 4 || source == 5) {
+                if (source == kSrcColMajor || source == kSrcColMajorGen) {
                     /* the firing-order walks need 50-53 KB of LDS, three workgroups per CU — fused, every stage of the launch
                      * would run three per CU; so the walk is a launch of its own and the later stages a fused launch without a
                      * walk behind it, four per CU (same box, three passes: config 3 + 0.3 ... 1.8 %, real MulRan sweeps + 2.1 ...
@@ -435,7 +435,7 @@ int run_pipeline(bev_ctx *c, int n_frames, const bev_point_t *d_pts, const uint6
 
         if (identity) {
             RoctxRange rr("bev:front (identity walk)");
-            int rc = walk(K_GATHER_GROUND, 1, kFrameGeneral);
+            int rc = walk(K_GATHER_GROUND, kSrcIdentity, kFrameGeneral);
             if (rc != BEV_OK) return rc;
         } else {
             RoctxRange rr("bev:front (probe, column walk beside the later stages of earlier sub-batches, verdict, order scan)");
@@ -475,13 +475,13 @@ int run_pipeline(bev_ctx *c, int n_frames, const bev_point_t *d_pts, const uint6
             if (c->layout_hint) seen |= 1u << c->layout_hint; /* (the probe hands the hinted mode out whatever the last verdicts saw) */
             int rc = BEV_OK;
             if (c->allow_stream && ln.tail_list && (seen & (1u << kFrameStream))) /* frames k_probe found sorted up to a tail: read in place, verified */
-                rc = walk(K_GATHER_GROUND, 2, kFrameStream);
+                rc = walk(K_GATHER_GROUND, kSrcInPlace, kFrameStream);
             if (rc == BEV_OK && c->allow_stream && n_exact_s > 0 && (seen & (1u << kFrameStructured))) /* structured clouds (only a frame of exactly S records can be one) */
-                rc = walk(K_WALK_STRUCTURED, 3, kFrameStructured);
+                rc = walk(K_WALK_STRUCTURED, kSrcStructured, kFrameStructured);
             if (rc == BEV_OK && c->allow_stream && n_exact_s > 0 && (seen & (1u << kFrameColMajor))) /* ... or S returns in firing order */
-                rc = walk(K_WALK_COLMAJOR, 4, kFrameColMajor);
+                rc = walk(K_WALK_COLMAJOR, kSrcColMajor, kFrameColMajor);
             if (rc == BEV_OK && c->allow_stream && n_exact_s > 0 && ln.cm_par && (seen & (1u << kFrameColMajorGen))) /* ... from any start azimuth, in either direction, with staggered beams and no-return records */
-                rc = walk(K_WALK_COLMAJOR_GEN, 5, kFrameColMajorGen);
+                rc = walk(K_WALK_COLMAJOR_GEN, kSrcColMajorGen, kFrameColMajorGen);
             if (rc != BEV_OK) return rc;
             if (c->allow_stream) {
                 ProfScope ps(c, K_VERDICT, nb, st);
@@ -495,7 +495,7 @@ int run_pipeline(bev_ctx *c, int n_frames, const bev_point_t *d_pts, const uint6
                 ProfScope ps(c, K_ORDER_SCAN, nb, st);
                 launch_order_scan(g, b, nb, max_pts, thin, st);
             }
-            rc = walk(K_WALK_GENERAL, 0, kFrameGeneral);
+            rc = walk(K_WALK_GENERAL, kSrcGather, kFrameGeneral);
             if (rc != BEV_OK) return rc;
         }
         if (fused) {

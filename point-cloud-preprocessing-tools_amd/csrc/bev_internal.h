@@ -114,7 +114,7 @@ constexpr int kTailBuckets = 2048;  /* (row, strip) pairs of a frame that k_prob
  * u = +-firing mod H (the sweep's direction) a return of row r has column (u + B[r] + 0 .. kColMaxDisp) mod H, B[r] the
  * row's base (start azimuth + the beam's azimuth offset), or is out of range (>= H: dropped), or sits in column 0 whatever
  * its firing (a no-return record: x = y = 0 -> atan2(0, 0) = 0, MulranPointCloudSelect.cpp:123-125). */
-constexpr int kPlainDisp = 8;        /* the PLAIN sweep (kFrameColMajor): column = firing + 0 .. kPlainDisp, or >= H (k_probe's test and k_walk<4>'s check) */
+constexpr int kPlainDisp = 8;        /* the PLAIN sweep (kFrameColMajor): column = firing + 0 .. kPlainDisp, or >= H (k_probe's test and k_walk<kSrcColMajor>'s check) */
 constexpr int kColMaxDisp = 12;      /* (a row's displacements may spread over 8 columns and still leave k_probe, which sees every 63rd record, two columns of slack on either side) */
 constexpr int kCmSpread = 18;        /* the rows' bases lie within this many columns of each other (an OS1-64's four laser columns: +-9) */
 constexpr int kCmProbeDisp = kColMaxDisp; /* spread of a row's SAMPLED displacements that k_probe accepts; what is left of kColMaxDisp is put half below, half above them, for the records it did not see */
@@ -243,10 +243,15 @@ size_t stage_lds_bytes(const Geometry &g, int source);
 /* launchers (bev_kernels.hip) — all asynchronous on `st` */
 /* the frames that are not read in place: general ones and (after k_verdict) those whose verification failed */
 void launch_order_scan(const Geometry &g, const BatchPtrs &b, int nf, uint32_t max_pts, bool thin, hipStream_t st);
-/* the column walk.  source 0: through the winner table (the frames that are not read in place: pass kFrameGeneral);
- * 1: identity, b.pts already is the ordered cloud (bev_mark_ground); 2: in place (frames of mode kFrameStream: pass
- * mode = kFrameStream); 3: structured clouds (kFrameStructured); 4: the plain sweep in firing order (kFrameColMajor);
- * 5: firing order in its general form (kFrameColMajorGen) — sources 2 .. 5 take the frames of the mode passed */
+/* the column walk and where it takes its points from.  source
+ *   kSrcGather       through the winner table of the order scan (the frames that are not read in place: pass kFrameGeneral);
+ *   kSrcIdentity     b.pts already is the ordered cloud (bev_mark_ground);
+ *   kSrcInPlace      a sorted prefix read in place (frames of mode kFrameStream: pass mode = kFrameStream);
+ *   kSrcStructured   structured clouds (kFrameStructured);
+ *   kSrcColMajor     the plain sweep in firing order (kFrameColMajor);
+ *   kSrcColMajorGen  firing order in its general form (kFrameColMajorGen)
+ * — the last four take the frames of the mode passed */
+enum : int { kSrcGather = 0, kSrcIdentity = 1, kSrcInPlace = 2, kSrcStructured = 3, kSrcColMajor = 4, kSrcColMajorGen = 5 };
 void launch_gather_ground(const Geometry &g, const BatchPtrs &b, int nf, int source, uint32_t mode, hipStream_t st);
 void launch_probe(const Geometry &g, const BatchPtrs &b, int nf, bool allow_stream, int layout_hint /* 0, kFrameStructured or kFrameColMajor */, hipStream_t st);
 void launch_verdict(const Geometry &g, const BatchPtrs &b, int nf, uint32_t *host_hint, hipStream_t st);

@@ -101,26 +101,43 @@ __global__ __launch_bounds__(kStageThreads, 4) void k_stage(StageArgs a)
     if (f < a.raster.nf) raster_body(reinterpret_cast<uint32_t *>(stage_arena), a.raster.b, a.g, f, k, a.want_multi, a.want_single);
 }
 
-template <int kSrc>
-static size_t walk_lds_bytes() { return sizeof(WalkLds<kSrc>); }
+/* the two dispatchers of the walk's template parameters: fn(std::integral_constant<int, kSrc>) for a source ... */
+template <class F>
+static auto with_source(int source, F &&fn)
+{
+    switch (source) {
+    case kSrcIdentity: return fn(std::integral_constant<int, kSrcIdentity>{});
+    case kSrcInPlace: return fn(std::integral_constant<int, kSrcInPlace>{});
+    case kSrcStructured: return fn(std::integral_constant<int, kSrcStructured>{});
+    case kSrcColMajor: return fn(std::integral_constant<int, kSrcColMajor>{});
+    case kSrcColMajorGen: return fn(std::integral_constant<int, kSrcColMajorGen>{});
+    default: return fn(std::integral_constant<int, kSrcGather>{});
+    }
+}
+/* ... and fn(kPow2, kGm) for the reciprocal / divide choice and the ground-mat output */
+template <class F>
+static void with_variant(bool pow2, bool gm, F &&fn)
+{
+    if (pow2 && !gm) fn(std::true_type{}, std::false_type{});
+    else if (pow2) fn(std::true_type{}, std::true_type{});
+    else if (!gm) fn(std::false_type{}, std::false_type{});
+    else fn(std::false_type{}, std::true_type{});
+}
+static bool raster_is_pow2(const Geometry &g) { return g.rp.inv_interval != 0.0f && g.rp.inv_height_res != 0.0f; } /* every configuration of the reference */
+/* the source k_stage is instantiated with.  (The firing-order walks are never fused — 50-53 KB of LDS would hold every stage
+ * of the launch to three per CU; they are launched apart, see run_pipeline — and the stages behind them take the gather's.) */
+constexpr int stage_source(int src) { return (src == kSrcColMajor || src == kSrcColMajorGen) ? (int)kSrcGather : src; }
+
 size_t stage_lds_bytes(const Geometry &g, int source)
 {
-    size_t w = 0;
-    switch (source) {
-    case kSrcIdentity: w = walk_lds_bytes<kSrcIdentity>(); break;
-    case kSrcInPlace: w = walk_lds_bytes<kSrcInPlace>(); break;
-    case kSrcStructured: w = walk_lds_bytes<kSrcStructured>(); break;
-    /* (the firing-order walks are never fused: 50-53 KB of LDS would hold every stage of the launch to three per CU) */
-    default: w = walk_lds_bytes<kSrcGather>(); break;
-    }
+    const size_t w = with_source(source, [](auto s) { return sizeof(WalkLds<stage_source(decltype(s)::value)>); });
     const size_t others = std::max(std::max(SumDims::lds_bytes(g.segs), sizeof(ResolveLds)), raster_lds_bytes(g));
     return std::max(w, others);
 }
-template <int kSrc>
-static void launch_stage_src(const StageArgs &a, hipStream_t st)
+void launch_stage(const StageArgs &a, int source, hipStream_t st)
 {
+    if (a.walk.nf == 0) source = kSrcInPlace; /* (any instantiation will do for a launch without a walk) */
     const Geometry &g = a.g;
-    const bool pow2 = g.rp.inv_interval != 0.0f && g.rp.inv_height_res != 0.0f; /* every configuration of the reference */
     const bool gm = a.walk.nf > 0 && a.walk.b.gm != nullptr;
     const int back = std::max(a.sums.nf, std::max(a.resolve.nf, a.raster.nf));
     const int lead = back > 0 ? a.lead : 0;
@@ -128,21 +145,15 @@ static void launch_stage_src(const StageArgs &a, hipStream_t st)
     if (slots == 0) return;
     const int per_slot = g.strips + kSumQ + kResolveWgs + g.raster_bands;
     const dim3 gr((unsigned)(8 * slots * per_slot)), bl(kStageThreads);
-    const size_t lds = stage_lds_bytes(g, kSrc);
+    const size_t lds = stage_lds_bytes(g, source);
     StageArgs args = a;
     args.lead = lead;
-    if (pow2 && !gm) hipLaunchKernelGGL((k_stage<kSrc, true, false>), gr, bl, lds, st, args);
-    else if (pow2) hipLaunchKernelGGL((k_stage<kSrc, true, true>), gr, bl, lds, st, args);
-    else if (!gm) hipLaunchKernelGGL((k_stage<kSrc, false, false>), gr, bl, lds, st, args);
-    else hipLaunchKernelGGL((k_stage<kSrc, false, true>), gr, bl, lds, st, args);
-}
-void launch_stage(const StageArgs &a, int source, hipStream_t st)
-{
-    if (a.walk.nf == 0) source = kSrcInPlace; /* (any instantiation will do for a launch without a walk) */
-    if (source == kSrcIdentity) launch_stage_src<kSrcIdentity>(a, st);
-    else if (source == kSrcInPlace) launch_stage_src<kSrcInPlace>(a, st);
-    else if (source == kSrcStructured) launch_stage_src<kSrcStructured>(a, st);
-    else launch_stage_src<kSrcGather>(a, st); /* (kSrcColMajor / kSrcColMajorGen: launched apart, see run_pipeline) */
+    with_source(source, [&](auto s) {
+        constexpr int kSrc = stage_source(decltype(s)::value);
+        with_variant(raster_is_pow2(g), gm, [&](auto p, auto m) {
+            hipLaunchKernelGGL((k_stage<kSrc, decltype(p)::value, decltype(m)::value>), gr, bl, lds, st, args);
+        });
+    });
 }
 
 /* ------------------------------------------------------------------------- */
@@ -169,26 +180,16 @@ void launch_order_scan(const Geometry &g, const BatchPtrs &b, int nf, uint32_t m
     hipLaunchKernelGGL(k_order_scan, grid, dim3(256), 0, st, b.pts, b.frames, b.info, b.winner, g.N, g.H, g.S,
                        b.win_tag << b.win_shift);
 }
-template <int kSrc>
-static void launch_walk(const Geometry &g, const BatchPtrs &b, int nf, uint32_t mode, int grid, hipStream_t st)
-{
-    const bool pow2 = g.rp.inv_interval != 0.0f && g.rp.inv_height_res != 0.0f; /* every configuration of the reference */
-    const dim3 gr(grid), bl(kStripThreads);
-    if (pow2 && !b.gm) hipLaunchKernelGGL((k_walk<kSrc, true, false>), gr, bl, 0, st, b, g, nf, mode);
-    else if (pow2) hipLaunchKernelGGL((k_walk<kSrc, true, true>), gr, bl, 0, st, b, g, nf, mode);
-    else if (!b.gm) hipLaunchKernelGGL((k_walk<kSrc, false, false>), gr, bl, 0, st, b, g, nf, mode);
-    else hipLaunchKernelGGL((k_walk<kSrc, false, true>), gr, bl, 0, st, b, g, nf, mode);
-}
 void launch_gather_ground(const Geometry &g, const BatchPtrs &b, int nf, int source, uint32_t mode, hipStream_t st)
 {
     if (nf == 0) return;
-    const int grid = xcd_grid(nf, g.strips);
-    if (source == kSrcIdentity) launch_walk<kSrcIdentity>(g, b, nf, mode, grid, st);
-    else if (source == kSrcInPlace) launch_walk<kSrcInPlace>(g, b, nf, mode, grid, st);
-    else if (source == kSrcStructured) launch_walk<kSrcStructured>(g, b, nf, mode, grid, st);
-    else if (source == kSrcColMajor) launch_walk<kSrcColMajor>(g, b, nf, mode, grid, st);
-    else if (source == kSrcColMajorGen) launch_walk<kSrcColMajorGen>(g, b, nf, mode, grid, st);
-    else launch_walk<kSrcGather>(g, b, nf, mode, grid, st);
+    const dim3 gr(xcd_grid(nf, g.strips)), bl(kStripThreads);
+    with_source(source, [&](auto s) {
+        constexpr int kSrc = decltype(s)::value;
+        with_variant(raster_is_pow2(g), b.gm != nullptr, [&](auto p, auto m) {
+            hipLaunchKernelGGL((k_walk<kSrc, decltype(p)::value, decltype(m)::value>), gr, bl, 0, st, b, g, nf, mode);
+        });
+    });
 }
 void launch_probe(const Geometry &g, const BatchPtrs &b, int nf, bool allow_stream, int layout_hint, hipStream_t st)
 {

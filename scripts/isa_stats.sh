@@ -7,13 +7,13 @@ import re,sys
 pat=re.compile(sys.argv[1])
 txt=open('/tmp/bev_k.s').read()
 meta={}
-for m in re.finditer(r'\.name:\s+(\S+)\n(.*?)\.wavefront_size', txt, re.S):
-    d=dict(re.findall(r'\.(\w+):\s+(\d+)', m.group(2))); meta[m.group(1)]=d
+for blk in re.split(r'^  - (?=\.agpr_count)', txt[txt.find('amdhsa.kernels:'):], flags=re.M)[1:]:
+    d=dict(re.findall(r'^    \.(\w+):\s+(\S+)', blk, re.M)); meta[d['name']]=d
 for m in re.finditer(r"^(_ZN4bevk\S+):[^\n]*\n(.*?)\.Lfunc_end", txt, re.S|re.M):
     name=m.group(1)
     if not pat.search(name): continue
     body=m.group(2); ins=re.findall(r'^\s+([a-z][a-z0-9_]+)', body, re.M)
     c=lambda p: sum(1 for i in ins if re.match(p,i))
     d=meta.get(name,{})
-    print(f"{name[9:60]:52s} vgpr {d.get('vgpr_count','?'):>3} sgpr_spill {d.get('sgpr_spill_count','?'):>3} lds {d.get('group_segment_fixed_size','?'):>6} | instr {len(ins):5d} valu {c('v_'):5d} (readlane {c('v_readlane'):4d} writelane {c('v_writelane'):3d}) salu {c('s_'):5d} lds {c('ds_'):4d} vmem {c('global_|buffer_'):3d} waitcnt {c('s_waitcnt'):3d}")
+    print(f"{name[9:60]:52s} vgpr {d.get('vgpr_count','?'):>3} sgpr {d.get('sgpr_count','?'):>3} sgpr_spill {d.get('sgpr_spill_count','?'):>3} vgpr_spill {d.get('vgpr_spill_count','?'):>2} scratch {d.get('private_segment_fixed_size','?'):>3} lds {d.get('group_segment_fixed_size','?'):>6} | instr {len(ins):5d} valu {c('v_'):5d} (readlane {c('v_readlane'):4d} writelane {c('v_writelane'):3d}) salu {c('s_'):5d} lds {c('ds_'):4d} vmem {c('global_|buffer_'):3d} waitcnt {c('s_waitcnt'):3d}")
 PY
