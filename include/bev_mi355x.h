@@ -218,6 +218,40 @@ void bev_yaw_translate_matrix(float tx, float ty, float tz, float yaw_deg, float
 int bev_project_xyzi(bev_ctx_t *ctx, int kind, const float *xyzi, uint32_t n, bev_point_t *out);
 size_t bev_project_out_points(int kind, uint32_t n); /* 0 for an unknown kind */
 
+/* The same projection for a batch of frames in DEVICE memory, asynchronous like bev_process_device_resident: what it writes
+ * is what that call reads.
+ * d_xyzi    : frames' raw returns, packed: frame f = returns [h_offsets[f], h_offsets[f+1]) of d_xyzi (16 bytes per return;
+ *             Oxford: SoA inside the frame, x[n] y[n] z[n] intensity[n] from float 4 * h_offsets[f]).  h_offsets: HOST
+ *             array of n_frames + 1 entries, non-decreasing.
+ * d_out     : kinds 0 / 1: frame f's records at the same offsets (the same h_offsets array then serves
+ *             bev_process_device_resident); MulRan's row = k % 64 counts k within the frame.  KITTI: frame f's structured
+ *             cloud at f * 64 * 2083 (offsets f * 64 * 2083 for bev_process_device_resident; the call sets the structured
+ *             layout hint, see bev_set_layout_hint).  bev_project_batch_out_points (host only) is the number of records
+ *             d_out must hold: h_offsets[n_frames], or n_frames * 64 * 2083; 0 for an unknown kind or decreasing offsets.
+ *             d_xyzi and d_out must not overlap.
+ * Ordering  : work the caller has queued on the DEFAULT stream before the call (the upload or the fill of d_xyzi) is waited
+ *             for on the device; a BEV call of this context issued before it, which may still read d_out, is finished
+ *             first; a bev_process_device_resident issued right after it, with no synchronisation between, reads finished
+ *             records.  bev_synchronize() before the host reads d_out.
+ * Status    : BEV_ERR_INVALID_ARG for an unknown kind, decreasing offsets or a NULL pointer with work to do;
+ *             BEV_ERR_TOO_LARGE for a frame of more than max(max_points, S) returns; nothing is launched in either case.
+ * Workspace : kinds 0 / 1: a table of 16 * (n_frames + 1) bytes.  KITTI: the frames go through the four steps in launch
+ *             groups of BEV_PROJECT_KITTI_GROUP; the group's workspace, allocated on first use, grown when a call needs more
+ *             and freed by bev_destroy, is G * (288 + 4 * n_max + 516 * ceil(n_max / 256) + 4 * 64 * 2083) bytes (pieces
+ *             rounded up to 256) for G = min(group, n_frames) and n_max the call's longest frame: 21 MB for 120 k-return
+ *             sweeps.  Results do not depend on the group size. */
+#define BEV_PROJECT_KITTI_GROUP 16
+int bev_project_device_resident(bev_ctx_t *ctx, int kind, int n_frames, const float *d_xyzi,
+                                const uint64_t *h_offsets, bev_point_t *d_out);
+size_t bev_project_batch_out_points(int kind, int n_frames, const uint64_t *h_offsets);   /* host only */
+/* bev_process_batch on raw returns: xyzi[f] holds n_returns[f] returns of `kind` (HOST memory, 16 bytes per return); they go
+ * up as they are, are projected on the device and enter the pipeline there; the outputs are those of bev_process_batch on
+ * the projected clouds.  The kind must be the context's sensor — MulRan: 64 x 1024, Oxford: 32 x 1056, KITTI: 64 x 2083 —
+ * or the call returns BEV_ERR_UNSUPPORTED.  n_returns[f] <= max_points (KITTI: <= max(max_points, S), and max_points >= S). */
+int bev_process_batch_xyzi(bev_ctx_t *ctx, int kind, int n_frames, const float *const *xyzi, const uint32_t *n_returns,
+                           bev_point_t *const *ordered_out, uint8_t *const *multi_out, uint8_t *const *single_out,
+                           int8_t *const *ground_mat_out);
+
 /* ---- registration front end ----------------------------------------------------------------------------------------
  * What the reference's registration tools (top_part_registration, batch_top_part_registration, batch_whole_registration)
  * do to every cloud before ICP.  The contract — restated from PCL / FLANN / Eigen's published sources, parity with the

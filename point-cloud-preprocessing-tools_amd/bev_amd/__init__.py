@@ -67,6 +67,9 @@ class BevError(RuntimeError):
 
 _lib = None
 LAYOUT_UNKNOWN, LAYOUT_STRUCTURED, LAYOUT_FIRING_ORDER = 0, 3, 4  # bev_set_layout_hint
+PROJECT_MULRAN, PROJECT_OXFORD, PROJECT_KITTI = 0, 1, 2  # BEV_PROJECT_*
+PROJECT_KITTI_GROUP = 16  # BEV_PROJECT_KITTI_GROUP: frames per launch group of the batched KITTI projection
+KITTI_SLOTS = 64 * 2083
 
 # every symbol include/bev_mi355x.h declares
 ABI_SYMBOLS = [
@@ -82,6 +85,7 @@ ABI_SYMBOLS = [
     "bev_icp_coarse_defaults", "bev_icp_point_to_plane", "bev_coarse_registration_device_resident",
     "bev_voxel_grid_irct", "bev_icp_fine_defaults", "bev_icp_whole_defaults", "bev_icp_point_to_point",
     "bev_fine_registration_device_resident",
+    "bev_project_device_resident", "bev_project_batch_out_points", "bev_process_batch_xyzi",
 ]
 
 # registration front end (include/bev_mi355x.h): pcl::PointXYZ, pcl::Normal, pcl::PointNormal as float rows
@@ -195,6 +199,12 @@ def load_lib() -> C.CDLL:
         lib.bev_icp_point_to_point.argtypes = [vp, vp, u32, vp, u32, vp, C.POINTER(IcpParams), vp]
         lib.bev_fine_registration_device_resident.argtypes = [vp, i32, vp, C.POINTER(C.c_uint64), C.c_float, i32, vp, vp,
                                                               vp, C.POINTER(IcpParams), vp]
+    if hasattr(lib, "bev_project_device_resident"):
+        lib.bev_project_device_resident.argtypes = [vp, i32, i32, vp, C.POINTER(C.c_uint64), vp]
+        lib.bev_project_batch_out_points.argtypes = [i32, i32, C.POINTER(C.c_uint64)]
+        lib.bev_project_batch_out_points.restype = sz
+        lib.bev_process_batch_xyzi.argtypes = [vp, i32, i32, C.POINTER(vp), C.POINTER(u32), C.POINTER(vp), C.POINTER(vp),
+                                               C.POINTER(vp), C.POINTER(vp)]
     _lib = lib
     return lib
 
@@ -263,6 +273,26 @@ class BevContext:
         self._check(rc, "bev_process_batch")
         return ordered, multi, single, gm
 
+    def process_batch_xyzi(self, kind: int, frames, want_multi=True, want_single=True, want_ground_mat=False):
+        """process_batch on raw returns (bev_process_batch_xyzi): frames[f] is what project_xyzi(kind, .) takes; the
+        outputs are those of process_batch on the projected clouds."""
+        n = len(frames)
+        frames = [np.ascontiguousarray(f, dtype=np.float32).reshape(-1) for f in frames]
+        ordered = np.empty((n, self.S), dtype=POINT_DTYPE)
+        multi = np.empty((n, self.L, self.M, self.M), dtype=np.uint8) if want_multi else None
+        single = np.empty((n, self.M, self.M), dtype=np.uint8) if want_single else None
+        gm = np.empty((n, self.params.n_scan, self.params.horizon_scan), dtype=np.int8) if want_ground_mat else None
+        VP = C.c_void_p * max(n, 1)
+        raw = VP(*[f.ctypes.data if f.size >= 4 else None for f in frames])
+        nret = (C.c_uint32 * max(n, 1))(*[f.size // 4 for f in frames])
+        o = VP(*[ordered[i].ctypes.data for i in range(n)])
+        m = VP(*[multi[i].ctypes.data for i in range(n)]) if want_multi else None
+        s = VP(*[single[i].ctypes.data for i in range(n)]) if want_single else None
+        g = VP(*[gm[i].ctypes.data for i in range(n)]) if want_ground_mat else None
+        rc = self.lib.bev_process_batch_xyzi(self._h, kind, n, raw, nret, o, m, s, g)
+        self._check(rc, "bev_process_batch_xyzi")
+        return ordered, multi, single, gm
+
     # ---- whole hot path, device pointers --------------------------------
     def process_device(self, n_frames, d_pts, offsets, d_ordered, d_multi, d_single, d_ground_mat=None):
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
@@ -271,6 +301,16 @@ class BevContext:
             self._h, n_frames, C.c_void_p(d_pts), offsets.ctypes.data_as(C.POINTER(C.c_uint64)),
             C.c_void_p(d_ordered), C.c_void_p(d_multi), C.c_void_p(d_single), C.c_void_p(d_ground_mat))
         self._check(rc, "bev_process_device_resident")
+
+    def project_device(self, kind, n_frames, d_xyzi, offsets, d_out):
+        """bev_project_device_resident on device pointers: frame f = returns [offsets[f], offsets[f + 1]) of d_xyzi; kinds
+        0 / 1 write records at the same offsets of d_out, KITTI frame f's structured cloud at f * KITTI_SLOTS.
+        Asynchronous: a process_device behind it reads finished records; synchronize() before the host reads d_out."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        assert offsets.shape[0] == n_frames + 1
+        rc = self.lib.bev_project_device_resident(self._h, kind, n_frames, C.c_void_p(d_xyzi),
+                                                  offsets.ctypes.data_as(C.POINTER(C.c_uint64)), C.c_void_p(d_out))
+        self._check(rc, "bev_project_device_resident")
 
     def synchronize(self):
         self._check(self.lib.bev_synchronize(self._h), "bev_synchronize")
@@ -585,6 +625,13 @@ class BevContext:
         self._check(self.lib.bev_debug_angle_predicate(self._h, _ptr(dx), _ptr(dy), _ptr(dz), _ptr(out), dx.shape[0]),
                     "bev_debug_angle_predicate")
         return out
+
+
+def project_batch_out_points(kind: int, n_frames: int, offsets) -> int:
+    """Records the d_out of project_device must hold (host only); 0 for an unknown kind or decreasing offsets."""
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    assert offsets.shape[0] == n_frames + 1
+    return int(load_lib().bev_project_batch_out_points(kind, n_frames, offsets.ctypes.data_as(C.POINTER(C.c_uint64))))
 
 
 def regfront_max_out(n: int) -> int:

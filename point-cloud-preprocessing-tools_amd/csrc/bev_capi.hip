@@ -537,6 +537,163 @@ int run_pipeline(bev_ctx *c, int n_frames, const bev_point_t *d_pts, const uint6
 }
 } // namespace
 
+namespace {
+
+bool project_kind_ok(int kind)
+{
+    return kind == BEV_PROJECT_MULRAN_OS1_64 || kind == BEV_PROJECT_OXFORD_HDL_32E || kind == BEV_PROJECT_KITTI_HDL_64E;
+}
+
+/* The projection of nf frames on the context's stream: frame f = returns [offs[f], offs[f + 1]) of d_xyzi (offsets checked by
+ * the caller).  Kinds 0 / 1: ONE launch, records at the same offsets of d_out.  KITTI: launch groups of kitti_group frames
+ * over one workspace (stream order hands it from group to group), frame f's structured cloud at d_out + f * 64 * 2083. */
+int project_frames(bev_ctx *c, int kind, int nf, const float *d_xyzi, const uint64_t *offs, bev_point_t *d_out)
+{
+    if (nf == 0) return BEV_OK;
+    ProjFrame *h = nullptr;
+    const size_t bytes = ((size_t)nf + 1) * sizeof(ProjFrame);
+    int rc = c->proj_tab.begin(c, bytes, 1024 * sizeof(ProjFrame), reinterpret_cast<void **>(&h));
+    if (rc != BEV_OK) return rc;
+    uint64_t blocks = 0;
+    uint32_t n_max = 0;
+    for (int f = 0; f < nf; ++f) {
+        const uint32_t n = (uint32_t)(offs[f + 1] - offs[f]);
+        h[f] = ProjFrame{offs[f], n, (uint32_t)blocks};
+        blocks += (n + (uint32_t)kProjBlock - 1u) / (uint32_t)kProjBlock;
+        n_max = std::max(n_max, n);
+        if (blocks > 0x7fffffffull) return BEV_ERR_TOO_LARGE; /* (2^41 returns in one call) */
+    }
+    h[nf] = ProjFrame{offs[nf], 0u, (uint32_t)blocks};
+    rc = c->proj_tab.push(c, bytes);
+    if (rc != BEV_OK) return rc;
+    const ProjFrame *d_tab = static_cast<const ProjFrame *>(c->proj_tab.dev);
+    if (kind != BEV_PROJECT_KITTI_HDL_64E) {
+        ProfScope ps(c, K_PROJECT, nf);
+        launch_project_batch(kind, d_xyzi, d_tab, nf, (uint32_t)blocks, d_out, c->stream);
+    } else {
+        c->layout_hint = BEV_LAYOUT_STRUCTURED; /* what this writes are structured clouds (bev_set_layout_hint) */
+        const size_t S = (size_t)bevx::kKittiRows * bevx::kKittiCols, G = (size_t)std::min(c->kitti_group, nf);
+        KittiWork w{};
+        w.n_cap = n_max;
+        w.blocks_cap = (n_max + bevx::kKittiBlock - 1u) / bevx::kKittiBlock;
+        const size_t sz[] = {G * sizeof(KittiHeader), G * w.n_cap * 4, G * w.blocks_cap * 4,
+                             G * w.blocks_cap * bevx::kKittiListCap * 4, G * S * 4};
+        void **const dst[] = {(void **)&w.hdr, (void **)&w.col, (void **)&w.cnt, (void **)&w.pos, (void **)&w.winner};
+        rc = c->kitti_ws.grow(c, carve(nullptr, sz, dst));
+        if (rc != BEV_OK) return rc;
+        carve(c->kitti_ws.p, sz, dst);
+        for (int f0 = 0; f0 < nf; f0 += (int)G) {
+            const int g = std::min((int)G, nf - f0);
+            HIPCK(c, hipMemsetAsync(w.winner, 0, (size_t)g * S * sizeof(uint32_t), c->stream));
+            for (int step = 0; step < 4; ++step) {
+                ProfScope ps(c, K_KITTI_CROSSINGS + step, g);
+                launch_project_kitti(step, d_xyzi, d_tab + f0, g, n_max, w, d_out + (size_t)f0 * S, c->stream);
+            }
+        }
+    }
+    HIPCK(c, hipGetLastError());
+    return BEV_OK;
+}
+
+/* packed frames of a projection call: BEV_OK, or what the entry point returns */
+int check_project_offsets(const bev_ctx *c, int n_frames, const uint64_t *h_offsets)
+{
+    const uint64_t cap = std::max(c->max_points, (size_t)c->geo.S);
+    for (int f = 0; f < n_frames; ++f)
+        if (h_offsets[f + 1] < h_offsets[f]) return BEV_ERR_INVALID_ARG;
+    for (int f = 0; f < n_frames; ++f)
+        if (h_offsets[f + 1] - h_offsets[f] > cap) return BEV_ERR_TOO_LARGE;
+    return BEV_OK;
+}
+
+/* bev_process_batch (kind < 0: in[f] holds n_pts[f] records) and bev_process_batch_xyzi (in[f] holds n_pts[f] raw returns
+ * of `kind`): chunks of the batch go up, through the projection where they are raw, through the pipeline and down again */
+int process_batch_host(bev_ctx_t *c, int kind, int n_frames, const void *const *in, const uint32_t *n_pts,
+                       bev_point_t *const *ordered_out, uint8_t *const *multi_out, uint8_t *const *single_out,
+                       int8_t *const *ground_mat_out)
+{
+    if (!c || n_frames < 0 || (n_frames > 0 && (!in || !n_pts || !ordered_out))) return BEV_ERR_INVALID_ARG;
+    const bool raw = kind >= 0, kitti = kind == BEV_PROJECT_KITTI_HDL_64E;
+    const size_t in_size = raw ? 16 : sizeof(bev_point_t);
+    if (kitti && (size_t)c->geo.S > c->max_points) return BEV_ERR_TOO_LARGE; /* (the pipeline is handed S records per frame) */
+    for (int f = 0; f < n_frames; ++f) {
+        if (n_pts[f] > (kitti ? std::max(c->max_points, (size_t)c->geo.S) : c->max_points)) return BEV_ERR_TOO_LARGE;
+        if (n_pts[f] && !in[f]) return BEV_ERR_INVALID_ARG;
+    }
+    if (n_frames == 0) return BEV_OK;
+    HIPCK(c, hipSetDevice(c->device));
+    { /* the later stages of sub-batches still in flight use the workspace this call is about to use */
+        const int rc_ = flush_pending(c);
+        if (rc_ != BEV_OK) return rc_;
+    }
+    int rc = ensure_staging(c);
+    if (rc != BEV_OK) return rc;
+    const size_t S = (size_t)c->geo.S;
+    if (raw && !c->st_raw) /* 16 bytes per return, as many returns as the input staging holds records */
+        HIPCK(c, hipMalloc((void **)&c->st_raw, c->st_in_elems * 16));
+    char *const d_in = raw ? reinterpret_cast<char *>(c->st_raw) : reinterpret_cast<char *>(c->st_in);
+    /* the output staging is used as two halves: chunk k is computed into half k % 2 while half (k - 1) % 2 drains */
+    const int halves = c->max_batch >= 2 ? 2 : 1;
+    const int chunk = c->max_batch / halves;
+    bool any_gm = false;
+    for (int f = 0; f < n_frames && ground_mat_out; ++f) any_gm = any_gm || ground_mat_out[f] != nullptr;
+
+    Downloader &dl = *c->downloader;
+    dl.begin_call();
+    std::vector<uint64_t> off, off_s;
+    int k = 0;
+    rc = BEV_OK;
+    for (int f0 = 0; f0 < n_frames && rc == BEV_OK; f0 += chunk, ++k) {
+        const int nb = std::min(chunk, n_frames - f0), half = k % halves;
+        RoctxRange rc_range("bev_process_batch: chunk (upload, pipeline, hand-over to the downloader)");
+        off.assign((size_t)nb + 1, 0);
+        hipError_t e = hipSuccess;
+        for (int f = 0; f < nb; ++f) off[f + 1] = off[f] + n_pts[f0 + f];
+        for (int f = 0; f < nb && e == hipSuccess;) { /* the input staging is free again: stream order */
+            /* clouds that follow each other in host memory go up in one copy (the staging is packed the same way) */
+            int last = f;
+            while (last + 1 < nb && n_pts[f0 + last] &&
+                   in[f0 + last + 1] == static_cast<const char *>(in[f0 + last]) + n_pts[f0 + last] * in_size)
+                ++last;
+            const uint64_t n = off[last + 1] - off[f];
+            if (n) e = hipMemcpyAsync(d_in + off[f] * in_size, in[f0 + f], (size_t)n * in_size, hipMemcpyHostToDevice, c->stream);
+            f = last + 1;
+        }
+        if (e != hipSuccess) {
+            rc = hip_fail(c, e, "hipMemcpyAsync (host -> device staging)", __LINE__);
+            break;
+        }
+        const uint64_t *pipe_off = off.data();
+        if (raw) { /* the chunk's records, written where an upload of records would have put them */
+            rc = project_frames(c, kind, nb, c->st_raw, off.data(), c->st_in);
+            if (rc != BEV_OK) break;
+            if (kitti) { /* structured clouds: S records each */
+                off_s.resize((size_t)nb + 1);
+                for (int f = 0; f <= nb; ++f) off_s[f] = (uint64_t)f * S;
+                pipe_off = off_s.data();
+            }
+        }
+        dl.wait_finished(k + 1 - halves); /* this half's previous tenant has reached the caller's buffers */
+        const size_t base = (size_t)half * chunk;
+        rc = run_pipeline(c, nb, c->st_in, pipe_off, false, c->st_ordered + base * S,
+                          multi_out ? c->st_multi + base * c->multi_bytes : nullptr,
+                          single_out ? c->st_single + base * c->single_bytes : nullptr, any_gm ? c->st_gm + base * S : nullptr,
+                          /*flush=*/true, /*sub_frames: two sub-batches, so that a chunk's stages overlap*/ nb >= 8 ? (nb + 1) / 2 : 0);
+        if (rc != BEV_OK) break;
+        e = hipEventRecord(c->out_ready[half], c->stream);
+        if (e != hipSuccess) {
+            rc = hip_fail(c, e, "hipEventRecord", __LINE__);
+            break;
+        }
+        dl.push({f0, nb, half, ordered_out, multi_out, single_out, any_gm ? ground_mat_out : nullptr, chunk});
+    }
+    dl.wait_finished(k); /* every chunk that was handed over has reached the caller's buffers */
+    if (rc == BEV_OK && dl.err != hipSuccess) rc = hip_fail(c, dl.err, "device -> host copy", __LINE__);
+    if (rc != BEV_OK) (void)hipDeviceSynchronize();
+    return rc;
+}
+} // namespace
+
 int bevh::ensure_staging(bev_ctx *c)
 {
     if (c->staging_ready) return BEV_OK;
@@ -670,6 +827,7 @@ int bev_create(bev_ctx_t **out, int device, const bev_params_t *p, int max_batch
         const char *sm = getenv("BEV_STREAM");
         c->allow_stream = !(sm && atoi(sm) == 0);
         if (const char *mt = getenv("BEV_MODE_TTL")) c->mode_ttl = std::max(1, atoi(mt));
+        if (const char *pg = getenv("BEV_PROJECT_GROUP")) c->kitti_group = std::max(1, std::min(64, atoi(pg)));
     }
     {   /* EQUAL priorities (profiles/r06_experiments.txt): the launches of two such streams share the chip workgroup by workgroup,
          * 396-400 k frames/s where different priorities (the higher stream's launch dispatched first, whole) gave 384-386 k
@@ -761,7 +919,7 @@ void bev_destroy(bev_ctx_t *c)
     if (c->dl_stream) (void)hipStreamDestroy(c->dl_stream);
     for (auto e : c->out_ready)
         if (e) (void)hipEventDestroy(e);
-    void *dev[] = {c->st_in, c->st_ordered, c->st_multi, c->st_single, c->st_gm, c->kitti_buf, c->codes, c->ctx_tab};
+    void *dev[] = {c->st_in, c->st_ordered, c->st_multi, c->st_single, c->st_gm, c->st_raw, c->codes, c->ctx_tab};
     for (void *p : dev)
         if (p) (void)hipFree(p);
     for (int k = 0; k < kDescRing; ++k) {
@@ -769,6 +927,8 @@ void bev_destroy(bev_ctx_t *c)
         if (c->desc_done[k]) (void)hipEventDestroy(c->desc_done[k]);
     }
     c->reg.release();
+    c->proj_tab.release();
+    c->kitti_ws.release();
     for (auto &s : c->prof_pool) {
         if (s.a) (void)hipEventDestroy(s.a);
         if (s.b) (void)hipEventDestroy(s.b);
@@ -802,69 +962,21 @@ int bev_process_batch(bev_ctx_t *c, int n_frames, const bev_point_t *const *pts,
                       bev_point_t *const *ordered_out, uint8_t *const *multi_out, uint8_t *const *single_out,
                       int8_t *const *ground_mat_out)
 {
-    if (!c || n_frames < 0 || (n_frames > 0 && (!pts || !n_pts || !ordered_out))) return BEV_ERR_INVALID_ARG;
-    for (int f = 0; f < n_frames; ++f) {
-        if (n_pts[f] > c->max_points) return BEV_ERR_TOO_LARGE;
-        if (n_pts[f] && !pts[f]) return BEV_ERR_INVALID_ARG;
-    }
-    if (n_frames == 0) return BEV_OK;
-    HIPCK(c, hipSetDevice(c->device));
-    { /* the later stages of sub-batches still in flight use the workspace this call is about to use */
-        const int rc_ = flush_pending(c);
-        if (rc_ != BEV_OK) return rc_;
-    }
-    int rc = ensure_staging(c);
-    if (rc != BEV_OK) return rc;
-    const size_t S = (size_t)c->geo.S;
-    /* the output staging is used as two halves: chunk k is computed into half k % 2 while half (k - 1) % 2 drains */
-    const int halves = c->max_batch >= 2 ? 2 : 1;
-    const int chunk = c->max_batch / halves;
-    bool any_gm = false;
-    for (int f = 0; f < n_frames && ground_mat_out; ++f) any_gm = any_gm || ground_mat_out[f] != nullptr;
+    return process_batch_host(c, -1, n_frames, reinterpret_cast<const void *const *>(pts), n_pts, ordered_out, multi_out,
+                              single_out, ground_mat_out);
+}
 
-    Downloader &dl = *c->downloader;
-    dl.begin_call();
-    std::vector<uint64_t> off;
-    int k = 0;
-    rc = BEV_OK;
-    for (int f0 = 0; f0 < n_frames && rc == BEV_OK; f0 += chunk, ++k) {
-        const int nb = std::min(chunk, n_frames - f0), half = k % halves;
-        RoctxRange rc_range("bev_process_batch: chunk (upload, pipeline, hand-over to the downloader)");
-        off.assign((size_t)nb + 1, 0);
-        hipError_t e = hipSuccess;
-        for (int f = 0; f < nb; ++f) off[f + 1] = off[f] + n_pts[f0 + f];
-        for (int f = 0; f < nb && e == hipSuccess;) { /* the input staging is free again: stream order */
-            /* clouds that follow each other in host memory go up in one copy (the staging is packed the same way) */
-            int last = f;
-            while (last + 1 < nb && n_pts[f0 + last] && pts[f0 + last + 1] == pts[f0 + last] + n_pts[f0 + last]) ++last;
-            const uint64_t n = off[last + 1] - off[f];
-            if (n)
-                e = hipMemcpyAsync(c->st_in + off[f], pts[f0 + f], (size_t)n * sizeof(bev_point_t), hipMemcpyHostToDevice,
-                                   c->stream);
-            f = last + 1;
-        }
-        if (e != hipSuccess) {
-            rc = hip_fail(c, e, "hipMemcpyAsync (host -> device staging)", __LINE__);
-            break;
-        }
-        dl.wait_finished(k + 1 - halves); /* this half's previous tenant has reached the caller's buffers */
-        const size_t base = (size_t)half * chunk;
-        rc = run_pipeline(c, nb, c->st_in, off.data(), false, c->st_ordered + base * S,
-                          multi_out ? c->st_multi + base * c->multi_bytes : nullptr,
-                          single_out ? c->st_single + base * c->single_bytes : nullptr, any_gm ? c->st_gm + base * S : nullptr,
-                          /*flush=*/true, /*sub_frames: two sub-batches, so that a chunk's stages overlap*/ nb >= 8 ? (nb + 1) / 2 : 0);
-        if (rc != BEV_OK) break;
-        e = hipEventRecord(c->out_ready[half], c->stream);
-        if (e != hipSuccess) {
-            rc = hip_fail(c, e, "hipEventRecord", __LINE__);
-            break;
-        }
-        dl.push({f0, nb, half, ordered_out, multi_out, single_out, any_gm ? ground_mat_out : nullptr, chunk});
-    }
-    dl.wait_finished(k); /* every chunk that was handed over has reached the caller's buffers */
-    if (rc == BEV_OK && dl.err != hipSuccess) rc = hip_fail(c, dl.err, "device -> host copy", __LINE__);
-    if (rc != BEV_OK) (void)hipDeviceSynchronize();
-    return rc;
+int bev_process_batch_xyzi(bev_ctx_t *c, int kind, int n_frames, const float *const *xyzi, const uint32_t *n_returns,
+                           bev_point_t *const *ordered_out, uint8_t *const *multi_out, uint8_t *const *single_out,
+                           int8_t *const *ground_mat_out)
+{
+    if (!c || !project_kind_ok(kind)) return BEV_ERR_INVALID_ARG;
+    /* what the kind writes must be the context's sensor (MulranPointCloudSelect.cpp:113, OxfordPointCloudSelect.cpp:172-218,
+     * KittiPointCloudSelect.cpp:148-149) */
+    static const int dims[3][2] = {{64, 1024}, {32, 1056}, {bevx::kKittiRows, bevx::kKittiCols}};
+    if (c->geo.N != dims[kind][0] || c->geo.H != dims[kind][1]) return BEV_ERR_UNSUPPORTED;
+    return process_batch_host(c, kind, n_frames, reinterpret_cast<const void *const *>(xyzi), n_returns, ordered_out,
+                              multi_out, single_out, ground_mat_out);
 }
 
 int bev_host_alloc(void **out, size_t bytes)
@@ -1000,39 +1112,11 @@ size_t bev_project_out_points(int kind, uint32_t n)
     }
 }
 
-namespace {
-/* carve the KITTI workspace out of one buffer (256-byte aligned pieces) */
-int kitti_workspace(bev_ctx *c, uint32_t n, KittiWork &w)
-{
-    const size_t blocks = ((size_t)n + bevx::kKittiBlock - 1) / bevx::kKittiBlock;
-    const size_t sz[] = {sizeof(KittiHeader), (size_t)n * 4, blocks * 4, blocks * bevx::kKittiListCap * 4,
-                         (size_t)bevx::kKittiRows * bevx::kKittiCols * 4};
-    void **const dst[] = {(void **)&w.hdr, (void **)&w.col, (void **)&w.cnt, (void **)&w.pos, (void **)&w.winner};
-    const size_t total = carve(nullptr, sz, dst);
-    if (n > c->kitti_points || !c->kitti_buf) {
-        if (c->kitti_buf) HIPCK(c, hipFree(c->kitti_buf));
-        c->kitti_buf = nullptr;
-        c->kitti_points = 0;
-        hipError_t e = hipMalloc(&c->kitti_buf, total);
-        if (e == hipErrorOutOfMemory) {
-            (void)hipGetLastError();
-            c->kitti_buf = nullptr;
-            return BEV_ERR_OOM;
-        }
-        HIPCK(c, e);
-        c->kitti_points = n;
-    }
-    carve(c->kitti_buf, sz, dst);
-    return BEV_OK;
-}
-} // namespace
-
 int bev_project_xyzi(bev_ctx_t *c, int kind, const float *xyzi, uint32_t n, bev_point_t *out)
 {
     const size_t n_out = bev_project_out_points(kind, n);
     if (!c || (n && !xyzi) || (n_out && !out)) return BEV_ERR_INVALID_ARG;
-    if (kind != BEV_PROJECT_MULRAN_OS1_64 && kind != BEV_PROJECT_OXFORD_HDL_32E && kind != BEV_PROJECT_KITTI_HDL_64E)
-        return BEV_ERR_INVALID_ARG;
+    if (!project_kind_ok(kind)) return BEV_ERR_INVALID_ARG;
     if ((size_t)n > std::max(c->max_points, (size_t)c->geo.S)) return BEV_ERR_TOO_LARGE;
     if (n_out == 0) return BEV_OK;
     HIPCK(c, hipSetDevice(c->device));
@@ -1047,26 +1131,40 @@ int bev_project_xyzi(bev_ctx_t *c, int kind, const float *xyzi, uint32_t n, bev_
     if ((size_t)n * 16 > (size_t)c->max_batch * c->geo.S * sizeof(bev_point_t)) return BEV_ERR_TOO_LARGE;
     if (n_out > c->st_in_elems) return BEV_ERR_TOO_LARGE;
     if (n) HIPCK(c, hipMemcpyAsync(d_raw, xyzi, (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
-    if (kind == BEV_PROJECT_KITTI_HDL_64E) c->layout_hint = BEV_LAYOUT_STRUCTURED; /* what this call writes is a structured cloud (bev_set_layout_hint) */
-    if (kind == BEV_PROJECT_KITTI_HDL_64E) {
-        if (n == 0) { /* defined here, undefined in the reference: an empty file gives the all-zero structured cloud */
-            HIPCK(c, hipMemsetAsync(c->st_in, 0, n_out * sizeof(bev_point_t), c->stream));
-        } else {
-            KittiWork w{};
-            rc = kitti_workspace(c, n, w);
-            if (rc != BEV_OK) return rc;
-            HIPCK(c, hipMemsetAsync(w.winner, 0, n_out * sizeof(uint32_t), c->stream));
-            ProfScope ps(c, K_PROJECT, 1);
-            launch_project_kitti(d_raw, n, w, c->st_in, c->stream);
-        }
-    } else {
-        ProfScope ps(c, K_PROJECT, 1);
-        launch_project(kind, d_raw, n, c->st_in, c->stream);
-    }
-    HIPCK(c, hipGetLastError());
+    const uint64_t offs[2] = {0, n}; /* one frame of the batched code (n = 0, KITTI: the all-zero structured cloud) */
+    rc = project_frames(c, kind, 1, d_raw, offs, c->st_in);
+    if (rc != BEV_OK) return rc;
     HIPCK(c, hipMemcpyAsync(out, c->st_in, n_out * sizeof(bev_point_t), hipMemcpyDeviceToHost, c->stream));
     HIPCK(c, hipStreamSynchronize(c->stream));
     return BEV_OK;
+}
+
+size_t bev_project_batch_out_points(int kind, int n_frames, const uint64_t *h_offsets)
+{
+    if (!project_kind_ok(kind) || n_frames < 0 || !h_offsets) return 0;
+    for (int f = 0; f < n_frames; ++f)
+        if (h_offsets[f + 1] < h_offsets[f]) return 0;
+    if (kind == BEV_PROJECT_KITTI_HDL_64E) return (size_t)n_frames * bevx::kKittiRows * bevx::kKittiCols;
+    return (size_t)h_offsets[n_frames]; /* records sit at their returns' offsets */
+}
+
+int bev_project_device_resident(bev_ctx_t *c, int kind, int n_frames, const float *d_xyzi, const uint64_t *h_offsets,
+                                bev_point_t *d_out)
+{
+    if (!c || !project_kind_ok(kind) || n_frames < 0 || !h_offsets) return BEV_ERR_INVALID_ARG;
+    int rc = check_project_offsets(c, n_frames, h_offsets);
+    if (rc != BEV_OK) return rc;
+    if (n_frames == 0) return BEV_OK;
+    const bool any_in = h_offsets[n_frames] != h_offsets[0], any_out = any_in || kind == BEV_PROJECT_KITTI_HDL_64E;
+    if ((any_in && !d_xyzi) || (any_out && !d_out)) return BEV_ERR_INVALID_ARG;
+    HIPCK(c, hipSetDevice(c->device));
+    rc = flush_pending(c); /* (joins the stage streams into the context's stream: a BEV call that still reads d_out comes first) */
+    if (rc != BEV_OK) return rc;
+    rc = wait_default_stream(c); /* (the upload or the fill of d_xyzi, typically) */
+    if (rc != BEV_OK) return rc;
+    rc = project_frames(c, kind, n_frames, d_xyzi, h_offsets, d_out);
+    if (rc != BEV_OK) return rc;
+    return record_tail(c); /* the stage streams of the next BEV call wait for it: it may read d_out at once */
 }
 
 size_t bev_float_bev_size(float interval)

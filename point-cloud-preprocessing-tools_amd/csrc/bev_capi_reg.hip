@@ -79,6 +79,22 @@ void RegState::release()
     tail_pending = false;
 }
 
+int bevh::wait_default_stream(bev_ctx *c)
+{
+    HIPCK(c, hipEventRecord(c->null_ev, nullptr));
+    HIPCK(c, hipStreamWaitEvent(c->stream, c->null_ev, 0));
+    return BEV_OK;
+}
+
+int bevh::record_tail(bev_ctx *c)
+{
+    RegState &r = c->reg;
+    if (!r.tail_ev) HIPCK(c, hipEventCreateWithFlags(&r.tail_ev, hipEventDisableTiming));
+    HIPCK(c, hipEventRecord(r.tail_ev, c->stream));
+    r.tail_pending = true;
+    return BEV_OK;
+}
+
 namespace {
 
 constexpr size_t kRegTabMin = (size_t)1 << 16; /* smallest problem / slot table */
@@ -90,25 +106,6 @@ bool matches_in_range(const bev_match_t *h_matches, int n_matches, int n_frames)
         if (mt.query_idx < 0 || mt.query_idx >= n_frames || mt.match_idx < 0 || mt.match_idx >= n_frames) return false;
     }
     return true;
-}
-
-/* device pointers from the caller: whatever it has queued on the default stream up to now (the upload or the fill of these
- * very buffers, typically) comes first */
-int wait_default_stream(bev_ctx *c)
-{
-    HIPCK(c, hipEventRecord(c->null_ev, nullptr));
-    HIPCK(c, hipStreamWaitEvent(c->stream, c->null_ev, 0));
-    return BEV_OK;
-}
-
-/* behind a batched call: the next BEV call's stage streams wait for it (run_pipeline) */
-int record_tail(bev_ctx *c)
-{
-    RegState &r = c->reg;
-    if (!r.tail_ev) HIPCK(c, hipEventCreateWithFlags(&r.tail_ev, hipEventDisableTiming));
-    HIPCK(c, hipEventRecord(r.tail_ev, c->stream));
-    r.tail_pending = true;
-    return BEV_OK;
 }
 
 /* workspace of the registration front end (RfWork, bev_internal.h), allocated on first use; the BEV path's is untouched */

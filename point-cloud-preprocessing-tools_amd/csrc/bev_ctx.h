@@ -219,9 +219,12 @@ struct bev_ctx {
     hipStream_t dl_stream = nullptr;             /* device -> host copies of bev_process_batch (own host thread) */
     bevh::Downloader *downloader = nullptr;            /* that thread, started with the staging buffers */
     hipEvent_t out_ready[2] = {nullptr, nullptr}; /* per half of the output staging: its chunk has been computed */
-    /* KITTI projection workspace, one allocation made on first use and grown on demand */
-    void *kitti_buf = nullptr;
-    size_t kitti_points = 0;
+    /* projection of raw returns (project_frames, bev_capi.hip): the frame table of a call; the KITTI workspace of one launch
+     * group, allocated on first use and grown on demand; the raw staging of bev_process_batch_xyzi (lazily allocated) */
+    bevh::UploadTable proj_tab;
+    bevh::DevBuf kitti_ws;
+    int kitti_group = bevk::kKittiGroup; /* BEV_PROJECT_GROUP=1 .. 64 (tests: results do not depend on it) */
+    float *st_raw = nullptr;
 
     bevh::RegState reg;
 
@@ -258,6 +261,12 @@ struct ProfScope {
 
 /* launches what is left of every pending sub-batch, then joins the stage streams into the context's stream */
 int flush_pending(bev_ctx *c);
+/* device pointers from the caller: whatever it has queued on the default stream up to now (the upload or the fill of these
+ * very buffers, typically) comes before what the context's stream is given next */
+int wait_default_stream(bev_ctx *c);
+/* behind an asynchronous call on the context's stream (batched registration, projection): the next BEV call's stage streams
+ * wait for it (run_pipeline) */
+int record_tail(bev_ctx *c);
 int ensure_staging(bev_ctx *c);
 
 inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }

@@ -215,6 +215,10 @@ enum KernelId {
     K_FINE_VOXEL, /* fine stage (bev_fine.h): VoxelGrid<PointXYZIRCT> of the full clouds */
     K_FINE_GRID,  /* ... the target frames' grids */
     K_FINE_ICP,   /* ... one workgroup per match: the point-to-point loop and the fitness */
+    K_KITTI_CROSSINGS, /* KITTI projection (bev_project.h): azimuths, columns, crossing lists (K_PROJECT: the MulRan / Oxford map) */
+    K_KITTI_CHAIN,     /* ... the chain of accepted crossings, one wave per frame */
+    K_KITTI_ASSIGN,    /* ... rings, last writer per slot */
+    K_KITTI_GATHER,    /* ... the structured clouds */
     K_COUNT
 };
 const char *kernel_name(int id);
@@ -267,23 +271,40 @@ void launch_ground_mat(const Geometry &g, const BatchPtrs &b, int8_t *out, int n
 void launch_cloud_codes(const Geometry &g, const bev_point_t *cloud, uint32_t n, uint32_t *codes, hipStream_t st);
 void launch_float_bev(const bev_point_t *cloud, uint32_t n, float interval, int M, bool skip_label0, float *grid,
                       hipStream_t st);
-void launch_project(int kind, const float *xyzi, uint32_t n, bev_point_t *out, hipStream_t st);
 void launch_transform(const bev_point_t *cloud, uint32_t n, const float m[12], bev_point_t *out, hipStream_t st);
-/* KITTI projection workspace (device): header with the chain of accepted crossings, per-point column,
- * per-block crossing lists, winner table of the 64 x 2083 structured cloud */
+/* ---- range-image projection of raw returns (bev_project.h) ---- */
+/* one frame of a projection call (device table of n_frames + 1 entries; the last one carries the total block count) */
+struct ProjFrame {
+    uint64_t off;  /* first return of the frame in the packed input (16 bytes per return) — and, kinds 0 / 1, its first record in the output */
+    uint32_t n;    /* returns */
+    uint32_t blk0; /* map kernels: workgroups before this frame's first (kProjBlock returns per workgroup) */
+};
+constexpr int kProjPerThread = 4;
+constexpr int kProjBlock = 256 * kProjPerThread; /* returns per workgroup of the map kernel */
+/* MulRan / Oxford: one launch for all frames; `blocks` = tab[nf].blk0 */
+void launch_project_batch(int kind, const float *xyzi, const ProjFrame *tab, int nf, uint32_t blocks, bev_point_t *out,
+                          hipStream_t st);
+/* KITTI projection workspace (device) of one launch group, per frame: header with the chain of accepted crossings,
+ * per-point column, per-block crossing lists, winner table of the 64 x 2083 structured cloud */
+constexpr int kKittiGroup = BEV_PROJECT_KITTI_GROUP; /* frames per launch group */
 struct KittiHeader {
     int32_t ring0;
     uint32_t n_links;
     uint32_t link[68];
 };
 struct KittiWork {
-    KittiHeader *hdr;
-    int32_t *col;     /* [n] */
-    uint32_t *cnt;    /* [ceil(n / 256)] */
-    uint32_t *pos;    /* [ceil(n / 256)][128] */
-    uint32_t *winner; /* [64 * 2083] */
+    KittiHeader *hdr; /* [group] */
+    int32_t *col;     /* [group][n_cap] */
+    uint32_t *cnt;    /* [group][blocks_cap], blocks_cap = ceil(n_cap / 256) */
+    uint32_t *pos;    /* [group][blocks_cap][128] */
+    uint32_t *winner; /* [group][64 * 2083] */
+    uint32_t n_cap, blocks_cap;
 };
-void launch_project_kitti(const float *xyzi, uint32_t n, const KittiWork &w, bev_point_t *out, hipStream_t st);
+/* the four steps for the nf <= group frames of tab (n_max: the longest of them); frame g's structured cloud at
+ * out + g * 64 * 2083; w.winner[0 .. nf * 64 * 2083) zeroed by the caller on the same stream.  step 0 .. 3: crossings, chain,
+ * assign, gather (a launch each, so that each has its own profile row: K_KITTI_CROSSINGS + step) */
+void launch_project_kitti(int step, const float *xyzi, const ProjFrame *tab, int nf, uint32_t n_max, const KittiWork &w,
+                          bev_point_t *out, hipStream_t st);
 void launch_angle_debug(const float *dx, const float *dy, const float *dz, uint8_t *out, size_t n, hipStream_t st);
 /* ---- registration front end (bev_regfront.h; DESIGN.md "Registration front end") ---- */
 constexpr int kRfThreads = 256;

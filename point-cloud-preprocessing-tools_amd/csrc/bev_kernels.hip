@@ -36,6 +36,7 @@
 #include "bev_resolve.h"
 #include "bev_raster.h"
 #include "bev_misc.h"
+#include "bev_project.h"
 #include "bev_reg_common.h"
 #include "bev_regfront.h"
 #include "bev_icp.h"
@@ -50,7 +51,7 @@ static const char *const kNames[K_COUNT] = {
     "k_gather_only", "k_ground_mat", "k_cloud_codes", "k_angle_debug", "k_float_bev", "k_project", "k_transform",
     "k_probe", "k_walk_general", "k_walk_structured", "k_walk_colmajor", "k_walk_colmajor_gen", "k_verdict", "k_stage",
     "k_rf_cells", "k_rf_top", "k_rf_voxel", "k_rf_normals", "k_icp_grid", "k_icp", "k_icp_best",
-    "k_fine_voxel", "k_fine_grid", "k_fine_icp",
+    "k_fine_voxel", "k_fine_grid", "k_fine_icp", "k_kitti_crossings", "k_kitti_chain", "k_kitti_assign", "k_kitti_gather",
 };
 const char *kernel_name(int id) { return (id >= 0 && id < K_COUNT) ? kNames[id] : "?"; }
 
@@ -254,19 +255,24 @@ void launch_transform(const bev_point_t *cloud, uint32_t n, const float m[12], b
     for (int k = 0; k < 12; ++k) a.m[k] = m[k];
     hipLaunchKernelGGL(k_transform, dim3((n + 255u) / 256u), dim3(256), 0, st, cloud, n, a, out);
 }
-void launch_project(int kind, const float *xyzi, uint32_t n, bev_point_t *out, hipStream_t st)
+void launch_project_batch(int kind, const float *xyzi, const ProjFrame *tab, int nf, uint32_t blocks, bev_point_t *out,
+                          hipStream_t st)
 {
-    if (n == 0) return;
-    hipLaunchKernelGGL(k_project, dim3((n + 255u) / 256u), dim3(256), 0, st, kind, xyzi, n, out);
+    if (blocks == 0 || nf == 0) return;
+    if (kind == BEV_PROJECT_MULRAN_OS1_64)
+        hipLaunchKernelGGL(k_project_batch<BEV_PROJECT_MULRAN_OS1_64>, dim3(blocks), dim3(256), 0, st, xyzi, tab, nf, out);
+    else
+        hipLaunchKernelGGL(k_project_batch<BEV_PROJECT_OXFORD_HDL_32E>, dim3(blocks), dim3(256), 0, st, xyzi, tab, nf, out);
 }
-void launch_project_kitti(const float *xyzi, uint32_t n, const KittiWork &w, bev_point_t *out, hipStream_t st)
+void launch_project_kitti(int step, const float *xyzi, const ProjFrame *tab, int nf, uint32_t n_max, const KittiWork &w,
+                          bev_point_t *out, hipStream_t st)
 {
-    /* n >= 1; w.winner zeroed by the caller on the same stream */
-    const unsigned blocks = (n + kKittiBlock - 1u) / kKittiBlock;
-    hipLaunchKernelGGL(k_kitti_crossings, dim3(blocks), dim3(kKittiBlock), 0, st, xyzi, n, w.col, w.cnt, w.pos, w.hdr);
-    hipLaunchKernelGGL(k_kitti_chain, dim3(1), dim3(64), 0, st, w.cnt, w.pos, n, kitti_ring_min(), w.hdr);
-    hipLaunchKernelGGL(k_kitti_assign, dim3((n + 255u) / 256u), dim3(256), 0, st, w.col, n, w.hdr, w.winner);
-    hipLaunchKernelGGL(k_kitti_gather, dim3((kKittiRows * kKittiCols + 255) / 256), dim3(256), 0, st, xyzi, w.winner, out);
+    if (nf == 0) return;
+    const unsigned blocks = (n_max + kKittiBlock - 1u) / kKittiBlock;
+    if (step == 0 && blocks) hipLaunchKernelGGL(k_kitti_crossings, dim3(blocks, (unsigned)nf), dim3(kKittiBlock), 0, st, xyzi, tab, w);
+    if (step == 1) hipLaunchKernelGGL(k_kitti_chain, dim3((unsigned)nf), dim3(64), 0, st, tab, w, kitti_ring_min());
+    if (step == 2 && blocks) hipLaunchKernelGGL(k_kitti_assign, dim3(blocks, (unsigned)nf), dim3(256), 0, st, tab, w);
+    if (step == 3) hipLaunchKernelGGL(k_kitti_gather, dim3((kKittiRows * kKittiCols + 255) / 256, (unsigned)nf), dim3(256), 0, st, xyzi, tab, w, out);
 }
 void launch_angle_debug(const float *dx, const float *dy, const float *dz, uint8_t *out, size_t n, hipStream_t st)
 {

@@ -15,6 +15,7 @@
 
 #include "../csrc/bev_exact.h"
 #include "FileFormats.h"
+#include "RawSweeps.h"
 
 SensorParams sensor_params_{0, 0, 0, 0.0f};
 std::vector<std::pair<int, int>> four_neighbor_iterator_;
@@ -213,19 +214,7 @@ void computeAndSaveSingleBev(pcl::PointCloud<pcl::PointXYZIRCT>::Ptr cloud, std:
 
 void getPcdFileNames(std::string path, std::vector<std::string> &filenames)
 {
-    DIR *dir = opendir(path.c_str());
-    if (!dir) {
-        std::cerr << "Folder doesn't Exist!" << std::endl; /* :473-476 */
-        return;
-    }
-    while (dirent *e = readdir(dir)) {
-        const std::string name = e->d_name;
-        const size_t dot = name.find_last_of('.');
-        if (name.substr(dot + 1) != "pcd") continue; /* :482-484 (also drops "." and "..") */
-        filenames.push_back(path.back() == '/' ? path + name : path + "/" + name);
-    }
-    closedir(dir);
-    std::sort(filenames.begin(), filenames.end()); /* :493 */
+    getFileNamesWithExtension(path, "pcd", filenames);
 }
 
 std::pair<int, int> getBelongingGrid(const pcl::PointCloud<PointType>::Ptr &cloud_ptr, int point_index)
@@ -301,7 +290,7 @@ void parallel_frames(int n, F fn)
 } // namespace
 
 double BatchMultiBevGen::processFiles(const std::vector<std::string> &files, std::size_t first, std::size_t count,
-                                      bool write_png, bool verbose)
+                                      bool write_png, bool verbose, int raw_format)
 {
     if (!ctx_) return 0.0;
     const size_t S = (size_t)params_.N_SCAN * params_.Horizon_SCAN;
@@ -309,24 +298,34 @@ double BatchMultiBevGen::processFiles(const std::vector<std::string> &files, std
     double timed_ms = 0.0;
     std::vector<pcl::PointCloud<pcl::PointXYZIRCT>> in(batch_frames_), ordered(batch_frames_);
     std::vector<std::vector<uint8_t>> multi(batch_frames_), single(batch_frames_);
+    const bool raw = raw_format != RAW_UNKNOWN; /* the files are raw sweeps: uploaded as they are, projected on the GPU */
+    std::vector<std::vector<float>> sweeps(raw ? batch_frames_ : 0);
     for (size_t b0 = first; b0 < first + count; b0 += batch_frames_) {
         const int nb = (int)std::min<size_t>(batch_frames_, first + count - b0);
         std::vector<const bev_point_t *> pts(nb);
+        std::vector<const float *> xyzi(nb);
         std::vector<uint32_t> npts(nb);
         std::vector<bev_point_t *> ord(nb);
         std::vector<uint8_t *> mo(nb), so(nb);
         std::vector<std::string> names(nb);
         parallel_frames(nb, [&](int i) {
-            in[i].clear();
-            if (bevio::loadPCDFile(files[b0 + i], in[i]) != 0) std::cerr << "Failed to load " << files[b0 + i] << "\n"; /* :730 */
+            bool loaded;
+            if (raw) {
+                loaded = readRawSweep((RawFormat)raw_format, files[b0 + i], sweeps[i]);
+            } else {
+                in[i].clear();
+                loaded = bevio::loadPCDFile(files[b0 + i], in[i]) == 0;
+            }
+            if (!loaded) std::cerr << "Failed to load " << files[b0 + i] << "\n"; /* :730 */
         });
         for (int i = 0; i < nb; ++i) {
             const std::string &fn = files[b0 + i];
             ordered[i].resize(S);
             multi[i].resize((size_t)kLayers * kMat * kMat);
             single[i].resize((size_t)kMat * kMat);
-            pts[i] = reinterpret_cast<const bev_point_t *>(in[i].points.data());
-            npts[i] = (uint32_t)in[i].points.size();
+            pts[i] = raw ? nullptr : reinterpret_cast<const bev_point_t *>(in[i].points.data());
+            xyzi[i] = raw ? sweeps[i].data() : nullptr;
+            npts[i] = raw ? (uint32_t)(sweeps[i].size() / 4) : (uint32_t)in[i].points.size();
             ord[i] = reinterpret_cast<bev_point_t *>(ordered[i].points.data());
             mo[i] = multi[i].data();
             so[i] = single[i].data();
@@ -338,6 +337,7 @@ double BatchMultiBevGen::processFiles(const std::vector<std::string> &files, std
          * reference processes every file whatever its size) */
         uint32_t largest = 0;
         for (int i = 0; i < nb; ++i) largest = std::max(largest, npts[i]);
+        if (raw_format == RAW_KITTI) largest = std::max(largest, (uint32_t)S); /* (the pipeline is handed the structured cloud's S records) */
         if ((std::size_t)largest > max_points_) {
             std::size_t want = max_points_;
             while (want < (std::size_t)largest) want *= 2;
@@ -353,7 +353,7 @@ double BatchMultiBevGen::processFiles(const std::vector<std::string> &files, std
              * — what kitti_point_cloud_select writes, KittiPointCloudSelect.cpp:206-207,240 — the clouds are announced as
              * structured and the library does not sample them; anything else: it looks by itself.  A wrong guess here costs
              * time only: the walk checks every record. */
-            bool structured = nb > 0;
+            bool structured = nb > 0 && !raw; /* (raw KITTI sweeps: the projection sets the hint by itself) */
             for (int i = 0; i < nb; ++i) structured = structured && (std::size_t)npts[i] == S;
             for (std::size_t k = 0; structured && k < 64; ++k) {
                 const std::size_t at = k * (S / 64) + k; /* (an odd walk over rows and columns) */
@@ -364,16 +364,21 @@ double BatchMultiBevGen::processFiles(const std::vector<std::string> &files, std
             }
             (void)bev_set_layout_hint(ctx_, structured ? BEV_LAYOUT_STRUCTURED : BEV_LAYOUT_UNKNOWN);
         }
+        /* one batch, or one frame of it, through the context: records or raw returns */
+        auto process = [&](int i0, int n) {
+            return raw ? bev_process_batch_xyzi(ctx_, raw_format, n, &xyzi[i0], &npts[i0], &ord[i0], &mo[i0], &so[i0], nullptr)
+                       : bev_process_batch(ctx_, n, &pts[i0], &npts[i0], &ord[i0], &mo[i0], &so[i0], nullptr);
+        };
         const auto t0 = std::chrono::steady_clock::now();
         std::vector<char> done(nb, 1);
-        int rc = bev_process_batch(ctx_, nb, pts.data(), npts.data(), ord.data(), mo.data(), so.data(), nullptr);
+        int rc = process(0, nb);
         if (rc != BEV_OK) {
             /* one bad frame must not take the other frames of its batch with it: retry frame by frame, count what
              * still fails; main() exits non-zero when anything failed */
             std::cerr << "bev_process_batch failed: " << bev_strerror(rc) << " " << bev_last_error(ctx_)
                       << "; retrying the batch frame by frame\n";
             for (int i = 0; i < nb; ++i) {
-                rc = bev_process_batch(ctx_, 1, &pts[i], &npts[i], &ord[i], &mo[i], &so[i], nullptr);
+                rc = process(i, 1);
                 if (rc != BEV_OK) {
                     std::cerr << "Failed to process " << files[b0 + i] << ": " << bev_strerror(rc) << " " << bev_last_error(ctx_) << "\n";
                     done[i] = 0;

@@ -55,9 +55,10 @@ public:
     /* Step 1 of main() (BatchMultiBevGen.cpp:727-757) for files[first, first+count):
      * load -> order -> ground -> BEVs -> write .bin/.png/.csv/.pcd.  Returns the
      * accumulated milliseconds of the reference's timed region (GPU path + BEV file
-     * writes; PCD load/save excluded, :732-752). */
+     * writes; PCD load/save excluded, :732-752).  raw_format: -1 — the files are PCDs; a RawFormat (RawSweeps.h) — they
+     * are raw sweeps of that selector, read by readRawSweep and projected on the GPU (bev_process_batch_xyzi). */
     double processFiles(const std::vector<std::string> &files, std::size_t first, std::size_t count,
-                        bool write_png = true, bool verbose = true);
+                        bool write_png = true, bool verbose = true, int raw_format = -1);
     /* frames whose outputs are missing because the GPU path failed on them (after a frame-by-frame retry of their
      * batch); the tool exits non-zero when this is not 0 */
     std::size_t failedFrames() const { return failed_frames_; }

@@ -1,9 +1,11 @@
 /*
- * batch_multi_bev_gen <keyframes_root_dir> <sensor_type>
+ * batch_multi_bev_gen <keyframes_root_dir> <sensor_type> [raw_format]
  *
  * Same command line, directory layout and stdout lines as the reference's tool
  * (BatchMultiBevGen.cpp:664-771); the per-file loop (:727-757) runs on MI355X
- * through the C ABI in batches.  Extra, optional environment:
+ * through the C ABI in batches.  With raw_format (mulran, oxford or kitti) keyframe_point_cloud/ holds the selectors'
+ * INPUT instead of their output: raw *.bin sweeps, read by RawSweeps.h and projected on the GPU (bev_process_batch_xyzi);
+ * everything behind that is the same.  Extra, optional environment:
  *   BEV_DEVICES=N   use GPUs 0..N-1 of this node (one host thread + one context
  *                   per GPU, contiguous shards of the sorted file list)
  *   BEV_DEVICE_MAP=a,b,...  the GPU of each of those N ranks instead of 0..N-1; an ordinal may repeat (0,0: two ranks, two
@@ -25,6 +27,7 @@
 
 #include "BatchMultiBevGen.h"
 #include "LabelStep.h"
+#include "RawSweeps.h"
 
 void bevhost_recreate_dir(const std::string &dir); /* BatchMultiBevGen.cpp (host): rm -rf + mkdir -p */
 
@@ -37,6 +40,8 @@ int main(int argc, char **argv)
                   << "  keyframe_point_cloud/  <- selected point clouds in pcd format, one per frame\n"
                   << "  keyframe_pose.csv      <- 6-DoF pose for each frame\n\n"
                   << "[sensor_type] could be HDL_32E, HDL_64E or OS1_64. \n\n"
+                  << "[raw_format] (optional) mulran, oxford or kitti: keyframe_point_cloud/ holds raw .bin sweeps of that\n"
+                  << "selector (OS1_64, HDL_32E, HDL_64E) instead of pcd files.\n\n"
                   << "Writes non_ground_point_cloud/, output_multi_bev/{binary,image}/, output_single_bev/{csv,image}/\n"
                   << "and keyframe_label.csv under [keyframes_root_dir].\n";
         return 1;
@@ -47,8 +52,23 @@ int main(int argc, char **argv)
     const std::string pose_file = root + "keyframe_pose.csv";
     const std::string label_file = root + "keyframe_label.csv";
 
+    RawFormat raw_format = RAW_UNKNOWN;
+    if (argc > 3 && argv[3] != nullptr) { /* before any directory is touched */
+        raw_format = parseRawFormat(argv[3]);
+        if (raw_format == RAW_UNKNOWN) {
+            std::cerr << "unknown raw_format " << argv[3] << " (mulran, oxford or kitti)\n";
+            return 1;
+        }
+        if (!rawFormatFitsSensor(raw_format, parseSensorType(std::string(argv[2])))) {
+            std::cerr << "raw_format " << argv[3] << " does not fit sensor_type " << argv[2]
+                      << " (mulran: OS1_64, oxford: HDL_32E, kitti: HDL_64E)\n";
+            return 1;
+        }
+    }
+
     std::vector<std::string> files;
-    getPcdFileNames(pcd_dir, files);
+    if (raw_format == RAW_UNKNOWN) getPcdFileNames(pcd_dir, files);
+    else getFileNamesWithExtension(pcd_dir, "bin", files);
     setNeighbors();
     initDirectories(root);
     bevhost_recreate_dir(root + "non_ground_point_cloud/"); /* :704-705 */
@@ -146,7 +166,7 @@ int main(int argc, char **argv)
         workers.emplace_back([&, d, first, count]() {
             BatchMultiBevGen gen(root, argv[2], dev_of[d], batch, max_pts);
             if (!gen.ok()) { bad[d] = 1; return; }
-            ms[d] = gen.processFiles(files, first, count, png, n_dev == 1);
+            ms[d] = gen.processFiles(files, first, count, png, n_dev == 1, raw_format);
             failed[d] = gen.failedFrames();
         });
     }
