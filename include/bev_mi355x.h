@@ -196,6 +196,37 @@ int bev_transform_cloud(bev_ctx_t *ctx, const bev_point_t *cloud, uint32_t n, co
                         bev_point_t *out);
 void bev_yaw_translate_matrix(float tx, float ty, float tz, float yaw_deg, float *m /* 12 */);
 
+/* The float BEV for a batch of frames in DEVICE memory, each under its own poses: what cloud_manip computes (the rigid
+ * transform above, then saveAsMat) without the moved cloud ever being written.  One launch for the whole call, asynchronous
+ * like bev_project_device_resident.
+ * d_clouds  : frame f = records [h_offsets[f], h_offsets[f+1]) of d_clouds; h_offsets: HOST array of n_frames + 1 entries,
+ *             non-decreasing.  With offsets f * S this is the d_ordered of bev_process_device_resident.
+ * h_poses   : HOST array of n_frames * n_poses * 12 floats, frame f's pose k the row-major 3 x 4 matrix (what
+ *             bev_yaw_translate_matrix builds) at (f * n_poses + k) * 12; NULL when n_poses == 0: the raw coordinates are
+ *             rastered (NOT the same as an identity matrix: 0 * inf is NaN, and -0.0 becomes +0.0).
+ * d_out     : n_frames * max(1, n_poses) grids of M * M floats, M = bev_float_bev_size(interval), row index = x; frame f's
+ *             pose k is grid f * max(1, n_poses) + k and equals bev_float_bev(bev_transform_cloud(frame f, pose k)).  The
+ *             call zeroes every grid itself (an empty frame gives an all-zero grid) and writes nothing else.  The host
+ *             arrays may be reused as soon as the call returns.
+ * Ordering  : a BEV call of this context issued before it (a bev_process_device_resident whose d_ordered it reads) is
+ *             finished first; work queued on the DEFAULT stream before the call is waited for on the device; a BEV call
+ *             issued right after it, which may overwrite d_clouds, waits for it.  bev_synchronize() before the host reads
+ *             d_out.
+ * Status    : BEV_ERR_INVALID_ARG for n_frames < 0, NULL or decreasing offsets, n_poses < 0 or > BEV_FLOAT_BEV_MAX_POSES,
+ *             n_poses > 0 with NULL h_poses, a NULL data pointer with work to do; BEV_ERR_UNSUPPORTED when
+ *             bev_float_bev_size(interval) == 0; BEV_ERR_TOO_LARGE for a frame of more than max(max_points, S) records;
+ *             nothing is launched and d_out is untouched in every case.  n_frames == 0 returns BEV_OK.
+ * Workspace : a table of 16 * (n_frames + 1) + 48 * n_frames * n_poses bytes, freed by bev_destroy. */
+#define BEV_FLOAT_BEV_MAX_POSES 64
+int bev_float_bev_device_resident(bev_ctx_t *ctx, int n_frames, const bev_point_t *d_clouds, const uint64_t *h_offsets,
+                                  float interval, int skip_label0, int n_poses, const float *h_poses, float *d_out);
+/* The same through HOST buffers, synchronous like bev_process_batch: clouds[f] holds n_pts[f] records (at most
+ * max(max_points, S)), out[f] receives max(1, n_poses) * M * M floats.  The frames go up in chunks of max_batch through the
+ * context's input staging; the chunks' grids live in a device buffer of the context that is allocated on first use, grown
+ * when a call needs more and freed by bev_destroy. */
+int bev_float_bev_batch(bev_ctx_t *ctx, int n_frames, const bev_point_t *const *clouds, const uint32_t *n_pts,
+                        float interval, int skip_label0, int n_poses, const float *h_poses, float *const *out);
+
 /* Range-image projection of raw XYZI returns — the selectors' row / col assignment ("polar binning"):
  *   BEV_PROJECT_MULRAN_OS1_64   extractPointCloud, MulranPointCloudSelect.cpp:112-130:
  *                               xyzi = n * (x, y, z, intensity); row = k % 64, col from the azimuth (0..1024)

@@ -70,6 +70,7 @@ LAYOUT_UNKNOWN, LAYOUT_STRUCTURED, LAYOUT_FIRING_ORDER = 0, 3, 4  # bev_set_layo
 PROJECT_MULRAN, PROJECT_OXFORD, PROJECT_KITTI = 0, 1, 2  # BEV_PROJECT_*
 PROJECT_KITTI_GROUP = 16  # BEV_PROJECT_KITTI_GROUP: frames per launch group of the batched KITTI projection
 KITTI_SLOTS = 64 * 2083
+FLOAT_BEV_MAX_POSES = 64  # BEV_FLOAT_BEV_MAX_POSES: poses per frame of float_bev_device / float_bev_batch
 
 # every symbol include/bev_mi355x.h declares
 ABI_SYMBOLS = [
@@ -86,6 +87,7 @@ ABI_SYMBOLS = [
     "bev_voxel_grid_irct", "bev_icp_fine_defaults", "bev_icp_whole_defaults", "bev_icp_point_to_point",
     "bev_fine_registration_device_resident",
     "bev_project_device_resident", "bev_project_batch_out_points", "bev_process_batch_xyzi",
+    "bev_float_bev_device_resident", "bev_float_bev_batch",
 ]
 
 # registration front end (include/bev_mi355x.h): pcl::PointXYZ, pcl::Normal, pcl::PointNormal as float rows
@@ -205,6 +207,9 @@ def load_lib() -> C.CDLL:
         lib.bev_project_batch_out_points.restype = sz
         lib.bev_process_batch_xyzi.argtypes = [vp, i32, i32, C.POINTER(vp), C.POINTER(u32), C.POINTER(vp), C.POINTER(vp),
                                                C.POINTER(vp), C.POINTER(vp)]
+    if hasattr(lib, "bev_float_bev_device_resident"):
+        lib.bev_float_bev_device_resident.argtypes = [vp, i32, vp, C.POINTER(C.c_uint64), C.c_float, i32, i32, vp, vp]
+        lib.bev_float_bev_batch.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(u32), C.c_float, i32, i32, vp, C.POINTER(vp)]
     _lib = lib
     return lib
 
@@ -350,6 +355,40 @@ class BevContext:
         out = np.empty((M, M), dtype=np.float32)
         self._check(self.lib.bev_float_bev(self._h, _ptr(cloud) if len(cloud) else None, len(cloud), interval,
                                            1 if skip_label0 else 0, _ptr(out)), "bev_float_bev")
+        return out
+
+    def _poses(self, poses, n_frames):
+        """(n_frames, n_poses, 12) float32 or None -> (n_poses, array or None)"""
+        if poses is None:
+            return 0, None
+        poses = np.ascontiguousarray(poses, dtype=np.float32).reshape(n_frames, -1, 12)
+        return poses.shape[1], (poses if poses.shape[1] else None)
+
+    def float_bev_device(self, n_frames, d_clouds, offsets, d_out, interval=1.0, skip_label0=True, poses=None):
+        """bev_float_bev_device_resident on device pointers: frame f = records [offsets[f], offsets[f + 1]) of d_clouds;
+        poses: None, or (n_frames, n_poses, 12) host floats (row-major 3 x 4, yaw_translate_matrix); d_out receives
+        n_frames * max(1, n_poses) grids of M * M floats.  Asynchronous: synchronize() before the host reads d_out."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        assert offsets.shape[0] == n_frames + 1
+        n_poses, poses = self._poses(poses, n_frames)
+        rc = self.lib.bev_float_bev_device_resident(self._h, n_frames, C.c_void_p(d_clouds),
+                                                    offsets.ctypes.data_as(C.POINTER(C.c_uint64)), interval,
+                                                    1 if skip_label0 else 0, n_poses, _ptr(poses), C.c_void_p(d_out))
+        self._check(rc, "bev_float_bev_device_resident")
+
+    def float_bev_batch(self, clouds, interval=1.0, skip_label0=True, poses=None):
+        """bev_float_bev_batch on host clouds; returns (n_frames, max(1, n_poses), M, M) float32."""
+        n = len(clouds)
+        clouds = [np.ascontiguousarray(f, dtype=POINT_DTYPE) for f in clouds]
+        n_poses, poses = self._poses(poses, n)
+        M = int(self.lib.bev_float_bev_size(interval))
+        out = np.empty((n, max(1, n_poses), M, M), dtype=np.float32)
+        VP = C.c_void_p * max(n, 1)
+        pts = VP(*[f.ctypes.data if len(f) else None for f in clouds])
+        npts = (C.c_uint32 * max(n, 1))(*[len(f) for f in clouds])
+        o = VP(*[out[i].ctypes.data for i in range(n)])
+        rc = self.lib.bev_float_bev_batch(self._h, n, pts, npts, interval, 1 if skip_label0 else 0, n_poses, _ptr(poses), o)
+        self._check(rc, "bev_float_bev_batch")
         return out
 
     def transform_cloud(self, cloud, m):

@@ -547,6 +547,26 @@ bool project_kind_ok(int kind)
 /* The projection of nf frames on the context's stream: frame f = returns [offs[f], offs[f + 1]) of d_xyzi (offsets checked by
  * the caller).  Kinds 0 / 1: ONE launch, records at the same offsets of d_out.  KITTI: launch groups of kitti_group frames
  * over one workspace (stream order hands it from group to group), frame f's structured cloud at d_out + f * 64 * 2083. */
+/* The frame table of a launch over packed frames (k_project_batch, k_float_bev_batch): per frame its offset, its count and
+ * the workgroups of kProjBlock points before it; entry nf closes the table with the launch's workgroups, also in *blocks.
+ * BEV_ERR_TOO_LARGE for a grid that one launch cannot have (2^41 points in one call). */
+int fill_proj_table(const uint64_t *offs, int nf, ProjFrame *tab, uint32_t *blocks, uint32_t *n_max = nullptr)
+{
+    uint64_t b = 0;
+    uint32_t m = 0;
+    for (int f = 0; f < nf; ++f) {
+        const uint32_t n = (uint32_t)(offs[f + 1] - offs[f]);
+        tab[f] = ProjFrame{offs[f], n, (uint32_t)b};
+        b += (n + (uint32_t)kProjBlock - 1u) / (uint32_t)kProjBlock;
+        m = std::max(m, n);
+        if (b > 0x7fffffffull) return BEV_ERR_TOO_LARGE;
+    }
+    tab[nf] = ProjFrame{offs[nf], 0u, (uint32_t)b};
+    *blocks = (uint32_t)b;
+    if (n_max) *n_max = m;
+    return BEV_OK;
+}
+
 int project_frames(bev_ctx *c, int kind, int nf, const float *d_xyzi, const uint64_t *offs, bev_point_t *d_out)
 {
     if (nf == 0) return BEV_OK;
@@ -554,22 +574,15 @@ int project_frames(bev_ctx *c, int kind, int nf, const float *d_xyzi, const uint
     const size_t bytes = ((size_t)nf + 1) * sizeof(ProjFrame);
     int rc = c->proj_tab.begin(c, bytes, 1024 * sizeof(ProjFrame), reinterpret_cast<void **>(&h));
     if (rc != BEV_OK) return rc;
-    uint64_t blocks = 0;
-    uint32_t n_max = 0;
-    for (int f = 0; f < nf; ++f) {
-        const uint32_t n = (uint32_t)(offs[f + 1] - offs[f]);
-        h[f] = ProjFrame{offs[f], n, (uint32_t)blocks};
-        blocks += (n + (uint32_t)kProjBlock - 1u) / (uint32_t)kProjBlock;
-        n_max = std::max(n_max, n);
-        if (blocks > 0x7fffffffull) return BEV_ERR_TOO_LARGE; /* (2^41 returns in one call) */
-    }
-    h[nf] = ProjFrame{offs[nf], 0u, (uint32_t)blocks};
+    uint32_t blocks = 0, n_max = 0;
+    rc = fill_proj_table(offs, nf, h, &blocks, &n_max);
+    if (rc != BEV_OK) return rc;
     rc = c->proj_tab.push(c, bytes);
     if (rc != BEV_OK) return rc;
     const ProjFrame *d_tab = static_cast<const ProjFrame *>(c->proj_tab.dev);
     if (kind != BEV_PROJECT_KITTI_HDL_64E) {
         ProfScope ps(c, K_PROJECT, nf);
-        launch_project_batch(kind, d_xyzi, d_tab, nf, (uint32_t)blocks, d_out, c->stream);
+        launch_project_batch(kind, d_xyzi, d_tab, nf, blocks, d_out, c->stream);
     } else {
         c->layout_hint = BEV_LAYOUT_STRUCTURED; /* what this writes are structured clouds (bev_set_layout_hint) */
         const size_t S = (size_t)bevx::kKittiRows * bevx::kKittiCols, G = (size_t)std::min(c->kitti_group, nf);
@@ -603,6 +616,40 @@ int check_project_offsets(const bev_ctx *c, int n_frames, const uint64_t *h_offs
         if (h_offsets[f + 1] < h_offsets[f]) return BEV_ERR_INVALID_ARG;
     for (int f = 0; f < n_frames; ++f)
         if (h_offsets[f + 1] - h_offsets[f] > cap) return BEV_ERR_TOO_LARGE;
+    return BEV_OK;
+}
+
+bool float_bev_poses_ok(int n_poses, const float *h_poses)
+{
+    return n_poses >= 0 && n_poses <= BEV_FLOAT_BEV_MAX_POSES && (n_poses == 0 || h_poses);
+}
+
+/* The float BEV of nf frames on the context's stream: frame f = records [offs[f], offs[f + 1]) of d_clouds (offsets checked by
+ * the caller), its pose k the 12 floats at h_poses + (f * n_poses + k) * 12; nf * max(1, n_poses) grids of M * M floats at
+ * d_out, zeroed here.  ONE launch; the frame table and the matrices go up in one block. */
+int float_bev_frames(bev_ctx *c, int nf, const bev_point_t *d_clouds, const uint64_t *offs, float interval, size_t M,
+                     bool skip_label0, int n_poses, const float *h_poses, float *d_out)
+{
+    if (nf == 0) return BEV_OK;
+    const size_t tab_bytes = ((size_t)nf + 1) * sizeof(ProjFrame), pose_bytes = (size_t)nf * n_poses * 12 * sizeof(float);
+    char *h = nullptr;
+    int rc = c->manip_tab.begin(c, tab_bytes + pose_bytes, 64 * 1024, reinterpret_cast<void **>(&h));
+    if (rc != BEV_OK) return rc;
+    uint32_t blocks = 0;
+    rc = fill_proj_table(offs, nf, reinterpret_cast<ProjFrame *>(h), &blocks);
+    if (rc != BEV_OK) return rc;
+    if (pose_bytes) memcpy(h + tab_bytes, h_poses, pose_bytes);
+    rc = c->manip_tab.push(c, tab_bytes + pose_bytes);
+    if (rc != BEV_OK) return rc;
+    const char *d = static_cast<const char *>(c->manip_tab.dev);
+    HIPCK(c, hipMemsetAsync(d_out, 0, (size_t)nf * std::max(1, n_poses) * M * M * sizeof(float), c->stream));
+    {
+        ProfScope ps(c, K_FLOAT_BEV_BATCH, nf);
+        launch_float_bev_batch(d_clouds, reinterpret_cast<const ProjFrame *>(d), nf, blocks,
+                               reinterpret_cast<const float *>(d + tab_bytes), n_poses, interval, (int)M, skip_label0, d_out,
+                               c->stream);
+    }
+    HIPCK(c, hipGetLastError());
     return BEV_OK;
 }
 
@@ -929,6 +976,8 @@ void bev_destroy(bev_ctx_t *c)
     c->reg.release();
     c->proj_tab.release();
     c->kitti_ws.release();
+    c->manip_tab.release();
+    c->manip_grids.release();
     for (auto &s : c->prof_pool) {
         if (s.a) (void)hipEventDestroy(s.a);
         if (s.b) (void)hipEventDestroy(s.b);
@@ -1200,6 +1249,79 @@ int bev_float_bev(bev_ctx_t *c, const bev_point_t *cloud, uint32_t n, float inte
     HIPCK(c, hipMemcpyAsync(out, grid, M * M * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIPCK(c, hipStreamSynchronize(c->stream));
     return BEV_OK;
+}
+
+int bev_float_bev_device_resident(bev_ctx_t *c, int n_frames, const bev_point_t *d_clouds, const uint64_t *h_offsets,
+                                  float interval, int skip_label0, int n_poses, const float *h_poses, float *d_out)
+{
+    if (!c || n_frames < 0 || !h_offsets || !float_bev_poses_ok(n_poses, h_poses)) return BEV_ERR_INVALID_ARG;
+    int rc = check_project_offsets(c, n_frames, h_offsets);
+    if (rc == BEV_ERR_INVALID_ARG) return rc;
+    const size_t M = bev_float_bev_size(interval);
+    if (M == 0) return BEV_ERR_UNSUPPORTED;
+    if (rc != BEV_OK) return rc;
+    if (n_frames == 0) return BEV_OK;
+    if (!d_out || (!d_clouds && h_offsets[n_frames] != h_offsets[0])) return BEV_ERR_INVALID_ARG;
+    HIPCK(c, hipSetDevice(c->device));
+    rc = flush_pending(c); /* (a bev_process_device_resident whose d_ordered this call reads has launched all its stages) */
+    if (rc != BEV_OK) return rc;
+    rc = wait_default_stream(c); /* (the upload or the fill of d_clouds, typically) */
+    if (rc != BEV_OK) return rc;
+    rc = float_bev_frames(c, n_frames, d_clouds, h_offsets, interval, M, skip_label0 != 0, n_poses, h_poses, d_out);
+    if (rc != BEV_OK) return rc;
+    return record_tail(c); /* the stage streams of the next BEV call wait for it: it may overwrite d_clouds at once */
+}
+
+int bev_float_bev_batch(bev_ctx_t *c, int n_frames, const bev_point_t *const *clouds, const uint32_t *n_pts, float interval,
+                        int skip_label0, int n_poses, const float *h_poses, float *const *out)
+{
+    if (!c || n_frames < 0 || (n_frames > 0 && (!clouds || !n_pts || !out)) || !float_bev_poses_ok(n_poses, h_poses))
+        return BEV_ERR_INVALID_ARG;
+    for (int f = 0; f < n_frames; ++f)
+        if (!out[f] || (n_pts[f] && !clouds[f])) return BEV_ERR_INVALID_ARG;
+    const size_t M = bev_float_bev_size(interval);
+    if (M == 0) return BEV_ERR_UNSUPPORTED;
+    for (int f = 0; f < n_frames; ++f)
+        if ((size_t)n_pts[f] > std::max(c->max_points, (size_t)c->geo.S)) return BEV_ERR_TOO_LARGE;
+    if (n_frames == 0) return BEV_OK;
+    HIPCK(c, hipSetDevice(c->device));
+    { /* the later stages of sub-batches still in flight use the workspace this call is about to use */
+        const int rc_ = flush_pending(c);
+        if (rc_ != BEV_OK) return rc_;
+    }
+    int rc = ensure_staging(c);
+    if (rc != BEV_OK) return rc;
+    /* chunks of max_batch frames fit the input staging whatever their sizes; a chunk's uploads, its launch and its
+     * downloads follow the chunk before in the order of the context's stream */
+    const size_t per_frame = (size_t)std::max(1, n_poses) * M * M;
+    rc = c->manip_grids.grow(c, (size_t)std::min(n_frames, c->max_batch) * per_frame * sizeof(float));
+    if (rc != BEV_OK) return rc;
+    float *grids = static_cast<float *>(c->manip_grids.p);
+    const auto chunks = [&]() -> int {
+        std::vector<uint64_t> off;
+        for (int f0 = 0; f0 < n_frames; f0 += c->max_batch) {
+            const int nb = std::min(c->max_batch, n_frames - f0);
+            off.assign((size_t)nb + 1, 0);
+            for (int f = 0; f < nb; ++f) {
+                off[f + 1] = off[f] + n_pts[f0 + f];
+                if (n_pts[f0 + f])
+                    HIPCK(c, hipMemcpyAsync(c->st_in + off[f], clouds[f0 + f], (size_t)n_pts[f0 + f] * sizeof(bev_point_t),
+                                            hipMemcpyHostToDevice, c->stream));
+            }
+            const int rc_ = float_bev_frames(c, nb, c->st_in, off.data(), interval, M, skip_label0 != 0, n_poses,
+                                             n_poses ? h_poses + (size_t)f0 * n_poses * 12 : nullptr, grids);
+            if (rc_ != BEV_OK) return rc_;
+            for (int f = 0; f < nb; ++f)
+                HIPCK(c, hipMemcpyAsync(out[f0 + f], grids + (size_t)f * per_frame, per_frame * sizeof(float),
+                                        hipMemcpyDeviceToHost, c->stream));
+        }
+        HIPCK(c, hipStreamSynchronize(c->stream));
+        return BEV_OK;
+    };
+    rc = chunks();
+    /* an error leaves nothing in flight either: copies of earlier chunks into out[] may still be on their way */
+    if (rc != BEV_OK) (void)hipDeviceSynchronize();
+    return rc;
 }
 
 int bev_transform_cloud(bev_ctx_t *c, const bev_point_t *cloud, uint32_t n, const float *m, bev_point_t *out)

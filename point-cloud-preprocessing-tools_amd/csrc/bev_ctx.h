@@ -225,6 +225,10 @@ struct bev_ctx {
     bevh::DevBuf kitti_ws;
     int kitti_group = bevk::kKittiGroup; /* BEV_PROJECT_GROUP=1 .. 64 (tests: results do not depend on it) */
     float *st_raw = nullptr;
+    /* float BEV of a batch (float_bev_frames, bev_capi.hip): the frame and pose table of a call; the grids of
+     * bev_float_bev_batch's chunks, allocated on first use and grown on demand */
+    bevh::UploadTable manip_tab;
+    bevh::DevBuf manip_grids;
 
     bevh::RegState reg;
 

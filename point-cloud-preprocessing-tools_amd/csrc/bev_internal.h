@@ -219,6 +219,7 @@ enum KernelId {
     K_KITTI_CHAIN,     /* ... the chain of accepted crossings, one wave per frame */
     K_KITTI_ASSIGN,    /* ... rings, last writer per slot */
     K_KITTI_GATHER,    /* ... the structured clouds */
+    K_FLOAT_BEV_BATCH, /* the float BEV of a batch of frames under per-frame poses (bev_manip.h; K_FLOAT_BEV: one cloud) */
     K_COUNT
 };
 const char *kernel_name(int id);
@@ -305,6 +306,12 @@ struct KittiWork {
  * assign, gather (a launch each, so that each has its own profile row: K_KITTI_CROSSINGS + step) */
 void launch_project_kitti(int step, const float *xyzi, const ProjFrame *tab, int nf, uint32_t n_max, const KittiWork &w,
                           bev_point_t *out, hipStream_t st);
+/* ---- float max-height BEV of a batch of frames (bev_manip.h) ----
+ * one launch for all frames and poses: tab as for launch_project_batch (offsets and counts in records), poses nf * n_poses
+ * row-major 3 x 4 matrices (n_poses == 0: none, raw coordinates), grids nf * max(1, n_poses) * M * M floats, zeroed by the
+ * caller on the same stream */
+void launch_float_bev_batch(const bev_point_t *clouds, const ProjFrame *tab, int nf, uint32_t blocks, const float *poses,
+                            int n_poses, float interval, int M, bool skip_label0, float *grids, hipStream_t st);
 void launch_angle_debug(const float *dx, const float *dy, const float *dz, uint8_t *out, size_t n, hipStream_t st);
 /* ---- registration front end (bev_regfront.h; DESIGN.md "Registration front end") ---- */
 constexpr int kRfThreads = 256;

@@ -37,6 +37,7 @@
 #include "bev_raster.h"
 #include "bev_misc.h"
 #include "bev_project.h"
+#include "bev_manip.h"
 #include "bev_reg_common.h"
 #include "bev_regfront.h"
 #include "bev_icp.h"
@@ -52,6 +53,7 @@ static const char *const kNames[K_COUNT] = {
     "k_probe", "k_walk_general", "k_walk_structured", "k_walk_colmajor", "k_walk_colmajor_gen", "k_verdict", "k_stage",
     "k_rf_cells", "k_rf_top", "k_rf_voxel", "k_rf_normals", "k_icp_grid", "k_icp", "k_icp_best",
     "k_fine_voxel", "k_fine_grid", "k_fine_icp", "k_kitti_crossings", "k_kitti_chain", "k_kitti_assign", "k_kitti_gather",
+    "k_float_bev_batch",
 };
 const char *kernel_name(int id) { return (id >= 0 && id < K_COUNT) ? kNames[id] : "?"; }
 
@@ -263,6 +265,15 @@ void launch_project_batch(int kind, const float *xyzi, const ProjFrame *tab, int
         hipLaunchKernelGGL(k_project_batch<BEV_PROJECT_MULRAN_OS1_64>, dim3(blocks), dim3(256), 0, st, xyzi, tab, nf, out);
     else
         hipLaunchKernelGGL(k_project_batch<BEV_PROJECT_OXFORD_HDL_32E>, dim3(blocks), dim3(256), 0, st, xyzi, tab, nf, out);
+}
+void launch_float_bev_batch(const bev_point_t *clouds, const ProjFrame *tab, int nf, uint32_t blocks, const float *poses,
+                            int n_poses, float interval, int M, bool skip_label0, float *grids, hipStream_t st)
+{
+    if (blocks == 0 || nf == 0) return;
+    static_assert(sizeof(Affine34) == 12 * sizeof(float), "a pose is 12 packed floats");
+    hipLaunchKernelGGL(k_float_bev_batch, dim3(blocks), dim3(256), 0, st, clouds, tab, nf,
+                       reinterpret_cast<const Affine34 *>(poses), n_poses, interval, M, skip_label0 ? 1 : 0,
+                       reinterpret_cast<uint32_t *>(grids));
 }
 void launch_project_kitti(int step, const float *xyzi, const ProjFrame *tab, int nf, uint32_t n_max, const KittiWork &w,
                           bev_point_t *out, hipStream_t st)

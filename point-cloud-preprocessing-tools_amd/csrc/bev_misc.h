@@ -67,7 +67,18 @@ __global__ __launch_bounds__(256) void k_cloud_codes(const bev_point_t *__restri
 
 /* saveAsMat of batch_cloud_manip / cloud_manip (BatchCloudManip.cpp:213-225, CloudManip.cpp:84-95):
  * float32 max of z + 2.0f per cell over a grid initialised to 0.  A stored value is always > 0, and
- * positive IEEE floats order like their bit patterns, so the max is an integer atomicMax. */
+ * positive IEEE floats order like their bit patterns, so the max is an integer atomicMax.
+ * float_bev_cell: the cell x * M + y of a point that counts and its height, or -1 (k_float_bev and k_float_bev_batch). */
+__device__ __forceinline__ int float_bev_cell(float px, float py, float pz, int label, float interval, int M, int skip_label0,
+                                              float &h)
+{
+    const int x = bev_bin(px, 100.0f, interval); /* MAX_RANGE = 100, :209 / :81 */
+    const int y = bev_bin(py, 100.0f, interval);
+    h = pz + 2.0f;                                 /* :222 / :92 */
+    if (x < 0 || x >= M || y < 0 || y >= M) return -1;
+    if (skip_label0 && label == 0) return -1;      /* :218 (batch variant only) */
+    return h > 0.0f ? x * M + y : -1;              /* "h > cell" with cells >= 0 */
+}
 __global__ __launch_bounds__(256) void k_float_bev(const bev_point_t *__restrict__ cloud, uint32_t n, float interval,
                                                    int M, int skip_label0, uint32_t *__restrict__ grid)
 {
@@ -75,12 +86,9 @@ __global__ __launch_bounds__(256) void k_float_bev(const bev_point_t *__restrict
     if (i >= n) return;
     const float4 a = *reinterpret_cast<const float4 *>(cloud + i);
     const int label = (int)reinterpret_cast<const int16_t *>(cloud + i)[14];
-    const int x = bev_bin(a.x, 100.0f, interval); /* MAX_RANGE = 100, :209 / :81 */
-    const int y = bev_bin(a.y, 100.0f, interval);
-    if (x < 0 || x >= M || y < 0 || y >= M) return;
-    if (skip_label0 && label == 0) return;         /* :218 (batch variant only) */
-    const float h = a.z + 2.0f;                    /* :222 / :92 */
-    if (h > 0.0f) atomicMax(&grid[(size_t)x * M + y], __float_as_uint(h)); /* "h > cell" with cells >= 0 */
+    float h;
+    const int cell = float_bev_cell(a.x, a.y, a.z, label, interval, M, skip_label0, h);
+    if (cell >= 0) atomicMax(&grid[cell], __float_as_uint(h));
 }
 
 /* pcl::transformPointCloud with the [R | t] of cloud_manip (CloudManip.cpp:119-128): out.xyz = col0 * x + (col1 * y +

@@ -64,11 +64,43 @@ cv::Mat BatchCloudManip::saveAsMat(pcl::PointCloud<pcl::PointXYZIRCT>::Ptr cloud
 {
     cv::Mat grid = float_bev(*cloud, interval, true);
     if (grid.empty()) return grid;
+    writeMat(grid, filename_sin_appendix);
+    return grid;
+}
+
+void BatchCloudManip::writeMat(const cv::Mat &grid, const std::string &filename_sin_appendix)
+{
     const std::string csv = csv_f32(grid);
     if (!bevio::writeFile(filename_sin_appendix + ".csv", csv.data(), csv.size()))
         std::cerr << "Can not open file: " << filename_sin_appendix << ".csv\n";
     png_from_f32(filename_sin_appendix + ".png", grid);
-    return grid;
+}
+
+int BatchCloudManip::processBatch(bev_ctx_t *ctx, const std::vector<pcl::PointCloud<pcl::PointXYZIRCT>> &in, int first,
+                                  int n, std::size_t slots, std::vector<pcl::PointCloud<pcl::PointXYZIRCT>> &ordered,
+                                  std::vector<cv::Mat> &grids, float interval)
+{
+    const size_t M = bev_float_bev_size(interval);
+    std::vector<const bev_point_t *> pts(n), ord_in(n);
+    std::vector<bev_point_t *> ord(n);
+    std::vector<uint32_t> npts(n), nord(n, (uint32_t)slots);
+    std::vector<float *> out(n);
+    for (int i = 0; i < n; ++i) {
+        const int k = first + i;
+        ordered[k].clear();
+        ordered[k].resize(slots);
+        grids[k].create((int)M, (int)M, cv::CV_32F);
+        pts[i] = reinterpret_cast<const bev_point_t *>(in[k].points.data());
+        npts[i] = (uint32_t)in[k].points.size();
+        ord[i] = reinterpret_cast<bev_point_t *>(ordered[k].points.data());
+        ord_in[i] = ord[i];
+        out[i] = grids[k].ptr<float>();
+    }
+    if (!ctx || M == 0) return BEV_ERR_UNSUPPORTED; /* (the clouds and grids of this batch are there, empty) */
+    int rc = bev_process_batch(ctx, n, pts.data(), npts.data(), ord.data(), nullptr, nullptr, nullptr);
+    if (rc != BEV_OK) return rc;
+    /* (the ordered clouds go up again: 4.3 MB per frame against the milliseconds of file work each frame costs) */
+    return bev_float_bev_batch(ctx, n, ord_in.data(), nord.data(), interval, 1, 0, nullptr, out.data());
 }
 
 cv::Mat CloudManip::saveAsMat(pcl::PointCloud<PointType>::Ptr cloud, std::string mat_filename, float interval)

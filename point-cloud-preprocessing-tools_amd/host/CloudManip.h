@@ -11,8 +11,11 @@
 #define BEV_HOST_CLOUDMANIP_H
 
 #include <string>
+#include <vector>
 
 #include "PointCloud.h"
+
+struct bev_ctx;
 
 class BatchCloudManip {
 public:
@@ -20,6 +23,14 @@ public:
      * points with label == 0 are skipped (BatchCloudManip.cpp:218).  Returns the grid. */
     static cv::Mat saveAsMat(pcl::PointCloud<pcl::PointXYZIRCT>::Ptr cloud, std::string filename_sin_appendix,
                              float interval = 2.0f);
+    /* the files of saveAsMat for a grid that has been computed already */
+    static void writeMat(const cv::Mat &grid, const std::string &filename_sin_appendix);
+    /* getOrderedCloud + markGroundPoints + saveAsMat's grid for clouds first .. first + n - 1 of `in`, in two calls on a context of the
+     * tool's sensor: bev_process_batch (order and ground), then bev_float_bev_batch on the ordered clouds.  ordered[i]
+     * becomes the labelled N_SCAN x Horizon_SCAN cloud of in[i], grids[i] its M x M grid.  Returns the library's status. */
+    static int processBatch(struct bev_ctx *ctx, const std::vector<pcl::PointCloud<pcl::PointXYZIRCT>> &in, int first,
+                            int n, std::size_t slots, std::vector<pcl::PointCloud<pcl::PointXYZIRCT>> &ordered,
+                            std::vector<cv::Mat> &grids, float interval);
 };
 
 class CloudManip {
