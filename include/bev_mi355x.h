@@ -227,6 +227,42 @@ int bev_float_bev_device_resident(bev_ctx_t *ctx, int n_frames, const bev_point_
 int bev_float_bev_batch(bev_ctx_t *ctx, int n_frames, const bev_point_t *const *clouds, const uint32_t *n_pts,
                         float interval, int skip_label0, int n_poses, const float *h_poses, float *const *out);
 
+/* The 24-layer occupancy BEV and the uint8 max-height BEV (bev_multi_bev, bev_single_bev) for a batch of frames in DEVICE
+ * memory, each under its own poses, without the moved clouds ever being written.  Asynchronous like
+ * bev_float_bev_device_resident; the sensor and the grid are the context's (height_res, interval, max_range, n_layers).
+ * d_clouds  : frame f = records [h_offsets[f], h_offsets[f+1]) of d_clouds; h_offsets: HOST array of n_frames + 1 entries,
+ *             non-decreasing.  With offsets f * S this is the d_ordered of bev_process_device_resident.
+ * h_poses   : HOST array of n_frames * n_poses * 12 floats, frame f's pose k the row-major 3 x 4 matrix (what
+ *             bev_yaw_translate_matrix builds) at (f * n_poses + k) * 12; NULL when n_poses == 0: the raw coordinates are
+ *             rastered (NOT the same as an identity matrix), and on d_ordered the images are exactly what
+ *             bev_process_device_resident wrote to its own d_multi / d_single.
+ * d_multi   : n_frames * max(1, n_poses) images of bev_multi_bytes, or NULL: not wanted.
+ * d_single  : as many images of bev_single_bytes, or NULL: not wanted (not both).  Frame f's pose k is image
+ *             f * max(1, n_poses) + k of either and equals bev_multi_bev / bev_single_bev of bev_transform_cloud(frame f,
+ *             pose k) byte for byte.  Every byte of a wanted image is written (an empty frame gives all-zero images), nothing
+ *             else is.  The host arrays may be reused as soon as the call returns.
+ * Ordering  : as for bev_float_bev_device_resident: a BEV call of this context issued before it is finished first; work
+ *             queued on the DEFAULT stream before the call is waited for on the device; a BEV call issued right after it,
+ *             which may overwrite d_clouds, waits for it.  bev_synchronize() before the host reads the images.
+ * Status    : BEV_ERR_INVALID_ARG for n_frames < 0, NULL or decreasing offsets, n_poses < 0 or > BEV_POSED_BEV_MAX_POSES,
+ *             n_poses > 0 with NULL h_poses, d_multi and d_single both NULL, NULL d_clouds with records to read;
+ *             BEV_ERR_TOO_LARGE for a frame of more than max(max_points, S) records; nothing is launched and the outputs are
+ *             untouched in every case.  n_frames == 0 returns BEV_OK.
+ * Workspace : the table of the float call, and two planes of M * M words per grid (8 * M * M bytes) for one launch group:
+ *             the call is cut into groups of consecutive whole frames whose grids fit 256 MiB (BEV_POSED_GROUP=<grids>,
+ *             1 .. 65535, in the environment of bev_create sets the cap in grids instead; results do not depend on it); a
+ *             frame is never split: one whose poses alone exceed the cap is a group of its own.  Freed by bev_destroy. */
+#define BEV_POSED_BEV_MAX_POSES 64
+int bev_posed_bev_device_resident(bev_ctx_t *ctx, int n_frames, const bev_point_t *d_clouds, const uint64_t *h_offsets,
+                                  int n_poses, const float *h_poses, uint8_t *d_multi, uint8_t *d_single);
+/* The same through HOST buffers, synchronous like bev_float_bev_batch: clouds[f] holds n_pts[f] records (at most
+ * max(max_points, S)); multi_out[f] receives max(1, n_poses) images of bev_multi_bytes, single_out[f] as many of
+ * bev_single_bytes; a NULL array: not wanted (not both).  The frames go up in chunks of max_batch through the context's input
+ * staging; the chunks' images live in a device buffer of the context that is allocated on first use, grown when a call
+ * needs more and freed by bev_destroy. */
+int bev_posed_bev_batch(bev_ctx_t *ctx, int n_frames, const bev_point_t *const *clouds, const uint32_t *n_pts,
+                        int n_poses, const float *h_poses, uint8_t *const *multi_out, uint8_t *const *single_out);
+
 /* Range-image projection of raw XYZI returns — the selectors' row / col assignment ("polar binning"):
  *   BEV_PROJECT_MULRAN_OS1_64   extractPointCloud, MulranPointCloudSelect.cpp:112-130:
  *                               xyzi = n * (x, y, z, intensity); row = k % 64, col from the azimuth (0..1024)

@@ -71,6 +71,7 @@ PROJECT_MULRAN, PROJECT_OXFORD, PROJECT_KITTI = 0, 1, 2  # BEV_PROJECT_*
 PROJECT_KITTI_GROUP = 16  # BEV_PROJECT_KITTI_GROUP: frames per launch group of the batched KITTI projection
 KITTI_SLOTS = 64 * 2083
 FLOAT_BEV_MAX_POSES = 64  # BEV_FLOAT_BEV_MAX_POSES: poses per frame of float_bev_device / float_bev_batch
+POSED_BEV_MAX_POSES = 64  # BEV_POSED_BEV_MAX_POSES: poses per frame of posed_bev_device / posed_bev_batch
 
 # every symbol include/bev_mi355x.h declares
 ABI_SYMBOLS = [
@@ -88,6 +89,7 @@ ABI_SYMBOLS = [
     "bev_fine_registration_device_resident",
     "bev_project_device_resident", "bev_project_batch_out_points", "bev_process_batch_xyzi",
     "bev_float_bev_device_resident", "bev_float_bev_batch",
+    "bev_posed_bev_device_resident", "bev_posed_bev_batch",
 ]
 
 # registration front end (include/bev_mi355x.h): pcl::PointXYZ, pcl::Normal, pcl::PointNormal as float rows
@@ -210,6 +212,9 @@ def load_lib() -> C.CDLL:
     if hasattr(lib, "bev_float_bev_device_resident"):
         lib.bev_float_bev_device_resident.argtypes = [vp, i32, vp, C.POINTER(C.c_uint64), C.c_float, i32, i32, vp, vp]
         lib.bev_float_bev_batch.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(u32), C.c_float, i32, i32, vp, C.POINTER(vp)]
+    if hasattr(lib, "bev_posed_bev_device_resident"):
+        lib.bev_posed_bev_device_resident.argtypes = [vp, i32, vp, C.POINTER(C.c_uint64), i32, vp, vp, vp]
+        lib.bev_posed_bev_batch.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(u32), i32, vp, C.POINTER(vp), C.POINTER(vp)]
     _lib = lib
     return lib
 
@@ -390,6 +395,36 @@ class BevContext:
         rc = self.lib.bev_float_bev_batch(self._h, n, pts, npts, interval, 1 if skip_label0 else 0, n_poses, _ptr(poses), o)
         self._check(rc, "bev_float_bev_batch")
         return out
+
+    def posed_bev_device(self, n_frames, d_clouds, offsets, d_multi, d_single, poses=None):
+        """bev_posed_bev_device_resident on device pointers: frame f = records [offsets[f], offsets[f + 1]) of d_clouds;
+        poses: None, or (n_frames, n_poses, 12) host floats; d_multi / d_single (0 or None: not wanted) receive
+        n_frames * max(1, n_poses) images of L * M * M / M * M bytes.  Asynchronous: synchronize() before the host reads them."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        assert offsets.shape[0] == n_frames + 1
+        n_poses, poses = self._poses(poses, n_frames)
+        rc = self.lib.bev_posed_bev_device_resident(self._h, n_frames, C.c_void_p(d_clouds),
+                                                    offsets.ctypes.data_as(C.POINTER(C.c_uint64)), n_poses, _ptr(poses),
+                                                    C.c_void_p(d_multi or None), C.c_void_p(d_single or None))
+        self._check(rc, "bev_posed_bev_device_resident")
+
+    def posed_bev_batch(self, clouds, poses=None, want_multi=True, want_single=True):
+        """bev_posed_bev_batch on host clouds; returns (multi, single): (n_frames, max(1, n_poses), L, M, M) and
+        (n_frames, max(1, n_poses), M, M) uint8, None for the one that is not wanted."""
+        n = len(clouds)
+        clouds = [np.ascontiguousarray(f, dtype=POINT_DTYPE) for f in clouds]
+        n_poses, poses = self._poses(poses, n)
+        K = max(1, n_poses)
+        multi = np.empty((n, K, self.L, self.M, self.M), dtype=np.uint8) if want_multi else None
+        single = np.empty((n, K, self.M, self.M), dtype=np.uint8) if want_single else None
+        VP = C.c_void_p * max(n, 1)
+        pts = VP(*[f.ctypes.data if len(f) else None for f in clouds])
+        npts = (C.c_uint32 * max(n, 1))(*[len(f) for f in clouds])
+        m = VP(*[multi[i].ctypes.data for i in range(n)]) if want_multi else None
+        s = VP(*[single[i].ctypes.data for i in range(n)]) if want_single else None
+        rc = self.lib.bev_posed_bev_batch(self._h, n, pts, npts, n_poses, _ptr(poses), m, s)
+        self._check(rc, "bev_posed_bev_batch")
+        return multi, single
 
     def transform_cloud(self, cloud, m):
         cloud = np.ascontiguousarray(cloud, dtype=POINT_DTYPE)

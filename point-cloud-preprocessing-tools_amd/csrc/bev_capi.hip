@@ -653,6 +653,61 @@ int float_bev_frames(bev_ctx *c, int nf, const bev_point_t *d_clouds, const uint
     return BEV_OK;
 }
 
+/* The 24-layer and uint8 BEVs of nf frames on the context's stream: frames and poses as for float_bev_frames;
+ * nf * max(1, n_poses) images at d_multi and at d_single (nullptr: not wanted).  The table and the matrices go up once; the
+ * frames go in launch groups of consecutive whole frames whose grids fit the workspace cap: the group's planes are zeroed,
+ * k_posed_splat fills them, k_posed_expand turns them into the images, and stream order hands the workspace from group to
+ * group.  256 MiB is the size of the memory-side cache and bounds the workspace; it is not a tuned figure: in one run per
+ * setting, not alternated, one group per call was 3-5 % faster at 0 and 1 poses and 10 % at 8, and groups of 64 grids were a
+ * third slower (profiles/posed_bev_groups.txt). */
+constexpr size_t kPosedWsCap = (size_t)256 << 20;
+bool posed_bev_poses_ok(int n_poses, const float *h_poses)
+{
+    return n_poses >= 0 && n_poses <= BEV_POSED_BEV_MAX_POSES && (n_poses == 0 || h_poses);
+}
+int posed_bev_frames(bev_ctx *c, int nf, const bev_point_t *d_clouds, const uint64_t *offs, int n_poses, const float *h_poses,
+                     uint8_t *d_multi, uint8_t *d_single)
+{
+    if (nf == 0) return BEV_OK;
+    const size_t tab_bytes = ((size_t)nf + 1) * sizeof(ProjFrame), pose_bytes = (size_t)nf * n_poses * 12 * sizeof(float);
+    char *h = nullptr;
+    int rc = c->posed_tab.begin(c, tab_bytes + pose_bytes, 64 * 1024, reinterpret_cast<void **>(&h));
+    if (rc != BEV_OK) return rc;
+    ProjFrame *h_tab = reinterpret_cast<ProjFrame *>(h);
+    uint32_t blocks = 0;
+    rc = fill_proj_table(offs, nf, h_tab, &blocks);
+    if (rc != BEV_OK) return rc;
+    if (pose_bytes) memcpy(h + tab_bytes, h_poses, pose_bytes);
+    const size_t M = (size_t)c->geo.rp.mat_size, K = (size_t)std::max(1, n_poses), grid_bytes = 2 * M * M * sizeof(uint32_t);
+    const size_t cap_grids = c->posed_group > 0 ? (size_t)c->posed_group : std::max<size_t>(1, kPosedWsCap / grid_bytes);
+    const int per_group = (int)std::min<size_t>((size_t)nf, std::max<size_t>(1, cap_grids / K)); /* (every frame has K grids) */
+    rc = c->posed_ws.grow(c, (size_t)per_group * K * grid_bytes);
+    if (rc != BEV_OK) return rc;
+    rc = c->posed_tab.push(c, tab_bytes + pose_bytes);
+    if (rc != BEV_OK) return rc;
+    const char *d = static_cast<const char *>(c->posed_tab.dev);
+    const ProjFrame *d_tab = reinterpret_cast<const ProjFrame *>(d);
+    const float *d_poses = reinterpret_cast<const float *>(d + tab_bytes);
+    uint32_t *planes = static_cast<uint32_t *>(c->posed_ws.p);
+    for (int f0 = 0; f0 < nf; f0 += per_group) {
+        const int g = std::min(per_group, nf - f0);
+        const size_t grids = (size_t)g * K, first = (size_t)f0 * K;
+        HIPCK(c, hipMemsetAsync(planes, 0, grids * grid_bytes, c->stream));
+        {
+            ProfScope ps(c, K_POSED_SPLAT, g);
+            launch_posed_splat(d_clouds, d_tab + f0, g, h_tab[f0 + g].blk0 - h_tab[f0].blk0, d_poses + (size_t)f0 * n_poses * 12,
+                               n_poses, c->geo, planes, c->stream);
+        }
+        {
+            ProfScope ps(c, K_POSED_EXPAND, g);
+            launch_posed_expand(c->geo, planes, (int)grids, d_multi ? d_multi + first * c->multi_bytes : nullptr,
+                                d_single ? d_single + first * c->single_bytes : nullptr, c->stream);
+        }
+    }
+    HIPCK(c, hipGetLastError());
+    return BEV_OK;
+}
+
 /* bev_process_batch (kind < 0: in[f] holds n_pts[f] records) and bev_process_batch_xyzi (in[f] holds n_pts[f] raw returns
  * of `kind`): chunks of the batch go up, through the projection where they are raw, through the pipeline and down again */
 int process_batch_host(bev_ctx_t *c, int kind, int n_frames, const void *const *in, const uint32_t *n_pts,
@@ -875,6 +930,7 @@ int bev_create(bev_ctx_t **out, int device, const bev_params_t *p, int max_batch
         c->allow_stream = !(sm && atoi(sm) == 0);
         if (const char *mt = getenv("BEV_MODE_TTL")) c->mode_ttl = std::max(1, atoi(mt));
         if (const char *pg = getenv("BEV_PROJECT_GROUP")) c->kitti_group = std::max(1, std::min(64, atoi(pg)));
+        if (const char *pg = getenv("BEV_POSED_GROUP")) c->posed_group = std::max(1, std::min(65535, atoi(pg)));
     }
     {   /* EQUAL priorities (profiles/r06_experiments.txt): the launches of two such streams share the chip workgroup by workgroup,
          * 396-400 k frames/s where different priorities (the higher stream's launch dispatched first, whole) gave 384-386 k
@@ -978,6 +1034,9 @@ void bev_destroy(bev_ctx_t *c)
     c->kitti_ws.release();
     c->manip_tab.release();
     c->manip_grids.release();
+    c->posed_tab.release();
+    c->posed_ws.release();
+    c->posed_imgs.release();
     for (auto &s : c->prof_pool) {
         if (s.a) (void)hipEventDestroy(s.a);
         if (s.b) (void)hipEventDestroy(s.b);
@@ -1320,6 +1379,82 @@ int bev_float_bev_batch(bev_ctx_t *c, int n_frames, const bev_point_t *const *cl
     };
     rc = chunks();
     /* an error leaves nothing in flight either: copies of earlier chunks into out[] may still be on their way */
+    if (rc != BEV_OK) (void)hipDeviceSynchronize();
+    return rc;
+}
+
+int bev_posed_bev_device_resident(bev_ctx_t *c, int n_frames, const bev_point_t *d_clouds, const uint64_t *h_offsets,
+                                  int n_poses, const float *h_poses, uint8_t *d_multi, uint8_t *d_single)
+{
+    if (!c || n_frames < 0 || !h_offsets || !posed_bev_poses_ok(n_poses, h_poses)) return BEV_ERR_INVALID_ARG;
+    int rc = check_project_offsets(c, n_frames, h_offsets);
+    if (rc != BEV_OK) return rc;
+    if (n_frames == 0) return BEV_OK;
+    if ((!d_multi && !d_single) || (!d_clouds && h_offsets[n_frames] != h_offsets[0])) return BEV_ERR_INVALID_ARG;
+    HIPCK(c, hipSetDevice(c->device));
+    rc = flush_pending(c); /* (a bev_process_device_resident whose d_ordered this call reads has launched all its stages) */
+    if (rc != BEV_OK) return rc;
+    rc = wait_default_stream(c); /* (the upload or the fill of d_clouds, typically) */
+    if (rc != BEV_OK) return rc;
+    rc = posed_bev_frames(c, n_frames, d_clouds, h_offsets, n_poses, h_poses, d_multi, d_single);
+    if (rc != BEV_OK) return rc;
+    return record_tail(c); /* the stage streams of the next BEV call wait for it: it may overwrite d_clouds at once */
+}
+
+int bev_posed_bev_batch(bev_ctx_t *c, int n_frames, const bev_point_t *const *clouds, const uint32_t *n_pts, int n_poses,
+                        const float *h_poses, uint8_t *const *multi_out, uint8_t *const *single_out)
+{
+    if (!c || n_frames < 0 || (n_frames > 0 && (!clouds || !n_pts || (!multi_out && !single_out))) ||
+        !posed_bev_poses_ok(n_poses, h_poses))
+        return BEV_ERR_INVALID_ARG;
+    for (int f = 0; f < n_frames; ++f)
+        if ((multi_out && !multi_out[f]) || (single_out && !single_out[f]) || (n_pts[f] && !clouds[f])) return BEV_ERR_INVALID_ARG;
+    for (int f = 0; f < n_frames; ++f)
+        if ((size_t)n_pts[f] > std::max(c->max_points, (size_t)c->geo.S)) return BEV_ERR_TOO_LARGE;
+    if (n_frames == 0) return BEV_OK;
+    HIPCK(c, hipSetDevice(c->device));
+    { /* the later stages of sub-batches still in flight use the workspace this call is about to use */
+        const int rc_ = flush_pending(c);
+        if (rc_ != BEV_OK) return rc_;
+    }
+    int rc = ensure_staging(c);
+    if (rc != BEV_OK) return rc;
+    /* chunks as in bev_float_bev_batch: a chunk's uploads, its launches and its downloads follow the chunk before in the
+     * order of the context's stream */
+    const size_t K = (size_t)std::max(1, n_poses), multi_frame = multi_out ? K * c->multi_bytes : 0,
+                 single_frame = single_out ? K * c->single_bytes : 0, nb_max = (size_t)std::min(n_frames, c->max_batch);
+    rc = c->posed_imgs.grow(c, nb_max * (multi_frame + single_frame));
+    if (rc != BEV_OK) return rc;
+    uint8_t *d_multi = multi_out ? static_cast<uint8_t *>(c->posed_imgs.p) : nullptr;
+    uint8_t *d_single = single_out ? static_cast<uint8_t *>(c->posed_imgs.p) + nb_max * multi_frame : nullptr;
+    const auto chunks = [&]() -> int {
+        std::vector<uint64_t> off;
+        for (int f0 = 0; f0 < n_frames; f0 += c->max_batch) {
+            const int nb = std::min(c->max_batch, n_frames - f0);
+            off.assign((size_t)nb + 1, 0);
+            for (int f = 0; f < nb; ++f) {
+                off[f + 1] = off[f] + n_pts[f0 + f];
+                if (n_pts[f0 + f])
+                    HIPCK(c, hipMemcpyAsync(c->st_in + off[f], clouds[f0 + f], (size_t)n_pts[f0 + f] * sizeof(bev_point_t),
+                                            hipMemcpyHostToDevice, c->stream));
+            }
+            const int rc_ = posed_bev_frames(c, nb, c->st_in, off.data(), n_poses,
+                                             n_poses ? h_poses + (size_t)f0 * n_poses * 12 : nullptr, d_multi, d_single);
+            if (rc_ != BEV_OK) return rc_;
+            for (int f = 0; f < nb; ++f) {
+                if (multi_out)
+                    HIPCK(c, hipMemcpyAsync(multi_out[f0 + f], d_multi + (size_t)f * multi_frame, multi_frame,
+                                            hipMemcpyDeviceToHost, c->stream));
+                if (single_out)
+                    HIPCK(c, hipMemcpyAsync(single_out[f0 + f], d_single + (size_t)f * single_frame, single_frame,
+                                            hipMemcpyDeviceToHost, c->stream));
+            }
+        }
+        HIPCK(c, hipStreamSynchronize(c->stream));
+        return BEV_OK;
+    };
+    rc = chunks();
+    /* an error leaves nothing in flight either: copies of earlier chunks into the outputs may still be on their way */
     if (rc != BEV_OK) (void)hipDeviceSynchronize();
     return rc;
 }

@@ -229,6 +229,12 @@ struct bev_ctx {
      * bev_float_bev_batch's chunks, allocated on first use and grown on demand */
     bevh::UploadTable manip_tab;
     bevh::DevBuf manip_grids;
+    /* 24-layer and uint8 BEVs of a batch under per-frame poses (posed_bev_frames, bev_capi.hip): the frame and pose table of
+     * a call; the planes of one launch group; the images of bev_posed_bev_batch's chunks; all allocated on first use and
+     * grown on demand */
+    bevh::UploadTable posed_tab;
+    bevh::DevBuf posed_ws, posed_imgs;
+    int posed_group = 0; /* BEV_POSED_GROUP=1 .. 65535: grids per launch group (tests: results do not depend on it); 0: what fits kPosedWsCap */
 
     bevh::RegState reg;
 

@@ -331,6 +331,24 @@ BEVX_HD uint32_t bev_code(float px, float py, float pz, int label, const RasterP
     const uint32_t code = bev_code_from_bins(in ? x : 0, in ? y : 0, pz, rp);
     return in ? code : kSkip;
 }
+/* pcl::transformPointCloud with a row-major 3 x 4 [R | t] (CloudManip.cpp:119-128): col0 * x + (col1 * y + (col2 * z + col3)),
+ * the association of pcl::detail::Transformer<float>::se3 — what k_transform and k_float_bev_batch compute (contraction is
+ * off in this file: no product is fused into a sum) */
+BEVX_HD void transform_xyz(const float m[12], float x, float y, float z, float &tx, float &ty, float &tz)
+{
+    tx = m[0] * x + (m[1] * y + (m[2] * z + m[3]));
+    ty = m[4] * x + (m[5] * y + (m[6] * z + m[7]));
+    tz = m[8] * x + (m[9] * y + (m[10] * z + m[11]));
+}
+/* bev_code of a point moved by the pose m; m == nullptr: of its raw coordinates (NOT an identity pose: 0 * inf is NaN and
+ * -0.0 + 0.0 is +0.0).  tests/posedcheck rasters clouds with this on the host against the oracle's transform + rasters. */
+BEVX_HD uint32_t posed_code(float x, float y, float z, int label, const float *m, const RasterParams &rp)
+{
+    if (!m) return bev_code(x, y, z, label, rp);
+    float tx, ty, tz;
+    transform_xyz(m, x, y, z, tx, ty, tz);
+    return bev_code(tx, ty, tz, label, rp);
+}
 BEVX_HD int code_x(uint32_t c) { return (int)(c & 511u); }
 BEVX_HD int code_y(uint32_t c) { return (int)((c >> 9) & 511u); }
 BEVX_HD int code_h(uint32_t c) { return (int)((c >> 18) & 255u); }

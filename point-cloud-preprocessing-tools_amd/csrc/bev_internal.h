@@ -220,6 +220,8 @@ enum KernelId {
     K_KITTI_ASSIGN,    /* ... rings, last writer per slot */
     K_KITTI_GATHER,    /* ... the structured clouds */
     K_FLOAT_BEV_BATCH, /* the float BEV of a batch of frames under per-frame poses (bev_manip.h; K_FLOAT_BEV: one cloud) */
+    K_POSED_SPLAT,     /* the 24-layer and uint8 BEVs of a batch of frames under per-frame poses (bev_posed.h): points into the workspace planes */
+    K_POSED_EXPAND,    /* ... the planes into the images */
     K_COUNT
 };
 const char *kernel_name(int id);
@@ -312,6 +314,14 @@ void launch_project_kitti(int step, const float *xyzi, const ProjFrame *tab, int
  * caller on the same stream */
 void launch_float_bev_batch(const bev_point_t *clouds, const ProjFrame *tab, int nf, uint32_t blocks, const float *poses,
                             int n_poses, float interval, int M, bool skip_label0, float *grids, hipStream_t st);
+/* ---- 24-layer and uint8 BEVs of a batch of frames under per-frame poses (bev_posed.h) ----
+ * one launch group: the nf frames from tab[0] on (tab: a piece of the call's table, as for launch_project_batch; blocks: the
+ * workgroups of these frames, tab[nf].blk0 - tab[0].blk0), poses nf * n_poses matrices (n_poses == 0: none), planes
+ * nf * max(1, n_poses) grids of 2 * M * M words, zeroed by the caller on the same stream; then the planes of n_grids grids into
+ * images n_grids of multi / single (nullptr: not wanted) */
+void launch_posed_splat(const bev_point_t *clouds, const ProjFrame *tab, int nf, uint32_t blocks, const float *poses, int n_poses,
+                        const Geometry &g, uint32_t *planes, hipStream_t st);
+void launch_posed_expand(const Geometry &g, const uint32_t *planes, int n_grids, uint8_t *multi, uint8_t *single, hipStream_t st);
 void launch_angle_debug(const float *dx, const float *dy, const float *dz, uint8_t *out, size_t n, hipStream_t st);
 /* ---- registration front end (bev_regfront.h; DESIGN.md "Registration front end") ---- */
 constexpr int kRfThreads = 256;

@@ -38,6 +38,7 @@
 #include "bev_misc.h"
 #include "bev_project.h"
 #include "bev_manip.h"
+#include "bev_posed.h"
 #include "bev_reg_common.h"
 #include "bev_regfront.h"
 #include "bev_icp.h"
@@ -53,7 +54,7 @@ static const char *const kNames[K_COUNT] = {
     "k_probe", "k_walk_general", "k_walk_structured", "k_walk_colmajor", "k_walk_colmajor_gen", "k_verdict", "k_stage",
     "k_rf_cells", "k_rf_top", "k_rf_voxel", "k_rf_normals", "k_icp_grid", "k_icp", "k_icp_best",
     "k_fine_voxel", "k_fine_grid", "k_fine_icp", "k_kitti_crossings", "k_kitti_chain", "k_kitti_assign", "k_kitti_gather",
-    "k_float_bev_batch",
+    "k_float_bev_batch", "k_posed_splat", "k_posed_expand",
 };
 const char *kernel_name(int id) { return (id >= 0 && id < K_COUNT) ? kNames[id] : "?"; }
 
@@ -169,6 +170,9 @@ hipError_t configure_kernels(const Geometry &g)
     e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_bev_raster), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)raster_lds_bytes(g));
     if (e != hipSuccess) return e;
+    e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_posed_expand), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)raster_lds_bytes(g));
+    if (e != hipSuccess) return e;
     return hipFuncSetAttribute(reinterpret_cast<const void *>(k_bev_raster_dense),
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)raster_lds_bytes(g));
 }
@@ -274,6 +278,19 @@ void launch_float_bev_batch(const bev_point_t *clouds, const ProjFrame *tab, int
     hipLaunchKernelGGL(k_float_bev_batch, dim3(blocks), dim3(256), 0, st, clouds, tab, nf,
                        reinterpret_cast<const Affine34 *>(poses), n_poses, interval, M, skip_label0 ? 1 : 0,
                        reinterpret_cast<uint32_t *>(grids));
+}
+void launch_posed_splat(const bev_point_t *clouds, const ProjFrame *tab, int nf, uint32_t blocks, const float *poses, int n_poses,
+                        const Geometry &g, uint32_t *planes, hipStream_t st)
+{
+    if (blocks == 0 || nf == 0) return;
+    hipLaunchKernelGGL(k_posed_splat, dim3(blocks), dim3(256), 0, st, clouds, tab, nf,
+                       reinterpret_cast<const Affine34 *>(poses), n_poses, g.rp, planes);
+}
+void launch_posed_expand(const Geometry &g, const uint32_t *planes, int n_grids, uint8_t *multi, uint8_t *single, hipStream_t st)
+{
+    if (n_grids == 0) return;
+    hipLaunchKernelGGL(k_posed_expand, dim3((unsigned)n_grids * (unsigned)g.raster_bands), dim3(kRasterThreads),
+                       raster_lds_bytes(g), st, planes, multi, single, g.rp);
 }
 void launch_project_kitti(int step, const float *xyzi, const ProjFrame *tab, int nf, uint32_t n_max, const KittiWork &w,
                           bev_point_t *out, hipStream_t st)

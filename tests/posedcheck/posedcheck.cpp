@@ -1,0 +1,152 @@
+/*
+ * posedcheck.cpp — TEST HELPER (never shipped, never loaded by the product).
+ *
+ * Rasters clouds on the host with posed_code (csrc/bev_exact.h) — the per-point arithmetic of k_posed_splat — into the two
+ * planes the device keeps per grid (max heights, layer masks), expands them the way k_posed_expand's store does, and compares
+ * every byte of both images with oracle_multi_bev / oracle_single_bev of oracle_transform_cloud.  A stand-alone program:
+ * exit status 0 and a last line "posedcheck ok: ..." when every case agrees, 1 and the failing cases otherwise.
+ */
+#include <cstdio>
+#include <cstring>
+#include <vector>
+
+#include "../../include/bev_mi355x.h"
+#include "../../oracle/bev_oracle.h"
+#include "../../point-cloud-preprocessing-tools_amd/csrc/bev_exact.h"
+
+extern "C" size_t bev_synth_adversarial(const bev_params_t *p, uint64_t seed, uint32_t n_points, int with_nonfinite,
+                                        bev_point_t *out, size_t cap);
+
+using namespace bevx;
+static_assert(sizeof(oracle_point_t) == sizeof(bev_point_t), "one record layout");
+
+namespace {
+
+RasterParams raster_params(float height_res, float interval)
+{
+    RasterParams rp{};
+    rp.max_range_f = 112.0f; /* BatchMultiBevGen.cpp:266-269 */
+    rp.interval = interval;
+    rp.height_res = height_res;
+    rp.lidar_to_ground = 2.0f;
+    rp.mat_size = cvtt_f32(224.0f / interval);
+    rp.n_layers = 24;
+    rp.inv_interval = exact_reciprocal(interval);
+    rp.inv_height_res = exact_reciprocal(height_res);
+    /* (the bands cut the device's work, not the result: posed_code does not read them) */
+    rp.coarse = rp.fine = rp.mat_size / 8;
+    rp.z0 = rp.z1 = 0;
+    rp.bands = 8;
+    rp.coarse_magic = rp.fine_magic = small_div_magic(rp.coarse);
+    return rp;
+}
+
+/* one point at the centre of every cell of the 224 x 224 grid of interval 1.0 (bin b holds (x + 112) in [b - 1, b)); z steps
+ * through the centres of layers -2 .. 26 of the given height resolution; every 37th point has label 0 */
+std::vector<bev_point_t> every_cell_cloud(float height_res)
+{
+    std::vector<bev_point_t> c((size_t)224 * 224);
+    memset(c.data(), 0, c.size() * sizeof(bev_point_t));
+    for (int bx = 0; bx < 224; ++bx)
+        for (int by = 0; by < 224; ++by) {
+            const int i = bx * 224 + by;
+            bev_point_t &q = c[(size_t)i];
+            q.x = (float)bx - 112.5f;
+            q.y = (float)by - 112.5f;
+            q.z = (float)(i % 29 - 2 - 2) * height_res; /* layer = round(z / height_res + 2) */
+            q.label = (int16_t)(i % 37 == 0 ? 0 : 1);
+        }
+    return c;
+}
+
+struct Pose { float tx, ty, tz, yaw; };
+/* tests/test_float_bev_batch_gpu.py's POSES and FAR, then translations that put the every-cell cloud's points on cell and band
+ * edges (+-0.5) or exactly one cell / one row further (+-1.0) */
+const Pose kPoses[] = {{0, 0, 0, 0}, {1.5f, -2.25f, 0.125f, 30}, {-3, 4, 1, -45.5f}, {10, 20, -1, 180}, {0.1f, 0.2f, 0.3f, 359.9f},
+                       {150, 0, 0, 10},
+                       {1.0f, 0, 0, 0}, {-1.0f, 0, 0, 0}, {0, 1.0f, 0, 0}, {0, -1.0f, 0, 0},
+                       {0.5f, 0, 0, 0}, {-0.5f, 0, 0, 0}, {0, 0.5f, 0, 0}, {0, -0.5f, 0, 0}};
+
+/* both images of the cloud under m (nullptr: raw coordinates) through posed_code */
+void host_raster(const std::vector<bev_point_t> &cloud, const float *m, const RasterParams &rp, std::vector<uint8_t> &multi,
+                 std::vector<uint8_t> &single)
+{
+    const size_t M = (size_t)rp.mat_size, cells = M * M;
+    std::vector<uint32_t> hmax(cells, 0u), mask(cells, 0u);
+    for (const bev_point_t &q : cloud) {
+        const uint32_t c = posed_code(q.x, q.y, q.z, (int)q.label, m, rp);
+        if (c == kSkip) continue;
+        const size_t idx = (size_t)code_x(c) * M + (size_t)code_y(c);
+        if ((uint32_t)code_h(c) > hmax[idx]) hmax[idx] = (uint32_t)code_h(c);
+        if (code_layer(c) != kNoLayer) mask[idx] |= 1u << code_layer(c);
+    }
+    multi.assign((size_t)rp.n_layers * cells, 0);
+    single.assign(cells, 0);
+    for (size_t i = 0; i < cells; ++i) {
+        single[i] = (uint8_t)hmax[i];
+        for (int l = 0; l < rp.n_layers; ++l) multi[(size_t)l * cells + i] = (mask[i] >> l) & 1u ? 255 : 0;
+    }
+}
+
+} // namespace
+
+int main()
+{
+    int cases = 0, bad = 0;
+    size_t set_bytes = 0;
+    const char *const sensor_name[] = {"HDL_32E", "HDL_64E", "OS1_64"};
+    for (int kind = 0; kind < 3; ++kind) {
+        oracle_sensor_t sp;
+        if (oracle_sensor_params(kind, &sp) != 0) return 2;
+        bev_params_t bp{};
+        bp.n_scan = sp.n_scan;
+        bp.horizon_scan = sp.horizon_scan;
+        bp.ground_upper_scan = sp.ground_upper_scan;
+        bp.height_res = sp.height_res;
+        bp.interval = 1.0f;
+        bp.max_range = 112;
+        bp.n_layers = 24;
+        bp.lidar_to_ground = 2.0f;
+        std::vector<bev_point_t> adv(60000);
+        adv.resize(bev_synth_adversarial(&bp, 3, 60000, 1, adv.data(), adv.size()));
+        const std::vector<bev_point_t> clouds[2] = {adv, every_cell_cloud(sp.height_res)};
+        for (const float interval : {1.0f, 2.0f}) {
+            const RasterParams rp = raster_params(sp.height_res, interval);
+            const size_t M = (size_t)rp.mat_size;
+            for (int ci = 0; ci < 2; ++ci) {
+                const std::vector<bev_point_t> &cloud = clouds[ci];
+                std::vector<oracle_point_t> moved(cloud.size());
+                const int n_poses = (int)(sizeof kPoses / sizeof kPoses[0]);
+                for (int k = -1; k < n_poses; ++k) { /* -1: no pose */
+                    float m[12];
+                    const oracle_point_t *src = reinterpret_cast<const oracle_point_t *>(cloud.data());
+                    if (k >= 0) {
+                        oracle_yaw_translate_matrix(kPoses[k].tx, kPoses[k].ty, kPoses[k].tz, kPoses[k].yaw, m);
+                        oracle_transform_cloud(src, cloud.size(), m, moved.data());
+                        src = moved.data();
+                    }
+                    std::vector<uint8_t> want_multi(24 * M * M), want_single(M * M), multi, single;
+                    oracle_multi_bev(&sp, src, cloud.size(), interval, want_multi.data());
+                    oracle_single_bev(src, cloud.size(), interval, want_single.data());
+                    host_raster(cloud, k >= 0 ? m : nullptr, rp, multi, single);
+                    ++cases;
+                    for (uint8_t v : want_multi) set_bytes += v != 0;
+                    if (multi != want_multi || single != want_single) {
+                        ++bad;
+                        size_t dm = 0, ds = 0;
+                        for (size_t i = 0; i < multi.size(); ++i) dm += multi[i] != want_multi[i];
+                        for (size_t i = 0; i < single.size(); ++i) ds += single[i] != want_single[i];
+                        printf("MISMATCH %s interval %g cloud %d pose %d: %zu multi bytes, %zu single bytes\n", sensor_name[kind],
+                               (double)interval, ci, k, dm, ds);
+                    }
+                }
+            }
+        }
+    }
+    if (bad || set_bytes == 0) {
+        printf("posedcheck FAILED: %d of %d cases differ\n", bad, cases);
+        return 1;
+    }
+    printf("posedcheck ok: %d cases, %zu occupied bytes compared\n", cases, set_bytes);
+    return 0;
+}
