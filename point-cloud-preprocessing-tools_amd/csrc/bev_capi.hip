@@ -1,6 +1,9 @@
 /*
  * bev_capi.hip — context (bev_ctx.h), workspace and the extern "C" boundary declared in include/bev_mi355x.h, but for
  * the registration entry points (bev_capi_reg.hip).  Host-side only; the kernels are in bev_kernels.hip.
+ * The three batched calls over packed frames (projection, float BEV, posed BEVs) share one path here: the
+ * frame table (upload_packed_table), the bracket of the device-resident calls (resident_call) and the chunk loop of the
+ * host-buffer calls (packed_host_chunks).
  *
  * There is deliberately no CPU implementation behind these entry points: if
  * HIP cannot give us a device, bev_create() fails.
@@ -544,14 +547,28 @@ bool project_kind_ok(int kind)
     return kind == BEV_PROJECT_MULRAN_OS1_64 || kind == BEV_PROJECT_OXFORD_HDL_32E || kind == BEV_PROJECT_KITTI_HDL_64E;
 }
 
-/* The projection of nf frames on the context's stream: frame f = returns [offs[f], offs[f + 1]) of d_xyzi (offsets checked by
- * the caller).  Kinds 0 / 1: ONE launch, records at the same offsets of d_out.  KITTI: launch groups of kitti_group frames
- * over one workspace (stream order hands it from group to group), frame f's structured cloud at d_out + f * 64 * 2083. */
-/* The frame table of a launch over packed frames (k_project_batch, k_float_bev_batch): per frame its offset, its count and
- * the workgroups of kProjBlock points before it; entry nf closes the table with the launch's workgroups, also in *blocks.
+/* ---- the packed-frame path: batched calls over several clouds that lie one after the other in one device buffer ---------- */
+/* The frame table of a call over packed frames (packed_place, bev_dev.h) and, behind it in the same block, the call's poses,
+ * as the host filled them and where they are on the device. */
+struct PackedTable {
+    ProjFrame *host = nullptr;
+    const ProjFrame *dev = nullptr;
+    const float *d_poses = nullptr; /* 12 floats per frame and pose, behind the table */
+    size_t bytes = 0;
+    uint32_t blocks = 0; /* workgroups of kProjBlock points of a launch over all frames: host[nf].blk0 */
+    uint32_t n_max = 0;  /* the longest frame */
+};
+/* Fills t's host block (UploadTable::begin): per frame f = [offs[f], offs[f + 1]) (offsets checked by the caller) its offset,
+ * its count and the workgroups before it, entry nf closing the table; then the nf * n_poses matrices at h_poses.
  * BEV_ERR_TOO_LARGE for a grid that one launch cannot have (2^41 points in one call). */
-int fill_proj_table(const uint64_t *offs, int nf, ProjFrame *tab, uint32_t *blocks, uint32_t *n_max = nullptr)
+int fill_packed_table(bev_ctx *c, UploadTable &t, size_t min_cap, int nf, const uint64_t *offs, int n_poses, const float *h_poses,
+                      PackedTable *pt)
 {
+    const size_t tab_bytes = ((size_t)nf + 1) * sizeof(ProjFrame), pose_bytes = (size_t)nf * n_poses * 12 * sizeof(float);
+    char *h = nullptr;
+    const int rc = t.begin(c, tab_bytes + pose_bytes, min_cap, reinterpret_cast<void **>(&h));
+    if (rc != BEV_OK) return rc;
+    ProjFrame *tab = reinterpret_cast<ProjFrame *>(h);
     uint64_t b = 0;
     uint32_t m = 0;
     for (int f = 0; f < nf; ++f) {
@@ -562,33 +579,39 @@ int fill_proj_table(const uint64_t *offs, int nf, ProjFrame *tab, uint32_t *bloc
         if (b > 0x7fffffffull) return BEV_ERR_TOO_LARGE;
     }
     tab[nf] = ProjFrame{offs[nf], 0u, (uint32_t)b};
-    *blocks = (uint32_t)b;
-    if (n_max) *n_max = m;
+    if (pose_bytes) memcpy(h + tab_bytes, h_poses, pose_bytes);
+    const char *d = static_cast<const char *>(t.dev); /* (begin alone sets dev; push only copies into it) */
+    *pt = PackedTable{tab, reinterpret_cast<const ProjFrame *>(d), reinterpret_cast<const float *>(d + tab_bytes),
+                      tab_bytes + pose_bytes, (uint32_t)b, m};
     return BEV_OK;
 }
+/* ... and sends it up the context's stream.  Each call has an UploadTable of its own: a shared one would make a call wait for
+ * another call's upload event. */
+int upload_packed_table(bev_ctx *c, UploadTable &t, size_t min_cap, int nf, const uint64_t *offs, int n_poses,
+                        const float *h_poses, PackedTable *pt)
+{
+    const int rc = fill_packed_table(c, t, min_cap, nf, offs, n_poses, h_poses, pt);
+    return rc != BEV_OK ? rc : t.push(c, pt->bytes);
+}
 
+/* The projection of nf frames on the context's stream: frame f = returns [offs[f], offs[f + 1]) of d_xyzi (offsets checked by
+ * the caller).  Kinds 0 / 1: ONE launch, records at the same offsets of d_out.  KITTI: launch groups of kitti_group frames
+ * over one workspace (stream order hands it from group to group), frame f's structured cloud at d_out + f * 64 * 2083. */
 int project_frames(bev_ctx *c, int kind, int nf, const float *d_xyzi, const uint64_t *offs, bev_point_t *d_out)
 {
     if (nf == 0) return BEV_OK;
-    ProjFrame *h = nullptr;
-    const size_t bytes = ((size_t)nf + 1) * sizeof(ProjFrame);
-    int rc = c->proj_tab.begin(c, bytes, 1024 * sizeof(ProjFrame), reinterpret_cast<void **>(&h));
+    PackedTable pt;
+    int rc = upload_packed_table(c, c->proj_tab, 1024 * sizeof(ProjFrame), nf, offs, 0, nullptr, &pt);
     if (rc != BEV_OK) return rc;
-    uint32_t blocks = 0, n_max = 0;
-    rc = fill_proj_table(offs, nf, h, &blocks, &n_max);
-    if (rc != BEV_OK) return rc;
-    rc = c->proj_tab.push(c, bytes);
-    if (rc != BEV_OK) return rc;
-    const ProjFrame *d_tab = static_cast<const ProjFrame *>(c->proj_tab.dev);
     if (kind != BEV_PROJECT_KITTI_HDL_64E) {
         ProfScope ps(c, K_PROJECT, nf);
-        launch_project_batch(kind, d_xyzi, d_tab, nf, blocks, d_out, c->stream);
+        launch_project_batch(kind, d_xyzi, pt.dev, nf, pt.blocks, d_out, c->stream);
     } else {
         c->layout_hint = BEV_LAYOUT_STRUCTURED; /* what this writes are structured clouds (bev_set_layout_hint) */
         const size_t S = (size_t)bevx::kKittiRows * bevx::kKittiCols, G = (size_t)std::min(c->kitti_group, nf);
         KittiWork w{};
-        w.n_cap = n_max;
-        w.blocks_cap = (n_max + bevx::kKittiBlock - 1u) / bevx::kKittiBlock;
+        w.n_cap = pt.n_max;
+        w.blocks_cap = (pt.n_max + bevx::kKittiBlock - 1u) / bevx::kKittiBlock;
         const size_t sz[] = {G * sizeof(KittiHeader), G * w.n_cap * 4, G * w.blocks_cap * 4,
                              G * w.blocks_cap * bevx::kKittiListCap * 4, G * S * 4};
         void **const dst[] = {(void **)&w.hdr, (void **)&w.col, (void **)&w.cnt, (void **)&w.pos, (void **)&w.winner};
@@ -600,7 +623,7 @@ int project_frames(bev_ctx *c, int kind, int nf, const float *d_xyzi, const uint
             HIPCK(c, hipMemsetAsync(w.winner, 0, (size_t)g * S * sizeof(uint32_t), c->stream));
             for (int step = 0; step < 4; ++step) {
                 ProfScope ps(c, K_KITTI_CROSSINGS + step, g);
-                launch_project_kitti(step, d_xyzi, d_tab + f0, g, n_max, w, d_out + (size_t)f0 * S, c->stream);
+                launch_project_kitti(step, d_xyzi, pt.dev + f0, g, pt.n_max, w, d_out + (size_t)f0 * S, c->stream);
             }
         }
     }
@@ -608,20 +631,75 @@ int project_frames(bev_ctx *c, int kind, int nf, const float *d_xyzi, const uint
     return BEV_OK;
 }
 
-/* packed frames of a projection call: BEV_OK, or what the entry point returns */
-int check_project_offsets(const bev_ctx *c, int n_frames, const uint64_t *h_offsets)
+/* the arguments every call over packed frames of the caller's has: BEV_OK, or what the entry point returns */
+int check_packed_frames(const bev_ctx *c, int n_frames, const uint64_t *h_offsets)
 {
-    const uint64_t cap = std::max(c->max_points, (size_t)c->geo.S);
+    if (!c || n_frames < 0 || !h_offsets) return BEV_ERR_INVALID_ARG;
+    const uint64_t cap = cloud_cap(c);
     for (int f = 0; f < n_frames; ++f)
         if (h_offsets[f + 1] < h_offsets[f]) return BEV_ERR_INVALID_ARG;
     for (int f = 0; f < n_frames; ++f)
         if (h_offsets[f + 1] - h_offsets[f] > cap) return BEV_ERR_TOO_LARGE;
     return BEV_OK;
 }
-
-bool float_bev_poses_ok(int n_poses, const float *h_poses)
+/* ... and the calls over host clouds: their arrays */
+bool host_clouds_ok(int n_frames, const bev_point_t *const *clouds, const uint32_t *n_pts)
 {
-    return n_poses >= 0 && n_poses <= BEV_FLOAT_BEV_MAX_POSES && (n_poses == 0 || h_poses);
+    if (n_frames > 0 && (!clouds || !n_pts)) return false;
+    for (int f = 0; f < n_frames; ++f)
+        if (n_pts[f] && !clouds[f]) return false;
+    return true;
+}
+bool poses_ok(int n_poses, const float *h_poses, int max_poses)
+{
+    return n_poses >= 0 && n_poses <= max_poses && (n_poses == 0 || h_poses);
+}
+
+/* A call on packed frames in device memory of the caller's: asynchronous, on the context's stream.  flush_pending joins the
+ * stage streams into it, so a BEV call that still reads or writes the caller's buffers (a bev_process_device_resident whose
+ * d_ordered this call reads, say) has launched all its stages and comes first; then whatever the caller has queued on the
+ * default stream (the upload or the fill of its input, typically); then the body; and the stage streams of the next BEV call
+ * wait for what record_tail records: it may read this call's output, or overwrite its input, at once. */
+template <class Body>
+int resident_call(bev_ctx *c, Body body)
+{
+    int rc = begin_call(c, false);
+    if (rc != BEV_OK) return rc;
+    rc = wait_default_stream(c);
+    if (rc != BEV_OK) return rc;
+    rc = body();
+    if (rc != BEV_OK) return rc;
+    return record_tail(c);
+}
+
+/* The host route of a batched call over packed frames (after begin_call with the staging): chunks of max_batch clouds fit the
+ * input staging whatever their sizes.  A chunk's clouds are packed into st_in, one copy per non-empty cloud;
+ * body(f0, nb, off) launches the chunk's nb frames [off[f], off[f + 1]) of st_in and queues the downloads of their results;
+ * all of it follows the chunk before in the order of the context's stream, and one synchronisation ends the call.  An error
+ * leaves nothing in flight either: copies of earlier chunks into the caller's buffers may still be on their way. */
+template <class Body>
+int packed_host_chunks(bev_ctx *c, int n_frames, const bev_point_t *const *clouds, const uint32_t *n_pts, Body body)
+{
+    const auto chunks = [&]() -> int {
+        std::vector<uint64_t> off;
+        for (int f0 = 0; f0 < n_frames; f0 += c->max_batch) {
+            const int nb = std::min(c->max_batch, n_frames - f0);
+            off.assign((size_t)nb + 1, 0);
+            for (int f = 0; f < nb; ++f) {
+                off[f + 1] = off[f] + n_pts[f0 + f];
+                if (n_pts[f0 + f])
+                    HIPCK(c, hipMemcpyAsync(c->st_in + off[f], clouds[f0 + f], (size_t)n_pts[f0 + f] * sizeof(bev_point_t),
+                                            hipMemcpyHostToDevice, c->stream));
+            }
+            const int rc_ = body(f0, nb, off.data());
+            if (rc_ != BEV_OK) return rc_;
+        }
+        HIPCK(c, hipStreamSynchronize(c->stream));
+        return BEV_OK;
+    };
+    const int rc = chunks();
+    if (rc != BEV_OK) (void)hipDeviceSynchronize();
+    return rc;
 }
 
 /* The float BEV of nf frames on the context's stream: frame f = records [offs[f], offs[f + 1]) of d_clouds (offsets checked by
@@ -631,22 +709,13 @@ int float_bev_frames(bev_ctx *c, int nf, const bev_point_t *d_clouds, const uint
                      bool skip_label0, int n_poses, const float *h_poses, float *d_out)
 {
     if (nf == 0) return BEV_OK;
-    const size_t tab_bytes = ((size_t)nf + 1) * sizeof(ProjFrame), pose_bytes = (size_t)nf * n_poses * 12 * sizeof(float);
-    char *h = nullptr;
-    int rc = c->manip_tab.begin(c, tab_bytes + pose_bytes, 64 * 1024, reinterpret_cast<void **>(&h));
+    PackedTable pt;
+    const int rc = upload_packed_table(c, c->manip_tab, 64 * 1024, nf, offs, n_poses, h_poses, &pt);
     if (rc != BEV_OK) return rc;
-    uint32_t blocks = 0;
-    rc = fill_proj_table(offs, nf, reinterpret_cast<ProjFrame *>(h), &blocks);
-    if (rc != BEV_OK) return rc;
-    if (pose_bytes) memcpy(h + tab_bytes, h_poses, pose_bytes);
-    rc = c->manip_tab.push(c, tab_bytes + pose_bytes);
-    if (rc != BEV_OK) return rc;
-    const char *d = static_cast<const char *>(c->manip_tab.dev);
     HIPCK(c, hipMemsetAsync(d_out, 0, (size_t)nf * std::max(1, n_poses) * M * M * sizeof(float), c->stream));
     {
         ProfScope ps(c, K_FLOAT_BEV_BATCH, nf);
-        launch_float_bev_batch(d_clouds, reinterpret_cast<const ProjFrame *>(d), nf, blocks,
-                               reinterpret_cast<const float *>(d + tab_bytes), n_poses, interval, (int)M, skip_label0, d_out,
+        launch_float_bev_batch(d_clouds, pt.dev, nf, pt.blocks, pt.d_poses, n_poses, interval, (int)M, skip_label0, d_out,
                                c->stream);
     }
     HIPCK(c, hipGetLastError());
@@ -661,33 +730,20 @@ int float_bev_frames(bev_ctx *c, int nf, const bev_point_t *d_clouds, const uint
  * setting, not alternated, one group per call was 3-5 % faster at 0 and 1 poses and 10 % at 8, and groups of 64 grids were a
  * third slower (profiles/posed_bev_groups.txt). */
 constexpr size_t kPosedWsCap = (size_t)256 << 20;
-bool posed_bev_poses_ok(int n_poses, const float *h_poses)
-{
-    return n_poses >= 0 && n_poses <= BEV_POSED_BEV_MAX_POSES && (n_poses == 0 || h_poses);
-}
 int posed_bev_frames(bev_ctx *c, int nf, const bev_point_t *d_clouds, const uint64_t *offs, int n_poses, const float *h_poses,
                      uint8_t *d_multi, uint8_t *d_single)
 {
     if (nf == 0) return BEV_OK;
-    const size_t tab_bytes = ((size_t)nf + 1) * sizeof(ProjFrame), pose_bytes = (size_t)nf * n_poses * 12 * sizeof(float);
-    char *h = nullptr;
-    int rc = c->posed_tab.begin(c, tab_bytes + pose_bytes, 64 * 1024, reinterpret_cast<void **>(&h));
+    PackedTable pt;
+    int rc = fill_packed_table(c, c->posed_tab, 64 * 1024, nf, offs, n_poses, h_poses, &pt);
     if (rc != BEV_OK) return rc;
-    ProjFrame *h_tab = reinterpret_cast<ProjFrame *>(h);
-    uint32_t blocks = 0;
-    rc = fill_proj_table(offs, nf, h_tab, &blocks);
-    if (rc != BEV_OK) return rc;
-    if (pose_bytes) memcpy(h + tab_bytes, h_poses, pose_bytes);
     const size_t M = (size_t)c->geo.rp.mat_size, K = (size_t)std::max(1, n_poses), grid_bytes = 2 * M * M * sizeof(uint32_t);
     const size_t cap_grids = c->posed_group > 0 ? (size_t)c->posed_group : std::max<size_t>(1, kPosedWsCap / grid_bytes);
     const int per_group = (int)std::min<size_t>((size_t)nf, std::max<size_t>(1, cap_grids / K)); /* (every frame has K grids) */
-    rc = c->posed_ws.grow(c, (size_t)per_group * K * grid_bytes);
+    rc = c->posed_ws.grow(c, (size_t)per_group * K * grid_bytes); /* (a grow waits for the stream: before the table goes up) */
     if (rc != BEV_OK) return rc;
-    rc = c->posed_tab.push(c, tab_bytes + pose_bytes);
+    rc = c->posed_tab.push(c, pt.bytes);
     if (rc != BEV_OK) return rc;
-    const char *d = static_cast<const char *>(c->posed_tab.dev);
-    const ProjFrame *d_tab = reinterpret_cast<const ProjFrame *>(d);
-    const float *d_poses = reinterpret_cast<const float *>(d + tab_bytes);
     uint32_t *planes = static_cast<uint32_t *>(c->posed_ws.p);
     for (int f0 = 0; f0 < nf; f0 += per_group) {
         const int g = std::min(per_group, nf - f0);
@@ -695,8 +751,8 @@ int posed_bev_frames(bev_ctx *c, int nf, const bev_point_t *d_clouds, const uint
         HIPCK(c, hipMemsetAsync(planes, 0, grids * grid_bytes, c->stream));
         {
             ProfScope ps(c, K_POSED_SPLAT, g);
-            launch_posed_splat(d_clouds, d_tab + f0, g, h_tab[f0 + g].blk0 - h_tab[f0].blk0, d_poses + (size_t)f0 * n_poses * 12,
-                               n_poses, c->geo, planes, c->stream);
+            launch_posed_splat(d_clouds, pt.dev + f0, g, pt.host[f0 + g].blk0 - pt.host[f0].blk0,
+                               pt.d_poses + (size_t)f0 * n_poses * 12, n_poses, c->geo, planes, c->stream);
         }
         {
             ProfScope ps(c, K_POSED_EXPAND, g);
@@ -800,8 +856,7 @@ int bevh::ensure_staging(bev_ctx *c)
 {
     if (c->staging_ready) return BEV_OK;
     const size_t S = (size_t)c->geo.S;
-    const size_t per_frame = std::max(c->max_points, S);
-    c->st_in_elems = per_frame * (size_t)c->max_batch;
+    c->st_in_elems = cloud_cap(c) * (size_t)c->max_batch;
     HIPCK(c, hipMalloc((void **)&c->st_in, c->st_in_elems * sizeof(bev_point_t)));
     HIPCK(c, hipMalloc((void **)&c->st_ordered, (size_t)c->max_batch * S * sizeof(bev_point_t)));
     HIPCK(c, hipMalloc((void **)&c->st_multi, (size_t)c->max_batch * c->multi_bytes));
@@ -814,6 +869,14 @@ int bevh::ensure_staging(bev_ctx *c)
     c->downloader->start(c);
     c->staging_ready = true;
     return BEV_OK;
+}
+
+int bevh::begin_call(bev_ctx *c, bool staging)
+{
+    HIPCK(c, hipSetDevice(c->device));
+    const int rc = flush_pending(c);
+    if (rc != BEV_OK) return rc;
+    return staging ? ensure_staging(c) : BEV_OK;
 }
 
 /* ======================================================================== */
@@ -1048,8 +1111,7 @@ void bev_destroy(bev_ctx_t *c)
 int bev_synchronize(bev_ctx_t *c)
 {
     if (!c) return BEV_ERR_INVALID_ARG;
-    HIPCK(c, hipSetDevice(c->device));
-    int rc = flush_pending(c); /* the later stages of the last sub-batches */
+    const int rc = begin_call(c, false); /* the later stages of the last sub-batches */
     if (rc != BEV_OK) return rc;
     HIPCK(c, hipStreamSynchronize(c->stream));
     return BEV_OK;
@@ -1111,12 +1173,7 @@ int bev_order_cloud(bev_ctx_t *c, const bev_point_t *pts, uint32_t n_pts, bev_po
 {
     if (!c || !ordered_out || (n_pts && !pts)) return BEV_ERR_INVALID_ARG;
     if (n_pts > c->max_points) return BEV_ERR_TOO_LARGE;
-    HIPCK(c, hipSetDevice(c->device));
-    { /* the later stages of sub-batches still in flight use the workspace this call is about to use */
-        const int rc_ = flush_pending(c);
-        if (rc_ != BEV_OK) return rc_;
-    }
-    int rc = ensure_staging(c);
+    int rc = begin_call(c, true);
     if (rc != BEV_OK) return rc;
     const Geometry &g = c->geo;
     const size_t S = (size_t)g.S;
@@ -1152,12 +1209,7 @@ int bev_order_cloud(bev_ctx_t *c, const bev_point_t *pts, uint32_t n_pts, bev_po
 int bev_mark_ground(bev_ctx_t *c, bev_point_t *ordered, int8_t *ground_mat_out)
 {
     if (!c || !ordered) return BEV_ERR_INVALID_ARG;
-    HIPCK(c, hipSetDevice(c->device));
-    { /* the later stages of sub-batches still in flight use the workspace this call is about to use */
-        const int rc_ = flush_pending(c);
-        if (rc_ != BEV_OK) return rc_;
-    }
-    int rc = ensure_staging(c);
+    int rc = begin_call(c, true);
     if (rc != BEV_OK) return rc;
     const size_t S = (size_t)c->geo.S;
     HIPCK(c, hipMemcpyAsync(c->st_in, ordered, S * sizeof(bev_point_t), hipMemcpyHostToDevice, c->stream));
@@ -1173,13 +1225,8 @@ int bev_mark_ground(bev_ctx_t *c, bev_point_t *ordered, int8_t *ground_mat_out)
 static int raster_cloud(bev_ctx_t *c, const bev_point_t *cloud, uint32_t n, uint8_t *multi_out, uint8_t *single_out)
 {
     if (!c || (n && !cloud)) return BEV_ERR_INVALID_ARG;
-    if ((size_t)n > std::max(c->max_points, (size_t)c->geo.S)) return BEV_ERR_TOO_LARGE;
-    HIPCK(c, hipSetDevice(c->device));
-    { /* the later stages of sub-batches still in flight use the workspace this call is about to use */
-        const int rc_ = flush_pending(c);
-        if (rc_ != BEV_OK) return rc_;
-    }
-    int rc = ensure_staging(c);
+    if ((size_t)n > cloud_cap(c)) return BEV_ERR_TOO_LARGE;
+    int rc = begin_call(c, true);
     if (rc != BEV_OK) return rc;
     if (n) HIPCK(c, hipMemcpyAsync(c->st_in, cloud, (size_t)n * sizeof(bev_point_t), hipMemcpyHostToDevice, c->stream));
     {
@@ -1225,14 +1272,9 @@ int bev_project_xyzi(bev_ctx_t *c, int kind, const float *xyzi, uint32_t n, bev_
     const size_t n_out = bev_project_out_points(kind, n);
     if (!c || (n && !xyzi) || (n_out && !out)) return BEV_ERR_INVALID_ARG;
     if (!project_kind_ok(kind)) return BEV_ERR_INVALID_ARG;
-    if ((size_t)n > std::max(c->max_points, (size_t)c->geo.S)) return BEV_ERR_TOO_LARGE;
+    if ((size_t)n > cloud_cap(c)) return BEV_ERR_TOO_LARGE;
     if (n_out == 0) return BEV_OK;
-    HIPCK(c, hipSetDevice(c->device));
-    { /* the later stages of sub-batches still in flight use the workspace this call is about to use */
-        const int rc_ = flush_pending(c);
-        if (rc_ != BEV_OK) return rc_;
-    }
-    int rc = ensure_staging(c);
+    int rc = begin_call(c, true);
     if (rc != BEV_OK) return rc;
     /* raw floats are staged in the ordered-cloud staging buffer (16 B per point fit its 32 B per slot) */
     float *d_raw = reinterpret_cast<float *>(c->st_ordered);
@@ -1259,20 +1301,13 @@ size_t bev_project_batch_out_points(int kind, int n_frames, const uint64_t *h_of
 int bev_project_device_resident(bev_ctx_t *c, int kind, int n_frames, const float *d_xyzi, const uint64_t *h_offsets,
                                 bev_point_t *d_out)
 {
-    if (!c || !project_kind_ok(kind) || n_frames < 0 || !h_offsets) return BEV_ERR_INVALID_ARG;
-    int rc = check_project_offsets(c, n_frames, h_offsets);
+    if (!project_kind_ok(kind)) return BEV_ERR_INVALID_ARG;
+    const int rc = check_packed_frames(c, n_frames, h_offsets);
     if (rc != BEV_OK) return rc;
     if (n_frames == 0) return BEV_OK;
     const bool any_in = h_offsets[n_frames] != h_offsets[0], any_out = any_in || kind == BEV_PROJECT_KITTI_HDL_64E;
     if ((any_in && !d_xyzi) || (any_out && !d_out)) return BEV_ERR_INVALID_ARG;
-    HIPCK(c, hipSetDevice(c->device));
-    rc = flush_pending(c); /* (joins the stage streams into the context's stream: a BEV call that still reads d_out comes first) */
-    if (rc != BEV_OK) return rc;
-    rc = wait_default_stream(c); /* (the upload or the fill of d_xyzi, typically) */
-    if (rc != BEV_OK) return rc;
-    rc = project_frames(c, kind, n_frames, d_xyzi, h_offsets, d_out);
-    if (rc != BEV_OK) return rc;
-    return record_tail(c); /* the stage streams of the next BEV call wait for it: it may read d_out at once */
+    return resident_call(c, [&] { return project_frames(c, kind, n_frames, d_xyzi, h_offsets, d_out); });
 }
 
 size_t bev_float_bev_size(float interval)
@@ -1288,14 +1323,9 @@ int bev_float_bev(bev_ctx_t *c, const bev_point_t *cloud, uint32_t n, float inte
     if (!c || !out || (n && !cloud)) return BEV_ERR_INVALID_ARG;
     const size_t M = bev_float_bev_size(interval);
     if (M == 0) return BEV_ERR_UNSUPPORTED;
-    if ((size_t)n > std::max(c->max_points, (size_t)c->geo.S)) return BEV_ERR_TOO_LARGE;
+    if ((size_t)n > cloud_cap(c)) return BEV_ERR_TOO_LARGE;
     if (M * M > c->codes_elems) return BEV_ERR_UNSUPPORTED; /* the grid borrows the single-cloud code buffer */
-    HIPCK(c, hipSetDevice(c->device));
-    { /* the later stages of sub-batches still in flight use the workspace this call is about to use */
-        const int rc_ = flush_pending(c);
-        if (rc_ != BEV_OK) return rc_;
-    }
-    int rc = ensure_staging(c);
+    int rc = begin_call(c, true);
     if (rc != BEV_OK) return rc;
     float *grid = reinterpret_cast<float *>(c->codes);
     if (n) HIPCK(c, hipMemcpyAsync(c->st_in, cloud, (size_t)n * sizeof(bev_point_t), hipMemcpyHostToDevice, c->stream));
@@ -1313,163 +1343,101 @@ int bev_float_bev(bev_ctx_t *c, const bev_point_t *cloud, uint32_t n, float inte
 int bev_float_bev_device_resident(bev_ctx_t *c, int n_frames, const bev_point_t *d_clouds, const uint64_t *h_offsets,
                                   float interval, int skip_label0, int n_poses, const float *h_poses, float *d_out)
 {
-    if (!c || n_frames < 0 || !h_offsets || !float_bev_poses_ok(n_poses, h_poses)) return BEV_ERR_INVALID_ARG;
-    int rc = check_project_offsets(c, n_frames, h_offsets);
+    if (!poses_ok(n_poses, h_poses, BEV_FLOAT_BEV_MAX_POSES)) return BEV_ERR_INVALID_ARG;
+    const int rc = check_packed_frames(c, n_frames, h_offsets);
     if (rc == BEV_ERR_INVALID_ARG) return rc;
     const size_t M = bev_float_bev_size(interval);
     if (M == 0) return BEV_ERR_UNSUPPORTED;
-    if (rc != BEV_OK) return rc;
+    if (rc != BEV_OK) return rc; /* (a frame that is too large: behind the interval) */
     if (n_frames == 0) return BEV_OK;
     if (!d_out || (!d_clouds && h_offsets[n_frames] != h_offsets[0])) return BEV_ERR_INVALID_ARG;
-    HIPCK(c, hipSetDevice(c->device));
-    rc = flush_pending(c); /* (a bev_process_device_resident whose d_ordered this call reads has launched all its stages) */
-    if (rc != BEV_OK) return rc;
-    rc = wait_default_stream(c); /* (the upload or the fill of d_clouds, typically) */
-    if (rc != BEV_OK) return rc;
-    rc = float_bev_frames(c, n_frames, d_clouds, h_offsets, interval, M, skip_label0 != 0, n_poses, h_poses, d_out);
-    if (rc != BEV_OK) return rc;
-    return record_tail(c); /* the stage streams of the next BEV call wait for it: it may overwrite d_clouds at once */
+    return resident_call(c, [&] {
+        return float_bev_frames(c, n_frames, d_clouds, h_offsets, interval, M, skip_label0 != 0, n_poses, h_poses, d_out);
+    });
 }
 
 int bev_float_bev_batch(bev_ctx_t *c, int n_frames, const bev_point_t *const *clouds, const uint32_t *n_pts, float interval,
                         int skip_label0, int n_poses, const float *h_poses, float *const *out)
 {
-    if (!c || n_frames < 0 || (n_frames > 0 && (!clouds || !n_pts || !out)) || !float_bev_poses_ok(n_poses, h_poses))
+    if (!c || n_frames < 0 || !host_clouds_ok(n_frames, clouds, n_pts) || (n_frames > 0 && !out) ||
+        !poses_ok(n_poses, h_poses, BEV_FLOAT_BEV_MAX_POSES))
         return BEV_ERR_INVALID_ARG;
     for (int f = 0; f < n_frames; ++f)
-        if (!out[f] || (n_pts[f] && !clouds[f])) return BEV_ERR_INVALID_ARG;
+        if (!out[f]) return BEV_ERR_INVALID_ARG;
     const size_t M = bev_float_bev_size(interval);
     if (M == 0) return BEV_ERR_UNSUPPORTED;
     for (int f = 0; f < n_frames; ++f)
-        if ((size_t)n_pts[f] > std::max(c->max_points, (size_t)c->geo.S)) return BEV_ERR_TOO_LARGE;
+        if ((size_t)n_pts[f] > cloud_cap(c)) return BEV_ERR_TOO_LARGE;
     if (n_frames == 0) return BEV_OK;
-    HIPCK(c, hipSetDevice(c->device));
-    { /* the later stages of sub-batches still in flight use the workspace this call is about to use */
-        const int rc_ = flush_pending(c);
-        if (rc_ != BEV_OK) return rc_;
-    }
-    int rc = ensure_staging(c);
+    int rc = begin_call(c, true);
     if (rc != BEV_OK) return rc;
-    /* chunks of max_batch frames fit the input staging whatever their sizes; a chunk's uploads, its launch and its
-     * downloads follow the chunk before in the order of the context's stream */
     const size_t per_frame = (size_t)std::max(1, n_poses) * M * M;
     rc = c->manip_grids.grow(c, (size_t)std::min(n_frames, c->max_batch) * per_frame * sizeof(float));
     if (rc != BEV_OK) return rc;
     float *grids = static_cast<float *>(c->manip_grids.p);
-    const auto chunks = [&]() -> int {
-        std::vector<uint64_t> off;
-        for (int f0 = 0; f0 < n_frames; f0 += c->max_batch) {
-            const int nb = std::min(c->max_batch, n_frames - f0);
-            off.assign((size_t)nb + 1, 0);
-            for (int f = 0; f < nb; ++f) {
-                off[f + 1] = off[f] + n_pts[f0 + f];
-                if (n_pts[f0 + f])
-                    HIPCK(c, hipMemcpyAsync(c->st_in + off[f], clouds[f0 + f], (size_t)n_pts[f0 + f] * sizeof(bev_point_t),
-                                            hipMemcpyHostToDevice, c->stream));
-            }
-            const int rc_ = float_bev_frames(c, nb, c->st_in, off.data(), interval, M, skip_label0 != 0, n_poses,
-                                             n_poses ? h_poses + (size_t)f0 * n_poses * 12 : nullptr, grids);
-            if (rc_ != BEV_OK) return rc_;
-            for (int f = 0; f < nb; ++f)
-                HIPCK(c, hipMemcpyAsync(out[f0 + f], grids + (size_t)f * per_frame, per_frame * sizeof(float),
-                                        hipMemcpyDeviceToHost, c->stream));
-        }
-        HIPCK(c, hipStreamSynchronize(c->stream));
+    return packed_host_chunks(c, n_frames, clouds, n_pts, [&](int f0, int nb, const uint64_t *off) -> int {
+        const int rc_ = float_bev_frames(c, nb, c->st_in, off, interval, M, skip_label0 != 0, n_poses,
+                                         n_poses ? h_poses + (size_t)f0 * n_poses * 12 : nullptr, grids);
+        if (rc_ != BEV_OK) return rc_;
+        for (int f = 0; f < nb; ++f)
+            HIPCK(c, hipMemcpyAsync(out[f0 + f], grids + (size_t)f * per_frame, per_frame * sizeof(float), hipMemcpyDeviceToHost,
+                                    c->stream));
         return BEV_OK;
-    };
-    rc = chunks();
-    /* an error leaves nothing in flight either: copies of earlier chunks into out[] may still be on their way */
-    if (rc != BEV_OK) (void)hipDeviceSynchronize();
-    return rc;
+    });
 }
 
 int bev_posed_bev_device_resident(bev_ctx_t *c, int n_frames, const bev_point_t *d_clouds, const uint64_t *h_offsets,
                                   int n_poses, const float *h_poses, uint8_t *d_multi, uint8_t *d_single)
 {
-    if (!c || n_frames < 0 || !h_offsets || !posed_bev_poses_ok(n_poses, h_poses)) return BEV_ERR_INVALID_ARG;
-    int rc = check_project_offsets(c, n_frames, h_offsets);
+    if (!poses_ok(n_poses, h_poses, BEV_POSED_BEV_MAX_POSES)) return BEV_ERR_INVALID_ARG;
+    const int rc = check_packed_frames(c, n_frames, h_offsets);
     if (rc != BEV_OK) return rc;
     if (n_frames == 0) return BEV_OK;
     if ((!d_multi && !d_single) || (!d_clouds && h_offsets[n_frames] != h_offsets[0])) return BEV_ERR_INVALID_ARG;
-    HIPCK(c, hipSetDevice(c->device));
-    rc = flush_pending(c); /* (a bev_process_device_resident whose d_ordered this call reads has launched all its stages) */
-    if (rc != BEV_OK) return rc;
-    rc = wait_default_stream(c); /* (the upload or the fill of d_clouds, typically) */
-    if (rc != BEV_OK) return rc;
-    rc = posed_bev_frames(c, n_frames, d_clouds, h_offsets, n_poses, h_poses, d_multi, d_single);
-    if (rc != BEV_OK) return rc;
-    return record_tail(c); /* the stage streams of the next BEV call wait for it: it may overwrite d_clouds at once */
+    return resident_call(c, [&] { return posed_bev_frames(c, n_frames, d_clouds, h_offsets, n_poses, h_poses, d_multi, d_single); });
 }
 
 int bev_posed_bev_batch(bev_ctx_t *c, int n_frames, const bev_point_t *const *clouds, const uint32_t *n_pts, int n_poses,
                         const float *h_poses, uint8_t *const *multi_out, uint8_t *const *single_out)
 {
-    if (!c || n_frames < 0 || (n_frames > 0 && (!clouds || !n_pts || (!multi_out && !single_out))) ||
-        !posed_bev_poses_ok(n_poses, h_poses))
+    if (!c || n_frames < 0 || !host_clouds_ok(n_frames, clouds, n_pts) || (n_frames > 0 && !multi_out && !single_out) ||
+        !poses_ok(n_poses, h_poses, BEV_POSED_BEV_MAX_POSES))
         return BEV_ERR_INVALID_ARG;
     for (int f = 0; f < n_frames; ++f)
-        if ((multi_out && !multi_out[f]) || (single_out && !single_out[f]) || (n_pts[f] && !clouds[f])) return BEV_ERR_INVALID_ARG;
+        if ((multi_out && !multi_out[f]) || (single_out && !single_out[f])) return BEV_ERR_INVALID_ARG;
     for (int f = 0; f < n_frames; ++f)
-        if ((size_t)n_pts[f] > std::max(c->max_points, (size_t)c->geo.S)) return BEV_ERR_TOO_LARGE;
+        if ((size_t)n_pts[f] > cloud_cap(c)) return BEV_ERR_TOO_LARGE;
     if (n_frames == 0) return BEV_OK;
-    HIPCK(c, hipSetDevice(c->device));
-    { /* the later stages of sub-batches still in flight use the workspace this call is about to use */
-        const int rc_ = flush_pending(c);
-        if (rc_ != BEV_OK) return rc_;
-    }
-    int rc = ensure_staging(c);
+    int rc = begin_call(c, true);
     if (rc != BEV_OK) return rc;
-    /* chunks as in bev_float_bev_batch: a chunk's uploads, its launches and its downloads follow the chunk before in the
-     * order of the context's stream */
     const size_t K = (size_t)std::max(1, n_poses), multi_frame = multi_out ? K * c->multi_bytes : 0,
                  single_frame = single_out ? K * c->single_bytes : 0, nb_max = (size_t)std::min(n_frames, c->max_batch);
     rc = c->posed_imgs.grow(c, nb_max * (multi_frame + single_frame));
     if (rc != BEV_OK) return rc;
     uint8_t *d_multi = multi_out ? static_cast<uint8_t *>(c->posed_imgs.p) : nullptr;
     uint8_t *d_single = single_out ? static_cast<uint8_t *>(c->posed_imgs.p) + nb_max * multi_frame : nullptr;
-    const auto chunks = [&]() -> int {
-        std::vector<uint64_t> off;
-        for (int f0 = 0; f0 < n_frames; f0 += c->max_batch) {
-            const int nb = std::min(c->max_batch, n_frames - f0);
-            off.assign((size_t)nb + 1, 0);
-            for (int f = 0; f < nb; ++f) {
-                off[f + 1] = off[f] + n_pts[f0 + f];
-                if (n_pts[f0 + f])
-                    HIPCK(c, hipMemcpyAsync(c->st_in + off[f], clouds[f0 + f], (size_t)n_pts[f0 + f] * sizeof(bev_point_t),
-                                            hipMemcpyHostToDevice, c->stream));
-            }
-            const int rc_ = posed_bev_frames(c, nb, c->st_in, off.data(), n_poses,
-                                             n_poses ? h_poses + (size_t)f0 * n_poses * 12 : nullptr, d_multi, d_single);
-            if (rc_ != BEV_OK) return rc_;
-            for (int f = 0; f < nb; ++f) {
-                if (multi_out)
-                    HIPCK(c, hipMemcpyAsync(multi_out[f0 + f], d_multi + (size_t)f * multi_frame, multi_frame,
-                                            hipMemcpyDeviceToHost, c->stream));
-                if (single_out)
-                    HIPCK(c, hipMemcpyAsync(single_out[f0 + f], d_single + (size_t)f * single_frame, single_frame,
-                                            hipMemcpyDeviceToHost, c->stream));
-            }
+    return packed_host_chunks(c, n_frames, clouds, n_pts, [&](int f0, int nb, const uint64_t *off) -> int {
+        const int rc_ = posed_bev_frames(c, nb, c->st_in, off, n_poses, n_poses ? h_poses + (size_t)f0 * n_poses * 12 : nullptr,
+                                         d_multi, d_single);
+        if (rc_ != BEV_OK) return rc_;
+        for (int f = 0; f < nb; ++f) {
+            if (multi_out)
+                HIPCK(c, hipMemcpyAsync(multi_out[f0 + f], d_multi + (size_t)f * multi_frame, multi_frame, hipMemcpyDeviceToHost,
+                                        c->stream));
+            if (single_out)
+                HIPCK(c, hipMemcpyAsync(single_out[f0 + f], d_single + (size_t)f * single_frame, single_frame,
+                                        hipMemcpyDeviceToHost, c->stream));
         }
-        HIPCK(c, hipStreamSynchronize(c->stream));
         return BEV_OK;
-    };
-    rc = chunks();
-    /* an error leaves nothing in flight either: copies of earlier chunks into the outputs may still be on their way */
-    if (rc != BEV_OK) (void)hipDeviceSynchronize();
-    return rc;
+    });
 }
 
 int bev_transform_cloud(bev_ctx_t *c, const bev_point_t *cloud, uint32_t n, const float *m, bev_point_t *out)
 {
     if (!c || !m || (n && (!cloud || !out))) return BEV_ERR_INVALID_ARG;
-    if ((size_t)n > std::max(c->max_points, (size_t)c->geo.S)) return BEV_ERR_TOO_LARGE;
+    if ((size_t)n > cloud_cap(c)) return BEV_ERR_TOO_LARGE;
     if (n == 0) return BEV_OK;
-    HIPCK(c, hipSetDevice(c->device));
-    { /* the later stages of sub-batches still in flight use the workspace this call is about to use */
-        const int rc_ = flush_pending(c);
-        if (rc_ != BEV_OK) return rc_;
-    }
-    int rc = ensure_staging(c);
+    int rc = begin_call(c, true);
     if (rc != BEV_OK) return rc;
     /* in place in the input staging (every thread reads and writes its own point) */
     HIPCK(c, hipMemcpyAsync(c->st_in, cloud, (size_t)n * sizeof(bev_point_t), hipMemcpyHostToDevice, c->stream));
@@ -1559,11 +1527,8 @@ int bev_debug_get_cell_avg(bev_ctx_t *c, int first_frame, int n_frames, float *o
 {
     if (!c || !out || first_frame < 0 || n_frames < 0 || first_frame + n_frames > c->last_sub_frames)
         return BEV_ERR_INVALID_ARG;
-    HIPCK(c, hipSetDevice(c->device));
-    { /* the later stages of sub-batches still in flight use the workspace this call is about to use */
-        const int rc_ = flush_pending(c);
-        if (rc_ != BEV_OK) return rc_;
-    }
+    const int rc = begin_call(c, false);
+    if (rc != BEV_OK) return rc;
     HIPCK(c, hipStreamSynchronize(c->stream));
     if (!c->last_avg) return BEV_ERR_INVALID_ARG;
     HIPCK(c, hipMemcpy(out, c->last_avg + (size_t)first_frame * bevx::kGridCells,
@@ -1575,11 +1540,8 @@ int bev_debug_get_frame_info(bev_ctx_t *c, int first_frame, int n_frames, uint32
 {
     if (!c || !out || first_frame < 0 || n_frames < 0 || first_frame + n_frames > c->last_sub_frames || !c->last_info)
         return BEV_ERR_INVALID_ARG;
-    HIPCK(c, hipSetDevice(c->device));
-    { /* the later stages of sub-batches still in flight use the workspace this call is about to use */
-        const int rc_ = flush_pending(c);
-        if (rc_ != BEV_OK) return rc_;
-    }
+    const int rc = begin_call(c, false);
+    if (rc != BEV_OK) return rc;
     HIPCK(c, hipStreamSynchronize(c->stream));
     HIPCK(c, hipMemcpy(out, c->last_info + first_frame, (size_t)n_frames * sizeof(FrameInfo), hipMemcpyDeviceToHost));
     return BEV_OK;
@@ -1589,11 +1551,8 @@ int bev_debug_get_code_overflow(bev_ctx_t *c, int first_frame, int n_frames, uin
 {
     if (!c || !out || first_frame < 0 || n_frames < 0 || first_frame + n_frames > c->last_sub_frames || !c->last_ncode)
         return BEV_ERR_INVALID_ARG;
-    HIPCK(c, hipSetDevice(c->device));
-    { /* the later stages of sub-batches still in flight use the workspace this call is about to use */
-        const int rc_ = flush_pending(c);
-        if (rc_ != BEV_OK) return rc_;
-    }
+    const int rc = begin_call(c, false);
+    if (rc != BEV_OK) return rc;
     HIPCK(c, hipStreamSynchronize(c->stream));
     const size_t per = (size_t)c->geo.emitters * c->geo.raster_bands;
     std::vector<uint32_t> counts((size_t)n_frames * per);

@@ -2,7 +2,7 @@
  * bev_capi_reg.hip — the registration half of the extern "C" boundary declared in include/bev_mi355x.h: the front end
  * (top-part flatten, voxel grid, 2-D normals), coarse point-to-plane ICP (§6c) and the fine stage (§6d).
  * Host-side only; the kernels are in bev_kernels.hip (bev_reg_common.h, bev_regfront.h, bev_icp.h, bev_fine.h).  With
- * the BEV pipeline of bev_capi.hip it shares the context (bev_ctx.h), its stream and flush_pending.
+ * the BEV pipeline of bev_capi.hip it shares the context (bev_ctx.h), its stream and the call prologue (begin_call).
  */
 #include <algorithm>
 #include <cfloat>
@@ -113,7 +113,7 @@ int ensure_rf(bev_ctx *c)
 {
     RegState &r = c->reg;
     if (r.rf_buf.p) return BEV_OK;
-    const size_t B = (size_t)c->max_batch, P = std::max(c->max_points, (size_t)c->geo.S), Q = P;
+    const size_t B = (size_t)c->max_batch, P = cloud_cap(c), Q = P;
     const size_t sz[] = {B * P * 8, B * 2 * P * 8, B * kRfCells * 4, B * (kRfCells + 1) * 4, B * (kRfCells + 1) * 4,
                          B * Q * 16, B * Q * 16, B * Q * 4, B * (Q + 1) * 4, B * sizeof(RfFrameMeta), P * 32};
     void **const dst[] = {(void **)&r.rf.keys, (void **)&r.rf.scr, (void **)&r.rf.cell_cnt, (void **)&r.rf.cell_off,
@@ -125,6 +125,12 @@ int ensure_rf(bev_ctx *c)
     r.rf.P = P;
     r.rf.Q = Q;
     return BEV_OK;
+}
+/* how the front end's entry points begin, behind their argument checks */
+int rf_begin(bev_ctx *c)
+{
+    const int rc = begin_call(c, false);
+    return rc != BEV_OK ? rc : ensure_rf(c);
 }
 
 /* the chain on nf <= max_batch frames of the workspace: top part -> voxel grid -> normals (PointNormal at out) */
@@ -158,25 +164,17 @@ extern "C" {
 /* ---- registration front end ------------------------------------------------------------------------------------------ */
 size_t bev_regfront_max_out(size_t n) { return n / 5 + 51; }
 
-#define RF_PROLOGUE(c)                                                                                                   \
-    do {                                                                                                                 \
-        HIPCK(c, hipSetDevice(c->device));                                                                               \
-        const int rc_ = flush_pending(c); /* (joins both stage streams into the context's stream) */                    \
-        if (rc_ != BEV_OK) return rc_;                                                                                   \
-        const int rc2_ = ensure_rf(c);                                                                                   \
-        if (rc2_ != BEV_OK) return rc2_;                                                                                 \
-    } while (0)
-
 static bool rf_positive(float v) { return std::isfinite(v) && v > 0.0f; }
 
 int bev_top_part_flatten(bev_ctx_t *c, const bev_point_t *cloud, uint32_t n, float *out, uint32_t *n_out)
 {
     if (!c || !n_out || (n && (!cloud || !out))) return BEV_ERR_INVALID_ARG;
-    if ((size_t)n > std::max(c->max_points, (size_t)c->geo.S)) return BEV_ERR_TOO_LARGE;
+    if ((size_t)n > cloud_cap(c)) return BEV_ERR_TOO_LARGE;
     *n_out = 0;
-    RF_PROLOGUE(c);
+    int rc = rf_begin(c);
+    if (rc != BEV_OK) return rc;
     if (n == 0) return BEV_OK;
-    int rc = ensure_staging(c);
+    rc = ensure_staging(c);
     if (rc != BEV_OK) return rc;
     HIPCK(c, hipMemcpyAsync(c->st_in, cloud, (size_t)n * sizeof(bev_point_t), hipMemcpyHostToDevice, c->stream));
     RfIn in{c->st_in, nullptr, n, n};
@@ -200,9 +198,10 @@ int bev_top_part_flatten(bev_ctx_t *c, const bev_point_t *cloud, uint32_t n, flo
 int bev_voxel_grid_xyz(bev_ctx_t *c, const float *xyz, uint32_t n, float leaf, float *out, uint32_t *n_out)
 {
     if (!c || !n_out || (n && (!xyz || !out)) || !rf_positive(leaf)) return BEV_ERR_INVALID_ARG;
-    if ((size_t)n > std::max(c->max_points, (size_t)c->geo.S)) return BEV_ERR_TOO_LARGE;
+    if ((size_t)n > cloud_cap(c)) return BEV_ERR_TOO_LARGE;
     *n_out = 0;
-    RF_PROLOGUE(c);
+    const int rc = rf_begin(c);
+    if (rc != BEV_OK) return rc;
     if (n == 0) return BEV_OK;
     RfFrameMeta meta{};
     meta.m = n;
@@ -226,8 +225,9 @@ int bev_normals_2d(bev_ctx_t *c, const float *xyz, uint32_t n, int k_search, flo
     if (!c || (n && (!xyz || !out))) return BEV_ERR_INVALID_ARG;
     if (k_search != 0) return BEV_ERR_UNSUPPORTED;
     if (!rf_positive(radius)) return BEV_ERR_INVALID_ARG;
-    if ((size_t)n > std::max(c->max_points, (size_t)c->geo.S)) return BEV_ERR_TOO_LARGE;
-    RF_PROLOGUE(c);
+    if ((size_t)n > cloud_cap(c)) return BEV_ERR_TOO_LARGE;
+    const int rc = rf_begin(c);
+    if (rc != BEV_OK) return rc;
     if (n == 0) return BEV_OK;
     const float vp[2] = {viewpoint ? viewpoint[0] : 0.0f, viewpoint ? viewpoint[1] : 0.0f};
     RfFrameMeta meta{};
@@ -251,7 +251,7 @@ int bev_registration_front_device_resident(bev_ctx_t *c, int n_frames, const bev
 {
     if (!c || n_frames < 0 || !rf_positive(leaf) || !rf_positive(radius)) return BEV_ERR_INVALID_ARG;
     if (n_frames > 0 && (!d_clouds || !d_out || !d_counts)) return BEV_ERR_INVALID_ARG;
-    const size_t P = std::max(c->max_points, (size_t)c->geo.S);
+    const size_t P = cloud_cap(c);
     uint32_t n_max = (uint32_t)c->geo.S;
     if (h_offsets) {
         n_max = 0;
@@ -261,9 +261,10 @@ int bev_registration_front_device_resident(bev_ctx_t *c, int n_frames, const bev
         }
     }
     if (n_frames > 0 && out_stride < bev_regfront_max_out(n_max)) return BEV_ERR_INVALID_ARG;
-    RF_PROLOGUE(c);
+    int rc = rf_begin(c);
+    if (rc != BEV_OK) return rc;
     if (n_frames == 0) return BEV_OK;
-    int rc = wait_default_stream(c); /* (the upload of packed clouds, typically) */
+    rc = wait_default_stream(c); /* (the upload of packed clouds, typically) */
     if (rc != BEV_OK) return rc;
     const uint64_t *d_offs = nullptr;
     if (h_offsets) {
@@ -294,7 +295,6 @@ int bev_registration_front_device_resident(bev_ctx_t *c, int n_frames, const bev
     }
     return record_tail(c);
 }
-#undef RF_PROLOGUE
 
 /* ---- coarse point-to-plane ICP --------------------------------------------------------------------------------------- */
 bev_icp_params_t bev_icp_coarse_defaults(void)
@@ -363,8 +363,7 @@ int bev_icp_point_to_plane(bev_ctx_t *c, const float *src, uint32_t n_src, const
 {
     const bev_icp_params_t prm = params ? *params : bev_icp_coarse_defaults();
     if (!c || !result || (n_src && !src) || (n_tgt && !tgt) || !icp_params_ok(prm)) return BEV_ERR_INVALID_ARG;
-    HIPCK(c, hipSetDevice(c->device));
-    int rc = flush_pending(c);
+    int rc = begin_call(c, false);
     if (rc != BEV_OK) return rc;
     const size_t stride = std::max<size_t>(std::max(n_src, n_tgt), 1);
     const size_t need = 2 * stride * 48 + 256 + sizeof(bev_icp_result_t);
@@ -402,8 +401,7 @@ int bev_coarse_registration_device_resident(bev_ctx_t *c, int n_frames, const vo
         if (!d_pn || !d_counts || !h_matches || !d_results || !d_best || stride == 0) return BEV_ERR_INVALID_ARG;
         if (!matches_in_range(h_matches, n_matches, n_frames)) return BEV_ERR_INVALID_ARG;
     }
-    HIPCK(c, hipSetDevice(c->device));
-    int rc = flush_pending(c); /* (joins both stage streams into the context's stream) */
+    int rc = begin_call(c, false);
     if (rc != BEV_OK) return rc;
     if (n_matches == 0) return BEV_OK;
     rc = wait_default_stream(c);
@@ -544,8 +542,7 @@ int bev_voxel_grid_irct(bev_ctx_t *c, const bev_point_t *cloud, uint32_t n, floa
 {
     if (!c || !n_out || (n && (!cloud || !out)) || !(std::isfinite(leaf) && leaf > 0.0f)) return BEV_ERR_INVALID_ARG;
     *n_out = 0;
-    HIPCK(c, hipSetDevice(c->device));
-    int rc = flush_pending(c);
+    int rc = begin_call(c, false);
     if (rc != BEV_OK) return rc;
     if (n == 0) return BEV_OK;
     size_t off = 0;
@@ -571,8 +568,7 @@ int bev_icp_point_to_point(bev_ctx_t *c, const bev_point_t *src, uint32_t n_src,
 {
     const bev_icp_params_t prm = params ? *params : bev_icp_fine_defaults();
     if (!c || !result || (n_src && !src) || (n_tgt && !tgt) || !icp_params_ok(prm)) return BEV_ERR_INVALID_ARG;
-    HIPCK(c, hipSetDevice(c->device));
-    int rc = flush_pending(c);
+    int rc = begin_call(c, false);
     if (rc != BEV_OK) return rc;
     const size_t Pn = std::max<size_t>(std::max(n_src, n_tgt), 1);
     std::vector<FineProblem> probs(1);
@@ -616,8 +612,7 @@ int bev_fine_registration_device_resident(bev_ctx_t *c, int n_frames, const bev_
             for (int f = 0; f < n_frames; ++f)
                 if (h_offsets[f + 1] < h_offsets[f] || h_offsets[f + 1] - h_offsets[f] > 0xffffffffull) return BEV_ERR_INVALID_ARG;
     }
-    HIPCK(c, hipSetDevice(c->device));
-    int rc = flush_pending(c); /* (joins both stage streams into the context's stream) */
+    int rc = begin_call(c, false);
     if (rc != BEV_OK) return rc;
     if (n_matches == 0) return BEV_OK;
     rc = wait_default_stream(c);

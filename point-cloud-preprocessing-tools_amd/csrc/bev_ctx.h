@@ -1,11 +1,13 @@
 /*
  * bev_ctx.h — the context behind bev_ctx_t and what the two files of the C ABI share: bev_capi.hip (the context, the BEV
- * pipeline and the single-cloud entry points) and bev_capi_reg.hip (the registration entry points).  Private, like
+ * pipeline and the single-cloud entry points) and bev_capi_reg.hip (the registration entry points) — among it the prologue
+ * of every call outside the fused pipeline (begin_call) and the bound on a cloud's points (cloud_cap).  Private, like
  * bev_internal.h.  The types live in a named namespace: struct bev_ctx is one type in both translation units.
  */
 #ifndef BEV_CTX_H
 #define BEV_CTX_H
 
+#include <algorithm>
 #include <condition_variable>
 #include <cstring>
 #include <deque>
@@ -269,8 +271,16 @@ struct ProfScope {
     ~ProfScope();
 };
 
+/* the most points a cloud may have in every call but the pipeline's own (which take max_points): a structured cloud of S
+ * records always fits */
+inline size_t cloud_cap(const bev_ctx *c) { return std::max(c->max_points, (size_t)c->geo.S); }
+
 /* launches what is left of every pending sub-batch, then joins the stage streams into the context's stream */
 int flush_pending(bev_ctx *c);
+/* How every entry point outside the fused pipeline begins, behind its argument checks: the calling thread's device;
+ * flush_pending (the later stages of sub-batches still in flight use the workspace the call is about to use, and the call's
+ * work on the context's stream comes behind theirs); staging: the staging buffers of the host-buffer calls (ensure_staging). */
+int begin_call(bev_ctx *c, bool staging);
 /* device pointers from the caller: whatever it has queued on the default stream up to now (the upload or the fill of these
  * very buffers, typically) comes before what the context's stream is given next */
 int wait_default_stream(bev_ctx *c);

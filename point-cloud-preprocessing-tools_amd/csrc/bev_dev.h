@@ -1,5 +1,5 @@
 /*
- * bev_dev.h — device helpers shared by the kernels: block -> (frame, tile) mapping, cache-policy loads and stores, LDS-only barrier, LDS-DMA, counted waits, BEV codes with compile-time reciprocal choice
+ * bev_dev.h — device helpers shared by the kernels: block -> (frame, tile) mapping, workgroup -> place in packed frames and its record loader, cache-policy loads and stores, LDS-only barrier, LDS-DMA, counted waits, BEV codes with compile-time reciprocal choice
  * Part of the device code of libbev_mi355x.so; included by bev_kernels.hip only (one translation unit).
  */
 #ifndef BEV_DEV_H
@@ -25,6 +25,43 @@ __device__ __forceinline__ bool map_block_xcd(int b, int nf, int tiles, int &f, 
     return f < nf;
 }
 static inline int xcd_grid(int nf, int tiles) { return 8 * ((nf + 7) / 8) * tiles; }
+
+/* Packed frames: several clouds one after the other in one buffer, described by a table of nf + 1 ProjFrame (bev_internal.h:
+ * offset, count, workgroups of kProjBlock points before the frame; entry nf closes it with the launch's workgroups).
+ * packed_place: workgroup bid of such a launch -> its frame f, the frame's count n and offset off, and k0, the first of the
+ * thread's kProjPerThread points, which lie 256 apart within the frame.  A binary search for tab[f].blk0 <= bid <
+ * tab[f + 1].blk0 over uniform addresses (scalar loads): empty frames share their successor's count and are passed over. */
+struct PackedPlace {
+    int f;
+    uint32_t n, k0;
+    uint64_t off;
+};
+__device__ __forceinline__ PackedPlace packed_place(const ProjFrame *__restrict__ tab, int nf, uint32_t bid)
+{
+    int lo = 0, hi = nf;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (tab[mid].blk0 <= bid) lo = mid;
+        else hi = mid;
+    }
+    return PackedPlace{lo, tab[lo].n, (bid - tab[lo].blk0) * (uint32_t)kProjBlock + threadIdx.x, tab[lo].off};
+}
+/* The thread's kProjPerThread records of a frame at src, every load in flight before the first use: the first half of a
+ * record (x, y, z, intensity) and, where want_label, of the second half the word with the label; else, and for a point past
+ * the frame's end, pad_label (and zeros). */
+__device__ __forceinline__ void load_packed_records(const bev_point_t *__restrict__ src, uint32_t n, uint32_t k0, bool want_label,
+                                                    int pad_label, float4 (&a)[kProjPerThread], int (&label)[kProjPerThread])
+{
+#pragma unroll
+    for (int j = 0; j < kProjPerThread; ++j) {
+        const uint32_t k = k0 + (uint32_t)j * 256u;
+        a[j] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        label[j] = pad_label;
+        if (k >= n) continue;
+        a[j] = *reinterpret_cast<const float4 *>(src + k);
+        if (want_label) label[j] = (int)reinterpret_cast<const int16_t *>(src + k)[14];
+    }
+}
 
 /* Cache policy.  The big streams of the path are touched ONCE by the kernel that moves them: the order scan's read of
  * the input, the walk's stores of the ordered cloud, codes and candidates, the raster's stores of the planes.  Issued

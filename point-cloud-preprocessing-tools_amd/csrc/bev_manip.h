@@ -24,38 +24,22 @@ __device__ __forceinline__ void float_bev_put(uint32_t *__restrict__ grid, int c
     if (cell >= 0) atomicMax(&grid[cell], __float_as_uint(h));
 }
 
-/* Workgroup -> (frame, block of kProjBlock points) as in k_project_batch (the same table: offset, count, workgroups before
- * the frame); a thread takes kProjPerThread points 256 apart, every load in flight before the first use: the first half of a
- * record always, of the second half the word with the label only where the label is tested.  Then, per pose k of the frame
- * (a uniform loop; the matrices are read at uniform addresses), k_transform's association and k_float_bev's raster into
- * grid f * max(1, n_poses) + k.  n_poses == 0: the raw coordinates (NOT an identity pose: 0 * inf is NaN, -0.0 + 0.0 is +0.0). */
+/* A map over packed frames (packed_place, load_packed_records; bev_dev.h): the label is loaded only where it is tested.
+ * Then, per pose k of the frame (a uniform loop; the matrices are read at uniform addresses), k_transform's association
+ * (transform_xyz, bev_exact.h) and k_float_bev's raster into grid f * max(1, n_poses) + k.  n_poses == 0: the raw coordinates
+ * (NOT an identity pose: 0 * inf is NaN, -0.0 + 0.0 is +0.0). */
 __global__ __launch_bounds__(256) void k_float_bev_batch(const bev_point_t *__restrict__ clouds,
                                                          const ProjFrame *__restrict__ tab, int nf,
                                                          const Affine34 *__restrict__ poses, int n_poses, float interval, int M,
                                                          int skip_label0, uint32_t *__restrict__ grids)
 {
-    const uint32_t bid = blockIdx.x;
-    int lo = 0, hi = nf; /* tab[lo].blk0 <= bid < tab[hi].blk0: empty frames share their successor's count and are passed over */
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (tab[mid].blk0 <= bid) lo = mid;
-        else hi = mid;
-    }
-    const uint32_t n = tab[lo].n, k0 = (bid - tab[lo].blk0) * (uint32_t)kProjBlock + threadIdx.x;
-    const bev_point_t *__restrict__ src = clouds + tab[lo].off;
+    const PackedPlace pl = packed_place(tab, nf, blockIdx.x);
+    const uint32_t n = pl.n, k0 = pl.k0;
     float4 a[kProjPerThread];
     int label[kProjPerThread];
-#pragma unroll
-    for (int j = 0; j < kProjPerThread; ++j) {
-        const uint32_t k = k0 + (uint32_t)j * 256u;
-        a[j] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        label[j] = 1;
-        if (k >= n) continue;
-        a[j] = *reinterpret_cast<const float4 *>(src + k);
-        if (skip_label0) label[j] = (int)reinterpret_cast<const int16_t *>(src + k)[14];
-    }
+    load_packed_records(clouds + pl.off, n, k0, skip_label0 != 0, 1, a, label);
     const size_t cells = (size_t)M * (size_t)M;
-    uint32_t *__restrict__ grid = grids + (size_t)lo * (size_t)(n_poses > 0 ? n_poses : 1) * cells;
+    uint32_t *__restrict__ grid = grids + (size_t)pl.f * (size_t)(n_poses > 0 ? n_poses : 1) * cells;
     if (n_poses == 0) {
 #pragma unroll
         for (int j = 0; j < kProjPerThread; ++j) {
@@ -66,16 +50,13 @@ __global__ __launch_bounds__(256) void k_float_bev_batch(const bev_point_t *__re
         }
         return;
     }
-    const Affine34 *__restrict__ pose = poses + (size_t)lo * (size_t)n_poses;
+    const Affine34 *__restrict__ pose = poses + (size_t)pl.f * (size_t)n_poses;
     for (int p = 0; p < n_poses; ++p, grid += cells) {
         const Affine34 m = pose[p];
 #pragma unroll
         for (int j = 0; j < kProjPerThread; ++j) {
-            const float x = a[j].x, y = a[j].y, z = a[j].z;
-            const float tx = m.m[0] * x + (m.m[1] * y + (m.m[2] * z + m.m[3]));
-            const float ty = m.m[4] * x + (m.m[5] * y + (m.m[6] * z + m.m[7]));
-            const float tz = m.m[8] * x + (m.m[9] * y + (m.m[10] * z + m.m[11]));
-            float h;
+            float tx, ty, tz, h;
+            transform_xyz(m.m, a[j].x, a[j].y, a[j].z, tx, ty, tz);
             int cell = float_bev_cell(tx, ty, tz, label[j], interval, M, skip_label0, h);
             if (k0 + (uint32_t)j * 256u >= n) cell = -1;
             float_bev_put(grid, cell, h);

@@ -92,7 +92,8 @@ __global__ __launch_bounds__(256) void k_float_bev(const bev_point_t *__restrict
 }
 
 /* pcl::transformPointCloud with the [R | t] of cloud_manip (CloudManip.cpp:119-128): out.xyz = col0 * x + (col1 * y +
- * (col2 * z + col3)) — the association of pcl::detail::Transformer<float>::se3 — every other field copied.  The matrix
+ * (col2 * z + col3)) — the association of pcl::detail::Transformer<float>::se3, transform_xyz (bev_exact.h) — every other
+ * field copied.  The matrix
  * is built on the host (sinf / cosf of the host libm), so no transcendental is evaluated here. */
 struct Affine34 { float m[12]; };
 __global__ __launch_bounds__(256) void k_transform(const bev_point_t *cloud, uint32_t n, Affine34 a, bev_point_t *out)
@@ -101,10 +102,11 @@ __global__ __launch_bounds__(256) void k_transform(const bev_point_t *cloud, uin
     if (i >= n) return;
     Half lo = reinterpret_cast<const Half *>(cloud + i)[0];
     const Half hi = reinterpret_cast<const Half *>(cloud + i)[1];
-    const float x = __uint_as_float(lo.w[0]), y = __uint_as_float(lo.w[1]), z = __uint_as_float(lo.w[2]);
-    lo.w[0] = __float_as_uint(a.m[0] * x + (a.m[1] * y + (a.m[2] * z + a.m[3])));
-    lo.w[1] = __float_as_uint(a.m[4] * x + (a.m[5] * y + (a.m[6] * z + a.m[7])));
-    lo.w[2] = __float_as_uint(a.m[8] * x + (a.m[9] * y + (a.m[10] * z + a.m[11])));
+    float tx, ty, tz;
+    transform_xyz(a.m, __uint_as_float(lo.w[0]), __uint_as_float(lo.w[1]), __uint_as_float(lo.w[2]), tx, ty, tz);
+    lo.w[0] = __float_as_uint(tx);
+    lo.w[1] = __float_as_uint(ty);
+    lo.w[2] = __float_as_uint(tz);
     reinterpret_cast<Half *>(out + i)[0] = lo;
     reinterpret_cast<Half *>(out + i)[1] = hi;
 }

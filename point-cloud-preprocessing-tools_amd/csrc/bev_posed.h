@@ -36,45 +36,29 @@ __device__ __forceinline__ void posed_put(uint32_t *__restrict__ planes, uint32_
     if (l != kNoLayer) atomicOr(&planes[cells + idx], 1u << l);     /* :289-291 */
 }
 
-/* Workgroup -> (frame, block of kProjBlock points) as in k_float_bev_batch: tab is the call's table (offset, count,
- * workgroups before the frame), of which this launch covers the nf frames from tab[0] on.  A thread
- * takes kProjPerThread points 256 apart; the first half of every record (x, y, z: the compiler fetches the 12 bytes that are
- * used, four global_load_dwordx3) and the word with its label are in flight before the first use.  Then, per pose k of the frame (a uniform loop; the matrices are read at uniform addresses), posed_code
- * into the planes of grid f * max(1, n_poses) + k.  n_poses == 0: the raw coordinates.  No LDS. */
+/* A map over packed frames (packed_place, load_packed_records; bev_dev.h): tab is a piece of the call's table, of which this
+ * launch covers the nf frames from tab[0] on, so its first workgroup is the call's workgroup tab[0].blk0.  Of the first half of
+ * a record only x, y, z are used (the compiler fetches those 12 bytes: four global_load_dwordx3); a point past the frame's end
+ * has label 0: no code.  Then, per pose k of the frame (a uniform loop; the matrices are read at uniform addresses),
+ * posed_code into the planes of grid f * max(1, n_poses) + k.  n_poses == 0: the raw coordinates.  No LDS. */
 __global__ __launch_bounds__(256) void k_posed_splat(const bev_point_t *__restrict__ clouds, const ProjFrame *__restrict__ tab,
                                                      int nf, const Affine34 *__restrict__ poses, int n_poses,
                                                      RasterParams rp, uint32_t *__restrict__ planes)
 {
-    const uint32_t bid = blockIdx.x + tab[0].blk0;
-    int lo = 0, hi = nf; /* tab[lo].blk0 <= bid < tab[hi].blk0: empty frames share their successor's count and are passed over */
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (tab[mid].blk0 <= bid) lo = mid;
-        else hi = mid;
-    }
-    const uint32_t n = tab[lo].n, k0 = (bid - tab[lo].blk0) * (uint32_t)kProjBlock + threadIdx.x;
-    const bev_point_t *__restrict__ src = clouds + tab[lo].off;
+    const PackedPlace pl = packed_place(tab, nf, blockIdx.x + tab[0].blk0);
     float4 a[kProjPerThread];
     int label[kProjPerThread];
-#pragma unroll
-    for (int j = 0; j < kProjPerThread; ++j) {
-        const uint32_t k = k0 + (uint32_t)j * 256u;
-        a[j] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        label[j] = 0; /* (a point past the frame's end: no code) */
-        if (k >= n) continue;
-        a[j] = *reinterpret_cast<const float4 *>(src + k);
-        label[j] = (int)reinterpret_cast<const int16_t *>(src + k)[14];
-    }
+    load_packed_records(clouds + pl.off, pl.n, pl.k0, true, 0, a, label);
     const int M = rp.mat_size;
     const uint32_t cells = (uint32_t)(M * M);
     const int per_frame = n_poses > 0 ? n_poses : 1;
-    uint32_t *__restrict__ grid = planes + (size_t)lo * (size_t)per_frame * 2u * cells;
+    uint32_t *__restrict__ grid = planes + (size_t)pl.f * (size_t)per_frame * 2u * cells;
     if (n_poses == 0) {
 #pragma unroll
         for (int j = 0; j < kProjPerThread; ++j) posed_put(grid, cells, M, posed_code(a[j].x, a[j].y, a[j].z, label[j], nullptr, rp));
         return;
     }
-    const Affine34 *__restrict__ pose = poses + (size_t)lo * (size_t)n_poses;
+    const Affine34 *__restrict__ pose = poses + (size_t)pl.f * (size_t)n_poses;
     for (int p = 0; p < n_poses; ++p, grid += 2u * cells) {
         const Affine34 m = pose[p];
 #pragma unroll

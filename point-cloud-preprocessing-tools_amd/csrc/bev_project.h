@@ -12,23 +12,16 @@
 namespace bevk {
 using namespace bevx;
 
-/* MulRan / Oxford: a pure map.  Workgroup -> (frame, block of kProjBlock returns) through the table's running block counts
- * (a binary search over uniform addresses: scalar loads); a thread takes kProjPerThread returns 256 apart, so a wave's load is
- * 1 KiB of consecutive records (MulRan: one 16-byte load per lane; Oxford's planes start at any multiple of 4 bytes: four
- * 4-byte loads).  A record leaves as two 16-byte halves. */
+/* MulRan / Oxford: a pure map over packed frames (packed_place, bev_dev.h).  A thread's kProjPerThread returns lie 256 apart,
+ * so a wave's load is 1 KiB of consecutive records (MulRan: one 16-byte load per lane; Oxford's planes start at any multiple
+ * of 4 bytes: four 4-byte loads).  A record leaves as two 16-byte halves. */
 template <int kKind>
 __global__ __launch_bounds__(256) void k_project_batch(const float *__restrict__ xyzi, const ProjFrame *__restrict__ tab,
                                                        int nf, bev_point_t *__restrict__ out)
 {
-    const uint32_t bid = blockIdx.x;
-    int lo = 0, hi = nf; /* tab[lo].blk0 <= bid < tab[hi].blk0: empty frames share their successor's count and are passed over */
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (tab[mid].blk0 <= bid) lo = mid;
-        else hi = mid;
-    }
-    const uint64_t off = tab[lo].off;
-    const uint32_t n = tab[lo].n, k0 = (bid - tab[lo].blk0) * (uint32_t)kProjBlock + threadIdx.x;
+    const PackedPlace pl = packed_place(tab, nf, blockIdx.x);
+    const uint64_t off = pl.off;
+    const uint32_t n = pl.n, k0 = pl.k0;
     const float *__restrict__ src = xyzi + 4 * off;
     float x[kProjPerThread], y[kProjPerThread], z[kProjPerThread], it[kProjPerThread];
 #pragma unroll
