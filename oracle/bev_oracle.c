@@ -213,14 +213,12 @@ static int bev_bin(float p, int max_range, float interval)
     return cvtt_f64_to_i32(round((double)shifted + 0.5));
 }
 
-/* BatchMultiBevGen.cpp:266-292 */
-void oracle_multi_bev(const oracle_sensor_t *sp, const oracle_point_t *cloud,
-                      size_t n, float interval, uint8_t *out)
+/* BatchMultiBevGen.cpp:266-292 with the constants of :266-269 as arguments */
+void oracle_multi_bev_ex(const oracle_sensor_t *sp, const oracle_point_t *cloud, size_t n, float interval,
+                         int max_range, int n_layers, float lidar_to_ground, uint8_t *out)
 {
-    const int max_range = 112;                                   /* :266 */
     const int M = cvtt_f32_to_i32((float)(max_range * 2) / interval); /* :267 */
-    const int layers = 24;                                       /* :268,:271 */
-    const float lidar_to_ground = 2.0f;                          /* :269 */
+    const int layers = n_layers;                                 /* :268,:271 */
     memset(out, 0, (size_t)layers * M * M);                      /* :272-275 */
     for (size_t i = 0; i < n; ++i) {
         const oracle_point_t *p = &cloud[i];
@@ -234,13 +232,18 @@ void oracle_multi_bev(const oracle_sensor_t *sp, const oracle_point_t *cloud,
     }
 }
 
-/* BatchMultiBevGen.cpp:336-356 */
-void oracle_single_bev(const oracle_point_t *cloud, size_t n, float interval,
-                       uint8_t *out)
+/* BatchMultiBevGen.cpp:266-292 */
+void oracle_multi_bev(const oracle_sensor_t *sp, const oracle_point_t *cloud,
+                      size_t n, float interval, uint8_t *out)
 {
-    const int max_range = 112;                                   /* :336 */
+    oracle_multi_bev_ex(sp, cloud, n, interval, 112 /* :266 */, 24 /* :268 */, 2.0f /* :269 */, out);
+}
+
+/* BatchMultiBevGen.cpp:336-356 with the constants of :336,:338 as arguments (the 4.0 of :345 stays) */
+void oracle_single_bev_ex(const oracle_point_t *cloud, size_t n, float interval, int max_range,
+                          float lidar_to_ground, uint8_t *out)
+{
     const int M = cvtt_f32_to_i32((float)(max_range * 2) / interval); /* :337 */
-    const float lidar_to_ground = 2.0f;                          /* :338 */
     memset(out, 0, (size_t)M * M);                               /* :340 */
     for (size_t i = 0; i < n; ++i) {
         const oracle_point_t *p = &cloud[i];
@@ -254,6 +257,13 @@ void oracle_single_bev(const oracle_point_t *cloud, size_t n, float interval,
         if (out[(size_t)x * M + y] < height)                     /* :353-355 */
             out[(size_t)x * M + y] = (uint8_t)height;
     }
+}
+
+/* BatchMultiBevGen.cpp:336-356 */
+void oracle_single_bev(const oracle_point_t *cloud, size_t n, float interval,
+                       uint8_t *out)
+{
+    oracle_single_bev_ex(cloud, n, interval, 112 /* :336 */, 2.0f /* :338 */, out);
 }
 
 /* BatchMultiBevGen.cpp:735-747 */

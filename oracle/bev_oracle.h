@@ -95,6 +95,15 @@ void oracle_multi_bev(const oracle_sensor_t *sp, const oracle_point_t *cloud,
 void oracle_single_bev(const oracle_point_t *cloud, size_t n, float interval,
                        uint8_t *out);
 
+/* The two rasters with the reference's literals as arguments: MAX_RANGE (:266 / :336), the layer count (:268) and
+ * lidar_to_ground (:269 / :338); M = (int)((float)(2 * max_range) / interval).  The same sequential loops: the two
+ * functions above are these at 112 / 24 / 2.0f.  out: n_layers * M * M and M * M bytes.  The product admits other
+ * values (bev_params_t), the reference does not: these exist to check those configurations. */
+void oracle_multi_bev_ex(const oracle_sensor_t *sp, const oracle_point_t *cloud, size_t n, float interval,
+                         int max_range, int n_layers, float lidar_to_ground, uint8_t *out);
+void oracle_single_bev_ex(const oracle_point_t *cloud, size_t n, float interval, int max_range,
+                          float lidar_to_ground, uint8_t *out);
+
 /* Whole per-frame body of main(), BatchMultiBevGen.cpp:735-747 (no file I/O).
  * ground_mat may be NULL. */
 void oracle_process_frame(const oracle_sensor_t *sp, const oracle_point_t *in,

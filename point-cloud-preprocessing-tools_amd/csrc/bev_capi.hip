@@ -114,21 +114,9 @@ void fill_geometry(const bev_params_t *p, Geometry *g)
     g->tiles = (g->S + kTile - 1) / kTile;
     g->strips = (g->H + kStripCols - 1) / kStripCols;
     g->segs = (g->G + 1) * g->strips;
-    {   /* raster bands: M / u rows each, the middle quarter of the image cut four times finer (bev_exact.h) */
-        const int M = mat_size_of(p), u = raster_bands_for(M);
-        const int coarse = u ? M / u : M;
-        int fine = coarse % kRasterFineDiv == 0 ? coarse / kRasterFineDiv : coarse;
-        const int z0 = (3 * u / 8) * coarse, z1 = M - z0;
-        if (2 * (z0 / coarse) + (z1 - z0) / fine > kMaxBands) fine = coarse; /* (large images: uniform bands) */
-        g->rp.coarse = coarse;
-        g->rp.fine = fine;
-        g->rp.z0 = z0;
-        g->rp.z1 = z1;
-        g->rp.bands = 2 * (z0 / coarse) + (z1 - z0) / fine;
-        g->rp.coarse_magic = bevx::small_div_magic(coarse);
-        g->rp.fine_magic = bevx::small_div_magic(fine);
-        g->raster_bands = g->rp.bands;
-    }
+    /* raster bands: M / u rows each, the middle of the image cut finer (bev_exact.h raster_band_layout) */
+    bevx::raster_band_layout(mat_size_of(p), raster_bands_for(mat_size_of(p)), &g->rp);
+    g->raster_bands = g->rp.bands;
     g->emitters = g->strips + kResolveParts;
     {   /* worst case: every slot of a strip / every candidate of a resolve part in one band; normally far fewer (kCodeListCap) */
         const uint32_t worst = std::max((uint32_t)g->N * (uint32_t)kStripCols, (uint32_t)((g->segs + kResolveParts - 1) / kResolveParts + 1) * (uint32_t)kSeg);
@@ -138,14 +126,7 @@ void fill_geometry(const bev_params_t *p, Geometry *g)
         const uint32_t pieces = (g->code_cap + 63u) / 64u; /* 256-byte pieces */
         g->code_stride = (pieces | 1u) * 64u;
     }
-    g->rp.max_range_f = (float)p->max_range;
-    g->rp.interval = p->interval;
-    g->rp.height_res = p->height_res;
-    g->rp.lidar_to_ground = p->lidar_to_ground;
-    g->rp.mat_size = mat_size_of(p);
-    g->rp.n_layers = p->n_layers;
-    g->rp.inv_interval = bevx::exact_reciprocal(p->interval);
-    g->rp.inv_height_res = bevx::exact_reciprocal(p->height_res);
+    bevx::raster_scalars(p->max_range, p->interval, p->height_res, p->lidar_to_ground, p->n_layers, &g->rp);
 }
 
 /* ---- profiling -------------------------------------------------------- */

@@ -226,6 +226,39 @@ BEVX_HD float exact_reciprocal(float v)
     c.u = (254u - e) << 23;
     return c.f;
 }
+/* The band layout of an image of M rows whose coarse bands are M / u rows (u: raster_bands_for, bev_raster.h — the
+ * fewest uniform bands whose LDS planes fit; 0: one band of M rows): the middle quarter of the image, [z0, z1), is cut
+ * kBandFineDiv times finer where the coarse height divides and the total stays within kBandMax (large images: uniform
+ * bands).  Fills bands, coarse, fine, z0, z1 and the two magics; fill_geometry (bev_capi.hip) and tests/hostcheck call it. */
+constexpr int kBandFineDiv = 2;
+constexpr int kBandMax = 64;
+BEVX_HD void raster_band_layout(int M, int u, RasterParams *rp)
+{
+    const int coarse = u ? M / u : M;
+    int fine = coarse % kBandFineDiv == 0 ? coarse / kBandFineDiv : coarse;
+    const int z0 = (3 * u / 8) * coarse, z1 = M - z0;
+    if (2 * (z0 / coarse) + (z1 - z0) / fine > kBandMax) fine = coarse; /* (large images: uniform bands) */
+    rp->coarse = coarse;
+    rp->fine = fine;
+    rp->z0 = z0;
+    rp->z1 = z1;
+    rp->bands = 2 * (z0 / coarse) + (z1 - z0) / fine;
+    rp->coarse_magic = small_div_magic(coarse);
+    rp->fine_magic = small_div_magic(fine);
+}
+/* everything in RasterParams that does not depend on how the image is cut (the reference's literals, :264-269, and the
+ * exact reciprocals) */
+BEVX_HD void raster_scalars(int max_range, float interval, float height_res, float lidar_to_ground, int n_layers, RasterParams *rp)
+{
+    rp->max_range_f = (float)max_range;
+    rp->interval = interval;
+    rp->height_res = height_res;
+    rp->lidar_to_ground = lidar_to_ground;
+    rp->mat_size = cvtt_f32((float)(max_range * 2) / interval); /* static int MAT_SIZE = MAX_RANGE*2 / interval;  :267 */
+    rp->n_layers = n_layers;
+    rp->inv_interval = exact_reciprocal(interval);
+    rp->inv_height_res = exact_reciprocal(height_res);
+}
 BEVX_HD float div_interval(float a, const RasterParams &rp) { return rp.inv_interval != 0.0f ? a * rp.inv_interval : a / rp.interval; }
 BEVX_HD float div_height_res(float a, const RasterParams &rp) { return rp.inv_height_res != 0.0f ? a * rp.inv_height_res : a / rp.height_res; }
 BEVX_HD int raster_band_of(int x, const RasterParams &rp)

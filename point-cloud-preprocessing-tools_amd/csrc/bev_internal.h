@@ -43,9 +43,9 @@ constexpr int kResolveWgs = BEV_RESOLVE_WGS;
 static_assert(kResolveParts % kResolveWgs == 0, "whole parts per workgroup");
 constexpr int kRasterThreads = kStageThreads;
 constexpr int kRasterLdsCap = kSlotLdsBytes; /* a raster band's two planes (+ its list prefix) */
-constexpr int kRasterFineDiv = 2;  /* the middle bands of the image are cut this many times finer (see fill_geometry) */
+constexpr int kRasterFineDiv = bevx::kBandFineDiv; /* (2) the middle bands of the image are cut this many times finer (see fill_geometry) */
 constexpr int kRasterSplit = 8;   /* fewest x-bands per frame in the raster kernel (see raster_bands_for) */
-constexpr int kMaxBands = 64;     /* coarse + fine raster bands (see RasterParams) */
+constexpr int kMaxBands = bevx::kBandMax; /* (64) coarse + fine raster bands (see RasterParams) */
 constexpr int kMaxStrips = 280;   /* ceil(65535 / kStripCols) rounded up */
 /* Entries of one (emitter, band) code list.  Measured fill (scripts/list_fill.py: which capacities overflow on the
  * synthetic layouts): HDL_64E sweeps stay under 2,048 codes per list, OS1_64 frames under 3,072 — of the 15,104 slots a
@@ -225,7 +225,7 @@ enum KernelId {
     K_COUNT
 };
 const char *kernel_name(int id);
-/* smallest of 4, 8, 16 bands whose LDS planes (2 * (M / bands) * M * 4 B) fit; 0 if none does */
+/* smallest of 8, 16, 32, 64 uniform bands whose LDS planes (2 * (M / bands) * M * 4 B + the list prefix) fit; 0 if none does */
 int raster_bands_for(int mat_size);
 
 /* One fused launch (k_stage): the column walk of one sub-batch and, as further workgroups of the same grid, phase B of the

@@ -27,25 +27,22 @@ struct ArrayFetch {
     const bev_point_t *pts;
     XYZI operator()(long long i) const { return XYZI{pts[i].x, pts[i].y, pts[i].z, pts[i].intensity}; }
 };
+/* A COPY of raster_bands_for's loop (csrc/bev_raster.h is device code and is not compiled here) with its constants
+ * (bev_internal.h: kRasterSplit, kRasterLdsCap = kSlotLdsBytes, kMaxStrips + kResolveParts + 2 tail words).
+ * tests/test_raster_layout_cpu.py holds the sizes this admits against bev_multi_bytes of the product library. */
+constexpr int kHcRasterSplit = 8, kHcRasterLdsCap = 32 * 1280, kHcRasterTailWords = 280 + 4 + 2;
+int raster_bands_for_copy(int M)
+{
+    for (int bands = kHcRasterSplit; bands <= kBandMax; bands *= 2)
+        if (M % bands == 0 && ((size_t)2 * (M / bands) * M + kHcRasterTailWords) * sizeof(uint32_t) <= (size_t)kHcRasterLdsCap) return bands;
+    return 0;
+}
+/* what fill_geometry (bev_capi.hip) computes from the same two helpers; results do not depend on the band layout */
 RasterParams raster_params(const bev_params_t *p)
 {
     RasterParams rp;
-    rp.max_range_f = (float)p->max_range;
-    rp.interval = p->interval;
-    rp.height_res = p->height_res;
-    rp.lidar_to_ground = p->lidar_to_ground;
-    rp.mat_size = cvtt_f32((float)(p->max_range * 2) / p->interval);
-    rp.n_layers = p->n_layers;
-    rp.inv_interval = exact_reciprocal(p->interval);
-    rp.inv_height_res = exact_reciprocal(p->height_res);
-    /* how the device cuts the images into workgroups (bev_capi.hip fill_geometry); results do not depend on it */
-    rp.coarse = rp.mat_size >= 8 ? rp.mat_size / 8 : 1;
-    rp.fine = rp.coarse % 4 == 0 ? rp.coarse / 4 : rp.coarse;
-    rp.z0 = 3 * rp.coarse;
-    rp.z1 = rp.mat_size - rp.z0;
-    rp.bands = 2 * (rp.z0 / rp.coarse) + (rp.z1 - rp.z0) / rp.fine;
-    rp.coarse_magic = small_div_magic(rp.coarse);
-    rp.fine_magic = small_div_magic(rp.fine);
+    raster_scalars(p->max_range, p->interval, p->height_res, p->lidar_to_ground, p->n_layers, &rp);
+    raster_band_layout(rp.mat_size, raster_bands_for_copy(rp.mat_size), &rp);
     return rp;
 }
 } // namespace
@@ -205,8 +202,9 @@ uint64_t hc_count_advance_check(uint32_t n_max)
 int hc_ground_cell(float x, float y) { return ground_cell(x, y); }
 
 /* small_div against the division for every 0 <= x < 512, 1 <= d <= 512, and raster_band_of_nodiv against raster_band_of
- * for every image size / band layout fill_geometry can produce (M a multiple of 16 up to 512; 4, 8 or 16 coarse bands):
- * the number of mismatches */
+ * for every image size fill_geometry lays out (M a multiple of 16 up to 512 that raster_bands_for admits: 8 to 64 coarse
+ * bands, the middle cut twice finer or not — raster_band_layout, the helper fill_geometry itself calls): the number of
+ * mismatches */
 uint64_t hc_small_div_check(void)
 {
     uint64_t bad = 0;
@@ -214,19 +212,48 @@ uint64_t hc_small_div_check(void)
         const uint32_t m = small_div_magic(d);
         for (int x = 0; x < 512; ++x) bad += small_div(x, m) != x / d;
     }
-    for (int M = 16; M <= 512; M += 16)
-        for (int u = 4; u <= 16; u *= 2) {
-            RasterParams rp{};
-            rp.mat_size = M;
-            rp.coarse = M / u;
-            if (rp.coarse < 1 || M % u) continue;
-            rp.fine = rp.coarse % 4 == 0 ? rp.coarse / 4 : rp.coarse;
-            rp.z0 = (3 * u / 8) * rp.coarse;
-            rp.z1 = M - rp.z0;
-            rp.coarse_magic = small_div_magic(rp.coarse);
-            rp.fine_magic = small_div_magic(rp.fine);
-            for (int x = 0; x < M; ++x) bad += raster_band_of_nodiv(x, rp) != raster_band_of(x, rp);
-        }
+    int layouts = 0;
+    for (int M = 16; M <= 512; M += 16) {
+        const int u = raster_bands_for_copy(M);
+        if (!u) continue;
+        RasterParams rp{};
+        rp.mat_size = M;
+        raster_band_layout(M, u, &rp);
+        ++layouts;
+        for (int x = 0; x < M; ++x) bad += raster_band_of_nodiv(x, rp) != raster_band_of(x, rp);
+    }
+    return bad + (layouts == 0);
+}
+
+/* The band layout of image size M as the library computes it.  out[0..7] = u (0: M is refused), bands, coarse, fine, z0,
+ * z1, LDS bytes of a band's workgroup (raster_lds_bytes), violations.  A violation is any of: more than kBandMax bands;
+ * z0 not a multiple of coarse or z1 - z0 not a multiple of fine; fine above coarse (the LDS planes are sized for coarse
+ * rows); the bands, walked with raster_band_x0 / raster_band_rows, not covering every row of [0, M) exactly once in
+ * order; raster_band_of or raster_band_of_nodiv of a row differing from the band that covers it; the planes above the
+ * LDS cap.  Returns the violations. */
+int hc_band_layout(int M, int *out)
+{
+    const int u = raster_bands_for_copy(M);
+    for (int k = 0; k < 8; ++k) out[k] = 0;
+    if (!u) return 0;
+    RasterParams rp{};
+    rp.mat_size = M;
+    raster_band_layout(M, u, &rp);
+    int bad = 0;
+    bad += rp.bands > kBandMax || rp.bands < 1;
+    bad += rp.coarse < 1 || rp.fine < 1 || rp.fine > rp.coarse;
+    bad += rp.z0 % rp.coarse != 0 || (rp.z1 - rp.z0) % rp.fine != 0 || (M - rp.z1) % rp.coarse != 0;
+    int next = 0;
+    for (int b = 0; b < rp.bands; ++b) {
+        const int x0 = raster_band_x0(b, rp), rows = raster_band_rows(b, rp);
+        bad += x0 != next || rows < 1;
+        for (int x = x0; x < x0 + rows && x < M; ++x) bad += raster_band_of(x, rp) != b || raster_band_of_nodiv(x, rp) != b;
+        next = x0 + rows;
+    }
+    bad += next != M;
+    const size_t lds = ((size_t)2 * rp.coarse * M + kHcRasterTailWords) * sizeof(uint32_t);
+    bad += lds > (size_t)kHcRasterLdsCap;
+    out[0] = u; out[1] = rp.bands; out[2] = rp.coarse; out[3] = rp.fine; out[4] = rp.z0; out[5] = rp.z1; out[6] = (int)lds; out[7] = bad;
     return bad;
 }
 

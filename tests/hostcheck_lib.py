@@ -27,6 +27,7 @@ def lib():
         l.hc_count_advance_check.restype = C.c_uint64
         l.hc_small_div_check.argtypes = []
         l.hc_small_div_check.restype = C.c_uint64
+        l.hc_band_layout.argtypes = [C.c_int, vp]
         l.hc_angle_nodiv_check.argtypes = [C.c_uint64]
         l.hc_angle_nodiv_check.restype = C.c_uint64
         l.hc_exact_reciprocal_check.argtypes = [C.c_uint64]
@@ -112,6 +113,16 @@ def process_frame(p: BevParams, pts):
     return ordered, gm, avg, multi, single
 
 
+def phase_a_ground_mat(p: BevParams, pts):
+    """(ordered cloud with its final labels, ground_mat as phase A leaves it: 1 marks the candidates whose BEV codes travel
+    in their keys, every other slot's code goes into its strip's lists)"""
+    pts = np.ascontiguousarray(pts, dtype=POINT_DTYPE)
+    ordered = np.empty(p.slots, POINT_DTYPE)
+    gm_a = np.empty((p.n_scan, p.horizon_scan), np.int8)
+    lib().hc_process_frame(C.byref(p), pts.ctypes.data, len(pts), ordered.ctypes.data, gm_a.ctypes.data, None, None, None, None)
+    return ordered, gm_a
+
+
 def project(kind: int, xyzi):
     xyzi = np.ascontiguousarray(xyzi, np.float32)
     n = xyzi.size // 4
@@ -137,6 +148,17 @@ def keyframe_labels(xyz, major):
     out = np.empty((len(xyz), len(major)), np.float32)
     lib().hc_keyframe_labels(xyz.ctypes.data, len(xyz), major.ctypes.data, len(major), out.ctypes.data)
     return out
+
+
+def band_layout(M: int) -> dict:
+    """the raster band layout of image size M (csrc/bev_exact.h raster_band_layout); u == 0: the size is refused"""
+    out = (C.c_int * 8)()
+    lib().hc_band_layout(M, out)
+    return dict(zip(("u", "bands", "coarse", "fine", "z0", "z1", "lds_bytes", "violations"), [int(v) for v in out]))
+
+
+def bev_code(p: BevParams, x, y, z, label) -> int:
+    return int(lib().hc_bev_code(C.byref(p), float(x), float(y), float(z), int(label)))
 
 
 def key_stats(reset=True):

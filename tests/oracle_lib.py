@@ -41,6 +41,10 @@ def lib():
         l.oracle_multi_bev.restype = None
         l.oracle_single_bev.argtypes = [vp, sz, C.c_float, vp]
         l.oracle_single_bev.restype = None
+        l.oracle_multi_bev_ex.argtypes = [SP, vp, sz, C.c_float, C.c_int, C.c_int, C.c_float, vp]
+        l.oracle_multi_bev_ex.restype = None
+        l.oracle_single_bev_ex.argtypes = [vp, sz, C.c_float, C.c_int, C.c_float, vp]
+        l.oracle_single_bev_ex.restype = None
         l.oracle_process_frame.argtypes = [SP, vp, sz, vp, vp, vp, vp]
         l.oracle_process_frame.restype = None
         l.oracle_float_bev.argtypes = [vp, sz, C.c_float, C.c_int, vp]
@@ -91,20 +95,55 @@ def mark_ground(sp: OracleSensor, ordered: np.ndarray, angle_variant: int = 0):
     return cloud, gm, avg
 
 
-def multi_bev(sp: OracleSensor, cloud: np.ndarray, interval: float = 1.0) -> np.ndarray:
+def mat_size(max_range: int, interval: float) -> int:
+    return int(np.float32(2 * max_range) / np.float32(interval))
+
+
+def multi_bev(sp: OracleSensor, cloud: np.ndarray, interval: float = 1.0, max_range: int = 112, n_layers: int = 24,
+              lidar_to_ground: float = 2.0) -> np.ndarray:
+    """oracle_multi_bev_ex: the reference's loop with its literals 112 / 24 / 2.0f (the defaults) as arguments"""
     cloud = np.ascontiguousarray(cloud, dtype=POINT_DTYPE)
-    M = int(np.float32(224) / np.float32(interval))
+    M = mat_size(max_range, interval)
+    out = np.empty((n_layers, M, M), dtype=np.uint8)
+    lib().oracle_multi_bev_ex(C.byref(sp), cloud.ctypes.data, len(cloud), interval, max_range, n_layers, lidar_to_ground,
+                              out.ctypes.data)
+    return out
+
+
+def single_bev(cloud: np.ndarray, interval: float = 1.0, max_range: int = 112, lidar_to_ground: float = 2.0) -> np.ndarray:
+    """oracle_single_bev_ex: the reference's loop with its literals 112 / 2.0f (the defaults) as arguments"""
+    cloud = np.ascontiguousarray(cloud, dtype=POINT_DTYPE)
+    M = mat_size(max_range, interval)
+    out = np.empty((M, M), dtype=np.uint8)
+    lib().oracle_single_bev_ex(cloud.ctypes.data, len(cloud), interval, max_range, lidar_to_ground, out.ctypes.data)
+    return out
+
+
+def multi_bev_fixed(sp: OracleSensor, cloud: np.ndarray, interval: float = 1.0) -> np.ndarray:
+    """oracle_multi_bev, the entry point with the reference's literals (kept to pin the _ex form against it)"""
+    cloud = np.ascontiguousarray(cloud, dtype=POINT_DTYPE)
+    M = mat_size(112, interval)
     out = np.empty((24, M, M), dtype=np.uint8)
     lib().oracle_multi_bev(C.byref(sp), cloud.ctypes.data, len(cloud), interval, out.ctypes.data)
     return out
 
 
-def single_bev(cloud: np.ndarray, interval: float = 1.0) -> np.ndarray:
+def single_bev_fixed(cloud: np.ndarray, interval: float = 1.0) -> np.ndarray:
     cloud = np.ascontiguousarray(cloud, dtype=POINT_DTYPE)
-    M = int(np.float32(224) / np.float32(interval))
+    M = mat_size(112, interval)
     out = np.empty((M, M), dtype=np.uint8)
     lib().oracle_single_bev(cloud.ctypes.data, len(cloud), interval, out.ctypes.data)
     return out
+
+
+def process_frame_params(p, pts: np.ndarray, want_gm: bool = True):
+    """oracle_process_frame's sequence (BatchMultiBevGen.cpp:735-747) under a bev_params_t the reference cannot express:
+    order, mark, then the two _ex rasters with p's interval, range, layers and offset"""
+    sp = sensor_from_params(p)
+    ordered, gm, _ = mark_ground(sp, order_cloud(sp, pts))
+    multi = multi_bev(sp, ordered, p.interval, p.max_range, p.n_layers, p.lidar_to_ground)
+    single = single_bev(ordered, p.interval, p.max_range, p.lidar_to_ground)
+    return ordered, (gm if want_gm else None), multi, single
 
 
 def process_frame(sp: OracleSensor, pts: np.ndarray, want_gm: bool = True):

@@ -126,31 +126,31 @@ def bev_bin(p, max_range, interval):
     return cvtt(round_half_away(v))
 
 
-def multi_bev(cloud, height_res, interval=1.0):
-    """BatchMultiBevGen.cpp:266-292"""
-    M = cvtt(F(112 * 2) / F(interval))
-    out = np.zeros((24, M, M), np.uint8)
+def multi_bev(cloud, height_res, interval=1.0, max_range=112, n_layers=24, lidar_to_ground=2.0):
+    """BatchMultiBevGen.cpp:266-292; max_range, n_layers and lidar_to_ground are literals there (:266, :268, :269)"""
+    M = cvtt(F(max_range * 2) / F(interval))
+    out = np.zeros((n_layers, M, M), np.uint8)
     with np.errstate(all="ignore"):
         for p in cloud:
-            x = bev_bin(p["x"], 112, interval)
-            y = bev_bin(p["y"], 112, interval)
-            layer = cvtt(round_half_away(F(F(p["z"] / F(height_res)) + F(2.0))))   # roundf of a float expression
-            if x < 0 or x >= M or y < 0 or y >= M or layer < 0 or layer >= 24 or p["label"] == 0:
+            x = bev_bin(p["x"], max_range, interval)
+            y = bev_bin(p["y"], max_range, interval)
+            layer = cvtt(round_half_away(F(F(p["z"] / F(height_res)) + F(lidar_to_ground))))   # roundf of a float expression
+            if x < 0 or x >= M or y < 0 or y >= M or layer < 0 or layer >= n_layers or p["label"] == 0:
                 continue
             if out[layer, x, y] == 0:
                 out[layer, x, y] = 255
     return out
 
 
-def single_bev(cloud, interval=1.0):
-    """BatchMultiBevGen.cpp:336-356"""
-    M = cvtt(F(112 * 2) / F(interval))
+def single_bev(cloud, interval=1.0, max_range=112, lidar_to_ground=2.0):
+    """BatchMultiBevGen.cpp:336-356; max_range and lidar_to_ground are literals there (:336, :338)"""
+    M = cvtt(F(max_range * 2) / F(interval))
     out = np.zeros((M, M), np.uint8)
     with np.errstate(all="ignore"):
         for p in cloud:
-            x = bev_bin(p["x"], 112, interval)
-            y = bev_bin(p["y"], 112, interval)
-            height = cvtt(D(F(p["z"] + F(2.0))) * 4.0)
+            x = bev_bin(p["x"], max_range, interval)
+            y = bev_bin(p["y"], max_range, interval)
+            height = cvtt(D(F(p["z"] + F(lidar_to_ground))) * 4.0)
             height = min(max(0, height), 255)
             if x < 0 or x >= M or y < 0 or y >= M or p["label"] == 0:
                 continue

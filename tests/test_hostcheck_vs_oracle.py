@@ -86,6 +86,21 @@ def test_candidate_key_reproduces_the_bev_code():
         assert (res != 0).all(), (interval, np.flatnonzero(res == 0)[:5])
         if interval == 1.0:
             assert (res == 2).mean() < 0.6  # escapes are the clamped cells / out-of-grid points of this artificial set
+    # configurations the reference does not have: intervals that are divided by, 8 bins per ground cell (0.25: nearly every
+    # key escapes), ranges below 75 m (the ground grid's cell edges fall off the image); the image's own bin edges and
+    # their float neighbours join the boundary set
+    import raster_cases as rc
+    for interval, max_range in ((0.25, 64), (0.7, 112), (1.75, 112), (1.0, 40), (1.0, 64)):
+        p = rc.with_fields(bev_amd.params_for_sensor("HDL_64E"), interval=interval, max_range=max_range)
+        edges = np.concatenate([rc.boundary_coords(p), rc.searched_coords(p)])
+        xs = np.concatenate([np.arange(-130, 131, 0.5), np.nextafter(np.arange(-130, 131, 1.0, dtype=np.float32), np.float32(1e9)),
+                             np.nextafter(np.arange(-130, 131, 1.0, dtype=np.float32), np.float32(-1e9)), edges,
+                             rng.uniform(-120, 120, 2000), [np.inf, -np.inf, np.nan, 1e30, -1e30, 0.0, -0.0, 1e-40]]).astype(np.float32)
+        ys = rng.permutation(xs)
+        zs = rng.permutation(np.resize(np.concatenate([rc.boundary_heights(p), rng.uniform(-3, 6, 500).astype(np.float32)]), len(xs)))
+        res = np.array([hc.key_roundtrip(p, x, y, z, lab) for x, y, z in zip(xs, ys, zs) for lab in (-2, 0, 7)])
+        assert (res != 0).all(), (interval, max_range, np.flatnonzero(res == 0)[:5])
+        assert (res == 1).any() and (res == 2).any(), (interval, max_range)
     # real frames: fast decodes dominate
     p = bev_amd.params_for_sensor("HDL_64E")
     hc.key_stats(reset=True)
