@@ -265,6 +265,46 @@ int bev_posed_bev_device_resident(bev_ctx_t *ctx, int n_frames, const bev_point_
 int bev_posed_bev_batch(bev_ctx_t *ctx, int n_frames, const bev_point_t *const *clouds, const uint32_t *n_pts,
                         int n_poses, const float *h_poses, uint8_t *const *multi_out, uint8_t *const *single_out);
 
+/* The same two images of SUBMAPS: map g is a list of (frame, pose) entries, and its images are those of all its entries' moved
+ * clouds together in ONE grid — bev_multi_bev / bev_single_bev of the concatenation of bev_transform_cloud(frame, pose) over
+ * the map's entries, byte for byte (both rasters are idempotent stores and a maximum: the order of the entries does not
+ * matter).  A local map around a key frame is the typical use: the key frame's neighbours, each under its pose relative to
+ * the key frame.  Asynchronous like bev_posed_bev_device_resident.
+ * d_clouds      : frames as for bev_posed_bev_device_resident: frame f = records [h_offsets[f], h_offsets[f+1]).
+ * h_map_offsets : HOST array of n_maps + 1 entries, non-decreasing: map g owns entries [h_map_offsets[g], h_map_offsets[g+1])
+ *                 of the two entry arrays (which are indexed from 0: h_map_offsets[0] is normally 0).
+ * h_entry_frame : HOST array: the frame entry e names, 0 .. n_frames - 1.
+ * h_entry_pose  : HOST array of 12 floats per entry: its row-major 3 x 4 matrix.  Every entry has one; the identity is
+ *                 bev_yaw_translate_matrix(0, 0, 0, 0) (on finite clouds it gives the raw cloud's images).
+ *                 A frame may feed any number of maps, appear several times in one map, or be named by none (it then costs no
+ *                 workgroup); a map without entries gives all-zero images.  Only the call's total of entries is bounded:
+ *                 BEV_SUBMAP_MAX_ENTRIES.
+ * d_multi       : n_maps images of bev_multi_bytes, or NULL: not wanted.
+ * d_single      : n_maps images of bev_single_bytes, or NULL: not wanted (not both).  Every byte of a wanted image is written,
+ *                 nothing else is.  The host arrays may be reused as soon as the call returns.
+ * Ordering      : as for bev_posed_bev_device_resident.
+ * Status        : BEV_ERR_INVALID_ARG for a NULL context, n_frames < 0, n_maps < 0, NULL or decreasing h_offsets or
+ *                 h_map_offsets, entries with a NULL entry array, an entry frame outside 0 .. n_frames - 1, d_multi and
+ *                 d_single both NULL while n_maps > 0, NULL d_clouds while an entry names a frame that has records;
+ *                 BEV_ERR_TOO_LARGE for a frame of more than max(max_points, S) records or more than BEV_SUBMAP_MAX_ENTRIES
+ *                 entries (checked before the entry arrays are read); nothing is launched and the outputs are untouched in
+ *                 every case.  n_maps == 0 returns BEV_OK.
+ * Workspace     : the planes of the posed call, one grid per map of a launch group: the call is cut into groups of consecutive
+ *                 maps that fit the same cap (256 MiB, or BEV_POSED_GROUP=<grids>; results do not depend on it), and per
+ *                 group a table of 20 bytes per distinct frame of the group and 64 bytes per entry.  Freed by bev_destroy. */
+#define BEV_SUBMAP_MAX_ENTRIES (1u << 20)   /* entries of one call */
+int bev_submap_bev_device_resident(bev_ctx_t *ctx, int n_frames, const bev_point_t *d_clouds, const uint64_t *h_offsets,
+                                   int n_maps, const uint64_t *h_map_offsets, const int32_t *h_entry_frame,
+                                   const float *h_entry_pose, uint8_t *d_multi, uint8_t *d_single);
+/* The same through HOST buffers, synchronous and argument-checked like bev_posed_bev_batch: clouds[f] holds n_pts[f] records
+ * (at most max(max_points, S)); multi_out[g] receives map g's image of bev_multi_bytes, single_out[g] its image of
+ * bev_single_bytes; a NULL array: not wanted (not both).  The maps go in chunks of at most max_batch maps (and never more than
+ * a launch group); the distinct frames a chunk names go up through the context's input staging max_batch at a time, each such
+ * piece rastered into the chunk's planes before the next goes up, so a map may name more distinct frames than max_batch. */
+int bev_submap_bev_batch(bev_ctx_t *ctx, int n_frames, const bev_point_t *const *clouds, const uint32_t *n_pts,
+                         int n_maps, const uint64_t *h_map_offsets, const int32_t *h_entry_frame,
+                         const float *h_entry_pose, uint8_t *const *multi_out, uint8_t *const *single_out);
+
 /* Range-image projection of raw XYZI returns — the selectors' row / col assignment ("polar binning"):
  *   BEV_PROJECT_MULRAN_OS1_64   extractPointCloud, MulranPointCloudSelect.cpp:112-130:
  *                               xyzi = n * (x, y, z, intensity); row = k % 64, col from the azimuth (0..1024)

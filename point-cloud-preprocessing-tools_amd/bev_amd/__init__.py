@@ -72,6 +72,7 @@ PROJECT_KITTI_GROUP = 16  # BEV_PROJECT_KITTI_GROUP: frames per launch group of 
 KITTI_SLOTS = 64 * 2083
 FLOAT_BEV_MAX_POSES = 64  # BEV_FLOAT_BEV_MAX_POSES: poses per frame of float_bev_device / float_bev_batch
 POSED_BEV_MAX_POSES = 64  # BEV_POSED_BEV_MAX_POSES: poses per frame of posed_bev_device / posed_bev_batch
+SUBMAP_MAX_ENTRIES = 1 << 20  # BEV_SUBMAP_MAX_ENTRIES: (frame, pose) entries of one submap_bev_device / submap_bev_batch call
 
 # every symbol include/bev_mi355x.h declares
 ABI_SYMBOLS = [
@@ -90,6 +91,7 @@ ABI_SYMBOLS = [
     "bev_project_device_resident", "bev_project_batch_out_points", "bev_process_batch_xyzi",
     "bev_float_bev_device_resident", "bev_float_bev_batch",
     "bev_posed_bev_device_resident", "bev_posed_bev_batch",
+    "bev_submap_bev_device_resident", "bev_submap_bev_batch",
 ]
 
 # registration front end (include/bev_mi355x.h): pcl::PointXYZ, pcl::Normal, pcl::PointNormal as float rows
@@ -215,6 +217,10 @@ def load_lib() -> C.CDLL:
     if hasattr(lib, "bev_posed_bev_device_resident"):
         lib.bev_posed_bev_device_resident.argtypes = [vp, i32, vp, C.POINTER(C.c_uint64), i32, vp, vp, vp]
         lib.bev_posed_bev_batch.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(u32), i32, vp, C.POINTER(vp), C.POINTER(vp)]
+    if hasattr(lib, "bev_submap_bev_device_resident"):
+        lib.bev_submap_bev_device_resident.argtypes = [vp, i32, vp, C.POINTER(C.c_uint64), i32, C.POINTER(C.c_uint64), vp, vp, vp, vp]
+        lib.bev_submap_bev_batch.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(u32), i32, C.POINTER(C.c_uint64), vp, vp,
+                                             C.POINTER(vp), C.POINTER(vp)]
     _lib = lib
     return lib
 
@@ -424,6 +430,49 @@ class BevContext:
         s = VP(*[single[i].ctypes.data for i in range(n)]) if want_single else None
         rc = self.lib.bev_posed_bev_batch(self._h, n, pts, npts, n_poses, _ptr(poses), m, s)
         self._check(rc, "bev_posed_bev_batch")
+        return multi, single
+
+    @staticmethod
+    def _submap_entries(map_offsets, entry_frame, entry_pose):
+        """the three host arrays of a submap call, contiguous: (n_maps, offsets, frames or None, matrices or None)"""
+        map_offsets = np.ascontiguousarray(map_offsets, dtype=np.uint64)
+        entry_frame = np.ascontiguousarray(entry_frame, dtype=np.int32).reshape(-1)
+        entry_pose = np.ascontiguousarray(entry_pose, dtype=np.float32).reshape(-1, 12)
+        assert map_offsets.ndim == 1 and len(map_offsets) >= 1 and len(entry_frame) == len(entry_pose)
+        assert len(entry_frame) >= int(map_offsets.max())
+        return len(map_offsets) - 1, map_offsets, (entry_frame if len(entry_frame) else None), (entry_pose if len(entry_pose) else None)
+
+    def submap_bev_device(self, n_frames, d_clouds, offsets, map_offsets, entry_frame, entry_pose, d_multi, d_single):
+        """bev_submap_bev_device_resident on device pointers: frame f = records [offsets[f], offsets[f + 1]) of d_clouds; map g
+        = entries [map_offsets[g], map_offsets[g + 1]), entry e = frame entry_frame[e] under the row-major 3 x 4 matrix
+        entry_pose[e] (12 floats); d_multi / d_single (0 or None: not wanted) receive one image of L * M * M / M * M bytes
+        per map: the rasters of all its entries' moved clouds together.  Asynchronous: synchronize() before the host reads
+        them."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        assert offsets.shape[0] == n_frames + 1
+        n_maps, map_offsets, entry_frame, entry_pose = self._submap_entries(map_offsets, entry_frame, entry_pose)
+        rc = self.lib.bev_submap_bev_device_resident(self._h, n_frames, C.c_void_p(d_clouds),
+                                                     offsets.ctypes.data_as(C.POINTER(C.c_uint64)), n_maps,
+                                                     map_offsets.ctypes.data_as(C.POINTER(C.c_uint64)), _ptr(entry_frame),
+                                                     _ptr(entry_pose), C.c_void_p(d_multi or None), C.c_void_p(d_single or None))
+        self._check(rc, "bev_submap_bev_device_resident")
+
+    def submap_bev_batch(self, clouds, map_offsets, entry_frame, entry_pose, want_multi=True, want_single=True):
+        """bev_submap_bev_batch on host clouds; maps as for submap_bev_device; returns (multi, single): (n_maps, L, M, M) and
+        (n_maps, M, M) uint8, None for the one that is not wanted."""
+        n = len(clouds)
+        clouds = [np.ascontiguousarray(f, dtype=POINT_DTYPE) for f in clouds]
+        n_maps, map_offsets, entry_frame, entry_pose = self._submap_entries(map_offsets, entry_frame, entry_pose)
+        multi = np.empty((n_maps, self.L, self.M, self.M), dtype=np.uint8) if want_multi else None
+        single = np.empty((n_maps, self.M, self.M), dtype=np.uint8) if want_single else None
+        VP, VM = C.c_void_p * max(n, 1), C.c_void_p * max(n_maps, 1)
+        pts = VP(*[f.ctypes.data if len(f) else None for f in clouds])
+        npts = (C.c_uint32 * max(n, 1))(*[len(f) for f in clouds])
+        m = VM(*[multi[i].ctypes.data for i in range(n_maps)]) if want_multi else None
+        s = VM(*[single[i].ctypes.data for i in range(n_maps)]) if want_single else None
+        rc = self.lib.bev_submap_bev_batch(self._h, n, pts, npts, n_maps, map_offsets.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                           _ptr(entry_frame), _ptr(entry_pose), m, s)
+        self._check(rc, "bev_submap_bev_batch")
         return multi, single
 
     def transform_cloud(self, cloud, m):

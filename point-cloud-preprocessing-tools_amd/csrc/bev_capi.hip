@@ -21,6 +21,7 @@
 #include "bev_ctx.h"
 #include "bev_libm.h"
 #include "bev_libm_f64.h"
+#include "bev_submap_plan.h"
 
 using namespace bevk;
 using namespace bevh;
@@ -745,6 +746,105 @@ int posed_bev_frames(bev_ctx *c, int nf, const bev_point_t *d_clouds, const uint
     return BEV_OK;
 }
 
+/* The cap of a launch group in grids, as posed_bev_frames computes it: maps take the planes of the posed call */
+size_t posed_cap_grids(const bev_ctx *c)
+{
+    const size_t M = (size_t)c->geo.rp.mat_size, grid_bytes = 2 * M * M * sizeof(uint32_t);
+    return c->posed_group > 0 ? (size_t)c->posed_group : std::max<size_t>(1, kPosedWsCap / grid_bytes);
+}
+
+/* ---- submaps: windows of posed frames rastered into one grid per map (bev_submap_plan.h, bev_submap.h) ---- */
+/* A plan on its way to the device: the planes of its largest group in posed_ws, its tables in ONE block of submap_tab, sent up
+ * the context's stream. */
+struct SubmapPlanUp {
+    bevsub::Plan plan;
+    std::vector<bevsub::GroupBytes> at; /* per group: where its tables lie in the block */
+    const char *dev = nullptr;
+    uint32_t *planes = nullptr;
+    size_t grid_bytes = 0;
+};
+int submap_plan_up(bev_ctx *c, SubmapPlanUp &u)
+{
+    const size_t M = (size_t)c->geo.rp.mat_size;
+    u.grid_bytes = 2 * M * M * sizeof(uint32_t);
+    int most = 0;
+    size_t bytes = 0;
+    for (const bevsub::Group &g : u.plan.groups) {
+        most = std::max(most, g.n_maps);
+        u.at.push_back(bevsub::group_bytes(g, bytes));
+        bytes = u.at.back().end;
+    }
+    int rc = c->posed_ws.grow(c, (size_t)most * u.grid_bytes); /* (a grow waits for the stream: before the table goes up) */
+    if (rc != BEV_OK) return rc;
+    char *h = nullptr;
+    rc = c->submap_tab.begin(c, bytes, 64 * 1024, reinterpret_cast<void **>(&h));
+    if (rc != BEV_OK) return rc;
+    bevsub::pack(u.plan, h);
+    u.dev = static_cast<const char *>(c->submap_tab.dev);
+    u.planes = static_cast<uint32_t *>(c->posed_ws.p);
+    return c->submap_tab.push(c, bytes);
+}
+/* group gi of an uploaded plan on the context's stream: its planes zeroed ... */
+int submap_clear(bev_ctx *c, const SubmapPlanUp &u, size_t gi)
+{
+    HIPCK(c, hipMemsetAsync(u.planes, 0, (size_t)u.plan.groups[gi].n_maps * u.grid_bytes, c->stream));
+    return BEV_OK;
+}
+/* ... its rows [r0, r0 + nr) splatted from d_clouds (left out where they hold no point) ... */
+void submap_splat(bev_ctx *c, const SubmapPlanUp &u, size_t gi, const bev_point_t *d_clouds, int r0, int nr)
+{
+    const bevsub::Group &g = u.plan.groups[gi];
+    const bevsub::Frame *rows = u.plan.rows.data() + g.row0;
+    const uint32_t blocks = rows[r0 + nr].blk0 - rows[r0].blk0;
+    if (blocks == 0) return;
+    ProfScope ps(c, K_SUBMAP_SPLAT, nr);
+    launch_submap_splat(d_clouds, u.dev + u.at[gi].rows + (size_t)r0 * sizeof(bevsub::Frame),
+                        reinterpret_cast<const uint32_t *>(u.dev + u.at[gi].ent0) + r0, nr, blocks, u.dev + u.at[gi].entries,
+                        c->geo, u.planes, c->stream);
+}
+/* ... and its planes expanded into its maps' images, the group's first map at d_multi / d_single (nullptr: not wanted) */
+void submap_expand(bev_ctx *c, const SubmapPlanUp &u, size_t gi, uint8_t *d_multi, uint8_t *d_single)
+{
+    const int n = u.plan.groups[gi].n_maps;
+    ProfScope ps(c, K_POSED_EXPAND, n);
+    launch_posed_expand(c->geo, u.planes, n, d_multi, d_single, c->stream);
+}
+
+/* The images of n_maps maps over nf frames in device memory, on the context's stream (arguments checked by the caller) */
+int submap_bev_frames(bev_ctx *c, const bev_point_t *d_clouds, const uint64_t *offs, int n_maps, const uint64_t *map_offs,
+                      const int32_t *entry_frame, const float *entry_pose, uint8_t *d_multi, uint8_t *d_single)
+{
+    SubmapPlanUp u;
+    if (!bevsub::plan_maps(u.plan, offs, map_offs, 0, n_maps, entry_frame, entry_pose, posed_cap_grids(c))) return BEV_ERR_TOO_LARGE;
+    int rc = submap_plan_up(c, u);
+    if (rc != BEV_OK) return rc;
+    for (size_t gi = 0; gi < u.plan.groups.size(); ++gi) {
+        const bevsub::Group &g = u.plan.groups[gi];
+        rc = submap_clear(c, u, gi);
+        if (rc != BEV_OK) return rc;
+        submap_splat(c, u, gi, d_clouds, 0, g.n_rows);
+        submap_expand(c, u, gi, d_multi ? d_multi + (size_t)g.map0 * c->multi_bytes : nullptr,
+                      d_single ? d_single + (size_t)g.map0 * c->single_bytes : nullptr);
+    }
+    HIPCK(c, hipGetLastError());
+    return BEV_OK;
+}
+
+/* What both submap entry points check of the maps: BEV_OK, or what the entry point returns.  The entry arrays are read only
+ * when their length has passed. */
+int check_submap_entries(int n_frames, int n_maps, const uint64_t *map_offs, const int32_t *entry_frame, const float *entry_pose)
+{
+    if (n_maps < 0 || !map_offs) return BEV_ERR_INVALID_ARG;
+    for (int g = 0; g < n_maps; ++g)
+        if (map_offs[g + 1] < map_offs[g]) return BEV_ERR_INVALID_ARG;
+    const uint64_t n_entries = map_offs[n_maps] - map_offs[0];
+    if (n_entries > BEV_SUBMAP_MAX_ENTRIES) return BEV_ERR_TOO_LARGE;
+    if (n_entries && (!entry_frame || !entry_pose)) return BEV_ERR_INVALID_ARG;
+    for (uint64_t e = map_offs[0]; e < map_offs[n_maps]; ++e)
+        if (entry_frame[e] < 0 || entry_frame[e] >= n_frames) return BEV_ERR_INVALID_ARG;
+    return BEV_OK;
+}
+
 /* bev_process_batch (kind < 0: in[f] holds n_pts[f] records) and bev_process_batch_xyzi (in[f] holds n_pts[f] raw returns
  * of `kind`): chunks of the batch go up, through the projection where they are raw, through the pipeline and down again */
 int process_batch_host(bev_ctx_t *c, int kind, int n_frames, const void *const *in, const uint32_t *n_pts,
@@ -1079,6 +1179,7 @@ void bev_destroy(bev_ctx_t *c)
     c->manip_tab.release();
     c->manip_grids.release();
     c->posed_tab.release();
+    c->submap_tab.release();
     c->posed_ws.release();
     c->posed_imgs.release();
     for (auto &s : c->prof_pool) {
@@ -1411,6 +1512,89 @@ int bev_posed_bev_batch(bev_ctx_t *c, int n_frames, const bev_point_t *const *cl
         }
         return BEV_OK;
     });
+}
+
+int bev_submap_bev_device_resident(bev_ctx_t *c, int n_frames, const bev_point_t *d_clouds, const uint64_t *h_offsets, int n_maps,
+                                   const uint64_t *h_map_offsets, const int32_t *h_entry_frame, const float *h_entry_pose,
+                                   uint8_t *d_multi, uint8_t *d_single)
+{
+    const int rc = check_packed_frames(c, n_frames, h_offsets);
+    if (rc == BEV_ERR_INVALID_ARG) return rc;
+    const int rc_maps = check_submap_entries(n_frames, n_maps, h_map_offsets, h_entry_frame, h_entry_pose);
+    if (rc_maps != BEV_OK) return rc_maps;
+    if (rc != BEV_OK) return rc; /* (a frame that is too large: behind the arguments that are wrong) */
+    if (n_maps == 0) return BEV_OK;
+    if (!d_multi && !d_single) return BEV_ERR_INVALID_ARG;
+    for (uint64_t e = h_map_offsets[0]; e < h_map_offsets[n_maps] && !d_clouds; ++e)
+        if (h_offsets[h_entry_frame[e] + 1] != h_offsets[h_entry_frame[e]]) return BEV_ERR_INVALID_ARG; /* records to read */
+    return resident_call(c, [&] {
+        return submap_bev_frames(c, d_clouds, h_offsets, n_maps, h_map_offsets, h_entry_frame, h_entry_pose, d_multi, d_single);
+    });
+}
+
+/* Maps in chunks of one launch group of at most max_batch maps; the distinct frames a chunk names go through the input
+ * staging max_batch at a time, each such piece splatted into the chunk's planes before the next piece goes up. */
+int bev_submap_bev_batch(bev_ctx_t *c, int n_frames, const bev_point_t *const *clouds, const uint32_t *n_pts, int n_maps,
+                         const uint64_t *h_map_offsets, const int32_t *h_entry_frame, const float *h_entry_pose,
+                         uint8_t *const *multi_out, uint8_t *const *single_out)
+{
+    if (!c || n_frames < 0 || !host_clouds_ok(n_frames, clouds, n_pts)) return BEV_ERR_INVALID_ARG;
+    int rc = check_submap_entries(n_frames, n_maps, h_map_offsets, h_entry_frame, h_entry_pose);
+    if (rc != BEV_OK) return rc;
+    if (n_maps > 0 && !multi_out && !single_out) return BEV_ERR_INVALID_ARG;
+    for (int g = 0; g < n_maps; ++g)
+        if ((multi_out && !multi_out[g]) || (single_out && !single_out[g])) return BEV_ERR_INVALID_ARG;
+    for (int f = 0; f < n_frames; ++f)
+        if ((size_t)n_pts[f] > cloud_cap(c)) return BEV_ERR_TOO_LARGE;
+    if (n_maps == 0) return BEV_OK;
+    rc = begin_call(c, true);
+    if (rc != BEV_OK) return rc;
+    const int chunk = (int)std::min<size_t>((size_t)std::min(n_maps, c->max_batch), posed_cap_grids(c));
+    const size_t multi_map = multi_out ? c->multi_bytes : 0, single_map = single_out ? c->single_bytes : 0;
+    rc = c->posed_imgs.grow(c, (size_t)chunk * (multi_map + single_map));
+    if (rc != BEV_OK) return rc;
+    uint8_t *d_multi = multi_out ? static_cast<uint8_t *>(c->posed_imgs.p) : nullptr;
+    uint8_t *d_single = single_out ? static_cast<uint8_t *>(c->posed_imgs.p) + (size_t)chunk * multi_map : nullptr;
+    const auto chunks = [&]() -> int {
+        std::vector<uint64_t> offs((size_t)n_frames + 1, 0); /* (only the counts matter: a row's offset is set per piece) */
+        for (int f = 0; f < n_frames; ++f) offs[f + 1] = offs[f] + n_pts[f];
+        for (int m0 = 0; m0 < n_maps; m0 += chunk) {
+            const int nm = std::min(chunk, n_maps - m0);
+            SubmapPlanUp u;
+            if (!bevsub::plan_maps(u.plan, offs.data(), h_map_offsets, m0, m0 + nm, h_entry_frame, h_entry_pose, (size_t)nm))
+                return BEV_ERR_TOO_LARGE;
+            const bevsub::Group &g = u.plan.groups[0];
+            bevsub::Frame *rows = u.plan.rows.data() + g.row0;
+            for (int r = 0; r < g.n_rows; ++r) /* where the row's frame will lie in the staging while its piece is there */
+                rows[r].off = r % c->max_batch ? rows[r - 1].off + rows[r - 1].n : 0;
+            int rc_ = submap_plan_up(c, u);
+            if (rc_ == BEV_OK) rc_ = submap_clear(c, u, 0);
+            if (rc_ != BEV_OK) return rc_;
+            for (int r0 = 0; r0 < g.n_rows; r0 += c->max_batch) {
+                const int nr = std::min(c->max_batch, g.n_rows - r0);
+                for (int r = r0; r < r0 + nr; ++r)
+                    if (rows[r].n)
+                        HIPCK(c, hipMemcpyAsync(c->st_in + rows[r].off, clouds[u.plan.frame[g.row0 + r]],
+                                                (size_t)rows[r].n * sizeof(bev_point_t), hipMemcpyHostToDevice, c->stream));
+                submap_splat(c, u, 0, c->st_in, r0, nr);
+            }
+            submap_expand(c, u, 0, d_multi, d_single);
+            HIPCK(c, hipGetLastError());
+            for (int m = 0; m < nm; ++m) {
+                if (multi_out)
+                    HIPCK(c, hipMemcpyAsync(multi_out[m0 + m], d_multi + (size_t)m * multi_map, multi_map, hipMemcpyDeviceToHost,
+                                            c->stream));
+                if (single_out)
+                    HIPCK(c, hipMemcpyAsync(single_out[m0 + m], d_single + (size_t)m * single_map, single_map,
+                                            hipMemcpyDeviceToHost, c->stream));
+            }
+        }
+        HIPCK(c, hipStreamSynchronize(c->stream));
+        return BEV_OK;
+    };
+    rc = chunks();
+    if (rc != BEV_OK) (void)hipDeviceSynchronize();
+    return rc;
 }
 
 int bev_transform_cloud(bev_ctx_t *c, const bev_point_t *cloud, uint32_t n, const float *m, bev_point_t *out)

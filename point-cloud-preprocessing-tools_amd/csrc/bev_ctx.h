@@ -236,6 +236,9 @@ struct bev_ctx {
      * grown on demand */
     bevh::UploadTable posed_tab;
     bevh::DevBuf posed_ws, posed_imgs;
+    /* ... of submaps (submap_plan_up & co., bev_capi.hip): the plan of a call; the planes are posed_ws, the images of
+     * bev_submap_bev_batch's chunks posed_imgs (both host-buffer calls are synchronous) */
+    bevh::UploadTable submap_tab;
     int posed_group = 0; /* BEV_POSED_GROUP=1 .. 65535: grids per launch group (tests: results do not depend on it); 0: what fits kPosedWsCap */
 
     bevh::RegState reg;

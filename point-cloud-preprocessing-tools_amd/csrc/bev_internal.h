@@ -222,6 +222,7 @@ enum KernelId {
     K_FLOAT_BEV_BATCH, /* the float BEV of a batch of frames under per-frame poses (bev_manip.h; K_FLOAT_BEV: one cloud) */
     K_POSED_SPLAT,     /* the 24-layer and uint8 BEVs of a batch of frames under per-frame poses (bev_posed.h): points into the workspace planes */
     K_POSED_EXPAND,    /* ... the planes into the images */
+    K_SUBMAP_SPLAT,    /* the same BEVs of submaps (bev_submap.h): the points of a group's frames into their entries' grids (the images: K_POSED_EXPAND) */
     K_COUNT
 };
 const char *kernel_name(int id);
@@ -322,6 +323,12 @@ void launch_float_bev_batch(const bev_point_t *clouds, const ProjFrame *tab, int
 void launch_posed_splat(const bev_point_t *clouds, const ProjFrame *tab, int nf, uint32_t blocks, const float *poses, int n_poses,
                         const Geometry &g, uint32_t *planes, hipStream_t st);
 void launch_posed_expand(const Geometry &g, const uint32_t *planes, int n_grids, uint8_t *multi, uint8_t *single, hipStream_t st);
+/* ---- the same BEVs of submaps: windows of posed frames rastered into one grid per map (bev_submap.h) ----
+ * a piece of one launch group of the plan (bev_submap_plan.h): the nf rows from rows[0] on (bevsub::Frame, read as ProjFrame)
+ * with their entry starts ent0 (nf + 1 values), blocks = rows[nf].blk0 - rows[0].blk0 workgroups; entries: the group's
+ * (bevsub::Entry); planes: the group's grids, zeroed by the caller on the same stream.  The images: launch_posed_expand. */
+void launch_submap_splat(const bev_point_t *clouds, const void *rows, const uint32_t *ent0, int nf, uint32_t blocks,
+                         const void *entries, const Geometry &g, uint32_t *planes, hipStream_t st);
 void launch_angle_debug(const float *dx, const float *dy, const float *dz, uint8_t *out, size_t n, hipStream_t st);
 /* ---- registration front end (bev_regfront.h; DESIGN.md "Registration front end") ---- */
 constexpr int kRfThreads = 256;

@@ -39,6 +39,7 @@
 #include "bev_project.h"
 #include "bev_manip.h"
 #include "bev_posed.h"
+#include "bev_submap.h"
 #include "bev_reg_common.h"
 #include "bev_regfront.h"
 #include "bev_icp.h"
@@ -54,7 +55,7 @@ static const char *const kNames[K_COUNT] = {
     "k_probe", "k_walk_general", "k_walk_structured", "k_walk_colmajor", "k_walk_colmajor_gen", "k_verdict", "k_stage",
     "k_rf_cells", "k_rf_top", "k_rf_voxel", "k_rf_normals", "k_icp_grid", "k_icp", "k_icp_best",
     "k_fine_voxel", "k_fine_grid", "k_fine_icp", "k_kitti_crossings", "k_kitti_chain", "k_kitti_assign", "k_kitti_gather",
-    "k_float_bev_batch", "k_posed_splat", "k_posed_expand",
+    "k_float_bev_batch", "k_posed_splat", "k_posed_expand", "k_submap_splat",
 };
 const char *kernel_name(int id) { return (id >= 0 && id < K_COUNT) ? kNames[id] : "?"; }
 
@@ -291,6 +292,13 @@ void launch_posed_expand(const Geometry &g, const uint32_t *planes, int n_grids,
     if (n_grids == 0) return;
     hipLaunchKernelGGL(k_posed_expand, dim3((unsigned)n_grids * (unsigned)g.raster_bands), dim3(kRasterThreads),
                        raster_lds_bytes(g), st, planes, multi, single, g.rp);
+}
+void launch_submap_splat(const bev_point_t *clouds, const void *rows, const uint32_t *ent0, int nf, uint32_t blocks,
+                         const void *entries, const Geometry &g, uint32_t *planes, hipStream_t st)
+{
+    if (blocks == 0 || nf == 0) return;
+    hipLaunchKernelGGL(k_submap_splat, dim3(blocks), dim3(256), 0, st, clouds, static_cast<const ProjFrame *>(rows), ent0, nf,
+                       static_cast<const bevsub::Entry *>(entries), g.rp, planes);
 }
 void launch_project_kitti(int step, const float *xyzi, const ProjFrame *tab, int nf, uint32_t n_max, const KittiWork &w,
                           bev_point_t *out, hipStream_t st)
