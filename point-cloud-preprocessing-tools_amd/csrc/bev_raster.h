@@ -109,17 +109,21 @@ __device__ __forceinline__ void raster_body(uint32_t *lds, const BatchPtrs &b, c
     PH_DECL;
     PH();
 
-    /* round trip 1: the list lengths; the planes are zeroed meanwhile */
-    uint32_t my_cnt = 0u;
+    /* round trip 1: the list lengths; the planes are zeroed meanwhile.  A sensor of more than 252 strips (H > 59,472) has more
+     * lists than the workgroup has threads: the first 28 threads take a second one */
+    static_assert(kMaxStrips + kResolveParts <= 2 * kRasterThreads, "two lists per thread at the most");
+    uint32_t my_cnt = 0u, my_cnt2 = 0u;
     if (tid < E) my_cnt = b.ncode[((size_t)f * E + tid) * bands + band];
+    if (tid + kRasterThreads < E) my_cnt2 = b.ncode[((size_t)f * E + tid + kRasterThreads) * bands + band];
     for (int k = tid; k < 2 * cells; k += kRasterThreads) lds[k] = 0u;
     if (tid < E) list_end[tid + 1] = my_cnt;
+    if (tid + kRasterThreads < E) list_end[tid + kRasterThreads + 1] = my_cnt2;
     if (tid == 0) {
         list_end[0] = 0u;
         over_l = 0u;
     }
     lds_barrier();
-    if (my_cnt > g.code_cap) over_l = 1u;
+    if (my_cnt > g.code_cap || my_cnt2 > g.code_cap) over_l = 1u;
     if (tid == 0) /* few lists (13 for HDL_64E): a serial prefix */
         for (int e = 0; e < E; ++e) list_end[e + 1] += list_end[e];
     lds_barrier();
