@@ -237,6 +237,27 @@ def _ptr(a: np.ndarray | None) -> C.c_void_p:
     return C.c_void_p(a.ctypes.data) if a is not None else C.c_void_p(None)
 
 
+def _offsets(offsets, n_frames):
+    """the n_frames + 1 offsets of packed frames as the C ABI takes them: (contiguous uint64 array, its pointer)"""
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    assert offsets.shape[0] == n_frames + 1
+    return offsets, offsets.ctypes.data_as(C.POINTER(C.c_uint64))
+
+
+def _host_clouds(clouds, dtype=POINT_DTYPE, per=1):
+    """host clouds as the batched calls take them: (the contiguous clouds, to be kept alive; their void* array, None for an
+    empty cloud; their uint32 counts of items of `per` elements)"""
+    clouds = [np.ascontiguousarray(f, dtype=dtype).reshape(-1) for f in clouds]
+    n = max(len(clouds), 1)
+    return (clouds, (C.c_void_p * n)(*[f.ctypes.data if f.size >= per else None for f in clouds]),
+            (C.c_uint32 * n)(*[f.size // per for f in clouds]))
+
+
+def _rows(out):
+    """the void* array of an output's rows (one per frame or map); None when the output is not wanted"""
+    return (C.c_void_p * max(len(out), 1))(*[row.ctypes.data for row in out]) if out is not None else None
+
+
 class BevContext:
     """One context per GPU (bev_create / bev_destroy)."""
 
@@ -271,50 +292,35 @@ class BevContext:
             raise BevError(f"{what} failed: {msg} (status {rc}) {detail}")
 
     # ---- whole hot path, host buffers ---------------------------------
-    def process_batch(self, frames, want_multi=True, want_single=True, want_ground_mat=False):
-        n = len(frames)
-        frames = [np.ascontiguousarray(f, dtype=POINT_DTYPE) for f in frames]
+    def _batch_outputs(self, n, want_multi, want_single, want_ground_mat):
+        """the four outputs of process_batch / process_batch_xyzi for n frames, None for those that are not wanted"""
         ordered = np.empty((n, self.S), dtype=POINT_DTYPE)
         multi = np.empty((n, self.L, self.M, self.M), dtype=np.uint8) if want_multi else None
         single = np.empty((n, self.M, self.M), dtype=np.uint8) if want_single else None
         gm = np.empty((n, self.params.n_scan, self.params.horizon_scan), dtype=np.int8) if want_ground_mat else None
-        VP = C.c_void_p * max(n, 1)
-        pts = VP(*[f.ctypes.data if len(f) else None for f in frames])
-        npts = (C.c_uint32 * max(n, 1))(*[len(f) for f in frames])
-        o = VP(*[ordered[i].ctypes.data for i in range(n)])
-        m = VP(*[multi[i].ctypes.data for i in range(n)]) if want_multi else None
-        s = VP(*[single[i].ctypes.data for i in range(n)]) if want_single else None
-        g = VP(*[gm[i].ctypes.data for i in range(n)]) if want_ground_mat else None
-        rc = self.lib.bev_process_batch(self._h, n, pts, npts, o, m, s, g)
-        self._check(rc, "bev_process_batch")
         return ordered, multi, single, gm
+
+    def process_batch(self, frames, want_multi=True, want_single=True, want_ground_mat=False):
+        frames, pts, npts = _host_clouds(frames)
+        out = self._batch_outputs(len(frames), want_multi, want_single, want_ground_mat)
+        rc = self.lib.bev_process_batch(self._h, len(frames), pts, npts, *[_rows(o) for o in out])
+        self._check(rc, "bev_process_batch")
+        return out
 
     def process_batch_xyzi(self, kind: int, frames, want_multi=True, want_single=True, want_ground_mat=False):
         """process_batch on raw returns (bev_process_batch_xyzi): frames[f] is what project_xyzi(kind, .) takes; the
         outputs are those of process_batch on the projected clouds."""
-        n = len(frames)
-        frames = [np.ascontiguousarray(f, dtype=np.float32).reshape(-1) for f in frames]
-        ordered = np.empty((n, self.S), dtype=POINT_DTYPE)
-        multi = np.empty((n, self.L, self.M, self.M), dtype=np.uint8) if want_multi else None
-        single = np.empty((n, self.M, self.M), dtype=np.uint8) if want_single else None
-        gm = np.empty((n, self.params.n_scan, self.params.horizon_scan), dtype=np.int8) if want_ground_mat else None
-        VP = C.c_void_p * max(n, 1)
-        raw = VP(*[f.ctypes.data if f.size >= 4 else None for f in frames])
-        nret = (C.c_uint32 * max(n, 1))(*[f.size // 4 for f in frames])
-        o = VP(*[ordered[i].ctypes.data for i in range(n)])
-        m = VP(*[multi[i].ctypes.data for i in range(n)]) if want_multi else None
-        s = VP(*[single[i].ctypes.data for i in range(n)]) if want_single else None
-        g = VP(*[gm[i].ctypes.data for i in range(n)]) if want_ground_mat else None
-        rc = self.lib.bev_process_batch_xyzi(self._h, kind, n, raw, nret, o, m, s, g)
+        frames, raw, nret = _host_clouds(frames, np.float32, 4)
+        out = self._batch_outputs(len(frames), want_multi, want_single, want_ground_mat)
+        rc = self.lib.bev_process_batch_xyzi(self._h, kind, len(frames), raw, nret, *[_rows(o) for o in out])
         self._check(rc, "bev_process_batch_xyzi")
-        return ordered, multi, single, gm
+        return out
 
     # ---- whole hot path, device pointers --------------------------------
     def process_device(self, n_frames, d_pts, offsets, d_ordered, d_multi, d_single, d_ground_mat=None):
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-        assert offsets.shape[0] == n_frames + 1
+        offsets, offs = _offsets(offsets, n_frames)
         rc = self.lib.bev_process_device_resident(
-            self._h, n_frames, C.c_void_p(d_pts), offsets.ctypes.data_as(C.POINTER(C.c_uint64)),
+            self._h, n_frames, C.c_void_p(d_pts), offs,
             C.c_void_p(d_ordered), C.c_void_p(d_multi), C.c_void_p(d_single), C.c_void_p(d_ground_mat))
         self._check(rc, "bev_process_device_resident")
 
@@ -322,10 +328,8 @@ class BevContext:
         """bev_project_device_resident on device pointers: frame f = returns [offsets[f], offsets[f + 1]) of d_xyzi; kinds
         0 / 1 write records at the same offsets of d_out, KITTI frame f's structured cloud at f * KITTI_SLOTS.
         Asynchronous: a process_device behind it reads finished records; synchronize() before the host reads d_out."""
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-        assert offsets.shape[0] == n_frames + 1
-        rc = self.lib.bev_project_device_resident(self._h, kind, n_frames, C.c_void_p(d_xyzi),
-                                                  offsets.ctypes.data_as(C.POINTER(C.c_uint64)), C.c_void_p(d_out))
+        offsets, offs = _offsets(offsets, n_frames)
+        rc = self.lib.bev_project_device_resident(self._h, kind, n_frames, C.c_void_p(d_xyzi), offs, C.c_void_p(d_out))
         self._check(rc, "bev_project_device_resident")
 
     def synchronize(self):
@@ -379,26 +383,21 @@ class BevContext:
         """bev_float_bev_device_resident on device pointers: frame f = records [offsets[f], offsets[f + 1]) of d_clouds;
         poses: None, or (n_frames, n_poses, 12) host floats (row-major 3 x 4, yaw_translate_matrix); d_out receives
         n_frames * max(1, n_poses) grids of M * M floats.  Asynchronous: synchronize() before the host reads d_out."""
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-        assert offsets.shape[0] == n_frames + 1
+        offsets, offs = _offsets(offsets, n_frames)
         n_poses, poses = self._poses(poses, n_frames)
-        rc = self.lib.bev_float_bev_device_resident(self._h, n_frames, C.c_void_p(d_clouds),
-                                                    offsets.ctypes.data_as(C.POINTER(C.c_uint64)), interval,
+        rc = self.lib.bev_float_bev_device_resident(self._h, n_frames, C.c_void_p(d_clouds), offs, interval,
                                                     1 if skip_label0 else 0, n_poses, _ptr(poses), C.c_void_p(d_out))
         self._check(rc, "bev_float_bev_device_resident")
 
     def float_bev_batch(self, clouds, interval=1.0, skip_label0=True, poses=None):
         """bev_float_bev_batch on host clouds; returns (n_frames, max(1, n_poses), M, M) float32."""
+        clouds, pts, npts = _host_clouds(clouds)
         n = len(clouds)
-        clouds = [np.ascontiguousarray(f, dtype=POINT_DTYPE) for f in clouds]
         n_poses, poses = self._poses(poses, n)
         M = int(self.lib.bev_float_bev_size(interval))
         out = np.empty((n, max(1, n_poses), M, M), dtype=np.float32)
-        VP = C.c_void_p * max(n, 1)
-        pts = VP(*[f.ctypes.data if len(f) else None for f in clouds])
-        npts = (C.c_uint32 * max(n, 1))(*[len(f) for f in clouds])
-        o = VP(*[out[i].ctypes.data for i in range(n)])
-        rc = self.lib.bev_float_bev_batch(self._h, n, pts, npts, interval, 1 if skip_label0 else 0, n_poses, _ptr(poses), o)
+        rc = self.lib.bev_float_bev_batch(self._h, n, pts, npts, interval, 1 if skip_label0 else 0, n_poses, _ptr(poses),
+                                          _rows(out))
         self._check(rc, "bev_float_bev_batch")
         return out
 
@@ -406,29 +405,22 @@ class BevContext:
         """bev_posed_bev_device_resident on device pointers: frame f = records [offsets[f], offsets[f + 1]) of d_clouds;
         poses: None, or (n_frames, n_poses, 12) host floats; d_multi / d_single (0 or None: not wanted) receive
         n_frames * max(1, n_poses) images of L * M * M / M * M bytes.  Asynchronous: synchronize() before the host reads them."""
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-        assert offsets.shape[0] == n_frames + 1
+        offsets, offs = _offsets(offsets, n_frames)
         n_poses, poses = self._poses(poses, n_frames)
-        rc = self.lib.bev_posed_bev_device_resident(self._h, n_frames, C.c_void_p(d_clouds),
-                                                    offsets.ctypes.data_as(C.POINTER(C.c_uint64)), n_poses, _ptr(poses),
+        rc = self.lib.bev_posed_bev_device_resident(self._h, n_frames, C.c_void_p(d_clouds), offs, n_poses, _ptr(poses),
                                                     C.c_void_p(d_multi or None), C.c_void_p(d_single or None))
         self._check(rc, "bev_posed_bev_device_resident")
 
     def posed_bev_batch(self, clouds, poses=None, want_multi=True, want_single=True):
         """bev_posed_bev_batch on host clouds; returns (multi, single): (n_frames, max(1, n_poses), L, M, M) and
         (n_frames, max(1, n_poses), M, M) uint8, None for the one that is not wanted."""
+        clouds, pts, npts = _host_clouds(clouds)
         n = len(clouds)
-        clouds = [np.ascontiguousarray(f, dtype=POINT_DTYPE) for f in clouds]
         n_poses, poses = self._poses(poses, n)
         K = max(1, n_poses)
         multi = np.empty((n, K, self.L, self.M, self.M), dtype=np.uint8) if want_multi else None
         single = np.empty((n, K, self.M, self.M), dtype=np.uint8) if want_single else None
-        VP = C.c_void_p * max(n, 1)
-        pts = VP(*[f.ctypes.data if len(f) else None for f in clouds])
-        npts = (C.c_uint32 * max(n, 1))(*[len(f) for f in clouds])
-        m = VP(*[multi[i].ctypes.data for i in range(n)]) if want_multi else None
-        s = VP(*[single[i].ctypes.data for i in range(n)]) if want_single else None
-        rc = self.lib.bev_posed_bev_batch(self._h, n, pts, npts, n_poses, _ptr(poses), m, s)
+        rc = self.lib.bev_posed_bev_batch(self._h, n, pts, npts, n_poses, _ptr(poses), _rows(multi), _rows(single))
         self._check(rc, "bev_posed_bev_batch")
         return multi, single
 
@@ -448,11 +440,9 @@ class BevContext:
         entry_pose[e] (12 floats); d_multi / d_single (0 or None: not wanted) receive one image of L * M * M / M * M bytes
         per map: the rasters of all its entries' moved clouds together.  Asynchronous: synchronize() before the host reads
         them."""
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-        assert offsets.shape[0] == n_frames + 1
+        offsets, offs = _offsets(offsets, n_frames)
         n_maps, map_offsets, entry_frame, entry_pose = self._submap_entries(map_offsets, entry_frame, entry_pose)
-        rc = self.lib.bev_submap_bev_device_resident(self._h, n_frames, C.c_void_p(d_clouds),
-                                                     offsets.ctypes.data_as(C.POINTER(C.c_uint64)), n_maps,
+        rc = self.lib.bev_submap_bev_device_resident(self._h, n_frames, C.c_void_p(d_clouds), offs, n_maps,
                                                      map_offsets.ctypes.data_as(C.POINTER(C.c_uint64)), _ptr(entry_frame),
                                                      _ptr(entry_pose), C.c_void_p(d_multi or None), C.c_void_p(d_single or None))
         self._check(rc, "bev_submap_bev_device_resident")
@@ -460,18 +450,13 @@ class BevContext:
     def submap_bev_batch(self, clouds, map_offsets, entry_frame, entry_pose, want_multi=True, want_single=True):
         """bev_submap_bev_batch on host clouds; maps as for submap_bev_device; returns (multi, single): (n_maps, L, M, M) and
         (n_maps, M, M) uint8, None for the one that is not wanted."""
-        n = len(clouds)
-        clouds = [np.ascontiguousarray(f, dtype=POINT_DTYPE) for f in clouds]
+        clouds, pts, npts = _host_clouds(clouds)
         n_maps, map_offsets, entry_frame, entry_pose = self._submap_entries(map_offsets, entry_frame, entry_pose)
         multi = np.empty((n_maps, self.L, self.M, self.M), dtype=np.uint8) if want_multi else None
         single = np.empty((n_maps, self.M, self.M), dtype=np.uint8) if want_single else None
-        VP, VM = C.c_void_p * max(n, 1), C.c_void_p * max(n_maps, 1)
-        pts = VP(*[f.ctypes.data if len(f) else None for f in clouds])
-        npts = (C.c_uint32 * max(n, 1))(*[len(f) for f in clouds])
-        m = VM(*[multi[i].ctypes.data for i in range(n_maps)]) if want_multi else None
-        s = VM(*[single[i].ctypes.data for i in range(n_maps)]) if want_single else None
-        rc = self.lib.bev_submap_bev_batch(self._h, n, pts, npts, n_maps, map_offsets.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                           _ptr(entry_frame), _ptr(entry_pose), m, s)
+        rc = self.lib.bev_submap_bev_batch(self._h, len(clouds), pts, npts, n_maps,
+                                           map_offsets.ctypes.data_as(C.POINTER(C.c_uint64)), _ptr(entry_frame),
+                                           _ptr(entry_pose), _rows(multi), _rows(single))
         self._check(rc, "bev_submap_bev_batch")
         return multi, single
 
@@ -526,11 +511,7 @@ class BevContext:
                                   viewpoint=(0.0, 0.0, 0.0)):
         """The chain on device pointers (bev_registration_front_device_resident); offsets None: d_clouds is the d_ordered
         layout (n_frames * S points).  Asynchronous: synchronize() before reading d_out / d_counts."""
-        offs = None
-        if offsets is not None:
-            offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-            assert offsets.shape[0] == n_frames + 1
-            offs = offsets.ctypes.data_as(C.POINTER(C.c_uint64))
+        offsets, offs = _offsets(offsets, n_frames) if offsets is not None else (None, None)
         vp = np.asarray(viewpoint, dtype=np.float32).reshape(3)
         self._check(self.lib.bev_registration_front_device_resident(
             self._h, n_frames, C.c_void_p(d_clouds), offs, leaf, radius, _ptr(vp), C.c_void_p(d_out), out_stride,
@@ -645,11 +626,7 @@ class BevContext:
         """bev_fine_registration_device_resident on device pointers; offsets None: d_clouds is the d_ordered layout
         (n_frames * S records); d_coarse / d_best: the coarse entry's outputs (top-part tool) or None (whole tool).
         Asynchronous: synchronize() before reading d_results (one ICP_RESULT_DTYPE per match)."""
-        offs = None
-        if offsets is not None:
-            offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-            assert offsets.shape[0] == n_frames + 1
-            offs = offsets.ctypes.data_as(C.POINTER(C.c_uint64))
+        offsets, offs = _offsets(offsets, n_frames) if offsets is not None else (None, None)
         m = np.ascontiguousarray(matches, dtype=MATCH_DTYPE)
         prm = params if params is not None else icp_fine_defaults()
         self._check(self.lib.bev_fine_registration_device_resident(
@@ -752,9 +729,8 @@ class BevContext:
 
 def project_batch_out_points(kind: int, n_frames: int, offsets) -> int:
     """Records the d_out of project_device must hold (host only); 0 for an unknown kind or decreasing offsets."""
-    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-    assert offsets.shape[0] == n_frames + 1
-    return int(load_lib().bev_project_batch_out_points(kind, n_frames, offsets.ctypes.data_as(C.POINTER(C.c_uint64))))
+    offsets, offs = _offsets(offsets, n_frames)
+    return int(load_lib().bev_project_batch_out_points(kind, n_frames, offs))
 
 
 def regfront_max_out(n: int) -> int:

@@ -1,15 +1,12 @@
 /*
  * bev_capi.hip — context (bev_ctx.h), workspace and the extern "C" boundary declared in include/bev_mi355x.h, but for
- * the registration entry points (bev_capi_reg.hip).  Host-side only; the kernels are in bev_kernels.hip.
- * The three batched calls over packed frames (projection, float BEV, posed BEVs) share one path here: the
- * frame table (upload_packed_table), the bracket of the device-resident calls (resident_call) and the chunk loop of the
- * host-buffer calls (packed_host_chunks).
+ * the batched calls over packed frames (bev_capi_packed.hip) and the registration entry points (bev_capi_reg.hip).
+ * Host-side only; the kernels are in bev_kernels.hip.
  *
  * There is deliberately no CPU implementation behind these entry points: if
  * HIP cannot give us a device, bev_create() fails.
  */
 #include <algorithm>
-#include <cfloat>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -20,8 +17,6 @@
 
 #include "bev_ctx.h"
 #include "bev_libm.h"
-#include "bev_libm_f64.h"
-#include "bev_submap_plan.h"
 
 using namespace bevk;
 using namespace bevh;
@@ -524,327 +519,6 @@ int run_pipeline(bev_ctx *c, int n_frames, const bev_point_t *d_pts, const uint6
 
 namespace {
 
-bool project_kind_ok(int kind)
-{
-    return kind == BEV_PROJECT_MULRAN_OS1_64 || kind == BEV_PROJECT_OXFORD_HDL_32E || kind == BEV_PROJECT_KITTI_HDL_64E;
-}
-
-/* ---- the packed-frame path: batched calls over several clouds that lie one after the other in one device buffer ---------- */
-/* The frame table of a call over packed frames (packed_place, bev_dev.h) and, behind it in the same block, the call's poses,
- * as the host filled them and where they are on the device. */
-struct PackedTable {
-    ProjFrame *host = nullptr;
-    const ProjFrame *dev = nullptr;
-    const float *d_poses = nullptr; /* 12 floats per frame and pose, behind the table */
-    size_t bytes = 0;
-    uint32_t blocks = 0; /* workgroups of kProjBlock points of a launch over all frames: host[nf].blk0 */
-    uint32_t n_max = 0;  /* the longest frame */
-};
-/* Fills t's host block (UploadTable::begin): per frame f = [offs[f], offs[f + 1]) (offsets checked by the caller) its offset,
- * its count and the workgroups before it, entry nf closing the table; then the nf * n_poses matrices at h_poses.
- * BEV_ERR_TOO_LARGE for a grid that one launch cannot have (2^41 points in one call). */
-int fill_packed_table(bev_ctx *c, UploadTable &t, size_t min_cap, int nf, const uint64_t *offs, int n_poses, const float *h_poses,
-                      PackedTable *pt)
-{
-    const size_t tab_bytes = ((size_t)nf + 1) * sizeof(ProjFrame), pose_bytes = (size_t)nf * n_poses * 12 * sizeof(float);
-    char *h = nullptr;
-    const int rc = t.begin(c, tab_bytes + pose_bytes, min_cap, reinterpret_cast<void **>(&h));
-    if (rc != BEV_OK) return rc;
-    ProjFrame *tab = reinterpret_cast<ProjFrame *>(h);
-    uint64_t b = 0;
-    uint32_t m = 0;
-    for (int f = 0; f < nf; ++f) {
-        const uint32_t n = (uint32_t)(offs[f + 1] - offs[f]);
-        tab[f] = ProjFrame{offs[f], n, (uint32_t)b};
-        b += (n + (uint32_t)kProjBlock - 1u) / (uint32_t)kProjBlock;
-        m = std::max(m, n);
-        if (b > 0x7fffffffull) return BEV_ERR_TOO_LARGE;
-    }
-    tab[nf] = ProjFrame{offs[nf], 0u, (uint32_t)b};
-    if (pose_bytes) memcpy(h + tab_bytes, h_poses, pose_bytes);
-    const char *d = static_cast<const char *>(t.dev); /* (begin alone sets dev; push only copies into it) */
-    *pt = PackedTable{tab, reinterpret_cast<const ProjFrame *>(d), reinterpret_cast<const float *>(d + tab_bytes),
-                      tab_bytes + pose_bytes, (uint32_t)b, m};
-    return BEV_OK;
-}
-/* ... and sends it up the context's stream.  Each call has an UploadTable of its own: a shared one would make a call wait for
- * another call's upload event. */
-int upload_packed_table(bev_ctx *c, UploadTable &t, size_t min_cap, int nf, const uint64_t *offs, int n_poses,
-                        const float *h_poses, PackedTable *pt)
-{
-    const int rc = fill_packed_table(c, t, min_cap, nf, offs, n_poses, h_poses, pt);
-    return rc != BEV_OK ? rc : t.push(c, pt->bytes);
-}
-
-/* The projection of nf frames on the context's stream: frame f = returns [offs[f], offs[f + 1]) of d_xyzi (offsets checked by
- * the caller).  Kinds 0 / 1: ONE launch, records at the same offsets of d_out.  KITTI: launch groups of kitti_group frames
- * over one workspace (stream order hands it from group to group), frame f's structured cloud at d_out + f * 64 * 2083. */
-int project_frames(bev_ctx *c, int kind, int nf, const float *d_xyzi, const uint64_t *offs, bev_point_t *d_out)
-{
-    if (nf == 0) return BEV_OK;
-    PackedTable pt;
-    int rc = upload_packed_table(c, c->proj_tab, 1024 * sizeof(ProjFrame), nf, offs, 0, nullptr, &pt);
-    if (rc != BEV_OK) return rc;
-    if (kind != BEV_PROJECT_KITTI_HDL_64E) {
-        ProfScope ps(c, K_PROJECT, nf);
-        launch_project_batch(kind, d_xyzi, pt.dev, nf, pt.blocks, d_out, c->stream);
-    } else {
-        c->layout_hint = BEV_LAYOUT_STRUCTURED; /* what this writes are structured clouds (bev_set_layout_hint) */
-        const size_t S = (size_t)bevx::kKittiRows * bevx::kKittiCols, G = (size_t)std::min(c->kitti_group, nf);
-        KittiWork w{};
-        w.n_cap = pt.n_max;
-        w.blocks_cap = (pt.n_max + bevx::kKittiBlock - 1u) / bevx::kKittiBlock;
-        const size_t sz[] = {G * sizeof(KittiHeader), G * w.n_cap * 4, G * w.blocks_cap * 4,
-                             G * w.blocks_cap * bevx::kKittiListCap * 4, G * S * 4};
-        void **const dst[] = {(void **)&w.hdr, (void **)&w.col, (void **)&w.cnt, (void **)&w.pos, (void **)&w.winner};
-        rc = c->kitti_ws.grow(c, carve(nullptr, sz, dst));
-        if (rc != BEV_OK) return rc;
-        carve(c->kitti_ws.p, sz, dst);
-        for (int f0 = 0; f0 < nf; f0 += (int)G) {
-            const int g = std::min((int)G, nf - f0);
-            HIPCK(c, hipMemsetAsync(w.winner, 0, (size_t)g * S * sizeof(uint32_t), c->stream));
-            for (int step = 0; step < 4; ++step) {
-                ProfScope ps(c, K_KITTI_CROSSINGS + step, g);
-                launch_project_kitti(step, d_xyzi, pt.dev + f0, g, pt.n_max, w, d_out + (size_t)f0 * S, c->stream);
-            }
-        }
-    }
-    HIPCK(c, hipGetLastError());
-    return BEV_OK;
-}
-
-/* the arguments every call over packed frames of the caller's has: BEV_OK, or what the entry point returns */
-int check_packed_frames(const bev_ctx *c, int n_frames, const uint64_t *h_offsets)
-{
-    if (!c || n_frames < 0 || !h_offsets) return BEV_ERR_INVALID_ARG;
-    const uint64_t cap = cloud_cap(c);
-    for (int f = 0; f < n_frames; ++f)
-        if (h_offsets[f + 1] < h_offsets[f]) return BEV_ERR_INVALID_ARG;
-    for (int f = 0; f < n_frames; ++f)
-        if (h_offsets[f + 1] - h_offsets[f] > cap) return BEV_ERR_TOO_LARGE;
-    return BEV_OK;
-}
-/* ... and the calls over host clouds: their arrays */
-bool host_clouds_ok(int n_frames, const bev_point_t *const *clouds, const uint32_t *n_pts)
-{
-    if (n_frames > 0 && (!clouds || !n_pts)) return false;
-    for (int f = 0; f < n_frames; ++f)
-        if (n_pts[f] && !clouds[f]) return false;
-    return true;
-}
-bool poses_ok(int n_poses, const float *h_poses, int max_poses)
-{
-    return n_poses >= 0 && n_poses <= max_poses && (n_poses == 0 || h_poses);
-}
-
-/* A call on packed frames in device memory of the caller's: asynchronous, on the context's stream.  flush_pending joins the
- * stage streams into it, so a BEV call that still reads or writes the caller's buffers (a bev_process_device_resident whose
- * d_ordered this call reads, say) has launched all its stages and comes first; then whatever the caller has queued on the
- * default stream (the upload or the fill of its input, typically); then the body; and the stage streams of the next BEV call
- * wait for what record_tail records: it may read this call's output, or overwrite its input, at once. */
-template <class Body>
-int resident_call(bev_ctx *c, Body body)
-{
-    int rc = begin_call(c, false);
-    if (rc != BEV_OK) return rc;
-    rc = wait_default_stream(c);
-    if (rc != BEV_OK) return rc;
-    rc = body();
-    if (rc != BEV_OK) return rc;
-    return record_tail(c);
-}
-
-/* The host route of a batched call over packed frames (after begin_call with the staging): chunks of max_batch clouds fit the
- * input staging whatever their sizes.  A chunk's clouds are packed into st_in, one copy per non-empty cloud;
- * body(f0, nb, off) launches the chunk's nb frames [off[f], off[f + 1]) of st_in and queues the downloads of their results;
- * all of it follows the chunk before in the order of the context's stream, and one synchronisation ends the call.  An error
- * leaves nothing in flight either: copies of earlier chunks into the caller's buffers may still be on their way. */
-template <class Body>
-int packed_host_chunks(bev_ctx *c, int n_frames, const bev_point_t *const *clouds, const uint32_t *n_pts, Body body)
-{
-    const auto chunks = [&]() -> int {
-        std::vector<uint64_t> off;
-        for (int f0 = 0; f0 < n_frames; f0 += c->max_batch) {
-            const int nb = std::min(c->max_batch, n_frames - f0);
-            off.assign((size_t)nb + 1, 0);
-            for (int f = 0; f < nb; ++f) {
-                off[f + 1] = off[f] + n_pts[f0 + f];
-                if (n_pts[f0 + f])
-                    HIPCK(c, hipMemcpyAsync(c->st_in + off[f], clouds[f0 + f], (size_t)n_pts[f0 + f] * sizeof(bev_point_t),
-                                            hipMemcpyHostToDevice, c->stream));
-            }
-            const int rc_ = body(f0, nb, off.data());
-            if (rc_ != BEV_OK) return rc_;
-        }
-        HIPCK(c, hipStreamSynchronize(c->stream));
-        return BEV_OK;
-    };
-    const int rc = chunks();
-    if (rc != BEV_OK) (void)hipDeviceSynchronize();
-    return rc;
-}
-
-/* The float BEV of nf frames on the context's stream: frame f = records [offs[f], offs[f + 1]) of d_clouds (offsets checked by
- * the caller), its pose k the 12 floats at h_poses + (f * n_poses + k) * 12; nf * max(1, n_poses) grids of M * M floats at
- * d_out, zeroed here.  ONE launch; the frame table and the matrices go up in one block. */
-int float_bev_frames(bev_ctx *c, int nf, const bev_point_t *d_clouds, const uint64_t *offs, float interval, size_t M,
-                     bool skip_label0, int n_poses, const float *h_poses, float *d_out)
-{
-    if (nf == 0) return BEV_OK;
-    PackedTable pt;
-    const int rc = upload_packed_table(c, c->manip_tab, 64 * 1024, nf, offs, n_poses, h_poses, &pt);
-    if (rc != BEV_OK) return rc;
-    HIPCK(c, hipMemsetAsync(d_out, 0, (size_t)nf * std::max(1, n_poses) * M * M * sizeof(float), c->stream));
-    {
-        ProfScope ps(c, K_FLOAT_BEV_BATCH, nf);
-        launch_float_bev_batch(d_clouds, pt.dev, nf, pt.blocks, pt.d_poses, n_poses, interval, (int)M, skip_label0, d_out,
-                               c->stream);
-    }
-    HIPCK(c, hipGetLastError());
-    return BEV_OK;
-}
-
-/* The 24-layer and uint8 BEVs of nf frames on the context's stream: frames and poses as for float_bev_frames;
- * nf * max(1, n_poses) images at d_multi and at d_single (nullptr: not wanted).  The table and the matrices go up once; the
- * frames go in launch groups of consecutive whole frames whose grids fit the workspace cap: the group's planes are zeroed,
- * k_posed_splat fills them, k_posed_expand turns them into the images, and stream order hands the workspace from group to
- * group.  256 MiB is the size of the memory-side cache and bounds the workspace; it is not a tuned figure: in one run per
- * setting, not alternated, one group per call was 3-5 % faster at 0 and 1 poses and 10 % at 8, and groups of 64 grids were a
- * third slower (profiles/posed_bev_groups.txt). */
-constexpr size_t kPosedWsCap = (size_t)256 << 20;
-int posed_bev_frames(bev_ctx *c, int nf, const bev_point_t *d_clouds, const uint64_t *offs, int n_poses, const float *h_poses,
-                     uint8_t *d_multi, uint8_t *d_single)
-{
-    if (nf == 0) return BEV_OK;
-    PackedTable pt;
-    int rc = fill_packed_table(c, c->posed_tab, 64 * 1024, nf, offs, n_poses, h_poses, &pt);
-    if (rc != BEV_OK) return rc;
-    const size_t M = (size_t)c->geo.rp.mat_size, K = (size_t)std::max(1, n_poses), grid_bytes = 2 * M * M * sizeof(uint32_t);
-    const size_t cap_grids = c->posed_group > 0 ? (size_t)c->posed_group : std::max<size_t>(1, kPosedWsCap / grid_bytes);
-    const int per_group = (int)std::min<size_t>((size_t)nf, std::max<size_t>(1, cap_grids / K)); /* (every frame has K grids) */
-    rc = c->posed_ws.grow(c, (size_t)per_group * K * grid_bytes); /* (a grow waits for the stream: before the table goes up) */
-    if (rc != BEV_OK) return rc;
-    rc = c->posed_tab.push(c, pt.bytes);
-    if (rc != BEV_OK) return rc;
-    uint32_t *planes = static_cast<uint32_t *>(c->posed_ws.p);
-    for (int f0 = 0; f0 < nf; f0 += per_group) {
-        const int g = std::min(per_group, nf - f0);
-        const size_t grids = (size_t)g * K, first = (size_t)f0 * K;
-        HIPCK(c, hipMemsetAsync(planes, 0, grids * grid_bytes, c->stream));
-        {
-            ProfScope ps(c, K_POSED_SPLAT, g);
-            launch_posed_splat(d_clouds, pt.dev + f0, g, pt.host[f0 + g].blk0 - pt.host[f0].blk0,
-                               pt.d_poses + (size_t)f0 * n_poses * 12, n_poses, c->geo, planes, c->stream);
-        }
-        {
-            ProfScope ps(c, K_POSED_EXPAND, g);
-            launch_posed_expand(c->geo, planes, (int)grids, d_multi ? d_multi + first * c->multi_bytes : nullptr,
-                                d_single ? d_single + first * c->single_bytes : nullptr, c->stream);
-        }
-    }
-    HIPCK(c, hipGetLastError());
-    return BEV_OK;
-}
-
-/* The cap of a launch group in grids, as posed_bev_frames computes it: maps take the planes of the posed call */
-size_t posed_cap_grids(const bev_ctx *c)
-{
-    const size_t M = (size_t)c->geo.rp.mat_size, grid_bytes = 2 * M * M * sizeof(uint32_t);
-    return c->posed_group > 0 ? (size_t)c->posed_group : std::max<size_t>(1, kPosedWsCap / grid_bytes);
-}
-
-/* ---- submaps: windows of posed frames rastered into one grid per map (bev_submap_plan.h, bev_submap.h) ---- */
-/* A plan on its way to the device: the planes of its largest group in posed_ws, its tables in ONE block of submap_tab, sent up
- * the context's stream. */
-struct SubmapPlanUp {
-    bevsub::Plan plan;
-    std::vector<bevsub::GroupBytes> at; /* per group: where its tables lie in the block */
-    const char *dev = nullptr;
-    uint32_t *planes = nullptr;
-    size_t grid_bytes = 0;
-};
-int submap_plan_up(bev_ctx *c, SubmapPlanUp &u)
-{
-    const size_t M = (size_t)c->geo.rp.mat_size;
-    u.grid_bytes = 2 * M * M * sizeof(uint32_t);
-    int most = 0;
-    size_t bytes = 0;
-    for (const bevsub::Group &g : u.plan.groups) {
-        most = std::max(most, g.n_maps);
-        u.at.push_back(bevsub::group_bytes(g, bytes));
-        bytes = u.at.back().end;
-    }
-    int rc = c->posed_ws.grow(c, (size_t)most * u.grid_bytes); /* (a grow waits for the stream: before the table goes up) */
-    if (rc != BEV_OK) return rc;
-    char *h = nullptr;
-    rc = c->submap_tab.begin(c, bytes, 64 * 1024, reinterpret_cast<void **>(&h));
-    if (rc != BEV_OK) return rc;
-    bevsub::pack(u.plan, h);
-    u.dev = static_cast<const char *>(c->submap_tab.dev);
-    u.planes = static_cast<uint32_t *>(c->posed_ws.p);
-    return c->submap_tab.push(c, bytes);
-}
-/* group gi of an uploaded plan on the context's stream: its planes zeroed ... */
-int submap_clear(bev_ctx *c, const SubmapPlanUp &u, size_t gi)
-{
-    HIPCK(c, hipMemsetAsync(u.planes, 0, (size_t)u.plan.groups[gi].n_maps * u.grid_bytes, c->stream));
-    return BEV_OK;
-}
-/* ... its rows [r0, r0 + nr) splatted from d_clouds (left out where they hold no point) ... */
-void submap_splat(bev_ctx *c, const SubmapPlanUp &u, size_t gi, const bev_point_t *d_clouds, int r0, int nr)
-{
-    const bevsub::Group &g = u.plan.groups[gi];
-    const bevsub::Frame *rows = u.plan.rows.data() + g.row0;
-    const uint32_t blocks = rows[r0 + nr].blk0 - rows[r0].blk0;
-    if (blocks == 0) return;
-    ProfScope ps(c, K_SUBMAP_SPLAT, nr);
-    launch_submap_splat(d_clouds, u.dev + u.at[gi].rows + (size_t)r0 * sizeof(bevsub::Frame),
-                        reinterpret_cast<const uint32_t *>(u.dev + u.at[gi].ent0) + r0, nr, blocks, u.dev + u.at[gi].entries,
-                        c->geo, u.planes, c->stream);
-}
-/* ... and its planes expanded into its maps' images, the group's first map at d_multi / d_single (nullptr: not wanted) */
-void submap_expand(bev_ctx *c, const SubmapPlanUp &u, size_t gi, uint8_t *d_multi, uint8_t *d_single)
-{
-    const int n = u.plan.groups[gi].n_maps;
-    ProfScope ps(c, K_POSED_EXPAND, n);
-    launch_posed_expand(c->geo, u.planes, n, d_multi, d_single, c->stream);
-}
-
-/* The images of n_maps maps over nf frames in device memory, on the context's stream (arguments checked by the caller) */
-int submap_bev_frames(bev_ctx *c, const bev_point_t *d_clouds, const uint64_t *offs, int n_maps, const uint64_t *map_offs,
-                      const int32_t *entry_frame, const float *entry_pose, uint8_t *d_multi, uint8_t *d_single)
-{
-    SubmapPlanUp u;
-    if (!bevsub::plan_maps(u.plan, offs, map_offs, 0, n_maps, entry_frame, entry_pose, posed_cap_grids(c))) return BEV_ERR_TOO_LARGE;
-    int rc = submap_plan_up(c, u);
-    if (rc != BEV_OK) return rc;
-    for (size_t gi = 0; gi < u.plan.groups.size(); ++gi) {
-        const bevsub::Group &g = u.plan.groups[gi];
-        rc = submap_clear(c, u, gi);
-        if (rc != BEV_OK) return rc;
-        submap_splat(c, u, gi, d_clouds, 0, g.n_rows);
-        submap_expand(c, u, gi, d_multi ? d_multi + (size_t)g.map0 * c->multi_bytes : nullptr,
-                      d_single ? d_single + (size_t)g.map0 * c->single_bytes : nullptr);
-    }
-    HIPCK(c, hipGetLastError());
-    return BEV_OK;
-}
-
-/* What both submap entry points check of the maps: BEV_OK, or what the entry point returns.  The entry arrays are read only
- * when their length has passed. */
-int check_submap_entries(int n_frames, int n_maps, const uint64_t *map_offs, const int32_t *entry_frame, const float *entry_pose)
-{
-    if (n_maps < 0 || !map_offs) return BEV_ERR_INVALID_ARG;
-    for (int g = 0; g < n_maps; ++g)
-        if (map_offs[g + 1] < map_offs[g]) return BEV_ERR_INVALID_ARG;
-    const uint64_t n_entries = map_offs[n_maps] - map_offs[0];
-    if (n_entries > BEV_SUBMAP_MAX_ENTRIES) return BEV_ERR_TOO_LARGE;
-    if (n_entries && (!entry_frame || !entry_pose)) return BEV_ERR_INVALID_ARG;
-    for (uint64_t e = map_offs[0]; e < map_offs[n_maps]; ++e)
-        if (entry_frame[e] < 0 || entry_frame[e] >= n_frames) return BEV_ERR_INVALID_ARG;
-    return BEV_OK;
-}
-
 /* bev_process_batch (kind < 0: in[f] holds n_pts[f] records) and bev_process_batch_xyzi (in[f] holds n_pts[f] raw returns
  * of `kind`): chunks of the batch go up, through the projection where they are raw, through the pipeline and down again */
 int process_batch_host(bev_ctx_t *c, int kind, int n_frames, const void *const *in, const uint32_t *n_pts,
@@ -958,6 +632,75 @@ int bevh::begin_call(bev_ctx *c, bool staging)
     const int rc = flush_pending(c);
     if (rc != BEV_OK) return rc;
     return staging ? ensure_staging(c) : BEV_OK;
+}
+
+int DevBuf::grow(bev_ctx *c, size_t need)
+{
+    if (need <= cap) return BEV_OK;
+    /* the last call's kernels may still use the buffer: this wait is what makes reuse safe across unsynchronised calls */
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    if (p) HIPCK(c, hipFree(p));
+    p = nullptr;
+    cap = 0;
+    HIPCK(c, hipMalloc(&p, need));
+    cap = need;
+    return BEV_OK;
+}
+void DevBuf::release()
+{
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+}
+
+int UploadTable::begin(bev_ctx *c, size_t bytes, size_t min_cap, void **host_out)
+{
+    if (!ev) HIPCK(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    else HIPCK(c, hipEventSynchronize(ev)); /* the last call's table has gone up */
+    if (bytes > cap) {
+        HIPCK(c, hipStreamSynchronize(c->stream)); /* (kernels of the last call may still read the device block) */
+        if (host) HIPCK(c, hipHostFree(host));
+        if (dev) HIPCK(c, hipFree(dev));
+        host = dev = nullptr;
+        cap = 0;
+        const size_t n = std::max(bytes, min_cap);
+        HIPCK(c, hipHostMalloc(&host, n, hipHostMallocDefault));
+        HIPCK(c, hipMalloc(&dev, n));
+        cap = n;
+    }
+    *host_out = host;
+    return BEV_OK;
+}
+int UploadTable::push(bev_ctx *c, size_t bytes)
+{
+    if (bytes) HIPCK(c, hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, hipEventRecord(ev, c->stream));
+    return BEV_OK;
+}
+void UploadTable::release()
+{
+    if (host) (void)hipHostFree(host);
+    if (dev) (void)hipFree(dev);
+    if (ev) (void)hipEventDestroy(ev);
+    host = dev = nullptr;
+    ev = nullptr;
+    cap = 0;
+}
+
+int bevh::wait_default_stream(bev_ctx *c)
+{
+    HIPCK(c, hipEventRecord(c->null_ev, nullptr));
+    HIPCK(c, hipStreamWaitEvent(c->stream, c->null_ev, 0));
+    return BEV_OK;
+}
+
+int bevh::record_tail(bev_ctx *c)
+{
+    RegState &r = c->reg;
+    if (!r.tail_ev) HIPCK(c, hipEventCreateWithFlags(&r.tail_ev, hipEventDisableTiming));
+    HIPCK(c, hipEventRecord(r.tail_ev, c->stream));
+    r.tail_pending = true;
+    return BEV_OK;
 }
 
 /* ======================================================================== */
@@ -1339,59 +1082,6 @@ int bev_single_bev(bev_ctx_t *c, const bev_point_t *cloud, uint32_t n, uint8_t *
     return raster_cloud(c, cloud, n, nullptr, single_out);
 }
 
-size_t bev_project_out_points(int kind, uint32_t n)
-{
-    switch (kind) {
-    case BEV_PROJECT_MULRAN_OS1_64:
-    case BEV_PROJECT_OXFORD_HDL_32E: return n;
-    case BEV_PROJECT_KITTI_HDL_64E: return (size_t)bevx::kKittiRows * bevx::kKittiCols;
-    default: return 0;
-    }
-}
-
-int bev_project_xyzi(bev_ctx_t *c, int kind, const float *xyzi, uint32_t n, bev_point_t *out)
-{
-    const size_t n_out = bev_project_out_points(kind, n);
-    if (!c || (n && !xyzi) || (n_out && !out)) return BEV_ERR_INVALID_ARG;
-    if (!project_kind_ok(kind)) return BEV_ERR_INVALID_ARG;
-    if ((size_t)n > cloud_cap(c)) return BEV_ERR_TOO_LARGE;
-    if (n_out == 0) return BEV_OK;
-    int rc = begin_call(c, true);
-    if (rc != BEV_OK) return rc;
-    /* raw floats are staged in the ordered-cloud staging buffer (16 B per point fit its 32 B per slot) */
-    float *d_raw = reinterpret_cast<float *>(c->st_ordered);
-    if ((size_t)n * 16 > (size_t)c->max_batch * c->geo.S * sizeof(bev_point_t)) return BEV_ERR_TOO_LARGE;
-    if (n_out > c->st_in_elems) return BEV_ERR_TOO_LARGE;
-    if (n) HIPCK(c, hipMemcpyAsync(d_raw, xyzi, (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
-    const uint64_t offs[2] = {0, n}; /* one frame of the batched code (n = 0, KITTI: the all-zero structured cloud) */
-    rc = project_frames(c, kind, 1, d_raw, offs, c->st_in);
-    if (rc != BEV_OK) return rc;
-    HIPCK(c, hipMemcpyAsync(out, c->st_in, n_out * sizeof(bev_point_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    return BEV_OK;
-}
-
-size_t bev_project_batch_out_points(int kind, int n_frames, const uint64_t *h_offsets)
-{
-    if (!project_kind_ok(kind) || n_frames < 0 || !h_offsets) return 0;
-    for (int f = 0; f < n_frames; ++f)
-        if (h_offsets[f + 1] < h_offsets[f]) return 0;
-    if (kind == BEV_PROJECT_KITTI_HDL_64E) return (size_t)n_frames * bevx::kKittiRows * bevx::kKittiCols;
-    return (size_t)h_offsets[n_frames]; /* records sit at their returns' offsets */
-}
-
-int bev_project_device_resident(bev_ctx_t *c, int kind, int n_frames, const float *d_xyzi, const uint64_t *h_offsets,
-                                bev_point_t *d_out)
-{
-    if (!project_kind_ok(kind)) return BEV_ERR_INVALID_ARG;
-    const int rc = check_packed_frames(c, n_frames, h_offsets);
-    if (rc != BEV_OK) return rc;
-    if (n_frames == 0) return BEV_OK;
-    const bool any_in = h_offsets[n_frames] != h_offsets[0], any_out = any_in || kind == BEV_PROJECT_KITTI_HDL_64E;
-    if ((any_in && !d_xyzi) || (any_out && !d_out)) return BEV_ERR_INVALID_ARG;
-    return resident_call(c, [&] { return project_frames(c, kind, n_frames, d_xyzi, h_offsets, d_out); });
-}
-
 size_t bev_float_bev_size(float interval)
 {
     if (!(interval > 0.0f)) return 0;
@@ -1420,181 +1110,6 @@ int bev_float_bev(bev_ctx_t *c, const bev_point_t *cloud, uint32_t n, float inte
     HIPCK(c, hipMemcpyAsync(out, grid, M * M * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIPCK(c, hipStreamSynchronize(c->stream));
     return BEV_OK;
-}
-
-int bev_float_bev_device_resident(bev_ctx_t *c, int n_frames, const bev_point_t *d_clouds, const uint64_t *h_offsets,
-                                  float interval, int skip_label0, int n_poses, const float *h_poses, float *d_out)
-{
-    if (!poses_ok(n_poses, h_poses, BEV_FLOAT_BEV_MAX_POSES)) return BEV_ERR_INVALID_ARG;
-    const int rc = check_packed_frames(c, n_frames, h_offsets);
-    if (rc == BEV_ERR_INVALID_ARG) return rc;
-    const size_t M = bev_float_bev_size(interval);
-    if (M == 0) return BEV_ERR_UNSUPPORTED;
-    if (rc != BEV_OK) return rc; /* (a frame that is too large: behind the interval) */
-    if (n_frames == 0) return BEV_OK;
-    if (!d_out || (!d_clouds && h_offsets[n_frames] != h_offsets[0])) return BEV_ERR_INVALID_ARG;
-    return resident_call(c, [&] {
-        return float_bev_frames(c, n_frames, d_clouds, h_offsets, interval, M, skip_label0 != 0, n_poses, h_poses, d_out);
-    });
-}
-
-int bev_float_bev_batch(bev_ctx_t *c, int n_frames, const bev_point_t *const *clouds, const uint32_t *n_pts, float interval,
-                        int skip_label0, int n_poses, const float *h_poses, float *const *out)
-{
-    if (!c || n_frames < 0 || !host_clouds_ok(n_frames, clouds, n_pts) || (n_frames > 0 && !out) ||
-        !poses_ok(n_poses, h_poses, BEV_FLOAT_BEV_MAX_POSES))
-        return BEV_ERR_INVALID_ARG;
-    for (int f = 0; f < n_frames; ++f)
-        if (!out[f]) return BEV_ERR_INVALID_ARG;
-    const size_t M = bev_float_bev_size(interval);
-    if (M == 0) return BEV_ERR_UNSUPPORTED;
-    for (int f = 0; f < n_frames; ++f)
-        if ((size_t)n_pts[f] > cloud_cap(c)) return BEV_ERR_TOO_LARGE;
-    if (n_frames == 0) return BEV_OK;
-    int rc = begin_call(c, true);
-    if (rc != BEV_OK) return rc;
-    const size_t per_frame = (size_t)std::max(1, n_poses) * M * M;
-    rc = c->manip_grids.grow(c, (size_t)std::min(n_frames, c->max_batch) * per_frame * sizeof(float));
-    if (rc != BEV_OK) return rc;
-    float *grids = static_cast<float *>(c->manip_grids.p);
-    return packed_host_chunks(c, n_frames, clouds, n_pts, [&](int f0, int nb, const uint64_t *off) -> int {
-        const int rc_ = float_bev_frames(c, nb, c->st_in, off, interval, M, skip_label0 != 0, n_poses,
-                                         n_poses ? h_poses + (size_t)f0 * n_poses * 12 : nullptr, grids);
-        if (rc_ != BEV_OK) return rc_;
-        for (int f = 0; f < nb; ++f)
-            HIPCK(c, hipMemcpyAsync(out[f0 + f], grids + (size_t)f * per_frame, per_frame * sizeof(float), hipMemcpyDeviceToHost,
-                                    c->stream));
-        return BEV_OK;
-    });
-}
-
-int bev_posed_bev_device_resident(bev_ctx_t *c, int n_frames, const bev_point_t *d_clouds, const uint64_t *h_offsets,
-                                  int n_poses, const float *h_poses, uint8_t *d_multi, uint8_t *d_single)
-{
-    if (!poses_ok(n_poses, h_poses, BEV_POSED_BEV_MAX_POSES)) return BEV_ERR_INVALID_ARG;
-    const int rc = check_packed_frames(c, n_frames, h_offsets);
-    if (rc != BEV_OK) return rc;
-    if (n_frames == 0) return BEV_OK;
-    if ((!d_multi && !d_single) || (!d_clouds && h_offsets[n_frames] != h_offsets[0])) return BEV_ERR_INVALID_ARG;
-    return resident_call(c, [&] { return posed_bev_frames(c, n_frames, d_clouds, h_offsets, n_poses, h_poses, d_multi, d_single); });
-}
-
-int bev_posed_bev_batch(bev_ctx_t *c, int n_frames, const bev_point_t *const *clouds, const uint32_t *n_pts, int n_poses,
-                        const float *h_poses, uint8_t *const *multi_out, uint8_t *const *single_out)
-{
-    if (!c || n_frames < 0 || !host_clouds_ok(n_frames, clouds, n_pts) || (n_frames > 0 && !multi_out && !single_out) ||
-        !poses_ok(n_poses, h_poses, BEV_POSED_BEV_MAX_POSES))
-        return BEV_ERR_INVALID_ARG;
-    for (int f = 0; f < n_frames; ++f)
-        if ((multi_out && !multi_out[f]) || (single_out && !single_out[f])) return BEV_ERR_INVALID_ARG;
-    for (int f = 0; f < n_frames; ++f)
-        if ((size_t)n_pts[f] > cloud_cap(c)) return BEV_ERR_TOO_LARGE;
-    if (n_frames == 0) return BEV_OK;
-    int rc = begin_call(c, true);
-    if (rc != BEV_OK) return rc;
-    const size_t K = (size_t)std::max(1, n_poses), multi_frame = multi_out ? K * c->multi_bytes : 0,
-                 single_frame = single_out ? K * c->single_bytes : 0, nb_max = (size_t)std::min(n_frames, c->max_batch);
-    rc = c->posed_imgs.grow(c, nb_max * (multi_frame + single_frame));
-    if (rc != BEV_OK) return rc;
-    uint8_t *d_multi = multi_out ? static_cast<uint8_t *>(c->posed_imgs.p) : nullptr;
-    uint8_t *d_single = single_out ? static_cast<uint8_t *>(c->posed_imgs.p) + nb_max * multi_frame : nullptr;
-    return packed_host_chunks(c, n_frames, clouds, n_pts, [&](int f0, int nb, const uint64_t *off) -> int {
-        const int rc_ = posed_bev_frames(c, nb, c->st_in, off, n_poses, n_poses ? h_poses + (size_t)f0 * n_poses * 12 : nullptr,
-                                         d_multi, d_single);
-        if (rc_ != BEV_OK) return rc_;
-        for (int f = 0; f < nb; ++f) {
-            if (multi_out)
-                HIPCK(c, hipMemcpyAsync(multi_out[f0 + f], d_multi + (size_t)f * multi_frame, multi_frame, hipMemcpyDeviceToHost,
-                                        c->stream));
-            if (single_out)
-                HIPCK(c, hipMemcpyAsync(single_out[f0 + f], d_single + (size_t)f * single_frame, single_frame,
-                                        hipMemcpyDeviceToHost, c->stream));
-        }
-        return BEV_OK;
-    });
-}
-
-int bev_submap_bev_device_resident(bev_ctx_t *c, int n_frames, const bev_point_t *d_clouds, const uint64_t *h_offsets, int n_maps,
-                                   const uint64_t *h_map_offsets, const int32_t *h_entry_frame, const float *h_entry_pose,
-                                   uint8_t *d_multi, uint8_t *d_single)
-{
-    const int rc = check_packed_frames(c, n_frames, h_offsets);
-    if (rc == BEV_ERR_INVALID_ARG) return rc;
-    const int rc_maps = check_submap_entries(n_frames, n_maps, h_map_offsets, h_entry_frame, h_entry_pose);
-    if (rc_maps != BEV_OK) return rc_maps;
-    if (rc != BEV_OK) return rc; /* (a frame that is too large: behind the arguments that are wrong) */
-    if (n_maps == 0) return BEV_OK;
-    if (!d_multi && !d_single) return BEV_ERR_INVALID_ARG;
-    for (uint64_t e = h_map_offsets[0]; e < h_map_offsets[n_maps] && !d_clouds; ++e)
-        if (h_offsets[h_entry_frame[e] + 1] != h_offsets[h_entry_frame[e]]) return BEV_ERR_INVALID_ARG; /* records to read */
-    return resident_call(c, [&] {
-        return submap_bev_frames(c, d_clouds, h_offsets, n_maps, h_map_offsets, h_entry_frame, h_entry_pose, d_multi, d_single);
-    });
-}
-
-/* Maps in chunks of one launch group of at most max_batch maps; the distinct frames a chunk names go through the input
- * staging max_batch at a time, each such piece splatted into the chunk's planes before the next piece goes up. */
-int bev_submap_bev_batch(bev_ctx_t *c, int n_frames, const bev_point_t *const *clouds, const uint32_t *n_pts, int n_maps,
-                         const uint64_t *h_map_offsets, const int32_t *h_entry_frame, const float *h_entry_pose,
-                         uint8_t *const *multi_out, uint8_t *const *single_out)
-{
-    if (!c || n_frames < 0 || !host_clouds_ok(n_frames, clouds, n_pts)) return BEV_ERR_INVALID_ARG;
-    int rc = check_submap_entries(n_frames, n_maps, h_map_offsets, h_entry_frame, h_entry_pose);
-    if (rc != BEV_OK) return rc;
-    if (n_maps > 0 && !multi_out && !single_out) return BEV_ERR_INVALID_ARG;
-    for (int g = 0; g < n_maps; ++g)
-        if ((multi_out && !multi_out[g]) || (single_out && !single_out[g])) return BEV_ERR_INVALID_ARG;
-    for (int f = 0; f < n_frames; ++f)
-        if ((size_t)n_pts[f] > cloud_cap(c)) return BEV_ERR_TOO_LARGE;
-    if (n_maps == 0) return BEV_OK;
-    rc = begin_call(c, true);
-    if (rc != BEV_OK) return rc;
-    const int chunk = (int)std::min<size_t>((size_t)std::min(n_maps, c->max_batch), posed_cap_grids(c));
-    const size_t multi_map = multi_out ? c->multi_bytes : 0, single_map = single_out ? c->single_bytes : 0;
-    rc = c->posed_imgs.grow(c, (size_t)chunk * (multi_map + single_map));
-    if (rc != BEV_OK) return rc;
-    uint8_t *d_multi = multi_out ? static_cast<uint8_t *>(c->posed_imgs.p) : nullptr;
-    uint8_t *d_single = single_out ? static_cast<uint8_t *>(c->posed_imgs.p) + (size_t)chunk * multi_map : nullptr;
-    const auto chunks = [&]() -> int {
-        std::vector<uint64_t> offs((size_t)n_frames + 1, 0); /* (only the counts matter: a row's offset is set per piece) */
-        for (int f = 0; f < n_frames; ++f) offs[f + 1] = offs[f] + n_pts[f];
-        for (int m0 = 0; m0 < n_maps; m0 += chunk) {
-            const int nm = std::min(chunk, n_maps - m0);
-            SubmapPlanUp u;
-            if (!bevsub::plan_maps(u.plan, offs.data(), h_map_offsets, m0, m0 + nm, h_entry_frame, h_entry_pose, (size_t)nm))
-                return BEV_ERR_TOO_LARGE;
-            const bevsub::Group &g = u.plan.groups[0];
-            bevsub::Frame *rows = u.plan.rows.data() + g.row0;
-            for (int r = 0; r < g.n_rows; ++r) /* where the row's frame will lie in the staging while its piece is there */
-                rows[r].off = r % c->max_batch ? rows[r - 1].off + rows[r - 1].n : 0;
-            int rc_ = submap_plan_up(c, u);
-            if (rc_ == BEV_OK) rc_ = submap_clear(c, u, 0);
-            if (rc_ != BEV_OK) return rc_;
-            for (int r0 = 0; r0 < g.n_rows; r0 += c->max_batch) {
-                const int nr = std::min(c->max_batch, g.n_rows - r0);
-                for (int r = r0; r < r0 + nr; ++r)
-                    if (rows[r].n)
-                        HIPCK(c, hipMemcpyAsync(c->st_in + rows[r].off, clouds[u.plan.frame[g.row0 + r]],
-                                                (size_t)rows[r].n * sizeof(bev_point_t), hipMemcpyHostToDevice, c->stream));
-                submap_splat(c, u, 0, c->st_in, r0, nr);
-            }
-            submap_expand(c, u, 0, d_multi, d_single);
-            HIPCK(c, hipGetLastError());
-            for (int m = 0; m < nm; ++m) {
-                if (multi_out)
-                    HIPCK(c, hipMemcpyAsync(multi_out[m0 + m], d_multi + (size_t)m * multi_map, multi_map, hipMemcpyDeviceToHost,
-                                            c->stream));
-                if (single_out)
-                    HIPCK(c, hipMemcpyAsync(single_out[m0 + m], d_single + (size_t)m * single_map, single_map,
-                                            hipMemcpyDeviceToHost, c->stream));
-            }
-        }
-        HIPCK(c, hipStreamSynchronize(c->stream));
-        return BEV_OK;
-    };
-    rc = chunks();
-    if (rc != BEV_OK) (void)hipDeviceSynchronize();
-    return rc;
 }
 
 int bev_transform_cloud(bev_ctx_t *c, const bev_point_t *cloud, uint32_t n, const float *m, bev_point_t *out)

@@ -16,60 +16,7 @@
 using namespace bevk;
 using namespace bevh;
 
-/* ---- what the entry points keep between calls (RegState, bev_ctx.h) --------------------------------------------------- */
-int DevBuf::grow(bev_ctx *c, size_t need)
-{
-    if (need <= cap) return BEV_OK;
-    /* the last call's kernels may still use the buffer: this wait is what makes reuse safe across unsynchronised calls */
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    if (p) HIPCK(c, hipFree(p));
-    p = nullptr;
-    cap = 0;
-    HIPCK(c, hipMalloc(&p, need));
-    cap = need;
-    return BEV_OK;
-}
-void DevBuf::release()
-{
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-}
-
-int UploadTable::begin(bev_ctx *c, size_t bytes, size_t min_cap, void **host_out)
-{
-    if (!ev) HIPCK(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    else HIPCK(c, hipEventSynchronize(ev)); /* the last call's table has gone up */
-    if (bytes > cap) {
-        HIPCK(c, hipStreamSynchronize(c->stream)); /* (kernels of the last call may still read the device block) */
-        if (host) HIPCK(c, hipHostFree(host));
-        if (dev) HIPCK(c, hipFree(dev));
-        host = dev = nullptr;
-        cap = 0;
-        const size_t n = std::max(bytes, min_cap);
-        HIPCK(c, hipHostMalloc(&host, n, hipHostMallocDefault));
-        HIPCK(c, hipMalloc(&dev, n));
-        cap = n;
-    }
-    *host_out = host;
-    return BEV_OK;
-}
-int UploadTable::push(bev_ctx *c, size_t bytes)
-{
-    if (bytes) HIPCK(c, hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, c->stream));
-    HIPCK(c, hipEventRecord(ev, c->stream));
-    return BEV_OK;
-}
-void UploadTable::release()
-{
-    if (host) (void)hipHostFree(host);
-    if (dev) (void)hipFree(dev);
-    if (ev) (void)hipEventDestroy(ev);
-    host = dev = nullptr;
-    ev = nullptr;
-    cap = 0;
-}
-
+/* ---- what the entry points keep between calls (RegState, bev_ctx.h; DevBuf and UploadTable themselves: bev_capi.hip) ---- */
 void RegState::release()
 {
     for (DevBuf *b : {&rf_buf, &icp_buf, &icp_one, &fine_buf, &fine_in}) b->release();
@@ -77,22 +24,6 @@ void RegState::release()
     if (tail_ev) (void)hipEventDestroy(tail_ev);
     tail_ev = nullptr;
     tail_pending = false;
-}
-
-int bevh::wait_default_stream(bev_ctx *c)
-{
-    HIPCK(c, hipEventRecord(c->null_ev, nullptr));
-    HIPCK(c, hipStreamWaitEvent(c->stream, c->null_ev, 0));
-    return BEV_OK;
-}
-
-int bevh::record_tail(bev_ctx *c)
-{
-    RegState &r = c->reg;
-    if (!r.tail_ev) HIPCK(c, hipEventCreateWithFlags(&r.tail_ev, hipEventDisableTiming));
-    HIPCK(c, hipEventRecord(r.tail_ev, c->stream));
-    r.tail_pending = true;
-    return BEV_OK;
 }
 
 namespace {

@@ -1,8 +1,8 @@
 /*
- * bev_ctx.h — the context behind bev_ctx_t and what the two files of the C ABI share: bev_capi.hip (the context, the BEV
- * pipeline and the single-cloud entry points) and bev_capi_reg.hip (the registration entry points) — among it the prologue
- * of every call outside the fused pipeline (begin_call) and the bound on a cloud's points (cloud_cap).  Private, like
- * bev_internal.h.  The types live in a named namespace: struct bev_ctx is one type in both translation units.
+ * bev_ctx.h — the context behind bev_ctx_t and what the three files of the C ABI share: bev_capi.hip (the context, the BEV
+ * pipeline and the single-cloud entry points), bev_capi_packed.hip (the batched calls over packed frames), bev_capi_reg.hip
+ * (the registration entry points) — among it the prologue of every call outside the fused pipeline (begin_call) and the bound
+ * on a cloud's points (cloud_cap).  Private, like bev_internal.h.  Named namespace: struct bev_ctx is one type in all of them.
  */
 #ifndef BEV_CTX_H
 #define BEV_CTX_H
@@ -112,7 +112,7 @@ struct Downloader {
     }
 };
 
-/* ---- what the registration entry points keep between calls (bev_capi_reg.hip) ---- */
+/* ---- what the batched entry points keep between calls (defined in bev_capi.hip; used by all three files) ---- */
 /* a device buffer that grows when a call needs more */
 struct DevBuf {
     void *p = nullptr;
@@ -221,22 +221,22 @@ struct bev_ctx {
     hipStream_t dl_stream = nullptr;             /* device -> host copies of bev_process_batch (own host thread) */
     bevh::Downloader *downloader = nullptr;            /* that thread, started with the staging buffers */
     hipEvent_t out_ready[2] = {nullptr, nullptr}; /* per half of the output staging: its chunk has been computed */
-    /* projection of raw returns (project_frames, bev_capi.hip): the frame table of a call; the KITTI workspace of one launch
+    /* projection of raw returns (project_frames, bev_capi_packed.hip): the frame table of a call; the KITTI workspace of one launch
      * group, allocated on first use and grown on demand; the raw staging of bev_process_batch_xyzi (lazily allocated) */
     bevh::UploadTable proj_tab;
     bevh::DevBuf kitti_ws;
     int kitti_group = bevk::kKittiGroup; /* BEV_PROJECT_GROUP=1 .. 64 (tests: results do not depend on it) */
     float *st_raw = nullptr;
-    /* float BEV of a batch (float_bev_frames, bev_capi.hip): the frame and pose table of a call; the grids of
+    /* float BEV of a batch (float_bev_frames, bev_capi_packed.hip): the frame and pose table of a call; the grids of
      * bev_float_bev_batch's chunks, allocated on first use and grown on demand */
     bevh::UploadTable manip_tab;
     bevh::DevBuf manip_grids;
-    /* 24-layer and uint8 BEVs of a batch under per-frame poses (posed_bev_frames, bev_capi.hip): the frame and pose table of
+    /* 24-layer and uint8 BEVs of a batch under per-frame poses (posed_bev_frames, bev_capi_packed.hip): the frame and pose table of
      * a call; the planes of one launch group; the images of bev_posed_bev_batch's chunks; all allocated on first use and
      * grown on demand */
     bevh::UploadTable posed_tab;
     bevh::DevBuf posed_ws, posed_imgs;
-    /* ... of submaps (submap_plan_up & co., bev_capi.hip): the plan of a call; the planes are posed_ws, the images of
+    /* ... of submaps (submap_plan_up & co., bev_capi_packed.hip): the plan of a call; the planes are posed_ws, the images of
      * bev_submap_bev_batch's chunks posed_imgs (both host-buffer calls are synchronous) */
     bevh::UploadTable submap_tab;
     int posed_group = 0; /* BEV_POSED_GROUP=1 .. 65535: grids per launch group (tests: results do not depend on it); 0: what fits kPosedWsCap */
@@ -291,6 +291,12 @@ int wait_default_stream(bev_ctx *c);
  * wait for it (run_pipeline) */
 int record_tail(bev_ctx *c);
 int ensure_staging(bev_ctx *c);
+/* of the packed-frame calls (bev_capi_packed.hip), for bev_process_batch_xyzi as well: a BEV_PROJECT_* value; the projection */
+inline bool project_kind_ok(int kind)
+{
+    return kind == BEV_PROJECT_MULRAN_OS1_64 || kind == BEV_PROJECT_OXFORD_HDL_32E || kind == BEV_PROJECT_KITTI_HDL_64E;
+}
+int project_frames(bev_ctx *c, int kind, int nf, const float *d_xyzi, const uint64_t *offs, bev_point_t *d_out);
 
 inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 /* one allocation in 256-byte aligned pieces: *dst[i] = the piece of sz[i] bytes (base == nullptr: nothing is written);

@@ -9,49 +9,13 @@ import torch
 
 import bev_amd
 import oracle_lib as orc
+import packed_cases
 from bev_amd import FLOAT_BEV_MAX_POSES, POINT_DTYPE, synth
+from packed_cases import (FAR, GUARD, INVALID, PATTERN, POSES, TOO_LARGE, UNSUPPORTED, _adversarial, _dev, _marked, _matrix,
+                          _one_cell, _p, _pack)
 
 pytestmark = pytest.mark.gpu
-GUARD = 1 << 16       # bytes behind d_out
-PATTERN = 0xA5
-# test_transform_cloud's poses (tx, ty, tz, yaw), and one that pushes most points off the grid
-POSES = [(0, 0, 0, 0), (1.5, -2.25, 0.125, 30), (-3, 4, 1, -45.5), (10, 20, -1, 180), (0.1, 0.2, 0.3, 359.9)]
-FAR = (150, 0, 0, 10)
-INVALID, UNSUPPORTED, TOO_LARGE = -1, -5, -6
-
-
-@functools.lru_cache(maxsize=None)
-def _p():
-    return bev_amd.params_for_sensor("HDL_64E")
-
-
-@functools.lru_cache(maxsize=None)
-def _marked(frame_id=21):
-    """a full HDL_64E sweep, ordered and ground-marked: S records, labels 0 among them"""
-    sp = orc.sensor_from_params(_p())
-    cloud = orc.mark_ground(sp, orc.order_cloud(sp, synth.sweep(_p(), frame_id)))[0]
-    assert (cloud["label"] == 0).any() and (cloud["label"] != 0).any()
-    cloud.setflags(write=False)
-    return cloud
-
-
-@functools.lru_cache(maxsize=None)
-def _adversarial(n=60000, seed=3):
-    cloud = synth.adversarial(_p(), n, seed, nonfinite=True)
-    assert (cloud["label"] == 0).any()
-    cloud.setflags(write=False)
-    return cloud
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a).reshape(-1).view(np.uint8).copy()).to(torch.device("cuda:0"))
-
-
-def _pack(frames):
-    offs = np.zeros(len(frames) + 1, dtype=np.uint64)
-    offs[1:] = np.cumsum([len(f) for f in frames])
-    flat = np.concatenate([np.ascontiguousarray(f, dtype=POINT_DTYPE) for f in frames] + [np.zeros(1, POINT_DTYPE)])
-    return offs, flat
+_ragged_frames = functools.partial(packed_cases._ragged_frames, 9, 24, (0,))
 
 
 def _out(n_grids, M):
@@ -66,25 +30,8 @@ def _guard_ok(t, n_grids, M):
     return bool((t[n_grids * M * M * 4:] == PATTERN).all())
 
 
-def _matrix(pose):
-    return orc.yaw_translate_matrix(*[float(v) for v in pose])
-
-
 def _want(cloud, interval, skip, m=None):
     return orc.float_bev(cloud if m is None else orc.transform_cloud(cloud, m), interval, skip)
-
-
-def _ragged_frames():
-    adv, marked = _adversarial(), _marked()
-    small = [0, 0, 1, 2, 255, 256, 257, 1023, 1024, 1025, 4097, 0]
-    frames = [adv[41 * i:41 * i + n] for i, n in enumerate(small)]
-    rng = np.random.default_rng(11)
-    for i, n in enumerate(rng.integers(3000, 40001, 9)):
-        src = adv if i % 2 else marked
-        frames.append(src[1000 * i:1000 * i + int(n)])
-    frames += [marked, adv[:0], adv[:0]]
-    assert len(frames) == 24
-    return frames
 
 
 @pytest.mark.parametrize("interval,skip", [(1.0, 1), (2.0, 0), (0.5, 1)])
@@ -110,12 +57,6 @@ def test_one_call_rasters_ragged_frames_bit_identically(interval, skip):
         assert _guard_ok(d_out, nf, M), "something was written behind d_out"
     finally:
         ctx.close()
-
-
-def _one_cell(zs, label=1):
-    cloud = np.zeros(len(zs), dtype=POINT_DTYPE)
-    cloud["x"], cloud["y"], cloud["z"], cloud["label"] = 0.3, -7.2, zs, label
-    return cloud
 
 
 def test_contention_and_the_zero_threshold():

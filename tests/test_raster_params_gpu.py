@@ -16,21 +16,11 @@ import bev_amd
 import oracle_lib as orc
 import raster_cases as rc
 from bev_amd import POINT_DTYPE, synth
+from packed_cases import _dev, _pack
 
 pytestmark = pytest.mark.gpu
 GENERAL, STREAM, REDO, STRUCTURED, COLMAJOR, COLMAJOR_GEN = 0, 1, 2, 3, 4, 5
 GUARD, PATTERN = 1 << 12, 0xA5
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a).reshape(-1).view(np.uint8).copy()).to(torch.device("cuda:0"))
-
-
-def _pack(frames):
-    offs = np.zeros(len(frames) + 1, dtype=np.uint64)
-    offs[1:] = np.cumsum([len(f) for f in frames])
-    flat = np.concatenate([np.ascontiguousarray(f, dtype=POINT_DTYPE) for f in frames] + [np.zeros(1, POINT_DTYPE)])
-    return offs, flat
 
 
 def _want(p, frames):

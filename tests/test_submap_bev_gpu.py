@@ -11,53 +11,13 @@ import torch
 
 import bev_amd
 import oracle_lib as orc
+import packed_cases
 from bev_amd import POINT_DTYPE, SUBMAP_MAX_ENTRIES, synth
+from packed_cases import (FAR, INVALID, PATTERN, POSES, TOO_LARGE, _adversarial, _dev, _marked, _matrix, _one_cell, _Out, _p,
+                          _pack)
 
 pytestmark = pytest.mark.gpu
-GUARD = 1 << 16       # bytes behind each output
-PATTERN = 0xA5
-POSES = [(0, 0, 0, 0), (1.5, -2.25, 0.125, 30), (-3, 4, 1, -45.5), (10, 20, -1, 180), (0.1, 0.2, 0.3, 359.9)]
-FAR = (150, 0, 0, 10)
-INVALID, TOO_LARGE = -1, -6
-
-
-@functools.lru_cache(maxsize=None)
-def _p(sensor="HDL_64E"):
-    return bev_amd.params_for_sensor(sensor)
-
-
-@functools.lru_cache(maxsize=None)
-def _marked(frame_id=21, sensor="HDL_64E"):
-    """a full sweep, ordered and ground-marked: S records, labels 0 among them"""
-    sp = orc.sensor_from_params(_p(sensor))
-    cloud = orc.mark_ground(sp, orc.order_cloud(sp, synth.sweep(_p(sensor), frame_id)))[0]
-    assert (cloud["label"] == 0).any() and (cloud["label"] != 0).any()
-    cloud.setflags(write=False)
-    return cloud
-
-
-@functools.lru_cache(maxsize=None)
-def _adversarial(n=60000, seed=3):
-    cloud = synth.adversarial(_p(), n, seed, nonfinite=True)
-    assert (cloud["label"] == 0).any() and not np.isfinite(cloud["z"]).all()
-    cloud.setflags(write=False)
-    return cloud
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a).reshape(-1).view(np.uint8).copy()).to(torch.device("cuda:0"))
-
-
-def _pack(frames):
-    offs = np.zeros(len(frames) + 1, dtype=np.uint64)
-    offs[1:] = np.cumsum([len(f) for f in frames])
-    flat = np.concatenate([np.ascontiguousarray(f, dtype=POINT_DTYPE) for f in frames] + [np.zeros(1, POINT_DTYPE)])
-    return offs, flat
-
-
-def _matrix(pose):
-    return orc.yaw_translate_matrix(*[float(v) for v in pose])
-
+_ragged_frames = functools.partial(packed_cases._ragged_frames, 4, 18)
 
 IDENTITY = np.eye(3, 4, dtype=np.float32).reshape(12)
 
@@ -78,32 +38,6 @@ def _want(p, frames, entries):
     return orc.multi_bev(orc.sensor_from_params(p), cloud, p.interval), orc.single_bev(cloud, p.interval)
 
 
-class _Out:
-    """both outputs of a device call with guard bytes behind them"""
-
-    def __init__(self, p, n_grids, multi=True, single=True):
-        dev = torch.device("cuda:0")
-        self.n, self.L, self.M = n_grids, p.n_layers, p.mat_size
-        self.mb, self.sb = n_grids * self.L * self.M ** 2, n_grids * self.M ** 2
-        self.multi = torch.full((self.mb + GUARD,), PATTERN, dtype=torch.uint8, device=dev) if multi else None
-        self.single = torch.full((self.sb + GUARD,), PATTERN, dtype=torch.uint8, device=dev) if single else None
-
-    def ptrs(self):
-        return (self.multi.data_ptr() if self.multi is not None else None,
-                self.single.data_ptr() if self.single is not None else None)
-
-    def images(self):
-        m = self.multi[:self.mb].cpu().numpy().reshape(self.n, self.L, self.M, self.M) if self.multi is not None else None
-        s = self.single[:self.sb].cpu().numpy().reshape(self.n, self.M, self.M) if self.single is not None else None
-        return m, s
-
-    def guards_ok(self):
-        return all(bool((t[b:] == PATTERN).all()) for t, b in ((self.multi, self.mb), (self.single, self.sb)) if t is not None)
-
-    def untouched(self):
-        return all(bool((t == PATTERN).all()) for t in (self.multi, self.single) if t is not None)
-
-
 def _call(ctx, frames, maps, multi=True, single=True):
     """one bev_submap_bev_device_resident call; returns the images (maps, ...) after the guards were checked"""
     offs, flat = _pack(frames)
@@ -122,19 +56,6 @@ def _check(p, frames, maps, got_multi, got_single, want=None):
             assert got_multi[g].tobytes() == wm.tobytes(), (g, len(entries))
         if got_single is not None:
             assert got_single[g].tobytes() == ws.tobytes(), (g, len(entries))
-
-
-def _ragged_frames():
-    adv, marked = _adversarial(), _marked()
-    small = [0, 0, 1, 2, 255, 256, 257, 1023, 1024, 1025, 4097]
-    frames = [adv[41 * i:41 * i + n] for i, n in enumerate(small)]
-    rng = np.random.default_rng(11)
-    for i, n in enumerate(rng.integers(3000, 40001, 4)):
-        src = adv if i % 2 else marked
-        frames.append(src[1000 * i:1000 * i + int(n)])
-    frames += [marked, adv[:0], adv[:0]]
-    assert len(frames) == 18 and len(marked) == 133312
-    return frames
 
 
 def test_maps_over_ragged_frames():
@@ -241,12 +162,6 @@ def test_long_entry_lists():
         assert gs[0].any() and gs[149].any() and gs[150].any()
     finally:
         ctx.close()
-
-
-def _one_cell(zs, labels=1):
-    cloud = np.zeros(len(zs), dtype=POINT_DTYPE)
-    cloud["x"], cloud["y"], cloud["z"], cloud["label"] = 0.3, -7.2, zs, labels
-    return cloud
 
 
 def test_contention_across_frames_and_exclusions():
