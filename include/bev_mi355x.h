@@ -305,6 +305,42 @@ int bev_submap_bev_batch(bev_ctx_t *ctx, int n_frames, const bev_point_t *const 
                          int n_maps, const uint64_t *h_map_offsets, const int32_t *h_entry_frame,
                          const float *h_entry_pose, uint8_t *const *multi_out, uint8_t *const *single_out);
 
+/* The float max-height BEV (bev_float_bev, the "saveAsMat" grid) of SUBMAPS: map g is a list of (frame, pose) entries as for
+ * bev_submap_bev_device_resident, and its grid is that of all its entries' moved clouds together — bev_float_bev of the
+ * concatenation of bev_transform_cloud(frame, pose) over the map's entries, bit for bit (a maximum has no rounding and no
+ * order).  Asynchronous like bev_float_bev_device_resident; ONE launch for the whole call.
+ * d_clouds, h_map_offsets, h_entry_frame, h_entry_pose : exactly as for bev_submap_bev_device_resident: every entry has a
+ *                 matrix; a frame may feed any number of maps, appear several times in one map, or be named by none (it then
+ *                 costs no workgroup); the call's total of entries is bounded by BEV_SUBMAP_MAX_ENTRIES.
+ * interval, skip_label0 : as for bev_float_bev.
+ * d_out         : n_maps grids of M * M floats, M = bev_float_bev_size(interval), row index = x; map g's grid is grid g.  The
+ *                 call zeroes every grid itself (a map without entries gives an all-zero grid) and accumulates in place:
+ *                 every float of every grid is written, nothing else is.  The host arrays may be reused as soon as the call
+ *                 returns.
+ * Ordering      : as for bev_float_bev_device_resident: a BEV call of this context issued before it is finished first; work
+ *                 queued on the DEFAULT stream before the call is waited for on the device; a BEV call issued right after it
+ *                 waits for it.  bev_synchronize() before the host reads d_out.
+ * Status        : the submap statuses: BEV_ERR_INVALID_ARG for a NULL context, n_frames < 0, n_maps < 0, NULL or decreasing
+ *                 h_offsets or h_map_offsets, entries with a NULL entry array, an entry frame outside 0 .. n_frames - 1;
+ *                 BEV_ERR_TOO_LARGE for more than BEV_SUBMAP_MAX_ENTRIES entries (checked before the entry arrays are read);
+ *                 then BEV_ERR_UNSUPPORTED when bev_float_bev_size(interval) == 0; then BEV_ERR_TOO_LARGE for a frame of more
+ *                 than max(max_points, S) records; then BEV_ERR_INVALID_ARG for NULL d_out while n_maps > 0 and for NULL
+ *                 d_clouds while an entry names a frame that has records.  Nothing is launched and d_out is untouched in
+ *                 every case.  n_maps == 0 returns BEV_OK.
+ * Workspace     : no planes (the output is the accumulator): a table of 20 bytes per distinct named frame and 64 bytes per
+ *                 entry, shared with bev_submap_bev_device_resident.  Freed by bev_destroy. */
+int bev_submap_float_bev_device_resident(bev_ctx_t *ctx, int n_frames, const bev_point_t *d_clouds, const uint64_t *h_offsets,
+                                         float interval, int skip_label0, int n_maps, const uint64_t *h_map_offsets,
+                                         const int32_t *h_entry_frame, const float *h_entry_pose, float *d_out);
+/* The same through HOST buffers, synchronous and argument-checked like bev_submap_bev_batch: clouds[f] holds n_pts[f] records
+ * (at most max(max_points, S)); out[g] receives map g's M * M floats (NULL out while n_maps > 0, or a NULL out[g]:
+ * BEV_ERR_INVALID_ARG).  The maps go in chunks of at most max_batch maps; the distinct frames a chunk names go up through the
+ * context's input staging max_batch at a time, each such piece rastered into the chunk's grids before the next goes up, so a
+ * map may name more distinct frames than max_batch.  The chunk's grids live in the device buffer of bev_float_bev_batch. */
+int bev_submap_float_bev_batch(bev_ctx_t *ctx, int n_frames, const bev_point_t *const *clouds, const uint32_t *n_pts,
+                               float interval, int skip_label0, int n_maps, const uint64_t *h_map_offsets,
+                               const int32_t *h_entry_frame, const float *h_entry_pose, float *const *out);
+
 /* Range-image projection of raw XYZI returns — the selectors' row / col assignment ("polar binning"):
  *   BEV_PROJECT_MULRAN_OS1_64   extractPointCloud, MulranPointCloudSelect.cpp:112-130:
  *                               xyzi = n * (x, y, z, intensity); row = k % 64, col from the azimuth (0..1024)

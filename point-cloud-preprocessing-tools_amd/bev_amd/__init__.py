@@ -92,6 +92,7 @@ ABI_SYMBOLS = [
     "bev_float_bev_device_resident", "bev_float_bev_batch",
     "bev_posed_bev_device_resident", "bev_posed_bev_batch",
     "bev_submap_bev_device_resident", "bev_submap_bev_batch",
+    "bev_submap_float_bev_device_resident", "bev_submap_float_bev_batch",
 ]
 
 # registration front end (include/bev_mi355x.h): pcl::PointXYZ, pcl::Normal, pcl::PointNormal as float rows
@@ -221,6 +222,11 @@ def load_lib() -> C.CDLL:
         lib.bev_submap_bev_device_resident.argtypes = [vp, i32, vp, C.POINTER(C.c_uint64), i32, C.POINTER(C.c_uint64), vp, vp, vp, vp]
         lib.bev_submap_bev_batch.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(u32), i32, C.POINTER(C.c_uint64), vp, vp,
                                              C.POINTER(vp), C.POINTER(vp)]
+    if hasattr(lib, "bev_submap_float_bev_device_resident"):
+        lib.bev_submap_float_bev_device_resident.argtypes = [vp, i32, vp, C.POINTER(C.c_uint64), C.c_float, i32, i32,
+                                                             C.POINTER(C.c_uint64), vp, vp, vp]
+        lib.bev_submap_float_bev_batch.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(u32), C.c_float, i32, i32,
+                                                   C.POINTER(C.c_uint64), vp, vp, C.POINTER(vp)]
     _lib = lib
     return lib
 
@@ -459,6 +465,31 @@ class BevContext:
                                            _ptr(entry_pose), _rows(multi), _rows(single))
         self._check(rc, "bev_submap_bev_batch")
         return multi, single
+
+    def submap_float_bev_device(self, n_frames, d_clouds, offsets, map_offsets, entry_frame, entry_pose, d_out, interval=1.0,
+                                skip_label0=True):
+        """bev_submap_float_bev_device_resident on device pointers: frames, maps and entries as for submap_bev_device; d_out
+        receives one grid of M * M floats per map: the float BEV of all its entries' moved clouds together.  Asynchronous:
+        synchronize() before the host reads d_out."""
+        offsets, offs = _offsets(offsets, n_frames)
+        n_maps, map_offsets, entry_frame, entry_pose = self._submap_entries(map_offsets, entry_frame, entry_pose)
+        rc = self.lib.bev_submap_float_bev_device_resident(self._h, n_frames, C.c_void_p(d_clouds), offs, interval,
+                                                           1 if skip_label0 else 0, n_maps,
+                                                           map_offsets.ctypes.data_as(C.POINTER(C.c_uint64)), _ptr(entry_frame),
+                                                           _ptr(entry_pose), C.c_void_p(d_out or None))
+        self._check(rc, "bev_submap_float_bev_device_resident")
+
+    def submap_float_bev_batch(self, clouds, map_offsets, entry_frame, entry_pose, interval=1.0, skip_label0=True):
+        """bev_submap_float_bev_batch on host clouds; maps as for submap_bev_device; returns (n_maps, M, M) float32."""
+        clouds, pts, npts = _host_clouds(clouds)
+        n_maps, map_offsets, entry_frame, entry_pose = self._submap_entries(map_offsets, entry_frame, entry_pose)
+        M = int(self.lib.bev_float_bev_size(interval))
+        out = np.empty((n_maps, M, M), dtype=np.float32)
+        rc = self.lib.bev_submap_float_bev_batch(self._h, len(clouds), pts, npts, interval, 1 if skip_label0 else 0, n_maps,
+                                                 map_offsets.ctypes.data_as(C.POINTER(C.c_uint64)), _ptr(entry_frame),
+                                                 _ptr(entry_pose), _rows(out))
+        self._check(rc, "bev_submap_float_bev_batch")
+        return out
 
     def transform_cloud(self, cloud, m):
         cloud = np.ascontiguousarray(cloud, dtype=POINT_DTYPE)

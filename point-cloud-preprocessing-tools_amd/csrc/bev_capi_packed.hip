@@ -1,7 +1,7 @@
 /*
  * bev_capi_packed.hip — the batched calls over packed frames (several clouds one after the other in one buffer, described by
  * n_frames + 1 offsets) of the boundary declared extern "C" in include/bev_mi355x.h: projection of raw sweeps, float BEV,
- * posed BEVs, submap BEVs (DESIGN.md §6e – §6i).  Host-side only.  They share one path (§6h): the frame table
+ * posed BEVs, submap BEVs, float submap BEVs (DESIGN.md §6e – §6j).  Host-side only.  They share one path (§6h): the frame table
  * (upload_packed_table), the bracket of the device-resident calls (resident_call), the chunk loop of the host-buffer calls
  * (packed_host_chunks) and the planes of a launch group (plane_pair_bytes, expand_planes).
  */
@@ -214,24 +214,29 @@ struct SubmapPlanUp {
     const char *dev = nullptr;
     uint32_t *planes = nullptr;
 };
-int submap_plan_up(bev_ctx *c, SubmapPlanUp &u)
+/* the tables alone (the float call has no planes: its output is the accumulator) */
+int submap_tables_up(bev_ctx *c, SubmapPlanUp &u)
 {
-    int most = 0;
     size_t bytes = 0;
     for (const bevsub::Group &g : u.plan.groups) {
-        most = std::max(most, g.n_maps);
         u.at.push_back(bevsub::group_bytes(g, bytes));
         bytes = u.at.back().end;
     }
-    int rc = c->posed_ws.grow(c, (size_t)most * plane_pair_bytes(c)); /* (a grow waits for the stream: before the table goes up) */
-    if (rc != BEV_OK) return rc;
     char *h = nullptr;
-    rc = c->submap_tab.begin(c, bytes, 64 * 1024, reinterpret_cast<void **>(&h));
+    const int rc = c->submap_tab.begin(c, bytes, 64 * 1024, reinterpret_cast<void **>(&h));
     if (rc != BEV_OK) return rc;
     bevsub::pack(u.plan, h);
     u.dev = static_cast<const char *>(c->submap_tab.dev);
-    u.planes = static_cast<uint32_t *>(c->posed_ws.p);
     return c->submap_tab.push(c, bytes);
+}
+int submap_plan_up(bev_ctx *c, SubmapPlanUp &u)
+{
+    int most = 0;
+    for (const bevsub::Group &g : u.plan.groups) most = std::max(most, g.n_maps);
+    const int rc = c->posed_ws.grow(c, (size_t)most * plane_pair_bytes(c)); /* (a grow waits for the stream: before the table goes up) */
+    if (rc != BEV_OK) return rc;
+    u.planes = static_cast<uint32_t *>(c->posed_ws.p);
+    return submap_tables_up(c, u);
 }
 /* group gi of an uploaded plan on the context's stream: its rows [r0, r0 + nr) splatted from d_clouds (left out where they hold no point) */
 void submap_splat(bev_ctx *c, const SubmapPlanUp &u, size_t gi, const bev_point_t *d_clouds, int r0, int nr)
@@ -264,7 +269,40 @@ int submap_bev_frames(bev_ctx *c, const bev_point_t *d_clouds, const uint64_t *o
     return BEV_OK;
 }
 
-/* What both submap entry points check of the maps: BEV_OK, or what the entry point returns.  The entry arrays are read only
+/* ---- the float max-height BEV of submaps (bev_submap_float.h): ONE launch group, the output its accumulator ---- */
+struct FloatGrid {
+    float interval;
+    size_t M;
+    bool skip_label0;
+};
+/* the rows [r0, r0 + nr) of an uploaded plan's one group splatted from d_clouds into grids (left out where they hold no point) */
+void submap_float_splat(bev_ctx *c, const SubmapPlanUp &u, const bev_point_t *d_clouds, int r0, int nr, const FloatGrid &fg,
+                        float *grids)
+{
+    const bevsub::Frame *rows = u.plan.rows.data() + u.plan.groups[0].row0;
+    const uint32_t blocks = rows[r0 + nr].blk0 - rows[r0].blk0;
+    if (blocks == 0) return;
+    ProfScope ps(c, K_SUBMAP_FLOAT_SPLAT, nr);
+    launch_submap_float_splat(d_clouds, u.dev + u.at[0].rows + (size_t)r0 * sizeof(bevsub::Frame),
+                              reinterpret_cast<const uint32_t *>(u.dev + u.at[0].ent0) + r0, nr, blocks, u.dev + u.at[0].entries,
+                              fg.interval, (int)fg.M, fg.skip_label0, grids, c->stream);
+}
+/* The grids of n_maps > 0 maps over frames in device memory, on the context's stream (arguments checked by the caller): map g's
+ * grid at d_out + g * M * M, zeroed here */
+int submap_float_frames(bev_ctx *c, const bev_point_t *d_clouds, const uint64_t *offs, const FloatGrid &fg, int n_maps,
+                        const uint64_t *map_offs, const int32_t *entry_frame, const float *entry_pose, float *d_out)
+{
+    SubmapPlanUp u;
+    if (!bevsub::plan_maps(u.plan, offs, map_offs, 0, n_maps, entry_frame, entry_pose, (size_t)n_maps)) return BEV_ERR_TOO_LARGE;
+    const int rc = submap_tables_up(c, u);
+    if (rc != BEV_OK) return rc;
+    HIPCK(c, hipMemsetAsync(d_out, 0, (size_t)n_maps * fg.M * fg.M * sizeof(float), c->stream));
+    submap_float_splat(c, u, d_clouds, 0, u.plan.groups[0].n_rows, fg, d_out);
+    HIPCK(c, hipGetLastError());
+    return BEV_OK;
+}
+
+/* What the submap entry points check of the maps: BEV_OK, or what the entry point returns.  The entry arrays are read only
  * when their length has passed. */
 int check_submap_entries(int n_frames, int n_maps, const uint64_t *map_offs, const int32_t *entry_frame, const float *entry_pose)
 {
@@ -538,6 +576,85 @@ int bev_submap_bev_batch(bev_ctx_t *c, int n_frames, const bev_point_t *const *c
                     HIPCK(c, hipMemcpyAsync(single_out[m0 + m], d_single + (size_t)m * single_map, single_map,
                                             hipMemcpyDeviceToHost, c->stream));
             }
+        }
+        HIPCK(c, hipStreamSynchronize(c->stream));
+        return BEV_OK;
+    };
+    rc = chunks();
+    if (rc != BEV_OK) (void)hipDeviceSynchronize();
+    return rc;
+}
+
+int bev_submap_float_bev_device_resident(bev_ctx_t *c, int n_frames, const bev_point_t *d_clouds, const uint64_t *h_offsets,
+                                         float interval, int skip_label0, int n_maps, const uint64_t *h_map_offsets,
+                                         const int32_t *h_entry_frame, const float *h_entry_pose, float *d_out)
+{
+    const int rc = check_packed_frames(c, n_frames, h_offsets);
+    if (rc == BEV_ERR_INVALID_ARG) return rc;
+    const int rc_maps = check_submap_entries(n_frames, n_maps, h_map_offsets, h_entry_frame, h_entry_pose);
+    if (rc_maps != BEV_OK) return rc_maps;
+    const FloatGrid fg{interval, bev_float_bev_size(interval), skip_label0 != 0};
+    if (fg.M == 0) return BEV_ERR_UNSUPPORTED;
+    if (rc != BEV_OK) return rc; /* (a frame that is too large: behind the arguments that are wrong and the interval) */
+    if (n_maps == 0) return BEV_OK;
+    if (!d_out) return BEV_ERR_INVALID_ARG;
+    for (uint64_t e = h_map_offsets[0]; e < h_map_offsets[n_maps] && !d_clouds; ++e)
+        if (h_offsets[h_entry_frame[e] + 1] != h_offsets[h_entry_frame[e]]) return BEV_ERR_INVALID_ARG; /* records to read */
+    return resident_call(c, [&] {
+        return submap_float_frames(c, d_clouds, h_offsets, fg, n_maps, h_map_offsets, h_entry_frame, h_entry_pose, d_out);
+    });
+}
+
+/* bev_submap_bev_batch's chunks and pieces; the chunk's grids in the float-grid buffer of bev_float_bev_batch. */
+int bev_submap_float_bev_batch(bev_ctx_t *c, int n_frames, const bev_point_t *const *clouds, const uint32_t *n_pts, float interval,
+                               int skip_label0, int n_maps, const uint64_t *h_map_offsets, const int32_t *h_entry_frame,
+                               const float *h_entry_pose, float *const *out)
+{
+    if (!c || n_frames < 0 || !host_clouds_ok(n_frames, clouds, n_pts)) return BEV_ERR_INVALID_ARG;
+    int rc = check_submap_entries(n_frames, n_maps, h_map_offsets, h_entry_frame, h_entry_pose);
+    if (rc != BEV_OK) return rc;
+    if (n_maps > 0 && !out) return BEV_ERR_INVALID_ARG;
+    for (int g = 0; g < n_maps; ++g)
+        if (!out[g]) return BEV_ERR_INVALID_ARG;
+    const FloatGrid fg{interval, bev_float_bev_size(interval), skip_label0 != 0};
+    if (fg.M == 0) return BEV_ERR_UNSUPPORTED;
+    for (int f = 0; f < n_frames; ++f)
+        if ((size_t)n_pts[f] > cloud_cap(c)) return BEV_ERR_TOO_LARGE;
+    if (n_maps == 0) return BEV_OK;
+    rc = begin_call(c, true);
+    if (rc != BEV_OK) return rc;
+    const int chunk = std::min(n_maps, c->max_batch);
+    const size_t per_map = fg.M * fg.M;
+    rc = c->manip_grids.grow(c, (size_t)chunk * per_map * sizeof(float));
+    if (rc != BEV_OK) return rc;
+    float *grids = static_cast<float *>(c->manip_grids.p);
+    const auto chunks = [&]() -> int {
+        std::vector<uint64_t> offs((size_t)n_frames + 1, 0); /* (only the counts matter: a row's offset is set per piece) */
+        for (int f = 0; f < n_frames; ++f) offs[f + 1] = offs[f] + n_pts[f];
+        for (int m0 = 0; m0 < n_maps; m0 += chunk) {
+            const int nm = std::min(chunk, n_maps - m0);
+            SubmapPlanUp u;
+            if (!bevsub::plan_maps(u.plan, offs.data(), h_map_offsets, m0, m0 + nm, h_entry_frame, h_entry_pose, (size_t)nm))
+                return BEV_ERR_TOO_LARGE;
+            const bevsub::Group &g = u.plan.groups[0];
+            bevsub::Frame *rows = u.plan.rows.data() + g.row0;
+            for (int r = 0; r < g.n_rows; ++r) /* where the row's frame will lie in the staging while its piece is there */
+                rows[r].off = r % c->max_batch ? rows[r - 1].off + rows[r - 1].n : 0;
+            const int rc_ = submap_tables_up(c, u);
+            if (rc_ != BEV_OK) return rc_;
+            HIPCK(c, hipMemsetAsync(grids, 0, (size_t)nm * per_map * sizeof(float), c->stream));
+            for (int r0 = 0; r0 < g.n_rows; r0 += c->max_batch) {
+                const int nr = std::min(c->max_batch, g.n_rows - r0);
+                for (int r = r0; r < r0 + nr; ++r)
+                    if (rows[r].n)
+                        HIPCK(c, hipMemcpyAsync(c->st_in + rows[r].off, clouds[u.plan.frame[g.row0 + r]],
+                                                (size_t)rows[r].n * sizeof(bev_point_t), hipMemcpyHostToDevice, c->stream));
+                submap_float_splat(c, u, c->st_in, r0, nr, fg, grids);
+            }
+            HIPCK(c, hipGetLastError());
+            for (int m = 0; m < nm; ++m)
+                HIPCK(c, hipMemcpyAsync(out[m0 + m], grids + (size_t)m * per_map, per_map * sizeof(float), hipMemcpyDeviceToHost,
+                                        c->stream));
         }
         HIPCK(c, hipStreamSynchronize(c->stream));
         return BEV_OK;

@@ -228,7 +228,8 @@ struct bev_ctx {
     int kitti_group = bevk::kKittiGroup; /* BEV_PROJECT_GROUP=1 .. 64 (tests: results do not depend on it) */
     float *st_raw = nullptr;
     /* float BEV of a batch (float_bev_frames, bev_capi_packed.hip): the frame and pose table of a call; the grids of
-     * bev_float_bev_batch's chunks, allocated on first use and grown on demand */
+     * bev_float_bev_batch's chunks (and of bev_submap_float_bev_batch's: both calls are synchronous), allocated on first use and
+     * grown on demand */
     bevh::UploadTable manip_tab;
     bevh::DevBuf manip_grids;
     /* 24-layer and uint8 BEVs of a batch under per-frame poses (posed_bev_frames, bev_capi_packed.hip): the frame and pose table of
@@ -237,7 +238,8 @@ struct bev_ctx {
     bevh::UploadTable posed_tab;
     bevh::DevBuf posed_ws, posed_imgs;
     /* ... of submaps (submap_plan_up & co., bev_capi_packed.hip): the plan of a call; the planes are posed_ws, the images of
-     * bev_submap_bev_batch's chunks posed_imgs (both host-buffer calls are synchronous) */
+     * bev_submap_bev_batch's chunks posed_imgs (both host-buffer calls are synchronous).  The float submap calls
+     * (submap_float_frames) send their plan up the same table and have no planes: their output is the accumulator */
     bevh::UploadTable submap_tab;
     int posed_group = 0; /* BEV_POSED_GROUP=1 .. 65535: grids per launch group (tests: results do not depend on it); 0: what fits kPosedWsCap */
 

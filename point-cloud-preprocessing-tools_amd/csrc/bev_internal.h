@@ -223,6 +223,7 @@ enum KernelId {
     K_POSED_SPLAT,     /* the 24-layer and uint8 BEVs of a batch of frames under per-frame poses (bev_posed.h): points into the workspace planes */
     K_POSED_EXPAND,    /* ... the planes into the images */
     K_SUBMAP_SPLAT,    /* the same BEVs of submaps (bev_submap.h): the points of a group's frames into their entries' grids (the images: K_POSED_EXPAND) */
+    K_SUBMAP_FLOAT_SPLAT, /* the float BEV of submaps (bev_submap_float.h): the same points into their entries' grids of the output itself */
     K_COUNT
 };
 const char *kernel_name(int id);
@@ -329,6 +330,11 @@ void launch_posed_expand(const Geometry &g, const uint32_t *planes, int n_grids,
  * (bevsub::Entry); planes: the group's grids, zeroed by the caller on the same stream.  The images: launch_posed_expand. */
 void launch_submap_splat(const bev_point_t *clouds, const void *rows, const uint32_t *ent0, int nf, uint32_t blocks,
                          const void *entries, const Geometry &g, uint32_t *planes, hipStream_t st);
+/* ---- the float max-height BEV of submaps (bev_submap_float.h) ----
+ * rows, ent0, blocks and entries as for launch_submap_splat, of the call's ONE launch group; grids: one grid of M * M floats
+ * per map, the atomics' target, zeroed by the caller on the same stream */
+void launch_submap_float_splat(const bev_point_t *clouds, const void *rows, const uint32_t *ent0, int nf, uint32_t blocks,
+                               const void *entries, float interval, int M, bool skip_label0, float *grids, hipStream_t st);
 void launch_angle_debug(const float *dx, const float *dy, const float *dz, uint8_t *out, size_t n, hipStream_t st);
 /* ---- registration front end (bev_regfront.h; DESIGN.md "Registration front end") ---- */
 constexpr int kRfThreads = 256;

@@ -40,6 +40,7 @@
 #include "bev_manip.h"
 #include "bev_posed.h"
 #include "bev_submap.h"
+#include "bev_submap_float.h"
 #include "bev_reg_common.h"
 #include "bev_regfront.h"
 #include "bev_icp.h"
@@ -55,7 +56,7 @@ static const char *const kNames[K_COUNT] = {
     "k_probe", "k_walk_general", "k_walk_structured", "k_walk_colmajor", "k_walk_colmajor_gen", "k_verdict", "k_stage",
     "k_rf_cells", "k_rf_top", "k_rf_voxel", "k_rf_normals", "k_icp_grid", "k_icp", "k_icp_best",
     "k_fine_voxel", "k_fine_grid", "k_fine_icp", "k_kitti_crossings", "k_kitti_chain", "k_kitti_assign", "k_kitti_gather",
-    "k_float_bev_batch", "k_posed_splat", "k_posed_expand", "k_submap_splat",
+    "k_float_bev_batch", "k_posed_splat", "k_posed_expand", "k_submap_splat", "k_submap_float_splat",
 };
 const char *kernel_name(int id) { return (id >= 0 && id < K_COUNT) ? kNames[id] : "?"; }
 
@@ -299,6 +300,14 @@ void launch_submap_splat(const bev_point_t *clouds, const void *rows, const uint
     if (blocks == 0 || nf == 0) return;
     hipLaunchKernelGGL(k_submap_splat, dim3(blocks), dim3(256), 0, st, clouds, static_cast<const ProjFrame *>(rows), ent0, nf,
                        static_cast<const bevsub::Entry *>(entries), g.rp, planes);
+}
+void launch_submap_float_splat(const bev_point_t *clouds, const void *rows, const uint32_t *ent0, int nf, uint32_t blocks,
+                               const void *entries, float interval, int M, bool skip_label0, float *grids, hipStream_t st)
+{
+    if (blocks == 0 || nf == 0) return;
+    hipLaunchKernelGGL(k_submap_float_splat, dim3(blocks), dim3(256), 0, st, clouds, static_cast<const ProjFrame *>(rows), ent0,
+                       nf, static_cast<const bevsub::Entry *>(entries), interval, M, skip_label0 ? 1 : 0,
+                       reinterpret_cast<uint32_t *>(grids));
 }
 void launch_project_kitti(int step, const float *xyzi, const ProjFrame *tab, int nf, uint32_t n_max, const KittiWork &w,
                           bev_point_t *out, hipStream_t st)
