@@ -543,6 +543,61 @@ int bev_fine_registration_device_resident(bev_ctx_t *ctx, int n_frames, const be
                                           const int32_t *d_best, const bev_icp_params_t *params,
                                           bev_icp_result_t *d_results);
 
+/* ---- scan-to-map fine ICP: frames registered against submaps -----------------------------------------------------------
+ * The fine stage with a MAP as its target: map g is a list of (frame, pose) entries, exactly as for
+ * bev_submap_bev_device_resident, and
+ *   target(g) = the concatenation, over g's entries e IN THE ORDER GIVEN, of
+ *               bev_transform_cloud(bev_voxel_grid_irct(frame(e), leaf), pose(e));
+ *   result(m) = bev_icp_point_to_point(bev_voxel_grid_irct(frame query_idx, leaf), target(match_idx), guess, params)
+ * for match m = (query_idx, match_idx = a MAP's index, angle_guess), bit for bit.  Every frame is voxelised on
+ * its own, once, and the voxel clouds are moved; there is no second voxel grid over the union.  A target point's index is its
+ * position in the concatenation, and the search's "lowest index on ties" is over that index: unlike in the rasters, the
+ * order of a map's entries matters.  Points a matrix makes non-finite keep their index and are never matched.  result.T takes
+ * the query frame into the map's coordinates.  A map without entries or without a searchable point ends as
+ * bev_icp_point_to_point ends on an empty target: BEV_ICP_NO_CORRESPONDENCES, fitness DBL_MAX.
+ * d_clouds, h_offsets : as bev_fine_registration_device_resident (h_offsets NULL: d_ordered, S records per frame).
+ * h_map_offsets, h_entry_frame, h_entry_pose : exactly as bev_submap_bev_device_resident: any number of entries per map; a
+ *                       frame may appear several times in one map, feed many maps, or be named by none; the call's total of
+ *                       entries is bounded by BEV_SUBMAP_MAX_ENTRIES, and the record counts of one map's entries' frames
+ *                       together by BEV_SUBMAP_REG_MAX_TARGET.  A map no match names costs nothing.
+ * h_matches           : n_matches HOST records; query_idx in 0 .. n_frames - 1, match_idx in 0 .. n_maps - 1.
+ * d_coarse, d_best    : as bev_fine_registration_device_resident: both NULL: the yaw guess of angle_guess; both given: match m
+ *                       starts from d_coarse[2m + d_best[m]].T; one NULL and the other not: BEV_ERR_INVALID_ARG.
+ * d_results           : n_matches results (device); match m's at index m.  params NULL: the fine defaults.
+ * Ordering  : asynchronous like bev_fine_registration_device_resident: it starts behind every call made on the context before
+ *             it and behind the caller's default-stream work; the next BEV call starts behind it.  bev_synchronize() before
+ *             reading the results.  The host arrays may be reused as soon as the call returns.
+ * Status    : BEV_ERR_INVALID_ARG for a NULL context, a negative count, invalid parameters or leaf, and, with matches to run,
+ *             a NULL array that would be read, decreasing offsets, an entry frame outside 0 .. n_frames - 1, a query_idx
+ *             outside the frames, a match_idx outside the maps; BEV_ERR_TOO_LARGE for more than BEV_SUBMAP_MAX_ENTRIES
+ *             entries (checked before the entry arrays are read) and for a map whose entries' frames total more than
+ *             BEV_SUBMAP_REG_MAX_TARGET records.  Nothing is launched and d_results is untouched in every such case.
+ *             n_matches == 0 returns BEV_OK.
+ * Workspace : in the fine stage's buffer (allocated on first use, grown when a call needs more, freed by bev_destroy).  With U
+ *             the distinct frames that queries and used maps' entries name, N the largest of their record counts, K the
+ *             smallest power of two >= N, E the entries of the used maps and, of the launch group that needs most, T the sum
+ *             of its maps' capacities (a map's capacity: the record counts of its entries' frames together) and M its maps:
+ *               U * (32 N + 4) + min(U, 256) * (8 K + 4 N + 4) + min(n_matches, 1024) * 20 N + 4 E + 32 T + M * (4 * 16385 + 32)
+ *             bytes (pieces rounded up to 256), plus the tables (16 bytes per frame and per map, 64 per entry, 80 per match).
+ *             The used maps are cut into launch groups of consecutive maps whose 32 T + M * (4 * 16385 + 32) bytes fit 8 GiB
+ *             (BEV_SUBMAP_REG_GROUP=<bytes> in the environment of bev_create sets the cap instead; results do not depend on
+ *             it); a map above the cap is a group of its own.  Frames run in voxel launches of 256, a group's matches in ICP
+ *             launches of 1024. */
+#define BEV_SUBMAP_REG_MAX_TARGET (1u << 22)   /* records of one map's entries' frames together */
+int bev_submap_registration_device_resident(bev_ctx_t *ctx, int n_frames, const bev_point_t *d_clouds, const uint64_t *h_offsets,
+                                            float leaf, int n_maps, const uint64_t *h_map_offsets,
+                                            const int32_t *h_entry_frame, const float *h_entry_pose, int n_matches,
+                                            const bev_match_t *h_matches, const bev_icp_result_t *d_coarse,
+                                            const int32_t *d_best, const bev_icp_params_t *params,
+                                            bev_icp_result_t *d_results);
+/* The same through HOST buffers, synchronous: clouds[f] holds n_pts[f] records (NULL clouds[f] with n_pts[f] > 0:
+ * BEV_ERR_INVALID_ARG); results receives n_matches records.  Yaw guesses only.  The clouds go up into the fine stage's input
+ * buffer (grown on demand), the results come down from a device buffer of the context. */
+int bev_submap_registration_batch(bev_ctx_t *ctx, int n_frames, const bev_point_t *const *clouds, const uint32_t *n_pts,
+                                  float leaf, int n_maps, const uint64_t *h_map_offsets, const int32_t *h_entry_frame,
+                                  const float *h_entry_pose, int n_matches, const bev_match_t *h_matches,
+                                  const bev_icp_params_t *params, bev_icp_result_t *results);
+
 /* ---- layout hint -------------------------------------------------------
  * What the caller knows about how its clouds are laid out, so that the library need not look (k_probe reads every 63rd
  * record of a frame to find out: 0.36 MB and 0.07 us of an HDL_64E frame).  Sticky per context; applies to frames of

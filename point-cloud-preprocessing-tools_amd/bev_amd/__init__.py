@@ -73,6 +73,7 @@ KITTI_SLOTS = 64 * 2083
 FLOAT_BEV_MAX_POSES = 64  # BEV_FLOAT_BEV_MAX_POSES: poses per frame of float_bev_device / float_bev_batch
 POSED_BEV_MAX_POSES = 64  # BEV_POSED_BEV_MAX_POSES: poses per frame of posed_bev_device / posed_bev_batch
 SUBMAP_MAX_ENTRIES = 1 << 20  # BEV_SUBMAP_MAX_ENTRIES: (frame, pose) entries of one submap_bev_device / submap_bev_batch call
+SUBMAP_REG_MAX_TARGET = 1 << 22  # BEV_SUBMAP_REG_MAX_TARGET: records of one map's entries' frames together (submap_registration_*)
 
 # every symbol include/bev_mi355x.h declares
 ABI_SYMBOLS = [
@@ -93,6 +94,7 @@ ABI_SYMBOLS = [
     "bev_posed_bev_device_resident", "bev_posed_bev_batch",
     "bev_submap_bev_device_resident", "bev_submap_bev_batch",
     "bev_submap_float_bev_device_resident", "bev_submap_float_bev_batch",
+    "bev_submap_registration_device_resident", "bev_submap_registration_batch",
 ]
 
 # registration front end (include/bev_mi355x.h): pcl::PointXYZ, pcl::Normal, pcl::PointNormal as float rows
@@ -227,6 +229,12 @@ def load_lib() -> C.CDLL:
                                                              C.POINTER(C.c_uint64), vp, vp, vp]
         lib.bev_submap_float_bev_batch.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(u32), C.c_float, i32, i32,
                                                    C.POINTER(C.c_uint64), vp, vp, C.POINTER(vp)]
+    if hasattr(lib, "bev_submap_registration_device_resident"):
+        lib.bev_submap_registration_device_resident.argtypes = [vp, i32, vp, C.POINTER(C.c_uint64), C.c_float, i32,
+                                                                C.POINTER(C.c_uint64), vp, vp, i32, vp, vp, vp,
+                                                                C.POINTER(IcpParams), vp]
+        lib.bev_submap_registration_batch.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(u32), C.c_float, i32,
+                                                      C.POINTER(C.c_uint64), vp, vp, i32, vp, C.POINTER(IcpParams), vp]
     _lib = lib
     return lib
 
@@ -696,6 +704,39 @@ class BevContext:
                                       d_best.data_ptr() if d_best is not None else None, leaf, params)
         self.synchronize()
         res[:] = d_res.cpu().numpy().view(ICP_RESULT_DTYPE)
+        return res
+
+    # ---- scan-to-map fine ICP: frames against submaps ---------------------------------------------
+    def submap_registration_device(self, n_frames, d_clouds, offsets, map_offsets, entry_frame, entry_pose, matches,
+                                   d_results, d_coarse=None, d_best=None, leaf=0.2, params: IcpParams | None = None):
+        """bev_submap_registration_device_resident on device pointers: frames as for fine_registration_device (offsets None:
+        the d_ordered layout), maps and entries as for submap_bev_device; matches: MATCH_DTYPE records (host) whose match_idx
+        names a MAP: the query frame's voxel cloud is registered against the map's entries' moved voxel clouds, concatenated
+        in the order given.  Asynchronous: synchronize() before reading d_results (one ICP_RESULT_DTYPE per match)."""
+        offsets, offs = _offsets(offsets, n_frames) if offsets is not None else (None, None)
+        n_maps, map_offsets, entry_frame, entry_pose = self._submap_entries(map_offsets, entry_frame, entry_pose)
+        m = np.ascontiguousarray(matches, dtype=MATCH_DTYPE)
+        prm = params if params is not None else icp_fine_defaults()
+        self._check(self.lib.bev_submap_registration_device_resident(
+            self._h, n_frames, C.c_void_p(d_clouds or None), offs, leaf, n_maps,
+            map_offsets.ctypes.data_as(C.POINTER(C.c_uint64)), _ptr(entry_frame), _ptr(entry_pose), len(m),
+            _ptr(m) if len(m) else None, C.c_void_p(d_coarse) if d_coarse else None, C.c_void_p(d_best) if d_best else None,
+            C.byref(prm), C.c_void_p(d_results or None)), "bev_submap_registration_device_resident")
+
+    def submap_registration_batch(self, clouds, map_offsets, entry_frame, entry_pose, matches, leaf=0.2,
+                                  params: IcpParams | None = None):
+        """bev_submap_registration_batch on host clouds (yaw guesses); maps as for submap_bev_device, matches MATCH_DTYPE
+        records or (query_idx, map index, angle_guess) tuples.  Returns (n_matches,) ICP_RESULT_DTYPE."""
+        clouds, pts, npts = _host_clouds(clouds)
+        n_maps, map_offsets, entry_frame, entry_pose = self._submap_entries(map_offsets, entry_frame, entry_pose)
+        m = np.array([tuple(r) for r in matches], dtype=MATCH_DTYPE) if not isinstance(matches, np.ndarray) else \
+            np.ascontiguousarray(matches, dtype=MATCH_DTYPE)
+        prm = params if params is not None else icp_fine_defaults()
+        res = np.zeros(len(m), dtype=ICP_RESULT_DTYPE)
+        self._check(self.lib.bev_submap_registration_batch(
+            self._h, len(clouds), pts, npts, leaf, n_maps, map_offsets.ctypes.data_as(C.POINTER(C.c_uint64)),
+            _ptr(entry_frame), _ptr(entry_pose), len(m), _ptr(m) if len(m) else None, C.byref(prm),
+            _ptr(res) if len(m) else None), "bev_submap_registration_batch")
         return res
 
     def set_layout_hint(self, layout: int):

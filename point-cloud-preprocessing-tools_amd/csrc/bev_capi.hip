@@ -818,6 +818,7 @@ int bev_create(bev_ctx_t **out, int device, const bev_params_t *p, int max_batch
         if (const char *mt = getenv("BEV_MODE_TTL")) c->mode_ttl = std::max(1, atoi(mt));
         if (const char *pg = getenv("BEV_PROJECT_GROUP")) c->kitti_group = std::max(1, std::min(64, atoi(pg)));
         if (const char *pg = getenv("BEV_POSED_GROUP")) c->posed_group = std::max(1, std::min(65535, atoi(pg)));
+        if (const char *sg = getenv("BEV_SUBMAP_REG_GROUP")) c->submap_reg_group = (size_t)std::max(1ll, atoll(sg));
     }
     {   /* EQUAL priorities (profiles/r06_experiments.txt): the launches of two such streams share the chip workgroup by workgroup,
          * 396-400 k frames/s where different priorities (the higher stream's launch dispatched first, whole) gave 384-386 k

@@ -302,9 +302,12 @@ int submap_float_frames(bev_ctx *c, const bev_point_t *d_clouds, const uint64_t 
     return BEV_OK;
 }
 
-/* What the submap entry points check of the maps: BEV_OK, or what the entry point returns.  The entry arrays are read only
- * when their length has passed. */
-int check_submap_entries(int n_frames, int n_maps, const uint64_t *map_offs, const int32_t *entry_frame, const float *entry_pose)
+} // namespace
+
+/* What the submap entry points (and those of bev_capi_reg.hip) check of the maps: BEV_OK, or what the entry point returns.
+ * The entry arrays are read only when their length has passed. */
+int bevh::check_submap_entries(int n_frames, int n_maps, const uint64_t *map_offs, const int32_t *entry_frame,
+                               const float *entry_pose)
 {
     if (n_maps < 0 || !map_offs) return BEV_ERR_INVALID_ARG;
     for (int g = 0; g < n_maps; ++g)
@@ -316,8 +319,6 @@ int check_submap_entries(int n_frames, int n_maps, const uint64_t *map_offs, con
         if (entry_frame[e] < 0 || entry_frame[e] >= n_frames) return BEV_ERR_INVALID_ARG;
     return BEV_OK;
 }
-
-} // namespace
 
 /* The projection of nf frames on the context's stream: frame f = returns [offs[f], offs[f + 1]) of d_xyzi (offsets checked by
  * the caller).  Kinds 0 / 1: ONE launch, records at the same offsets of d_out.  KITTI: launch groups of kitti_group frames

@@ -1,7 +1,9 @@
 /*
  * bev_capi_reg.hip — the registration half of the extern "C" boundary declared in include/bev_mi355x.h: the front end
- * (top-part flatten, voxel grid, 2-D normals), coarse point-to-plane ICP (§6c) and the fine stage (§6d).
- * Host-side only; the kernels are in bev_kernels.hip (bev_reg_common.h, bev_regfront.h, bev_icp.h, bev_fine.h).  With
+ * (top-part flatten, voxel grid, 2-D normals), coarse point-to-plane ICP (§6c), the fine stage (§6d) and
+ * scan-to-map fine ICP (§6k).
+ * Host-side only; the kernels are in bev_kernels.hip (bev_reg_common.h, bev_regfront.h, bev_icp.h, bev_fine.h,
+ * bev_submap_reg.h).  With
  * the BEV pipeline of bev_capi.hip it shares the context (bev_ctx.h), its stream and the call prologue (begin_call).
  */
 #include <algorithm>
@@ -12,6 +14,7 @@
 
 #include "bev_ctx.h"
 #include "bev_libm_f64.h"
+#include "bev_submap_reg_plan.h"
 
 using namespace bevk;
 using namespace bevh;
@@ -19,7 +22,7 @@ using namespace bevh;
 /* ---- what the entry points keep between calls (RegState, bev_ctx.h; DevBuf and UploadTable themselves: bev_capi.hip) ---- */
 void RegState::release()
 {
-    for (DevBuf *b : {&rf_buf, &icp_buf, &icp_one, &fine_buf, &fine_in}) b->release();
+    for (DevBuf *b : {&rf_buf, &icp_buf, &icp_one, &fine_buf, &fine_in, &sub_res}) b->release();
     for (UploadTable *t : {&rf_offs, &icp_tab, &fine_tab}) t->release();
     if (tail_ev) (void)hipEventDestroy(tail_ev);
     tail_ev = nullptr;
@@ -588,6 +591,180 @@ int bev_fine_registration_device_resident(bev_ctx_t *c, int n_frames, const bev_
     rc = fine_icp(c, U, d_probs, probs.size(), w, d_coarse, d_best, prm, d_results);
     if (rc != BEV_OK) return rc;
     return record_tail(c);
+}
+
+/* ---- scan-to-map fine ICP: frames against submaps (bev_submap_reg_plan.h, bev_submap_reg.h) ------------- */
+namespace {
+
+constexpr uint64_t kSubmapRegCap = (uint64_t)8 << 30; /* bytes of a launch group's maps (BEV_SUBMAP_REG_GROUP): 8 GiB, of the order of
+                                                        * the voxel clouds of a call on a thousand sweeps, and hundreds of maps of full sweeps
+                                                        * in one launch (a map is one workgroup of k_submap_target, a match one of k_submap_icp) */
+
+/* what both entries check behind their own arguments: BEV_OK, or what the entry returns.  frame_n: the frames' record counts */
+static int submap_reg_check(int n_frames, const std::vector<uint64_t> &frame_n, int n_maps, const uint64_t *map_offs,
+                     const int32_t *entry_frame, const float *entry_pose, int n_matches, const bev_match_t *h_matches)
+{
+    const int rc = check_submap_entries(n_frames, n_maps, map_offs, entry_frame, entry_pose);
+    if (rc != BEV_OK) return rc;
+    for (int m = 0; m < n_matches; ++m) {
+        const bev_match_t &mt = h_matches[m];
+        if (mt.query_idx < 0 || mt.query_idx >= n_frames || mt.match_idx < 0 || mt.match_idx >= n_maps) return BEV_ERR_INVALID_ARG;
+    }
+    for (int g = 0; g < n_maps; ++g)
+        if (bevsubreg::map_capacity(frame_n.data(), map_offs, entry_frame, g) > BEV_SUBMAP_REG_MAX_TARGET) return BEV_ERR_TOO_LARGE;
+    return BEV_OK;
+}
+
+/* The call on the context's stream, behind the entries' checks and begin_call: frame f = frame_n[f] records at frame_off[f]
+ * of d_clouds. */
+static int submap_reg_frames(bev_ctx *c, int n_frames, const bev_point_t *d_clouds, const std::vector<uint64_t> &frame_off,
+                      const std::vector<uint64_t> &frame_n, float leaf, int n_maps, const uint64_t *map_offs,
+                      const int32_t *entry_frame, const float *entry_pose, int n_matches, const bev_match_t *h_matches,
+                      const bev_icp_result_t *d_coarse, const int32_t *d_best, const bev_icp_params_t &prm,
+                      bev_icp_result_t *d_results)
+{
+    std::vector<int32_t> query((size_t)n_matches), match_map((size_t)n_matches);
+    for (int m = 0; m < n_matches; ++m) {
+        query[(size_t)m] = h_matches[m].query_idx;
+        match_map[(size_t)m] = h_matches[m].match_idx;
+    }
+    const uint64_t cap = c->submap_reg_group ? (uint64_t)c->submap_reg_group : kSubmapRegCap;
+    const bevsubreg::Plan plan = bevsubreg::plan_call(n_frames, frame_off.data(), frame_n.data(), n_maps, map_offs, entry_frame,
+                                                      entry_pose, n_matches, query.data(), match_map.data(), cap);
+    const size_t U = plan.slots.size(), P = plan.probs.size(), E = plan.entries.size(), Pn = plan.Pn, Kn = pow2_at_least(Pn);
+    const size_t G = std::min(U, (size_t)kFineVoxelGroup), L = std::min(P, (size_t)kFineProblemsPerLaunch);
+    const size_t T = std::max<size_t>((size_t)plan.max_group_pts, 1), M = std::max<size_t>(plan.max_group_maps, 1);
+    /* the workspace: the voxel clouds of the slots (no grids: no frame is a target), the scratch of a voxel launch and of an
+     * ICP launch, the entries' first indices, the maps of one launch group */
+    FineWork w{};
+    SubmapRegWork t{};
+    uint32_t *ent_start = nullptr;
+    const size_t sz[] = {U * Pn * sizeof(bev_point_t), U * 4, G * Kn * 8, G * (Pn + 1) * 4, L * Pn * 16, L * Pn * 4,
+                         std::max<size_t>(E, 1) * 4, T * 16, T * 16, M * sizeof(IcpGridHdr), M * 4 * (size_t)(kFineCells + 1)};
+    void **const dst[] = {(void **)&w.vox, (void **)&w.vox_n, (void **)&w.keys, (void **)&w.vstart, (void **)&w.cur,
+                          (void **)&w.corr, (void **)&ent_start, (void **)&t.pts, (void **)&t.sorted, (void **)&t.hdr,
+                          (void **)&t.cell_off};
+    int rc = c->reg.fine_buf.grow(c, carve(nullptr, sz, dst));
+    if (rc != BEV_OK) return rc;
+    carve(c->reg.fine_buf.p, sz, dst);
+    w.Pn = Pn;
+    w.Kn = Kn;
+    /* the tables, one block: slots, maps, entries (64-byte aligned), problems */
+    static_assert(sizeof(bevsubreg::Slot) == sizeof(FineSlot), "the plan's slots are k_fine_voxel's");
+    const size_t o_maps = align256(U * sizeof(FineSlot)), o_ent = o_maps + align256(plan.maps.size() * sizeof(bevsubreg::Map)),
+                 o_probs = o_ent + align256(E * sizeof(bevsubreg::Entry)), tab = o_probs + P * sizeof(FineProblem);
+    void *hv;
+    rc = c->reg.fine_tab.begin(c, tab, kRegTabMin, &hv);
+    if (rc != BEV_OK) return rc;
+    char *h = static_cast<char *>(hv);
+    if (U) std::memcpy(h, plan.slots.data(), U * sizeof(FineSlot));
+    if (!plan.maps.empty()) std::memcpy(h + o_maps, plan.maps.data(), plan.maps.size() * sizeof(bevsubreg::Map));
+    if (E) std::memcpy(h + o_ent, plan.entries.data(), E * sizeof(bevsubreg::Entry));
+    FineProblem *hp = reinterpret_cast<FineProblem *>(h + o_probs);
+    for (size_t k = 0; k < P; ++k) {
+        const bevsubreg::Problem &pp = plan.probs[k];
+        FineProblem &pb = hp[k];
+        pb.src_slot = pp.src_slot;
+        pb.tgt_slot = pp.map;
+        pb.result = pp.result;
+        pb.coarse_match = d_coarse ? pp.result : 0xffffffffu;
+        bevx::icp_tool_guess(h_matches[pp.result].angle_guess, 0, pb.guess);
+    }
+    rc = c->reg.fine_tab.push(c, tab);
+    if (rc != BEV_OK) return rc;
+    const char *dev = static_cast<const char *>(c->reg.fine_tab.dev);
+    const FineSlot *d_slots = reinterpret_cast<const FineSlot *>(dev);
+    const void *d_maps = dev + o_maps, *d_entries = dev + o_ent;
+    const FineProblem *d_probs = reinterpret_cast<const FineProblem *>(dev + o_probs);
+    rc = fine_voxel(c, d_clouds, d_slots, (int)U, w, leaf);
+    if (rc != BEV_OK) return rc;
+    /* the groups one behind the other on the stream: its order hands the maps' arrays from group to group */
+    for (const bevsubreg::Group &g : plan.groups) {
+        {
+            ProfScope ps(c, K_SUBMAP_TARGET, (int)g.n_maps);
+            launch_submap_target(d_maps, g.map0, (int)g.n_maps, d_entries, w, ent_start, t, c->stream);
+        }
+        for (uint32_t p0 = 0; p0 < g.n_probs; p0 += kFineProblemsPerLaunch) {
+            const int n = (int)std::min<uint32_t>(kFineProblemsPerLaunch, g.n_probs - p0);
+            ProfScope ps(c, K_SUBMAP_ICP, n);
+            launch_submap_icp(d_probs + g.prob0 + p0, n, d_maps, g.map0, w, t, d_coarse, d_best, prm, d_results, c->stream);
+        }
+    }
+    HIPCK(c, hipGetLastError());
+    return BEV_OK;
+}
+
+} // namespace
+
+int bev_submap_registration_device_resident(bev_ctx_t *c, int n_frames, const bev_point_t *d_clouds, const uint64_t *h_offsets,
+                                            float leaf, int n_maps, const uint64_t *h_map_offsets, const int32_t *h_entry_frame,
+                                            const float *h_entry_pose, int n_matches, const bev_match_t *h_matches,
+                                            const bev_icp_result_t *d_coarse, const int32_t *d_best,
+                                            const bev_icp_params_t *params, bev_icp_result_t *d_results)
+{
+    const bev_icp_params_t prm = params ? *params : bev_icp_fine_defaults();
+    if (!c || n_frames < 0 || n_maps < 0 || n_matches < 0 || !icp_params_ok(prm) || !(std::isfinite(leaf) && leaf > 0.0f) ||
+        (d_coarse == nullptr) != (d_best == nullptr))
+        return BEV_ERR_INVALID_ARG;
+    std::vector<uint64_t> frame_off, frame_n;
+    if (n_matches > 0) {
+        if (!h_matches || !d_results) return BEV_ERR_INVALID_ARG;
+        frame_off.resize((size_t)n_frames);
+        frame_n.resize((size_t)n_frames);
+        for (int f = 0; f < n_frames; ++f) {
+            if (h_offsets && (h_offsets[f + 1] < h_offsets[f] || h_offsets[f + 1] - h_offsets[f] > 0xffffffffull)) return BEV_ERR_INVALID_ARG;
+            frame_off[(size_t)f] = h_offsets ? h_offsets[f] : (uint64_t)f * c->geo.S;
+            frame_n[(size_t)f] = h_offsets ? h_offsets[f + 1] - h_offsets[f] : (uint64_t)c->geo.S;
+        }
+        const int rc_ = submap_reg_check(n_frames, frame_n, n_maps, h_map_offsets, h_entry_frame, h_entry_pose, n_matches, h_matches);
+        if (rc_ != BEV_OK) return rc_;
+        if (!d_clouds) return BEV_ERR_INVALID_ARG;
+    }
+    int rc = begin_call(c, false);
+    if (rc != BEV_OK) return rc;
+    if (n_matches == 0) return BEV_OK;
+    rc = wait_default_stream(c);
+    if (rc != BEV_OK) return rc;
+    rc = submap_reg_frames(c, n_frames, d_clouds, frame_off, frame_n, leaf, n_maps, h_map_offsets, h_entry_frame, h_entry_pose,
+                           n_matches, h_matches, d_coarse, d_best, prm, d_results);
+    if (rc != BEV_OK) return rc;
+    return record_tail(c);
+}
+
+int bev_submap_registration_batch(bev_ctx_t *c, int n_frames, const bev_point_t *const *clouds, const uint32_t *n_pts, float leaf,
+                                  int n_maps, const uint64_t *h_map_offsets, const int32_t *h_entry_frame,
+                                  const float *h_entry_pose, int n_matches, const bev_match_t *h_matches,
+                                  const bev_icp_params_t *params, bev_icp_result_t *results)
+{
+    const bev_icp_params_t prm = params ? *params : bev_icp_fine_defaults();
+    if (!c || n_frames < 0 || n_maps < 0 || n_matches < 0 || !icp_params_ok(prm) || !(std::isfinite(leaf) && leaf > 0.0f))
+        return BEV_ERR_INVALID_ARG;
+    if (n_frames > 0 && (!clouds || !n_pts)) return BEV_ERR_INVALID_ARG;
+    for (int f = 0; f < n_frames; ++f)
+        if (n_pts[f] && !clouds[f]) return BEV_ERR_INVALID_ARG;
+    std::vector<uint64_t> frame_off((size_t)n_frames), frame_n((size_t)n_frames);
+    if (n_matches > 0) {
+        if (!h_matches || !results) return BEV_ERR_INVALID_ARG;
+        for (int f = 0; f < n_frames; ++f) frame_n[(size_t)f] = n_pts[f];
+        const int rc_ = submap_reg_check(n_frames, frame_n, n_maps, h_map_offsets, h_entry_frame, h_entry_pose, n_matches, h_matches);
+        if (rc_ != BEV_OK) return rc_;
+    }
+    int rc = begin_call(c, false);
+    if (rc != BEV_OK) return rc;
+    if (n_matches == 0) return BEV_OK;
+    std::vector<size_t> offs((size_t)std::max(n_frames, 1));
+    rc = fine_upload(c, clouds, n_pts, n_frames, offs.data());
+    if (rc != BEV_OK) return rc;
+    for (int f = 0; f < n_frames; ++f) frame_off[(size_t)f] = offs[(size_t)f];
+    rc = c->reg.sub_res.grow(c, (size_t)n_matches * sizeof(bev_icp_result_t));
+    if (rc != BEV_OK) return rc;
+    bev_icp_result_t *d_res = static_cast<bev_icp_result_t *>(c->reg.sub_res.p);
+    rc = submap_reg_frames(c, n_frames, static_cast<const bev_point_t *>(c->reg.fine_in.p), frame_off, frame_n, leaf, n_maps,
+                           h_map_offsets, h_entry_frame, h_entry_pose, n_matches, h_matches, nullptr, nullptr, prm, d_res);
+    if (rc != BEV_OK) return rc;
+    HIPCK(c, hipMemcpyAsync(results, d_res, (size_t)n_matches * sizeof(bev_icp_result_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    return BEV_OK;
 }
 
 } /* extern "C" */

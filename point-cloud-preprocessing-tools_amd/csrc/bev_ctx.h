@@ -145,6 +145,9 @@ struct RegState {
      * clouds of the per-cloud entries; the slot and problem tables */
     DevBuf fine_buf, fine_in;
     UploadTable fine_tab;
+    /* scan-to-map fine ICP (bev_submap_registration_device_resident & co.) works in fine_buf and sends its plan
+     * up fine_tab; sub_res: the results of bev_submap_registration_batch on the device */
+    DevBuf sub_res;
     /* Recorded on the context's stream behind the last batched registration call (front end, coarse, fine): the next BEV
      * call's stage streams wait for it.  One event serves all three: they record on the same stream, so the latest record
      * covers the earlier ones. */
@@ -241,6 +244,7 @@ struct bev_ctx {
      * bev_submap_bev_batch's chunks posed_imgs (both host-buffer calls are synchronous).  The float submap calls
      * (submap_float_frames) send their plan up the same table and have no planes: their output is the accumulator */
     bevh::UploadTable submap_tab;
+    size_t submap_reg_group = 0; /* BEV_SUBMAP_REG_GROUP=<bytes>: the cap of a launch group of bev_submap_registration_* (tests: results do not depend on it); 0: kSubmapRegCap */
     int posed_group = 0; /* BEV_POSED_GROUP=1 .. 65535: grids per launch group (tests: results do not depend on it); 0: what fits kPosedWsCap */
 
     bevh::RegState reg;
@@ -299,6 +303,9 @@ inline bool project_kind_ok(int kind)
     return kind == BEV_PROJECT_MULRAN_OS1_64 || kind == BEV_PROJECT_OXFORD_HDL_32E || kind == BEV_PROJECT_KITTI_HDL_64E;
 }
 int project_frames(bev_ctx *c, int kind, int nf, const float *d_xyzi, const uint64_t *offs, bev_point_t *d_out);
+/* What the submap entry points check of the maps (bev_capi_packed.hip): BEV_OK, or what the entry point returns.  The entry
+ * arrays are read only when their length has passed. */
+int check_submap_entries(int n_frames, int n_maps, const uint64_t *map_offs, const int32_t *entry_frame, const float *entry_pose);
 
 inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 /* one allocation in 256-byte aligned pieces: *dst[i] = the piece of sz[i] bytes (base == nullptr: nothing is written);

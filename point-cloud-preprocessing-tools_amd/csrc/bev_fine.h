@@ -265,29 +265,28 @@ __device__ void fine_step(FineShared &sh, const bev_icp_params_t &prm, double ms
     reg_converge(sh.loop, prm, mse_sum, sh.sums.cnt, prev);
 }
 
-__global__ __launch_bounds__(kFineThreads) void k_fine_icp(const FineProblem *probs, FineWork w,
-                                                           const bev_icp_result_t *coarse, const int32_t *best,
-                                                           bev_icp_params_t prm, bev_icp_result_t *results)
+/* a problem's first guess: the better coarse result of its match (top-part tool), or the one it carries */
+__device__ __forceinline__ void fine_guess(const FineProblem &pb, const bev_icp_result_t *coarse, const int32_t *best, float *G)
 {
-    __shared__ FineShared sh;
-    const int tid = threadIdx.x;
-    const FineProblem pb = probs[blockIdx.x];
-    const uint32_t n_src = w.vox_n[pb.src_slot];
-    const bev_point_t *src = w.vox + (size_t)pb.src_slot * w.Pn;
-    const bev_point_t *tgt = w.vox + (size_t)pb.tgt_slot * w.Pn;
-    const float4 *tpts = w.sorted + (size_t)pb.tgt_slot * w.Pn;
-    const uint32_t *toff = w.cell_off + (size_t)pb.tgt_slot * (kFineCells + 1);
-    const IcpGridHdr h = w.hdr[pb.tgt_slot];
-    float4 *cur = w.cur + (size_t)(blockIdx.x % kFineProblemsPerLaunch) * w.Pn;
-    uint32_t *corr = w.corr + (size_t)(blockIdx.x % kFineProblemsPerLaunch) * w.Pn;
-    float G[16];
-    if (pb.coarse_match != 0xffffffffu) { /* the better coarse result of the match (top-part tool) */
+    if (pb.coarse_match != 0xffffffffu) {
         const uint32_t m = pb.coarse_match;
         const bev_icp_result_t &r = coarse[2 * (size_t)m + (best[m] ? 1 : 0)];
         for (int k = 0; k < 16; ++k) G[k] = r.T[k];
     } else {
         for (int k = 0; k < 16; ++k) G[k] = pb.guess[k];
     }
+}
+
+/* One problem by its workgroup: the voxel cloud src of n_src points onto a target that is read through tgt(j), the position of
+ * target point j, and its search grid (h, toff, tpts); cur, corr: the problem's scratch.  k_fine_icp's target is a slot's voxel
+ * cloud, k_submap_icp's (bev_submap_reg.h) a map's moved points. */
+template <class Tgt>
+__device__ __forceinline__ void fine_icp_problem(FineShared &sh, uint32_t n_src, const bev_point_t *src, Tgt tgt,
+                                                 const IcpGridHdr &h, const uint32_t *toff, const float4 *tpts, float4 *cur,
+                                                 uint32_t *corr, const float *G, const bev_icp_params_t &prm,
+                                                 bev_icp_result_t *result)
+{
+    const int tid = threadIdx.x;
     reg_start(sh.loop, G, n_src, FinePts{src}, cur);
     __syncthreads();
     const double D2 = prm.max_correspondence_distance * prm.max_correspondence_distance;
@@ -303,7 +302,7 @@ __global__ __launch_bounds__(kFineThreads) void k_fine_icp(const FineProblem *pr
                 return false;
             }
             corr[i] = j;
-            const bev_point_t &tp = tgt[j];
+            const float3 tp = tgt(j);
             t[0] = s.x;
             t[1] = s.y;
             t[2] = s.z;
@@ -331,7 +330,7 @@ __global__ __launch_bounds__(kFineThreads) void k_fine_icp(const FineProblem *pr
             const uint32_t j = corr[i];
             if (j == 0xffffffffu) return false;
             const float4 s = cur[i];
-            const bev_point_t &tp = tgt[j];
+            const float3 tp = tgt(j);
             const float sd[3] = {s.x - M[0], s.y - M[1], s.z - M[2]};
             const float dd[3] = {tp.x - M[3], tp.y - M[4], tp.z - M[5]};
 #pragma unroll
@@ -345,7 +344,21 @@ __global__ __launch_bounds__(kFineThreads) void k_fine_icp(const FineProblem *pr
         if (sh.loop.state != 0) break;
         reg_advance(sh.loop, n_src, cur);
     }
-    reg_finish(sh.sums, sh.loop, n_src, FinePts{src}, h, toff, tpts, results + pb.result);
+    reg_finish(sh.sums, sh.loop, n_src, FinePts{src}, h, toff, tpts, result);
+}
+
+__global__ __launch_bounds__(kFineThreads) void k_fine_icp(const FineProblem *probs, FineWork w,
+                                                           const bev_icp_result_t *coarse, const int32_t *best,
+                                                           bev_icp_params_t prm, bev_icp_result_t *results)
+{
+    __shared__ FineShared sh;
+    const FineProblem pb = probs[blockIdx.x];
+    float G[16];
+    fine_guess(pb, coarse, best, G);
+    fine_icp_problem(sh, w.vox_n[pb.src_slot], w.vox + (size_t)pb.src_slot * w.Pn, FinePts{w.vox + (size_t)pb.tgt_slot * w.Pn},
+                     w.hdr[pb.tgt_slot], w.cell_off + (size_t)pb.tgt_slot * (kFineCells + 1),
+                     w.sorted + (size_t)pb.tgt_slot * w.Pn, w.cur + (size_t)(blockIdx.x % kFineProblemsPerLaunch) * w.Pn,
+                     w.corr + (size_t)(blockIdx.x % kFineProblemsPerLaunch) * w.Pn, G, prm, results + pb.result);
 }
 
 void launch_fine_voxel(const bev_point_t *pts, const FineSlot *slots, int slot0, int n, const FineWork &w, float leaf,

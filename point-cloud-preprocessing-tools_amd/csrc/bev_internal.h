@@ -224,6 +224,8 @@ enum KernelId {
     K_POSED_EXPAND,    /* ... the planes into the images */
     K_SUBMAP_SPLAT,    /* the same BEVs of submaps (bev_submap.h): the points of a group's frames into their entries' grids (the images: K_POSED_EXPAND) */
     K_SUBMAP_FLOAT_SPLAT, /* the float BEV of submaps (bev_submap_float.h): the same points into their entries' grids of the output itself */
+    K_SUBMAP_TARGET,   /* scan-to-map fine ICP (bev_submap_reg.h): a map's entries' moved voxel clouds and their search grid */
+    K_SUBMAP_ICP,      /* ... one workgroup per match: K_FINE_ICP's loop against the map */
     K_COUNT
 };
 const char *kernel_name(int id);
@@ -442,6 +444,23 @@ void launch_fine_voxel(const bev_point_t *pts, const FineSlot *slots, int slot0,
 void launch_fine_grid(int n_slots, const FineWork &w, hipStream_t st);
 void launch_fine_icp(const FineProblem *probs, int n, const FineWork &w, const bev_icp_result_t *coarse,
                      const int32_t *best, const bev_icp_params_t &prm, bev_icp_result_t *results, hipStream_t st);
+
+/* ---- scan-to-map fine ICP (bev_submap_reg.h, bev_submap_reg_plan.h) ----
+ * the maps of ONE launch group of the plan: a map's points at its pt0, its header and cell offsets at its index in the group */
+struct SubmapRegWork {
+    float4 *pts;        /* [the group's points]   the entries' moved voxel points: x, y, z */
+    float4 *sorted;     /* [the group's points]   the searchable ones by cell (x, y, z, index bits) */
+    IcpGridHdr *hdr;    /* [the group's maps] */
+    uint32_t *cell_off; /* [the group's maps][kFineCells + 1] */
+};
+/* maps / entries: the plan's tables (bevsubreg::Map, ::Entry); the n_maps maps from map0 on; ent_start: a word per entry of
+ * the call; w: the voxel clouds (vox, vox_n, Pn) */
+void launch_submap_target(const void *maps, uint32_t map0, int n_maps, const void *entries, const FineWork &w,
+                          uint32_t *ent_start, const SubmapRegWork &t, hipStream_t st);
+/* n <= kFineProblemsPerLaunch problems whose tgt_slot is a map's index in the plan (all in the group from map0 on) */
+void launch_submap_icp(const FineProblem *probs, int n, const void *maps, uint32_t map0, const FineWork &w,
+                       const SubmapRegWork &t, const bev_icp_result_t *coarse, const int32_t *best, const bev_icp_params_t &prm,
+                       bev_icp_result_t *results, hipStream_t st);
 
 /* opt in to > 64 KiB of dynamic LDS for the kernels that need it */
 hipError_t configure_kernels(const Geometry &g);

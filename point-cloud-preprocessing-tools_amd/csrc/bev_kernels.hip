@@ -45,6 +45,7 @@
 #include "bev_regfront.h"
 #include "bev_icp.h"
 #include "bev_fine.h"
+#include "bev_submap_reg.h"
 
 using namespace bevx;
 
@@ -57,6 +58,7 @@ static const char *const kNames[K_COUNT] = {
     "k_rf_cells", "k_rf_top", "k_rf_voxel", "k_rf_normals", "k_icp_grid", "k_icp", "k_icp_best",
     "k_fine_voxel", "k_fine_grid", "k_fine_icp", "k_kitti_crossings", "k_kitti_chain", "k_kitti_assign", "k_kitti_gather",
     "k_float_bev_batch", "k_posed_splat", "k_posed_expand", "k_submap_splat", "k_submap_float_splat",
+    "k_submap_target", "k_submap_icp",
 };
 const char *kernel_name(int id) { return (id >= 0 && id < K_COUNT) ? kNames[id] : "?"; }
 

@@ -1,0 +1,161 @@
+/*
+ * bev_submap_reg_plan.h — the host plan of a scan-to-map registration call (bev_submap_registration_device_resident,
+ * bev_submap_registration_batch): which frames get a voxel cloud, which voxel clouds under which matrices
+ * make which map's target, which maps share a launch group and which matches run against them.  Plain C++, no HIP:
+ * bev_capi_reg.hip builds and uploads the plan, tests/submapregcheck builds it and checks its invariants.
+ *
+ *   slots    the distinct frames that a match's query or a used map's entry names, in the order of first appearance (the
+ *            matches in their order, a match's query before its map's entries): one voxel cloud each;
+ *   maps     the maps that a match names ("used"), ascending by map index; a map that no match names costs nothing.  A
+ *            map's entries stay IN MAP ORDER (the index of a target point is its position in the concatenation, and ties
+ *            of the search go to the lowest index), each with its slot and its matrix; its capacity is the sum of its
+ *            entries' record counts, an upper bound of its voxel count (which only the device knows);
+ *   groups   consecutive used maps whose workspace (map_bytes of each) fits the cap; a map above the cap is a group alone.
+ *            A map's points lie at pt0 of the group's point arrays, its header and cell offsets at its index in the group;
+ *   problems the matches of a group's maps, ascending by map and among equal maps in the order of the call; match m's
+ *            result lands at index m whatever the grouping.
+ * bev_submap_plan.h sorts a group's entries by frame (its rasters are order-free) and is not used here.
+ */
+#ifndef BEV_SUBMAP_REG_PLAN_H
+#define BEV_SUBMAP_REG_PLAN_H
+
+#include <algorithm>
+#include <cstddef>
+#include <cstdint>
+#include <cstring>
+#include <vector>
+
+namespace bevsubreg {
+
+constexpr uint32_t kGridCells = 128 * 128; /* kFineCells (bev_internal.h): cells of a map's search grid */
+
+struct Slot { /* FineSlot's layout (bev_internal.h): k_fine_voxel reads the slots */
+    uint64_t off;
+    uint32_t n, _pad;
+};
+struct alignas(64) Entry { /* one aligned 64-byte line per entry, read at a workgroup-uniform address */
+    float m[12];   /* row-major 3 x 4 */
+    uint32_t slot; /* whose voxel cloud it moves */
+    uint32_t pad[3];
+};
+struct Map {
+    uint64_t pt0;         /* its first point in the group's point arrays */
+    uint32_t ent0, n_ent; /* its entries: [ent0, ent0 + n_ent) of Plan::entries */
+};
+struct Problem {
+    uint32_t src_slot; /* the query's slot */
+    uint32_t map;      /* index into Plan::maps */
+    uint32_t result;   /* the match's index in the call */
+    uint32_t _pad;
+};
+static_assert(sizeof(Slot) == 16 && sizeof(Entry) == 64 && sizeof(Map) == 16 && sizeof(Problem) == 16, "the device reads these layouts");
+
+struct Group {
+    uint32_t map0 = 0, n_maps = 0;   /* [map0, map0 + n_maps) of Plan::maps */
+    uint32_t prob0 = 0, n_probs = 0; /* [prob0, prob0 + n_probs) of Plan::probs */
+    uint64_t pts = 0;                /* points its maps can hold together */
+    uint64_t bytes = 0;              /* sum of map_bytes over its maps */
+};
+struct Plan {
+    std::vector<Slot> slots;
+    std::vector<int32_t> slot_frame; /* the call's frame index of a slot */
+    std::vector<Entry> entries;
+    std::vector<Map> maps;
+    std::vector<int32_t> map_id;     /* the call's map index of a used map */
+    std::vector<uint64_t> map_cap;   /* points a used map can hold */
+    std::vector<Problem> probs;
+    std::vector<Group> groups;
+    size_t Pn = 1;                   /* the largest record count of a slot (at least 1) */
+    uint64_t max_group_pts = 0;
+    uint32_t max_group_maps = 0;
+};
+
+/* device bytes of a map that can hold cap points: the moved points and the searchable points by cell (16 bytes each),
+ * the cell offsets, the header */
+inline uint64_t map_bytes(uint64_t cap) { return cap * 32 + (uint64_t)(kGridCells + 1) * 4 + 32; }
+
+/* points the entries of map g can hold together: the sum of their frames' record counts */
+inline uint64_t map_capacity(const uint64_t *frame_n, const uint64_t *map_offs, const int32_t *entry_frame, int g)
+{
+    uint64_t cap = 0;
+    for (uint64_t e = map_offs[g]; e < map_offs[g + 1]; ++e) cap += frame_n[entry_frame[e]];
+    return cap;
+}
+
+/* frame f = frame_n[f] records at frame_off[f]; map g owns entries [map_offs[g], map_offs[g + 1]); entry e names frame
+ * entry_frame[e] and the matrix at entry_pose + 12 * e; match m registers frame query[m] against map match_map[m] (all
+ * indices checked by the caller).  cap_bytes: the group cap. */
+inline Plan plan_call(int n_frames, const uint64_t *frame_off, const uint64_t *frame_n, int n_maps, const uint64_t *map_offs,
+                      const int32_t *entry_frame, const float *entry_pose, int n_matches, const int32_t *query,
+                      const int32_t *match_map, uint64_t cap_bytes)
+{
+    Plan p;
+    std::vector<int32_t> slot_of((size_t)std::max(n_frames, 0), -1), used((size_t)std::max(n_maps, 0), -1);
+    auto slot = [&](int f) -> uint32_t {
+        if (slot_of[f] < 0) {
+            slot_of[f] = (int32_t)p.slots.size();
+            p.slots.push_back(Slot{frame_off[f], (uint32_t)frame_n[f], 0u});
+            p.slot_frame.push_back(f);
+            p.Pn = std::max(p.Pn, (size_t)frame_n[f]);
+        }
+        return (uint32_t)slot_of[f];
+    };
+    /* slots in the order of first appearance; which maps are used */
+    for (int m = 0; m < n_matches; ++m) {
+        slot(query[m]);
+        const int g = match_map[m];
+        if (used[g] >= 0) continue;
+        used[g] = 0;
+        for (uint64_t e = map_offs[g]; e < map_offs[g + 1]; ++e) slot(entry_frame[e]);
+    }
+    /* the used maps, ascending, their entries in map order */
+    for (int g = 0; g < n_maps; ++g) {
+        if (used[g] < 0) continue;
+        used[g] = (int32_t)p.maps.size();
+        Map mp{0u, (uint32_t)p.entries.size(), (uint32_t)(map_offs[g + 1] - map_offs[g])};
+        for (uint64_t e = map_offs[g]; e < map_offs[g + 1]; ++e) {
+            Entry en;
+            memcpy(en.m, entry_pose + 12 * (size_t)e, sizeof en.m);
+            en.slot = (uint32_t)slot_of[entry_frame[e]];
+            en.pad[0] = en.pad[1] = en.pad[2] = 0u;
+            p.entries.push_back(en);
+        }
+        p.maps.push_back(mp);
+        p.map_id.push_back(g);
+        p.map_cap.push_back(map_capacity(frame_n, map_offs, entry_frame, g));
+    }
+    /* the problems: by map, the call's order among equal maps */
+    std::vector<uint64_t> keys((size_t)std::max(n_matches, 0));
+    for (int m = 0; m < n_matches; ++m) keys[(size_t)m] = (uint64_t)(uint32_t)used[match_map[m]] << 32 | (uint32_t)m;
+    std::sort(keys.begin(), keys.end());
+    for (uint64_t k : keys) {
+        const uint32_t m = (uint32_t)k;
+        p.probs.push_back(Problem{(uint32_t)slot_of[query[m]], (uint32_t)(k >> 32), m, 0u});
+    }
+    /* the groups */
+    size_t pr = 0;
+    for (uint32_t u = 0; u < (uint32_t)p.maps.size();) {
+        Group g;
+        g.map0 = u;
+        g.prob0 = (uint32_t)pr;
+        while (u < (uint32_t)p.maps.size()) {
+            const uint64_t b = map_bytes(p.map_cap[u]);
+            if (g.n_maps > 0 && g.bytes + b > cap_bytes) break;
+            p.maps[u].pt0 = g.pts;
+            g.pts += p.map_cap[u];
+            g.bytes += b;
+            ++g.n_maps;
+            ++u;
+        }
+        while (pr < p.probs.size() && p.probs[pr].map < u) ++pr;
+        g.n_probs = (uint32_t)pr - g.prob0;
+        p.max_group_pts = std::max(p.max_group_pts, g.pts);
+        p.max_group_maps = std::max(p.max_group_maps, g.n_maps);
+        p.groups.push_back(g);
+    }
+    return p;
+}
+
+} /* namespace bevsubreg */
+
+#endif /* BEV_SUBMAP_REG_PLAN_H */

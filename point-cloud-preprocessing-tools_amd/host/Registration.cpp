@@ -3,6 +3,7 @@
 #include "Registration.h"
 
 #include <algorithm>
+#include <cmath>
 #include <string>
 
 #include <hip/hip_runtime_api.h>
@@ -287,4 +288,34 @@ std::vector<IcpAlignResult> fineRegisterMatches(const std::vector<pcl::PointClou
     release();
     for (size_t m = 0; m < matches.size(); ++m) out[m] = to_align_result(res[m]);
     return out;
+}
+
+/* (diff_xy, diff_yaw) of a successful match (BatchTopPartRegistration.cpp:512-527), in float with the host libm */
+void icpPrecisionReport(const float *Tf, const float *Tc, float &diff_xy, float &diff_yaw)
+{
+    const float dx = Tf[3] - Tc[3], dy = Tf[7] - Tc[7];
+    diff_xy = std::sqrt(dx * dx + dy * dy);
+    float m[9], c[9];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            m[i * 3 + j] = Tf[i * 4 + j];
+            c[i * 3 + j] = Tc[i * 4 + j];
+        }
+    /* Eigen's cofactor inverse of a 3 x 3: result(r, k) = cofactor(k, r) / det */
+    auto cof = [&](int i, int j) {
+        const int i1 = (i + 1) % 3, i2 = (i + 2) % 3, j1 = (j + 1) % 3, j2 = (j + 2) % 3;
+        return m[i1 * 3 + j1] * m[i2 * 3 + j2] - m[i1 * 3 + j2] * m[i2 * 3 + j1];
+    };
+    const float c00 = cof(0, 0), c10 = cof(1, 0), c20 = cof(2, 0);
+    const float det = (c00 * m[0] + c10 * m[3]) + c20 * m[6];
+    const float inv = 1.0f / det;
+    const float Ri[9] = {c00 * inv, c10 * inv, c20 * inv, cof(0, 1) * inv, cof(1, 1) * inv,
+                         cof(2, 1) * inv, cof(0, 2) * inv, cof(1, 2) * inv, cof(2, 2) * inv};
+    std::array<float, 9> rel;
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) rel[i * 3 + j] = (Ri[i * 3] * c[j] + Ri[i * 3 + 1] * c[3 + j]) + Ri[i * 3 + 2] * c[6 + j];
+    const std::array<float, 3> e = rotationMatrixToEulerAngles(rel);
+    diff_yaw = e[2] / M_PI * 180.0f;
+    if (diff_yaw > 180.0f) diff_yaw -= 360.0f;
+    if (diff_yaw < -180.0f) diff_yaw += 360.0f;
 }

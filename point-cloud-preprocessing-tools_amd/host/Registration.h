@@ -133,4 +133,8 @@ std::vector<IcpAlignResult> fineRegisterMatches(const std::vector<pcl::PointClou
 /* rotationMatrixToEulerAngles (:290-309) on a row-major 3 x 3, in float with the host libm: (x, y, z) */
 std::array<float, 3> rotationMatrixToEulerAngles(const std::array<float, 9> &R);
 
+/* (diff_xy, diff_yaw) of a successful match's report line (BatchTopPartRegistration.cpp:512-527): the fine transform Tf
+ * against the transform Tc it started from (row-major 4 x 4), in float with the host libm */
+void icpPrecisionReport(const float *Tf, const float *Tc, float &diff_xy, float &diff_yaw);
+
 #endif

@@ -62,36 +62,6 @@ std::string cloud_path(const std::string &dir, int idx)
     return (!dir.empty() && dir.back() == '/') ? dir + name : dir + "/" + name;
 }
 
-/* (diff_xy, diff_yaw) of a successful match (BatchTopPartRegistration.cpp:512-527), in float with the host libm */
-void report_line(const float *Tf, const float *Tc, float &diff_xy, float &diff_yaw)
-{
-    const float dx = Tf[3] - Tc[3], dy = Tf[7] - Tc[7];
-    diff_xy = std::sqrt(dx * dx + dy * dy);
-    float m[9], c[9];
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) {
-            m[i * 3 + j] = Tf[i * 4 + j];
-            c[i * 3 + j] = Tc[i * 4 + j];
-        }
-    /* Eigen's cofactor inverse of a 3 x 3: result(r, k) = cofactor(k, r) / det */
-    auto cof = [&](int i, int j) {
-        const int i1 = (i + 1) % 3, i2 = (i + 2) % 3, j1 = (j + 1) % 3, j2 = (j + 2) % 3;
-        return m[i1 * 3 + j1] * m[i2 * 3 + j2] - m[i1 * 3 + j2] * m[i2 * 3 + j1];
-    };
-    const float c00 = cof(0, 0), c10 = cof(1, 0), c20 = cof(2, 0);
-    const float det = (c00 * m[0] + c10 * m[3]) + c20 * m[6];
-    const float inv = 1.0f / det;
-    const float Ri[9] = {c00 * inv, c10 * inv, c20 * inv, cof(0, 1) * inv, cof(1, 1) * inv,
-                         cof(2, 1) * inv, cof(0, 2) * inv, cof(1, 2) * inv, cof(2, 2) * inv};
-    std::array<float, 9> rel;
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) rel[i * 3 + j] = (Ri[i * 3] * c[j] + Ri[i * 3 + 1] * c[3 + j]) + Ri[i * 3 + 2] * c[6 + j];
-    const std::array<float, 3> e = rotationMatrixToEulerAngles(rel);
-    diff_yaw = e[2] / M_PI * 180.0f;
-    if (diff_yaw > 180.0f) diff_yaw -= 360.0f;
-    if (diff_yaw < -180.0f) diff_yaw += 360.0f;
-}
-
 } // namespace
 
 int main(int argc, char **argv)
@@ -211,7 +181,7 @@ int main(int argc, char **argv)
             ++count_success;
             if (!BEV_WHOLE_TOOL) {
                 float xy, yaw;
-                report_line(fine[k].T, coarse[2 * k + (best[k] ? 1 : 0)].T, xy, yaw);
+                icpPrecisionReport(fine[k].T, coarse[2 * k + (best[k] ? 1 : 0)].T, xy, yaw);
                 report << xy << " " << yaw << "\n";
             }
         }

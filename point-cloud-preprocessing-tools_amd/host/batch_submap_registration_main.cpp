@@ -1,0 +1,183 @@
+/*
+ * batch_submap_registration <match_result_text_file> <keyframes_root_dir> <half_window> [<chunk>]
+ *
+ * Scan-to-map registration: batch_whole_registration with a LOCAL MAP as every match's target.  The match list
+ * is batch_whole_registration's ("query match yaw" per line); the indices name the sorted files of
+ * <root>/non_ground_point_cloud/, and row j of <root>/keyframe_pose.csv is file j's pose — what batch_submap_bev_gen and
+ * batch_submap_cloud_manip read.  The map of match (q, m) holds the files j in [m - half_window, m + half_window], clipped to
+ * the files, in ascending order, each under T_m^-1 T_j (submapwin::relativePose; j == m gets the exact identity); the query's
+ * voxel cloud is registered against the map's moved voxel clouds from the yaw guess, with the whole tool's settings
+ * (bev_icp_whole_defaults), by bev_submap_registration_device_resident.  half_window 0 is batch_whole_registration.
+ *
+ * Bookkeeping, summary line and [TIME] line are batch_whole_registration's (a match fails when its fitness exceeds 1.5); like
+ * that tool it creates icp_precision_report_3d_icp_directly.txt in the working directory and writes nothing to it.  Beside
+ * it, icp_precision_report_submap.txt gets one "diff_xy diff_yaw" line per successful match: the final transform against the
+ * yaw guess it started from (the top-part tool's report arithmetic).  What the pose reader says goes to stderr: stdout is
+ * batch_whole_registration's.  The matches go in chunks of consecutive matches
+ * naming at most <chunk> distinct files (default 256, at least 2 * half_window + 2; the results do not depend on it).  Wrong
+ * arguments, an unreadable match list or pose file, an index outside the files or an unreadable cloud exit 1.
+ */
+#include <chrono>
+#include <cstdio>
+#include <fstream>
+#include <iostream>
+#include <map>
+#include <vector>
+
+#include <hip/hip_runtime_api.h>
+
+#include "../csrc/bev_libm_f64.h"
+#include "Registration.h"
+#include "SubmapWindows.h"
+
+bev_ctx_t *bevhost_context(); /* BatchMultiBevGen.cpp (host) */
+
+namespace {
+
+void hip_or_die(hipError_t e, const char *what)
+{
+    if (e != hipSuccess) {
+        std::cerr << what << ": " << hipGetErrorString(e) << "\n";
+        std::exit(2);
+    }
+}
+
+} // namespace
+
+int main(int argc, char **argv)
+{
+    if (argc < 4) {
+        std::cerr << "Usage: batch_submap_registration <match_result_text_file> <keyframes_root_dir> <half_window> [<chunk>]\n";
+        return 1;
+    }
+    std::string root(argv[2]);
+    if (root.empty() || root.back() != '/') root.append("/");
+    long half = 0, chunk = 256;
+    if (!submapwin::parseCount(argv[3], 0, &half)) {
+        std::cerr << "half_window '" << argv[3] << "': expected an integer >= 0\n";
+        return 1;
+    }
+    if (argc > 4 && !submapwin::parseCount(argv[4], 2 * half + 2, &chunk)) {
+        std::cerr << "chunk '" << argv[4] << "': expected an integer >= 2 * half_window + 2\n";
+        return 1;
+    }
+    chunk = std::max(chunk, 2 * half + 2);
+    std::ofstream report("./icp_precision_report_3d_icp_directly.txt"), submap_report("./icp_precision_report_submap.txt");
+    std::vector<MatchResult> matches;
+    try {
+        matches = loadMatchResults(argv[1]);
+    } catch (const std::exception &e) {
+        std::cerr << e.what() << "\n";
+        return 1;
+    }
+    std::vector<std::string> files;
+    getPcdFileNames(root + "non_ground_point_cloud/", files);
+    bool ok = false;
+    std::streambuf *const out = std::cout.rdbuf(std::cerr.rdbuf()); /* the reader's chatter: off stdout, which is the whole tool's */
+    const std::vector<Pose6f> pose = readKeyframePose(root + "keyframe_pose.csv", &ok);
+    std::cout.rdbuf(out);
+    if (!ok || pose.size() < files.size()) {
+        std::cerr << "pose file " << root << "keyframe_pose.csv: can not be read, or fewer rows than clouds\n";
+        return 1;
+    }
+    const long n_files = (long)files.size();
+    for (const MatchResult &mt : matches)
+        if (mt.query_idx < 0 || mt.query_idx >= n_files || mt.match_idx < 0 || mt.match_idx >= n_files) {
+            std::cerr << "match " << mt.query_idx << " " << mt.match_idx << ": outside the " << n_files << " clouds\n";
+            return 1;
+        }
+    sensor_params_ = getSensorParams(parseSensorType("HDL_64E")); /* (the context follows a sensor; packed clouds read none) */
+    const bev_icp_params_t prm = bev_icp_whole_defaults();
+    double t_fine = 0.0;
+    int count_success = 0, count_failure = 0;
+    using clk = std::chrono::steady_clock;
+
+    for (size_t m0 = 0; m0 < matches.size();) {
+        /* the chunk: consecutive matches whose queries and windows name at most `chunk` distinct files */
+        std::map<long, int> local;
+        size_t m1 = m0;
+        while (m1 < matches.size()) {
+            const long q = matches[m1].query_idx, m = matches[m1].match_idx;
+            std::vector<long> add;
+            if (!local.count(q)) add.push_back(q);
+            for (long j = std::max(0L, m - half); j <= std::min(n_files - 1, m + half); ++j)
+                if (!local.count(j) && j != q) add.push_back(j);
+            if ((long)(local.size() + add.size()) > chunk) break;
+            for (long f : add) local.emplace(f, (int)local.size());
+            ++m1;
+        }
+        const int F = (int)local.size();
+        std::vector<long> file_of(F);
+        for (const auto &kv : local) file_of[kv.second] = kv.first;
+        std::vector<uint64_t> offs(F + 1, 0);
+        std::vector<pcl::PointCloud<pcl::PointXYZIRCT>> clouds(F);
+        for (int f = 0; f < F; ++f) {
+            if (bevio::loadPCDFile(files[file_of[f]], clouds[f]) != 0) {
+                std::cerr << "Cloud NOT load file: " << files[file_of[f]] << "\n";
+                return 1;
+            }
+            offs[f + 1] = offs[f] + clouds[f].points.size();
+        }
+        bev_ctx_t *ctx = bevhost_context();
+        if (!ctx) return 2;
+        /* one map per match (two matches of one key frame get two equal maps) */
+        const size_t n = m1 - m0;
+        std::vector<bev_match_t> cm(n);
+        std::vector<uint64_t> map_offs(1, 0);
+        std::vector<int32_t> entry_frame;
+        std::vector<float> entry_pose;
+        for (size_t k = 0; k < n; ++k) {
+            const long m = matches[m0 + k].match_idx;
+            cm[k] = bev_match_t{local[matches[m0 + k].query_idx], (int32_t)k, matches[m0 + k].angle_guess};
+            for (long j = std::max(0L, m - half); j <= std::min(n_files - 1, m + half); ++j) {
+                entry_frame.push_back(local[j]);
+                entry_pose.resize(entry_pose.size() + 12);
+                float *mat = entry_pose.data() + entry_pose.size() - 12;
+                if (j == m) bev_yaw_translate_matrix(0.0f, 0.0f, 0.0f, 0.0f, mat); /* the exact identity */
+                else submapwin::relativePose(pose[m], pose[j], mat);
+            }
+            map_offs.push_back(entry_frame.size());
+        }
+        auto t0 = clk::now();
+        void *d_pts = nullptr, *d_fine = nullptr;
+        hip_or_die(hipMalloc(&d_pts, std::max<uint64_t>(offs[F], 1) * sizeof(bev_point_t)), "hipMalloc");
+        for (int f = 0; f < F; ++f)
+            if (!clouds[f].points.empty())
+                hip_or_die(hipMemcpy(static_cast<bev_point_t *>(d_pts) + offs[f], clouds[f].points.data(),
+                                     clouds[f].points.size() * sizeof(bev_point_t), hipMemcpyHostToDevice),
+                           "hipMemcpy");
+        hip_or_die(hipMalloc(&d_fine, n * sizeof(bev_icp_result_t)), "hipMalloc");
+        int rc = bev_submap_registration_device_resident(ctx, F, static_cast<bev_point_t *>(d_pts), offs.data(), 0.2f, (int)n,
+                                                         map_offs.data(), entry_frame.data(), entry_pose.data(), (int)n, cm.data(),
+                                                         nullptr, nullptr, &prm, static_cast<bev_icp_result_t *>(d_fine));
+        if (rc == BEV_OK) rc = bev_synchronize(ctx);
+        if (rc != BEV_OK) {
+            std::cerr << "bev_submap_registration_device_resident: " << bev_strerror(rc) << " " << bev_last_error(ctx) << "\n";
+            return 2;
+        }
+        t_fine += std::chrono::duration<double, std::milli>(clk::now() - t0).count();
+        std::vector<bev_icp_result_t> fine(n);
+        hip_or_die(hipMemcpy(fine.data(), d_fine, n * sizeof(bev_icp_result_t), hipMemcpyDeviceToHost), "hipMemcpy");
+        (void)hipFree(d_pts);
+        (void)hipFree(d_fine);
+        for (size_t k = 0; k < n; ++k) {
+            if (fine[k].fitness > 1.5f) {
+                ++count_failure;
+                continue;
+            }
+            ++count_success;
+            float guess[16], xy, yaw;
+            bevx::icp_tool_guess(cm[k].angle_guess, 0, guess);
+            icpPrecisionReport(fine[k].T, guess, xy, yaw);
+            submap_report << xy << " " << yaw << "\n";
+        }
+        m0 = m1;
+    }
+    t_fine /= matches.size();
+    std::cout << "[TIME] Avg Tiempo for 2nd Stage (fine): " << t_fine << "\n";
+    std::cout << "count_success: " << count_success << ", count_failure: " << count_failure
+              << ", SR: " << (1.0f * count_success) / (count_success + count_failure) << ". \n";
+    report.close();
+    submap_report.close();
+    return 0;
+}
