@@ -598,6 +598,53 @@ int bev_submap_registration_batch(bev_ctx_t *ctx, int n_frames, const bev_point_
                                   const float *h_entry_pose, int n_matches, const bev_match_t *h_matches,
                                   const bev_icp_params_t *params, bev_icp_result_t *results);
 
+/* ---- scan-to-map fine ICP against THINNED maps: a voxel grid over the union ----------------------------------------------
+ * bev_submap_registration_device_resident with a second leaf size.  With
+ *   concat(g) = bev_submap_registration_device_resident's target(g) (above), and map_leaf > 0:
+ *   target(g) = bev_voxel_grid_irct(concat(g), map_leaf), of which only x, y, z are ever read;
+ *   result(m) = bev_icp_point_to_point(bev_voxel_grid_irct(frame query_idx, leaf), target(match_idx), guess, params),
+ * bit for bit as a whole bev_icp_result_t.  So the target's points are in ascending voxel index of the UNION's grid, whose
+ * bounds and divisions come from the finite points of concat(g); a centroid is the float sum of its voxel's points IN
+ * CONCATENATION ORDER divided by float(n), without FMA; non-finite points of concat(g) (a matrix that overflows, NaN records
+ * that a frame's own "leaf too small" branch copied) are dropped.  When the union's grid would have more than INT32_MAX voxels,
+ * target(g) is concat(g) unchanged: non-finite points then keep their index and stay unsearchable.  The search's "lowest index
+ * on ties" is over the thinned target's index; the order of a map's entries matters only through the order of the sums inside a
+ * voxel.  An empty map, or one whose union has no finite point, ends as above: BEV_ICP_NO_CORRESPONDENCES, fitness DBL_MAX.
+ * map_leaf == 0     : no second grid: bev_submap_registration_device_resident itself, byte for byte (that function is this
+ *                     one with map_leaf = 0).
+ * map_leaf < 0, NaN, infinite : BEV_ERR_INVALID_ARG.
+ * Every other argument, status and bound, and the ordering, are bev_submap_registration_device_resident's; a refused call
+ * launches nothing and leaves d_results untouched.
+ * Workspace : with map_leaf > 0 a launch group also holds the concatenations, the padded sort keys, the voxel starts and a
+ *             header per map: with T, M as above and K' the sum over the group's maps of the smallest power of two >= the map's
+ *             capacity (0 for capacity 0), the formula above plus
+ *               16 T + 8 K' + 4 (T + M) + 32 M
+ *             bytes (pieces rounded up to 256), and 8 bytes per map in the tables.  The launch groups are cut so that
+ *             48 T + 8 K' + 4 (T + M) + M * (4 * 16385 + 64) fits the cap.  The sort runs in tiles of 4096 keys per workgroup. */
+int bev_submap_voxel_registration_device_resident(bev_ctx_t *ctx, int n_frames, const bev_point_t *d_clouds,
+                                                  const uint64_t *h_offsets, float leaf, float map_leaf, int n_maps,
+                                                  const uint64_t *h_map_offsets, const int32_t *h_entry_frame,
+                                                  const float *h_entry_pose, int n_matches, const bev_match_t *h_matches,
+                                                  const bev_icp_result_t *d_coarse, const int32_t *d_best,
+                                                  const bev_icp_params_t *params, bev_icp_result_t *d_results);
+/* The same through HOST buffers, synchronous, yaw guesses only: bev_submap_registration_batch with map_leaf (that function is
+ * this one with map_leaf = 0). */
+int bev_submap_voxel_registration_batch(bev_ctx_t *ctx, int n_frames, const bev_point_t *const *clouds, const uint32_t *n_pts,
+                                        float leaf, float map_leaf, int n_maps, const uint64_t *h_map_offsets,
+                                        const int32_t *h_entry_frame, const float *h_entry_pose, int n_matches,
+                                        const bev_match_t *h_matches, const bev_icp_params_t *params, bev_icp_result_t *results);
+/* The local maps themselves: target(g) of EVERY map of the call (there are no matches), as PointXYZ records (x, y, z and a
+ * pad of 0, 16 bytes).  Map g's records go to d_out + 4 * g * out_stride floats, its record count to d_counts[g]; records past
+ * the count are not written.  map_leaf == 0 is allowed: concat(g).  Frames, maps, ordering and workspace as above (no ICP
+ * scratch, no search grids).
+ * Status    : as above; also BEV_ERR_INVALID_ARG for NULL d_out or d_counts with n_maps > 0, and for an out_stride (in
+ *             records) smaller than the largest map's capacity (the record counts of its entries' frames together).
+ *             n_maps == 0 returns BEV_OK.  A refused call launches nothing and leaves d_out and d_counts untouched. */
+int bev_submap_voxel_cloud_device_resident(bev_ctx_t *ctx, int n_frames, const bev_point_t *d_clouds, const uint64_t *h_offsets,
+                                           float leaf, float map_leaf, int n_maps, const uint64_t *h_map_offsets,
+                                           const int32_t *h_entry_frame, const float *h_entry_pose, uint64_t out_stride,
+                                           float *d_out, uint32_t *d_counts);
+
 /* ---- layout hint -------------------------------------------------------
  * What the caller knows about how its clouds are laid out, so that the library need not look (k_probe reads every 63rd
  * record of a frame to find out: 0.36 MB and 0.07 us of an HDL_64E frame).  Sticky per context; applies to frames of

@@ -95,6 +95,8 @@ ABI_SYMBOLS = [
     "bev_submap_bev_device_resident", "bev_submap_bev_batch",
     "bev_submap_float_bev_device_resident", "bev_submap_float_bev_batch",
     "bev_submap_registration_device_resident", "bev_submap_registration_batch",
+    "bev_submap_voxel_registration_device_resident", "bev_submap_voxel_registration_batch",
+    "bev_submap_voxel_cloud_device_resident",
 ]
 
 # registration front end (include/bev_mi355x.h): pcl::PointXYZ, pcl::Normal, pcl::PointNormal as float rows
@@ -235,6 +237,14 @@ def load_lib() -> C.CDLL:
                                                                 C.POINTER(IcpParams), vp]
         lib.bev_submap_registration_batch.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(u32), C.c_float, i32,
                                                       C.POINTER(C.c_uint64), vp, vp, i32, vp, C.POINTER(IcpParams), vp]
+    if hasattr(lib, "bev_submap_voxel_registration_device_resident"):
+        lib.bev_submap_voxel_registration_device_resident.argtypes = [vp, i32, vp, C.POINTER(C.c_uint64), C.c_float, C.c_float,
+                                                                      i32, C.POINTER(C.c_uint64), vp, vp, i32, vp, vp, vp,
+                                                                      C.POINTER(IcpParams), vp]
+        lib.bev_submap_voxel_registration_batch.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(u32), C.c_float, C.c_float, i32,
+                                                            C.POINTER(C.c_uint64), vp, vp, i32, vp, C.POINTER(IcpParams), vp]
+        lib.bev_submap_voxel_cloud_device_resident.argtypes = [vp, i32, vp, C.POINTER(C.c_uint64), C.c_float, C.c_float, i32,
+                                                               C.POINTER(C.c_uint64), vp, vp, C.c_uint64, vp, vp]
     _lib = lib
     return lib
 
@@ -738,6 +748,49 @@ class BevContext:
             _ptr(entry_frame), _ptr(entry_pose), len(m), _ptr(m) if len(m) else None, C.byref(prm),
             _ptr(res) if len(m) else None), "bev_submap_registration_batch")
         return res
+
+    # ---- the same against maps thinned by a voxel grid over their union --------------------------------
+    def submap_voxel_registration_device(self, n_frames, d_clouds, offsets, map_offsets, entry_frame, entry_pose, matches,
+                                         d_results, map_leaf, d_coarse=None, d_best=None, leaf=0.2,
+                                         params: IcpParams | None = None):
+        """bev_submap_voxel_registration_device_resident: submap_registration_device with every map's concatenation thinned
+        by a voxel grid of map_leaf over the union (map_leaf 0: no second grid, submap_registration_device's bytes)."""
+        offsets, offs = _offsets(offsets, n_frames) if offsets is not None else (None, None)
+        n_maps, map_offsets, entry_frame, entry_pose = self._submap_entries(map_offsets, entry_frame, entry_pose)
+        m = np.ascontiguousarray(matches, dtype=MATCH_DTYPE)
+        prm = params if params is not None else icp_fine_defaults()
+        self._check(self.lib.bev_submap_voxel_registration_device_resident(
+            self._h, n_frames, C.c_void_p(d_clouds or None), offs, leaf, map_leaf, n_maps,
+            map_offsets.ctypes.data_as(C.POINTER(C.c_uint64)), _ptr(entry_frame), _ptr(entry_pose), len(m),
+            _ptr(m) if len(m) else None, C.c_void_p(d_coarse) if d_coarse else None, C.c_void_p(d_best) if d_best else None,
+            C.byref(prm), C.c_void_p(d_results or None)), "bev_submap_voxel_registration_device_resident")
+
+    def submap_voxel_registration_batch(self, clouds, map_offsets, entry_frame, entry_pose, matches, map_leaf, leaf=0.2,
+                                        params: IcpParams | None = None):
+        """bev_submap_voxel_registration_batch on host clouds (yaw guesses): submap_registration_batch with map_leaf.
+        Returns (n_matches,) ICP_RESULT_DTYPE."""
+        clouds, pts, npts = _host_clouds(clouds)
+        n_maps, map_offsets, entry_frame, entry_pose = self._submap_entries(map_offsets, entry_frame, entry_pose)
+        m = np.array([tuple(r) for r in matches], dtype=MATCH_DTYPE) if not isinstance(matches, np.ndarray) else \
+            np.ascontiguousarray(matches, dtype=MATCH_DTYPE)
+        prm = params if params is not None else icp_fine_defaults()
+        res = np.zeros(len(m), dtype=ICP_RESULT_DTYPE)
+        self._check(self.lib.bev_submap_voxel_registration_batch(
+            self._h, len(clouds), pts, npts, leaf, map_leaf, n_maps, map_offsets.ctypes.data_as(C.POINTER(C.c_uint64)),
+            _ptr(entry_frame), _ptr(entry_pose), len(m), _ptr(m) if len(m) else None, C.byref(prm),
+            _ptr(res) if len(m) else None), "bev_submap_voxel_registration_batch")
+        return res
+
+    def submap_voxel_cloud_device(self, n_frames, d_clouds, offsets, map_offsets, entry_frame, entry_pose, map_leaf,
+                                  out_stride, d_out, d_counts, leaf=0.2):
+        """bev_submap_voxel_cloud_device_resident: every map's target (map_leaf 0: the concatenation) as x, y, z, 0 float
+        rows at d_out + 16 * g * out_stride bytes, its row count at d_counts[g] (uint32).  Asynchronous."""
+        offsets, offs = _offsets(offsets, n_frames) if offsets is not None else (None, None)
+        n_maps, map_offsets, entry_frame, entry_pose = self._submap_entries(map_offsets, entry_frame, entry_pose)
+        self._check(self.lib.bev_submap_voxel_cloud_device_resident(
+            self._h, n_frames, C.c_void_p(d_clouds or None), offs, leaf, map_leaf, n_maps,
+            map_offsets.ctypes.data_as(C.POINTER(C.c_uint64)), _ptr(entry_frame), _ptr(entry_pose), int(out_stride),
+            C.c_void_p(d_out or None), C.c_void_p(d_counts or None)), "bev_submap_voxel_cloud_device_resident")
 
     def set_layout_hint(self, layout: int):
         """LAYOUT_UNKNOWN (the library looks), LAYOUT_STRUCTURED, LAYOUT_FIRING_ORDER: include/bev_mi355x.h"""

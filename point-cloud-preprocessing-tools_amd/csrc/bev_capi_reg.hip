@@ -1,9 +1,9 @@
 /*
  * bev_capi_reg.hip — the registration half of the extern "C" boundary declared in include/bev_mi355x.h: the front end
  * (top-part flatten, voxel grid, 2-D normals), coarse point-to-plane ICP (§6c), the fine stage (§6d) and
- * scan-to-map fine ICP (§6k).
+ * scan-to-map fine ICP (§6k), with the voxel grid over a map's union in front of it (§6l).
  * Host-side only; the kernels are in bev_kernels.hip (bev_reg_common.h, bev_regfront.h, bev_icp.h, bev_fine.h,
- * bev_submap_reg.h).  With
+ * bev_submap_reg.h, bev_submap_vox.h).  With
  * the BEV pipeline of bev_capi.hip it shares the context (bev_ctx.h), its stream and the call prologue (begin_call).
  */
 #include <algorithm>
@@ -615,14 +615,23 @@ static int submap_reg_check(int n_frames, const std::vector<uint64_t> &frame_n, 
     return BEV_OK;
 }
 
+/* the cloud call's outputs (bev_submap_voxel_cloud_device_resident) */
+struct SubmapCloudOut {
+    float4 *d_out;
+    uint64_t stride;
+    uint32_t *d_counts;
+};
+
 /* The call on the context's stream, behind the entries' checks and begin_call: frame f = frame_n[f] records at frame_off[f]
- * of d_clouds. */
+ * of d_clouds.  map_leaf > 0: the maps are thinned by a voxel grid over their union (bev_submap_vox.h);
+ * map_leaf == 0 with matches: §6k's launches and workspace, unchanged.  cloud: no matches; every map's target goes out. */
 static int submap_reg_frames(bev_ctx *c, int n_frames, const bev_point_t *d_clouds, const std::vector<uint64_t> &frame_off,
-                      const std::vector<uint64_t> &frame_n, float leaf, int n_maps, const uint64_t *map_offs,
+                      const std::vector<uint64_t> &frame_n, float leaf, float map_leaf, int n_maps, const uint64_t *map_offs,
                       const int32_t *entry_frame, const float *entry_pose, int n_matches, const bev_match_t *h_matches,
                       const bev_icp_result_t *d_coarse, const int32_t *d_best, const bev_icp_params_t &prm,
-                      bev_icp_result_t *d_results)
+                      bev_icp_result_t *d_results, const SubmapCloudOut *cloud)
 {
+    const bool vox = map_leaf > 0.0f, staged = vox || cloud; /* staged: the moved points get an array of their own */
     std::vector<int32_t> query((size_t)n_matches), match_map((size_t)n_matches);
     for (int m = 0; m < n_matches; ++m) {
         query[(size_t)m] = h_matches[m].query_idx;
@@ -630,36 +639,48 @@ static int submap_reg_frames(bev_ctx *c, int n_frames, const bev_point_t *d_clou
     }
     const uint64_t cap = c->submap_reg_group ? (uint64_t)c->submap_reg_group : kSubmapRegCap;
     const bevsubreg::Plan plan = bevsubreg::plan_call(n_frames, frame_off.data(), frame_n.data(), n_maps, map_offs, entry_frame,
-                                                      entry_pose, n_matches, query.data(), match_map.data(), cap);
+                                                      entry_pose, n_matches, query.data(), match_map.data(), cap, vox,
+                                                      cloud != nullptr);
     const size_t U = plan.slots.size(), P = plan.probs.size(), E = plan.entries.size(), Pn = plan.Pn, Kn = pow2_at_least(Pn);
     const size_t G = std::min(U, (size_t)kFineVoxelGroup), L = std::min(P, (size_t)kFineProblemsPerLaunch);
     const size_t T = std::max<size_t>((size_t)plan.max_group_pts, 1), M = std::max<size_t>(plan.max_group_maps, 1);
+    const size_t NM = plan.maps.size();
     /* the workspace: the voxel clouds of the slots (no grids: no frame is a target), the scratch of a voxel launch and of an
-     * ICP launch, the entries' first indices, the maps of one launch group */
+     * ICP launch, the entries' first indices, the maps of one launch group; staged: the concatenations; vox: the union
+     * grid's keys, voxel starts and headers (t.pts is then the thinned array) */
     FineWork w{};
     SubmapRegWork t{};
+    SubmapVoxWork v{};
     uint32_t *ent_start = nullptr;
+    const bool grid = !cloud, thin = !cloud || vox;
     const size_t sz[] = {U * Pn * sizeof(bev_point_t), U * 4, G * Kn * 8, G * (Pn + 1) * 4, L * Pn * 16, L * Pn * 4,
-                         std::max<size_t>(E, 1) * 4, T * 16, T * 16, M * sizeof(IcpGridHdr), M * 4 * (size_t)(kFineCells + 1)};
+                         std::max<size_t>(E, 1) * 4, thin ? T * 16 : 0, grid ? T * 16 : 0, grid ? M * sizeof(IcpGridHdr) : 0,
+                         grid ? M * 4 * (size_t)(kFineCells + 1) : 0, staged ? T * 16 : 0,
+                         vox ? std::max<size_t>((size_t)plan.max_group_keys, 1) * 8 : 0, vox ? (T + M) * 4 : 0,
+                         staged ? M * sizeof(SubvoxHdr) : 0};
     void **const dst[] = {(void **)&w.vox, (void **)&w.vox_n, (void **)&w.keys, (void **)&w.vstart, (void **)&w.cur,
                           (void **)&w.corr, (void **)&ent_start, (void **)&t.pts, (void **)&t.sorted, (void **)&t.hdr,
-                          (void **)&t.cell_off};
+                          (void **)&t.cell_off, (void **)&v.moved, (void **)&v.keys, (void **)&v.vstart, (void **)&v.vh};
     int rc = c->reg.fine_buf.grow(c, carve(nullptr, sz, dst));
     if (rc != BEV_OK) return rc;
     carve(c->reg.fine_buf.p, sz, dst);
+    if (!grid) t.sorted = nullptr, t.hdr = nullptr, t.cell_off = nullptr; /* (k_submap_vox_finish builds no grid) */
     w.Pn = Pn;
     w.Kn = Kn;
-    /* the tables, one block: slots, maps, entries (64-byte aligned), problems */
+    /* the tables, one block: slots, maps, entries (64-byte aligned), problems; vox: the maps' first keys behind them */
     static_assert(sizeof(bevsubreg::Slot) == sizeof(FineSlot), "the plan's slots are k_fine_voxel's");
-    const size_t o_maps = align256(U * sizeof(FineSlot)), o_ent = o_maps + align256(plan.maps.size() * sizeof(bevsubreg::Map)),
-                 o_probs = o_ent + align256(E * sizeof(bevsubreg::Entry)), tab = o_probs + P * sizeof(FineProblem);
+    const size_t o_maps = align256(U * sizeof(FineSlot)), o_ent = o_maps + align256(NM * sizeof(bevsubreg::Map)),
+                 o_probs = o_ent + align256(E * sizeof(bevsubreg::Entry)),
+                 o_key0 = vox ? o_probs + align256(P * sizeof(FineProblem)) : 0,
+                 tab = vox ? o_key0 + NM * 8 : o_probs + P * sizeof(FineProblem);
     void *hv;
     rc = c->reg.fine_tab.begin(c, tab, kRegTabMin, &hv);
     if (rc != BEV_OK) return rc;
     char *h = static_cast<char *>(hv);
     if (U) std::memcpy(h, plan.slots.data(), U * sizeof(FineSlot));
-    if (!plan.maps.empty()) std::memcpy(h + o_maps, plan.maps.data(), plan.maps.size() * sizeof(bevsubreg::Map));
+    if (NM) std::memcpy(h + o_maps, plan.maps.data(), NM * sizeof(bevsubreg::Map));
     if (E) std::memcpy(h + o_ent, plan.entries.data(), E * sizeof(bevsubreg::Entry));
+    if (vox && NM) std::memcpy(h + o_key0, plan.map_key0.data(), NM * 8);
     FineProblem *hp = reinterpret_cast<FineProblem *>(h + o_probs);
     for (size_t k = 0; k < P; ++k) {
         const bevsubreg::Problem &pp = plan.probs[k];
@@ -676,13 +697,41 @@ static int submap_reg_frames(bev_ctx *c, int n_frames, const bev_point_t *d_clou
     const FineSlot *d_slots = reinterpret_cast<const FineSlot *>(dev);
     const void *d_maps = dev + o_maps, *d_entries = dev + o_ent;
     const FineProblem *d_probs = reinterpret_cast<const FineProblem *>(dev + o_probs);
+    v.key0 = vox ? reinterpret_cast<const uint64_t *>(dev + o_key0) : nullptr;
     rc = fine_voxel(c, d_clouds, d_slots, (int)U, w, leaf);
     if (rc != BEV_OK) return rc;
     /* the groups one behind the other on the stream: its order hands the maps' arrays from group to group */
     for (const bevsubreg::Group &g : plan.groups) {
-        {
-            ProfScope ps(c, K_SUBMAP_TARGET, (int)g.n_maps);
-            launch_submap_target(d_maps, g.map0, (int)g.n_maps, d_entries, w, ent_start, t, c->stream);
+        const int gm = (int)g.n_maps;
+        if (!staged) {
+            ProfScope ps(c, K_SUBMAP_TARGET, gm);
+            launch_submap_target(d_maps, g.map0, gm, d_entries, w, ent_start, t, c->stream);
+        } else {
+            {
+                ProfScope ps(c, K_SUBMAP_VOX_MOVE, gm);
+                launch_submap_vox_move(d_maps, g.map0, gm, d_entries, w, ent_start, v, c->stream);
+            }
+            if (vox) {
+                {
+                    ProfScope ps(c, K_SUBMAP_VOX_KEYS, gm);
+                    launch_submap_vox_keys(d_maps, g.map0, gm, v, map_leaf, c->stream);
+                }
+                const uint32_t tiles = bevsubvox::tiles(g.max_slots);
+                for (const bevsubvox::Stage &sg : bevsubvox::schedule(g.max_slots)) {
+                    ProfScope ps(c, sg.kind == bevsubvox::kStageGlobal ? K_SUBMAP_VOX_GLOBAL : K_SUBMAP_VOX_TILE, gm);
+                    launch_submap_vox_stage(sg.kind, sg.k, sg.j, g.map0, gm, tiles, v, c->stream);
+                }
+                ProfScope ps(c, K_SUBMAP_VOX_FINISH, gm);
+                launch_submap_vox_finish(d_maps, g.map0, gm, v, t, c->stream);
+            }
+            if (cloud) {
+                uint64_t largest = 0;
+                for (uint32_t u = g.map0; u < g.map0 + g.n_maps; ++u) largest = std::max(largest, plan.map_cap[u]);
+                const uint32_t parts = (uint32_t)std::min<uint64_t>((largest + 4 * kFineThreads - 1) / (4 * kFineThreads), 256);
+                ProfScope ps(c, K_SUBMAP_VOX_OUT, gm);
+                launch_submap_vox_out(d_maps, g.map0, gm, parts, v.vh, vox ? t.pts : v.moved, cloud->d_out, cloud->stride,
+                                      cloud->d_counts, c->stream);
+            }
         }
         for (uint32_t p0 = 0; p0 < g.n_probs; p0 += kFineProblemsPerLaunch) {
             const int n = (int)std::min<uint32_t>(kFineProblemsPerLaunch, g.n_probs - p0);
@@ -696,15 +745,16 @@ static int submap_reg_frames(bev_ctx *c, int n_frames, const bev_point_t *d_clou
 
 } // namespace
 
-int bev_submap_registration_device_resident(bev_ctx_t *c, int n_frames, const bev_point_t *d_clouds, const uint64_t *h_offsets,
-                                            float leaf, int n_maps, const uint64_t *h_map_offsets, const int32_t *h_entry_frame,
-                                            const float *h_entry_pose, int n_matches, const bev_match_t *h_matches,
-                                            const bev_icp_result_t *d_coarse, const int32_t *d_best,
-                                            const bev_icp_params_t *params, bev_icp_result_t *d_results)
+int bev_submap_voxel_registration_device_resident(bev_ctx_t *c, int n_frames, const bev_point_t *d_clouds,
+                                                  const uint64_t *h_offsets, float leaf, float map_leaf, int n_maps,
+                                                  const uint64_t *h_map_offsets, const int32_t *h_entry_frame,
+                                                  const float *h_entry_pose, int n_matches, const bev_match_t *h_matches,
+                                                  const bev_icp_result_t *d_coarse, const int32_t *d_best,
+                                                  const bev_icp_params_t *params, bev_icp_result_t *d_results)
 {
     const bev_icp_params_t prm = params ? *params : bev_icp_fine_defaults();
     if (!c || n_frames < 0 || n_maps < 0 || n_matches < 0 || !icp_params_ok(prm) || !(std::isfinite(leaf) && leaf > 0.0f) ||
-        (d_coarse == nullptr) != (d_best == nullptr))
+        !(std::isfinite(map_leaf) && map_leaf >= 0.0f) || (d_coarse == nullptr) != (d_best == nullptr))
         return BEV_ERR_INVALID_ARG;
     std::vector<uint64_t> frame_off, frame_n;
     if (n_matches > 0) {
@@ -725,19 +775,66 @@ int bev_submap_registration_device_resident(bev_ctx_t *c, int n_frames, const be
     if (n_matches == 0) return BEV_OK;
     rc = wait_default_stream(c);
     if (rc != BEV_OK) return rc;
-    rc = submap_reg_frames(c, n_frames, d_clouds, frame_off, frame_n, leaf, n_maps, h_map_offsets, h_entry_frame, h_entry_pose,
-                           n_matches, h_matches, d_coarse, d_best, prm, d_results);
+    rc = submap_reg_frames(c, n_frames, d_clouds, frame_off, frame_n, leaf, map_leaf, n_maps, h_map_offsets, h_entry_frame,
+                           h_entry_pose, n_matches, h_matches, d_coarse, d_best, prm, d_results, nullptr);
     if (rc != BEV_OK) return rc;
     return record_tail(c);
 }
 
-int bev_submap_registration_batch(bev_ctx_t *c, int n_frames, const bev_point_t *const *clouds, const uint32_t *n_pts, float leaf,
-                                  int n_maps, const uint64_t *h_map_offsets, const int32_t *h_entry_frame,
-                                  const float *h_entry_pose, int n_matches, const bev_match_t *h_matches,
-                                  const bev_icp_params_t *params, bev_icp_result_t *results)
+int bev_submap_registration_device_resident(bev_ctx_t *c, int n_frames, const bev_point_t *d_clouds, const uint64_t *h_offsets,
+                                            float leaf, int n_maps, const uint64_t *h_map_offsets, const int32_t *h_entry_frame,
+                                            const float *h_entry_pose, int n_matches, const bev_match_t *h_matches,
+                                            const bev_icp_result_t *d_coarse, const int32_t *d_best,
+                                            const bev_icp_params_t *params, bev_icp_result_t *d_results)
+{
+    return bev_submap_voxel_registration_device_resident(c, n_frames, d_clouds, h_offsets, leaf, 0.0f, n_maps, h_map_offsets,
+                                                         h_entry_frame, h_entry_pose, n_matches, h_matches, d_coarse, d_best,
+                                                         params, d_results);
+}
+
+int bev_submap_voxel_cloud_device_resident(bev_ctx_t *c, int n_frames, const bev_point_t *d_clouds, const uint64_t *h_offsets,
+                                           float leaf, float map_leaf, int n_maps, const uint64_t *h_map_offsets,
+                                           const int32_t *h_entry_frame, const float *h_entry_pose, uint64_t out_stride,
+                                           float *d_out, uint32_t *d_counts)
+{
+    if (!c || n_frames < 0 || n_maps < 0 || !(std::isfinite(leaf) && leaf > 0.0f) || !(std::isfinite(map_leaf) && map_leaf >= 0.0f))
+        return BEV_ERR_INVALID_ARG;
+    std::vector<uint64_t> frame_off, frame_n;
+    if (n_maps > 0) {
+        if (!d_out || !d_counts) return BEV_ERR_INVALID_ARG;
+        frame_off.resize((size_t)n_frames);
+        frame_n.resize((size_t)n_frames);
+        for (int f = 0; f < n_frames; ++f) {
+            if (h_offsets && (h_offsets[f + 1] < h_offsets[f] || h_offsets[f + 1] - h_offsets[f] > 0xffffffffull)) return BEV_ERR_INVALID_ARG;
+            frame_off[(size_t)f] = h_offsets ? h_offsets[f] : (uint64_t)f * c->geo.S;
+            frame_n[(size_t)f] = h_offsets ? h_offsets[f + 1] - h_offsets[f] : (uint64_t)c->geo.S;
+        }
+        const int rc_ = submap_reg_check(n_frames, frame_n, n_maps, h_map_offsets, h_entry_frame, h_entry_pose, 0, nullptr);
+        if (rc_ != BEV_OK) return rc_;
+        for (int g = 0; g < n_maps; ++g)
+            if (bevsubreg::map_capacity(frame_n.data(), h_map_offsets, h_entry_frame, g) > out_stride) return BEV_ERR_INVALID_ARG;
+        if (!d_clouds) return BEV_ERR_INVALID_ARG;
+    }
+    int rc = begin_call(c, false);
+    if (rc != BEV_OK) return rc;
+    if (n_maps == 0) return BEV_OK;
+    rc = wait_default_stream(c);
+    if (rc != BEV_OK) return rc;
+    const SubmapCloudOut out{reinterpret_cast<float4 *>(d_out), out_stride, d_counts};
+    rc = submap_reg_frames(c, n_frames, d_clouds, frame_off, frame_n, leaf, map_leaf, n_maps, h_map_offsets, h_entry_frame,
+                           h_entry_pose, 0, nullptr, nullptr, nullptr, bev_icp_fine_defaults(), nullptr, &out);
+    if (rc != BEV_OK) return rc;
+    return record_tail(c);
+}
+
+int bev_submap_voxel_registration_batch(bev_ctx_t *c, int n_frames, const bev_point_t *const *clouds, const uint32_t *n_pts,
+                                        float leaf, float map_leaf, int n_maps, const uint64_t *h_map_offsets,
+                                        const int32_t *h_entry_frame, const float *h_entry_pose, int n_matches,
+                                        const bev_match_t *h_matches, const bev_icp_params_t *params, bev_icp_result_t *results)
 {
     const bev_icp_params_t prm = params ? *params : bev_icp_fine_defaults();
-    if (!c || n_frames < 0 || n_maps < 0 || n_matches < 0 || !icp_params_ok(prm) || !(std::isfinite(leaf) && leaf > 0.0f))
+    if (!c || n_frames < 0 || n_maps < 0 || n_matches < 0 || !icp_params_ok(prm) || !(std::isfinite(leaf) && leaf > 0.0f) ||
+        !(std::isfinite(map_leaf) && map_leaf >= 0.0f))
         return BEV_ERR_INVALID_ARG;
     if (n_frames > 0 && (!clouds || !n_pts)) return BEV_ERR_INVALID_ARG;
     for (int f = 0; f < n_frames; ++f)
@@ -759,12 +856,22 @@ int bev_submap_registration_batch(bev_ctx_t *c, int n_frames, const bev_point_t 
     rc = c->reg.sub_res.grow(c, (size_t)n_matches * sizeof(bev_icp_result_t));
     if (rc != BEV_OK) return rc;
     bev_icp_result_t *d_res = static_cast<bev_icp_result_t *>(c->reg.sub_res.p);
-    rc = submap_reg_frames(c, n_frames, static_cast<const bev_point_t *>(c->reg.fine_in.p), frame_off, frame_n, leaf, n_maps,
-                           h_map_offsets, h_entry_frame, h_entry_pose, n_matches, h_matches, nullptr, nullptr, prm, d_res);
+    rc = submap_reg_frames(c, n_frames, static_cast<const bev_point_t *>(c->reg.fine_in.p), frame_off, frame_n, leaf, map_leaf,
+                           n_maps, h_map_offsets, h_entry_frame, h_entry_pose, n_matches, h_matches, nullptr, nullptr, prm, d_res,
+                           nullptr);
     if (rc != BEV_OK) return rc;
     HIPCK(c, hipMemcpyAsync(results, d_res, (size_t)n_matches * sizeof(bev_icp_result_t), hipMemcpyDeviceToHost, c->stream));
     HIPCK(c, hipStreamSynchronize(c->stream));
     return BEV_OK;
+}
+
+int bev_submap_registration_batch(bev_ctx_t *c, int n_frames, const bev_point_t *const *clouds, const uint32_t *n_pts, float leaf,
+                                  int n_maps, const uint64_t *h_map_offsets, const int32_t *h_entry_frame,
+                                  const float *h_entry_pose, int n_matches, const bev_match_t *h_matches,
+                                  const bev_icp_params_t *params, bev_icp_result_t *results)
+{
+    return bev_submap_voxel_registration_batch(c, n_frames, clouds, n_pts, leaf, 0.0f, n_maps, h_map_offsets, h_entry_frame,
+                                               h_entry_pose, n_matches, h_matches, params, results);
 }
 
 } /* extern "C" */

@@ -226,6 +226,12 @@ enum KernelId {
     K_SUBMAP_FLOAT_SPLAT, /* the float BEV of submaps (bev_submap_float.h): the same points into their entries' grids of the output itself */
     K_SUBMAP_TARGET,   /* scan-to-map fine ICP (bev_submap_reg.h): a map's entries' moved voxel clouds and their search grid */
     K_SUBMAP_ICP,      /* ... one workgroup per match: K_FINE_ICP's loop against the map */
+    K_SUBMAP_VOX_MOVE,   /* the union voxel grid of a map (bev_submap_vox.h): the entries' moved voxel clouds, concatenated */
+    K_SUBMAP_VOX_KEYS,   /* ... the union's bounds and the sort keys */
+    K_SUBMAP_VOX_TILE,   /* ... the sort's stages inside tiles of LDS */
+    K_SUBMAP_VOX_GLOBAL, /* ... the sort's stages across tiles */
+    K_SUBMAP_VOX_FINISH, /* ... voxel starts, centroids and the search grid of the thinned points */
+    K_SUBMAP_VOX_OUT,    /* ... the cloud call: the maps' points and counts into the caller's arrays */
     K_COUNT
 };
 const char *kernel_name(int id);
@@ -461,6 +467,36 @@ void launch_submap_target(const void *maps, uint32_t map0, int n_maps, const voi
 void launch_submap_icp(const FineProblem *probs, int n, const void *maps, uint32_t map0, const FineWork &w,
                        const SubmapRegWork &t, const bev_icp_result_t *coarse, const int32_t *best, const bev_icp_params_t &prm,
                        bev_icp_result_t *results, hipStream_t st);
+
+/* ---- the union voxel grid of a map (bev_submap_vox.h, bev_submap_vox_plan.h) ----
+ * the maps of ONE launch group of a plan with union_voxel */
+struct SubvoxHdr {
+    uint32_t n;        /* points of the concatenation */
+    uint32_t np2;      /* keys to sort: the smallest power of two >= n, or 0: nothing to sort */
+    uint32_t nf;       /* finite points among them */
+    uint32_t overflow; /* the union's grid has more than INT32_MAX voxels: the target is the concatenation */
+    uint32_t n_out;    /* points of the target */
+    uint32_t _pad[3];
+};
+struct SubmapVoxWork {
+    float4 *moved;        /* [the group's points]        the concatenation: a map's at its pt0 */
+    uint64_t *keys;       /* [the group's keys]          a map's at key0[its index in the plan] */
+    uint32_t *vstart;     /* [the group's points + maps] a map's capacity + 1 words at pt0 + its index in the group */
+    SubvoxHdr *vh;        /* [the group's maps] */
+    const uint64_t *key0; /* [the plan's maps]           device table */
+};
+void launch_submap_vox_move(const void *maps, uint32_t map0, int n_maps, const void *entries, const FineWork &w,
+                            uint32_t *ent_start, const SubmapVoxWork &v, hipStream_t st);
+void launch_submap_vox_keys(const void *maps, uint32_t map0, int n_maps, const SubmapVoxWork &v, float map_leaf, hipStream_t st);
+/* one launch of bevsubvox::schedule: tiles workgroups along x for each of the n_maps maps */
+void launch_submap_vox_stage(uint32_t kind, uint32_t k, uint32_t j, uint32_t map0, int n_maps, uint32_t tiles,
+                             const SubmapVoxWork &v, hipStream_t st);
+/* t.pts: the thinned points; t.hdr == nullptr: no search grid (the cloud call) */
+void launch_submap_vox_finish(const void *maps, uint32_t map0, int n_maps, const SubmapVoxWork &v, const SubmapRegWork &t,
+                              hipStream_t st);
+/* src: the group's point array that holds the targets (moved or thinned); out, counts: the caller's, indexed by map of the plan */
+void launch_submap_vox_out(const void *maps, uint32_t map0, int n_maps, uint32_t parts, const SubvoxHdr *vh, const float4 *src,
+                           float4 *out, uint64_t stride, uint32_t *counts, hipStream_t st);
 
 /* opt in to > 64 KiB of dynamic LDS for the kernels that need it */
 hipError_t configure_kernels(const Geometry &g);

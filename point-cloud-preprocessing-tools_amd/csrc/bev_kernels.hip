@@ -46,6 +46,7 @@
 #include "bev_icp.h"
 #include "bev_fine.h"
 #include "bev_submap_reg.h"
+#include "bev_submap_vox.h"
 
 using namespace bevx;
 
@@ -59,6 +60,7 @@ static const char *const kNames[K_COUNT] = {
     "k_fine_voxel", "k_fine_grid", "k_fine_icp", "k_kitti_crossings", "k_kitti_chain", "k_kitti_assign", "k_kitti_gather",
     "k_float_bev_batch", "k_posed_splat", "k_posed_expand", "k_submap_splat", "k_submap_float_splat",
     "k_submap_target", "k_submap_icp",
+    "k_submap_vox_move", "k_submap_vox_keys", "k_submap_vox_tile", "k_submap_vox_global", "k_submap_vox_finish", "k_submap_vox_out",
 };
 const char *kernel_name(int id) { return (id >= 0 && id < K_COUNT) ? kNames[id] : "?"; }
 

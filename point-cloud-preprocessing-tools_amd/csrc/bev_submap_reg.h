@@ -34,18 +34,14 @@ struct SubregPts {
     }
 };
 
-/* Map map0 + blockIdx.x of the plan.  ent_start: one word per entry of the call (the entry's first target index).  The
- * workgroup's own global writes (ent_start, the moved points) are read back by its other waves behind a barrier: they share
- * the CU's vector cache (rf_bitonic). */
-__global__ __launch_bounds__(kFineThreads) void k_submap_target(const bevsubreg::Map *maps, uint32_t map0,
-                                                                const bevsubreg::Entry *entries, FineWork w,
-                                                                uint32_t *ent_start, SubmapRegWork t)
+/* Steps 1 and 2 of a map's target, by the whole workgroup: the entries' voxel counts scanned into ent_start (one word per
+ * entry of the call: the entry's first target index), every entry's voxel points moved into pts.  Returns the map's point
+ * count; the workgroup is in step on return.  The workgroup's own global writes (ent_start, the moved points) are read back by
+ * its other waves behind a barrier: they share the CU's vector cache (rf_bitonic). */
+__device__ __forceinline__ uint32_t submap_move(const bevsubreg::Map &mp, const bevsubreg::Entry *entries, const FineWork &w,
+                                                uint32_t *ent_start, float4 *pts, uint32_t *wave_sum, uint32_t &s_base)
 {
-    __shared__ uint32_t wave_sum[kRegWaves];
-    __shared__ uint32_t s_base;
     const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const bevsubreg::Map mp = maps[map0 + blockIdx.x];
-    float4 *pts = t.pts + mp.pt0;
     /* 1: an exclusive scan of the entries' voxel counts, 256 entries at a time (a map's total is at most
      * BEV_SUBMAP_REG_MAX_TARGET: the host checked the record counts, which bound the voxel counts) */
     if (tid == 0) s_base = 0;
@@ -82,6 +78,19 @@ __global__ __launch_bounds__(kFineThreads) void k_submap_target(const bevsubreg:
         }
     }
     __syncthreads();
+    return n;
+}
+
+/* Map map0 + blockIdx.x of the plan: submap_move, then the search grid of the moved points. */
+__global__ __launch_bounds__(kFineThreads) void k_submap_target(const bevsubreg::Map *maps, uint32_t map0,
+                                                                const bevsubreg::Entry *entries, FineWork w,
+                                                                uint32_t *ent_start, SubmapRegWork t)
+{
+    __shared__ uint32_t wave_sum[kRegWaves];
+    __shared__ uint32_t s_base;
+    const bevsubreg::Map mp = maps[map0 + blockIdx.x];
+    float4 *pts = t.pts + mp.pt0;
+    const uint32_t n = submap_move(mp, entries, w, ent_start, pts, wave_sum, s_base);
     /* 3: the search grid of the moved points */
     reg_grid_build<kFineCells>(n, SubregPts{pts}, t.hdr + blockIdx.x, t.cell_off + (size_t)blockIdx.x * (kFineCells + 1),
                                t.sorted + mp.pt0);

@@ -15,6 +15,11 @@
  *   problems the matches of a group's maps, ascending by map and among equal maps in the order of the call; match m's
  *            result lands at index m whatever the grouping.
  * bev_submap_plan.h sorts a group's entries by frame (its rasters are order-free) and is not used here.
+ *
+ * union_voxel: the maps are thinned by a second voxel grid over their union (bev_submap_vox.h), so a map also
+ * owns its sort keys at key0 of the group's key array (bev_submap_vox_plan.h pads them), its voxel starts and the thinned
+ * points, and map_bytes counts them.  all_maps: every map of the call is used, whatever the matches name
+ * (bev_submap_voxel_cloud_device_resident has none).
  */
 #ifndef BEV_SUBMAP_REG_PLAN_H
 #define BEV_SUBMAP_REG_PLAN_H
@@ -24,6 +29,8 @@
 #include <cstdint>
 #include <cstring>
 #include <vector>
+
+#include "bev_submap_vox_plan.h"
 
 namespace bevsubreg {
 
@@ -55,6 +62,8 @@ struct Group {
     uint32_t prob0 = 0, n_probs = 0; /* [prob0, prob0 + n_probs) of Plan::probs */
     uint64_t pts = 0;                /* points its maps can hold together */
     uint64_t bytes = 0;              /* sum of map_bytes over its maps */
+    uint64_t keys = 0;               /* union_voxel: sort keys of its maps together (bevsubvox::key_slots of each) */
+    uint64_t max_slots = 0;          /* union_voxel: the largest key array among its maps: it sizes the sort's launches */
 };
 struct Plan {
     std::vector<Slot> slots;
@@ -63,16 +72,25 @@ struct Plan {
     std::vector<Map> maps;
     std::vector<int32_t> map_id;     /* the call's map index of a used map */
     std::vector<uint64_t> map_cap;   /* points a used map can hold */
+    std::vector<uint64_t> map_key0;  /* union_voxel: a used map's first key in its group's key array */
     std::vector<Problem> probs;
     std::vector<Group> groups;
     size_t Pn = 1;                   /* the largest record count of a slot (at least 1) */
     uint64_t max_group_pts = 0;
     uint32_t max_group_maps = 0;
+    uint64_t max_group_keys = 0;     /* union_voxel */
 };
 
+/* what the union grid adds to a map that can hold cap points: the thinned points (16 bytes each), the padded sort keys
+ * (8 bytes each), the voxel starts (cap + 1 words), the sort's header (32 bytes) */
+inline uint64_t map_union_bytes(uint64_t cap) { return cap * 16 + bevsubvox::key_slots(cap) * 8 + (cap + 1) * 4 + 32; }
+
 /* device bytes of a map that can hold cap points: the moved points and the searchable points by cell (16 bytes each),
- * the cell offsets, the header */
-inline uint64_t map_bytes(uint64_t cap) { return cap * 32 + (uint64_t)(kGridCells + 1) * 4 + 32; }
+ * the cell offsets, the header; union_voxel: and map_union_bytes */
+inline uint64_t map_bytes(uint64_t cap, bool union_voxel = false)
+{
+    return cap * 32 + (uint64_t)(kGridCells + 1) * 4 + 32 + (union_voxel ? map_union_bytes(cap) : 0);
+}
 
 /* points the entries of map g can hold together: the sum of their frames' record counts */
 inline uint64_t map_capacity(const uint64_t *frame_n, const uint64_t *map_offs, const int32_t *entry_frame, int g)
@@ -87,7 +105,7 @@ inline uint64_t map_capacity(const uint64_t *frame_n, const uint64_t *map_offs, 
  * indices checked by the caller).  cap_bytes: the group cap. */
 inline Plan plan_call(int n_frames, const uint64_t *frame_off, const uint64_t *frame_n, int n_maps, const uint64_t *map_offs,
                       const int32_t *entry_frame, const float *entry_pose, int n_matches, const int32_t *query,
-                      const int32_t *match_map, uint64_t cap_bytes)
+                      const int32_t *match_map, uint64_t cap_bytes, bool union_voxel = false, bool all_maps = false)
 {
     Plan p;
     std::vector<int32_t> slot_of((size_t)std::max(n_frames, 0), -1), used((size_t)std::max(n_maps, 0), -1);
@@ -104,6 +122,11 @@ inline Plan plan_call(int n_frames, const uint64_t *frame_off, const uint64_t *f
     for (int m = 0; m < n_matches; ++m) {
         slot(query[m]);
         const int g = match_map[m];
+        if (used[g] >= 0) continue;
+        used[g] = 0;
+        for (uint64_t e = map_offs[g]; e < map_offs[g + 1]; ++e) slot(entry_frame[e]);
+    }
+    for (int g = 0; all_maps && g < n_maps; ++g) {
         if (used[g] >= 0) continue;
         used[g] = 0;
         for (uint64_t e = map_offs[g]; e < map_offs[g + 1]; ++e) slot(entry_frame[e]);
@@ -133,15 +156,22 @@ inline Plan plan_call(int n_frames, const uint64_t *frame_off, const uint64_t *f
         p.probs.push_back(Problem{(uint32_t)slot_of[query[m]], (uint32_t)(k >> 32), m, 0u});
     }
     /* the groups */
+    p.map_key0.assign(p.maps.size(), 0);
     size_t pr = 0;
     for (uint32_t u = 0; u < (uint32_t)p.maps.size();) {
         Group g;
         g.map0 = u;
         g.prob0 = (uint32_t)pr;
         while (u < (uint32_t)p.maps.size()) {
-            const uint64_t b = map_bytes(p.map_cap[u]);
+            const uint64_t b = map_bytes(p.map_cap[u], union_voxel);
             if (g.n_maps > 0 && g.bytes + b > cap_bytes) break;
             p.maps[u].pt0 = g.pts;
+            if (union_voxel) {
+                const uint64_t slots = bevsubvox::key_slots(p.map_cap[u]);
+                p.map_key0[u] = g.keys;
+                g.keys += slots;
+                g.max_slots = std::max(g.max_slots, slots);
+            }
             g.pts += p.map_cap[u];
             g.bytes += b;
             ++g.n_maps;
@@ -151,6 +181,7 @@ inline Plan plan_call(int n_frames, const uint64_t *frame_off, const uint64_t *f
         g.n_probs = (uint32_t)pr - g.prob0;
         p.max_group_pts = std::max(p.max_group_pts, g.pts);
         p.max_group_maps = std::max(p.max_group_maps, g.n_maps);
+        p.max_group_keys = std::max(p.max_group_keys, g.keys);
         p.groups.push_back(g);
     }
     return p;

@@ -1,5 +1,5 @@
 /*
- * batch_submap_registration <match_result_text_file> <keyframes_root_dir> <half_window> [<chunk>]
+ * batch_submap_registration <match_result_text_file> <keyframes_root_dir> <half_window> [<chunk> [<map_leaf>]]
  *
  * Scan-to-map registration: batch_whole_registration with a LOCAL MAP as every match's target.  The match list
  * is batch_whole_registration's ("query match yaw" per line); the indices name the sorted files of
@@ -8,6 +8,9 @@
  * the files, in ascending order, each under T_m^-1 T_j (submapwin::relativePose; j == m gets the exact identity); the query's
  * voxel cloud is registered against the map's moved voxel clouds from the yaw guess, with the whole tool's settings
  * (bev_icp_whole_defaults), by bev_submap_registration_device_resident.  half_window 0 is batch_whole_registration.
+ * <map_leaf> > 0 thins every map by a voxel grid of that leaf over the union of its moved voxel clouds
+ * (bev_submap_voxel_registration_device_resident); absent or 0: no second grid, the files as ever; negative or
+ * not a finite number: refused with the usage line.
  *
  * Bookkeeping, summary line and [TIME] line are batch_whole_registration's (a match fails when its fitness exceeds 1.5); like
  * that tool it creates icp_precision_report_3d_icp_directly.txt in the working directory and writes nothing to it.  Beside
@@ -18,7 +21,9 @@
  * arguments, an unreadable match list or pose file, an index outside the files or an unreadable cloud exit 1.
  */
 #include <chrono>
+#include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <fstream>
 #include <iostream>
 #include <map>
@@ -42,12 +47,31 @@ void hip_or_die(hipError_t e, const char *what)
     }
 }
 
+const char kUsage[] =
+    "Usage: batch_submap_registration <match_result_text_file> <keyframes_root_dir> <half_window> [<chunk> [<map_leaf>]]\n";
+
+/* a finite number >= 0 and nothing else */
+bool parse_map_leaf(const char *s, float *out)
+{
+    if (!s || !*s) return false;
+    char *end = nullptr;
+    const float v = std::strtof(s, &end);
+    if (end == s || *end != '\0' || !std::isfinite(v) || v < 0.0f) return false;
+    *out = v;
+    return true;
+}
+
 } // namespace
 
 int main(int argc, char **argv)
 {
     if (argc < 4) {
-        std::cerr << "Usage: batch_submap_registration <match_result_text_file> <keyframes_root_dir> <half_window> [<chunk>]\n";
+        std::cerr << kUsage;
+        return 1;
+    }
+    float map_leaf = 0.0f;
+    if (argc > 5 && !parse_map_leaf(argv[5], &map_leaf)) {
+        std::cerr << "map_leaf '" << argv[5] << "': expected a finite number >= 0\n" << kUsage;
         return 1;
     }
     std::string root(argv[2]);
@@ -147,9 +171,15 @@ int main(int argc, char **argv)
                                      clouds[f].points.size() * sizeof(bev_point_t), hipMemcpyHostToDevice),
                            "hipMemcpy");
         hip_or_die(hipMalloc(&d_fine, n * sizeof(bev_icp_result_t)), "hipMalloc");
-        int rc = bev_submap_registration_device_resident(ctx, F, static_cast<bev_point_t *>(d_pts), offs.data(), 0.2f, (int)n,
-                                                         map_offs.data(), entry_frame.data(), entry_pose.data(), (int)n, cm.data(),
-                                                         nullptr, nullptr, &prm, static_cast<bev_icp_result_t *>(d_fine));
+        int rc = map_leaf > 0.0f
+                     ? bev_submap_voxel_registration_device_resident(ctx, F, static_cast<bev_point_t *>(d_pts), offs.data(), 0.2f,
+                                                                     map_leaf, (int)n, map_offs.data(), entry_frame.data(),
+                                                                     entry_pose.data(), (int)n, cm.data(), nullptr, nullptr,
+                                                                     &prm, static_cast<bev_icp_result_t *>(d_fine))
+                     : bev_submap_registration_device_resident(ctx, F, static_cast<bev_point_t *>(d_pts), offs.data(), 0.2f, (int)n,
+                                                               map_offs.data(), entry_frame.data(), entry_pose.data(), (int)n,
+                                                               cm.data(), nullptr, nullptr, &prm,
+                                                               static_cast<bev_icp_result_t *>(d_fine));
         if (rc == BEV_OK) rc = bev_synchronize(ctx);
         if (rc != BEV_OK) {
             std::cerr << "bev_submap_registration_device_resident: " << bev_strerror(rc) << " " << bev_last_error(ctx) << "\n";
