@@ -645,6 +645,60 @@ int bev_submap_voxel_cloud_device_resident(bev_ctx_t *ctx, int n_frames, const b
                                            const int32_t *h_entry_frame, const float *h_entry_pose, uint64_t out_stride,
                                            float *d_out, uint32_t *d_counts);
 
+/* ---- scan-to-map coarse ICP: PointNormal frames registered point-to-plane against submaps ------------------------------
+ * The coarse stage with a MAP as its target: bev_coarse_registration_device_resident's loop, the target of
+ * match m being map match_idx instead of one frame.  Its two outputs are what the fine stages take as d_coarse / d_best, so
+ * the top-part pipeline against local maps is: bev_registration_front_device_resident, this call,
+ * bev_submap_voxel_registration_device_resident, with no synchronisation between them.
+ * Frames    : PointNormal clouds, d_pn / stride / d_counts exactly as bev_coarse_registration_device_resident reads them (the
+ *             output of bev_registration_front_device_resident; a count above stride is read as stride).
+ * Maps      : h_map_offsets, h_entry_frame, h_entry_pose exactly as bev_submap_bev_device_resident (12 floats per entry, a
+ *             row-major 3 x 4 matrix m); any number of entries per map; a frame may appear several times in one map, feed many
+ *             maps, or be named by none; a map no match names costs nothing.
+ * Moving a PointNormal record r under m, all in float, without FMA:
+ *             position component i = m[i][0] * x + (m[i][1] * y + (m[i][2] * z + m[i][3]))   (bev_transform_cloud's association);
+ *             normal component i   = m[i][0] * nx + (m[i][1] * ny + m[i][2] * nz)            (the same without the translation);
+ *             the normal is neither renormalised nor flipped again, so a matrix that is no rotation gives what this formula
+ *             gives; the curvature is copied, every pad is 0, every NaN written is 0x7fc00000; 48 bytes in the layout above.
+ * target(g) : the concatenation, over g's entries e IN THE ORDER GIVEN, of the moved records of frame(e) under pose(e).  A
+ *             target point's index is its position in the concatenation, and the search's "lowest index on ties" is over that
+ *             index, so the order of a map's entries matters.  Points made non-finite keep their index and are never matched;
+ *             a correspondence whose moved normal has a non-finite component adds nothing to the sums, but counts (§6c).
+ * Results   : for match m = (query_idx, match_idx = a MAP's index, angle_guess) and guess k in {0, 1}
+ *               d_results[2m + k] = bev_icp_point_to_plane(frame query_idx, target(match_idx), guess k of angle_guess, params)
+ *             bit for bit as a whole bev_icp_result_t (guess 0: yaw theta, guess 1: theta + 180, as above);
+ *             d_best[m] = 0 iff fitness[2m] < fitness[2m + 1], else 1.  result.T takes the query frame into the map's
+ *             coordinates.  A map without entries or without a searchable point ends as bev_icp_point_to_plane ends on an
+ *             empty target: BEV_ICP_NO_CORRESPONDENCES, fitness DBL_MAX.  params NULL: the coarse defaults.
+ * Ordering  : asynchronous and ordered exactly like bev_coarse_registration_device_resident: it starts behind every call made
+ *             on the context before it and behind the caller's default-stream work; the next BEV call starts behind it, so
+ *             d_results / d_best can go straight into bev_submap_voxel_registration_device_resident (or any fine call) as
+ *             d_coarse / d_best.  bev_synchronize() before reading them on the host.  The host arrays may be reused as soon as
+ *             the call returns.
+ * Status    : BEV_ERR_INVALID_ARG for a NULL context, a negative count, invalid parameters, and, with matches to run,
+ *             stride == 0, a NULL array that would be read, decreasing offsets, an entry frame outside 0 .. n_frames - 1, a
+ *             query_idx outside the frames, a match_idx outside the maps; BEV_ERR_TOO_LARGE for more than
+ *             BEV_SUBMAP_MAX_ENTRIES entries (checked before the entry arrays are read) and for a map whose CAPACITY exceeds
+ *             BEV_SUBMAP_COARSE_MAX_TARGET rows.  A map's capacity is n_entries * stride: the frames' true counts live on the
+ *             device and the host does not wait for them, so a caller whose frames are short passes a tighter stride (any
+ *             stride >= the largest count reads the same rows).  A refused call launches nothing and leaves d_results and
+ *             d_best untouched.  n_matches == 0 returns BEV_OK.
+ * Workspace : in the coarse stage's buffer (allocated on first use, grown when a call needs more, freed by bev_destroy; the
+ *             pair call and this one hand it to each other in stream order).  With E the entries of the used maps and, of the
+ *             launch group that needs most, T the sum of its maps' capacities and M its maps:
+ *               min(2 * n_matches, 1024) * 16 * stride + 4 E + 64 T + M * (4 * 4097 + 32)
+ *             bytes (pieces rounded up to 256), plus the tables (16 bytes per used map, 64 per entry, 80 per problem, two
+ *             problems per match).  The used maps are cut into launch groups of consecutive maps whose
+ *             64 T + M * (4 * 4097 + 32) bytes fit 8 GiB (BEV_SUBMAP_REG_GROUP=<bytes>, as above; results do not depend on
+ *             it); a map above the cap is a group of its own.  A group's problems run in launches of 1024.  The search grid of
+ *             a map has at most 64 x 64 cells, as a frame's has. */
+#define BEV_SUBMAP_COARSE_MAX_TARGET (1u << 22)   /* rows of one map: its entries times the stride */
+int bev_submap_coarse_registration_device_resident(bev_ctx_t *ctx, int n_frames, const void *d_pn, size_t stride,
+                                                   const uint32_t *d_counts, int n_maps, const uint64_t *h_map_offsets,
+                                                   const int32_t *h_entry_frame, const float *h_entry_pose, int n_matches,
+                                                   const bev_match_t *h_matches, const bev_icp_params_t *params,
+                                                   bev_icp_result_t *d_results, int32_t *d_best);
+
 /* ---- layout hint -------------------------------------------------------
  * What the caller knows about how its clouds are laid out, so that the library need not look (k_probe reads every 63rd
  * record of a frame to find out: 0.36 MB and 0.07 us of an HDL_64E frame).  Sticky per context; applies to frames of

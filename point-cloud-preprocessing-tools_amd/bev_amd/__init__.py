@@ -73,6 +73,7 @@ KITTI_SLOTS = 64 * 2083
 FLOAT_BEV_MAX_POSES = 64  # BEV_FLOAT_BEV_MAX_POSES: poses per frame of float_bev_device / float_bev_batch
 POSED_BEV_MAX_POSES = 64  # BEV_POSED_BEV_MAX_POSES: poses per frame of posed_bev_device / posed_bev_batch
 SUBMAP_MAX_ENTRIES = 1 << 20  # BEV_SUBMAP_MAX_ENTRIES: (frame, pose) entries of one submap_bev_device / submap_bev_batch call
+SUBMAP_COARSE_MAX_TARGET = 1 << 22  # BEV_SUBMAP_COARSE_MAX_TARGET: rows of one map, entries times stride (submap_coarse_registration_device)
 SUBMAP_REG_MAX_TARGET = 1 << 22  # BEV_SUBMAP_REG_MAX_TARGET: records of one map's entries' frames together (submap_registration_*)
 
 # every symbol include/bev_mi355x.h declares
@@ -97,6 +98,7 @@ ABI_SYMBOLS = [
     "bev_submap_registration_device_resident", "bev_submap_registration_batch",
     "bev_submap_voxel_registration_device_resident", "bev_submap_voxel_registration_batch",
     "bev_submap_voxel_cloud_device_resident",
+    "bev_submap_coarse_registration_device_resident",
 ]
 
 # registration front end (include/bev_mi355x.h): pcl::PointXYZ, pcl::Normal, pcl::PointNormal as float rows
@@ -245,6 +247,9 @@ def load_lib() -> C.CDLL:
                                                             C.POINTER(C.c_uint64), vp, vp, i32, vp, C.POINTER(IcpParams), vp]
         lib.bev_submap_voxel_cloud_device_resident.argtypes = [vp, i32, vp, C.POINTER(C.c_uint64), C.c_float, C.c_float, i32,
                                                                C.POINTER(C.c_uint64), vp, vp, C.c_uint64, vp, vp]
+    if hasattr(lib, "bev_submap_coarse_registration_device_resident"):
+        lib.bev_submap_coarse_registration_device_resident.argtypes = [vp, i32, vp, sz, vp, i32, C.POINTER(C.c_uint64), vp, vp,
+                                                                       i32, vp, C.POINTER(IcpParams), vp, vp]
     _lib = lib
     return lib
 
@@ -791,6 +796,23 @@ class BevContext:
             self._h, n_frames, C.c_void_p(d_clouds or None), offs, leaf, map_leaf, n_maps,
             map_offsets.ctypes.data_as(C.POINTER(C.c_uint64)), _ptr(entry_frame), _ptr(entry_pose), int(out_stride),
             C.c_void_p(d_out or None), C.c_void_p(d_counts or None)), "bev_submap_voxel_cloud_device_resident")
+
+    # ---- scan-to-map coarse ICP: PointNormal frames against submaps ---------------------------------
+    def submap_coarse_registration_device(self, n_frames, d_pn, stride, d_counts, map_offsets, entry_frame, entry_pose,
+                                          matches, d_results, d_best, params: IcpParams | None = None):
+        """bev_submap_coarse_registration_device_resident on device pointers: frames as for coarse_registration_device
+        (PointNormal rows, stride, counts), maps and entries as for submap_bev_device; matches: MATCH_DTYPE records (host)
+        whose match_idx names a MAP: the query frame is registered point-to-plane, from both yaw guesses, against the map's
+        entries' moved rows, concatenated in the order given.  Asynchronous: synchronize() before reading d_results (2
+        ICP_RESULT_DTYPE per match) and d_best (int32); both go as they are into the fine calls' d_coarse / d_best."""
+        n_maps, map_offsets, entry_frame, entry_pose = self._submap_entries(map_offsets, entry_frame, entry_pose)
+        m = np.ascontiguousarray(matches, dtype=MATCH_DTYPE)
+        prm = params if params is not None else icp_params()
+        self._check(self.lib.bev_submap_coarse_registration_device_resident(
+            self._h, n_frames, C.c_void_p(d_pn or None), stride, C.c_void_p(d_counts or None), n_maps,
+            map_offsets.ctypes.data_as(C.POINTER(C.c_uint64)), _ptr(entry_frame), _ptr(entry_pose), len(m),
+            _ptr(m) if len(m) else None, C.byref(prm), C.c_void_p(d_results or None), C.c_void_p(d_best or None)),
+            "bev_submap_coarse_registration_device_resident")
 
     def set_layout_hint(self, layout: int):
         """LAYOUT_UNKNOWN (the library looks), LAYOUT_STRUCTURED, LAYOUT_FIRING_ORDER: include/bev_mi355x.h"""

@@ -1,9 +1,9 @@
 /*
  * bev_capi_reg.hip — the registration half of the extern "C" boundary declared in include/bev_mi355x.h: the front end
  * (top-part flatten, voxel grid, 2-D normals), coarse point-to-plane ICP (§6c), the fine stage (§6d) and
- * scan-to-map fine ICP (§6k), with the voxel grid over a map's union in front of it (§6l).
+ * scan-to-map fine ICP (§6k), with the voxel grid over a map's union in front of it (§6l), and scan-to-map coarse ICP (§6m).
  * Host-side only; the kernels are in bev_kernels.hip (bev_reg_common.h, bev_regfront.h, bev_icp.h, bev_fine.h,
- * bev_submap_reg.h, bev_submap_vox.h).  With
+ * bev_submap_reg.h, bev_submap_vox.h, bev_submap_coarse.h).  With
  * the BEV pipeline of bev_capi.hip it shares the context (bev_ctx.h), its stream and the call prologue (begin_call).
  */
 #include <algorithm>
@@ -872,6 +872,107 @@ int bev_submap_registration_batch(bev_ctx_t *c, int n_frames, const bev_point_t 
 {
     return bev_submap_voxel_registration_batch(c, n_frames, clouds, n_pts, leaf, 0.0f, n_maps, h_map_offsets, h_entry_frame,
                                                h_entry_pose, n_matches, h_matches, params, results);
+}
+
+/* ---- scan-to-map coarse ICP: PointNormal frames against submaps (bev_submap_coarse.h) ------------------ */
+int bev_submap_coarse_registration_device_resident(bev_ctx_t *c, int n_frames, const void *d_pn, size_t stride,
+                                                   const uint32_t *d_counts, int n_maps, const uint64_t *h_map_offsets,
+                                                   const int32_t *h_entry_frame, const float *h_entry_pose, int n_matches,
+                                                   const bev_match_t *h_matches, const bev_icp_params_t *params,
+                                                   bev_icp_result_t *d_results, int32_t *d_best)
+{
+    const bev_icp_params_t prm = params ? *params : bev_icp_coarse_defaults();
+    if (!c || n_frames < 0 || n_maps < 0 || n_matches < 0 || !icp_params_ok(prm)) return BEV_ERR_INVALID_ARG;
+    if (n_matches > 0) {
+        if (!d_pn || !d_counts || !h_matches || !d_results || !d_best || stride == 0) return BEV_ERR_INVALID_ARG;
+        const int rc_ = check_submap_entries(n_frames, n_maps, h_map_offsets, h_entry_frame, h_entry_pose);
+        if (rc_ != BEV_OK) return rc_;
+        for (int m = 0; m < n_matches; ++m) {
+            const bev_match_t &mt = h_matches[m];
+            if (mt.query_idx < 0 || mt.query_idx >= n_frames || mt.match_idx < 0 || mt.match_idx >= n_maps) return BEV_ERR_INVALID_ARG;
+        }
+        /* a map's capacity is n_entries * stride rows: the true counts live on the device, and the host does not wait for them */
+        for (int g = 0; g < n_maps; ++g) {
+            const uint64_t ne = h_map_offsets[g + 1] - h_map_offsets[g];
+            if (ne && (uint64_t)stride > BEV_SUBMAP_COARSE_MAX_TARGET / ne) return BEV_ERR_TOO_LARGE;
+        }
+    }
+    int rc = begin_call(c, false);
+    if (rc != BEV_OK) return rc;
+    if (n_matches == 0) return BEV_OK;
+    rc = wait_default_stream(c);
+    if (rc != BEV_OK) return rc;
+    /* §6k's plan with every frame counted at stride rows and a PointNormal map's bytes */
+    std::vector<int32_t> query((size_t)n_matches), match_map((size_t)n_matches);
+    for (int m = 0; m < n_matches; ++m) {
+        query[(size_t)m] = h_matches[m].query_idx;
+        match_map[(size_t)m] = h_matches[m].match_idx;
+    }
+    const std::vector<uint64_t> frame_off((size_t)n_frames, 0), frame_n((size_t)n_frames, (uint64_t)stride);
+    const uint64_t cap = c->submap_reg_group ? (uint64_t)c->submap_reg_group : kSubmapRegCap;
+    bevsubreg::Plan plan = bevsubreg::plan_call(n_frames, frame_off.data(), frame_n.data(), n_maps, h_map_offsets, h_entry_frame,
+                                                h_entry_pose, n_matches, query.data(), match_map.data(), cap, false, false, true);
+    for (bevsubreg::Entry &en : plan.entries) en.slot = (uint32_t)plan.slot_frame[en.slot]; /* the device reads the frame */
+    const size_t P = 2 * plan.probs.size(), E = plan.entries.size(), NM = plan.maps.size();
+    const size_t L = std::min(P, (size_t)kIcpProblemsPerLaunch);
+    const size_t T = std::max<size_t>((size_t)plan.max_group_pts, 1), M = std::max<size_t>(plan.max_group_maps, 1);
+    /* the workspace, in the coarse stage's buffer: the scratch of an ICP launch, the entries' first indices, the maps of one
+     * launch group */
+    SubmapCoarseWork t{};
+    uint32_t *ent_start = nullptr;
+    const size_t sz[] = {L * 16 * stride, std::max<size_t>(E, 1) * 4, T * 48, T * 16, M * sizeof(IcpGridHdr),
+                         M * 4 * (size_t)(kIcpCells + 1)};
+    void **const dst[] = {(void **)&t.cur, (void **)&ent_start, (void **)&t.rows, (void **)&t.sorted, (void **)&t.hdr,
+                          (void **)&t.cell_off};
+    rc = c->reg.icp_buf.grow(c, carve(nullptr, sz, dst));
+    if (rc != BEV_OK) return rc;
+    carve(c->reg.icp_buf.p, sz, dst);
+    /* the tables, one block: maps, entries (64-byte aligned), problems: two per match, the guesses adjacent */
+    const size_t o_ent = align256(NM * sizeof(bevsubreg::Map)), o_probs = o_ent + align256(E * sizeof(bevsubreg::Entry)),
+                 tab = o_probs + P * sizeof(IcpProblem);
+    void *hv;
+    rc = c->reg.icp_tab.begin(c, tab, kRegTabMin, &hv);
+    if (rc != BEV_OK) return rc;
+    char *h = static_cast<char *>(hv);
+    if (NM) std::memcpy(h, plan.maps.data(), NM * sizeof(bevsubreg::Map));
+    if (E) std::memcpy(h + o_ent, plan.entries.data(), E * sizeof(bevsubreg::Entry));
+    IcpProblem *hp = reinterpret_cast<IcpProblem *>(h + o_probs);
+    for (size_t k = 0; k < plan.probs.size(); ++k) {
+        const bevsubreg::Problem &pp = plan.probs[k];
+        for (int g = 0; g < 2; ++g) {
+            IcpProblem &pb = hp[2 * k + g];
+            pb.src_frame = (uint32_t)h_matches[pp.result].query_idx;
+            pb.tgt_frame = 0xffffffffu; /* (not read: the target is a map) */
+            pb.tgt_slot = pp.map;
+            pb.result = 2 * pp.result + (uint32_t)g;
+            bevx::icp_tool_guess(h_matches[pp.result].angle_guess, g, pb.guess);
+        }
+    }
+    rc = c->reg.icp_tab.push(c, tab);
+    if (rc != BEV_OK) return rc;
+    const char *dev = static_cast<const char *>(c->reg.icp_tab.dev);
+    const void *d_maps = dev, *d_entries = dev + o_ent;
+    const IcpProblem *d_probs = reinterpret_cast<const IcpProblem *>(dev + o_probs);
+    const float *pn = static_cast<const float *>(d_pn);
+    /* the groups one behind the other on the stream: its order hands the maps' arrays from group to group */
+    for (const bevsubreg::Group &g : plan.groups) {
+        {
+            ProfScope ps(c, K_SUBMAP_PN_TARGET, (int)g.n_maps);
+            launch_submap_pn_target(d_maps, g.map0, (int)g.n_maps, d_entries, pn, stride, d_counts, ent_start, t, c->stream);
+        }
+        for (uint32_t p0 = 0; p0 < 2 * g.n_probs; p0 += kIcpProblemsPerLaunch) {
+            const int n = (int)std::min<uint32_t>(kIcpProblemsPerLaunch, 2 * g.n_probs - p0);
+            ProfScope ps(c, K_SUBMAP_COARSE_ICP, n);
+            launch_submap_coarse_icp(pn, stride, d_counts, d_probs + 2 * (size_t)g.prob0 + p0, n, d_maps, g.map0, t, prm, d_results,
+                                     c->stream);
+        }
+    }
+    {
+        ProfScope ps(c, K_ICP_BEST, n_matches);
+        launch_icp_best(d_results, n_matches, d_best, c->stream);
+    }
+    HIPCK(c, hipGetLastError());
+    return record_tail(c);
 }
 
 } /* extern "C" */

@@ -232,6 +232,8 @@ enum KernelId {
     K_SUBMAP_VOX_GLOBAL, /* ... the sort's stages across tiles */
     K_SUBMAP_VOX_FINISH, /* ... voxel starts, centroids and the search grid of the thinned points */
     K_SUBMAP_VOX_OUT,    /* ... the cloud call: the maps' points and counts into the caller's arrays */
+    K_SUBMAP_PN_TARGET,  /* scan-to-map coarse ICP (bev_submap_coarse.h): a map's entries' moved PointNormal rows and their search grid */
+    K_SUBMAP_COARSE_ICP, /* ... one workgroup per (match, guess): K_ICP's loop against the map (the better guess: K_ICP_BEST) */
     K_COUNT
 };
 const char *kernel_name(int id);
@@ -497,6 +499,24 @@ void launch_submap_vox_finish(const void *maps, uint32_t map0, int n_maps, const
 /* src: the group's point array that holds the targets (moved or thinned); out, counts: the caller's, indexed by map of the plan */
 void launch_submap_vox_out(const void *maps, uint32_t map0, int n_maps, uint32_t parts, const SubvoxHdr *vh, const float4 *src,
                            float4 *out, uint64_t stride, uint32_t *counts, hipStream_t st);
+
+/* ---- scan-to-map coarse ICP (bev_submap_coarse.h, bev_submap_reg_plan.h) ----
+ * the maps of ONE launch group of the plan: a map's rows at its pt0, its header and cell offsets at its index in the group */
+struct SubmapCoarseWork {
+    float *rows;        /* [the group's rows][12]  the entries' moved PointNormal rows */
+    float4 *sorted;     /* [the group's rows]      the searchable ones by cell (x, y, z, index bits) */
+    IcpGridHdr *hdr;    /* [the group's maps] */
+    uint32_t *cell_off; /* [the group's maps][kIcpCells + 1] */
+    float4 *cur;        /* [kIcpProblemsPerLaunch][stride] */
+};
+/* maps / entries: the plan's tables, an entry's slot word holding its FRAME; the n_maps maps from map0 on; pn, stride, counts:
+ * the call's frames; ent_start: a word per entry of the call */
+void launch_submap_pn_target(const void *maps, uint32_t map0, int n_maps, const void *entries, const float *pn, size_t stride,
+                             const uint32_t *counts, uint32_t *ent_start, const SubmapCoarseWork &t, hipStream_t st);
+/* n <= kIcpProblemsPerLaunch problems whose tgt_slot is a map's index in the plan (all in the group from map0 on) */
+void launch_submap_coarse_icp(const float *pn, size_t stride, const uint32_t *counts, const IcpProblem *probs, int n,
+                              const void *maps, uint32_t map0, const SubmapCoarseWork &t, const bev_icp_params_t &prm,
+                              bev_icp_result_t *results, hipStream_t st);
 
 /* opt in to > 64 KiB of dynamic LDS for the kernels that need it */
 hipError_t configure_kernels(const Geometry &g);

@@ -47,6 +47,7 @@
 #include "bev_fine.h"
 #include "bev_submap_reg.h"
 #include "bev_submap_vox.h"
+#include "bev_submap_coarse.h"
 
 using namespace bevx;
 
@@ -61,6 +62,7 @@ static const char *const kNames[K_COUNT] = {
     "k_float_bev_batch", "k_posed_splat", "k_posed_expand", "k_submap_splat", "k_submap_float_splat",
     "k_submap_target", "k_submap_icp",
     "k_submap_vox_move", "k_submap_vox_keys", "k_submap_vox_tile", "k_submap_vox_global", "k_submap_vox_finish", "k_submap_vox_out",
+    "k_submap_pn_target", "k_submap_coarse_icp",
 };
 const char *kernel_name(int id) { return (id >= 0 && id < K_COUNT) ? kNames[id] : "?"; }
 

@@ -34,21 +34,20 @@ struct SubregPts {
     }
 };
 
-/* Steps 1 and 2 of a map's target, by the whole workgroup: the entries' voxel counts scanned into ent_start (one word per
- * entry of the call: the entry's first target index), every entry's voxel points moved into pts.  Returns the map's point
- * count; the workgroup is in step on return.  The workgroup's own global writes (ent_start, the moved points) are read back by
- * its other waves behind a barrier: they share the CU's vector cache (rf_bitonic). */
-__device__ __forceinline__ uint32_t submap_move(const bevsubreg::Map &mp, const bevsubreg::Entry *entries, const FineWork &w,
-                                                uint32_t *ent_start, float4 *pts, uint32_t *wave_sum, uint32_t &s_base)
+/* An exclusive scan of the row counts count_of(e) of a map's entries e = 0 .. n_ent - 1, by the whole workgroup, 256 entries at
+ * a time: ent_start (one word per entry of the call) gets every entry's first target index.  Returns the map's total; the
+ * workgroup is in step on return.  (k_submap_target, k_submap_vox_move: voxel counts; k_submap_pn_target, bev_submap_coarse.h:
+ * PointNormal rows.) */
+template <class CountOf>
+__device__ __forceinline__ uint32_t submap_scan(const bevsubreg::Map &mp, CountOf count_of, uint32_t *ent_start,
+                                                uint32_t *wave_sum, uint32_t &s_base)
 {
     const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    /* 1: an exclusive scan of the entries' voxel counts, 256 entries at a time (a map's total is at most
-     * BEV_SUBMAP_REG_MAX_TARGET: the host checked the record counts, which bound the voxel counts) */
     if (tid == 0) s_base = 0;
     __syncthreads();
     for (uint32_t e0 = 0; e0 < mp.n_ent; e0 += kRegThreads) {
         const uint32_t e = e0 + (uint32_t)tid;
-        const uint32_t v = e < mp.n_ent ? w.vox_n[entries[mp.ent0 + e].slot] : 0u;
+        const uint32_t v = e < mp.n_ent ? count_of(e) : 0u;
         uint32_t incl = v;
         for (int off = 1; off < 64; off <<= 1) {
             const uint32_t up = __shfl_up(incl, off);
@@ -63,7 +62,21 @@ __device__ __forceinline__ uint32_t submap_move(const bevsubreg::Map &mp, const 
         if (tid == kRegThreads - 1) s_base = before + incl;
         __syncthreads();
     }
-    const uint32_t n = s_base;
+    return s_base;
+}
+
+/* Steps 1 and 2 of a map's target, by the whole workgroup: the entries' voxel counts scanned into ent_start (one word per
+ * entry of the call: the entry's first target index), every entry's voxel points moved into pts.  Returns the map's point
+ * count; the workgroup is in step on return.  The workgroup's own global writes (ent_start, the moved points) are read back by
+ * its other waves behind a barrier: they share the CU's vector cache (rf_bitonic). */
+__device__ __forceinline__ uint32_t submap_move(const bevsubreg::Map &mp, const bevsubreg::Entry *entries, const FineWork &w,
+                                                uint32_t *ent_start, float4 *pts, uint32_t *wave_sum, uint32_t &s_base)
+{
+    const int tid = (int)threadIdx.x;
+    /* 1: an exclusive scan of the entries' voxel counts (a map's total is at most BEV_SUBMAP_REG_MAX_TARGET: the host checked
+     * the record counts, which bound the voxel counts) */
+    const uint32_t n = submap_scan(
+        mp, [&](uint32_t e) { return w.vox_n[entries[mp.ent0 + e].slot]; }, ent_start, wave_sum, s_base);
     /* 2: every entry's voxel points under its matrix (a workgroup-uniform loop over the entries) */
     for (uint32_t e = 0; e < mp.n_ent; ++e) {
         const bevsubreg::Entry &en = entries[mp.ent0 + e];

@@ -20,6 +20,11 @@
  * owns its sort keys at key0 of the group's key array (bev_submap_vox_plan.h pads them), its voxel starts and the thinned
  * points, and map_bytes counts them.  all_maps: every map of the call is used, whatever the matches name
  * (bev_submap_voxel_cloud_device_resident has none).
+ *
+ * point_normal: the call is bev_submap_coarse_registration_device_resident's: the frames are PointNormal clouds
+ * of `stride` rows each (frame_n[f] = stride, frame_off unused), a map's capacity is n_entries * stride rows and its bytes are
+ * map_coarse_bytes; the caller makes two problems (the guesses) of every Problem.  Everything else is as above; with the
+ * default (false) every call plans exactly as before.
  */
 #ifndef BEV_SUBMAP_REG_PLAN_H
 #define BEV_SUBMAP_REG_PLAN_H
@@ -35,6 +40,8 @@
 namespace bevsubreg {
 
 constexpr uint32_t kGridCells = 128 * 128; /* kFineCells (bev_internal.h): cells of a map's search grid */
+constexpr uint32_t kCoarseGridCells = 64 * 64; /* kIcpCells: cells of a PointNormal map's search grid */
+constexpr uint32_t kCoarseRowBytes = 48 + 16;  /* ... a moved PointNormal row and its searchable copy */
 
 struct Slot { /* FineSlot's layout (bev_internal.h): k_fine_voxel reads the slots */
     uint64_t off;
@@ -92,6 +99,10 @@ inline uint64_t map_bytes(uint64_t cap, bool union_voxel = false)
     return cap * 32 + (uint64_t)(kGridCells + 1) * 4 + 32 + (union_voxel ? map_union_bytes(cap) : 0);
 }
 
+/* device bytes of a PointNormal map of cap rows (bev_submap_coarse_registration_device_resident): the moved rows and the
+ * searchable points by cell, the 64 x 64 grid's cell offsets, the header */
+inline uint64_t map_coarse_bytes(uint64_t cap) { return cap * kCoarseRowBytes + (uint64_t)(kCoarseGridCells + 1) * 4 + 32; }
+
 /* points the entries of map g can hold together: the sum of their frames' record counts */
 inline uint64_t map_capacity(const uint64_t *frame_n, const uint64_t *map_offs, const int32_t *entry_frame, int g)
 {
@@ -105,7 +116,8 @@ inline uint64_t map_capacity(const uint64_t *frame_n, const uint64_t *map_offs, 
  * indices checked by the caller).  cap_bytes: the group cap. */
 inline Plan plan_call(int n_frames, const uint64_t *frame_off, const uint64_t *frame_n, int n_maps, const uint64_t *map_offs,
                       const int32_t *entry_frame, const float *entry_pose, int n_matches, const int32_t *query,
-                      const int32_t *match_map, uint64_t cap_bytes, bool union_voxel = false, bool all_maps = false)
+                      const int32_t *match_map, uint64_t cap_bytes, bool union_voxel = false, bool all_maps = false,
+                      bool point_normal = false)
 {
     Plan p;
     std::vector<int32_t> slot_of((size_t)std::max(n_frames, 0), -1), used((size_t)std::max(n_maps, 0), -1);
@@ -163,7 +175,7 @@ inline Plan plan_call(int n_frames, const uint64_t *frame_off, const uint64_t *f
         g.map0 = u;
         g.prob0 = (uint32_t)pr;
         while (u < (uint32_t)p.maps.size()) {
-            const uint64_t b = map_bytes(p.map_cap[u], union_voxel);
+            const uint64_t b = point_normal ? map_coarse_bytes(p.map_cap[u]) : map_bytes(p.map_cap[u], union_voxel);
             if (g.n_maps > 0 && g.bytes + b > cap_bytes) break;
             p.maps[u].pt0 = g.pts;
             if (union_voxel) {

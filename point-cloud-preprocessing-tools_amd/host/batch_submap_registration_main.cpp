@@ -1,5 +1,8 @@
 /*
- * batch_submap_registration <match_result_text_file> <keyframes_root_dir> <half_window> [<chunk> [<map_leaf>]]
+ * batch_submap_registration          <match_result_text_file> <keyframes_root_dir> <half_window> [<chunk> [<map_leaf>]]
+ * batch_submap_top_part_registration <match_result_text_file> <keyframes_root_dir> <half_window> [<chunk> [<map_leaf>]]
+ *
+ * One source, built twice (BEV_SUBMAP_TOP_PART 0 / 1).  The first tool:
  *
  * Scan-to-map registration: batch_whole_registration with a LOCAL MAP as every match's target.  The match list
  * is batch_whole_registration's ("query match yaw" per line); the indices name the sorted files of
@@ -19,6 +22,15 @@
  * batch_whole_registration's.  The matches go in chunks of consecutive matches
  * naming at most <chunk> distinct files (default 256, at least 2 * half_window + 2; the results do not depend on it).  Wrong
  * arguments, an unreadable match list or pose file, an index outside the files or an unreadable cloud exit 1.
+ *
+ * batch_submap_top_part_registration is batch_top_part_registration against the same windows: arguments, window
+ * rule, chunking, refusals and the pose reader's redirection are those above.  Per chunk it runs the registration front end
+ * on every file (leaf 0.2, radius 2, viewpoint 0), coarse point-to-plane ICP of the query's PointNormal cloud against the
+ * window's moved PointNormal clouds from theta and theta + 180 (bev_submap_coarse_registration_device_resident, the coarse
+ * defaults), then fine ICP from the better coarse result (bev_submap_voxel_registration_device_resident with the coarse table,
+ * bev_icp_fine_defaults() and map_leaf).  Bookkeeping, both [TIME] lines, the summary line and the report file
+ * (icp_precision_report.txt: the final transform against the chosen coarse one) are batch_top_part_registration's; with half_window
+ * 0 and map_leaf 0 it is that tool.
  */
 #include <chrono>
 #include <cmath>
@@ -35,7 +47,17 @@
 #include "Registration.h"
 #include "SubmapWindows.h"
 
+#ifndef BEV_SUBMAP_TOP_PART
+#define BEV_SUBMAP_TOP_PART 0
+#endif
+
 bev_ctx_t *bevhost_context(); /* BatchMultiBevGen.cpp (host) */
+
+#if BEV_SUBMAP_TOP_PART
+#define BEV_TOOL_NAME "batch_submap_top_part_registration"
+#else
+#define BEV_TOOL_NAME "batch_submap_registration"
+#endif
 
 namespace {
 
@@ -47,8 +69,17 @@ void hip_or_die(hipError_t e, const char *what)
     }
 }
 
-const char kUsage[] =
-    "Usage: batch_submap_registration <match_result_text_file> <keyframes_root_dir> <half_window> [<chunk> [<map_leaf>]]\n";
+#if BEV_SUBMAP_TOP_PART
+void bev_or_die(int rc, const char *what)
+{
+    if (rc != BEV_OK) {
+        std::cerr << what << ": " << bev_strerror(rc) << "\n";
+        std::exit(2);
+    }
+}
+#endif
+
+const char kUsage[] = "Usage: " BEV_TOOL_NAME " <match_result_text_file> <keyframes_root_dir> <half_window> [<chunk> [<map_leaf>]]\n";
 
 /* a finite number >= 0 and nothing else */
 bool parse_map_leaf(const char *s, float *out)
@@ -86,7 +117,11 @@ int main(int argc, char **argv)
         return 1;
     }
     chunk = std::max(chunk, 2 * half + 2);
+#if BEV_SUBMAP_TOP_PART
+    std::ofstream report("./icp_precision_report.txt");
+#else
     std::ofstream report("./icp_precision_report_3d_icp_directly.txt"), submap_report("./icp_precision_report_submap.txt");
+#endif
     std::vector<MatchResult> matches;
     try {
         matches = loadMatchResults(argv[1]);
@@ -111,8 +146,8 @@ int main(int argc, char **argv)
             return 1;
         }
     sensor_params_ = getSensorParams(parseSensorType("HDL_64E")); /* (the context follows a sensor; packed clouds read none) */
-    const bev_icp_params_t prm = bev_icp_whole_defaults();
-    double t_fine = 0.0;
+    const bev_icp_params_t prm = BEV_SUBMAP_TOP_PART ? bev_icp_fine_defaults() : bev_icp_whole_defaults();
+    double t_coarse = 0.0, t_fine = 0.0;
     int count_success = 0, count_failure = 0;
     using clk = std::chrono::steady_clock;
 
@@ -171,6 +206,54 @@ int main(int argc, char **argv)
                                      clouds[f].points.size() * sizeof(bev_point_t), hipMemcpyHostToDevice),
                            "hipMemcpy");
         hip_or_die(hipMalloc(&d_fine, n * sizeof(bev_icp_result_t)), "hipMalloc");
+#if BEV_SUBMAP_TOP_PART
+        void *d_pn = nullptr, *d_cnt = nullptr, *d_coarse = nullptr, *d_best = nullptr;
+        size_t n_max = 1;
+        for (int f = 0; f < F; ++f) n_max = std::max<size_t>(n_max, offs[f + 1] - offs[f]);
+        const size_t stride = bev_regfront_max_out(n_max);
+        hip_or_die(hipMalloc(&d_pn, (size_t)F * stride * 48), "hipMalloc");
+        hip_or_die(hipMalloc(&d_cnt, (size_t)F * 4), "hipMalloc");
+        hip_or_die(hipMalloc(&d_coarse, n * 2 * sizeof(bev_icp_result_t)), "hipMalloc");
+        hip_or_die(hipMalloc(&d_best, n * 4), "hipMalloc");
+        const float vp[3] = {0.0f, 0.0f, 0.0f};
+        bev_or_die(bev_registration_front_device_resident(ctx, F, static_cast<bev_point_t *>(d_pts), offs.data(), 0.2f, 2.0f, vp,
+                                                          d_pn, stride, static_cast<uint32_t *>(d_cnt)),
+                   "bev_registration_front_device_resident");
+        bev_or_die(bev_submap_coarse_registration_device_resident(ctx, F, d_pn, stride, static_cast<uint32_t *>(d_cnt), (int)n,
+                                                                  map_offs.data(), entry_frame.data(), entry_pose.data(), (int)n,
+                                                                  cm.data(), nullptr, static_cast<bev_icp_result_t *>(d_coarse),
+                                                                  static_cast<int32_t *>(d_best)),
+                   "bev_submap_coarse_registration_device_resident");
+        bev_or_die(bev_synchronize(ctx), "bev_synchronize");
+        auto t1 = clk::now();
+        bev_or_die(bev_submap_voxel_registration_device_resident(ctx, F, static_cast<bev_point_t *>(d_pts), offs.data(), 0.2f,
+                                                                 map_leaf, (int)n, map_offs.data(), entry_frame.data(),
+                                                                 entry_pose.data(), (int)n, cm.data(),
+                                                                 static_cast<bev_icp_result_t *>(d_coarse),
+                                                                 static_cast<int32_t *>(d_best), &prm,
+                                                                 static_cast<bev_icp_result_t *>(d_fine)),
+                   "bev_submap_voxel_registration_device_resident");
+        bev_or_die(bev_synchronize(ctx), "bev_synchronize");
+        auto t2 = clk::now();
+        t_coarse += std::chrono::duration<double, std::milli>(t1 - t0).count();
+        t_fine += std::chrono::duration<double, std::milli>(t2 - t1).count();
+        std::vector<bev_icp_result_t> fine(n), coarse(2 * n);
+        std::vector<int32_t> best(n);
+        hip_or_die(hipMemcpy(fine.data(), d_fine, n * sizeof(bev_icp_result_t), hipMemcpyDeviceToHost), "hipMemcpy");
+        hip_or_die(hipMemcpy(coarse.data(), d_coarse, 2 * n * sizeof(bev_icp_result_t), hipMemcpyDeviceToHost), "hipMemcpy");
+        hip_or_die(hipMemcpy(best.data(), d_best, n * 4, hipMemcpyDeviceToHost), "hipMemcpy");
+        for (void *p : {d_pts, d_pn, d_cnt, d_coarse, d_best, d_fine}) (void)hipFree(p);
+        for (size_t k = 0; k < n; ++k) {
+            if (fine[k].fitness > 1.5f) {
+                ++count_failure;
+                continue;
+            }
+            ++count_success;
+            float xy, yaw;
+            icpPrecisionReport(fine[k].T, coarse[2 * k + (best[k] ? 1 : 0)].T, xy, yaw);
+            report << xy << " " << yaw << "\n";
+        }
+#else
         int rc = map_leaf > 0.0f
                      ? bev_submap_voxel_registration_device_resident(ctx, F, static_cast<bev_point_t *>(d_pts), offs.data(), 0.2f,
                                                                      map_leaf, (int)n, map_offs.data(), entry_frame.data(),
@@ -201,13 +284,18 @@ int main(int argc, char **argv)
             icpPrecisionReport(fine[k].T, guess, xy, yaw);
             submap_report << xy << " " << yaw << "\n";
         }
+#endif
         m0 = m1;
     }
+    t_coarse /= matches.size();
     t_fine /= matches.size();
+    if (BEV_SUBMAP_TOP_PART) std::cout << "[TIME] Avg Tiempo for 1st Stage (coarse): " << t_coarse << "\n";
     std::cout << "[TIME] Avg Tiempo for 2nd Stage (fine): " << t_fine << "\n";
     std::cout << "count_success: " << count_success << ", count_failure: " << count_failure
               << ", SR: " << (1.0f * count_success) / (count_success + count_failure) << ". \n";
     report.close();
+#if !BEV_SUBMAP_TOP_PART
     submap_report.close();
+#endif
     return 0;
 }
