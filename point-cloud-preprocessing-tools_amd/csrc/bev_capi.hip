@@ -1,6 +1,7 @@
 /*
  * bev_capi.hip — context (bev_ctx.h), workspace and the extern "C" boundary declared in include/bev_mi355x.h, but for
- * the batched calls over packed frames (bev_capi_packed.hip) and the registration entry points (bev_capi_reg.hip).
+ * the batched calls over packed frames (bev_capi_packed.hip) and the registration entry points (bev_capi_reg.hip, frame against
+ * frame; bev_capi_submap_reg.hip, frames against submaps).
  * Host-side only; the kernels are in bev_kernels.hip.
  *
  * There is deliberately no CPU implementation behind these entry points: if

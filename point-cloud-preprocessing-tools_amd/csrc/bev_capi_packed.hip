@@ -304,7 +304,7 @@ int submap_float_frames(bev_ctx *c, const bev_point_t *d_clouds, const uint64_t 
 
 } // namespace
 
-/* What the submap entry points (and those of bev_capi_reg.hip) check of the maps: BEV_OK, or what the entry point returns.
+/* What the submap entry points (and those of bev_capi_submap_reg.hip) check of the maps: BEV_OK, or what the entry point returns.
  * The entry arrays are read only when their length has passed. */
 int bevh::check_submap_entries(int n_frames, int n_maps, const uint64_t *map_offs, const int32_t *entry_frame,
                                const float *entry_pose)

@@ -1,0 +1,370 @@
+/*
+ * bev_capi_submap_reg.hip — the scan-to-map part of the extern "C" boundary declared in include/bev_mi355x.h: fine ICP of frames
+ * against submaps, the voxel grid over a map's union in front of it (§6l), coarse ICP against them (§6m).
+ * Host-side only: the kernels are in bev_kernels.hip, the plan of a call in bev_submap_reg_plan.h; bev_reg_host.h is shared with
+ * bev_capi_reg.hip, the context (bev_ctx.h) with every file of the C ABI.  What is shared and what is not: DESIGN.md §6n.
+ */
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "bev_reg_host.h"
+
+#include "bev_libm_f64.h"
+
+using namespace bevk;
+using namespace bevh;
+using bevsubreg::Call, bevsubreg::Group, bevsubreg::Options, bevsubreg::Plan;
+
+namespace {
+
+/* bytes of a launch group's maps (BEV_SUBMAP_REG_GROUP): 8 GiB, of the order of the voxel clouds of a call on a thousand sweeps,
+ * and hundreds of maps of full sweeps in one launch (a map is one workgroup of k_submap_target, a match one of k_submap_icp) */
+constexpr uint64_t kSubmapRegCap = (uint64_t)8 << 30;
+uint64_t group_cap(const bev_ctx *c) { return c->submap_reg_group ? (uint64_t)c->submap_reg_group : kSubmapRegCap; }
+
+/* what the fine entries check behind their own arguments: BEV_OK, or what the entry returns */
+int submap_reg_check(const Call &call)
+{
+    const int n_frames = call.frames.size();
+    BEVCK(check_submap_entries(n_frames, call.n_maps, call.map_offs, call.entry_frame, call.entry_pose));
+    if (!matches_in_range(call.matches, call.n_matches, n_frames, call.n_maps)) return BEV_ERR_INVALID_ARG;
+    for (int g = 0; g < call.n_maps; ++g)
+        if (bevsubreg::map_capacity(call.frames.n.data(), call.map_offs, call.entry_frame, g) > BEV_SUBMAP_REG_MAX_TARGET)
+            return BEV_ERR_TOO_LARGE;
+    return BEV_OK;
+}
+
+/* the plan's tables in one block of tab, the device's on return: the slots (fine), the maps, the entries (64-byte aligned), the
+ * caller's problems if it has any, the maps' first keys (union_voxel; else nullptr) */
+struct PlanDev {
+    void *slots, *maps, *entries, *probs, *key0;
+};
+int plan_up(bev_ctx *c, UploadTable &tab, const Plan &plan, const Options &opt, PlanDev &d, const void *probs = nullptr,
+            size_t prob_bytes = 0)
+{
+    static_assert(sizeof(bevsubreg::Slot) == sizeof(FineSlot), "the plan's slots are k_fine_voxel's");
+    const void *const src[] = {plan.slots.data(), plan.maps.data(), plan.entries.data(), probs, plan.map_key0.data()};
+    const size_t sz[] = {opt.point_normal ? 0 : plan.slots.size() * sizeof(FineSlot), plan.maps.size() * sizeof(bevsubreg::Map),
+                         plan.entries.size() * sizeof(bevsubreg::Entry), prob_bytes, opt.union_voxel ? plan.maps.size() * 8 : 0};
+    void **const dst[] = {&d.slots, &d.maps, &d.entries, &d.probs, &d.key0};
+    BEVCK(table_up(c, tab, sz, src, dst));
+    if (!sz[4]) d.key0 = nullptr;
+    return BEV_OK;
+}
+
+/* ---- the fine path: registration (§6k, §6l) and the cloud call (§6l) ---- */
+
+/* A fine call's workspace in fine_buf, and its tables: the voxel clouds of the slots (no grids: no frame is a target), the scratch
+ * of a voxel launch and of an ICP launch, the entries' first indices, the maps of one launch group.  Of the group's arrays, a call
+ * with matches (icp: every one but the cloud call) has t.pts and the search grids t.sorted, t.hdr, t.cell_off; the union grid
+ * (vox) has v.keys, v.vstart and thins into t.pts; who concatenates into an array of its own (vox, the cloud call): v.moved, v.vh */
+struct SubmapFine {
+    FineWork w{};
+    SubmapRegWork t{};
+    SubmapVoxWork v{};
+    uint32_t *ent_start = nullptr;
+    PlanDev d{};
+};
+int submap_fine_work(bev_ctx *c, const Plan &plan, const Options &opt, SubmapFine &s)
+{
+    const bool icp = !opt.all_maps, vox = opt.union_voxel, staged = vox || !icp;
+    const size_t U = plan.slots.size(), P = plan.probs.size(), E = plan.entries.size(), Pn = plan.Pn, Kn = pow2_at_least(Pn);
+    const size_t G = std::min(U, (size_t)kFineVoxelGroup), L = std::min(P, (size_t)kFineProblemsPerLaunch);
+    const size_t T = std::max<size_t>((size_t)plan.max_group_pts, 1), M = std::max<size_t>(plan.max_group_maps, 1);
+    const size_t sz[] = {U * Pn * sizeof(bev_point_t), U * 4, G * Kn * 8, G * (Pn + 1) * 4, L * Pn * 16, L * Pn * 4,
+                         std::max<size_t>(E, 1) * 4, icp || vox ? T * 16 : 0, icp ? T * 16 : 0, icp ? M * sizeof(IcpGridHdr) : 0,
+                         icp ? M * 4 * (size_t)(kFineCells + 1) : 0, staged ? T * 16 : 0,
+                         vox ? std::max<size_t>((size_t)plan.max_group_keys, 1) * 8 : 0, vox ? (T + M) * 4 : 0,
+                         staged ? M * sizeof(SubvoxHdr) : 0};
+    void **const dst[] = {(void **)&s.w.vox, (void **)&s.w.vox_n, (void **)&s.w.keys, (void **)&s.w.vstart, (void **)&s.w.cur,
+                          (void **)&s.w.corr, (void **)&s.ent_start, (void **)&s.t.pts, (void **)&s.t.sorted, (void **)&s.t.hdr,
+                          (void **)&s.t.cell_off, (void **)&s.v.moved, (void **)&s.v.keys, (void **)&s.v.vstart, (void **)&s.v.vh};
+    BEVCK(c->reg.fine_buf.grow(c, carve(nullptr, sz, dst)));
+    carve(c->reg.fine_buf.p, sz, dst);
+    if (!icp) s.t.sorted = nullptr, s.t.hdr = nullptr, s.t.cell_off = nullptr; /* k_submap_vox_finish builds no grid at nullptr */
+    s.w.Pn = Pn;
+    s.w.Kn = Kn;
+    return BEV_OK;
+}
+
+/* the workspace, the tables and the voxel clouds of the plan's slots: frame f = frames.n[f] records at frames.off[f] of d_clouds */
+int submap_fine_begin(bev_ctx *c, const Plan &plan, const Options &opt, const bev_point_t *d_clouds, float leaf, SubmapFine &s,
+                      const std::vector<FineProblem> &probs = {})
+{
+    BEVCK(submap_fine_work(c, plan, opt, s));
+    BEVCK(plan_up(c, c->reg.fine_tab, plan, opt, s.d, probs.data(), probs.size() * sizeof(FineProblem)));
+    s.v.key0 = static_cast<const uint64_t *>(s.d.key0);
+    return fine_voxel(c, d_clouds, static_cast<const FineSlot *>(s.d.slots), (int)plan.slots.size(), s.w, leaf);
+}
+
+/* a group's targets in s.t.pts (the plain cloud call: in s.v.moved): the entries' voxel clouds moved and concatenated, with their
+ * search grids where the call has matches; map_leaf > 0: thinned by the voxel grid over the union */
+void submap_fine_targets(bev_ctx *c, const Group &g, const Options &opt, const SubmapFine &s, float map_leaf)
+{
+    const int gm = (int)g.n_maps;
+    const PlanDev &d = s.d;
+    if (!opt.union_voxel && !opt.all_maps) {
+        ProfScope ps(c, K_SUBMAP_TARGET, gm);
+        launch_submap_target(d.maps, g.map0, gm, d.entries, s.w, s.ent_start, s.t, c->stream);
+        return;
+    }
+    {
+        ProfScope ps(c, K_SUBMAP_VOX_MOVE, gm);
+        launch_submap_vox_move(d.maps, g.map0, gm, d.entries, s.w, s.ent_start, s.v, c->stream);
+    }
+    if (!opt.union_voxel) return;
+    {
+        ProfScope ps(c, K_SUBMAP_VOX_KEYS, gm);
+        launch_submap_vox_keys(d.maps, g.map0, gm, s.v, map_leaf, c->stream);
+    }
+    const uint32_t tiles = bevsubvox::tiles(g.max_slots);
+    for (const bevsubvox::Stage &sg : bevsubvox::schedule(g.max_slots)) {
+        ProfScope ps(c, sg.kind == bevsubvox::kStageGlobal ? K_SUBMAP_VOX_GLOBAL : K_SUBMAP_VOX_TILE, gm);
+        launch_submap_vox_stage(sg.kind, sg.k, sg.j, g.map0, gm, tiles, s.v, c->stream);
+    }
+    ProfScope ps(c, K_SUBMAP_VOX_FINISH, gm);
+    launch_submap_vox_finish(d.maps, g.map0, gm, s.v, s.t, c->stream);
+}
+
+/* the registration call on the context's stream, behind the entries' checks and begin_call.  map_leaf > 0: the maps are thinned
+ * (DESIGN.md §6l); 0: §6k's launches and workspace */
+int submap_reg_frames(bev_ctx *c, const bev_point_t *d_clouds, const Call &call, float leaf, float map_leaf,
+                      const bev_icp_result_t *d_coarse, const int32_t *d_best, const bev_icp_params_t &prm,
+                      bev_icp_result_t *d_results)
+{
+    Options opt;
+    opt.union_voxel = map_leaf > 0.0f;
+    const Plan plan = bevsubreg::plan_call(call, opt, group_cap(c));
+    std::vector<FineProblem> probs(plan.probs.size());
+    for (size_t i = 0; i < probs.size(); ++i) {
+        const bevsubreg::Problem &pp = plan.probs[i];
+        FineProblem &pb = probs[i];
+        pb.src_slot = pp.src_slot;
+        pb.tgt_slot = pp.map;
+        pb.result = pp.result;
+        pb.coarse_match = d_coarse ? pp.result : 0xffffffffu;
+        bevx::icp_tool_guess(call.matches[pp.result].angle_guess, 0, pb.guess);
+    }
+    SubmapFine s;
+    BEVCK(submap_fine_begin(c, plan, opt, d_clouds, leaf, s, probs));
+    const FineProblem *d_probs = static_cast<const FineProblem *>(s.d.probs);
+    for (const Group &g : plan.groups) { /* one behind the other: the stream's order hands the maps' arrays on */
+        submap_fine_targets(c, g, opt, s, map_leaf);
+        for (uint32_t p0 = 0; p0 < g.n_probs; p0 += kFineProblemsPerLaunch) {
+            const int n = (int)std::min<uint32_t>(kFineProblemsPerLaunch, g.n_probs - p0);
+            ProfScope ps(c, K_SUBMAP_ICP, n);
+            launch_submap_icp(d_probs + g.prob0 + p0, n, s.d.maps, g.map0, s.w, s.t, d_coarse, d_best, prm, d_results, c->stream);
+        }
+    }
+    HIPCK(c, hipGetLastError());
+    return BEV_OK;
+}
+
+/* ---- the coarse path (§6m) ---- */
+
+/* a coarse call's workspace in the coarse stage's buffer: the scratch of an ICP launch, the entries' first indices, the maps of
+ * one launch group */
+int submap_coarse_work(bev_ctx *c, const Plan &plan, size_t stride, SubmapCoarseWork &t, uint32_t *&ent_start)
+{
+    const size_t L = std::min(2 * plan.probs.size(), (size_t)kIcpProblemsPerLaunch), E = plan.entries.size();
+    const size_t T = std::max<size_t>((size_t)plan.max_group_pts, 1), M = std::max<size_t>(plan.max_group_maps, 1);
+    t = SubmapCoarseWork{};
+    const size_t sz[] = {L * 16 * stride, std::max<size_t>(E, 1) * 4, T * 48, T * 16, M * sizeof(IcpGridHdr),
+                         M * 4 * (size_t)(kIcpCells + 1)};
+    void **const dst[] = {(void **)&t.cur, (void **)&ent_start, (void **)&t.rows, (void **)&t.sorted, (void **)&t.hdr,
+                          (void **)&t.cell_off};
+    BEVCK(c->reg.icp_buf.grow(c, carve(nullptr, sz, dst)));
+    carve(c->reg.icp_buf.p, sz, dst);
+    return BEV_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+/* ---- scan-to-map fine ICP: frames against submaps (bev_submap_reg_plan.h, bev_submap_reg.h) ------- */
+int bev_submap_voxel_registration_device_resident(bev_ctx_t *c, int n_frames, const bev_point_t *d_clouds,
+                                                  const uint64_t *h_offsets, float leaf, float map_leaf, int n_maps,
+                                                  const uint64_t *h_map_offsets, const int32_t *h_entry_frame,
+                                                  const float *h_entry_pose, int n_matches, const bev_match_t *h_matches,
+                                                  const bev_icp_result_t *d_coarse, const int32_t *d_best,
+                                                  const bev_icp_params_t *params, bev_icp_result_t *d_results)
+{
+    const bev_icp_params_t prm = params ? *params : bev_icp_fine_defaults();
+    if (!c || n_frames < 0 || n_maps < 0 || n_matches < 0 || !icp_params_ok(prm) || !positive(leaf) || !not_negative(map_leaf) ||
+        (d_coarse == nullptr) != (d_best == nullptr))
+        return BEV_ERR_INVALID_ARG;
+    Call call{{}, n_maps, h_map_offsets, h_entry_frame, h_entry_pose, n_matches, h_matches};
+    if (n_matches > 0) {
+        if (!h_matches || !d_results) return BEV_ERR_INVALID_ARG;
+        if (!frame_table(n_frames, h_offsets, (uint64_t)c->geo.S, call.frames)) return BEV_ERR_INVALID_ARG;
+        BEVCK(submap_reg_check(call));
+        if (!d_clouds) return BEV_ERR_INVALID_ARG;
+    }
+    BEVCK(begin_call(c, false));
+    if (n_matches == 0) return BEV_OK;
+    BEVCK(wait_default_stream(c));
+    BEVCK(submap_reg_frames(c, d_clouds, call, leaf, map_leaf, d_coarse, d_best, prm, d_results));
+    return record_tail(c);
+}
+
+int bev_submap_registration_device_resident(bev_ctx_t *c, int n_frames, const bev_point_t *d_clouds, const uint64_t *h_offsets,
+                                            float leaf, int n_maps, const uint64_t *h_map_offsets, const int32_t *h_entry_frame,
+                                            const float *h_entry_pose, int n_matches, const bev_match_t *h_matches,
+                                            const bev_icp_result_t *d_coarse, const int32_t *d_best,
+                                            const bev_icp_params_t *params, bev_icp_result_t *d_results)
+{
+    return bev_submap_voxel_registration_device_resident(c, n_frames, d_clouds, h_offsets, leaf, 0.0f, n_maps, h_map_offsets,
+                                                         h_entry_frame, h_entry_pose, n_matches, h_matches, d_coarse, d_best,
+                                                         params, d_results);
+}
+
+int bev_submap_voxel_cloud_device_resident(bev_ctx_t *c, int n_frames, const bev_point_t *d_clouds, const uint64_t *h_offsets,
+                                           float leaf, float map_leaf, int n_maps, const uint64_t *h_map_offsets,
+                                           const int32_t *h_entry_frame, const float *h_entry_pose, uint64_t out_stride,
+                                           float *d_out, uint32_t *d_counts)
+{
+    if (!c || n_frames < 0 || n_maps < 0 || !positive(leaf) || !not_negative(map_leaf)) return BEV_ERR_INVALID_ARG;
+    Call call{{}, n_maps, h_map_offsets, h_entry_frame, h_entry_pose, 0, nullptr};
+    if (n_maps > 0) {
+        if (!d_out || !d_counts) return BEV_ERR_INVALID_ARG;
+        if (!frame_table(n_frames, h_offsets, (uint64_t)c->geo.S, call.frames)) return BEV_ERR_INVALID_ARG;
+        BEVCK(submap_reg_check(call));
+        for (int g = 0; g < n_maps; ++g)
+            if (bevsubreg::map_capacity(call.frames.n.data(), h_map_offsets, h_entry_frame, g) > out_stride)
+                return BEV_ERR_INVALID_ARG;
+        if (!d_clouds) return BEV_ERR_INVALID_ARG;
+    }
+    BEVCK(begin_call(c, false));
+    if (n_maps == 0) return BEV_OK;
+    BEVCK(wait_default_stream(c));
+    /* no matches and no ICP: every map's target, built as the registration call builds it, goes out */
+    Options opt;
+    opt.union_voxel = map_leaf > 0.0f;
+    opt.all_maps = true;
+    const Plan plan = bevsubreg::plan_call(call, opt, group_cap(c));
+    SubmapFine s;
+    BEVCK(submap_fine_begin(c, plan, opt, d_clouds, leaf, s));
+    for (const Group &g : plan.groups) {
+        submap_fine_targets(c, g, opt, s, map_leaf);
+        uint64_t largest = 0;
+        for (uint32_t u = g.map0; u < g.map0 + g.n_maps; ++u) largest = std::max(largest, plan.map_cap[u]);
+        const uint32_t parts = (uint32_t)std::min<uint64_t>((largest + 4 * kFineThreads - 1) / (4 * kFineThreads), 256);
+        ProfScope ps(c, K_SUBMAP_VOX_OUT, (int)g.n_maps);
+        launch_submap_vox_out(s.d.maps, g.map0, (int)g.n_maps, parts, s.v.vh, opt.union_voxel ? s.t.pts : s.v.moved,
+                              reinterpret_cast<float4 *>(d_out), out_stride, d_counts, c->stream);
+    }
+    HIPCK(c, hipGetLastError());
+    return record_tail(c);
+}
+
+int bev_submap_voxel_registration_batch(bev_ctx_t *c, int n_frames, const bev_point_t *const *clouds, const uint32_t *n_pts,
+                                        float leaf, float map_leaf, int n_maps, const uint64_t *h_map_offsets,
+                                        const int32_t *h_entry_frame, const float *h_entry_pose, int n_matches,
+                                        const bev_match_t *h_matches, const bev_icp_params_t *params, bev_icp_result_t *results)
+{
+    const bev_icp_params_t prm = params ? *params : bev_icp_fine_defaults();
+    if (!c || n_frames < 0 || n_maps < 0 || n_matches < 0 || !icp_params_ok(prm) || !positive(leaf) || !not_negative(map_leaf))
+        return BEV_ERR_INVALID_ARG;
+    if (n_frames > 0 && (!clouds || !n_pts)) return BEV_ERR_INVALID_ARG;
+    for (int f = 0; f < n_frames; ++f)
+        if (n_pts[f] && !clouds[f]) return BEV_ERR_INVALID_ARG;
+    Call call{{}, n_maps, h_map_offsets, h_entry_frame, h_entry_pose, n_matches, h_matches};
+    if (n_matches > 0) {
+        if (!h_matches || !results) return BEV_ERR_INVALID_ARG;
+        call.frames.n.assign(n_pts, n_pts + n_frames);
+        BEVCK(submap_reg_check(call));
+    }
+    BEVCK(begin_call(c, false));
+    if (n_matches == 0) return BEV_OK;
+    std::vector<size_t> offs((size_t)std::max(n_frames, 1));
+    BEVCK(fine_upload(c, clouds, n_pts, n_frames, offs.data()));
+    call.frames.off.assign(offs.begin(), offs.begin() + n_frames);
+    BEVCK(c->reg.sub_res.grow(c, (size_t)n_matches * sizeof(bev_icp_result_t)));
+    bev_icp_result_t *d_res = static_cast<bev_icp_result_t *>(c->reg.sub_res.p);
+    BEVCK(submap_reg_frames(c, static_cast<const bev_point_t *>(c->reg.fine_in.p), call, leaf, map_leaf, nullptr, nullptr, prm, d_res));
+    HIPCK(c, hipMemcpyAsync(results, d_res, (size_t)n_matches * sizeof(bev_icp_result_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    return BEV_OK;
+}
+
+int bev_submap_registration_batch(bev_ctx_t *c, int n_frames, const bev_point_t *const *clouds, const uint32_t *n_pts, float leaf,
+                                  int n_maps, const uint64_t *h_map_offsets, const int32_t *h_entry_frame,
+                                  const float *h_entry_pose, int n_matches, const bev_match_t *h_matches,
+                                  const bev_icp_params_t *params, bev_icp_result_t *results)
+{
+    return bev_submap_voxel_registration_batch(c, n_frames, clouds, n_pts, leaf, 0.0f, n_maps, h_map_offsets, h_entry_frame,
+                                               h_entry_pose, n_matches, h_matches, params, results);
+}
+
+/* ---- scan-to-map coarse ICP: PointNormal frames against submaps (bev_submap_coarse.h) ------------------ */
+int bev_submap_coarse_registration_device_resident(bev_ctx_t *c, int n_frames, const void *d_pn, size_t stride,
+                                                   const uint32_t *d_counts, int n_maps, const uint64_t *h_map_offsets,
+                                                   const int32_t *h_entry_frame, const float *h_entry_pose, int n_matches,
+                                                   const bev_match_t *h_matches, const bev_icp_params_t *params,
+                                                   bev_icp_result_t *d_results, int32_t *d_best)
+{
+    const bev_icp_params_t prm = params ? *params : bev_icp_coarse_defaults();
+    if (!c || n_frames < 0 || n_maps < 0 || n_matches < 0 || !icp_params_ok(prm)) return BEV_ERR_INVALID_ARG;
+    if (n_matches > 0) {
+        if (!d_pn || !d_counts || !h_matches || !d_results || !d_best || stride == 0) return BEV_ERR_INVALID_ARG;
+        BEVCK(check_submap_entries(n_frames, n_maps, h_map_offsets, h_entry_frame, h_entry_pose));
+        if (!matches_in_range(h_matches, n_matches, n_frames, n_maps)) return BEV_ERR_INVALID_ARG;
+        /* a map's capacity is n_entries * stride rows: the true counts live on the device, and the host does not wait for them */
+        for (int g = 0; g < n_maps; ++g) {
+            const uint64_t ne = h_map_offsets[g + 1] - h_map_offsets[g];
+            if (ne && (uint64_t)stride > BEV_SUBMAP_COARSE_MAX_TARGET / ne) return BEV_ERR_TOO_LARGE;
+        }
+    }
+    BEVCK(begin_call(c, false));
+    if (n_matches == 0) return BEV_OK;
+    BEVCK(wait_default_stream(c));
+    /* §6k's plan with every frame counted at stride rows and a PointNormal map's bytes */
+    Call call{{}, n_maps, h_map_offsets, h_entry_frame, h_entry_pose, n_matches, h_matches};
+    call.frames.off.assign((size_t)n_frames, 0);
+    call.frames.n.assign((size_t)n_frames, (uint64_t)stride);
+    Options opt;
+    opt.point_normal = true;
+    Plan plan = bevsubreg::plan_call(call, opt, group_cap(c));
+    for (bevsubreg::Entry &en : plan.entries) en.slot = (uint32_t)plan.slot_frame[en.slot]; /* the device reads the frame */
+    SubmapCoarseWork t;
+    uint32_t *ent_start = nullptr;
+    BEVCK(submap_coarse_work(c, plan, stride, t, ent_start));
+    std::vector<IcpProblem> probs; /* two problems per match, the guesses adjacent */
+    probs.reserve(2 * plan.probs.size());
+    for (const bevsubreg::Problem &pp : plan.probs)
+        for (int g = 0; g < 2; ++g) {
+            IcpProblem pb{};
+            pb.src_frame = (uint32_t)h_matches[pp.result].query_idx;
+            pb.tgt_frame = 0xffffffffu; /* (not read: the target is a map) */
+            pb.tgt_slot = pp.map;
+            pb.result = 2 * pp.result + (uint32_t)g;
+            bevx::icp_tool_guess(h_matches[pp.result].angle_guess, g, pb.guess);
+            probs.push_back(pb);
+        }
+    PlanDev d;
+    BEVCK(plan_up(c, c->reg.icp_tab, plan, opt, d, probs.data(), probs.size() * sizeof(IcpProblem)));
+    const float *pn = static_cast<const float *>(d_pn);
+    const IcpProblem *d_probs = static_cast<const IcpProblem *>(d.probs);
+    for (const Group &g : plan.groups) {
+        {
+            ProfScope ps(c, K_SUBMAP_PN_TARGET, (int)g.n_maps);
+            launch_submap_pn_target(d.maps, g.map0, (int)g.n_maps, d.entries, pn, stride, d_counts, ent_start, t, c->stream);
+        }
+        for (uint32_t p0 = 0; p0 < 2 * g.n_probs; p0 += kIcpProblemsPerLaunch) {
+            const int n = (int)std::min<uint32_t>(kIcpProblemsPerLaunch, 2 * g.n_probs - p0);
+            ProfScope ps(c, K_SUBMAP_COARSE_ICP, n);
+            launch_submap_coarse_icp(pn, stride, d_counts, d_probs + 2 * (size_t)g.prob0 + p0, n, d.maps, g.map0, t, prm, d_results,
+                                     c->stream);
+        }
+    }
+    {
+        ProfScope ps(c, K_ICP_BEST, n_matches);
+        launch_icp_best(d_results, n_matches, d_best, c->stream);
+    }
+    HIPCK(c, hipGetLastError());
+    return record_tail(c);
+}
+
+} /* extern "C" */

@@ -1,7 +1,8 @@
 /*
- * bev_ctx.h — the context behind bev_ctx_t and what the three files of the C ABI share: bev_capi.hip (the context, the BEV
+ * bev_ctx.h — the context behind bev_ctx_t and what the four files of the C ABI share: bev_capi.hip (the context, the BEV
  * pipeline and the single-cloud entry points), bev_capi_packed.hip (the batched calls over packed frames), bev_capi_reg.hip
- * (the registration entry points) — among it the prologue of every call outside the fused pipeline (begin_call) and the bound
+ * (the registration entry points, frame against frame) and bev_capi_submap_reg.hip (frames against submaps; what only these
+ * two share: bev_reg_host.h) — among it the prologue of every call outside the fused pipeline (begin_call) and the bound
  * on a cloud's points (cloud_cap).  Private, like bev_internal.h.  Named namespace: struct bev_ctx is one type in all of them.
  */
 #ifndef BEV_CTX_H
@@ -112,7 +113,7 @@ struct Downloader {
     }
 };
 
-/* ---- what the batched entry points keep between calls (defined in bev_capi.hip; used by all three files) ---- */
+/* ---- what the batched entry points keep between calls (defined in bev_capi.hip; used by all four files) ---- */
 /* a device buffer that grows when a call needs more */
 struct DevBuf {
     void *p = nullptr;

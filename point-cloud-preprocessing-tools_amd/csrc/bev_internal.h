@@ -1,6 +1,6 @@
 /*
  * bev_internal.h — shared between the HIP kernels (bev_kernels.hip) and the
- * C-ABI / context code (bev_capi.hip, bev_capi_reg.hip).  Not installed; the public boundary is
+ * C-ABI / context code (bev_capi*.hip).  Not installed; the public boundary is
  * include/bev_mi355x.h.
  */
 #ifndef BEV_INTERNAL_H

@@ -2,9 +2,9 @@
  * bev_libm_f64.h — double sin / cos for the coarse ICP: fdlibm's s_sin.c / s_cos.c over __kernel_sin,
  * __kernel_cos and the small / medium ranges of __ieee754_rem_pio2 (|x| <= 2^20 * pi/2), restated from the published
  * algorithm.  Beyond that range, and for non-finite x, the result is the quiet NaN 0x7ff8000000000000.  Host and device
- * (the kernel's increment, bev_icp.h; the tool's initial guesses, bev_capi_reg.hip).  Only IEEE + - * / and no FMA (see
- * bev_exact.h), so both sides round alike; tests/test_icp_cpu.py bounds the checker's independent restatement against
- * the host libm and the GPU tests compare whole ICP results byte for byte.
+ * (the kernel's increment, bev_icp.h; the tool's initial guesses, bev_capi_reg.hip and bev_capi_submap_reg.hip).  Only
+ * IEEE + - * / and no FMA (see bev_exact.h), so both sides round alike; tests/test_icp_cpu.py bounds the checker's
+ * independent restatement against the host libm and the GPU tests compare whole ICP results byte for byte.
  */
 #ifndef BEV_LIBM_F64_H
 #define BEV_LIBM_F64_H

@@ -1,0 +1,88 @@
+/*
+ * bev_reg_host.h — what the two registration files of the C ABI share over bev_ctx.h: bev_capi_reg.hip (the front end and the
+ * pair stages) and bev_capi_submap_reg.hip (scan-to-map).  Argument checks, the frame table of a packed or
+ * d_ordered buffer, upload tables laid out by carve, and the fine stage's two steps that scan-to-map runs as they are.
+ * Declarations and short inline functions, no state (RegState: bev_ctx.h).  Private.
+ */
+#ifndef BEV_REG_HOST_H
+#define BEV_REG_HOST_H
+
+#include <cmath>
+#include <cstring>
+
+#include "bev_ctx.h"
+#include "bev_submap_reg_plan.h"
+
+namespace bevh {
+
+/* a step that returns a status: anything but BEV_OK is what the caller returns */
+#define BEVCK(expr)                    \
+    do {                               \
+        const int rc_ = (expr);        \
+        if (rc_ != BEV_OK) return rc_; \
+    } while (0)
+
+constexpr size_t kRegTabMin = (size_t)1 << 16; /* smallest problem / slot table */
+
+/* ---- argument checks ---- */
+inline bool positive(float v) { return std::isfinite(v) && v > 0.0f; }      /* a leaf, a radius */
+inline bool not_negative(float v) { return std::isfinite(v) && v >= 0.0f; } /* map_leaf: 0 is "no second grid" */
+inline bool icp_params_ok(const bev_icp_params_t &p)
+{
+    return p.max_iterations >= 1 && p.max_iterations <= 1000 && std::isfinite(p.max_correspondence_distance) &&
+           p.max_correspondence_distance > 0.0;
+}
+/* every query_idx inside the n_queries frames, every match_idx inside the n_targets frames or maps */
+inline bool matches_in_range(const bev_match_t *h_matches, int n_matches, int n_queries, int n_targets)
+{
+    for (int m = 0; m < n_matches; ++m) {
+        const bev_match_t &mt = h_matches[m];
+        if (mt.query_idx < 0 || mt.query_idx >= n_queries || mt.match_idx < 0 || mt.match_idx >= n_targets) return false;
+    }
+    return true;
+}
+/* the n_frames frames of a packed buffer (h_offsets) or of d_ordered (NULL: S records each); false for decreasing offsets or
+ * a frame above 2^32 - 1 records */
+inline bool frame_table(int n_frames, const uint64_t *h_offsets, uint64_t S, bevsubreg::FrameTable &ft)
+{
+    ft.off.resize((size_t)n_frames);
+    ft.n.resize((size_t)n_frames);
+    for (int f = 0; f < n_frames; ++f) {
+        if (h_offsets && (h_offsets[f + 1] < h_offsets[f] || h_offsets[f + 1] - h_offsets[f] > 0xffffffffull)) return false;
+        ft.off[(size_t)f] = h_offsets ? h_offsets[f] : (uint64_t)f * S;
+        ft.n[(size_t)f] = h_offsets ? h_offsets[f + 1] - h_offsets[f] : S;
+    }
+    return true;
+}
+
+inline size_t pow2_at_least(size_t n)
+{
+    size_t p = 1;
+    while (p < n) p <<= 1;
+    return p;
+}
+
+/* ---- an upload table in carve's pieces: piece i is sz[i] bytes from src[i]; the block goes up the context's stream, and dst
+ * points at the device's copies ---- */
+template <size_t N>
+int table_up(bev_ctx *c, UploadTable &t, const size_t (&sz)[N], const void *const (&src)[N], void **const (&dst)[N])
+{
+    void *h;
+    const size_t total = carve(nullptr, sz, dst);
+    BEVCK(t.begin(c, total, kRegTabMin, &h));
+    carve(h, sz, dst);
+    for (size_t i = 0; i < N; ++i)
+        if (sz[i]) std::memcpy(*dst[i], src[i], sz[i]);
+    BEVCK(t.push(c, total));
+    carve(t.dev, sz, dst);
+    return BEV_OK;
+}
+
+/* ---- of the fine stage (bev_capi_reg.hip) ---- */
+/* the voxel clouds of U slots, in launches of kFineVoxelGroup, on the context's stream */
+int fine_voxel(bev_ctx *c, const bev_point_t *d_pts, const FineSlot *d_slots, int U, const FineWork &w, float leaf);
+/* host records -> c->reg.fine_in (grown on demand); offs[i]: where cloud i went */
+int fine_upload(bev_ctx *c, const bev_point_t *const *clouds, const uint32_t *n, int k, size_t *offs);
+
+} // namespace bevh
+#endif

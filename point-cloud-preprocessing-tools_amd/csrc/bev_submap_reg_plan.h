@@ -2,7 +2,7 @@
  * bev_submap_reg_plan.h — the host plan of a scan-to-map registration call (bev_submap_registration_device_resident,
  * bev_submap_registration_batch): which frames get a voxel cloud, which voxel clouds under which matrices
  * make which map's target, which maps share a launch group and which matches run against them.  Plain C++, no HIP:
- * bev_capi_reg.hip builds and uploads the plan, tests/submapregcheck builds it and checks its invariants.
+ * bev_capi_submap_reg.hip builds and uploads the plan, tests/submapregcheck builds it and checks its invariants.
  *
  *   slots    the distinct frames that a match's query or a used map's entry names, in the order of first appearance (the
  *            matches in their order, a match's query before its map's entries): one voxel cloud each;
@@ -16,15 +16,17 @@
  *            result lands at index m whatever the grouping.
  * bev_submap_plan.h sorts a group's entries by frame (its rasters are order-free) and is not used here.
  *
+ * A call is described by one Call (the frame table, the maps, the matches) and its Options:
+ *
  * union_voxel: the maps are thinned by a second voxel grid over their union (bev_submap_vox.h), so a map also
  * owns its sort keys at key0 of the group's key array (bev_submap_vox_plan.h pads them), its voxel starts and the thinned
  * points, and map_bytes counts them.  all_maps: every map of the call is used, whatever the matches name
  * (bev_submap_voxel_cloud_device_resident has none).
  *
  * point_normal: the call is bev_submap_coarse_registration_device_resident's: the frames are PointNormal clouds
- * of `stride` rows each (frame_n[f] = stride, frame_off unused), a map's capacity is n_entries * stride rows and its bytes are
+ * of `stride` rows each (frames.n[f] = stride, frames.off unused), a map's capacity is n_entries * stride rows and its bytes are
  * map_coarse_bytes; the caller makes two problems (the guesses) of every Problem.  Everything else is as above; with the
- * default (false) every call plans exactly as before.
+ * default Options every call plans exactly as before.
  */
 #ifndef BEV_SUBMAP_REG_PLAN_H
 #define BEV_SUBMAP_REG_PLAN_H
@@ -35,6 +37,7 @@
 #include <cstring>
 #include <vector>
 
+#include "../../include/bev_mi355x.h" /* bev_match_t */
 #include "bev_submap_vox_plan.h"
 
 namespace bevsubreg {
@@ -111,14 +114,34 @@ inline uint64_t map_capacity(const uint64_t *frame_n, const uint64_t *map_offs, 
     return cap;
 }
 
-/* frame f = frame_n[f] records at frame_off[f]; map g owns entries [map_offs[g], map_offs[g + 1]); entry e names frame
- * entry_frame[e] and the matrix at entry_pose + 12 * e; match m registers frame query[m] against map match_map[m] (all
- * indices checked by the caller).  cap_bytes: the group cap. */
-inline Plan plan_call(int n_frames, const uint64_t *frame_off, const uint64_t *frame_n, int n_maps, const uint64_t *map_offs,
-                      const int32_t *entry_frame, const float *entry_pose, int n_matches, const int32_t *query,
-                      const int32_t *match_map, uint64_t cap_bytes, bool union_voxel = false, bool all_maps = false,
-                      bool point_normal = false)
+/* the frames of a call: frame f = n[f] records at off[f] of the caller's buffer */
+struct FrameTable {
+    std::vector<uint64_t> off, n;
+    int size() const { return (int)n.size(); }
+};
+/* a call: map g owns entries [map_offs[g], map_offs[g + 1]); entry e names frame entry_frame[e] and the matrix at
+ * entry_pose + 12 * e; match m registers frame matches[m].query_idx against map matches[m].match_idx (all indices checked by
+ * the caller; the arrays are the caller's and outlive the struct's use) */
+struct Call {
+    FrameTable frames;
+    int n_maps = 0;
+    const uint64_t *map_offs = nullptr;
+    const int32_t *entry_frame = nullptr;
+    const float *entry_pose = nullptr;
+    int n_matches = 0;
+    const bev_match_t *matches = nullptr;
+};
+struct Options { /* see the head of the file */
+    bool union_voxel = false, all_maps = false, point_normal = false;
+};
+
+/* cap_bytes: the group cap */
+inline Plan plan_call(const Call &call, const Options &opt, uint64_t cap_bytes)
 {
+    const int n_frames = call.frames.size(), n_maps = call.n_maps, n_matches = call.n_matches;
+    const uint64_t *const frame_off = call.frames.off.data(), *const frame_n = call.frames.n.data(), *const map_offs = call.map_offs;
+    const int32_t *const entry_frame = call.entry_frame;
+    const bev_match_t *const mt = call.matches;
     Plan p;
     std::vector<int32_t> slot_of((size_t)std::max(n_frames, 0), -1), used((size_t)std::max(n_maps, 0), -1);
     auto slot = [&](int f) -> uint32_t {
@@ -132,13 +155,13 @@ inline Plan plan_call(int n_frames, const uint64_t *frame_off, const uint64_t *f
     };
     /* slots in the order of first appearance; which maps are used */
     for (int m = 0; m < n_matches; ++m) {
-        slot(query[m]);
-        const int g = match_map[m];
+        slot(mt[m].query_idx);
+        const int g = mt[m].match_idx;
         if (used[g] >= 0) continue;
         used[g] = 0;
         for (uint64_t e = map_offs[g]; e < map_offs[g + 1]; ++e) slot(entry_frame[e]);
     }
-    for (int g = 0; all_maps && g < n_maps; ++g) {
+    for (int g = 0; opt.all_maps && g < n_maps; ++g) {
         if (used[g] >= 0) continue;
         used[g] = 0;
         for (uint64_t e = map_offs[g]; e < map_offs[g + 1]; ++e) slot(entry_frame[e]);
@@ -150,7 +173,7 @@ inline Plan plan_call(int n_frames, const uint64_t *frame_off, const uint64_t *f
         Map mp{0u, (uint32_t)p.entries.size(), (uint32_t)(map_offs[g + 1] - map_offs[g])};
         for (uint64_t e = map_offs[g]; e < map_offs[g + 1]; ++e) {
             Entry en;
-            memcpy(en.m, entry_pose + 12 * (size_t)e, sizeof en.m);
+            memcpy(en.m, call.entry_pose + 12 * (size_t)e, sizeof en.m);
             en.slot = (uint32_t)slot_of[entry_frame[e]];
             en.pad[0] = en.pad[1] = en.pad[2] = 0u;
             p.entries.push_back(en);
@@ -161,11 +184,11 @@ inline Plan plan_call(int n_frames, const uint64_t *frame_off, const uint64_t *f
     }
     /* the problems: by map, the call's order among equal maps */
     std::vector<uint64_t> keys((size_t)std::max(n_matches, 0));
-    for (int m = 0; m < n_matches; ++m) keys[(size_t)m] = (uint64_t)(uint32_t)used[match_map[m]] << 32 | (uint32_t)m;
+    for (int m = 0; m < n_matches; ++m) keys[(size_t)m] = (uint64_t)(uint32_t)used[mt[m].match_idx] << 32 | (uint32_t)m;
     std::sort(keys.begin(), keys.end());
     for (uint64_t k : keys) {
         const uint32_t m = (uint32_t)k;
-        p.probs.push_back(Problem{(uint32_t)slot_of[query[m]], (uint32_t)(k >> 32), m, 0u});
+        p.probs.push_back(Problem{(uint32_t)slot_of[mt[m].query_idx], (uint32_t)(k >> 32), m, 0u});
     }
     /* the groups */
     p.map_key0.assign(p.maps.size(), 0);
@@ -175,10 +198,10 @@ inline Plan plan_call(int n_frames, const uint64_t *frame_off, const uint64_t *f
         g.map0 = u;
         g.prob0 = (uint32_t)pr;
         while (u < (uint32_t)p.maps.size()) {
-            const uint64_t b = point_normal ? map_coarse_bytes(p.map_cap[u]) : map_bytes(p.map_cap[u], union_voxel);
+            const uint64_t b = opt.point_normal ? map_coarse_bytes(p.map_cap[u]) : map_bytes(p.map_cap[u], opt.union_voxel);
             if (g.n_maps > 0 && g.bytes + b > cap_bytes) break;
             p.maps[u].pt0 = g.pts;
-            if (union_voxel) {
+            if (opt.union_voxel) {
                 const uint64_t slots = bevsubvox::key_slots(p.map_cap[u]);
                 p.map_key0[u] = g.keys;
                 g.keys += slots;

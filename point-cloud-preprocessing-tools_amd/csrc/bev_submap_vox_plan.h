@@ -2,7 +2,7 @@
  * bev_submap_vox_plan.h — the sort of a map's union voxel grid (bev_submap_vox.h): the tile size, the padding of
  * a map's key array, the list of launches that sorts the keys of every map of a launch group, and the index rules of one
  * compare-exchange.  Plain C++, no HIP (the two index rules are also compiled for the device, where the kernels use them):
- * bev_capi_reg.hip walks the schedule and launches it, tests/submapvoxcheck executes it sequentially on the host.
+ * bev_capi_submap_reg.hip walks the schedule and launches it, tests/submapvoxcheck executes it sequentially on the host.
  *
  * The sort is the ascending bitonic network over np2 keys, np2 the smallest power of two >= a map's point count (known on the
  * device only), the keys behind the points padded with ~0:

@@ -53,15 +53,17 @@ int main()
         std::vector<float> entry_pose(entry_frame.size() * 12 + 1);
         for (float &v : entry_pose) v = (float)uni(0, 1000000) / 1000.0f;
         std::vector<int32_t> query((size_t)n_matches), match_map((size_t)n_matches);
+        std::vector<bev_match_t> matches((size_t)n_matches);
         for (int m = 0; m < n_matches; ++m) {
             query[m] = (int32_t)uni(0, n_frames - 1);
             match_map[m] = (int32_t)uni(0, n_maps - 1);
+            matches[m] = bev_match_t{query[m], match_map[m], 0.0f};
         }
+        const Call desc{FrameTable{off, cnt}, n_maps, map_offs.data(), entry_frame.data(), entry_pose.data(), n_matches, matches.data()};
         uint64_t all = 0;
         for (int g = 0; g < n_maps; ++g) all += map_bytes(map_capacity(cnt.data(), map_offs.data(), entry_frame.data(), g));
         for (uint64_t cap : {(uint64_t)1, map_bytes(3000), map_bytes(12000), all / 3 + 1, all + 1}) {
-            const Plan p = plan_call(n_frames, off.data(), cnt.data(), n_maps, map_offs.data(), entry_frame.data(), entry_pose.data(),
-                                     n_matches, query.data(), match_map.data(), cap);
+            const Plan p = plan_call(desc, Options{}, cap);
             ++plans;
             /* slots */
             std::vector<int> named((size_t)n_frames, 0), used((size_t)n_maps, 0), slots_of((size_t)n_frames, 0);

@@ -113,19 +113,21 @@ int main()
         }
         std::vector<float> entry_pose(entry_frame.size() * 12 + 1);
         for (float &v : entry_pose) v = (float)uni(0, 1000000) / 1000.0f;
-        std::vector<int32_t> query((size_t)n_matches), match_map((size_t)n_matches);
+        std::vector<bev_match_t> matches((size_t)n_matches);
         for (int m = 0; m < n_matches; ++m) {
-            query[m] = (int32_t)uni(0, n_frames - 1);
-            match_map[m] = (int32_t)uni(0, n_maps - 1);
+            const int32_t query = (int32_t)uni(0, n_frames - 1); /* (in this order: the seeded calls stay the same) */
+            matches[m] = bev_match_t{query, (int32_t)uni(0, n_maps - 1), 0.0f};
         }
+        const Call desc{FrameTable{off, cnt}, n_maps, map_offs.data(), entry_frame.data(), entry_pose.data(), n_matches, matches.data()};
         uint64_t all = 0;
         for (int g = 0; g < n_maps; ++g) all += map_bytes(map_capacity(cnt.data(), map_offs.data(), entry_frame.data(), g), true);
         for (uint64_t cap : {(uint64_t)1, map_bytes(3000, true), map_bytes(12000, true), all / 3 + 1, all + 1}) {
             for (int every = 0; every < 2; ++every) {
-                const Plan base = plan_call(n_frames, off.data(), cnt.data(), n_maps, map_offs.data(), entry_frame.data(), entry_pose.data(),
-                                            n_matches, query.data(), match_map.data(), cap, false, every != 0);
-                const Plan p = plan_call(n_frames, off.data(), cnt.data(), n_maps, map_offs.data(), entry_frame.data(), entry_pose.data(),
-                                         n_matches, query.data(), match_map.data(), cap, true, every != 0);
+                Options opt;
+                opt.all_maps = every != 0;
+                const Plan base = plan_call(desc, opt, cap);
+                opt.union_voxel = true;
+                const Plan p = plan_call(desc, opt, cap);
                 ++plans;
                 CHECK(p.slot_frame == base.slot_frame && p.map_id == base.map_id && p.map_cap == base.map_cap && p.Pn == base.Pn &&
                           p.entries.size() == base.entries.size() && p.probs.size() == base.probs.size(),

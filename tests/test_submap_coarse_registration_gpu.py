@@ -31,12 +31,9 @@ import regfront_lib as rf
 import submap_coarse_cases as cc
 import submap_reg_cases as sc
 from bev_amd import ICP_RESULT_DTYPE
+from submap_reg_gpu_lib import F32, INVALID, OK, R, THREADS, TOO_LARGE, _ctx, _dev, _same
 
 pytestmark = pytest.mark.gpu
-THREADS = min(16, os.cpu_count() or 4)
-F32 = np.float32
-R = ICP_RESULT_DTYPE.itemsize
-OK, INVALID, TOO_LARGE = 0, -1, -6
 GROUP_CAP = 150000  # bytes: a few small maps per launch group
 
 
@@ -47,11 +44,6 @@ def _checkers():
     rf.build()
 
 
-def _same(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return a.shape == b.shape and a.tobytes() == b.tobytes()
-
-
 def _check(name, got, exp):
     """got, exp: ((n, 2) results, (n,) best)"""
     (gr, gb), (er, eb) = got, exp
@@ -60,16 +52,6 @@ def _check(name, got, exp):
     bad = [k for k in range(len(er)) if not _same(gr[k], er[k])]
     assert not bad, f"{name}: {len(bad)} of {len(er)} results differ, first match {bad[0] // 2} guess {bad[0] % 2}: {gr[bad[0]]} != {er[bad[0]]}"
     assert np.array_equal(np.asarray(gb), np.asarray(eb)), f"{name}: best differs at {np.flatnonzero(np.asarray(gb) != np.asarray(eb))[:5]}"
-
-
-def _dev(a):
-    import torch
-
-    return torch.from_numpy(np.ascontiguousarray(a).reshape(-1).view(np.uint8).copy()).to(torch.device("cuda:0"))
-
-
-def _ctx(max_points=1000):
-    return bev_amd.BevContext(bev_amd.params_for_sensor("HDL_32E"), device=0, max_batch=2, max_points=max_points)
 
 
 def _counts(frames):

@@ -26,13 +26,10 @@ import bev_amd
 import fineicp_lib as fl
 import reg_cases as rc
 import submap_reg_cases as sc
-from bev_amd import ICP_RESULT_DTYPE, MATCH_DTYPE, POINT_DTYPE, synth
+from bev_amd import MATCH_DTYPE, POINT_DTYPE, synth
+from submap_reg_gpu_lib import F32, INVALID, OK, R, THREADS, TOO_LARGE, _check, _ctx, _dev, _fine_call, _offsets, _results, _same
 
 pytestmark = pytest.mark.gpu
-THREADS = min(16, os.cpu_count() or 4)
-F32 = np.float32
-R = ICP_RESULT_DTYPE.itemsize
-OK, INVALID, TOO_LARGE = 0, -1, -6
 GROUP_CAP = 400000  # bytes: a few small maps per launch group
 
 
@@ -41,51 +38,9 @@ def _checker():
     fl.build()
 
 
-def _same(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return a.shape == b.shape and a.tobytes() == b.tobytes()
-
-
-def _check(name, got, exp):
-    assert len(got) == len(exp), f"{name}: {len(got)} records, expected {len(exp)}"
-    bad = [k for k in range(len(exp)) if not _same(got[k], exp[k])]
-    assert not bad, f"{name}: {len(bad)} of {len(exp)} differ, first {bad[0]}: {got[bad[0]]} != {exp[bad[0]]}"
-
-
-def _dev(a):
-    import torch
-
-    return torch.from_numpy(np.ascontiguousarray(a).reshape(-1).view(np.uint8).copy()).to(torch.device("cuda:0"))
-
-
-def _results(d):
-    return d.cpu().numpy().view(ICP_RESULT_DTYPE).reshape(-1)
-
-
-def _ctx(sensor="HDL_32E", max_batch=2, max_points=1000):
-    return bev_amd.BevContext(bev_amd.params_for_sensor(sensor), device=0, max_batch=max_batch, max_points=max_points)
-
-
-def _offsets(clouds):
-    offs = np.zeros(len(clouds) + 1, np.uint64)
-    offs[1:] = np.cumsum([len(c) for c in clouds])
-    return offs
-
-
 def _call(ctx, clouds, maps, m, prm, d_clouds=None, coarse=None, best=None, fill=0):
     """one device-resident call on packed clouds, synchronised: (n,) ICP_RESULT_DTYPE"""
-    import torch
-
-    d_clouds = d_clouds if d_clouds is not None else _dev(rc.packed(clouds))
-    d_res = torch.full((max(len(m), 1) * R,), fill, dtype=torch.uint8, device=d_clouds.device)
-    d_coarse = _dev(coarse) if coarse is not None else None
-    d_best = _dev(best) if best is not None else None
-    torch.cuda.synchronize()
-    ctx.submap_registration_device(len(clouds), d_clouds.data_ptr(), _offsets(clouds), *maps.arrays(), m, d_res.data_ptr(),
-                                   d_coarse.data_ptr() if d_coarse is not None else None,
-                                   d_best.data_ptr() if d_best is not None else None, params=prm)
-    ctx.synchronize()
-    return _results(d_res)[: len(m)]
+    return _fine_call(ctx, clouds, maps, m, prm, None, d_clouds, coarse, best, fill)
 
 
 def _lattice(n, seed, spacing=0.5):

@@ -15,7 +15,8 @@ fine stage's sequential ICP):
   e. the cloud call on all of those maps: counts, records, nothing behind the count; map_leaf 0 gives the concatenation;
   f. ordering: d_ordered input behind bev_process_device_resident; calls of different sizes and leaves and the pair call
      without a synchronisation; a call behind a non-blocking upload and a fill;
-  g. every refused argument, outputs untouched; the batch form.
+  g. every refused argument, outputs untouched; the batch form;
+  h. which status a call gets that is wrong in two ways at once, for every scan-to-map entry point.
 """
 import ctypes as C
 import functools
@@ -29,66 +30,17 @@ import fineicp_lib as fl
 import reg_cases as rc
 import submap_reg_cases as sc
 import submap_vox_cases as vc
-from bev_amd import ICP_RESULT_DTYPE, POINT_DTYPE, synth
+from bev_amd import POINT_DTYPE, synth
+from submap_reg_gpu_lib import F32, INVALID, OK, R, THREADS, TOO_LARGE, _check, _ctx, _dev, _offsets, _results, _same
+from submap_reg_gpu_lib import _fine_call as _call
 
 pytestmark = pytest.mark.gpu
-THREADS = min(16, os.cpu_count() or 4)
-F32 = np.float32
-R = ICP_RESULT_DTYPE.itemsize
-OK, INVALID, TOO_LARGE = 0, -1, -6
 GROUP_CAP = 300000  # bytes: a few small maps per launch group, the map of 8 x 512 records alone above it
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _checker():
     fl.build()
-
-
-def _same(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return a.shape == b.shape and a.tobytes() == b.tobytes()
-
-
-def _check(name, got, exp):
-    assert len(got) == len(exp), f"{name}: {len(got)} records, expected {len(exp)}"
-    bad = [k for k in range(len(exp)) if not _same(got[k], exp[k])]
-    assert not bad, f"{name}: {len(bad)} of {len(exp)} differ, first {bad[0]}: {got[bad[0]]} != {exp[bad[0]]}"
-
-
-def _dev(a):
-    import torch
-
-    return torch.from_numpy(np.ascontiguousarray(a).reshape(-1).view(np.uint8).copy()).to(torch.device("cuda:0"))
-
-
-def _results(d):
-    return d.cpu().numpy().view(ICP_RESULT_DTYPE).reshape(-1)
-
-
-def _ctx(sensor="HDL_32E", max_batch=2, max_points=1000):
-    return bev_amd.BevContext(bev_amd.params_for_sensor(sensor), device=0, max_batch=max_batch, max_points=max_points)
-
-
-def _offsets(clouds):
-    offs = np.zeros(len(clouds) + 1, np.uint64)
-    offs[1:] = np.cumsum([len(c) for c in clouds])
-    return offs
-
-
-def _call(ctx, clouds, maps, m, prm, map_leaf, d_clouds=None, coarse=None, best=None, fill=0):
-    """one device-resident call on packed clouds, synchronised: (n,) ICP_RESULT_DTYPE"""
-    import torch
-
-    d_clouds = d_clouds if d_clouds is not None else _dev(rc.packed(clouds))
-    d_res = torch.full((max(len(m), 1) * R,), fill, dtype=torch.uint8, device=d_clouds.device)
-    d_coarse = _dev(coarse) if coarse is not None else None
-    d_best = _dev(best) if best is not None else None
-    torch.cuda.synchronize()
-    ctx.submap_voxel_registration_device(len(clouds), d_clouds.data_ptr(), _offsets(clouds), *maps.arrays(), m, d_res.data_ptr(),
-                                         map_leaf, d_coarse.data_ptr() if d_coarse is not None else None,
-                                         d_best.data_ptr() if d_best is not None else None, params=prm)
-    ctx.synchronize()
-    return _results(d_res)[: len(m)]
 
 
 def _capacity(clouds, maps, g):
@@ -588,5 +540,91 @@ def test_every_refused_argument_leaves_the_outputs_untouched():
         _check("accepted", _results(d_res), vc.expected(clouds, maps, m, fl.params(**fl.WHOLE), 0.2, threads=2))
         tg = vc.targets(clouds, maps, [0, 1], 0.2, threads=2)
         assert d_cnt.cpu().numpy().view(np.uint32).tolist() == [len(tg[0][1]), len(tg[1][1])]
+    finally:
+        ctx.close()
+
+
+# ---- h. status precedence ---------------------------------------------------------------------------------------------------------
+def test_status_precedence_of_calls_wrong_in_two_ways():
+    """Every scan-to-map entry keeps its own order of checks: a call with two faults gets the status of the
+    check that comes first.  Nothing is launched; every output stays as it was filled."""
+    import torch
+
+    lib = bev_amd.load_lib()
+    u64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint64))
+    ptr = lambda a: a.ctypes.data if a is not None else None
+    big, small = rc.scene(65536, 7001), rc.scene(200, 7002)
+    clouds = [big, small]
+    offs = _offsets(clouds)
+    maps = sc.Maps()
+    maps.add([(1, sc.IDENTITY), (1, sc.shift(0.03))])
+    maps.add([(1, sc.IDENTITY)])
+    moffs, eframe, epose = maps.arrays()
+    m = sc.matches([(1, 0, 0.0), (1, 1, 1.0)])
+    prm = bev_amd.icp_whole_defaults()
+    above = sc.Maps()                                   # map 0: one frame above BEV_SUBMAP_REG_MAX_TARGET records, and (at a
+    above.add([(0, sc.IDENTITY)] * (sc.REG_MAX_TARGET // len(big) + 1))   # stride of 65,536) above BEV_SUBMAP_COARSE_MAX_TARGET rows
+    above.add([(1, sc.IDENTITY)])
+    a_offs, a_frame, a_pose = above.arrays()
+    too_many = np.array([0, bev_amd.SUBMAP_MAX_ENTRIES + 1, bev_amd.SUBMAP_MAX_ENTRIES + 2], np.uint64)
+    decreasing = np.array([0, 70000, 65536], np.uint64)
+    STRIDE, PN_STRIDE = 2 * len(small), len(big)
+
+    def match(k, field, v):
+        mm = m.copy()
+        mm[field][k] = v
+        return mm
+
+    ctx = _ctx()
+    try:
+        dev = torch.device("cuda:0")
+        d_clouds = _dev(rc.packed(clouds))
+        filled = lambda n: torch.full((n,), 0xA5, dtype=torch.uint8, device=dev)
+        d_res, d_out, d_cnt, d_cres, d_cbest = filled(len(m) * R), filled(2 * STRIDE * 16), filled(2 * 4), filled(len(m) * 2 * R), filled(len(m) * 4)
+        d_pn, d_pcnt = torch.zeros(2 * PN_STRIDE * 48, dtype=torch.uint8, device=dev), _dev(np.array([len(big), len(small)], np.uint32))
+        h_res = np.full(len(m) * R, 0xA5, np.uint8)
+        torch.cuda.synchronize()
+        h, cl = ctx._h, C.c_void_p(d_clouds.data_ptr())
+        vp = lambda d: C.c_void_p(d.data_ptr()) if d is not None else None
+
+        def reg(clouds_=cl, offs_=offs, moffs_=moffs, eframe_=eframe, epose_=epose, m_=m):
+            return lib.bev_submap_voxel_registration_device_resident(h, 2, clouds_, u64(offs_), 0.2, 0.2, 2, u64(moffs_), ptr(eframe_),
+                                                                     ptr(epose_), 2, ptr(m_), None, None, C.byref(prm), vp(d_res))
+
+        def cloud(clouds_=cl, moffs_=moffs, eframe_=eframe, epose_=epose, stride=STRIDE, out_=d_out):
+            return lib.bev_submap_voxel_cloud_device_resident(h, 2, clouds_, u64(offs), 0.2, 0.2, 2, u64(moffs_), ptr(eframe_), ptr(epose_),
+                                                              stride, vp(out_), vp(d_cnt))
+
+        def coarse(stride=PN_STRIDE, moffs_=moffs, eframe_=eframe, epose_=epose, m_=m):
+            return lib.bev_submap_coarse_registration_device_resident(h, 2, vp(d_pn), stride, vp(d_pcnt), 2, u64(moffs_), ptr(eframe_),
+                                                                      ptr(epose_), 2, ptr(m_), None, vp(d_cres), vp(d_cbest))
+
+        def batch(moffs_=moffs):
+            pts = (C.c_void_p * 2)(big.ctypes.data, None)            # frame 1: 200 records at NULL
+            npts = np.array([len(big), len(small)], np.uint32)
+            return lib.bev_submap_voxel_registration_batch(h, 2, pts, npts.ctypes.data_as(C.POINTER(C.c_uint32)), 0.2, 0.2, 2, u64(moffs_),
+                                                           ptr(eframe), ptr(epose), 2, ptr(m), C.byref(prm), h_res.ctypes.data)
+
+        got = {
+            "reg: a map above the target bound, NULL clouds": (reg(clouds_=None, moffs_=a_offs, eframe_=a_frame, epose_=a_pose), TOO_LARGE),
+            "reg: query 2, a map above the target bound": (reg(m_=match(0, "query_idx", 2), moffs_=a_offs, eframe_=a_frame, epose_=a_pose), INVALID),
+            "reg: decreasing frame offsets, too many entries": (reg(offs_=decreasing, moffs_=too_many), INVALID),
+            "reg: too many entries, map 2": (reg(moffs_=too_many, m_=match(1, "match_idx", 2)), TOO_LARGE),
+            "reg: NULL matches, too many entries": (reg(m_=None, moffs_=too_many), INVALID),
+            "cloud: a map above the target bound, a stride one record short": (cloud(moffs_=a_offs, eframe_=a_frame, epose_=a_pose, stride=STRIDE - 1), TOO_LARGE),
+            "cloud: too many entries, NULL clouds": (cloud(moffs_=too_many, clouds_=None), TOO_LARGE),
+            "cloud: NULL out, too many entries": (cloud(out_=None, moffs_=too_many), INVALID),
+            "coarse: too many entries, map 2": (coarse(moffs_=too_many, m_=match(1, "match_idx", 2)), TOO_LARGE),
+            "coarse: map 2, a capacity above the bound": (coarse(m_=match(1, "match_idx", 2), moffs_=a_offs, eframe_=a_frame, epose_=a_pose), INVALID),
+            "coarse: stride 0, too many entries": (coarse(stride=0, moffs_=too_many), INVALID),
+            "batch: a NULL cloud of 200 records, too many entries": (batch(moffs_=too_many), INVALID),
+        }
+        ctx.synchronize()
+        wrong = {k: v for k, v in got.items() if v[0] != v[1]}
+        assert not wrong, wrong
+        assert all((d.cpu().numpy() == 0xA5).all() for d in (d_res, d_out, d_cnt, d_cres, d_cbest)) and (h_res == 0xA5).all(), \
+            "a refused call wrote an output"
+        # each fault alone is the existing tests'; the faults of a pair do not depend on each other
+        assert coarse(moffs_=a_offs, eframe_=a_frame, epose_=a_pose) == TOO_LARGE and cloud(stride=STRIDE - 1) == INVALID
     finally:
         ctx.close()
