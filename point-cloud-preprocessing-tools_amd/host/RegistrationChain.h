@@ -1,0 +1,84 @@
+/*
+ * RegistrationChain.h — the one host program under the four batch registration tools (batch_top_part_registration,
+ * batch_whole_registration, batch_submap_registration, batch_submap_top_part_registration).  A tool's main() reads
+ * its arguments and says which file an index names; then, per chunk of matches (RegistrationChunks.h):
+ *   load         the chunk's files, packed one behind the other
+ *   runChunk     uploads, [front end, coarse ICP,] synchronise, fine ICP, synchronise, downloads — against the matches' target
+ *                frames, or against their maps
+ *   Tally        a match fails when its fitness exceeds 1.5; the report line of one that does not; the closing lines
+ * registerChunk is the three in a row.  A HIP or library failure throws std::runtime_error naming the call; device memory is
+ * owned, so every way out frees it.
+ */
+#ifndef BEV_HOST_REGISTRATIONCHAIN_H
+#define BEV_HOST_REGISTRATIONCHAIN_H
+
+#include <iosfwd>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "PointCloud.h"
+#include "RegistrationChunks.h"
+
+bev_ctx_t *bevhost_context(); /* BatchMultiBevGen.cpp: the free functions' context, created at the first call */
+
+namespace regchain {
+
+/* device memory that frees itself: hipMalloc / hipFree; move-only; default-constructed it holds nullptr */
+class DeviceBuffer {
+public:
+    DeviceBuffer() = default;
+    explicit DeviceBuffer(size_t bytes);
+    DeviceBuffer(DeviceBuffer &&o) noexcept : p_(std::exchange(o.p_, nullptr)) {}
+    DeviceBuffer &operator=(DeviceBuffer &&o) noexcept { return std::swap(p_, o.p_), *this; }
+    ~DeviceBuffer();
+    template <class T = void> T *as() const { return static_cast<T *>(p_); }
+    void upload(const void *src, size_t bytes, size_t offset = 0);
+    void download(void *dst, size_t bytes) const;
+
+private:
+    void *p_ = nullptr;
+};
+
+using Cloud = pcl::PointCloud<pcl::PointXYZIRCT>;
+
+struct ChunkResult {
+    std::vector<bev_icp_result_t> fine;   /* per match */
+    std::vector<bev_icp_result_t> coarse; /* top part: per match, from the guess and from the guess + 180 */
+    std::vector<int32_t> best;            /* top part: which of the two the fine stage started from */
+    double ms_first = 0.0; /* from before the first allocation to the synchronise behind coarse ICP (whole: the uploads) */
+    double ms_fine = 0.0;  /* the fine stage and its synchronise */
+};
+
+/* The chain on one chunk: frame f is clouds[f], offs[f] its first point in the packed array.  entry_pose null: every match
+ * against its target frame (chunk.matches[k].match_idx); else against its map (chunk.map_offs, chunk.entry_frame, 12 floats of
+ * *entry_pose per entry), thinned by map_leaf if that is > 0.  top_part: front end (leaf 0.2, radius 2, viewpoint 0) and coarse
+ * ICP, then fine ICP from the better coarse result; else fine ICP from the yaw guess */
+ChunkResult runChunk(bev_ctx_t *ctx, const std::vector<Cloud> &clouds, const std::vector<uint64_t> &offs, const Chunk &chunk,
+                     const std::vector<float> *entry_pose, float map_leaf, bool top_part, const bev_icp_params_t &fine_prm);
+
+/* what a successful match's "diff_xy diff_yaw" line compares its final transform with */
+enum class ReportAgainst { Nothing, ChosenCoarse, YawGuess };
+
+class Tally {
+public:
+    Tally(std::ostream *report, ReportAgainst against) : report_(report), against_(against) {}
+    void add(const Chunk &chunk, const ChunkResult &r);
+    /* the [TIME] lines (ms per match; the first only with coarse_line; fine_is_both: the fine line is both stages) and the summary */
+    void print(std::ostream &out, bool coarse_line, bool fine_is_both) const;
+
+private:
+    std::ostream *report_;
+    ReportAgainst against_;
+    int success_ = 0, failure_ = 0;
+    double ms_first_ = 0.0, ms_fine_ = 0.0;
+};
+
+/* The files paths[f] as the chunk's frames, the context (after the files: an unreadable one ends the tool first), runChunk, Tally::add.  0, or the tool's exit
+ * status with the reason on stderr: 1 an unreadable cloud, 2 no context or a failed call */
+int registerChunk(const std::vector<std::string> &paths, const Chunk &chunk, const std::vector<float> *entry_pose, float map_leaf,
+                  bool top_part, const bev_icp_params_t &fine_prm, Tally &tally);
+
+} // namespace regchain
+
+#endif

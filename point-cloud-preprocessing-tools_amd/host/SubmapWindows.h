@@ -49,6 +49,16 @@ inline void relativePose(const Pose6f &pi, const Pose6f &pj, float m[12])
     }
 }
 
+/* file j's entry in the map of key file i, appended to entry_pose: T_i^-1 T_j, the key itself the exact identity.  The one rule
+ * of every submap tool, BEV (loadBatch) and registration (batch_submap_registration_main.cpp) */
+inline void appendEntryPose(const std::vector<Pose6f> &pose, long i, long j, std::vector<float> &entry_pose)
+{
+    entry_pose.resize(entry_pose.size() + 12);
+    float *mat = entry_pose.data() + entry_pose.size() - 12;
+    if (j == i) bev_yaw_translate_matrix(0.0f, 0.0f, 0.0f, 0.0f, mat); /* the exact identity */
+    else relativePose(pose[i], pose[j], mat);
+}
+
 /* What a tool's command line and <root> say: argv[1 .. 4] = root, sensor, half_window, [stride] (argc >= 4 checked by the
  * caller, which prints its own usage), the sorted files of <root>/non_ground_point_cloud/ and row j of
  * <root>/keyframe_pose.csv for file j. */
@@ -147,10 +157,7 @@ inline void loadBatch(const Setup &s, long k0, int nb, Batch &b)
         const long i = (k0 + m) * stride;
         for (long j = std::max(0L, i - half); j <= std::min(n_files - 1, i + half); ++j) {
             b.entry_frame.push_back((int32_t)(std::lower_bound(b.loaded.begin(), b.loaded.end(), j) - b.loaded.begin()));
-            b.entry_pose.resize(b.entry_pose.size() + 12);
-            float *mat = b.entry_pose.data() + b.entry_pose.size() - 12;
-            if (j == i) bev_yaw_translate_matrix(0.0f, 0.0f, 0.0f, 0.0f, mat); /* the exact identity */
-            else relativePose(s.pose[i], s.pose[j], mat);
+            appendEntryPose(s.pose, i, j, b.entry_pose);
         }
         b.map_offs.push_back(b.entry_frame.size());
     }

@@ -10,10 +10,10 @@
  * batch_submap_cloud_manip read.  The map of match (q, m) holds the files j in [m - half_window, m + half_window], clipped to
  * the files, in ascending order, each under T_m^-1 T_j (submapwin::relativePose; j == m gets the exact identity); the query's
  * voxel cloud is registered against the map's moved voxel clouds from the yaw guess, with the whole tool's settings
- * (bev_icp_whole_defaults), by bev_submap_registration_device_resident.  half_window 0 is batch_whole_registration.
- * <map_leaf> > 0 thins every map by a voxel grid of that leaf over the union of its moved voxel clouds
- * (bev_submap_voxel_registration_device_resident); absent or 0: no second grid, the files as ever; negative or
- * not a finite number: refused with the usage line.
+ * (bev_icp_whole_defaults), by bev_submap_voxel_registration_device_resident.  half_window 0 is batch_whole_registration.
+ * <map_leaf> > 0 thins every map by a voxel grid of that leaf over the union of its moved voxel clouds; absent
+ * or 0: no second grid, the files as ever (the call is then bev_submap_registration_device_resident's); negative
+ * or not a finite number: refused with the usage line.
  *
  * Bookkeeping, summary line and [TIME] line are batch_whole_registration's (a match fails when its fitness exceeds 1.5); like
  * that tool it creates icp_precision_report_3d_icp_directly.txt in the working directory and writes nothing to it.  Beside
@@ -31,55 +31,31 @@
  * bev_icp_fine_defaults() and map_leaf).  Bookkeeping, both [TIME] lines, the summary line and the report file
  * (icp_precision_report.txt: the final transform against the chosen coarse one) are batch_top_part_registration's; with half_window
  * 0 and map_leaf 0 it is that tool.
+ *
+ * The chunks, the chain and the bookkeeping are the four registration tools' own (RegistrationChunks.h, RegistrationChain.h;
+ * DESIGN.md §6p), the entries' matrices every submap tool's (submapwin::appendEntryPose): this file is the command line, which
+ * file an index names, and the poses.
  */
-#include <chrono>
 #include <cmath>
-#include <cstdio>
 #include <cstdlib>
 #include <fstream>
 #include <iostream>
-#include <map>
 #include <vector>
 
-#include <hip/hip_runtime_api.h>
-
-#include "../csrc/bev_libm_f64.h"
 #include "Registration.h"
+#include "RegistrationChain.h"
 #include "SubmapWindows.h"
 
 #ifndef BEV_SUBMAP_TOP_PART
 #define BEV_SUBMAP_TOP_PART 0
 #endif
 
-bev_ctx_t *bevhost_context(); /* BatchMultiBevGen.cpp (host) */
-
-#if BEV_SUBMAP_TOP_PART
-#define BEV_TOOL_NAME "batch_submap_top_part_registration"
-#else
-#define BEV_TOOL_NAME "batch_submap_registration"
-#endif
-
 namespace {
 
-void hip_or_die(hipError_t e, const char *what)
-{
-    if (e != hipSuccess) {
-        std::cerr << what << ": " << hipGetErrorString(e) << "\n";
-        std::exit(2);
-    }
-}
+constexpr bool kTopPart = BEV_SUBMAP_TOP_PART;
+const char *const kTool = kTopPart ? "batch_submap_top_part_registration" : "batch_submap_registration";
 
-#if BEV_SUBMAP_TOP_PART
-void bev_or_die(int rc, const char *what)
-{
-    if (rc != BEV_OK) {
-        std::cerr << what << ": " << bev_strerror(rc) << "\n";
-        std::exit(2);
-    }
-}
-#endif
-
-const char kUsage[] = "Usage: " BEV_TOOL_NAME " <match_result_text_file> <keyframes_root_dir> <half_window> [<chunk> [<map_leaf>]]\n";
+void usage() { std::cerr << "Usage: " << kTool << " <match_result_text_file> <keyframes_root_dir> <half_window> [<chunk> [<map_leaf>]]\n"; }
 
 /* a finite number >= 0 and nothing else */
 bool parse_map_leaf(const char *s, float *out)
@@ -97,31 +73,30 @@ bool parse_map_leaf(const char *s, float *out)
 int main(int argc, char **argv)
 {
     if (argc < 4) {
-        std::cerr << kUsage;
+        usage();
         return 1;
     }
     float map_leaf = 0.0f;
     if (argc > 5 && !parse_map_leaf(argv[5], &map_leaf)) {
-        std::cerr << "map_leaf '" << argv[5] << "': expected a finite number >= 0\n" << kUsage;
+        std::cerr << "map_leaf '" << argv[5] << "': expected a finite number >= 0\n";
+        usage();
         return 1;
     }
     std::string root(argv[2]);
     if (root.empty() || root.back() != '/') root.append("/");
-    long half = 0, chunk = 256;
+    long half = 0, limit = 256;
     if (!submapwin::parseCount(argv[3], 0, &half)) {
         std::cerr << "half_window '" << argv[3] << "': expected an integer >= 0\n";
         return 1;
     }
-    if (argc > 4 && !submapwin::parseCount(argv[4], 2 * half + 2, &chunk)) {
+    if (argc > 4 && !submapwin::parseCount(argv[4], 2 * half + 2, &limit)) {
         std::cerr << "chunk '" << argv[4] << "': expected an integer >= 2 * half_window + 2\n";
         return 1;
     }
-    chunk = std::max(chunk, 2 * half + 2);
-#if BEV_SUBMAP_TOP_PART
-    std::ofstream report("./icp_precision_report.txt");
-#else
-    std::ofstream report("./icp_precision_report_3d_icp_directly.txt"), submap_report("./icp_precision_report_submap.txt");
-#endif
+    limit = std::max(limit, 2 * half + 2); /* (the default too: a match's query and window always fit) */
+    /* the whole tool's empty report and this tool's own beside it; the top-part tool's report */
+    std::ofstream report(kTopPart ? "./icp_precision_report.txt" : "./icp_precision_report_3d_icp_directly.txt"), submap_report;
+    if (!kTopPart) submap_report.open("./icp_precision_report_submap.txt");
     std::vector<MatchResult> matches;
     try {
         matches = loadMatchResults(argv[1]);
@@ -146,156 +121,22 @@ int main(int argc, char **argv)
             return 1;
         }
     sensor_params_ = getSensorParams(parseSensorType("HDL_64E")); /* (the context follows a sensor; packed clouds read none) */
-    const bev_icp_params_t prm = BEV_SUBMAP_TOP_PART ? bev_icp_fine_defaults() : bev_icp_whole_defaults();
-    double t_coarse = 0.0, t_fine = 0.0;
-    int count_success = 0, count_failure = 0;
-    using clk = std::chrono::steady_clock;
-
+    const bev_icp_params_t prm = kTopPart ? bev_icp_fine_defaults() : bev_icp_whole_defaults();
+    regchain::Tally tally(kTopPart ? &report : &submap_report,
+                          kTopPart ? regchain::ReportAgainst::ChosenCoarse : regchain::ReportAgainst::YawGuess);
     for (size_t m0 = 0; m0 < matches.size();) {
-        /* the chunk: consecutive matches whose queries and windows name at most `chunk` distinct files */
-        std::map<long, int> local;
-        size_t m1 = m0;
-        while (m1 < matches.size()) {
-            const long q = matches[m1].query_idx, m = matches[m1].match_idx;
-            std::vector<long> add;
-            if (!local.count(q)) add.push_back(q);
-            for (long j = std::max(0L, m - half); j <= std::min(n_files - 1, m + half); ++j)
-                if (!local.count(j) && j != q) add.push_back(j);
-            if ((long)(local.size() + add.size()) > chunk) break;
-            for (long f : add) local.emplace(f, (int)local.size());
-            ++m1;
-        }
-        const int F = (int)local.size();
-        std::vector<long> file_of(F);
-        for (const auto &kv : local) file_of[kv.second] = kv.first;
-        std::vector<uint64_t> offs(F + 1, 0);
-        std::vector<pcl::PointCloud<pcl::PointXYZIRCT>> clouds(F);
-        for (int f = 0; f < F; ++f) {
-            if (bevio::loadPCDFile(files[file_of[f]], clouds[f]) != 0) {
-                std::cerr << "Cloud NOT load file: " << files[file_of[f]] << "\n";
-                return 1;
-            }
-            offs[f + 1] = offs[f] + clouds[f].points.size();
-        }
-        bev_ctx_t *ctx = bevhost_context();
-        if (!ctx) return 2;
-        /* one map per match (two matches of one key frame get two equal maps) */
-        const size_t n = m1 - m0;
-        std::vector<bev_match_t> cm(n);
-        std::vector<uint64_t> map_offs(1, 0);
-        std::vector<int32_t> entry_frame;
+        /* the indices are places in the sorted listing: windows clipped to it, one map per match */
+        const regchain::Chunk chunk = regchain::planChunk(matches.data(), matches.size(), m0, half, 0, n_files - 1, limit, true);
+        std::vector<std::string> paths;
+        for (long f : chunk.files) paths.push_back(files[f]);
         std::vector<float> entry_pose;
-        for (size_t k = 0; k < n; ++k) {
-            const long m = matches[m0 + k].match_idx;
-            cm[k] = bev_match_t{local[matches[m0 + k].query_idx], (int32_t)k, matches[m0 + k].angle_guess};
-            for (long j = std::max(0L, m - half); j <= std::min(n_files - 1, m + half); ++j) {
-                entry_frame.push_back(local[j]);
-                entry_pose.resize(entry_pose.size() + 12);
-                float *mat = entry_pose.data() + entry_pose.size() - 12;
-                if (j == m) bev_yaw_translate_matrix(0.0f, 0.0f, 0.0f, 0.0f, mat); /* the exact identity */
-                else submapwin::relativePose(pose[m], pose[j], mat);
-            }
-            map_offs.push_back(entry_frame.size());
-        }
-        auto t0 = clk::now();
-        void *d_pts = nullptr, *d_fine = nullptr;
-        hip_or_die(hipMalloc(&d_pts, std::max<uint64_t>(offs[F], 1) * sizeof(bev_point_t)), "hipMalloc");
-        for (int f = 0; f < F; ++f)
-            if (!clouds[f].points.empty())
-                hip_or_die(hipMemcpy(static_cast<bev_point_t *>(d_pts) + offs[f], clouds[f].points.data(),
-                                     clouds[f].points.size() * sizeof(bev_point_t), hipMemcpyHostToDevice),
-                           "hipMemcpy");
-        hip_or_die(hipMalloc(&d_fine, n * sizeof(bev_icp_result_t)), "hipMalloc");
-#if BEV_SUBMAP_TOP_PART
-        void *d_pn = nullptr, *d_cnt = nullptr, *d_coarse = nullptr, *d_best = nullptr;
-        size_t n_max = 1;
-        for (int f = 0; f < F; ++f) n_max = std::max<size_t>(n_max, offs[f + 1] - offs[f]);
-        const size_t stride = bev_regfront_max_out(n_max);
-        hip_or_die(hipMalloc(&d_pn, (size_t)F * stride * 48), "hipMalloc");
-        hip_or_die(hipMalloc(&d_cnt, (size_t)F * 4), "hipMalloc");
-        hip_or_die(hipMalloc(&d_coarse, n * 2 * sizeof(bev_icp_result_t)), "hipMalloc");
-        hip_or_die(hipMalloc(&d_best, n * 4), "hipMalloc");
-        const float vp[3] = {0.0f, 0.0f, 0.0f};
-        bev_or_die(bev_registration_front_device_resident(ctx, F, static_cast<bev_point_t *>(d_pts), offs.data(), 0.2f, 2.0f, vp,
-                                                          d_pn, stride, static_cast<uint32_t *>(d_cnt)),
-                   "bev_registration_front_device_resident");
-        bev_or_die(bev_submap_coarse_registration_device_resident(ctx, F, d_pn, stride, static_cast<uint32_t *>(d_cnt), (int)n,
-                                                                  map_offs.data(), entry_frame.data(), entry_pose.data(), (int)n,
-                                                                  cm.data(), nullptr, static_cast<bev_icp_result_t *>(d_coarse),
-                                                                  static_cast<int32_t *>(d_best)),
-                   "bev_submap_coarse_registration_device_resident");
-        bev_or_die(bev_synchronize(ctx), "bev_synchronize");
-        auto t1 = clk::now();
-        bev_or_die(bev_submap_voxel_registration_device_resident(ctx, F, static_cast<bev_point_t *>(d_pts), offs.data(), 0.2f,
-                                                                 map_leaf, (int)n, map_offs.data(), entry_frame.data(),
-                                                                 entry_pose.data(), (int)n, cm.data(),
-                                                                 static_cast<bev_icp_result_t *>(d_coarse),
-                                                                 static_cast<int32_t *>(d_best), &prm,
-                                                                 static_cast<bev_icp_result_t *>(d_fine)),
-                   "bev_submap_voxel_registration_device_resident");
-        bev_or_die(bev_synchronize(ctx), "bev_synchronize");
-        auto t2 = clk::now();
-        t_coarse += std::chrono::duration<double, std::milli>(t1 - t0).count();
-        t_fine += std::chrono::duration<double, std::milli>(t2 - t1).count();
-        std::vector<bev_icp_result_t> fine(n), coarse(2 * n);
-        std::vector<int32_t> best(n);
-        hip_or_die(hipMemcpy(fine.data(), d_fine, n * sizeof(bev_icp_result_t), hipMemcpyDeviceToHost), "hipMemcpy");
-        hip_or_die(hipMemcpy(coarse.data(), d_coarse, 2 * n * sizeof(bev_icp_result_t), hipMemcpyDeviceToHost), "hipMemcpy");
-        hip_or_die(hipMemcpy(best.data(), d_best, n * 4, hipMemcpyDeviceToHost), "hipMemcpy");
-        for (void *p : {d_pts, d_pn, d_cnt, d_coarse, d_best, d_fine}) (void)hipFree(p);
-        for (size_t k = 0; k < n; ++k) {
-            if (fine[k].fitness > 1.5f) {
-                ++count_failure;
-                continue;
-            }
-            ++count_success;
-            float xy, yaw;
-            icpPrecisionReport(fine[k].T, coarse[2 * k + (best[k] ? 1 : 0)].T, xy, yaw);
-            report << xy << " " << yaw << "\n";
-        }
-#else
-        int rc = map_leaf > 0.0f
-                     ? bev_submap_voxel_registration_device_resident(ctx, F, static_cast<bev_point_t *>(d_pts), offs.data(), 0.2f,
-                                                                     map_leaf, (int)n, map_offs.data(), entry_frame.data(),
-                                                                     entry_pose.data(), (int)n, cm.data(), nullptr, nullptr,
-                                                                     &prm, static_cast<bev_icp_result_t *>(d_fine))
-                     : bev_submap_registration_device_resident(ctx, F, static_cast<bev_point_t *>(d_pts), offs.data(), 0.2f, (int)n,
-                                                               map_offs.data(), entry_frame.data(), entry_pose.data(), (int)n,
-                                                               cm.data(), nullptr, nullptr, &prm,
-                                                               static_cast<bev_icp_result_t *>(d_fine));
-        if (rc == BEV_OK) rc = bev_synchronize(ctx);
-        if (rc != BEV_OK) {
-            std::cerr << "bev_submap_registration_device_resident: " << bev_strerror(rc) << " " << bev_last_error(ctx) << "\n";
-            return 2;
-        }
-        t_fine += std::chrono::duration<double, std::milli>(clk::now() - t0).count();
-        std::vector<bev_icp_result_t> fine(n);
-        hip_or_die(hipMemcpy(fine.data(), d_fine, n * sizeof(bev_icp_result_t), hipMemcpyDeviceToHost), "hipMemcpy");
-        (void)hipFree(d_pts);
-        (void)hipFree(d_fine);
-        for (size_t k = 0; k < n; ++k) {
-            if (fine[k].fitness > 1.5f) {
-                ++count_failure;
-                continue;
-            }
-            ++count_success;
-            float guess[16], xy, yaw;
-            bevx::icp_tool_guess(cm[k].angle_guess, 0, guess);
-            icpPrecisionReport(fine[k].T, guess, xy, yaw);
-            submap_report << xy << " " << yaw << "\n";
-        }
-#endif
-        m0 = m1;
+        for (size_t k = 0; k < chunk.matches.size(); ++k)
+            for (uint64_t e = chunk.map_offs[k]; e < chunk.map_offs[k + 1]; ++e)
+                submapwin::appendEntryPose(pose, matches[m0 + k].match_idx, chunk.files[chunk.entry_frame[e]], entry_pose);
+        if (const int rc = regchain::registerChunk(paths, chunk, &entry_pose, map_leaf, kTopPart, prm, tally)) return rc;
+        m0 = chunk.m1;
     }
-    t_coarse /= matches.size();
-    t_fine /= matches.size();
-    if (BEV_SUBMAP_TOP_PART) std::cout << "[TIME] Avg Tiempo for 1st Stage (coarse): " << t_coarse << "\n";
-    std::cout << "[TIME] Avg Tiempo for 2nd Stage (fine): " << t_fine << "\n";
-    std::cout << "count_success: " << count_success << ", count_failure: " << count_failure
-              << ", SR: " << (1.0f * count_success) / (count_success + count_failure) << ". \n";
-    report.close();
-#if !BEV_SUBMAP_TOP_PART
-    submap_report.close();
-#endif
+    /* batch_submap_registration's fine line is the whole visit of the device, uploads included */
+    tally.print(std::cout, kTopPart, !kTopPart);
     return 0;
 }

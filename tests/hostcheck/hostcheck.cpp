@@ -19,6 +19,7 @@
 #include "../../point-cloud-preprocessing-tools_amd/csrc/bev_libm.h"
 #include "../../point-cloud-preprocessing-tools_amd/host/FileFormats.h"
 #include "../../point-cloud-preprocessing-tools_amd/host/LabelStep.h"
+#include "../../point-cloud-preprocessing-tools_amd/host/RegistrationChunks.h"
 
 using namespace bevx;
 
@@ -641,6 +642,22 @@ size_t hc_csv_u8(const uint8_t *pixels, int rows, int cols, char *out, size_t ca
     const std::string s = bevio::formatCsvU8(pixels, rows, cols);
     if (out && cap) std::memcpy(out, s.data(), std::min(cap, s.size()));
     return s.size();
+}
+
+/* ---- host/RegistrationChunks.h: the chunk of the registration tools that starts at match m0 ---- */
+/* counts[0..2] = m1, files, entries.  files has room for `limit` numbers, out_matches for n - m0 matches, map_offs for one more,
+ * entry_frame for (n - m0) * (2 * half + 1) entries; without maps the last two are not written */
+void hc_plan_chunk(const bev_match_t *matches, uint64_t n, uint64_t m0, int64_t half, int64_t lo, int64_t hi, int64_t limit, int maps,
+                   uint64_t *counts, int64_t *files, bev_match_t *out_matches, uint64_t *map_offs, int32_t *entry_frame)
+{
+    const regchain::Chunk c = regchain::planChunk(matches, (size_t)n, (size_t)m0, (long)half, (long)lo, (long)hi, (long)limit, maps != 0);
+    counts[0] = c.m1;
+    counts[1] = c.files.size();
+    counts[2] = c.entry_frame.size();
+    std::copy(c.files.begin(), c.files.end(), files);
+    std::copy(c.matches.begin(), c.matches.end(), out_matches);
+    std::copy(c.map_offs.begin(), c.map_offs.end(), map_offs);
+    std::copy(c.entry_frame.begin(), c.entry_frame.end(), entry_frame);
 }
 
 } /* extern "C" */

@@ -60,6 +60,8 @@ def lib():
         l.hc_png_write.argtypes = [C.c_char_p, vp, C.c_int, C.c_int]
         l.hc_csv_u8.argtypes = [vp, C.c_int, C.c_int, vp, C.c_size_t]
         l.hc_csv_u8.restype = C.c_size_t
+        l.hc_plan_chunk.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, vp, vp, vp, vp, vp]
+        l.hc_plan_chunk.restype = None
         _lib = l
     return _lib
 
@@ -171,3 +173,26 @@ def key_stats(reset=True):
 def key_roundtrip(p: BevParams, x, y, z, label) -> int:
     """0: wrong, 1: key + height reproduce bev_code (or flag 'no code'), 2: escape (the point itself is read)"""
     return int(lib().hc_key_roundtrip(C.byref(p), float(x), float(y), float(z), int(label)))
+
+
+MATCH_DTYPE = np.dtype([("query_idx", "<i4"), ("match_idx", "<i4"), ("angle_guess", "<f4")])
+NO_CLIP = (-(1 << 62), 1 << 62)
+
+
+def plan_chunk(matches, m0, half, lo, hi, limit, maps):
+    """host/RegistrationChunks.h planChunk -> (m1, files, match table as (q, m, angle) tuples, map_offs, entry_frame); the last two
+    are None without maps"""
+    m = np.ascontiguousarray(matches, MATCH_DTYPE)
+    n = len(m)
+    counts = np.zeros(3, np.uint64)
+    files = np.zeros(max(limit, 1), np.int64)
+    out = np.zeros(max(n - m0, 1), MATCH_DTYPE)
+    map_offs = np.zeros(n - m0 + 1, np.uint64)
+    entry_frame = np.zeros(max((n - m0) * (2 * half + 1), 1), np.int32)
+    lib().hc_plan_chunk(m.ctypes.data, n, m0, half, lo, hi, limit, 1 if maps else 0, counts.ctypes.data, files.ctypes.data,
+                        out.ctypes.data, map_offs.ctypes.data, entry_frame.ctypes.data)
+    m1, nf, ne = (int(v) for v in counts)
+    table = [(int(r["query_idx"]), int(r["match_idx"]), float(r["angle_guess"])) for r in out[:m1 - m0]]
+    if not maps:
+        return m1, files[:nf].tolist(), table, None, None
+    return m1, files[:nf].tolist(), table, map_offs[:m1 - m0 + 1].tolist(), entry_frame[:ne].tolist()
