@@ -699,6 +699,57 @@ int bev_submap_coarse_registration_device_resident(bev_ctx_t *ctx, int n_frames,
                                                    const bev_match_t *h_matches, const bev_icp_params_t *params,
                                                    bev_icp_result_t *d_results, int32_t *d_best);
 
+/* ---- scan-to-map coarse ICP against THINNED maps: a voxel grid and 2-D normals over the union ----------------------------
+ * bev_submap_coarse_registration_device_resident with a leaf size for the map: what the reference pipeline does
+ * to every cloud it hands to coarse ICP (VoxelGrid<PointXYZ>, Normal2dEstimation, concatenateFields), done to the union of a
+ * map's entries.  With concat(g) = bev_submap_coarse_registration_device_resident's target(g) (above; a frame's count cut at
+ * stride), and pn_leaf > 0:
+ *   V = bev_voxel_grid_xyz(positions of concat(g), pn_leaf): bounds and divisions from the finite positions of the union,
+ *       voxels in ascending index, a centroid the float sum of its voxel's points IN CONCATENATION ORDER divided by float(n),
+ *       without FMA; non-finite positions are dropped;
+ *   N = bev_normals_2d(V, radius mode, radius, viewpoint): neighbours by the 3-D float distance in ascending index, the
+ *       |N| = 0 / 1 / 2 / >= 3 branches, the flip towards the viewpoint (its x and y; NULL: the origin), every NaN 0x7fc00000;
+ *   target(g)[i] = the PointNormal record  x y z 0 | nx ny nz 0 | curvature 0 0 0  of V[i] and N[i].
+ * The moved normals and curvatures of concat(g) are NOT used: the rule for a merged voxel's normal is "recompute", so a
+ * thinned map's normals have nz = 0 exactly, whatever its entries' poses.  When the union's grid would have more than INT32_MAX
+ * voxels ("leaf too small"), target(g) is concat(g) unchanged, moved normals included, as §6l keeps the concatenation.  A map
+ * without entries, or whose union has no finite position, ends as an empty target does.
+ *   d_results[2m + k] = bev_icp_point_to_plane(frame query_idx, target(match_idx), guess k of angle_guess, params)
+ * bit for bit as a whole bev_icp_result_t, d_best as above; both go straight into
+ * bev_submap_voxel_registration_device_resident without a synchronisation.
+ * pn_leaf == 0      : no grid over the union: bev_submap_coarse_registration_device_resident itself, byte for byte (that
+ *                     function is this one with pn_leaf = 0); radius and viewpoint are not read.
+ * pn_leaf < 0, NaN, infinite : BEV_ERR_INVALID_ARG.  With pn_leaf > 0 also a radius that bev_normals_2d refuses (not finite,
+ *                     or <= 0).
+ * Every other argument, status and bound, and the ordering, are bev_submap_coarse_registration_device_resident's
+ * (BEV_SUBMAP_COARSE_MAX_TARGET applies to the capacity n_entries * stride); a refused call launches nothing and leaves
+ * d_results and d_best untouched; n_matches == 0 returns BEV_OK.
+ * Workspace : in the coarse stage's buffer.  With pn_leaf > 0 a launch group also holds the moved rows, the padded sort keys,
+ *             the voxel starts, the voxel indices, the thinned positions and a header per map: with E, T, M as above and K' the
+ *             sum over the group's maps of the smallest power of two >= the map's capacity (0 for capacity 0),
+ *               min(2 * n_matches, 1024) * 16 * stride + 4 E + 136 T + 8 K' + M * (4 * 4097 + 32 + 4 + 32)
+ *             bytes (pieces rounded up to 256), and 8 more bytes per used map in the tables.  The launch groups are cut so that
+ *             136 T + 8 K' + M * (4 * 4097 + 68) fits the cap (BEV_SUBMAP_REG_GROUP; results do not depend on it).  The sort
+ *             runs in tiles of 4096 keys per workgroup, the normals in workgroups of 256 thinned points. */
+int bev_submap_coarse_voxel_registration_device_resident(bev_ctx_t *ctx, int n_frames, const void *d_pn, size_t stride,
+                                                         const uint32_t *d_counts, float pn_leaf, float radius,
+                                                         const float *viewpoint, int n_maps, const uint64_t *h_map_offsets,
+                                                         const int32_t *h_entry_frame, const float *h_entry_pose, int n_matches,
+                                                         const bev_match_t *h_matches, const bev_icp_params_t *params,
+                                                         bev_icp_result_t *d_results, int32_t *d_best);
+/* The local maps themselves: target(g) of EVERY map of the call (there are no matches), as PointNormal records of 48 bytes.
+ * Map g's records go to d_out + 12 * g * out_stride floats, its record count to d_counts_out[g]; records past the count are
+ * not written.  pn_leaf == 0 is allowed: concat(g).  Frames, maps, ordering and workspace as above (no ICP scratch, no search
+ * grids: 4 E + 120 T + 8 K' + M * (4 + 32) bytes with pn_leaf > 0, 4 E + 48 T + 32 M with pn_leaf == 0; the launch groups are
+ * cut as above).
+ * Status    : as above; with maps also BEV_ERR_INVALID_ARG for NULL d_pn, d_counts, d_out or d_counts_out, stride == 0, and an
+ *             out_stride (in records) smaller than the largest map's capacity n_entries * stride.  n_maps == 0 returns BEV_OK.
+ *             A refused call launches nothing and leaves d_out and d_counts_out untouched. */
+int bev_submap_pn_cloud_device_resident(bev_ctx_t *ctx, int n_frames, const void *d_pn, size_t stride, const uint32_t *d_counts,
+                                        float pn_leaf, float radius, const float *viewpoint, int n_maps,
+                                        const uint64_t *h_map_offsets, const int32_t *h_entry_frame, const float *h_entry_pose,
+                                        uint64_t out_stride, float *d_out, uint32_t *d_counts_out);
+
 /* ---- layout hint -------------------------------------------------------
  * What the caller knows about how its clouds are laid out, so that the library need not look (k_probe reads every 63rd
  * record of a frame to find out: 0.36 MB and 0.07 us of an HDL_64E frame).  Sticky per context; applies to frames of

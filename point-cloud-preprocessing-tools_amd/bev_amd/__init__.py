@@ -99,6 +99,7 @@ ABI_SYMBOLS = [
     "bev_submap_voxel_registration_device_resident", "bev_submap_voxel_registration_batch",
     "bev_submap_voxel_cloud_device_resident",
     "bev_submap_coarse_registration_device_resident",
+    "bev_submap_coarse_voxel_registration_device_resident", "bev_submap_pn_cloud_device_resident",
 ]
 
 # registration front end (include/bev_mi355x.h): pcl::PointXYZ, pcl::Normal, pcl::PointNormal as float rows
@@ -250,6 +251,12 @@ def load_lib() -> C.CDLL:
     if hasattr(lib, "bev_submap_coarse_registration_device_resident"):
         lib.bev_submap_coarse_registration_device_resident.argtypes = [vp, i32, vp, sz, vp, i32, C.POINTER(C.c_uint64), vp, vp,
                                                                        i32, vp, C.POINTER(IcpParams), vp, vp]
+    if hasattr(lib, "bev_submap_coarse_voxel_registration_device_resident"):
+        lib.bev_submap_coarse_voxel_registration_device_resident.argtypes = [vp, i32, vp, sz, vp, C.c_float, C.c_float, vp, i32,
+                                                                             C.POINTER(C.c_uint64), vp, vp, i32, vp,
+                                                                             C.POINTER(IcpParams), vp, vp]
+        lib.bev_submap_pn_cloud_device_resident.argtypes = [vp, i32, vp, sz, vp, C.c_float, C.c_float, vp, i32,
+                                                            C.POINTER(C.c_uint64), vp, vp, C.c_uint64, vp, vp]
     _lib = lib
     return lib
 
@@ -813,6 +820,34 @@ class BevContext:
             map_offsets.ctypes.data_as(C.POINTER(C.c_uint64)), _ptr(entry_frame), _ptr(entry_pose), len(m),
             _ptr(m) if len(m) else None, C.byref(prm), C.c_void_p(d_results or None), C.c_void_p(d_best or None)),
             "bev_submap_coarse_registration_device_resident")
+
+    # ---- the same against maps thinned over their union, normals recomputed ----------------------------
+    def submap_coarse_voxel_registration_device(self, n_frames, d_pn, stride, d_counts, map_offsets, entry_frame, entry_pose,
+                                                matches, d_results, d_best, pn_leaf, radius=2.0, viewpoint=None,
+                                                params: IcpParams | None = None):
+        """bev_submap_coarse_voxel_registration_device_resident: submap_coarse_registration_device with every map's
+        concatenation thinned by a voxel grid of pn_leaf over the union and its 2-D normals recomputed there (radius,
+        viewpoint: three floats, None: the origin).  pn_leaf 0: no grid, submap_coarse_registration_device's bytes."""
+        n_maps, map_offsets, entry_frame, entry_pose = self._submap_entries(map_offsets, entry_frame, entry_pose)
+        m = np.ascontiguousarray(matches, dtype=MATCH_DTYPE)
+        prm = params if params is not None else icp_params()
+        vp = np.ascontiguousarray(viewpoint, dtype=np.float32).reshape(3) if viewpoint is not None else None
+        self._check(self.lib.bev_submap_coarse_voxel_registration_device_resident(
+            self._h, n_frames, C.c_void_p(d_pn or None), stride, C.c_void_p(d_counts or None), pn_leaf, radius, _ptr(vp), n_maps,
+            map_offsets.ctypes.data_as(C.POINTER(C.c_uint64)), _ptr(entry_frame), _ptr(entry_pose), len(m),
+            _ptr(m) if len(m) else None, C.byref(prm), C.c_void_p(d_results or None), C.c_void_p(d_best or None)),
+            "bev_submap_coarse_voxel_registration_device_resident")
+
+    def submap_pn_cloud_device(self, n_frames, d_pn, stride, d_counts, map_offsets, entry_frame, entry_pose, pn_leaf,
+                               out_stride, d_out, d_counts_out, radius=2.0, viewpoint=None):
+        """bev_submap_pn_cloud_device_resident: every map's target (pn_leaf 0: the concatenation) as PointNormal rows of 12
+        floats at d_out + 48 * g * out_stride bytes, its row count at d_counts_out[g] (uint32).  Asynchronous."""
+        n_maps, map_offsets, entry_frame, entry_pose = self._submap_entries(map_offsets, entry_frame, entry_pose)
+        vp = np.ascontiguousarray(viewpoint, dtype=np.float32).reshape(3) if viewpoint is not None else None
+        self._check(self.lib.bev_submap_pn_cloud_device_resident(
+            self._h, n_frames, C.c_void_p(d_pn or None), stride, C.c_void_p(d_counts or None), pn_leaf, radius, _ptr(vp), n_maps,
+            map_offsets.ctypes.data_as(C.POINTER(C.c_uint64)), _ptr(entry_frame), _ptr(entry_pose), int(out_stride),
+            C.c_void_p(d_out or None), C.c_void_p(d_counts_out or None)), "bev_submap_pn_cloud_device_resident")
 
     def set_layout_hint(self, layout: int):
         """LAYOUT_UNKNOWN (the library looks), LAYOUT_STRUCTURED, LAYOUT_FIRING_ORDER: include/bev_mi355x.h"""

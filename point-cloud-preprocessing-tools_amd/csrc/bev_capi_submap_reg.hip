@@ -1,6 +1,7 @@
 /*
  * bev_capi_submap_reg.hip — the scan-to-map part of the extern "C" boundary declared in include/bev_mi355x.h: fine ICP of frames
- * against submaps, the voxel grid over a map's union in front of it (§6l), coarse ICP against them (§6m).
+ * against submaps, the voxel grid over a map's union in front of it (§6l), coarse ICP against them (§6m) and
+ * against maps thinned over their union with recomputed normals (§6q).
  * Host-side only: the kernels are in bev_kernels.hip, the plan of a call in bev_submap_reg_plan.h; bev_reg_host.h is shared with
  * bev_capi_reg.hip, the context (bev_ctx.h) with every file of the C ABI.  What is shared and what is not: DESIGN.md §6n.
  */
@@ -161,22 +162,100 @@ int submap_reg_frames(bev_ctx *c, const bev_point_t *d_clouds, const Call &call,
     return BEV_OK;
 }
 
-/* ---- the coarse path (§6m) ---- */
+/* ---- the coarse path (§6m) and its thinned maps (§6q) ---- */
 
-/* a coarse call's workspace in the coarse stage's buffer: the scratch of an ICP launch, the entries' first indices, the maps of
- * one launch group */
-int submap_coarse_work(bev_ctx *c, const Plan &plan, size_t stride, SubmapCoarseWork &t, uint32_t *&ent_start)
+/* A coarse call's workspace in the coarse stage's buffer: the scratch of an ICP launch (icp: the registration calls), the
+ * entries' first indices, the maps of one launch group: the target rows and their search grids (icp), and for maps thinned over
+ * their union (vox) or written out (the cloud call) the moved rows, the sort's arrays, the voxel indices and positions */
+struct SubmapCoarse {
+    SubmapCoarseWork t{};
+    SubmapPnVoxWork p{};
+    uint32_t *ent_start = nullptr;
+    PlanDev d{};
+};
+int submap_coarse_work(bev_ctx *c, const Plan &plan, const Options &opt, size_t stride, SubmapCoarse &s)
 {
-    const size_t L = std::min(2 * plan.probs.size(), (size_t)kIcpProblemsPerLaunch), E = plan.entries.size();
+    const bool icp = !opt.all_maps, vox = opt.union_voxel, staged = vox || !icp;
+    const size_t L = icp ? std::min(2 * plan.probs.size(), (size_t)kIcpProblemsPerLaunch) : 0, E = plan.entries.size();
     const size_t T = std::max<size_t>((size_t)plan.max_group_pts, 1), M = std::max<size_t>(plan.max_group_maps, 1);
-    t = SubmapCoarseWork{};
-    const size_t sz[] = {L * 16 * stride, std::max<size_t>(E, 1) * 4, T * 48, T * 16, M * sizeof(IcpGridHdr),
-                         M * 4 * (size_t)(kIcpCells + 1)};
-    void **const dst[] = {(void **)&t.cur, (void **)&ent_start, (void **)&t.rows, (void **)&t.sorted, (void **)&t.hdr,
-                          (void **)&t.cell_off};
+    s.t = SubmapCoarseWork{};
+    s.p = SubmapPnVoxWork{};
+    const size_t sz[] = {L * 16 * stride, std::max<size_t>(E, 1) * 4, icp || vox ? T * 48 : 0, icp ? T * 16 : 0,
+                         icp ? M * sizeof(IcpGridHdr) : 0, icp ? M * 4 * (size_t)(kIcpCells + 1) : 0, staged ? T * 48 : 0,
+                         vox ? std::max<size_t>((size_t)plan.max_group_keys, 1) * 8 : 0, vox ? (T + M) * 4 : 0, vox ? T * 4 : 0,
+                         vox ? T * 16 : 0, staged ? M * sizeof(SubvoxHdr) : 0};
+    void **const dst[] = {(void **)&s.t.cur, (void **)&s.ent_start, (void **)&s.t.rows, (void **)&s.t.sorted, (void **)&s.t.hdr,
+                          (void **)&s.t.cell_off, (void **)&s.p.moved, (void **)&s.p.v.keys, (void **)&s.p.v.vstart,
+                          (void **)&s.p.vidx, (void **)&s.p.vpos, (void **)&s.p.v.vh};
     BEVCK(c->reg.icp_buf.grow(c, carve(nullptr, sz, dst)));
     carve(c->reg.icp_buf.p, sz, dst);
+    if (!icp) s.t.sorted = nullptr, s.t.hdr = nullptr, s.t.cell_off = nullptr, s.t.cur = nullptr;
     return BEV_OK;
+}
+
+/* what the coarse entries check behind their own arguments, with maps to build: BEV_OK, or what the entry returns */
+int submap_coarse_check(int n_frames, const void *d_pn, size_t stride, const uint32_t *d_counts, int n_maps,
+                        const uint64_t *h_map_offsets, const int32_t *h_entry_frame, const float *h_entry_pose)
+{
+    if (!d_pn || !d_counts || stride == 0) return BEV_ERR_INVALID_ARG;
+    BEVCK(check_submap_entries(n_frames, n_maps, h_map_offsets, h_entry_frame, h_entry_pose));
+    return BEV_OK;
+}
+/* a map's capacity is n_entries * stride rows: the true counts live on the device, and the host does not wait for them */
+int submap_coarse_capacity(size_t stride, int n_maps, const uint64_t *h_map_offsets)
+{
+    for (int g = 0; g < n_maps; ++g) {
+        const uint64_t ne = h_map_offsets[g + 1] - h_map_offsets[g];
+        if (ne && (uint64_t)stride > BEV_SUBMAP_COARSE_MAX_TARGET / ne) return BEV_ERR_TOO_LARGE;
+    }
+    return BEV_OK;
+}
+
+/* §6k's plan with every frame counted at stride rows and a PointNormal map's bytes; the device reads an entry's FRAME */
+Plan submap_coarse_plan(bev_ctx *c, Call &call, const Options &opt, int n_frames, size_t stride)
+{
+    call.frames.off.assign((size_t)n_frames, 0);
+    call.frames.n.assign((size_t)n_frames, (uint64_t)stride);
+    Plan plan = bevsubreg::plan_call(call, opt, group_cap(c));
+    for (bevsubreg::Entry &en : plan.entries) en.slot = (uint32_t)plan.slot_frame[en.slot];
+    return plan;
+}
+
+/* a group's targets thinned over their union into s.t.rows: moved rows, keys, the sort, centroids, normals;
+ * the search grids where the call has matches */
+void submap_coarse_thin(bev_ctx *c, const Plan &plan, const Group &g, const SubmapCoarse &s, const float *pn, size_t stride,
+                        const uint32_t *d_counts, float pn_leaf, float radius, const float vp[2])
+{
+    const int gm = (int)g.n_maps;
+    const PlanDev &d = s.d;
+    {
+        ProfScope ps(c, K_SUBMAP_PN_MOVE, gm);
+        launch_submap_pn_move(d.maps, g.map0, gm, d.entries, pn, stride, d_counts, s.ent_start, s.p, c->stream);
+    }
+    {
+        ProfScope ps(c, K_SUBMAP_PN_KEYS, gm);
+        launch_submap_pn_keys(d.maps, g.map0, gm, s.p, pn_leaf, c->stream);
+    }
+    const uint32_t tiles = bevsubvox::tiles(g.max_slots);
+    for (const bevsubvox::Stage &sg : bevsubvox::schedule(g.max_slots)) {
+        ProfScope ps(c, sg.kind == bevsubvox::kStageGlobal ? K_SUBMAP_VOX_GLOBAL : K_SUBMAP_VOX_TILE, gm);
+        launch_submap_vox_stage(sg.kind, sg.k, sg.j, g.map0, gm, tiles, s.p.v, c->stream);
+    }
+    {
+        ProfScope ps(c, K_SUBMAP_PN_FINISH, gm);
+        launch_submap_pn_finish(d.maps, g.map0, gm, s.p, s.t.rows, c->stream);
+    }
+    {
+        uint64_t largest = 0;
+        for (uint32_t u = g.map0; u < g.map0 + g.n_maps; ++u) largest = std::max(largest, plan.map_cap[u]);
+        ProfScope ps(c, K_SUBMAP_PN_NORMALS, gm);
+        launch_submap_pn_normals(d.maps, g.map0, gm, (uint32_t)((largest + kIcpThreads - 1) / kIcpThreads), s.p, radius, pn_leaf, vp,
+                                 s.t.rows, c->stream);
+    }
+    if (s.t.hdr) {
+        ProfScope ps(c, K_SUBMAP_PN_GRID, gm);
+        launch_submap_pn_grid(d.maps, g.map0, gm, s.p.v.vh, s.t, c->stream);
+    }
 }
 
 } // namespace
@@ -298,39 +377,35 @@ int bev_submap_registration_batch(bev_ctx_t *c, int n_frames, const bev_point_t 
                                                h_entry_pose, n_matches, h_matches, params, results);
 }
 
-/* ---- scan-to-map coarse ICP: PointNormal frames against submaps (bev_submap_coarse.h) ------------------ */
-int bev_submap_coarse_registration_device_resident(bev_ctx_t *c, int n_frames, const void *d_pn, size_t stride,
-                                                   const uint32_t *d_counts, int n_maps, const uint64_t *h_map_offsets,
-                                                   const int32_t *h_entry_frame, const float *h_entry_pose, int n_matches,
-                                                   const bev_match_t *h_matches, const bev_icp_params_t *params,
-                                                   bev_icp_result_t *d_results, int32_t *d_best)
+/* ---- scan-to-map coarse ICP: PointNormal frames against submaps (bev_submap_coarse.h), and against submaps
+ * thinned over their union with their normals recomputed (bev_submap_pn_vox.h) ---------------------------- */
+int bev_submap_coarse_voxel_registration_device_resident(bev_ctx_t *c, int n_frames, const void *d_pn, size_t stride,
+                                                         const uint32_t *d_counts, float pn_leaf, float radius,
+                                                         const float *viewpoint, int n_maps, const uint64_t *h_map_offsets,
+                                                         const int32_t *h_entry_frame, const float *h_entry_pose, int n_matches,
+                                                         const bev_match_t *h_matches, const bev_icp_params_t *params,
+                                                         bev_icp_result_t *d_results, int32_t *d_best)
 {
     const bev_icp_params_t prm = params ? *params : bev_icp_coarse_defaults();
-    if (!c || n_frames < 0 || n_maps < 0 || n_matches < 0 || !icp_params_ok(prm)) return BEV_ERR_INVALID_ARG;
+    if (!c || n_frames < 0 || n_maps < 0 || n_matches < 0 || !icp_params_ok(prm) || !not_negative(pn_leaf)) return BEV_ERR_INVALID_ARG;
+    const bool vox = pn_leaf > 0.0f;
+    if (vox && !positive(radius)) return BEV_ERR_INVALID_ARG;
     if (n_matches > 0) {
-        if (!d_pn || !d_counts || !h_matches || !d_results || !d_best || stride == 0) return BEV_ERR_INVALID_ARG;
-        BEVCK(check_submap_entries(n_frames, n_maps, h_map_offsets, h_entry_frame, h_entry_pose));
+        if (!h_matches || !d_results || !d_best) return BEV_ERR_INVALID_ARG;
+        BEVCK(submap_coarse_check(n_frames, d_pn, stride, d_counts, n_maps, h_map_offsets, h_entry_frame, h_entry_pose));
         if (!matches_in_range(h_matches, n_matches, n_frames, n_maps)) return BEV_ERR_INVALID_ARG;
-        /* a map's capacity is n_entries * stride rows: the true counts live on the device, and the host does not wait for them */
-        for (int g = 0; g < n_maps; ++g) {
-            const uint64_t ne = h_map_offsets[g + 1] - h_map_offsets[g];
-            if (ne && (uint64_t)stride > BEV_SUBMAP_COARSE_MAX_TARGET / ne) return BEV_ERR_TOO_LARGE;
-        }
+        BEVCK(submap_coarse_capacity(stride, n_maps, h_map_offsets));
     }
     BEVCK(begin_call(c, false));
     if (n_matches == 0) return BEV_OK;
     BEVCK(wait_default_stream(c));
-    /* §6k's plan with every frame counted at stride rows and a PointNormal map's bytes */
     Call call{{}, n_maps, h_map_offsets, h_entry_frame, h_entry_pose, n_matches, h_matches};
-    call.frames.off.assign((size_t)n_frames, 0);
-    call.frames.n.assign((size_t)n_frames, (uint64_t)stride);
     Options opt;
     opt.point_normal = true;
-    Plan plan = bevsubreg::plan_call(call, opt, group_cap(c));
-    for (bevsubreg::Entry &en : plan.entries) en.slot = (uint32_t)plan.slot_frame[en.slot]; /* the device reads the frame */
-    SubmapCoarseWork t;
-    uint32_t *ent_start = nullptr;
-    BEVCK(submap_coarse_work(c, plan, stride, t, ent_start));
+    opt.union_voxel = vox;
+    const Plan plan = submap_coarse_plan(c, call, opt, n_frames, stride);
+    SubmapCoarse s;
+    BEVCK(submap_coarse_work(c, plan, opt, stride, s));
     std::vector<IcpProblem> probs; /* two problems per match, the guesses adjacent */
     probs.reserve(2 * plan.probs.size());
     for (const bevsubreg::Problem &pp : plan.probs)
@@ -343,25 +418,88 @@ int bev_submap_coarse_registration_device_resident(bev_ctx_t *c, int n_frames, c
             bevx::icp_tool_guess(h_matches[pp.result].angle_guess, g, pb.guess);
             probs.push_back(pb);
         }
-    PlanDev d;
-    BEVCK(plan_up(c, c->reg.icp_tab, plan, opt, d, probs.data(), probs.size() * sizeof(IcpProblem)));
+    BEVCK(plan_up(c, c->reg.icp_tab, plan, opt, s.d, probs.data(), probs.size() * sizeof(IcpProblem)));
+    s.p.v.key0 = static_cast<const uint64_t *>(s.d.key0);
+    const float vp[2] = {viewpoint && vox ? viewpoint[0] : 0.0f, viewpoint && vox ? viewpoint[1] : 0.0f};
     const float *pn = static_cast<const float *>(d_pn);
-    const IcpProblem *d_probs = static_cast<const IcpProblem *>(d.probs);
+    const IcpProblem *d_probs = static_cast<const IcpProblem *>(s.d.probs);
     for (const Group &g : plan.groups) {
-        {
+        if (vox) {
+            submap_coarse_thin(c, plan, g, s, pn, stride, d_counts, pn_leaf, radius, vp);
+        } else {
             ProfScope ps(c, K_SUBMAP_PN_TARGET, (int)g.n_maps);
-            launch_submap_pn_target(d.maps, g.map0, (int)g.n_maps, d.entries, pn, stride, d_counts, ent_start, t, c->stream);
+            launch_submap_pn_target(s.d.maps, g.map0, (int)g.n_maps, s.d.entries, pn, stride, d_counts, s.ent_start, s.t, c->stream);
         }
         for (uint32_t p0 = 0; p0 < 2 * g.n_probs; p0 += kIcpProblemsPerLaunch) {
             const int n = (int)std::min<uint32_t>(kIcpProblemsPerLaunch, 2 * g.n_probs - p0);
             ProfScope ps(c, K_SUBMAP_COARSE_ICP, n);
-            launch_submap_coarse_icp(pn, stride, d_counts, d_probs + 2 * (size_t)g.prob0 + p0, n, d.maps, g.map0, t, prm, d_results,
-                                     c->stream);
+            launch_submap_coarse_icp(pn, stride, d_counts, d_probs + 2 * (size_t)g.prob0 + p0, n, s.d.maps, g.map0, s.t, prm,
+                                     d_results, c->stream);
         }
     }
     {
         ProfScope ps(c, K_ICP_BEST, n_matches);
         launch_icp_best(d_results, n_matches, d_best, c->stream);
+    }
+    HIPCK(c, hipGetLastError());
+    return record_tail(c);
+}
+
+int bev_submap_coarse_registration_device_resident(bev_ctx_t *c, int n_frames, const void *d_pn, size_t stride,
+                                                   const uint32_t *d_counts, int n_maps, const uint64_t *h_map_offsets,
+                                                   const int32_t *h_entry_frame, const float *h_entry_pose, int n_matches,
+                                                   const bev_match_t *h_matches, const bev_icp_params_t *params,
+                                                   bev_icp_result_t *d_results, int32_t *d_best)
+{
+    return bev_submap_coarse_voxel_registration_device_resident(c, n_frames, d_pn, stride, d_counts, 0.0f, 0.0f, nullptr, n_maps,
+                                                                h_map_offsets, h_entry_frame, h_entry_pose, n_matches, h_matches,
+                                                                params, d_results, d_best);
+}
+
+int bev_submap_pn_cloud_device_resident(bev_ctx_t *c, int n_frames, const void *d_pn, size_t stride, const uint32_t *d_counts,
+                                        float pn_leaf, float radius, const float *viewpoint, int n_maps,
+                                        const uint64_t *h_map_offsets, const int32_t *h_entry_frame, const float *h_entry_pose,
+                                        uint64_t out_stride, float *d_out, uint32_t *d_counts_out)
+{
+    if (!c || n_frames < 0 || n_maps < 0 || !not_negative(pn_leaf)) return BEV_ERR_INVALID_ARG;
+    const bool vox = pn_leaf > 0.0f;
+    if (vox && !positive(radius)) return BEV_ERR_INVALID_ARG;
+    if (n_maps > 0) {
+        if (!d_out || !d_counts_out) return BEV_ERR_INVALID_ARG;
+        BEVCK(submap_coarse_check(n_frames, d_pn, stride, d_counts, n_maps, h_map_offsets, h_entry_frame, h_entry_pose));
+        BEVCK(submap_coarse_capacity(stride, n_maps, h_map_offsets));
+        for (int g = 0; g < n_maps; ++g)
+            if ((h_map_offsets[g + 1] - h_map_offsets[g]) * (uint64_t)stride > out_stride) return BEV_ERR_INVALID_ARG;
+    }
+    BEVCK(begin_call(c, false));
+    if (n_maps == 0) return BEV_OK;
+    BEVCK(wait_default_stream(c));
+    /* no matches and no ICP: every map's target, built as the registration call builds it, goes out */
+    Call call{{}, n_maps, h_map_offsets, h_entry_frame, h_entry_pose, 0, nullptr};
+    Options opt;
+    opt.point_normal = true;
+    opt.union_voxel = vox;
+    opt.all_maps = true;
+    const Plan plan = submap_coarse_plan(c, call, opt, n_frames, stride);
+    SubmapCoarse s;
+    BEVCK(submap_coarse_work(c, plan, opt, stride, s));
+    BEVCK(plan_up(c, c->reg.icp_tab, plan, opt, s.d));
+    s.p.v.key0 = static_cast<const uint64_t *>(s.d.key0);
+    const float vp[2] = {viewpoint && vox ? viewpoint[0] : 0.0f, viewpoint && vox ? viewpoint[1] : 0.0f};
+    const float *pn = static_cast<const float *>(d_pn);
+    for (const Group &g : plan.groups) {
+        if (vox) {
+            submap_coarse_thin(c, plan, g, s, pn, stride, d_counts, pn_leaf, radius, vp);
+        } else {
+            ProfScope ps(c, K_SUBMAP_PN_MOVE, (int)g.n_maps);
+            launch_submap_pn_move(s.d.maps, g.map0, (int)g.n_maps, s.d.entries, pn, stride, d_counts, s.ent_start, s.p, c->stream);
+        }
+        uint64_t largest = 0;
+        for (uint32_t u = g.map0; u < g.map0 + g.n_maps; ++u) largest = std::max(largest, plan.map_cap[u]);
+        const uint32_t parts = (uint32_t)std::min<uint64_t>((3 * largest + 4 * kIcpThreads - 1) / (4 * kIcpThreads), 256);
+        ProfScope ps(c, K_SUBMAP_PN_OUT, (int)g.n_maps);
+        launch_submap_pn_out(s.d.maps, g.map0, (int)g.n_maps, parts, s.p.v.vh, vox ? s.t.rows : s.p.moved, d_out, out_stride,
+                             d_counts_out, c->stream);
     }
     HIPCK(c, hipGetLastError());
     return record_tail(c);

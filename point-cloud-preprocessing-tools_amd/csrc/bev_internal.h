@@ -234,6 +234,12 @@ enum KernelId {
     K_SUBMAP_VOX_OUT,    /* ... the cloud call: the maps' points and counts into the caller's arrays */
     K_SUBMAP_PN_TARGET,  /* scan-to-map coarse ICP (bev_submap_coarse.h): a map's entries' moved PointNormal rows and their search grid */
     K_SUBMAP_COARSE_ICP, /* ... one workgroup per (match, guess): K_ICP's loop against the map (the better guess: K_ICP_BEST) */
+    K_SUBMAP_PN_MOVE,    /* the union voxel grid and 2-D normals of a PointNormal map (bev_submap_pn_vox.h): the entries' moved rows, concatenated */
+    K_SUBMAP_PN_KEYS,    /* ... the union's bounds and the sort keys (the sort: K_SUBMAP_VOX_TILE, K_SUBMAP_VOX_GLOBAL) */
+    K_SUBMAP_PN_FINISH,  /* ... voxel starts, voxel indices and centroids */
+    K_SUBMAP_PN_NORMALS, /* ... the normals of the thinned points over a 3-D window of the union's grid */
+    K_SUBMAP_PN_GRID,    /* ... the search grid of the thinned rows */
+    K_SUBMAP_PN_OUT,     /* ... the cloud call: the maps' rows and counts into the caller's arrays */
     K_COUNT
 };
 const char *kernel_name(int id);
@@ -478,7 +484,7 @@ struct SubvoxHdr {
     uint32_t nf;       /* finite points among them */
     uint32_t overflow; /* the union's grid has more than INT32_MAX voxels: the target is the concatenation */
     uint32_t n_out;    /* points of the target */
-    uint32_t _pad[3];
+    uint32_t div[3];   /* bev_submap_pn_vox.h: the union grid's divisions along x, y, z where the keys are sorted; else 0 */
 };
 struct SubmapVoxWork {
     float4 *moved;        /* [the group's points]        the concatenation: a map's at its pt0 */
@@ -517,6 +523,28 @@ void launch_submap_pn_target(const void *maps, uint32_t map0, int n_maps, const 
 void launch_submap_coarse_icp(const float *pn, size_t stride, const uint32_t *counts, const IcpProblem *probs, int n,
                               const void *maps, uint32_t map0, const SubmapCoarseWork &t, const bev_icp_params_t &prm,
                               bev_icp_result_t *results, hipStream_t st);
+
+/* ---- the union voxel grid and 2-D normals of a PointNormal map (bev_submap_pn_vox.h) ----
+ * the maps of ONE launch group of a plan with point_normal and union_voxel; the target rows are SubmapCoarseWork::rows */
+struct SubmapPnVoxWork {
+    float *moved;    /* [the group's rows][12]  the concatenation: a map's at its pt0 */
+    SubmapVoxWork v; /* keys, vstart, vh, key0 as in §6l (the sort's kernels read them); v.moved is not used */
+    uint32_t *vidx;  /* [the group's rows]      a thinned point's voxel index in the union's grid */
+    float4 *vpos;    /* [the group's rows]      a thinned point's position */
+};
+void launch_submap_pn_move(const void *maps, uint32_t map0, int n_maps, const void *entries, const float *pn, size_t stride,
+                           const uint32_t *counts, uint32_t *ent_start, const SubmapPnVoxWork &p, hipStream_t st);
+void launch_submap_pn_keys(const void *maps, uint32_t map0, int n_maps, const SubmapPnVoxWork &p, float pn_leaf, hipStream_t st);
+/* target: the group's target rows (thinned positions go to p.vpos; the overflow branch copies the moved rows to target) */
+void launch_submap_pn_finish(const void *maps, uint32_t map0, int n_maps, const SubmapPnVoxWork &p, float *target, hipStream_t st);
+/* parts: workgroups of 256 thinned points along x for each of the n_maps maps (the largest capacity's) */
+void launch_submap_pn_normals(const void *maps, uint32_t map0, int n_maps, uint32_t parts, const SubmapPnVoxWork &p, float radius,
+                              float pn_leaf, const float vp[2], float *target, hipStream_t st);
+void launch_submap_pn_grid(const void *maps, uint32_t map0, int n_maps, const SubvoxHdr *vh, const SubmapCoarseWork &t,
+                           hipStream_t st);
+/* src: the group's row array that holds the targets (moved or thinned); out, counts: the caller's, indexed by map of the plan */
+void launch_submap_pn_out(const void *maps, uint32_t map0, int n_maps, uint32_t parts, const SubvoxHdr *vh, const float *src,
+                          float *out, uint64_t stride, uint32_t *counts, hipStream_t st);
 
 /* opt in to > 64 KiB of dynamic LDS for the kernels that need it */
 hipError_t configure_kernels(const Geometry &g);

@@ -27,6 +27,10 @@
  * of `stride` rows each (frames.n[f] = stride, frames.off unused), a map's capacity is n_entries * stride rows and its bytes are
  * map_coarse_bytes; the caller makes two problems (the guesses) of every Problem.  Everything else is as above; with the
  * default Options every call plans exactly as before.
+ *
+ * point_normal with union_voxel: the PointNormal maps are thinned over their union and their normals recomputed
+ * (bev_submap_pn_vox.h): a map owns its sort keys as under union_voxel, and its bytes are map_coarse_union_bytes.  With all_maps
+ * as well: bev_submap_pn_cloud_device_resident.  Every other combination plans exactly as before.
  */
 #ifndef BEV_SUBMAP_REG_PLAN_H
 #define BEV_SUBMAP_REG_PLAN_H
@@ -45,6 +49,9 @@ namespace bevsubreg {
 constexpr uint32_t kGridCells = 128 * 128; /* kFineCells (bev_internal.h): cells of a map's search grid */
 constexpr uint32_t kCoarseGridCells = 64 * 64; /* kIcpCells: cells of a PointNormal map's search grid */
 constexpr uint32_t kCoarseRowBytes = 48 + 16;  /* ... a moved PointNormal row and its searchable copy */
+/* ... of a PointNormal map thinned over its union, per row of capacity: the thinned row and its searchable copy,
+ * the moved row, a voxel start, a voxel index, a thinned position */
+constexpr uint32_t kCoarseUnionRowBytes = kCoarseRowBytes + 48 + 4 + 4 + 16;
 
 struct Slot { /* FineSlot's layout (bev_internal.h): k_fine_voxel reads the slots */
     uint64_t off;
@@ -105,6 +112,14 @@ inline uint64_t map_bytes(uint64_t cap, bool union_voxel = false)
 /* device bytes of a PointNormal map of cap rows (bev_submap_coarse_registration_device_resident): the moved rows and the
  * searchable points by cell, the 64 x 64 grid's cell offsets, the header */
 inline uint64_t map_coarse_bytes(uint64_t cap) { return cap * kCoarseRowBytes + (uint64_t)(kCoarseGridCells + 1) * 4 + 32; }
+
+/* device bytes of a PointNormal map of cap rows that is thinned over its union (bev_submap_coarse_voxel_registration_device_resident,
+ * bev_submap_pn_cloud_device_resident): kCoarseUnionRowBytes per row, the padded sort keys (8 bytes each), the last voxel start,
+ * the 64 x 64 grid's cell offsets and header, the sort's header */
+inline uint64_t map_coarse_union_bytes(uint64_t cap)
+{
+    return cap * kCoarseUnionRowBytes + bevsubvox::key_slots(cap) * 8 + 4 + (uint64_t)(kCoarseGridCells + 1) * 4 + 32 + 32;
+}
 
 /* points the entries of map g can hold together: the sum of their frames' record counts */
 inline uint64_t map_capacity(const uint64_t *frame_n, const uint64_t *map_offs, const int32_t *entry_frame, int g)
@@ -198,7 +213,9 @@ inline Plan plan_call(const Call &call, const Options &opt, uint64_t cap_bytes)
         g.map0 = u;
         g.prob0 = (uint32_t)pr;
         while (u < (uint32_t)p.maps.size()) {
-            const uint64_t b = opt.point_normal ? map_coarse_bytes(p.map_cap[u]) : map_bytes(p.map_cap[u], opt.union_voxel);
+            const uint64_t b = !opt.point_normal ? map_bytes(p.map_cap[u], opt.union_voxel)
+                               : opt.union_voxel ? map_coarse_union_bytes(p.map_cap[u])
+                                                 : map_coarse_bytes(p.map_cap[u]);
             if (g.n_maps > 0 && g.bytes + b > cap_bytes) break;
             p.maps[u].pt0 = g.pts;
             if (opt.union_voxel) {

@@ -30,7 +30,10 @@
  * defaults), then fine ICP from the better coarse result (bev_submap_voxel_registration_device_resident with the coarse table,
  * bev_icp_fine_defaults() and map_leaf).  Bookkeeping, both [TIME] lines, the summary line and the report file
  * (icp_precision_report.txt: the final transform against the chosen coarse one) are batch_top_part_registration's; with half_window
- * 0 and map_leaf 0 it is that tool.
+ * 0 and map_leaf 0 it is that tool.  BEV_SUBMAP_PN_LEAF in the environment (this tool alone): a finite number > 0
+ * thins every coarse map by a voxel grid of that leaf over the union of its moved clouds and recomputes its 2-D normals there
+ * (bev_submap_coarse_voxel_registration_device_resident, radius 2, viewpoint 0: the front end's settings); unset, empty or 0: the
+ * output as ever; anything else: exit 1 with "BEV_SUBMAP_PN_LEAF '<text>': expected a finite number >= 0" before any GPU work.
  *
  * The chunks, the chain and the bookkeeping are the four registration tools' own (RegistrationChunks.h, RegistrationChain.h;
  * DESIGN.md §6p), the entries' matrices every submap tool's (submapwin::appendEntryPose): this file is the command line, which
@@ -76,7 +79,12 @@ int main(int argc, char **argv)
         usage();
         return 1;
     }
-    float map_leaf = 0.0f;
+    float map_leaf = 0.0f, pn_leaf = 0.0f;
+    if (const char *env = kTopPart ? std::getenv("BEV_SUBMAP_PN_LEAF") : nullptr)
+        if (*env && !parse_map_leaf(env, &pn_leaf)) {
+            std::cerr << "BEV_SUBMAP_PN_LEAF '" << env << "': expected a finite number >= 0\n";
+            return 1;
+        }
     if (argc > 5 && !parse_map_leaf(argv[5], &map_leaf)) {
         std::cerr << "map_leaf '" << argv[5] << "': expected a finite number >= 0\n";
         usage();
@@ -133,7 +141,7 @@ int main(int argc, char **argv)
         for (size_t k = 0; k < chunk.matches.size(); ++k)
             for (uint64_t e = chunk.map_offs[k]; e < chunk.map_offs[k + 1]; ++e)
                 submapwin::appendEntryPose(pose, matches[m0 + k].match_idx, chunk.files[chunk.entry_frame[e]], entry_pose);
-        if (const int rc = regchain::registerChunk(paths, chunk, &entry_pose, map_leaf, kTopPart, prm, tally)) return rc;
+        if (const int rc = regchain::registerChunk(paths, chunk, &entry_pose, map_leaf, kTopPart, prm, tally, pn_leaf)) return rc;
         m0 = chunk.m1;
     }
     /* batch_submap_registration's fine line is the whole visit of the device, uploads included */
