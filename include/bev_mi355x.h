@@ -750,6 +750,70 @@ int bev_submap_pn_cloud_device_resident(bev_ctx_t *ctx, int n_frames, const void
                                         const uint64_t *h_map_offsets, const int32_t *h_entry_frame, const float *h_entry_pose,
                                         uint64_t out_stride, float *d_out, uint32_t *d_counts_out);
 
+/* ---- scan-to-map coarse ICP against the TOP PART OVER THE UNION of a map's moved full clouds ---------------------------------
+ * What the reference hands coarse ICP is ONE cloud put through extractTopAndFlatten, VoxelGrid<PointXYZ> and Normal2dEstimation;
+ * where the target is a local map, that cloud is the union of the map's moved full clouds.  The calls above
+ * concatenate each sweep's own top part instead; these two build the top part over the union.  Maps: h_map_offsets,
+ * h_entry_frame, h_entry_pose exactly as above.  Full labelled clouds: d_clouds / h_offsets exactly as
+ * bev_submap_voxel_registration_device_resident takes them (h_offsets == NULL: d_ordered, S records per frame).
+ *   union(g)  = the concatenation, over g's entries IN THE ORDER GIVEN, of bev_transform_cloud(frame(e), pose(e)): whole
+ *               bev_point_t records, labels and the other fields carried; a record's index is its position in the concatenation;
+ *   top(g)    = bev_top_part_flatten(union(g)), its contract unchanged: label 0 is skipped; a record whose MOVED x, y or z is
+ *               not finite is skipped; the cell is taken from the moved x, y with round, in the 10 x 10 grid; a cell of fewer
+ *               than 20 records is skipped; a kept cell emits round(0.2f * n) records, highest moved z first (-0 = +0), the
+ *               lower union index first on equal z; output (x, y, 0), cells in gx-major then gy order.  Ties therefore go to the
+ *               earlier entry: the order of a map's entries matters;
+ *   V         = bev_voxel_grid_xyz(top(g), pn_leaf); in its "leaf too small" branch V = top(g) (and N is still computed);
+ *   N         = bev_normals_2d(V, radius mode, radius, viewpoint);
+ *   target(g)[i] = the PointNormal record  x y z 0 | nx ny nz 0 | curvature 0 0 0  of V[i] and N[i]: 48 bytes, pads 0, every
+ *               NaN 0x7fc00000.
+ * A map without entries, or whose cells all stay under 20 records, has an empty target and ends as an empty target does above.
+ * Capacity  : a map's capacity is the sum of its entries' frames' record counts, at most BEV_SUBMAP_TOP_MAX_UNION = 2^24: the
+ *             selection works on keys  cell (7 bits) | descending-z key (32) | union index (25)  and holds at most
+ *             bev_submap_top_part_max_out(2^24) < 2^22 of them.
+ * Ordering  : both calls are asynchronous and ordered exactly like bev_submap_coarse_voxel_registration_device_resident.
+ * Workspace : in the coarse stage's buffer.  With U the union records, T' the sum of bev_submap_top_part_max_out(capacity) and
+ *             K" the sum of the smallest powers of two >= these, over the maps of the launch group that needs most, and M its
+ *             maps: 8 U (a key per record; the moved records are never written: a selected record is moved again) +
+ *             M * (2816 + 25600) (the 100 cells' tables and histograms) + 136 T' + 8 K" + M * (4 * 4097 + 68) + the ICP scratch
+ *             min(2 * n_matches, 1024) * 16 * stride, pieces rounded up to 256; the tables take 16 bytes per frame named and 16
+ *             more per used map.  The launch groups are cut so that all but the scratch fits the cap (BEV_SUBMAP_REG_GROUP;
+ *             results do not depend on it).
+ *
+ * The cloud call: target(g) of EVERY map as rows of 48 bytes at d_out + 12 * g * out_stride floats, its count in
+ * d_counts_out[g]; rows past the count are not written.  out_stride is in records and must be at least
+ * bev_submap_top_part_max_out of the largest capacity.  pn_leaf == 0 writes top(g) itself as rows
+ * x y 0 0 | 0 0 0 0 | 0 0 0 0: no voxel stage and no normals; radius and viewpoint are not read.
+ * Status    : BEV_ERR_INVALID_ARG for a NULL context, a negative count, a negative, NaN or infinite pn_leaf, with pn_leaf > 0 a
+ *             radius that bev_normals_2d refuses, and, with maps, a NULL array that is needed, decreasing offsets, an entry frame
+ *             outside the frames, a capacity above BEV_SUBMAP_TOP_MAX_UNION, a short out_stride; BEV_ERR_TOO_LARGE for more than
+ *             BEV_SUBMAP_MAX_ENTRIES entries.  n_maps == 0 returns BEV_OK.  A refused call launches nothing and leaves d_out
+ *             and d_counts_out untouched. */
+#define BEV_SUBMAP_TOP_MAX_UNION (1u << 24) /* records of one map's union */
+size_t bev_submap_top_part_max_out(size_t union_records); /* host only: bev_regfront_max_out of the union */
+int bev_submap_top_part_cloud_device_resident(bev_ctx_t *ctx, int n_frames, const bev_point_t *d_clouds, const uint64_t *h_offsets,
+                                              float pn_leaf, float radius, const float *viewpoint, int n_maps,
+                                              const uint64_t *h_map_offsets, const int32_t *h_entry_frame,
+                                              const float *h_entry_pose, uint64_t out_stride, float *d_out, uint32_t *d_counts_out);
+/* The registration call.  The QUERIES are d_pn / stride / d_counts, the front end's output for the same n_frames frames, exactly
+ * as bev_submap_coarse_registration_device_resident reads them.  For match m = (query_idx, match_idx = a MAP's index,
+ * angle_guess) and guess k in {0, 1}
+ *   d_results[2m + k] = bev_icp_point_to_plane(d_pn rows of frame query_idx, target(match_idx), guess k of angle_guess, params)
+ * bit for bit as a whole bev_icp_result_t; d_best as above; both go straight into
+ * bev_submap_voxel_registration_device_resident as d_coarse / d_best without a synchronisation.  A map no match names costs
+ * nothing.  params NULL: the coarse defaults.
+ * Status    : as the cloud call's, and BEV_ERR_INVALID_ARG for a pn_leaf that is not finite and > 0 (0 too), invalid
+ *             parameters, and, with matches, NULL h_matches, d_results, d_best, d_pn or d_counts, stride == 0, a query_idx
+ *             outside the frames, a match_idx outside the maps.  n_matches == 0 returns BEV_OK.  A refused call launches nothing
+ *             and leaves d_results and d_best untouched. */
+int bev_submap_top_part_coarse_registration_device_resident(bev_ctx_t *ctx, int n_frames, const bev_point_t *d_clouds,
+                                                            const uint64_t *h_offsets, const void *d_pn, size_t stride,
+                                                            const uint32_t *d_counts, float pn_leaf, float radius,
+                                                            const float *viewpoint, int n_maps, const uint64_t *h_map_offsets,
+                                                            const int32_t *h_entry_frame, const float *h_entry_pose, int n_matches,
+                                                            const bev_match_t *h_matches, const bev_icp_params_t *params,
+                                                            bev_icp_result_t *d_results, int32_t *d_best);
+
 /* ---- layout hint -------------------------------------------------------
  * What the caller knows about how its clouds are laid out, so that the library need not look (k_probe reads every 63rd
  * record of a frame to find out: 0.36 MB and 0.07 us of an HDL_64E frame).  Sticky per context; applies to frames of

@@ -100,6 +100,8 @@ ABI_SYMBOLS = [
     "bev_submap_voxel_cloud_device_resident",
     "bev_submap_coarse_registration_device_resident",
     "bev_submap_coarse_voxel_registration_device_resident", "bev_submap_pn_cloud_device_resident",
+    "bev_submap_top_part_cloud_device_resident", "bev_submap_top_part_coarse_registration_device_resident",
+    "bev_submap_top_part_max_out",
 ]
 
 # registration front end (include/bev_mi355x.h): pcl::PointXYZ, pcl::Normal, pcl::PointNormal as float rows
@@ -257,6 +259,14 @@ def load_lib() -> C.CDLL:
                                                                              C.POINTER(IcpParams), vp, vp]
         lib.bev_submap_pn_cloud_device_resident.argtypes = [vp, i32, vp, sz, vp, C.c_float, C.c_float, vp, i32,
                                                             C.POINTER(C.c_uint64), vp, vp, C.c_uint64, vp, vp]
+    if hasattr(lib, "bev_submap_top_part_cloud_device_resident"):
+        lib.bev_submap_top_part_cloud_device_resident.argtypes = [vp, i32, vp, C.POINTER(C.c_uint64), C.c_float, C.c_float, vp,
+                                                                  i32, C.POINTER(C.c_uint64), vp, vp, C.c_uint64, vp, vp]
+        lib.bev_submap_top_part_coarse_registration_device_resident.argtypes = [
+            vp, i32, vp, C.POINTER(C.c_uint64), vp, sz, vp, C.c_float, C.c_float, vp, i32, C.POINTER(C.c_uint64), vp, vp, i32, vp,
+            C.POINTER(IcpParams), vp, vp]
+        lib.bev_submap_top_part_max_out.argtypes = [sz]
+        lib.bev_submap_top_part_max_out.restype = sz
     _lib = lib
     return lib
 
@@ -849,6 +859,39 @@ class BevContext:
             map_offsets.ctypes.data_as(C.POINTER(C.c_uint64)), _ptr(entry_frame), _ptr(entry_pose), int(out_stride),
             C.c_void_p(d_out or None), C.c_void_p(d_counts_out or None)), "bev_submap_pn_cloud_device_resident")
 
+    # ---- the same against the thinned top part over the union of a map's moved FULL clouds -------------
+    def submap_top_part_cloud_device(self, n_frames, d_clouds, offsets, map_offsets, entry_frame, entry_pose, pn_leaf,
+                                     out_stride, d_out, d_counts_out, radius=2.0, viewpoint=None):
+        """bev_submap_top_part_cloud_device_resident: full labelled clouds as for submap_voxel_registration_device (offsets
+        None: d_ordered); every map's target, the top part over the union of its entries' moved clouds thinned by pn_leaf with
+        its 2-D normals (pn_leaf 0: the top part's rows x y 0 and zeros), as PointNormal rows of 12 floats at
+        d_out + 48 * g * out_stride bytes (out_stride >= submap_top_part_max_out of the largest union), its row count at
+        d_counts_out[g] (uint32).  Asynchronous."""
+        offsets, offs = _offsets(offsets, n_frames) if offsets is not None else (None, None)
+        n_maps, map_offsets, entry_frame, entry_pose = self._submap_entries(map_offsets, entry_frame, entry_pose)
+        vp = np.ascontiguousarray(viewpoint, dtype=np.float32).reshape(3) if viewpoint is not None else None
+        self._check(self.lib.bev_submap_top_part_cloud_device_resident(
+            self._h, n_frames, C.c_void_p(d_clouds or None), offs, pn_leaf, radius, _ptr(vp), n_maps,
+            map_offsets.ctypes.data_as(C.POINTER(C.c_uint64)), _ptr(entry_frame), _ptr(entry_pose), int(out_stride),
+            C.c_void_p(d_out or None), C.c_void_p(d_counts_out or None)), "bev_submap_top_part_cloud_device_resident")
+
+    def submap_top_part_coarse_registration_device(self, n_frames, d_clouds, offsets, d_pn, stride, d_counts, map_offsets,
+                                                   entry_frame, entry_pose, matches, d_results, d_best, pn_leaf, radius=2.0,
+                                                   viewpoint=None, params: IcpParams | None = None):
+        """bev_submap_top_part_coarse_registration_device_resident: the queries are the front end's rows (d_pn, stride,
+        d_counts) of the same n_frames frames; match m's query is registered point-to-plane, from both yaw guesses, against
+        submap_top_part_cloud_device's target of map match_idx (pn_leaf > 0).  Outputs as submap_coarse_registration_device's."""
+        offsets, offs = _offsets(offsets, n_frames) if offsets is not None else (None, None)
+        n_maps, map_offsets, entry_frame, entry_pose = self._submap_entries(map_offsets, entry_frame, entry_pose)
+        m = np.ascontiguousarray(matches, dtype=MATCH_DTYPE)
+        prm = params if params is not None else icp_params()
+        vp = np.ascontiguousarray(viewpoint, dtype=np.float32).reshape(3) if viewpoint is not None else None
+        self._check(self.lib.bev_submap_top_part_coarse_registration_device_resident(
+            self._h, n_frames, C.c_void_p(d_clouds or None), offs, C.c_void_p(d_pn or None), stride, C.c_void_p(d_counts or None),
+            pn_leaf, radius, _ptr(vp), n_maps, map_offsets.ctypes.data_as(C.POINTER(C.c_uint64)), _ptr(entry_frame),
+            _ptr(entry_pose), len(m), _ptr(m) if len(m) else None, C.byref(prm), C.c_void_p(d_results or None),
+            C.c_void_p(d_best or None)), "bev_submap_top_part_coarse_registration_device_resident")
+
     def set_layout_hint(self, layout: int):
         """LAYOUT_UNKNOWN (the library looks), LAYOUT_STRUCTURED, LAYOUT_FIRING_ORDER: include/bev_mi355x.h"""
         self._check(self.lib.bev_set_layout_hint(self._h, layout), "bev_set_layout_hint")
@@ -918,6 +961,11 @@ def project_batch_out_points(kind: int, n_frames: int, offsets) -> int:
 def regfront_max_out(n: int) -> int:
     """Records the registration front end can emit for a cloud of n points (host only)."""
     return int(load_lib().bev_regfront_max_out(n))
+
+
+def submap_top_part_max_out(union_records: int) -> int:
+    """Rows the top part over a union of that many records can have (host only): submap_top_part_cloud_device's out_stride."""
+    return int(load_lib().bev_submap_top_part_max_out(union_records))
 
 
 def _pn12(a) -> np.ndarray:

@@ -1,7 +1,8 @@
 /*
  * bev_capi_submap_reg.hip — the scan-to-map part of the extern "C" boundary declared in include/bev_mi355x.h: fine ICP of frames
  * against submaps, the voxel grid over a map's union in front of it (§6l), coarse ICP against them (§6m) and
- * against maps thinned over their union with recomputed normals (§6q).
+ * against maps thinned over their union with recomputed normals (§6q), and against the top part over the union of a map's moved
+ * full clouds, thinned the same way (§6r).
  * Host-side only: the kernels are in bev_kernels.hip, the plan of a call in bev_submap_reg_plan.h; bev_reg_host.h is shared with
  * bev_capi_reg.hip, the context (bev_ctx.h) with every file of the C ABI.  What is shared and what is not: DESIGN.md §6n.
  */
@@ -36,21 +37,25 @@ int submap_reg_check(const Call &call)
     return BEV_OK;
 }
 
-/* the plan's tables in one block of tab, the device's on return: the slots (fine), the maps, the entries (64-byte aligned), the
- * caller's problems if it has any, the maps' first keys (union_voxel; else nullptr) */
+/* the plan's tables in one block of tab, the device's on return: the slots (fine, top_union), the maps, the entries (64-byte
+ * aligned), the caller's problems if it has any, the maps' first keys (union_voxel; else nullptr), their first union keys
+ * (top_union; else nullptr) */
 struct PlanDev {
-    void *slots, *maps, *entries, *probs, *key0;
+    void *slots, *maps, *entries, *probs, *key0, *u0;
 };
 int plan_up(bev_ctx *c, UploadTable &tab, const Plan &plan, const Options &opt, PlanDev &d, const void *probs = nullptr,
             size_t prob_bytes = 0)
 {
     static_assert(sizeof(bevsubreg::Slot) == sizeof(FineSlot), "the plan's slots are k_fine_voxel's");
-    const void *const src[] = {plan.slots.data(), plan.maps.data(), plan.entries.data(), probs, plan.map_key0.data()};
-    const size_t sz[] = {opt.point_normal ? 0 : plan.slots.size() * sizeof(FineSlot), plan.maps.size() * sizeof(bevsubreg::Map),
-                         plan.entries.size() * sizeof(bevsubreg::Entry), prob_bytes, opt.union_voxel ? plan.maps.size() * 8 : 0};
-    void **const dst[] = {&d.slots, &d.maps, &d.entries, &d.probs, &d.key0};
+    const void *const src[] = {plan.slots.data(), plan.maps.data(), plan.entries.data(), probs, plan.map_key0.data(),
+                               plan.map_u0.data()};
+    const size_t sz[] = {opt.point_normal && !opt.top_union ? 0 : plan.slots.size() * sizeof(FineSlot),
+                         plan.maps.size() * sizeof(bevsubreg::Map), plan.entries.size() * sizeof(bevsubreg::Entry), prob_bytes,
+                         opt.union_voxel ? plan.maps.size() * 8 : 0, opt.top_union ? plan.maps.size() * 8 : 0};
+    void **const dst[] = {&d.slots, &d.maps, &d.entries, &d.probs, &d.key0, &d.u0};
     BEVCK(table_up(c, tab, sz, src, dst));
     if (!sz[4]) d.key0 = nullptr;
+    if (!sz[5]) d.u0 = nullptr;
     return BEV_OK;
 }
 
@@ -256,6 +261,128 @@ void submap_coarse_thin(bev_ctx *c, const Plan &plan, const Group &g, const Subm
         ProfScope ps(c, K_SUBMAP_PN_GRID, gm);
         launch_submap_pn_grid(d.maps, g.map0, gm, s.p.v.vh, s.t, c->stream);
     }
+}
+
+/* ---- the top part over the union of a map's moved full clouds (§6r) ---- */
+
+/* what the two entries check behind their own arguments, with maps to build: the frame table, the entries, the unions' sizes;
+ * largest: the largest union of the call's maps */
+int submap_top_check(bev_ctx *c, int n_frames, const bev_point_t *d_clouds, const uint64_t *h_offsets, Call &call, uint64_t *largest)
+{
+    if (!frame_table(n_frames, h_offsets, (uint64_t)c->geo.S, call.frames)) return BEV_ERR_INVALID_ARG;
+    BEVCK(check_submap_entries(n_frames, call.n_maps, call.map_offs, call.entry_frame, call.entry_pose));
+    *largest = 0;
+    for (int g = 0; g < call.n_maps; ++g) {
+        const uint64_t cap = bevsubreg::map_capacity(call.frames.n.data(), call.map_offs, call.entry_frame, g);
+        if (cap > BEV_SUBMAP_TOP_MAX_UNION) return BEV_ERR_INVALID_ARG;
+        *largest = std::max(*largest, cap);
+    }
+    return d_clouds ? BEV_OK : BEV_ERR_INVALID_ARG;
+}
+
+/* A call's workspace in the coarse stage's buffer: submap_coarse_work's pieces for thinned maps of top_max_out rows (icp: the
+ * registration call's scratch and search grids), and the select's: a key per record of the group's unions, the cells' tables and
+ * histograms (adjacent: one memset clears both) */
+struct SubmapTop {
+    SubmapCoarse s;
+    SubmapTopWork t{};
+    size_t cell_stride = 0; /* bytes from the cells' tables to the histograms */
+};
+int submap_top_work(bev_ctx *c, const Plan &plan, bool icp, size_t stride, SubmapTop &w)
+{
+    SubmapCoarse &s = w.s;
+    const size_t L = icp ? std::min(2 * plan.probs.size(), (size_t)kIcpProblemsPerLaunch) : 0;
+    const size_t T = std::max<size_t>((size_t)plan.max_group_pts, 1), M = std::max<size_t>(plan.max_group_maps, 1);
+    const size_t U = std::max<size_t>((size_t)plan.max_group_union, 1);
+    s.t = SubmapCoarseWork{};
+    s.p = SubmapPnVoxWork{};
+    const size_t sz[] = {L * 16 * stride, T * 48, icp ? T * 16 : 0, icp ? M * sizeof(IcpGridHdr) : 0,
+                         icp ? M * 4 * (size_t)(kIcpCells + 1) : 0, T * 48, std::max<size_t>((size_t)plan.max_group_keys, 1) * 8,
+                         (T + M) * 4, T * 4, T * 16, M * sizeof(SubvoxHdr), U * 8, M * sizeof(SubtopCells),
+                         M * (size_t)kTopHistWords * 4};
+    void **const dst[] = {(void **)&s.t.cur, (void **)&s.t.rows, (void **)&s.t.sorted, (void **)&s.t.hdr, (void **)&s.t.cell_off,
+                          (void **)&s.p.moved, (void **)&s.p.v.keys, (void **)&s.p.v.vstart, (void **)&s.p.vidx, (void **)&s.p.vpos,
+                          (void **)&s.p.v.vh, (void **)&w.t.ukeys, (void **)&w.t.cells, (void **)&w.t.hist};
+    BEVCK(c->reg.icp_buf.grow(c, carve(nullptr, sz, dst)));
+    carve(c->reg.icp_buf.p, sz, dst);
+    if (!icp) s.t.sorted = nullptr, s.t.hdr = nullptr, s.t.cell_off = nullptr, s.t.cur = nullptr;
+    w.cell_stride = align256(M * sizeof(SubtopCells));
+    return BEV_OK;
+}
+
+/* the sort of a group's key arrays as bev_submap_vox_plan.h schedules it */
+void submap_sort_keys(bev_ctx *c, const Group &g, const SubmapVoxWork &v)
+{
+    const uint32_t tiles = bevsubvox::tiles(g.max_slots);
+    for (const bevsubvox::Stage &sg : bevsubvox::schedule(g.max_slots)) {
+        ProfScope ps(c, sg.kind == bevsubvox::kStageGlobal ? K_SUBMAP_VOX_GLOBAL : K_SUBMAP_VOX_TILE, (int)g.n_maps);
+        launch_submap_vox_stage(sg.kind, sg.k, sg.j, g.map0, (int)g.n_maps, tiles, v, c->stream);
+    }
+}
+
+/* a group's targets: the keys of the unions, the select, the sorted selection, the rows of top(g) in s.p.moved;
+ * pn_leaf > 0: thinned with their normals into s.t.rows as §6q thins a concatenation, the search grids where the call has matches */
+int submap_top_targets(bev_ctx *c, const Plan &plan, const Group &g, const SubmapTop &w, const bev_point_t *d_clouds, float pn_leaf,
+                       float radius, const float vp[2])
+{
+    const int gm = (int)g.n_maps;
+    const SubmapCoarse &s = w.s;
+    const PlanDev &d = s.d;
+    uint64_t rows = 0;
+    for (uint32_t u = g.map0; u < g.map0 + g.n_maps; ++u) rows = std::max(rows, plan.map_cap[u]);
+    /* workgroups of 4096 records of the largest union, of 256 rows of the largest top part */
+    const uint32_t parts = (uint32_t)std::min<uint64_t>((g.max_union + 16 * kIcpThreads - 1) / (16 * kIcpThreads), 512);
+    const uint32_t row_parts = (uint32_t)std::min<uint64_t>((rows + kIcpThreads - 1) / kIcpThreads, 1024);
+    HIPCK(c, hipMemsetAsync(w.t.cells, 0, w.cell_stride + (size_t)gm * kTopHistWords * 4, c->stream));
+    {
+        ProfScope ps(c, K_SUBMAP_TOP_KEYS, gm);
+        launch_submap_top_keys(d.maps, g.map0, gm, parts, d.entries, d.slots, d_clouds, w.t, c->stream);
+    }
+    {
+        ProfScope ps(c, K_SUBMAP_TOP_CELLS, gm);
+        launch_submap_top_cells(gm, w.t, s.p.v.vh, c->stream);
+    }
+    for (int shift = (int)((kTopKeyBits - 1) / kTopDigitBits * kTopDigitBits); shift >= 0; shift -= (int)kTopDigitBits) {
+        {
+            ProfScope ps(c, K_SUBMAP_TOP_HIST, gm);
+            launch_submap_top_digit(d.maps, g.map0, gm, parts, d.entries, w.t, (uint32_t)shift, false, c->stream);
+        }
+        ProfScope ps(c, K_SUBMAP_TOP_SCAN, gm);
+        launch_submap_top_digit(d.maps, g.map0, gm, parts, d.entries, w.t, (uint32_t)shift, true, c->stream);
+    }
+    {
+        ProfScope ps(c, K_SUBMAP_TOP_COMPACT, gm);
+        launch_submap_top_compact(d.maps, g.map0, gm, parts, d.entries, w.t, s.p.v, c->stream);
+    }
+    submap_sort_keys(c, g, s.p.v);
+    {
+        ProfScope ps(c, K_SUBMAP_TOP_ROWS, gm);
+        launch_submap_top_rows(d.maps, g.map0, gm, row_parts, d.entries, d.slots, d_clouds, w.t, s.p, c->stream);
+    }
+    if (!(pn_leaf > 0.0f)) return BEV_OK;
+    {
+        ProfScope ps(c, K_SUBMAP_PN_KEYS, gm);
+        launch_submap_pn_keys(d.maps, g.map0, gm, s.p, pn_leaf, c->stream);
+    }
+    submap_sort_keys(c, g, s.p.v);
+    {
+        ProfScope ps(c, K_SUBMAP_PN_FINISH, gm);
+        launch_submap_pn_finish(d.maps, g.map0, gm, s.p, s.t.rows, c->stream);
+    }
+    {
+        ProfScope ps(c, K_SUBMAP_TOP_OVERFLOW, gm);
+        launch_submap_top_overflow(d.maps, g.map0, gm, s.p, c->stream);
+    }
+    {
+        ProfScope ps(c, K_SUBMAP_PN_NORMALS, gm);
+        launch_submap_pn_normals(d.maps, g.map0, gm, (uint32_t)((rows + kIcpThreads - 1) / kIcpThreads), s.p, radius, pn_leaf, vp,
+                                 s.t.rows, c->stream);
+    }
+    if (s.t.hdr) {
+        ProfScope ps(c, K_SUBMAP_PN_GRID, gm);
+        launch_submap_pn_grid(d.maps, g.map0, gm, s.p.v.vh, s.t, c->stream);
+    }
+    return BEV_OK;
 }
 
 } // namespace
@@ -500,6 +627,111 @@ int bev_submap_pn_cloud_device_resident(bev_ctx_t *c, int n_frames, const void *
         ProfScope ps(c, K_SUBMAP_PN_OUT, (int)g.n_maps);
         launch_submap_pn_out(s.d.maps, g.map0, (int)g.n_maps, parts, s.p.v.vh, vox ? s.t.rows : s.p.moved, d_out, out_stride,
                              d_counts_out, c->stream);
+    }
+    HIPCK(c, hipGetLastError());
+    return record_tail(c);
+}
+
+/* ---- the top part over the union of a map's moved full clouds, thinned, as the coarse stage's target (bev_submap_top.h;
+ * DESIGN.md §6r) ---------------------------------------------------------------------------------------------------------- */
+size_t bev_submap_top_part_max_out(size_t union_records) { return (size_t)bevsubreg::top_max_out(union_records); }
+
+int bev_submap_top_part_cloud_device_resident(bev_ctx_t *c, int n_frames, const bev_point_t *d_clouds, const uint64_t *h_offsets,
+                                              float pn_leaf, float radius, const float *viewpoint, int n_maps,
+                                              const uint64_t *h_map_offsets, const int32_t *h_entry_frame,
+                                              const float *h_entry_pose, uint64_t out_stride, float *d_out, uint32_t *d_counts_out)
+{
+    if (!c || n_frames < 0 || n_maps < 0 || !not_negative(pn_leaf)) return BEV_ERR_INVALID_ARG;
+    const bool vox = pn_leaf > 0.0f;
+    if (vox && !positive(radius)) return BEV_ERR_INVALID_ARG;
+    Call call{{}, n_maps, h_map_offsets, h_entry_frame, h_entry_pose, 0, nullptr};
+    if (n_maps > 0) {
+        if (!d_out || !d_counts_out) return BEV_ERR_INVALID_ARG;
+        uint64_t largest = 0;
+        BEVCK(submap_top_check(c, n_frames, d_clouds, h_offsets, call, &largest));
+        if (out_stride < bevsubreg::top_max_out(largest)) return BEV_ERR_INVALID_ARG;
+    }
+    BEVCK(begin_call(c, false));
+    if (n_maps == 0) return BEV_OK;
+    BEVCK(wait_default_stream(c));
+    Options opt;
+    opt.point_normal = opt.union_voxel = opt.top_union = opt.all_maps = true;
+    const Plan plan = bevsubreg::plan_call(call, opt, group_cap(c));
+    SubmapTop w;
+    BEVCK(submap_top_work(c, plan, false, 0, w));
+    BEVCK(plan_up(c, c->reg.icp_tab, plan, opt, w.s.d));
+    w.s.p.v.key0 = static_cast<const uint64_t *>(w.s.d.key0);
+    w.t.u0 = static_cast<const uint64_t *>(w.s.d.u0);
+    const float vp[2] = {viewpoint && vox ? viewpoint[0] : 0.0f, viewpoint && vox ? viewpoint[1] : 0.0f};
+    for (const Group &g : plan.groups) {
+        BEVCK(submap_top_targets(c, plan, g, w, d_clouds, pn_leaf, radius, vp));
+        uint64_t largest = 0;
+        for (uint32_t u = g.map0; u < g.map0 + g.n_maps; ++u) largest = std::max(largest, plan.map_cap[u]);
+        const uint32_t parts = (uint32_t)std::min<uint64_t>((3 * largest + 4 * kIcpThreads - 1) / (4 * kIcpThreads), 256);
+        ProfScope ps(c, K_SUBMAP_PN_OUT, (int)g.n_maps);
+        launch_submap_pn_out(w.s.d.maps, g.map0, (int)g.n_maps, parts, w.s.p.v.vh, vox ? w.s.t.rows : w.s.p.moved, d_out, out_stride,
+                             d_counts_out, c->stream);
+    }
+    HIPCK(c, hipGetLastError());
+    return record_tail(c);
+}
+
+int bev_submap_top_part_coarse_registration_device_resident(bev_ctx_t *c, int n_frames, const bev_point_t *d_clouds,
+                                                            const uint64_t *h_offsets, const void *d_pn, size_t stride,
+                                                            const uint32_t *d_counts, float pn_leaf, float radius,
+                                                            const float *viewpoint, int n_maps, const uint64_t *h_map_offsets,
+                                                            const int32_t *h_entry_frame, const float *h_entry_pose, int n_matches,
+                                                            const bev_match_t *h_matches, const bev_icp_params_t *params,
+                                                            bev_icp_result_t *d_results, int32_t *d_best)
+{
+    const bev_icp_params_t prm = params ? *params : bev_icp_coarse_defaults();
+    if (!c || n_frames < 0 || n_maps < 0 || n_matches < 0 || !icp_params_ok(prm) || !positive(pn_leaf) || !positive(radius))
+        return BEV_ERR_INVALID_ARG;
+    Call call{{}, n_maps, h_map_offsets, h_entry_frame, h_entry_pose, n_matches, h_matches};
+    if (n_matches > 0) {
+        if (!h_matches || !d_results || !d_best || !d_pn || !d_counts || stride == 0) return BEV_ERR_INVALID_ARG;
+        uint64_t largest = 0;
+        BEVCK(submap_top_check(c, n_frames, d_clouds, h_offsets, call, &largest));
+        if (!matches_in_range(h_matches, n_matches, n_frames, n_maps)) return BEV_ERR_INVALID_ARG;
+    }
+    BEVCK(begin_call(c, false));
+    if (n_matches == 0) return BEV_OK;
+    BEVCK(wait_default_stream(c));
+    Options opt;
+    opt.point_normal = opt.union_voxel = opt.top_union = true;
+    const Plan plan = bevsubreg::plan_call(call, opt, group_cap(c));
+    SubmapTop w;
+    BEVCK(submap_top_work(c, plan, true, stride, w));
+    std::vector<IcpProblem> probs; /* two problems per match, the guesses adjacent */
+    probs.reserve(2 * plan.probs.size());
+    for (const bevsubreg::Problem &pp : plan.probs)
+        for (int g = 0; g < 2; ++g) {
+            IcpProblem pb{};
+            pb.src_frame = (uint32_t)h_matches[pp.result].query_idx;
+            pb.tgt_frame = 0xffffffffu; /* (not read: the target is a map) */
+            pb.tgt_slot = pp.map;
+            pb.result = 2 * pp.result + (uint32_t)g;
+            bevx::icp_tool_guess(h_matches[pp.result].angle_guess, g, pb.guess);
+            probs.push_back(pb);
+        }
+    BEVCK(plan_up(c, c->reg.icp_tab, plan, opt, w.s.d, probs.data(), probs.size() * sizeof(IcpProblem)));
+    w.s.p.v.key0 = static_cast<const uint64_t *>(w.s.d.key0);
+    w.t.u0 = static_cast<const uint64_t *>(w.s.d.u0);
+    const float vp[2] = {viewpoint ? viewpoint[0] : 0.0f, viewpoint ? viewpoint[1] : 0.0f};
+    const float *pn = static_cast<const float *>(d_pn);
+    const IcpProblem *d_probs = static_cast<const IcpProblem *>(w.s.d.probs);
+    for (const Group &g : plan.groups) {
+        BEVCK(submap_top_targets(c, plan, g, w, d_clouds, pn_leaf, radius, vp));
+        for (uint32_t p0 = 0; p0 < 2 * g.n_probs; p0 += kIcpProblemsPerLaunch) {
+            const int n = (int)std::min<uint32_t>(kIcpProblemsPerLaunch, 2 * g.n_probs - p0);
+            ProfScope ps(c, K_SUBMAP_COARSE_ICP, n);
+            launch_submap_coarse_icp(pn, stride, d_counts, d_probs + 2 * (size_t)g.prob0 + p0, n, w.s.d.maps, g.map0, w.s.t, prm,
+                                     d_results, c->stream);
+        }
+    }
+    {
+        ProfScope ps(c, K_ICP_BEST, n_matches);
+        launch_icp_best(d_results, n_matches, d_best, c->stream);
     }
     HIPCK(c, hipGetLastError());
     return record_tail(c);

@@ -240,6 +240,13 @@ enum KernelId {
     K_SUBMAP_PN_NORMALS, /* ... the normals of the thinned points over a 3-D window of the union's grid */
     K_SUBMAP_PN_GRID,    /* ... the search grid of the thinned rows */
     K_SUBMAP_PN_OUT,     /* ... the cloud call: the maps' rows and counts into the caller's arrays */
+    K_SUBMAP_TOP_KEYS,     /* the top part over the union of a map's moved full clouds (bev_submap_top.h): the moved records' keys, the cells' counts */
+    K_SUBMAP_TOP_CELLS,    /* ... the cells' ranks and the selection's size */
+    K_SUBMAP_TOP_HIST,     /* ... the radix select: one digit's histogram per cell */
+    K_SUBMAP_TOP_SCAN,     /* ... the radix select: the cells' buckets, prefixes and thresholds */
+    K_SUBMAP_TOP_COMPACT,  /* ... the selected keys (the sort: K_SUBMAP_VOX_TILE, K_SUBMAP_VOX_GLOBAL) */
+    K_SUBMAP_TOP_ROWS,     /* ... the rows of top(g) from the sorted keys */
+    K_SUBMAP_TOP_OVERFLOW, /* ... the voxel grid's overflow branch: top(g) kept for the normals' full scan */
     K_COUNT
 };
 const char *kernel_name(int id);
@@ -545,6 +552,44 @@ void launch_submap_pn_grid(const void *maps, uint32_t map0, int n_maps, const Su
 /* src: the group's row array that holds the targets (moved or thinned); out, counts: the caller's, indexed by map of the plan */
 void launch_submap_pn_out(const void *maps, uint32_t map0, int n_maps, uint32_t parts, const SubvoxHdr *vh, const float *src,
                           float *out, uint64_t stride, uint32_t *counts, hipStream_t st);
+
+/* ---- the top part over the union of a map's moved full clouds (bev_submap_top.h) ----
+ * the maps of ONE launch group of a plan with top_union (and point_normal, union_voxel): a map's rows (SubmapPnVoxWork::moved and
+ * everything behind it) are counted in rows of top(g), its keys in records of the union */
+constexpr uint32_t kTopIndexBits = 25;               /* a record's index in the union: BEV_SUBMAP_TOP_MAX_UNION = 2^24 records */
+constexpr uint32_t kTopKeyBits = 32 + kTopIndexBits; /* rf_z_desc_key << 25 | index; the cell above them */
+constexpr uint32_t kTopDigitBits = 6, kTopDigits = 1u << kTopDigitBits; /* of the radix select: 10 digits, the first of 3 bits */
+constexpr uint32_t kTopHistWords = kRfCells * kTopDigits;               /* 25 KiB of LDS: six workgroups per CU */
+struct SubtopCells {
+    uint32_t cnt[kRfCells];    /* kept records of the cell (zeroed by the caller on the same stream) */
+    uint32_t k[kRfCells];      /* round(0.2f * cnt) where cnt >= 20, else 0 */
+    uint32_t rank[kRfCells];   /* the rank sought among the keys that share the prefix; 0: the cell is finished, or not kept */
+    uint64_t prefix[kRfCells]; /* the digits found so far */
+    uint64_t thr[kRfCells];    /* finished: the cell's keys (57 bits) at or below it are its selection */
+    uint32_t n_sel;            /* sum of k: rows of top(g) */
+    uint32_t cursor;           /* slots handed out (zeroed by the caller) */
+    uint32_t open;             /* cells not finished */
+    uint32_t _pad;
+};
+struct SubmapTopWork {
+    uint64_t *ukeys;    /* [the group's union records] a map's at u0[its index in the plan] */
+    SubtopCells *cells; /* [the group's maps] */
+    uint32_t *hist;     /* [the group's maps][kTopHistWords]  zeroed by the caller on the same stream, zero again after every digit */
+    const uint64_t *u0; /* [the plan's maps]  device table */
+};
+/* maps / entries / slots: the plan's tables (an entry's pad words: its first union index, its records); parts: workgroups
+ * along x for each of the n_maps maps from map0 on */
+void launch_submap_top_keys(const void *maps, uint32_t map0, int n_maps, uint32_t parts, const void *entries, const void *slots,
+                            const bev_point_t *clouds, const SubmapTopWork &t, hipStream_t st);
+void launch_submap_top_cells(int n_maps, const SubmapTopWork &t, SubvoxHdr *vh, hipStream_t st);
+/* one digit of the select at `shift`: its histogram (scan false), then its scan (true) */
+void launch_submap_top_digit(const void *maps, uint32_t map0, int n_maps, uint32_t parts, const void *entries,
+                             const SubmapTopWork &t, uint32_t shift, bool scan, hipStream_t st);
+void launch_submap_top_compact(const void *maps, uint32_t map0, int n_maps, uint32_t parts, const void *entries,
+                               const SubmapTopWork &t, const SubmapVoxWork &v, hipStream_t st);
+void launch_submap_top_rows(const void *maps, uint32_t map0, int n_maps, uint32_t parts, const void *entries, const void *slots,
+                            const bev_point_t *clouds, const SubmapTopWork &t, const SubmapPnVoxWork &p, hipStream_t st);
+void launch_submap_top_overflow(const void *maps, uint32_t map0, int n_maps, const SubmapPnVoxWork &p, hipStream_t st);
 
 /* opt in to > 64 KiB of dynamic LDS for the kernels that need it */
 hipError_t configure_kernels(const Geometry &g);

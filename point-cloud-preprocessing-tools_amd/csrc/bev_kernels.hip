@@ -49,6 +49,7 @@
 #include "bev_submap_vox.h"
 #include "bev_submap_coarse.h"
 #include "bev_submap_pn_vox.h"
+#include "bev_submap_top.h"
 
 using namespace bevx;
 
@@ -65,6 +66,8 @@ static const char *const kNames[K_COUNT] = {
     "k_submap_vox_move", "k_submap_vox_keys", "k_submap_vox_tile", "k_submap_vox_global", "k_submap_vox_finish", "k_submap_vox_out",
     "k_submap_pn_target", "k_submap_coarse_icp",
     "k_submap_pn_move", "k_submap_pn_keys", "k_submap_pn_finish", "k_submap_pn_normals", "k_submap_pn_grid", "k_submap_pn_out",
+    "k_submap_top_keys", "k_submap_top_cells", "k_submap_top_hist", "k_submap_top_scan", "k_submap_top_compact", "k_submap_top_rows",
+    "k_submap_top_overflow",
 };
 const char *kernel_name(int id) { return (id >= 0 && id < K_COUNT) ? kNames[id] : "?"; }
 

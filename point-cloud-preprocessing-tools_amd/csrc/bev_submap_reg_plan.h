@@ -31,6 +31,14 @@
  * point_normal with union_voxel: the PointNormal maps are thinned over their union and their normals recomputed
  * (bev_submap_pn_vox.h): a map owns its sort keys as under union_voxel, and its bytes are map_coarse_union_bytes.  With all_maps
  * as well: bev_submap_pn_cloud_device_resident.  Every other combination plans exactly as before.
+ *
+ * top_union, with point_normal and union_voxel: the call is bev_submap_top_part_coarse_registration_device_resident's
+ * or, with all_maps, bev_submap_top_part_cloud_device_resident's: the frames are FULL clouds (frames.off, frames.n as in a fine
+ * call), and a map is the top part over the union of its moved full clouds (bev_submap_top.h), thinned as above.  A map then has
+ * two sizes: map_union_cap, the records of its union (the sum of its entries' record counts), whose keys lie at map_u0 of the
+ * group's union keys; and map_cap, top_max_out of that: the rows its top part can have, which is what pt0, the sort keys and
+ * everything of §6q are counted in.  An entry's pad words carry its first index in the union and its record count.  A map's
+ * bytes are map_top_union_bytes.  Without top_union nothing of this is computed and every plan is what it was.
  */
 #ifndef BEV_SUBMAP_REG_PLAN_H
 #define BEV_SUBMAP_REG_PLAN_H
@@ -53,6 +61,12 @@ constexpr uint32_t kCoarseRowBytes = 48 + 16;  /* ... a moved PointNormal row an
  * the moved row, a voxel start, a voxel index, a thinned position */
 constexpr uint32_t kCoarseUnionRowBytes = kCoarseRowBytes + 48 + 4 + 4 + 16;
 
+/* of a map's top part over its union (bev_internal.h has the device's structures): the cells' counts, ranks,
+ * prefixes and thresholds of the radix select and its three counters; its histograms, 64 digits per cell */
+constexpr uint32_t kTopCellBytes = 100 * (3 * 4 + 2 * 8) + 16;
+constexpr uint32_t kTopHistBytes = 100 * 64 * 4;
+constexpr uint64_t kTopMaxUnion = (uint64_t)1 << 24; /* BEV_SUBMAP_TOP_MAX_UNION: the key has 25 bits for a union index */
+
 struct Slot { /* FineSlot's layout (bev_internal.h): k_fine_voxel reads the slots */
     uint64_t off;
     uint32_t n, _pad;
@@ -60,7 +74,7 @@ struct Slot { /* FineSlot's layout (bev_internal.h): k_fine_voxel reads the slot
 struct alignas(64) Entry { /* one aligned 64-byte line per entry, read at a workgroup-uniform address */
     float m[12];   /* row-major 3 x 4 */
     uint32_t slot; /* whose voxel cloud it moves */
-    uint32_t pad[3];
+    uint32_t pad[3]; /* 0; top_union: its first index in the map's union, its record count, 0 */
 };
 struct Map {
     uint64_t pt0;         /* its first point in the group's point arrays */
@@ -81,6 +95,8 @@ struct Group {
     uint64_t bytes = 0;              /* sum of map_bytes over its maps */
     uint64_t keys = 0;               /* union_voxel: sort keys of its maps together (bevsubvox::key_slots of each) */
     uint64_t max_slots = 0;          /* union_voxel: the largest key array among its maps: it sizes the sort's launches */
+    uint64_t union_pts = 0;          /* top_union: records of its maps' unions together */
+    uint64_t max_union = 0;          /* top_union: the largest union among its maps: it sizes the select's launches */
 };
 struct Plan {
     std::vector<Slot> slots;
@@ -96,6 +112,9 @@ struct Plan {
     uint64_t max_group_pts = 0;
     uint32_t max_group_maps = 0;
     uint64_t max_group_keys = 0;     /* union_voxel */
+    std::vector<uint64_t> map_union_cap; /* top_union: records of a used map's union (map_cap: rows of its top part) */
+    std::vector<uint64_t> map_u0;        /* top_union: a used map's first key in its group's union keys */
+    uint64_t max_group_union = 0;        /* top_union */
 };
 
 /* what the union grid adds to a map that can hold cap points: the thinned points (16 bytes each), the padded sort keys
@@ -119,6 +138,18 @@ inline uint64_t map_coarse_bytes(uint64_t cap) { return cap * kCoarseRowBytes + 
 inline uint64_t map_coarse_union_bytes(uint64_t cap)
 {
     return cap * kCoarseUnionRowBytes + bevsubvox::key_slots(cap) * 8 + 4 + (uint64_t)(kCoarseGridCells + 1) * 4 + 32 + 32;
+}
+
+/* rows the top part of n records can have: bev_regfront_max_out (sum over 100 cells of round(0.2f * n_c) <= n / 5 + 50) */
+inline uint64_t top_max_out(uint64_t n) { return n / 5 + 51; }
+
+/* device bytes of a map whose union holds c records and whose target is the thinned top part over it
+ * (bev_submap_top_part_coarse_registration_device_resident, bev_submap_top_part_cloud_device_resident): a key per record of the
+ * union (the moved records are not kept: a row is moved again from its entry and record), the cells' table and histograms, and
+ * what a thinned PointNormal map of top_max_out(c) rows takes, its padded sort keys holding the padded selection first */
+inline uint64_t map_top_union_bytes(uint64_t c)
+{
+    return c * 8 + kTopCellBytes + kTopHistBytes + map_coarse_union_bytes(top_max_out(c));
 }
 
 /* points the entries of map g can hold together: the sum of their frames' record counts */
@@ -147,7 +178,7 @@ struct Call {
     const bev_match_t *matches = nullptr;
 };
 struct Options { /* see the head of the file */
-    bool union_voxel = false, all_maps = false, point_normal = false;
+    bool union_voxel = false, all_maps = false, point_normal = false, top_union = false;
 };
 
 /* cap_bytes: the group cap */
@@ -186,16 +217,24 @@ inline Plan plan_call(const Call &call, const Options &opt, uint64_t cap_bytes)
         if (used[g] < 0) continue;
         used[g] = (int32_t)p.maps.size();
         Map mp{0u, (uint32_t)p.entries.size(), (uint32_t)(map_offs[g + 1] - map_offs[g])};
+        uint64_t at = 0;
         for (uint64_t e = map_offs[g]; e < map_offs[g + 1]; ++e) {
             Entry en;
             memcpy(en.m, call.entry_pose + 12 * (size_t)e, sizeof en.m);
             en.slot = (uint32_t)slot_of[entry_frame[e]];
             en.pad[0] = en.pad[1] = en.pad[2] = 0u;
+            if (opt.top_union) {
+                en.pad[0] = (uint32_t)at;
+                en.pad[1] = (uint32_t)frame_n[entry_frame[e]];
+                at += frame_n[entry_frame[e]];
+            }
             p.entries.push_back(en);
         }
         p.maps.push_back(mp);
         p.map_id.push_back(g);
-        p.map_cap.push_back(map_capacity(frame_n, map_offs, entry_frame, g));
+        const uint64_t cap = map_capacity(frame_n, map_offs, entry_frame, g);
+        if (opt.top_union) p.map_union_cap.push_back(cap);
+        p.map_cap.push_back(opt.top_union ? top_max_out(cap) : cap);
     }
     /* the problems: by map, the call's order among equal maps */
     std::vector<uint64_t> keys((size_t)std::max(n_matches, 0));
@@ -207,13 +246,15 @@ inline Plan plan_call(const Call &call, const Options &opt, uint64_t cap_bytes)
     }
     /* the groups */
     p.map_key0.assign(p.maps.size(), 0);
+    if (opt.top_union) p.map_u0.assign(p.maps.size(), 0);
     size_t pr = 0;
     for (uint32_t u = 0; u < (uint32_t)p.maps.size();) {
         Group g;
         g.map0 = u;
         g.prob0 = (uint32_t)pr;
         while (u < (uint32_t)p.maps.size()) {
-            const uint64_t b = !opt.point_normal ? map_bytes(p.map_cap[u], opt.union_voxel)
+            const uint64_t b = opt.top_union      ? map_top_union_bytes(p.map_union_cap[u])
+                               : !opt.point_normal ? map_bytes(p.map_cap[u], opt.union_voxel)
                                : opt.union_voxel ? map_coarse_union_bytes(p.map_cap[u])
                                                  : map_coarse_bytes(p.map_cap[u]);
             if (g.n_maps > 0 && g.bytes + b > cap_bytes) break;
@@ -223,6 +264,11 @@ inline Plan plan_call(const Call &call, const Options &opt, uint64_t cap_bytes)
                 p.map_key0[u] = g.keys;
                 g.keys += slots;
                 g.max_slots = std::max(g.max_slots, slots);
+            }
+            if (opt.top_union) {
+                p.map_u0[u] = g.union_pts;
+                g.union_pts += p.map_union_cap[u];
+                g.max_union = std::max(g.max_union, p.map_union_cap[u]);
             }
             g.pts += p.map_cap[u];
             g.bytes += b;
@@ -234,6 +280,7 @@ inline Plan plan_call(const Call &call, const Options &opt, uint64_t cap_bytes)
         p.max_group_pts = std::max(p.max_group_pts, g.pts);
         p.max_group_maps = std::max(p.max_group_maps, g.n_maps);
         p.max_group_keys = std::max(p.max_group_keys, g.keys);
+        p.max_group_union = std::max(p.max_group_union, g.union_pts);
         p.groups.push_back(g);
     }
     return p;

@@ -46,7 +46,7 @@ void DeviceBuffer::download(void *dst, size_t bytes) const { hip_check(hipMemcpy
 
 ChunkResult runChunk(bev_ctx_t *ctx, const std::vector<Cloud> &clouds, const std::vector<uint64_t> &offs, const Chunk &chunk,
                      const std::vector<float> *entry_pose, float map_leaf, bool top_part, const bev_icp_params_t &fine_prm,
-                     float pn_leaf)
+                     float pn_leaf, bool top_union)
 {
     using clk = std::chrono::steady_clock;
     const int F = (int)clouds.size(), n = (int)chunk.matches.size();
@@ -72,7 +72,11 @@ ChunkResult runChunk(bev_ctx_t *ctx, const std::vector<Cloud> &clouds, const std
         const float vp[3] = {0.0f, 0.0f, 0.0f};
         BEV_CALL(bev_registration_front_device_resident, F, pts.as<bev_point_t>(), offs.data(), 0.2f, 2.0f, vp, pn.as(), stride,
                  cnt.as<uint32_t>());
-        if (entry_pose && pn_leaf > 0.0f) /* the maps thinned over their union, under the front end's settings */
+        if (entry_pose && pn_leaf > 0.0f && top_union) /* the top part over the union of the moved full clouds, thinned */
+            BEV_CALL(bev_submap_top_part_coarse_registration_device_resident, F, pts.as<bev_point_t>(), offs.data(), pn.as(), stride,
+                     cnt.as<uint32_t>(), pn_leaf, 2.0f, vp, n, map_offs, entry_frame, entry_pose->data(), n, cm, nullptr,
+                     coarse.as<bev_icp_result_t>(), best.as<int32_t>());
+        else if (entry_pose && pn_leaf > 0.0f) /* the maps thinned over their union, under the front end's settings */
             BEV_CALL(bev_submap_coarse_voxel_registration_device_resident, F, pn.as(), stride, cnt.as<uint32_t>(), pn_leaf, 2.0f, vp,
                      n, map_offs, entry_frame, entry_pose->data(), n, cm, nullptr, coarse.as<bev_icp_result_t>(), best.as<int32_t>());
         else if (entry_pose)
@@ -129,7 +133,7 @@ void Tally::print(std::ostream &out, bool coarse_line, bool fine_is_both) const
 }
 
 int registerChunk(const std::vector<std::string> &paths, const Chunk &chunk, const std::vector<float> *entry_pose, float map_leaf,
-                  bool top_part, const bev_icp_params_t &fine_prm, Tally &tally, float pn_leaf)
+                  bool top_part, const bev_icp_params_t &fine_prm, Tally &tally, float pn_leaf, bool top_union)
 {
     std::vector<Cloud> clouds(paths.size());
     std::vector<uint64_t> offs(paths.size() + 1, 0);
@@ -143,7 +147,7 @@ int registerChunk(const std::vector<std::string> &paths, const Chunk &chunk, con
     bev_ctx_t *ctx = bevhost_context();
     if (!ctx) return 2;
     try {
-        tally.add(chunk, runChunk(ctx, clouds, offs, chunk, entry_pose, map_leaf, top_part, fine_prm, pn_leaf));
+        tally.add(chunk, runChunk(ctx, clouds, offs, chunk, entry_pose, map_leaf, top_part, fine_prm, pn_leaf, top_union));
     } catch (const std::exception &e) {
         std::cerr << e.what() << "\n";
         return 2;

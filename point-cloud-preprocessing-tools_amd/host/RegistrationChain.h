@@ -55,10 +55,12 @@ struct ChunkResult {
  * *entry_pose per entry), thinned by map_leaf if that is > 0.  top_part: front end (leaf 0.2, radius 2, viewpoint 0) and coarse
  * ICP, then fine ICP from the better coarse result; else fine ICP from the yaw guess.  pn_leaf > 0 (top_part against maps): the
  * coarse stage's maps are thinned over their union and their normals recomputed there, with the front end's radius and viewpoint
- * (bev_submap_coarse_voxel_registration_device_resident) */
+ * (bev_submap_coarse_voxel_registration_device_resident); with top_union as well, the coarse stage's maps are the
+ * top part over the union of the entries' moved FULL clouds, thinned the same way, the front end's rows being the queries
+ * (bev_submap_top_part_coarse_registration_device_resident) */
 ChunkResult runChunk(bev_ctx_t *ctx, const std::vector<Cloud> &clouds, const std::vector<uint64_t> &offs, const Chunk &chunk,
                      const std::vector<float> *entry_pose, float map_leaf, bool top_part, const bev_icp_params_t &fine_prm,
-                     float pn_leaf = 0.0f);
+                     float pn_leaf = 0.0f, bool top_union = false);
 
 /* what a successful match's "diff_xy diff_yaw" line compares its final transform with */
 enum class ReportAgainst { Nothing, ChosenCoarse, YawGuess };
@@ -80,7 +82,7 @@ private:
 /* The files paths[f] as the chunk's frames, the context (after the files: an unreadable one ends the tool first), runChunk, Tally::add.  0, or the tool's exit
  * status with the reason on stderr: 1 an unreadable cloud, 2 no context or a failed call */
 int registerChunk(const std::vector<std::string> &paths, const Chunk &chunk, const std::vector<float> *entry_pose, float map_leaf,
-                  bool top_part, const bev_icp_params_t &fine_prm, Tally &tally, float pn_leaf = 0.0f);
+                  bool top_part, const bev_icp_params_t &fine_prm, Tally &tally, float pn_leaf = 0.0f, bool top_union = false);
 
 } // namespace regchain
 

@@ -34,6 +34,11 @@
  * thins every coarse map by a voxel grid of that leaf over the union of its moved clouds and recomputes its 2-D normals there
  * (bev_submap_coarse_voxel_registration_device_resident, radius 2, viewpoint 0: the front end's settings); unset, empty or 0: the
  * output as ever; anything else: exit 1 with "BEV_SUBMAP_PN_LEAF '<text>': expected a finite number >= 0" before any GPU work.
+ * BEV_SUBMAP_TOP_UNION in the environment (this tool alone): 1 sends every chunk's coarse stage against the top
+ * part over the union of each window's moved FULL clouds, thinned by BEV_SUBMAP_PN_LEAF (which must then be > 0) with radius 2
+ * and viewpoint 0 (bev_submap_top_part_coarse_registration_device_resident; the front end's rows are the queries); unset, empty
+ * or 0: the output as ever; 1 without a leaf: exit 1 with "BEV_SUBMAP_TOP_UNION=1 needs BEV_SUBMAP_PN_LEAF > 0"; anything else:
+ * exit 1 with "BEV_SUBMAP_TOP_UNION '<text>': expected 0 or 1"; both before any GPU work.
  *
  * The chunks, the chain and the bookkeeping are the four registration tools' own (RegistrationChunks.h, RegistrationChain.h;
  * DESIGN.md §6p), the entries' matrices every submap tool's (submapwin::appendEntryPose): this file is the command line, which
@@ -43,6 +48,7 @@
 #include <cstdlib>
 #include <fstream>
 #include <iostream>
+#include <string>
 #include <vector>
 
 #include "Registration.h"
@@ -84,6 +90,19 @@ int main(int argc, char **argv)
         if (*env && !parse_map_leaf(env, &pn_leaf)) {
             std::cerr << "BEV_SUBMAP_PN_LEAF '" << env << "': expected a finite number >= 0\n";
             return 1;
+        }
+    bool top_union = false;
+    if (const char *env = kTopPart ? std::getenv("BEV_SUBMAP_TOP_UNION") : nullptr)
+        if (*env && std::string(env) != "0") {
+            if (std::string(env) != "1") {
+                std::cerr << "BEV_SUBMAP_TOP_UNION '" << env << "': expected 0 or 1\n";
+                return 1;
+            }
+            if (!(pn_leaf > 0.0f)) {
+                std::cerr << "BEV_SUBMAP_TOP_UNION=1 needs BEV_SUBMAP_PN_LEAF > 0\n";
+                return 1;
+            }
+            top_union = true;
         }
     if (argc > 5 && !parse_map_leaf(argv[5], &map_leaf)) {
         std::cerr << "map_leaf '" << argv[5] << "': expected a finite number >= 0\n";
@@ -141,7 +160,8 @@ int main(int argc, char **argv)
         for (size_t k = 0; k < chunk.matches.size(); ++k)
             for (uint64_t e = chunk.map_offs[k]; e < chunk.map_offs[k + 1]; ++e)
                 submapwin::appendEntryPose(pose, matches[m0 + k].match_idx, chunk.files[chunk.entry_frame[e]], entry_pose);
-        if (const int rc = regchain::registerChunk(paths, chunk, &entry_pose, map_leaf, kTopPart, prm, tally, pn_leaf)) return rc;
+        if (const int rc = regchain::registerChunk(paths, chunk, &entry_pose, map_leaf, kTopPart, prm, tally, pn_leaf, top_union))
+            return rc;
         m0 = chunk.m1;
     }
     /* batch_submap_registration's fine line is the whole visit of the device, uploads included */
