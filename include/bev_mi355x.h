@@ -814,6 +814,26 @@ int bev_submap_top_part_coarse_registration_device_resident(bev_ctx_t *ctx, int 
                                                             const bev_match_t *h_matches, const bev_icp_params_t *params,
                                                             bev_icp_result_t *d_results, int32_t *d_best);
 
+/* ---- scan-to-map search grids sized to the map ------------------------------------------------------------
+ * The scan-to-map calls search a map's target on a uniform 2-D grid of at most dim x dim cells,
+ *   dim = min(D, max(1, ceil(sqrtf(n)))),  n the target's points,
+ * with D = 128 in the fine calls and D = 64 in the coarse ones: the cell counts of that build fit one workgroup's LDS.  This
+ * call sets D per stage for the calls made after it (sticky per context):
+ *   0          (default) the stage runs as it always has: the same kernels, launches and workspace;
+ *   1 ... BEV_SUBMAP_SEARCH_GRID_MAX
+ *              the stage's map targets get grids with that cap, built by several workgroups per map with the cell counts in
+ *              global memory, and the ICP reads a map's cell offsets from there.  Values below 128 / 64 are allowed.
+ * fine_dim governs bev_submap_registration_* and bev_submap_voxel_registration_* (both leaf branches, the batch forms too);
+ * coarse_dim governs bev_submap_coarse_registration_device_resident, bev_submap_coarse_voxel_registration_device_resident and
+ * bev_submap_top_part_coarse_registration_device_resident.  The cloud-writing calls build no grid; the pair calls keep theirs.
+ * Results never depend on it: the search is an exact 1-NN with the lowest target index on equal distance whatever the cell
+ * size, so every result is bit for bit what D = 0 gives.  Only time and workspace do: with D > 0 a map of capacity c takes
+ * 8 (dim(c)^2 + 1) bytes of offsets and counters plus 5 KiB in place of the fixed grid's offsets.
+ * No synchronisation is needed around it: a call made before it and not yet finished keeps its grids.
+ * Status: BEV_ERR_INVALID_ARG for a NULL context or a value outside 0 ... BEV_SUBMAP_SEARCH_GRID_MAX; nothing changes then. */
+#define BEV_SUBMAP_SEARCH_GRID_MAX 1024
+int bev_set_submap_search_grid(bev_ctx_t *ctx, int fine_dim, int coarse_dim);
+
 /* ---- layout hint -------------------------------------------------------
  * What the caller knows about how its clouds are laid out, so that the library need not look (k_probe reads every 63rd
  * record of a frame to find out: 0.36 MB and 0.07 us of an HDL_64E frame).  Sticky per context; applies to frames of
@@ -886,6 +906,13 @@ int bev_debug_get_code_overflow(bev_ctx_t *ctx, int first_frame, int n_frames, u
  * device for n (dx,dy,dz) triples given as HOST arrays; out[i] = 1 if GROUND. */
 int bev_debug_angle_predicate(bev_ctx_t *ctx, const float *dx, const float *dy,
                               const float *dz, uint8_t *out, size_t n);
+
+/* Test hook: the search grids of the LAST launch group of the last fine (coarse == 0) or coarse (coarse == 1) scan-to-map call
+ * with matches, whichever path built them.  Synchronises.  out[4 * i .. 4 * i + 3] = { nx, ny, searchable points, largest count
+ * of one cell } of map first_map + i of that group, the maps in the plan's order (ascending map index among the maps that a
+ * match names).  BEV_ERR_INVALID_ARG for a NULL context or out, a range outside that group, before any such call, and once
+ * another call has moved the stage's workspace. */
+int bev_debug_get_submap_grid(bev_ctx_t *ctx, int coarse, int first_map, int n_maps, uint32_t *out);
 
 int bev_abi_version(void);
 

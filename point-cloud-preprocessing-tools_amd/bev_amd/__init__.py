@@ -74,6 +74,7 @@ FLOAT_BEV_MAX_POSES = 64  # BEV_FLOAT_BEV_MAX_POSES: poses per frame of float_be
 POSED_BEV_MAX_POSES = 64  # BEV_POSED_BEV_MAX_POSES: poses per frame of posed_bev_device / posed_bev_batch
 SUBMAP_MAX_ENTRIES = 1 << 20  # BEV_SUBMAP_MAX_ENTRIES: (frame, pose) entries of one submap_bev_device / submap_bev_batch call
 SUBMAP_COARSE_MAX_TARGET = 1 << 22  # BEV_SUBMAP_COARSE_MAX_TARGET: rows of one map, entries times stride (submap_coarse_registration_device)
+SUBMAP_SEARCH_GRID_MAX = 1024  # BEV_SUBMAP_SEARCH_GRID_MAX: the largest cap of cells per axis of set_submap_search_grid
 SUBMAP_REG_MAX_TARGET = 1 << 22  # BEV_SUBMAP_REG_MAX_TARGET: records of one map's entries' frames together (submap_registration_*)
 
 # every symbol include/bev_mi355x.h declares
@@ -102,6 +103,7 @@ ABI_SYMBOLS = [
     "bev_submap_coarse_voxel_registration_device_resident", "bev_submap_pn_cloud_device_resident",
     "bev_submap_top_part_cloud_device_resident", "bev_submap_top_part_coarse_registration_device_resident",
     "bev_submap_top_part_max_out",
+    "bev_set_submap_search_grid", "bev_debug_get_submap_grid",
 ]
 
 # registration front end (include/bev_mi355x.h): pcl::PointXYZ, pcl::Normal, pcl::PointNormal as float rows
@@ -267,6 +269,9 @@ def load_lib() -> C.CDLL:
             C.POINTER(IcpParams), vp, vp]
         lib.bev_submap_top_part_max_out.argtypes = [sz]
         lib.bev_submap_top_part_max_out.restype = sz
+    if hasattr(lib, "bev_set_submap_search_grid"):
+        lib.bev_set_submap_search_grid.argtypes = [vp, i32, i32]
+        lib.bev_debug_get_submap_grid.argtypes = [vp, i32, i32, i32, vp]
     _lib = lib
     return lib
 
@@ -895,6 +900,20 @@ class BevContext:
     def set_layout_hint(self, layout: int):
         """LAYOUT_UNKNOWN (the library looks), LAYOUT_STRUCTURED, LAYOUT_FIRING_ORDER: include/bev_mi355x.h"""
         self._check(self.lib.bev_set_layout_hint(self._h, layout), "bev_set_layout_hint")
+
+    def set_submap_search_grid(self, fine: int, coarse: int):
+        """The cap of cells per axis of the maps' search grids in the fine and the coarse scan-to-map calls made from now on:
+        0 the grids of always (128 and 64 at most), 1 .. SUBMAP_SEARCH_GRID_MAX grids sized to the map (bev_set_submap_search_grid;
+        DESIGN.md §6s).  Results do not depend on it."""
+        self._check(self.lib.bev_set_submap_search_grid(self._h, int(fine), int(coarse)), "bev_set_submap_search_grid")
+
+    def debug_submap_grid(self, coarse: int, first: int, n: int) -> np.ndarray:
+        """Test hook (synchronises): (n, 4) uint32 rows {nx, ny, searchable points, largest count of one cell} of maps first ..
+        first + n - 1 of the last launch group of the last fine (coarse = 0) or coarse (1) scan-to-map call."""
+        out = np.zeros((n, 4), dtype=np.uint32)
+        self._check(self.lib.bev_debug_get_submap_grid(self._h, int(coarse), int(first), int(n), _ptr(out)),
+                    "bev_debug_get_submap_grid")
+        return out
 
     # ---- measurement / test hooks ------------------------------------------
     def set_lanes(self, n: int) -> int:

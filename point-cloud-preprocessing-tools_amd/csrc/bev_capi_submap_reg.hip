@@ -39,24 +39,74 @@ int submap_reg_check(const Call &call)
 
 /* the plan's tables in one block of tab, the device's on return: the slots (fine, top_union), the maps, the entries (64-byte
  * aligned), the caller's problems if it has any, the maps' first keys (union_voxel; else nullptr), their first union keys
- * (top_union; else nullptr) */
+ * (top_union; else nullptr), their first cells (grid_cap > 0; else nullptr) */
 struct PlanDev {
-    void *slots, *maps, *entries, *probs, *key0, *u0;
+    void *slots, *maps, *entries, *probs, *key0, *u0, *cell0;
 };
 int plan_up(bev_ctx *c, UploadTable &tab, const Plan &plan, const Options &opt, PlanDev &d, const void *probs = nullptr,
             size_t prob_bytes = 0)
 {
     static_assert(sizeof(bevsubreg::Slot) == sizeof(FineSlot), "the plan's slots are k_fine_voxel's");
     const void *const src[] = {plan.slots.data(), plan.maps.data(), plan.entries.data(), probs, plan.map_key0.data(),
-                               plan.map_u0.data()};
+                               plan.map_u0.data(), plan.map_cell0.data()};
     const size_t sz[] = {opt.point_normal && !opt.top_union ? 0 : plan.slots.size() * sizeof(FineSlot),
                          plan.maps.size() * sizeof(bevsubreg::Map), plan.entries.size() * sizeof(bevsubreg::Entry), prob_bytes,
-                         opt.union_voxel ? plan.maps.size() * 8 : 0, opt.top_union ? plan.maps.size() * 8 : 0};
-    void **const dst[] = {&d.slots, &d.maps, &d.entries, &d.probs, &d.key0, &d.u0};
+                         opt.union_voxel ? plan.maps.size() * 8 : 0, opt.top_union ? plan.maps.size() * 8 : 0,
+                         opt.grid_cap ? plan.maps.size() * 8 : 0};
+    void **const dst[] = {&d.slots, &d.maps, &d.entries, &d.probs, &d.key0, &d.u0, &d.cell0};
     BEVCK(table_up(c, tab, sz, src, dst));
     if (!sz[4]) d.key0 = nullptr;
     if (!sz[5]) d.u0 = nullptr;
+    if (!sz[6]) d.cell0 = nullptr;
     return BEV_OK;
+}
+
+/* ---- search grids sized to the maps (bev_set_submap_search_grid; bev_submap_grid.h) ---- */
+
+/* the pieces a wide grid adds to a stage's workspace, behind everything else (all 0 without one, so that the layout stands):
+ * the counters, the parts' bounds, the tiles' sums */
+struct GridPieces {
+    size_t cnt, bounds, sums;
+};
+GridPieces grid_pieces(const Plan &plan, bool wide)
+{
+    const size_t C = std::max<size_t>((size_t)plan.max_group_cells, 1), M = std::max<size_t>(plan.max_group_maps, 1);
+    return wide ? GridPieces{C * 4, M * kSubgridParts * sizeof(float4), M * kSubgridScanParts * 4} : GridPieces{0, 0, 0};
+}
+
+/* the search grids of a group's maps by several workgroups per map: the maps' point counts are vh's n_out, their points pts
+ * (float4) or, pts == nullptr, the PointNormal rows */
+int submap_grid_build(bev_ctx *c, const Plan &plan, const Group &g, int cap, const void *d_maps, const SubvoxHdr *vh,
+                      const float4 *pts, const float *rows, const SubmapGridWork &w)
+{
+    uint64_t largest = 0;
+    for (uint32_t u = g.map0; u < g.map0 + g.n_maps; ++u) largest = std::max(largest, plan.map_cap[u]);
+    /* workgroups of 2048 points of the largest map, of 4096 cells of the largest grid */
+    const uint32_t parts = (uint32_t)std::min<uint64_t>((largest + 8 * kIcpThreads - 1) / (8 * kIcpThreads), kSubgridParts);
+    const uint32_t tiles = (uint32_t)((g.max_cells + bevsubreg::kGridScanTile - 1) / bevsubreg::kGridScanTile);
+    HIPCK(c, hipMemsetAsync(w.cnt, 0, (size_t)g.cells * 4, c->stream));
+    for (int step = 0; step < 6; ++step) {
+        ProfScope ps(c, K_SUBMAP_GRID_BOUNDS + step, (int)g.n_maps);
+        launch_submap_grid(step, d_maps, g.map0, (int)g.n_maps, parts, tiles, cap, vh, pts, rows, w, c->stream);
+    }
+    return BEV_OK;
+}
+
+/* what bev_debug_get_submap_grid reads of a call: the grids of its last group */
+void submap_grid_record(bev_ctx *c, int coarse, const Plan &plan, int cap, uint32_t fixed_cells, const void *buf,
+                        const IcpGridHdr *hdr, const uint32_t *cell_off)
+{
+    SubmapGridRecord &r = c->submap_grid_rec[coarse];
+    r = SubmapGridRecord{};
+    if (plan.groups.empty()) return;
+    const Group &g = plan.groups.back();
+    r.buf = buf;
+    r.hdr = hdr;
+    r.cell_off = cell_off;
+    for (uint32_t i = 0; i < g.n_maps; ++i) {
+        r.off0.push_back(cap ? plan.map_cell0[g.map0 + i] : (uint64_t)i * (fixed_cells + 1));
+        r.cells.push_back(cap ? bevsubreg::grid_cells(plan.map_cap[g.map0 + i], cap) : fixed_cells);
+    }
 }
 
 /* ---- the fine path: registration (§6k, §6l) and the cloud call (§6l) ---- */
@@ -71,24 +121,32 @@ struct SubmapFine {
     SubmapVoxWork v{};
     uint32_t *ent_start = nullptr;
     PlanDev d{};
+    SubmapGridWork gw{}; /* grid_cap > 0: the wide grids (gw.off is t.cell_off, gw.hdr t.hdr, gw.sorted t.sorted) */
 };
 int submap_fine_work(bev_ctx *c, const Plan &plan, const Options &opt, SubmapFine &s)
 {
-    const bool icp = !opt.all_maps, vox = opt.union_voxel, staged = vox || !icp;
+    /* wide: the concatenation is k_submap_vox_move's (v.moved, v.vh) where the maps are not thinned, and t.pts points at it */
+    const bool icp = !opt.all_maps, vox = opt.union_voxel, wide = opt.grid_cap > 0 && icp, staged = vox || !icp || wide;
+    const GridPieces gp = grid_pieces(plan, wide);
     const size_t U = plan.slots.size(), P = plan.probs.size(), E = plan.entries.size(), Pn = plan.Pn, Kn = pow2_at_least(Pn);
     const size_t G = std::min(U, (size_t)kFineVoxelGroup), L = std::min(P, (size_t)kFineProblemsPerLaunch);
     const size_t T = std::max<size_t>((size_t)plan.max_group_pts, 1), M = std::max<size_t>(plan.max_group_maps, 1);
     const size_t sz[] = {U * Pn * sizeof(bev_point_t), U * 4, G * Kn * 8, G * (Pn + 1) * 4, L * Pn * 16, L * Pn * 4,
-                         std::max<size_t>(E, 1) * 4, icp || vox ? T * 16 : 0, icp ? T * 16 : 0, icp ? M * sizeof(IcpGridHdr) : 0,
-                         icp ? M * 4 * (size_t)(kFineCells + 1) : 0, staged ? T * 16 : 0,
-                         vox ? std::max<size_t>((size_t)plan.max_group_keys, 1) * 8 : 0, vox ? (T + M) * 4 : 0,
-                         staged ? M * sizeof(SubvoxHdr) : 0};
+                         std::max<size_t>(E, 1) * 4, (icp && !wide) || vox ? T * 16 : 0, icp ? T * 16 : 0,
+                         icp ? M * sizeof(IcpGridHdr) : 0, !icp ? 0 : wide ? gp.cnt : M * 4 * (size_t)(kFineCells + 1),
+                         staged ? T * 16 : 0, vox ? std::max<size_t>((size_t)plan.max_group_keys, 1) * 8 : 0, vox ? (T + M) * 4 : 0,
+                         staged ? M * sizeof(SubvoxHdr) : 0, gp.cnt, gp.bounds, gp.sums};
     void **const dst[] = {(void **)&s.w.vox, (void **)&s.w.vox_n, (void **)&s.w.keys, (void **)&s.w.vstart, (void **)&s.w.cur,
                           (void **)&s.w.corr, (void **)&s.ent_start, (void **)&s.t.pts, (void **)&s.t.sorted, (void **)&s.t.hdr,
-                          (void **)&s.t.cell_off, (void **)&s.v.moved, (void **)&s.v.keys, (void **)&s.v.vstart, (void **)&s.v.vh};
+                          (void **)&s.t.cell_off, (void **)&s.v.moved, (void **)&s.v.keys, (void **)&s.v.vstart, (void **)&s.v.vh,
+                          (void **)&s.gw.cnt, (void **)&s.gw.part_bounds, (void **)&s.gw.part_sum};
     BEVCK(c->reg.fine_buf.grow(c, carve(nullptr, sz, dst)));
     carve(c->reg.fine_buf.p, sz, dst);
     if (!icp) s.t.sorted = nullptr, s.t.hdr = nullptr, s.t.cell_off = nullptr; /* k_submap_vox_finish builds no grid at nullptr */
+    if (wide && !vox) s.t.pts = s.v.moved;
+    s.gw.hdr = s.t.hdr;
+    s.gw.off = s.t.cell_off;
+    s.gw.sorted = s.t.sorted;
     s.w.Pn = Pn;
     s.w.Kn = Kn;
     return BEV_OK;
@@ -101,25 +159,27 @@ int submap_fine_begin(bev_ctx *c, const Plan &plan, const Options &opt, const be
     BEVCK(submap_fine_work(c, plan, opt, s));
     BEVCK(plan_up(c, c->reg.fine_tab, plan, opt, s.d, probs.data(), probs.size() * sizeof(FineProblem)));
     s.v.key0 = static_cast<const uint64_t *>(s.d.key0);
+    s.gw.cell0 = static_cast<const uint64_t *>(s.d.cell0);
     return fine_voxel(c, d_clouds, static_cast<const FineSlot *>(s.d.slots), (int)plan.slots.size(), s.w, leaf);
 }
 
 /* a group's targets in s.t.pts (the plain cloud call: in s.v.moved): the entries' voxel clouds moved and concatenated, with their
  * search grids where the call has matches; map_leaf > 0: thinned by the voxel grid over the union */
-void submap_fine_targets(bev_ctx *c, const Group &g, const Options &opt, const SubmapFine &s, float map_leaf)
+int submap_fine_targets(bev_ctx *c, const Plan &plan, const Group &g, const Options &opt, const SubmapFine &s, float map_leaf)
 {
     const int gm = (int)g.n_maps;
     const PlanDev &d = s.d;
-    if (!opt.union_voxel && !opt.all_maps) {
+    const bool wide = opt.grid_cap > 0 && !opt.all_maps;
+    if (!opt.union_voxel && !opt.all_maps && !wide) {
         ProfScope ps(c, K_SUBMAP_TARGET, gm);
         launch_submap_target(d.maps, g.map0, gm, d.entries, s.w, s.ent_start, s.t, c->stream);
-        return;
+        return BEV_OK;
     }
     {
         ProfScope ps(c, K_SUBMAP_VOX_MOVE, gm);
         launch_submap_vox_move(d.maps, g.map0, gm, d.entries, s.w, s.ent_start, s.v, c->stream);
     }
-    if (!opt.union_voxel) return;
+    if (!opt.union_voxel) return wide ? submap_grid_build(c, plan, g, opt.grid_cap, d.maps, s.v.vh, s.t.pts, nullptr, s.gw) : BEV_OK;
     {
         ProfScope ps(c, K_SUBMAP_VOX_KEYS, gm);
         launch_submap_vox_keys(d.maps, g.map0, gm, s.v, map_leaf, c->stream);
@@ -129,8 +189,13 @@ void submap_fine_targets(bev_ctx *c, const Group &g, const Options &opt, const S
         ProfScope ps(c, sg.kind == bevsubvox::kStageGlobal ? K_SUBMAP_VOX_GLOBAL : K_SUBMAP_VOX_TILE, gm);
         launch_submap_vox_stage(sg.kind, sg.k, sg.j, g.map0, gm, tiles, s.v, c->stream);
     }
-    ProfScope ps(c, K_SUBMAP_VOX_FINISH, gm);
-    launch_submap_vox_finish(d.maps, g.map0, gm, s.v, s.t, c->stream);
+    {
+        SubmapRegWork t = s.t;
+        if (wide) t.sorted = nullptr, t.hdr = nullptr, t.cell_off = nullptr; /* (no grid at nullptr) */
+        ProfScope ps(c, K_SUBMAP_VOX_FINISH, gm);
+        launch_submap_vox_finish(d.maps, g.map0, gm, s.v, t, c->stream);
+    }
+    return wide ? submap_grid_build(c, plan, g, opt.grid_cap, d.maps, s.v.vh, s.t.pts, nullptr, s.gw) : BEV_OK;
 }
 
 /* the registration call on the context's stream, behind the entries' checks and begin_call.  map_leaf > 0: the maps are thinned
@@ -141,6 +206,7 @@ int submap_reg_frames(bev_ctx *c, const bev_point_t *d_clouds, const Call &call,
 {
     Options opt;
     opt.union_voxel = map_leaf > 0.0f;
+    opt.grid_cap = c->submap_grid_cap[0];
     const Plan plan = bevsubreg::plan_call(call, opt, group_cap(c));
     std::vector<FineProblem> probs(plan.probs.size());
     for (size_t i = 0; i < probs.size(); ++i) {
@@ -156,13 +222,18 @@ int submap_reg_frames(bev_ctx *c, const bev_point_t *d_clouds, const Call &call,
     BEVCK(submap_fine_begin(c, plan, opt, d_clouds, leaf, s, probs));
     const FineProblem *d_probs = static_cast<const FineProblem *>(s.d.probs);
     for (const Group &g : plan.groups) { /* one behind the other: the stream's order hands the maps' arrays on */
-        submap_fine_targets(c, g, opt, s, map_leaf);
+        BEVCK(submap_fine_targets(c, plan, g, opt, s, map_leaf));
         for (uint32_t p0 = 0; p0 < g.n_probs; p0 += kFineProblemsPerLaunch) {
             const int n = (int)std::min<uint32_t>(kFineProblemsPerLaunch, g.n_probs - p0);
-            ProfScope ps(c, K_SUBMAP_ICP, n);
-            launch_submap_icp(d_probs + g.prob0 + p0, n, s.d.maps, g.map0, s.w, s.t, d_coarse, d_best, prm, d_results, c->stream);
+            ProfScope ps(c, opt.grid_cap ? K_SUBMAP_ICP_WIDE : K_SUBMAP_ICP, n);
+            if (opt.grid_cap)
+                launch_submap_icp_wide(d_probs + g.prob0 + p0, n, s.d.maps, g.map0, s.w, s.t, s.gw.cell0, d_coarse, d_best, prm,
+                                       d_results, c->stream);
+            else
+                launch_submap_icp(d_probs + g.prob0 + p0, n, s.d.maps, g.map0, s.w, s.t, d_coarse, d_best, prm, d_results, c->stream);
         }
     }
+    submap_grid_record(c, 0, plan, opt.grid_cap, kFineCells, c->reg.fine_buf.p, s.t.hdr, s.t.cell_off);
     HIPCK(c, hipGetLastError());
     return BEV_OK;
 }
@@ -177,25 +248,57 @@ struct SubmapCoarse {
     SubmapPnVoxWork p{};
     uint32_t *ent_start = nullptr;
     PlanDev d{};
+    int grid_cap = 0;    /* > 0: the wide grids, in place of k_submap_pn_target's and k_submap_pn_grid's */
+    SubmapGridWork gw{}; /* ... (gw.off is t.cell_off, gw.hdr t.hdr, gw.sorted t.sorted) */
 };
+/* the target rows' searchable copies, headers and offsets are the wide grid's too */
+void submap_coarse_grid_work(SubmapCoarse &s, const Options &opt, const PlanDev &d)
+{
+    s.grid_cap = opt.all_maps ? 0 : opt.grid_cap;
+    s.gw.hdr = s.t.hdr;
+    s.gw.off = s.t.cell_off;
+    s.gw.sorted = s.t.sorted;
+    s.gw.cell0 = static_cast<const uint64_t *>(d.cell0);
+}
 int submap_coarse_work(bev_ctx *c, const Plan &plan, const Options &opt, size_t stride, SubmapCoarse &s)
 {
-    const bool icp = !opt.all_maps, vox = opt.union_voxel, staged = vox || !icp;
+    /* wide: the concatenation is k_submap_pn_move's (p.moved, p.v.vh) where the maps are not thinned, and t.rows points at it */
+    const bool icp = !opt.all_maps, vox = opt.union_voxel, wide = opt.grid_cap > 0 && icp, staged = vox || !icp || wide;
+    const GridPieces gp = grid_pieces(plan, wide);
     const size_t L = icp ? std::min(2 * plan.probs.size(), (size_t)kIcpProblemsPerLaunch) : 0, E = plan.entries.size();
     const size_t T = std::max<size_t>((size_t)plan.max_group_pts, 1), M = std::max<size_t>(plan.max_group_maps, 1);
     s.t = SubmapCoarseWork{};
     s.p = SubmapPnVoxWork{};
-    const size_t sz[] = {L * 16 * stride, std::max<size_t>(E, 1) * 4, icp || vox ? T * 48 : 0, icp ? T * 16 : 0,
-                         icp ? M * sizeof(IcpGridHdr) : 0, icp ? M * 4 * (size_t)(kIcpCells + 1) : 0, staged ? T * 48 : 0,
-                         vox ? std::max<size_t>((size_t)plan.max_group_keys, 1) * 8 : 0, vox ? (T + M) * 4 : 0, vox ? T * 4 : 0,
-                         vox ? T * 16 : 0, staged ? M * sizeof(SubvoxHdr) : 0};
+    const size_t sz[] = {L * 16 * stride, std::max<size_t>(E, 1) * 4, (icp && !wide) || vox ? T * 48 : 0, icp ? T * 16 : 0,
+                         icp ? M * sizeof(IcpGridHdr) : 0, !icp ? 0 : wide ? gp.cnt : M * 4 * (size_t)(kIcpCells + 1),
+                         staged ? T * 48 : 0, vox ? std::max<size_t>((size_t)plan.max_group_keys, 1) * 8 : 0, vox ? (T + M) * 4 : 0,
+                         vox ? T * 4 : 0, vox ? T * 16 : 0, staged ? M * sizeof(SubvoxHdr) : 0, gp.cnt, gp.bounds, gp.sums};
     void **const dst[] = {(void **)&s.t.cur, (void **)&s.ent_start, (void **)&s.t.rows, (void **)&s.t.sorted, (void **)&s.t.hdr,
                           (void **)&s.t.cell_off, (void **)&s.p.moved, (void **)&s.p.v.keys, (void **)&s.p.v.vstart,
-                          (void **)&s.p.vidx, (void **)&s.p.vpos, (void **)&s.p.v.vh};
+                          (void **)&s.p.vidx, (void **)&s.p.vpos, (void **)&s.p.v.vh, (void **)&s.gw.cnt, (void **)&s.gw.part_bounds,
+                          (void **)&s.gw.part_sum};
     BEVCK(c->reg.icp_buf.grow(c, carve(nullptr, sz, dst)));
     carve(c->reg.icp_buf.p, sz, dst);
     if (!icp) s.t.sorted = nullptr, s.t.hdr = nullptr, s.t.cell_off = nullptr, s.t.cur = nullptr;
+    if (wide && !vox) s.t.rows = s.p.moved;
     return BEV_OK;
+}
+
+/* the coarse ICP of a group's problems (two per match), in launches of kIcpProblemsPerLaunch, against the grids the group has */
+void submap_coarse_icp_launches(bev_ctx *c, const Group &g, const SubmapCoarse &s, const float *pn, size_t stride,
+                                const uint32_t *d_counts, const IcpProblem *d_probs, const bev_icp_params_t &prm,
+                                bev_icp_result_t *d_results)
+{
+    for (uint32_t p0 = 0; p0 < 2 * g.n_probs; p0 += kIcpProblemsPerLaunch) {
+        const int n = (int)std::min<uint32_t>(kIcpProblemsPerLaunch, 2 * g.n_probs - p0);
+        ProfScope ps(c, s.grid_cap ? K_SUBMAP_COARSE_ICP_WIDE : K_SUBMAP_COARSE_ICP, n);
+        if (s.grid_cap)
+            launch_submap_coarse_icp_wide(pn, stride, d_counts, d_probs + 2 * (size_t)g.prob0 + p0, n, s.d.maps, g.map0, s.t,
+                                          s.gw.cell0, prm, d_results, c->stream);
+        else
+            launch_submap_coarse_icp(pn, stride, d_counts, d_probs + 2 * (size_t)g.prob0 + p0, n, s.d.maps, g.map0, s.t, prm,
+                                     d_results, c->stream);
+    }
 }
 
 /* what the coarse entries check behind their own arguments, with maps to build: BEV_OK, or what the entry returns */
@@ -228,8 +331,8 @@ Plan submap_coarse_plan(bev_ctx *c, Call &call, const Options &opt, int n_frames
 
 /* a group's targets thinned over their union into s.t.rows: moved rows, keys, the sort, centroids, normals;
  * the search grids where the call has matches */
-void submap_coarse_thin(bev_ctx *c, const Plan &plan, const Group &g, const SubmapCoarse &s, const float *pn, size_t stride,
-                        const uint32_t *d_counts, float pn_leaf, float radius, const float vp[2])
+int submap_coarse_thin(bev_ctx *c, const Plan &plan, const Group &g, const SubmapCoarse &s, const float *pn, size_t stride,
+                       const uint32_t *d_counts, float pn_leaf, float radius, const float vp[2])
 {
     const int gm = (int)g.n_maps;
     const PlanDev &d = s.d;
@@ -257,10 +360,12 @@ void submap_coarse_thin(bev_ctx *c, const Plan &plan, const Group &g, const Subm
         launch_submap_pn_normals(d.maps, g.map0, gm, (uint32_t)((largest + kIcpThreads - 1) / kIcpThreads), s.p, radius, pn_leaf, vp,
                                  s.t.rows, c->stream);
     }
+    if (s.t.hdr && s.grid_cap) return submap_grid_build(c, plan, g, s.grid_cap, d.maps, s.p.v.vh, nullptr, s.t.rows, s.gw);
     if (s.t.hdr) {
         ProfScope ps(c, K_SUBMAP_PN_GRID, gm);
         launch_submap_pn_grid(d.maps, g.map0, gm, s.p.v.vh, s.t, c->stream);
     }
+    return BEV_OK;
 }
 
 /* ---- the top part over the union of a map's moved full clouds (§6r) ---- */
@@ -288,21 +393,24 @@ struct SubmapTop {
     SubmapTopWork t{};
     size_t cell_stride = 0; /* bytes from the cells' tables to the histograms */
 };
-int submap_top_work(bev_ctx *c, const Plan &plan, bool icp, size_t stride, SubmapTop &w)
+int submap_top_work(bev_ctx *c, const Plan &plan, bool icp, int grid_cap, size_t stride, SubmapTop &w)
 {
     SubmapCoarse &s = w.s;
     const size_t L = icp ? std::min(2 * plan.probs.size(), (size_t)kIcpProblemsPerLaunch) : 0;
     const size_t T = std::max<size_t>((size_t)plan.max_group_pts, 1), M = std::max<size_t>(plan.max_group_maps, 1);
     const size_t U = std::max<size_t>((size_t)plan.max_group_union, 1);
+    const bool wide = grid_cap > 0 && icp;
+    const GridPieces gp = grid_pieces(plan, wide);
     s.t = SubmapCoarseWork{};
     s.p = SubmapPnVoxWork{};
     const size_t sz[] = {L * 16 * stride, T * 48, icp ? T * 16 : 0, icp ? M * sizeof(IcpGridHdr) : 0,
-                         icp ? M * 4 * (size_t)(kIcpCells + 1) : 0, T * 48, std::max<size_t>((size_t)plan.max_group_keys, 1) * 8,
-                         (T + M) * 4, T * 4, T * 16, M * sizeof(SubvoxHdr), U * 8, M * sizeof(SubtopCells),
-                         M * (size_t)kTopHistWords * 4};
+                         !icp ? 0 : wide ? gp.cnt : M * 4 * (size_t)(kIcpCells + 1), T * 48,
+                         std::max<size_t>((size_t)plan.max_group_keys, 1) * 8, (T + M) * 4, T * 4, T * 16, M * sizeof(SubvoxHdr), U * 8,
+                         M * sizeof(SubtopCells), M * (size_t)kTopHistWords * 4, gp.cnt, gp.bounds, gp.sums};
     void **const dst[] = {(void **)&s.t.cur, (void **)&s.t.rows, (void **)&s.t.sorted, (void **)&s.t.hdr, (void **)&s.t.cell_off,
                           (void **)&s.p.moved, (void **)&s.p.v.keys, (void **)&s.p.v.vstart, (void **)&s.p.vidx, (void **)&s.p.vpos,
-                          (void **)&s.p.v.vh, (void **)&w.t.ukeys, (void **)&w.t.cells, (void **)&w.t.hist};
+                          (void **)&s.p.v.vh, (void **)&w.t.ukeys, (void **)&w.t.cells, (void **)&w.t.hist, (void **)&s.gw.cnt,
+                          (void **)&s.gw.part_bounds, (void **)&s.gw.part_sum};
     BEVCK(c->reg.icp_buf.grow(c, carve(nullptr, sz, dst)));
     carve(c->reg.icp_buf.p, sz, dst);
     if (!icp) s.t.sorted = nullptr, s.t.hdr = nullptr, s.t.cell_off = nullptr, s.t.cur = nullptr;
@@ -378,6 +486,7 @@ int submap_top_targets(bev_ctx *c, const Plan &plan, const Group &g, const Subma
         launch_submap_pn_normals(d.maps, g.map0, gm, (uint32_t)((rows + kIcpThreads - 1) / kIcpThreads), s.p, radius, pn_leaf, vp,
                                  s.t.rows, c->stream);
     }
+    if (s.t.hdr && s.grid_cap) return submap_grid_build(c, plan, g, s.grid_cap, d.maps, s.p.v.vh, nullptr, s.t.rows, s.gw);
     if (s.t.hdr) {
         ProfScope ps(c, K_SUBMAP_PN_GRID, gm);
         launch_submap_pn_grid(d.maps, g.map0, gm, s.p.v.vh, s.t, c->stream);
@@ -453,7 +562,7 @@ int bev_submap_voxel_cloud_device_resident(bev_ctx_t *c, int n_frames, const bev
     SubmapFine s;
     BEVCK(submap_fine_begin(c, plan, opt, d_clouds, leaf, s));
     for (const Group &g : plan.groups) {
-        submap_fine_targets(c, g, opt, s, map_leaf);
+        BEVCK(submap_fine_targets(c, plan, g, opt, s, map_leaf));
         uint64_t largest = 0;
         for (uint32_t u = g.map0; u < g.map0 + g.n_maps; ++u) largest = std::max(largest, plan.map_cap[u]);
         const uint32_t parts = (uint32_t)std::min<uint64_t>((largest + 4 * kFineThreads - 1) / (4 * kFineThreads), 256);
@@ -530,6 +639,7 @@ int bev_submap_coarse_voxel_registration_device_resident(bev_ctx_t *c, int n_fra
     Options opt;
     opt.point_normal = true;
     opt.union_voxel = vox;
+    opt.grid_cap = c->submap_grid_cap[1];
     const Plan plan = submap_coarse_plan(c, call, opt, n_frames, stride);
     SubmapCoarse s;
     BEVCK(submap_coarse_work(c, plan, opt, stride, s));
@@ -547,23 +657,26 @@ int bev_submap_coarse_voxel_registration_device_resident(bev_ctx_t *c, int n_fra
         }
     BEVCK(plan_up(c, c->reg.icp_tab, plan, opt, s.d, probs.data(), probs.size() * sizeof(IcpProblem)));
     s.p.v.key0 = static_cast<const uint64_t *>(s.d.key0);
+    submap_coarse_grid_work(s, opt, s.d);
     const float vp[2] = {viewpoint && vox ? viewpoint[0] : 0.0f, viewpoint && vox ? viewpoint[1] : 0.0f};
     const float *pn = static_cast<const float *>(d_pn);
     const IcpProblem *d_probs = static_cast<const IcpProblem *>(s.d.probs);
     for (const Group &g : plan.groups) {
         if (vox) {
-            submap_coarse_thin(c, plan, g, s, pn, stride, d_counts, pn_leaf, radius, vp);
+            BEVCK(submap_coarse_thin(c, plan, g, s, pn, stride, d_counts, pn_leaf, radius, vp));
+        } else if (s.grid_cap) {
+            {
+                ProfScope ps(c, K_SUBMAP_PN_MOVE, (int)g.n_maps);
+                launch_submap_pn_move(s.d.maps, g.map0, (int)g.n_maps, s.d.entries, pn, stride, d_counts, s.ent_start, s.p, c->stream);
+            }
+            BEVCK(submap_grid_build(c, plan, g, s.grid_cap, s.d.maps, s.p.v.vh, nullptr, s.t.rows, s.gw));
         } else {
             ProfScope ps(c, K_SUBMAP_PN_TARGET, (int)g.n_maps);
             launch_submap_pn_target(s.d.maps, g.map0, (int)g.n_maps, s.d.entries, pn, stride, d_counts, s.ent_start, s.t, c->stream);
         }
-        for (uint32_t p0 = 0; p0 < 2 * g.n_probs; p0 += kIcpProblemsPerLaunch) {
-            const int n = (int)std::min<uint32_t>(kIcpProblemsPerLaunch, 2 * g.n_probs - p0);
-            ProfScope ps(c, K_SUBMAP_COARSE_ICP, n);
-            launch_submap_coarse_icp(pn, stride, d_counts, d_probs + 2 * (size_t)g.prob0 + p0, n, s.d.maps, g.map0, s.t, prm,
-                                     d_results, c->stream);
-        }
+        submap_coarse_icp_launches(c, g, s, pn, stride, d_counts, d_probs, prm, d_results);
     }
+    submap_grid_record(c, 1, plan, s.grid_cap, kIcpCells, c->reg.icp_buf.p, s.t.hdr, s.t.cell_off);
     {
         ProfScope ps(c, K_ICP_BEST, n_matches);
         launch_icp_best(d_results, n_matches, d_best, c->stream);
@@ -616,7 +729,7 @@ int bev_submap_pn_cloud_device_resident(bev_ctx_t *c, int n_frames, const void *
     const float *pn = static_cast<const float *>(d_pn);
     for (const Group &g : plan.groups) {
         if (vox) {
-            submap_coarse_thin(c, plan, g, s, pn, stride, d_counts, pn_leaf, radius, vp);
+            BEVCK(submap_coarse_thin(c, plan, g, s, pn, stride, d_counts, pn_leaf, radius, vp));
         } else {
             ProfScope ps(c, K_SUBMAP_PN_MOVE, (int)g.n_maps);
             launch_submap_pn_move(s.d.maps, g.map0, (int)g.n_maps, s.d.entries, pn, stride, d_counts, s.ent_start, s.p, c->stream);
@@ -658,7 +771,7 @@ int bev_submap_top_part_cloud_device_resident(bev_ctx_t *c, int n_frames, const 
     opt.point_normal = opt.union_voxel = opt.top_union = opt.all_maps = true;
     const Plan plan = bevsubreg::plan_call(call, opt, group_cap(c));
     SubmapTop w;
-    BEVCK(submap_top_work(c, plan, false, 0, w));
+    BEVCK(submap_top_work(c, plan, false, 0, 0, w));
     BEVCK(plan_up(c, c->reg.icp_tab, plan, opt, w.s.d));
     w.s.p.v.key0 = static_cast<const uint64_t *>(w.s.d.key0);
     w.t.u0 = static_cast<const uint64_t *>(w.s.d.u0);
@@ -699,9 +812,10 @@ int bev_submap_top_part_coarse_registration_device_resident(bev_ctx_t *c, int n_
     BEVCK(wait_default_stream(c));
     Options opt;
     opt.point_normal = opt.union_voxel = opt.top_union = true;
+    opt.grid_cap = c->submap_grid_cap[1];
     const Plan plan = bevsubreg::plan_call(call, opt, group_cap(c));
     SubmapTop w;
-    BEVCK(submap_top_work(c, plan, true, stride, w));
+    BEVCK(submap_top_work(c, plan, true, opt.grid_cap, stride, w));
     std::vector<IcpProblem> probs; /* two problems per match, the guesses adjacent */
     probs.reserve(2 * plan.probs.size());
     for (const bevsubreg::Problem &pp : plan.probs)
@@ -717,24 +831,59 @@ int bev_submap_top_part_coarse_registration_device_resident(bev_ctx_t *c, int n_
     BEVCK(plan_up(c, c->reg.icp_tab, plan, opt, w.s.d, probs.data(), probs.size() * sizeof(IcpProblem)));
     w.s.p.v.key0 = static_cast<const uint64_t *>(w.s.d.key0);
     w.t.u0 = static_cast<const uint64_t *>(w.s.d.u0);
+    submap_coarse_grid_work(w.s, opt, w.s.d);
     const float vp[2] = {viewpoint ? viewpoint[0] : 0.0f, viewpoint ? viewpoint[1] : 0.0f};
     const float *pn = static_cast<const float *>(d_pn);
     const IcpProblem *d_probs = static_cast<const IcpProblem *>(w.s.d.probs);
     for (const Group &g : plan.groups) {
         BEVCK(submap_top_targets(c, plan, g, w, d_clouds, pn_leaf, radius, vp));
-        for (uint32_t p0 = 0; p0 < 2 * g.n_probs; p0 += kIcpProblemsPerLaunch) {
-            const int n = (int)std::min<uint32_t>(kIcpProblemsPerLaunch, 2 * g.n_probs - p0);
-            ProfScope ps(c, K_SUBMAP_COARSE_ICP, n);
-            launch_submap_coarse_icp(pn, stride, d_counts, d_probs + 2 * (size_t)g.prob0 + p0, n, w.s.d.maps, g.map0, w.s.t, prm,
-                                     d_results, c->stream);
-        }
+        submap_coarse_icp_launches(c, g, w.s, pn, stride, d_counts, d_probs, prm, d_results);
     }
+    submap_grid_record(c, 1, plan, w.s.grid_cap, kIcpCells, c->reg.icp_buf.p, w.s.t.hdr, w.s.t.cell_off);
     {
         ProfScope ps(c, K_ICP_BEST, n_matches);
         launch_icp_best(d_results, n_matches, d_best, c->stream);
     }
     HIPCK(c, hipGetLastError());
     return record_tail(c);
+}
+
+/* ---- search grids sized to the maps (bev_submap_grid.h) ---------------------------------------------------- */
+int bev_set_submap_search_grid(bev_ctx_t *c, int fine_dim, int coarse_dim)
+{
+    static_assert(BEV_SUBMAP_SEARCH_GRID_MAX == bevsubreg::kGridCapMax, "one cap");
+    if (!c || fine_dim < 0 || fine_dim > BEV_SUBMAP_SEARCH_GRID_MAX || coarse_dim < 0 || coarse_dim > BEV_SUBMAP_SEARCH_GRID_MAX)
+        return BEV_ERR_INVALID_ARG;
+    c->submap_grid_cap[0] = fine_dim;
+    c->submap_grid_cap[1] = coarse_dim;
+    return BEV_OK;
+}
+
+int bev_debug_get_submap_grid(bev_ctx_t *c, int coarse, int first_map, int n_maps, uint32_t *out)
+{
+    if (!c || (coarse != 0 && coarse != 1) || first_map < 0 || n_maps < 0 || !out) return BEV_ERR_INVALID_ARG;
+    const SubmapGridRecord &r = c->submap_grid_rec[coarse];
+    if (!r.hdr || (size_t)first_map + (size_t)n_maps > r.off0.size()) return BEV_ERR_INVALID_ARG;
+    BEVCK(begin_call(c, false));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    if (r.buf != (coarse ? c->reg.icp_buf.p : c->reg.fine_buf.p)) return BEV_ERR_INVALID_ARG;
+    std::vector<IcpGridHdr> hdr((size_t)n_maps);
+    std::vector<uint32_t> off;
+    if (n_maps) HIPCK(c, hipMemcpy(hdr.data(), r.hdr + first_map, hdr.size() * sizeof(IcpGridHdr), hipMemcpyDeviceToHost));
+    for (int i = 0; i < n_maps; ++i) {
+        const IcpGridHdr &h = hdr[(size_t)i];
+        const size_t m = (size_t)(first_map + i);
+        if (h.nx < 1 || h.ny < 1 || (uint64_t)h.nx * (uint64_t)h.ny > r.cells[m]) return BEV_ERR_INVALID_ARG; /* (not a grid) */
+        off.resize((size_t)h.nx * (size_t)h.ny + 1);
+        HIPCK(c, hipMemcpy(off.data(), r.cell_off + r.off0[m], off.size() * 4, hipMemcpyDeviceToHost));
+        uint32_t largest = 0;
+        for (size_t k = 0; k + 1 < off.size(); ++k) largest = std::max(largest, off[k + 1] - off[k]);
+        out[4 * i] = (uint32_t)h.nx;
+        out[4 * i + 1] = (uint32_t)h.ny;
+        out[4 * i + 2] = h.n;
+        out[4 * i + 3] = largest;
+    }
+    return BEV_OK;
 }
 
 } /* extern "C" */

@@ -157,6 +157,16 @@ struct RegState {
     void release();
 };
 
+/* what bev_debug_get_submap_grid reads: the search grids of the last launch group of the last scan-to-map call of a stage, in
+ * that stage's workspace (buf: the workspace's address then; the record holds while it has not moved) */
+struct SubmapGridRecord {
+    const void *buf = nullptr;
+    const IcpGridHdr *hdr = nullptr;  /* [the group's maps] */
+    const uint32_t *cell_off = nullptr;
+    std::vector<uint64_t> off0;       /* a map's first offset word behind cell_off */
+    std::vector<uint64_t> cells;      /* the cells its offsets have room for */
+};
+
 } // namespace bevh
 
 struct bev_ctx {
@@ -246,6 +256,10 @@ struct bev_ctx {
      * (submap_float_frames) send their plan up the same table and have no planes: their output is the accumulator */
     bevh::UploadTable submap_tab;
     size_t submap_reg_group = 0; /* BEV_SUBMAP_REG_GROUP=<bytes>: the cap of a launch group of bev_submap_registration_* (tests: results do not depend on it); 0: kSubmapRegCap */
+    /* bev_set_submap_search_grid: the cap of cells per axis of the maps' search grids, fine and coarse stage;
+     * 0: the one-workgroup grids of 128 x 128 and 64 x 64 cells at most.  [0] fine, [1] coarse, as the records of the hook */
+    int submap_grid_cap[2] = {0, 0};
+    bevh::SubmapGridRecord submap_grid_rec[2];
     int posed_group = 0; /* BEV_POSED_GROUP=1 .. 65535: grids per launch group (tests: results do not depend on it); 0: what fits kPosedWsCap */
 
     bevh::RegState reg;

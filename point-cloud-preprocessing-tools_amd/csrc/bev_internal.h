@@ -247,6 +247,14 @@ enum KernelId {
     K_SUBMAP_TOP_COMPACT,  /* ... the selected keys (the sort: K_SUBMAP_VOX_TILE, K_SUBMAP_VOX_GLOBAL) */
     K_SUBMAP_TOP_ROWS,     /* ... the rows of top(g) from the sorted keys */
     K_SUBMAP_TOP_OVERFLOW, /* ... the voxel grid's overflow branch: top(g) kept for the normals' full scan */
+    K_SUBMAP_GRID_BOUNDS,  /* a map's search grid sized to the map (bev_submap_grid.h): the parts' bounds */
+    K_SUBMAP_GRID_HEADER,  /* ... the grid's header */
+    K_SUBMAP_GRID_COUNT,   /* ... the cells' counts in global memory */
+    K_SUBMAP_GRID_SUMS,    /* ... the scan: the tiles' sums */
+    K_SUBMAP_GRID_SCAN,    /* ... the scan: the cells' offsets and cursors */
+    K_SUBMAP_GRID_SCATTER, /* ... the searchable points by cell */
+    K_SUBMAP_ICP_WIDE,        /* K_SUBMAP_ICP against such a grid */
+    K_SUBMAP_COARSE_ICP_WIDE, /* K_SUBMAP_COARSE_ICP against such a grid, its offsets in global memory */
     K_COUNT
 };
 const char *kernel_name(int id);
@@ -590,6 +598,32 @@ void launch_submap_top_compact(const void *maps, uint32_t map0, int n_maps, uint
 void launch_submap_top_rows(const void *maps, uint32_t map0, int n_maps, uint32_t parts, const void *entries, const void *slots,
                             const bev_point_t *clouds, const SubmapTopWork &t, const SubmapPnVoxWork &p, hipStream_t st);
 void launch_submap_top_overflow(const void *maps, uint32_t map0, int n_maps, const SubmapPnVoxWork &p, hipStream_t st);
+
+/* ---- a map's search grid sized to the map (bev_submap_grid.h) ----
+ * the maps of ONE launch group of a plan with grid_cap > 0: a map's offsets and counters at cell0[its index in the plan] */
+constexpr uint32_t kSubgridParts = 256;     /* workgroups over a map's points at most (bevsubreg::kGridParts) */
+constexpr uint32_t kSubgridScanParts = 256; /* tiles of 4096 cells of a map at most (bevsubreg::kGridScanParts) */
+struct SubmapGridWork {
+    IcpGridHdr *hdr;        /* [the group's maps] */
+    uint32_t *off;          /* [the group's cells]  nx * ny + 1 offsets per map */
+    uint32_t *cnt;          /* [the group's cells]  the counters, then the cursors; zeroed by the caller on the same stream */
+    float4 *sorted;         /* [the group's points] the searchable points by cell: a map's at its pt0 */
+    float4 *part_bounds;    /* [the group's maps][kSubgridParts]      min x, min y, max x, max y */
+    uint32_t *part_sum;     /* [the group's maps][kSubgridScanParts] */
+    const uint64_t *cell0;  /* [the plan's maps]    device table */
+};
+/* one step of the build for the n_maps maps from map0 on: 0 bounds, 1 header, 2 count, 3 sums, 4 scan, 5 scatter.  parts:
+ * workgroups over the largest map's points; tiles: over the largest map's cells; cap: the cap of cells per axis; vh: the maps'
+ * point counts (n_out); the points: pts (float4, a map's at its pt0) or, pts == nullptr, PointNormal rows */
+void launch_submap_grid(int step, const void *maps, uint32_t map0, int n_maps, uint32_t parts, uint32_t tiles, int cap,
+                        const SubvoxHdr *vh, const float4 *pts, const float *rows, const SubmapGridWork &w, hipStream_t st);
+/* launch_submap_icp and launch_submap_coarse_icp with t.cell_off the group's offsets and cell0 the plan's table of bases */
+void launch_submap_icp_wide(const FineProblem *probs, int n, const void *maps, uint32_t map0, const FineWork &w,
+                            const SubmapRegWork &t, const uint64_t *cell0, const bev_icp_result_t *coarse, const int32_t *best,
+                            const bev_icp_params_t &prm, bev_icp_result_t *results, hipStream_t st);
+void launch_submap_coarse_icp_wide(const float *pn, size_t stride, const uint32_t *counts, const IcpProblem *probs, int n,
+                                   const void *maps, uint32_t map0, const SubmapCoarseWork &t, const uint64_t *cell0,
+                                   const bev_icp_params_t &prm, bev_icp_result_t *results, hipStream_t st);
 
 /* opt in to > 64 KiB of dynamic LDS for the kernels that need it */
 hipError_t configure_kernels(const Geometry &g);

@@ -50,6 +50,7 @@
 #include "bev_submap_coarse.h"
 #include "bev_submap_pn_vox.h"
 #include "bev_submap_top.h"
+#include "bev_submap_grid.h"
 
 using namespace bevx;
 
@@ -68,6 +69,8 @@ static const char *const kNames[K_COUNT] = {
     "k_submap_pn_move", "k_submap_pn_keys", "k_submap_pn_finish", "k_submap_pn_normals", "k_submap_pn_grid", "k_submap_pn_out",
     "k_submap_top_keys", "k_submap_top_cells", "k_submap_top_hist", "k_submap_top_scan", "k_submap_top_compact", "k_submap_top_rows",
     "k_submap_top_overflow",
+    "k_subgrid_bounds", "k_subgrid_header", "k_subgrid_count", "k_subgrid_sums", "k_subgrid_scan", "k_subgrid_scatter",
+    "k_submap_icp_wide", "k_submap_coarse_icp_wide",
 };
 const char *kernel_name(int id) { return (id >= 0 && id < K_COUNT) ? kNames[id] : "?"; }
 

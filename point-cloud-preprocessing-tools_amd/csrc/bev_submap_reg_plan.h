@@ -39,11 +39,19 @@
  * group's union keys; and map_cap, top_max_out of that: the rows its top part can have, which is what pt0, the sort keys and
  * everything of §6q are counted in.  An entry's pad words carry its first index in the union and its record count.  A map's
  * bytes are map_top_union_bytes.  Without top_union nothing of this is computed and every plan is what it was.
+ *
+ * grid_cap (bev_set_submap_search_grid): 0: a map's search grid is the one-workgroup build's, at most 128 x 128
+ * (fine) or 64 x 64 (PointNormal) cells whose offsets lie at the map's index in the group, and every plan is what it was.
+ * 1 .. kGridCapMax: the grid is built by bev_submap_grid.h with grid_dim(n, grid_cap) cells per axis, n the map's point count,
+ * which only the device knows; grid_dim is monotone in n, so grid_cells(capacity, grid_cap) bounds a map's cells.  A map then
+ * owns grid_cells + 1 offsets and as many counters at map_cell0 of the group's two arrays (a prefix inside its group), and the
+ * byte models count them, with the build's partial bounds and sums, in place of the fixed grid.
  */
 #ifndef BEV_SUBMAP_REG_PLAN_H
 #define BEV_SUBMAP_REG_PLAN_H
 
 #include <algorithm>
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <cstring>
@@ -52,7 +60,38 @@
 #include "../../include/bev_mi355x.h" /* bev_match_t */
 #include "bev_submap_vox_plan.h"
 
+#if defined(__HIPCC__)
+#define BEV_PLAN_HD __host__ __device__
+#else
+#define BEV_PLAN_HD
+#endif
+
 namespace bevsubreg {
+
+/* ---- the size of a search grid (bev_reg_common.h's rule, here once for the host plan and for bev_submap_grid.h) ---- */
+constexpr int kGridCapMax = 1024; /* the largest settable cap of cells per axis */
+/* cells per axis of the grid of a target of n points (searchable or not) under the cap D >= 1 */
+BEV_PLAN_HD inline int grid_dim(uint32_t n, int D)
+{
+    const int r = (int)ceilf(sqrtf((float)n));
+    return r < 1 ? 1 : r > D ? D : r;
+}
+/* cells a target of at most cap points can have: grid_dim is monotone in n */
+inline uint64_t grid_cells(uint64_t cap, int D)
+{
+    const uint64_t d = (uint64_t)grid_dim((uint32_t)std::min<uint64_t>(cap, 0xffffffffull), D);
+    return d * d;
+}
+/* bev_submap_grid.h's partial results per map: kGridParts bounds of four floats, kGridScanParts sums of cell counts */
+constexpr uint32_t kGridParts = 256, kGridScanTile = 4096;
+constexpr uint32_t kGridScanParts = (uint32_t)kGridCapMax * kGridCapMax / kGridScanTile;
+constexpr uint32_t kGridPartBytes = kGridParts * 16 + kGridScanParts * 4;
+/* device bytes of a map's search grid besides its points: D == 0: the offsets of fixed_cells cells; else the offsets and the
+ * counters of grid_cells(cap, D) cells and the partial results */
+inline uint64_t grid_bytes(uint64_t cap, int D, uint32_t fixed_cells)
+{
+    return D == 0 ? (uint64_t)(fixed_cells + 1) * 4 : (grid_cells(cap, D) + 1) * 8 + kGridPartBytes;
+}
 
 constexpr uint32_t kGridCells = 128 * 128; /* kFineCells (bev_internal.h): cells of a map's search grid */
 constexpr uint32_t kCoarseGridCells = 64 * 64; /* kIcpCells: cells of a PointNormal map's search grid */
@@ -97,6 +136,8 @@ struct Group {
     uint64_t max_slots = 0;          /* union_voxel: the largest key array among its maps: it sizes the sort's launches */
     uint64_t union_pts = 0;          /* top_union: records of its maps' unions together */
     uint64_t max_union = 0;          /* top_union: the largest union among its maps: it sizes the select's launches */
+    uint64_t cells = 0;              /* grid_cap > 0: grid_cells + 1 of its maps together */
+    uint64_t max_cells = 0;          /* grid_cap > 0: the largest grid_cells among its maps: it sizes the scan's launches */
 };
 struct Plan {
     std::vector<Slot> slots;
@@ -115,6 +156,8 @@ struct Plan {
     std::vector<uint64_t> map_union_cap; /* top_union: records of a used map's union (map_cap: rows of its top part) */
     std::vector<uint64_t> map_u0;        /* top_union: a used map's first key in its group's union keys */
     uint64_t max_group_union = 0;        /* top_union */
+    std::vector<uint64_t> map_cell0;     /* grid_cap > 0: a used map's first word in its group's offsets and counters */
+    uint64_t max_group_cells = 0;        /* grid_cap > 0 */
 };
 
 /* what the union grid adds to a map that can hold cap points: the thinned points (16 bytes each), the padded sort keys
@@ -122,22 +165,27 @@ struct Plan {
 inline uint64_t map_union_bytes(uint64_t cap) { return cap * 16 + bevsubvox::key_slots(cap) * 8 + (cap + 1) * 4 + 32; }
 
 /* device bytes of a map that can hold cap points: the moved points and the searchable points by cell (16 bytes each),
- * the cell offsets, the header; union_voxel: and map_union_bytes */
-inline uint64_t map_bytes(uint64_t cap, bool union_voxel = false)
+ * the search grid (grid_bytes), the header; union_voxel: and map_union_bytes; a wide grid (D > 0) without it: the count's
+ * header (32 bytes), since the concatenation is then bev_submap_vox.h's */
+inline uint64_t map_bytes(uint64_t cap, bool union_voxel = false, int D = 0)
 {
-    return cap * 32 + (uint64_t)(kGridCells + 1) * 4 + 32 + (union_voxel ? map_union_bytes(cap) : 0);
+    return cap * 32 + grid_bytes(cap, D, kGridCells) + 32 + (union_voxel ? map_union_bytes(cap) : D ? 32 : 0);
 }
 
 /* device bytes of a PointNormal map of cap rows (bev_submap_coarse_registration_device_resident): the moved rows and the
- * searchable points by cell, the 64 x 64 grid's cell offsets, the header */
-inline uint64_t map_coarse_bytes(uint64_t cap) { return cap * kCoarseRowBytes + (uint64_t)(kCoarseGridCells + 1) * 4 + 32; }
+ * searchable points by cell, the search grid (grid_bytes: D == 0, the 64 x 64 grid's cell offsets), the header; a wide grid: the
+ * count's header too (the concatenation is then bev_submap_pn_vox.h's) */
+inline uint64_t map_coarse_bytes(uint64_t cap, int D = 0)
+{
+    return cap * kCoarseRowBytes + grid_bytes(cap, D, kCoarseGridCells) + 32 + (D ? 32 : 0);
+}
 
 /* device bytes of a PointNormal map of cap rows that is thinned over its union (bev_submap_coarse_voxel_registration_device_resident,
  * bev_submap_pn_cloud_device_resident): kCoarseUnionRowBytes per row, the padded sort keys (8 bytes each), the last voxel start,
- * the 64 x 64 grid's cell offsets and header, the sort's header */
-inline uint64_t map_coarse_union_bytes(uint64_t cap)
+ * the search grid (grid_bytes) and its header, the sort's header */
+inline uint64_t map_coarse_union_bytes(uint64_t cap, int D = 0)
 {
-    return cap * kCoarseUnionRowBytes + bevsubvox::key_slots(cap) * 8 + 4 + (uint64_t)(kCoarseGridCells + 1) * 4 + 32 + 32;
+    return cap * kCoarseUnionRowBytes + bevsubvox::key_slots(cap) * 8 + 4 + grid_bytes(cap, D, kCoarseGridCells) + 32 + 32;
 }
 
 /* rows the top part of n records can have: bev_regfront_max_out (sum over 100 cells of round(0.2f * n_c) <= n / 5 + 50) */
@@ -147,9 +195,9 @@ inline uint64_t top_max_out(uint64_t n) { return n / 5 + 51; }
  * (bev_submap_top_part_coarse_registration_device_resident, bev_submap_top_part_cloud_device_resident): a key per record of the
  * union (the moved records are not kept: a row is moved again from its entry and record), the cells' table and histograms, and
  * what a thinned PointNormal map of top_max_out(c) rows takes, its padded sort keys holding the padded selection first */
-inline uint64_t map_top_union_bytes(uint64_t c)
+inline uint64_t map_top_union_bytes(uint64_t c, int D = 0)
 {
-    return c * 8 + kTopCellBytes + kTopHistBytes + map_coarse_union_bytes(top_max_out(c));
+    return c * 8 + kTopCellBytes + kTopHistBytes + map_coarse_union_bytes(top_max_out(c), D);
 }
 
 /* points the entries of map g can hold together: the sum of their frames' record counts */
@@ -179,6 +227,7 @@ struct Call {
 };
 struct Options { /* see the head of the file */
     bool union_voxel = false, all_maps = false, point_normal = false, top_union = false;
+    int grid_cap = 0; /* 0 .. kGridCapMax */
 };
 
 /* cap_bytes: the group cap */
@@ -247,16 +296,18 @@ inline Plan plan_call(const Call &call, const Options &opt, uint64_t cap_bytes)
     /* the groups */
     p.map_key0.assign(p.maps.size(), 0);
     if (opt.top_union) p.map_u0.assign(p.maps.size(), 0);
+    if (opt.grid_cap) p.map_cell0.assign(p.maps.size(), 0);
     size_t pr = 0;
     for (uint32_t u = 0; u < (uint32_t)p.maps.size();) {
         Group g;
         g.map0 = u;
         g.prob0 = (uint32_t)pr;
         while (u < (uint32_t)p.maps.size()) {
-            const uint64_t b = opt.top_union      ? map_top_union_bytes(p.map_union_cap[u])
-                               : !opt.point_normal ? map_bytes(p.map_cap[u], opt.union_voxel)
-                               : opt.union_voxel ? map_coarse_union_bytes(p.map_cap[u])
-                                                 : map_coarse_bytes(p.map_cap[u]);
+            const int D = opt.grid_cap;
+            const uint64_t b = opt.top_union      ? map_top_union_bytes(p.map_union_cap[u], D)
+                               : !opt.point_normal ? map_bytes(p.map_cap[u], opt.union_voxel, D)
+                               : opt.union_voxel ? map_coarse_union_bytes(p.map_cap[u], D)
+                                                 : map_coarse_bytes(p.map_cap[u], D);
             if (g.n_maps > 0 && g.bytes + b > cap_bytes) break;
             p.maps[u].pt0 = g.pts;
             if (opt.union_voxel) {
@@ -270,6 +321,12 @@ inline Plan plan_call(const Call &call, const Options &opt, uint64_t cap_bytes)
                 g.union_pts += p.map_union_cap[u];
                 g.max_union = std::max(g.max_union, p.map_union_cap[u]);
             }
+            if (D) {
+                const uint64_t cells = grid_cells(p.map_cap[u], D);
+                p.map_cell0[u] = g.cells;
+                g.cells += cells + 1;
+                g.max_cells = std::max(g.max_cells, cells);
+            }
             g.pts += p.map_cap[u];
             g.bytes += b;
             ++g.n_maps;
@@ -281,6 +338,7 @@ inline Plan plan_call(const Call &call, const Options &opt, uint64_t cap_bytes)
         p.max_group_maps = std::max(p.max_group_maps, g.n_maps);
         p.max_group_keys = std::max(p.max_group_keys, g.keys);
         p.max_group_union = std::max(p.max_group_union, g.union_pts);
+        p.max_group_cells = std::max(p.max_group_cells, g.cells);
         p.groups.push_back(g);
     }
     return p;

@@ -40,6 +40,12 @@
  * or 0: the output as ever; 1 without a leaf: exit 1 with "BEV_SUBMAP_TOP_UNION=1 needs BEV_SUBMAP_PN_LEAF > 0"; anything else:
  * exit 1 with "BEV_SUBMAP_TOP_UNION '<text>': expected 0 or 1"; both before any GPU work.
  *
+ * BEV_SUBMAP_SEARCH_GRID=<fine>[,<coarse>] in the environment (both tools): the cap of cells per axis of the maps'
+ * search grids in the fine and the coarse stage, handed to bev_set_submap_search_grid before the first chunk; a single number
+ * sets both stages.  Integers 0 ... 1024; unset, empty or 0: the grids, the launches and the output as ever.  The output does
+ * not depend on it.  Anything else: exit 1 with "BEV_SUBMAP_SEARCH_GRID '<text>': expected <fine>[,<coarse>], integers 0 ...
+ * 1024" and the usage line, before any GPU work.
+ *
  * The chunks, the chain and the bookkeeping are the four registration tools' own (RegistrationChunks.h, RegistrationChain.h;
  * DESIGN.md §6p), the entries' matrices every submap tool's (submapwin::appendEntryPose): this file is the command line, which
  * file an index names, and the poses.
@@ -77,6 +83,25 @@ bool parse_map_leaf(const char *s, float *out)
     return true;
 }
 
+/* "<fine>[,<coarse>]": one or two integers 0 ... BEV_SUBMAP_SEARCH_GRID_MAX and nothing else; one number sets both */
+bool parse_search_grid(const char *s, int dims[2])
+{
+    for (int k = 0; k < 2; ++k) {
+        if (*s < '0' || *s > '9') return false; /* (strtol would take a sign or blanks) */
+        char *end = nullptr;
+        const long v = std::strtol(s, &end, 10);
+        if (v > BEV_SUBMAP_SEARCH_GRID_MAX) return false;
+        dims[k] = (int)v;
+        if (*end == '\0') {
+            if (k == 0) dims[1] = dims[0];
+            return true;
+        }
+        if (*end != ',' || k == 1) return false;
+        s = end + 1;
+    }
+    return false;
+}
+
 } // namespace
 
 int main(int argc, char **argv)
@@ -103,6 +128,14 @@ int main(int argc, char **argv)
                 return 1;
             }
             top_union = true;
+        }
+    int search_grid[2] = {0, 0};
+    if (const char *env = std::getenv("BEV_SUBMAP_SEARCH_GRID"))
+        if (*env && !parse_search_grid(env, search_grid)) {
+            std::cerr << "BEV_SUBMAP_SEARCH_GRID '" << env << "': expected <fine>[,<coarse>], integers 0 ... " << BEV_SUBMAP_SEARCH_GRID_MAX
+                      << "\n";
+            usage();
+            return 1;
         }
     if (argc > 5 && !parse_map_leaf(argv[5], &map_leaf)) {
         std::cerr << "map_leaf '" << argv[5] << "': expected a finite number >= 0\n";
@@ -151,6 +184,10 @@ int main(int argc, char **argv)
     const bev_icp_params_t prm = kTopPart ? bev_icp_fine_defaults() : bev_icp_whole_defaults();
     regchain::Tally tally(kTopPart ? &report : &submap_report,
                           kTopPart ? regchain::ReportAgainst::ChosenCoarse : regchain::ReportAgainst::YawGuess);
+    if (search_grid[0] || search_grid[1]) {
+        bev_ctx_t *ctx = bevhost_context();
+        if (!ctx || bev_set_submap_search_grid(ctx, search_grid[0], search_grid[1]) != BEV_OK) return 2;
+    }
     for (size_t m0 = 0; m0 < matches.size();) {
         /* the indices are places in the sorted listing: windows clipped to it, one map per match */
         const regchain::Chunk chunk = regchain::planChunk(matches.data(), matches.size(), m0, half, 0, n_files - 1, limit, true);
