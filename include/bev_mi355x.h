@@ -834,6 +834,31 @@ int bev_submap_top_part_coarse_registration_device_resident(bev_ctx_t *ctx, int 
 #define BEV_SUBMAP_SEARCH_GRID_MAX 1024
 int bev_set_submap_search_grid(bev_ctx_t *ctx, int fine_dim, int coarse_dim);
 
+/* ---- pair registration search grids sized to the cloud ------------------------------------------------------
+ * The pair calls search a target cloud on the same kind of grid, dim = min(D, max(1, ceil(sqrtf(n)))) cells per axis for a target
+ * of n points, with D = 128 in the fine stage and D = 64 in the coarse one.  This call sets D per stage for the pair calls made
+ * after it (sticky per context; host state read when a call is made):
+ *   0          (default) the stage runs as it always has: the same kernels, launches and workspace layout;
+ *   1 ... BEV_PAIR_SEARCH_GRID_MAX
+ *              every cloud that a match names as a target gets a grid with that cap, built by several workgroups per target with
+ *              the cell counts in global memory, and the ICP reads the target's cell offsets from there.  Values below 128 / 64
+ *              are allowed.  A cloud that is a query only gets no grid.
+ * fine_dim governs bev_icp_point_to_point and bev_fine_registration_device_resident (d_ordered or packed offsets, with or
+ * without a coarse table); coarse_dim governs bev_icp_point_to_plane and bev_coarse_registration_device_resident.  No
+ * bev_submap_* call reads it: those keep bev_set_submap_search_grid, and neither setter reads the other's state.
+ * Results never depend on it: the search is an exact 1-NN with the lowest target index on equal distance whatever the cell size
+ * or the order inside a cell, so every result is bit for bit what D = 0 gives.  Only time and workspace do.  With c the capacity
+ * of a slot (the call's largest cloud in the fine stage, stride in the coarse one) and cells = dim(c)^2:
+ *   a target slot      4 (cells + 1) bytes of offsets in place of the fixed grid's 4 * 16385 (fine) or 4 * 4097 (coarse), and
+ *                      56 bytes of tables and point count;
+ *   a build group      the grids are built in groups of at most 256 targets, one group behind the other in front of the ICP
+ *                      launches; a slot of ONE group takes 4 (cells + 1) bytes of counters plus 5 KiB of partial bounds and sums;
+ *   the coarse stage   keeps the searchable points (16 bytes a row) for every frame of the call, not for its targets alone.
+ * No synchronisation is needed around it: a call made before it and not yet finished keeps its grids.
+ * Status: BEV_ERR_INVALID_ARG for a NULL context or a value outside 0 ... BEV_PAIR_SEARCH_GRID_MAX; nothing changes then. */
+#define BEV_PAIR_SEARCH_GRID_MAX 1024
+int bev_set_pair_search_grid(bev_ctx_t *ctx, int fine_dim, int coarse_dim);
+
 /* ---- layout hint -------------------------------------------------------
  * What the caller knows about how its clouds are laid out, so that the library need not look (k_probe reads every 63rd
  * record of a frame to find out: 0.36 MB and 0.07 us of an HDL_64E frame).  Sticky per context; applies to frames of
@@ -913,6 +938,13 @@ int bev_debug_angle_predicate(bev_ctx_t *ctx, const float *dx, const float *dy,
  * match names).  BEV_ERR_INVALID_ARG for a NULL context or out, a range outside that group, before any such call, and once
  * another call has moved the stage's workspace. */
 int bev_debug_get_submap_grid(bev_ctx_t *ctx, int coarse, int first_map, int n_maps, uint32_t *out);
+
+/* Test hook: the search grids of the targets of the last fine (coarse == 0) or coarse (coarse == 1) PAIR call with matches,
+ * whichever path built them.  Synchronises.  out[4 * i .. 4 * i + 3] = { nx, ny, searchable points, largest count of one cell } of
+ * the grid of the target of match first_match + i of that call; bev_icp_point_to_point and bev_icp_point_to_plane count as one
+ * match, index 0.  BEV_ERR_INVALID_ARG for a NULL context or out, a range outside that call's matches, before any such call, and
+ * once another call (a scan-to-map one included) has used the stage's workspace. */
+int bev_debug_get_pair_grid(bev_ctx_t *ctx, int coarse, int first_match, int n_matches, uint32_t *out);
 
 int bev_abi_version(void);
 

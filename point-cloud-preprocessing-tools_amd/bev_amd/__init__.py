@@ -75,6 +75,7 @@ POSED_BEV_MAX_POSES = 64  # BEV_POSED_BEV_MAX_POSES: poses per frame of posed_be
 SUBMAP_MAX_ENTRIES = 1 << 20  # BEV_SUBMAP_MAX_ENTRIES: (frame, pose) entries of one submap_bev_device / submap_bev_batch call
 SUBMAP_COARSE_MAX_TARGET = 1 << 22  # BEV_SUBMAP_COARSE_MAX_TARGET: rows of one map, entries times stride (submap_coarse_registration_device)
 SUBMAP_SEARCH_GRID_MAX = 1024  # BEV_SUBMAP_SEARCH_GRID_MAX: the largest cap of cells per axis of set_submap_search_grid
+PAIR_SEARCH_GRID_MAX = 1024  # BEV_PAIR_SEARCH_GRID_MAX: the largest cap of cells per axis of set_pair_search_grid
 SUBMAP_REG_MAX_TARGET = 1 << 22  # BEV_SUBMAP_REG_MAX_TARGET: records of one map's entries' frames together (submap_registration_*)
 
 # every symbol include/bev_mi355x.h declares
@@ -104,6 +105,7 @@ ABI_SYMBOLS = [
     "bev_submap_top_part_cloud_device_resident", "bev_submap_top_part_coarse_registration_device_resident",
     "bev_submap_top_part_max_out",
     "bev_set_submap_search_grid", "bev_debug_get_submap_grid",
+    "bev_set_pair_search_grid", "bev_debug_get_pair_grid",
 ]
 
 # registration front end (include/bev_mi355x.h): pcl::PointXYZ, pcl::Normal, pcl::PointNormal as float rows
@@ -272,6 +274,9 @@ def load_lib() -> C.CDLL:
     if hasattr(lib, "bev_set_submap_search_grid"):
         lib.bev_set_submap_search_grid.argtypes = [vp, i32, i32]
         lib.bev_debug_get_submap_grid.argtypes = [vp, i32, i32, i32, vp]
+    if hasattr(lib, "bev_set_pair_search_grid"):
+        lib.bev_set_pair_search_grid.argtypes = [vp, i32, i32]
+        lib.bev_debug_get_pair_grid.argtypes = [vp, i32, i32, i32, vp]
     _lib = lib
     return lib
 
@@ -913,6 +918,21 @@ class BevContext:
         out = np.zeros((n, 4), dtype=np.uint32)
         self._check(self.lib.bev_debug_get_submap_grid(self._h, int(coarse), int(first), int(n), _ptr(out)),
                     "bev_debug_get_submap_grid")
+        return out
+
+    def set_pair_search_grid(self, fine: int, coarse: int):
+        """The cap of cells per axis of the targets' search grids in the fine and the coarse PAIR calls made from now on
+        (icp_point_to_point, fine_registration*; icp_point_to_plane, coarse_registration*): 0 the grids of always (128 and 64 at
+        most), 1 .. PAIR_SEARCH_GRID_MAX grids sized to the cloud (bev_set_pair_search_grid).  Results do not
+        depend on it; the scan-to-map calls do not read it."""
+        self._check(self.lib.bev_set_pair_search_grid(self._h, int(fine), int(coarse)), "bev_set_pair_search_grid")
+
+    def debug_pair_grid(self, coarse: int, first: int, n: int) -> np.ndarray:
+        """Test hook (synchronises): (n, 4) uint32 rows {nx, ny, searchable points, largest count of one cell} of the grids of
+        the targets of matches first .. first + n - 1 of the last fine (coarse = 0) or coarse (1) pair call."""
+        out = np.zeros((max(n, 0), 4), dtype=np.uint32)
+        self._check(self.lib.bev_debug_get_pair_grid(self._h, int(coarse), int(first), int(n), _ptr(out)),
+                    "bev_debug_get_pair_grid")
         return out
 
     # ---- measurement / test hooks ------------------------------------------

@@ -637,6 +637,7 @@ int bevh::begin_call(bev_ctx *c, bool staging)
 
 int DevBuf::grow(bev_ctx *c, size_t need)
 {
+    ++uses;
     if (need <= cap) return BEV_OK;
     /* the last call's kernels may still use the buffer: this wait is what makes reuse safe across unsynchronised calls */
     HIPCK(c, hipStreamSynchronize(c->stream));

@@ -14,6 +14,7 @@
 #include "bev_reg_host.h"
 
 #include "bev_libm_f64.h"
+#include "bev_pair_grid_plan.h"
 
 using namespace bevk;
 using namespace bevh;
@@ -82,6 +83,69 @@ int rf_chain(bev_ctx *c, const RfIn &in, int nf, float leaf, float radius, const
     }
     HIPCK(c, hipGetLastError());
     return BEV_OK;
+}
+
+/* ---- search grids sized to the cloud (bev_set_pair_search_grid; bev_pair_grid.h, bev_pair_grid_plan.h) ---- */
+
+/* what a stage's cap D > 0 adds to its call: the layout, the host's tables of the targets and, behind pair_grid_work and
+ * table_up, where the pieces lie on the device */
+struct PairGrid {
+    int cap = 0;
+    size_t targets = 0;
+    bevpair::Layout l;
+    std::vector<bevsubreg::Map> maps; /* a target's first point, its slot (fine) or frame (coarse) */
+    std::vector<uint64_t> cell0;      /* its first counter inside its build group */
+    uint32_t *off = nullptr;          /* [targets][l.off_words] */
+    SubmapGridWork gw{};              /* cnt, part_bounds, part_sum: one build group's */
+    SubvoxHdr *vh = nullptr;          /* [targets] */
+    void *d_maps = nullptr, *d_cell0 = nullptr;
+};
+/* the tables of `targets` targets of one capacity; target t's points begin at first[t] * capacity, first[t] its slot or frame */
+template <class First>
+void pair_grid_plan(PairGrid &g, int cap, size_t targets, size_t capacity, First first)
+{
+    g.cap = cap;
+    g.targets = targets;
+    g.l = bevpair::layout(targets, capacity, cap);
+    if (!cap) return;
+    for (size_t t = 0; t < targets; ++t) {
+        g.maps.push_back(bevsubreg::Map{(uint64_t)first(t) * capacity, (uint32_t)first(t), 0u});
+        g.cell0.push_back(bevpair::cell0(t, g.l));
+    }
+}
+/* the grids of the call's targets, one build group behind the other on the context's stream: the point counts, then §6s's six
+ * steps per group over zeroed counters.  hdr, sorted: the stage's own arrays; the points: recs (fine) or rows (coarse) */
+int pair_grid_build(bev_ctx *c, PairGrid &g, IcpGridHdr *hdr, float4 *sorted, const uint32_t *vox_n, const uint32_t *counts,
+                    size_t stride, const bev_point_t *recs, const float *rows)
+{
+    {
+        ProfScope ps(c, K_PAIRGRID_DESC, (int)g.targets);
+        launch_pairgrid_desc(g.d_maps, (int)g.targets, vox_n, counts, stride, g.vh, c->stream);
+    }
+    g.gw.sorted = sorted;
+    g.gw.cell0 = static_cast<const uint64_t *>(g.d_cell0);
+    for (const bevpair::Group &gr : bevpair::groups(g.targets, g.l)) {
+        g.gw.hdr = hdr + gr.t0;
+        g.gw.off = g.off + (size_t)gr.t0 * g.l.off_words;
+        HIPCK(c, hipMemsetAsync(g.gw.cnt, 0, (size_t)gr.n * g.l.off_words * 4, c->stream));
+        for (int step = 0; step < 6; ++step) {
+            ProfScope ps(c, K_SUBMAP_GRID_BOUNDS + step, (int)gr.n);
+            launch_pair_grid(step, g.d_maps, gr.t0, (int)gr.n, g.l.parts, g.l.tiles, g.cap, g.vh + gr.t0, recs, rows, g.gw, c->stream);
+        }
+    }
+    return BEV_OK;
+}
+/* what bev_debug_get_pair_grid reads of a call of n_matches matches, match m's first problem being probs[m * per_match] */
+template <class Problem>
+void pair_grid_record(PairGridRecord &r, const DevBuf &buf, const IcpGridHdr *hdr, const uint32_t *cell_off, uint64_t off_words,
+                      const std::vector<Problem> &probs, size_t per_match)
+{
+    r = PairGridRecord{};
+    r.uses = buf.uses;
+    r.hdr = hdr;
+    r.cell_off = cell_off;
+    r.off_words = off_words;
+    for (size_t m = 0; m * per_match < probs.size(); ++m) r.match_slot.push_back(probs[m * per_match].tgt_slot);
 }
 
 } // namespace
@@ -255,31 +319,45 @@ bev_icp_params_t bev_icp_coarse_defaults(void)
 namespace {
 
 /* the grids of the target frames slot_frames, then every problem (launches of kIcpProblemsPerLaunch), then, when d_best is
- * set, the better guess of each of the n_best matches; all on the context's stream */
-int icp_launch(bev_ctx *c, const float *d_pn, size_t stride, const uint32_t *d_counts,
-               const std::vector<IcpProblem> &probs, const std::vector<uint32_t> &slot_frames,
-               const bev_icp_params_t &prm, bev_icp_result_t *d_res, int n_best, int32_t *d_best)
+ * set, the better guess of each of the n_best matches; all on the context's stream.  per_match: problems of a match (the hook's
+ * record); cap: the stage's search grid cap, 0 the fixed grids; n_frames: the frames behind d_pn (read under a cap only) */
+int icp_launch(bev_ctx *c, const float *d_pn, size_t stride, const uint32_t *d_counts, size_t n_frames,
+               const std::vector<IcpProblem> &probs, size_t per_match, const std::vector<uint32_t> &slot_frames,
+               const bev_icp_params_t &prm, bev_icp_result_t *d_res, int n_best, int32_t *d_best, int cap)
 {
     const size_t U = slot_frames.size(), P = probs.size(), L = std::min(P, (size_t)kIcpProblemsPerLaunch);
     IcpWork w{};
-    const size_t sz[] = {U * sizeof(IcpGridHdr), U * 4 * (size_t)(kIcpCells + 1), U * 16 * stride, L * 16 * stride};
-    void **const dst[] = {(void **)&w.hdr, (void **)&w.cell_off, (void **)&w.sorted, (void **)&w.cur};
+    PairGrid g;
+    pair_grid_plan(g, cap, U, stride, [&](size_t t) { return slot_frames[t]; });
+    float4 *by_frame = nullptr; /* under a cap the searchable points lie by FRAME: the build writes them where it reads */
+    const size_t sz[] = {U * sizeof(IcpGridHdr), cap ? 0 : U * 4 * (size_t)(kIcpCells + 1), cap ? 0 : U * 16 * stride, L * 16 * stride,
+                         g.l.off_bytes, cap ? n_frames * 16 * stride : 0, g.l.cnt_bytes, g.l.bounds_bytes, g.l.sums_bytes,
+                         g.l.hdr_bytes};
+    void **const dst[] = {(void **)&w.hdr, (void **)&w.cell_off, (void **)&w.sorted, (void **)&w.cur, (void **)&g.off,
+                          (void **)&by_frame, (void **)&g.gw.cnt, (void **)&g.gw.part_bounds, (void **)&g.gw.part_sum, (void **)&g.vh};
     BEVCK(c->reg.icp_buf.grow(c, carve(nullptr, sz, dst)));
     carve(c->reg.icp_buf.p, sz, dst);
     IcpProblem *d_probs;
     uint32_t *d_slots;
-    const size_t tsz[] = {P * sizeof(IcpProblem), U * 4};
-    const void *const tsrc[] = {probs.data(), slot_frames.data()};
-    void **const tdst[] = {(void **)&d_probs, (void **)&d_slots};
+    const size_t tsz[] = {P * sizeof(IcpProblem), U * 4, g.l.map_bytes, g.l.cell0_bytes};
+    const void *const tsrc[] = {probs.data(), slot_frames.data(), g.maps.data(), g.cell0.data()};
+    void **const tdst[] = {(void **)&d_probs, (void **)&d_slots, &g.d_maps, &g.d_cell0};
     BEVCK(table_up(c, c->reg.icp_tab, tsz, tsrc, tdst));
-    {
+    if (cap) {
+        w.cell_off = g.off;
+        w.sorted = by_frame;
+        BEVCK(pair_grid_build(c, g, w.hdr, w.sorted, nullptr, d_counts, stride, nullptr, d_pn));
+    } else {
         ProfScope ps(c, K_ICP_GRID, (int)U);
         launch_icp_grid(d_pn, stride, d_counts, d_slots, (int)U, w, c->stream);
     }
+    pair_grid_record(c->pair_grid_rec[1], c->reg.icp_buf, w.hdr, w.cell_off, cap ? g.l.off_words : (uint64_t)kIcpCells + 1, probs,
+                     per_match);
     for (size_t p0 = 0; p0 < P; p0 += kIcpProblemsPerLaunch) {
         const int n = (int)std::min((size_t)kIcpProblemsPerLaunch, P - p0);
-        ProfScope ps(c, K_ICP, n);
-        launch_icp(d_pn, stride, d_counts, d_probs + p0, n, w, prm, d_res, c->stream);
+        ProfScope ps(c, cap ? K_ICP_WIDE : K_ICP, n);
+        if (cap) launch_icp_wide(d_pn, stride, d_counts, d_probs + p0, n, w, g.l.off_words, prm, d_res, c->stream);
+        else launch_icp(d_pn, stride, d_counts, d_probs + p0, n, w, prm, d_res, c->stream);
     }
     if (d_best) {
         ProfScope ps(c, K_ICP_BEST, n_best);
@@ -314,7 +392,7 @@ int bev_icp_point_to_plane(bev_ctx_t *c, const float *src, uint32_t n_src, const
     probs[0].tgt_slot = 0;
     probs[0].result = 0;
     guess_or_identity(guess16, probs[0].guess);
-    BEVCK(icp_launch(c, d_pn, stride, d_counts, probs, std::vector<uint32_t>{1u}, prm, d_res, 0, nullptr));
+    BEVCK(icp_launch(c, d_pn, stride, d_counts, 2, probs, 1, std::vector<uint32_t>{1u}, prm, d_res, 0, nullptr, c->pair_grid_cap[1]));
     HIPCK(c, hipMemcpyAsync(result, d_res, sizeof(bev_icp_result_t), hipMemcpyDeviceToHost, c->stream));
     HIPCK(c, hipStreamSynchronize(c->stream));
     return BEV_OK;
@@ -352,7 +430,8 @@ int bev_coarse_registration_device_resident(bev_ctx_t *c, int n_frames, const vo
             bevx::icp_tool_guess(mt.angle_guess, g, pb.guess);
         }
     }
-    BEVCK(icp_launch(c, static_cast<const float *>(d_pn), stride, d_counts, probs, slot_frames, prm, d_results, n_matches, d_best));
+    BEVCK(icp_launch(c, static_cast<const float *>(d_pn), stride, d_counts, (size_t)n_frames, probs, 2, slot_frames, prm, d_results,
+                     n_matches, d_best, c->pair_grid_cap[1]));
     return record_tail(c);
 }
 
@@ -380,38 +459,48 @@ bev_icp_params_t bev_icp_whole_defaults(void)
 namespace {
 
 /* the device workspace for U slots of at most Pn records and P problems (grown when a call needs more), the slot and
- * problem tables uploaded behind everything on the context's stream */
+ * problem tables uploaded behind everything on the context's stream.  cap: the stage's search grid cap (0: the fixed grids, the
+ * layout of always); under a cap the first T slots are the call's targets, and g gets their grids' pieces and tables */
 int fine_setup(bev_ctx *c, size_t U, size_t Pn, const std::vector<FineSlot> &slots, const std::vector<FineProblem> &probs,
-               FineWork &w, const FineSlot **d_slots, const FineProblem **d_probs)
+               FineWork &w, const FineSlot **d_slots, const FineProblem **d_probs, int cap, size_t T, PairGrid &g)
 {
     const size_t P = probs.size(), G = std::min(U, (size_t)kFineVoxelGroup), L = std::min(P, (size_t)kFineProblemsPerLaunch);
     const size_t Kn = pow2_at_least(Pn);
     w = FineWork{};
+    pair_grid_plan(g, cap, T, Pn, [](size_t t) { return t; });
     const size_t sz[] = {U * Pn * sizeof(bev_point_t), U * 4, G * Kn * 8, G * (Pn + 1) * 4, U * sizeof(IcpGridHdr),
-                         U * 4 * (size_t)(kFineCells + 1), U * Pn * 16, L * Pn * 16, L * Pn * 4};
+                         cap ? 0 : U * 4 * (size_t)(kFineCells + 1), U * Pn * 16, L * Pn * 16, L * Pn * 4,
+                         g.l.off_bytes, g.l.cnt_bytes, g.l.bounds_bytes, g.l.sums_bytes, g.l.hdr_bytes};
     void **const dst[] = {(void **)&w.vox, (void **)&w.vox_n, (void **)&w.keys, (void **)&w.vstart, (void **)&w.hdr,
-                          (void **)&w.cell_off, (void **)&w.sorted, (void **)&w.cur, (void **)&w.corr};
+                          (void **)&w.cell_off, (void **)&w.sorted, (void **)&w.cur, (void **)&w.corr,
+                          (void **)&g.off, (void **)&g.gw.cnt, (void **)&g.gw.part_bounds, (void **)&g.gw.part_sum, (void **)&g.vh};
     BEVCK(c->reg.fine_buf.grow(c, carve(nullptr, sz, dst)));
     carve(c->reg.fine_buf.p, sz, dst);
+    if (cap) w.cell_off = g.off;
     w.Pn = Pn;
     w.Kn = Kn;
-    const size_t tsz[] = {slots.size() * sizeof(FineSlot), P * sizeof(FineProblem)};
-    const void *const tsrc[] = {slots.data(), probs.data()};
-    void **const tdst[] = {(void **)d_slots, (void **)d_probs};
+    const size_t tsz[] = {slots.size() * sizeof(FineSlot), P * sizeof(FineProblem), g.l.map_bytes, g.l.cell0_bytes};
+    const void *const tsrc[] = {slots.data(), probs.data(), g.maps.data(), g.cell0.data()};
+    void **const tdst[] = {(void **)d_slots, (void **)d_probs, &g.d_maps, &g.d_cell0};
     return table_up(c, c->reg.fine_tab, tsz, tsrc, tdst);
 }
 
+/* the grids, then the problems in launches of kFineProblemsPerLaunch.  g.cap == 0: a grid for every one of the U slots, as ever;
+ * else the wide grids of the targets alone */
 int fine_icp(bev_ctx *c, int U, const FineProblem *d_probs, size_t P, const FineWork &w, const bev_icp_result_t *d_coarse,
-             const int32_t *d_best, const bev_icp_params_t &prm, bev_icp_result_t *d_res)
+             const int32_t *d_best, const bev_icp_params_t &prm, bev_icp_result_t *d_res, PairGrid &g)
 {
-    {
+    if (g.cap) {
+        BEVCK(pair_grid_build(c, g, w.hdr, w.sorted, w.vox_n, nullptr, w.Pn, w.vox, nullptr));
+    } else {
         ProfScope ps(c, K_FINE_GRID, U);
         launch_fine_grid(U, w, c->stream);
     }
     for (size_t p0 = 0; p0 < P; p0 += kFineProblemsPerLaunch) {
         const int n = (int)std::min((size_t)kFineProblemsPerLaunch, P - p0);
-        ProfScope ps(c, K_FINE_ICP, n);
-        launch_fine_icp(d_probs + p0, n, w, d_coarse, d_best, prm, d_res, c->stream);
+        ProfScope ps(c, g.cap ? K_FINE_ICP_WIDE : K_FINE_ICP, n);
+        if (g.cap) launch_fine_icp_wide(d_probs + p0, n, w, g.l.off_words, d_coarse, d_best, prm, d_res, c->stream);
+        else launch_fine_icp(d_probs + p0, n, w, d_coarse, d_best, prm, d_res, c->stream);
     }
     HIPCK(c, hipGetLastError());
     return BEV_OK;
@@ -430,7 +519,8 @@ int bev_voxel_grid_irct(bev_ctx_t *c, const bev_point_t *cloud, uint32_t n, floa
     FineWork w;
     const FineSlot *d_slots;
     const FineProblem *d_probs;
-    BEVCK(fine_setup(c, 1, n, std::vector<FineSlot>{FineSlot{0, n, 0}}, std::vector<FineProblem>{}, w, &d_slots, &d_probs));
+    PairGrid none;
+    BEVCK(fine_setup(c, 1, n, std::vector<FineSlot>{FineSlot{0, n, 0}}, std::vector<FineProblem>{}, w, &d_slots, &d_probs, 0, 0, none));
     BEVCK(fine_voxel(c, static_cast<const bev_point_t *>(c->reg.fine_in.p), d_slots, 1, w, leaf));
     uint32_t nv = 0;
     HIPCK(c, hipMemcpyAsync(&nv, w.vox_n, 4, hipMemcpyDeviceToHost, c->stream));
@@ -447,23 +537,29 @@ int bev_icp_point_to_point(bev_ctx_t *c, const bev_point_t *src, uint32_t n_src,
     if (!c || !result || (n_src && !src) || (n_tgt && !tgt) || !icp_params_ok(prm)) return BEV_ERR_INVALID_ARG;
     BEVCK(begin_call(c, false));
     const size_t Pn = std::max<size_t>(std::max(n_src, n_tgt), 1);
+    const int cap = c->pair_grid_cap[0];
+    const uint32_t ts = cap ? 0u : 1u, ss = 1u - ts; /* under a cap the targets are the first slots */
     std::vector<FineProblem> probs(1);
-    probs[0].src_slot = 0;
-    probs[0].tgt_slot = 1;
+    probs[0].src_slot = ss;
+    probs[0].tgt_slot = ts;
     probs[0].result = 0;
     probs[0].coarse_match = 0xffffffffu;
     guess_or_identity(guess16, probs[0].guess);
     FineWork w;
     const FineSlot *d_slots;
     const FineProblem *d_probs;
-    BEVCK(fine_setup(c, 2, Pn, std::vector<FineSlot>{}, probs, w, &d_slots, &d_probs));
-    /* the clouds are the "voxel clouds" of slots 0 and 1; the result goes behind them in the sort scratch */
-    const uint32_t counts[2] = {n_src, n_tgt};
-    if (n_src) HIPCK(c, hipMemcpyAsync(w.vox, src, (size_t)n_src * sizeof(bev_point_t), hipMemcpyHostToDevice, c->stream));
-    if (n_tgt) HIPCK(c, hipMemcpyAsync(w.vox + Pn, tgt, (size_t)n_tgt * sizeof(bev_point_t), hipMemcpyHostToDevice, c->stream));
+    PairGrid g;
+    BEVCK(fine_setup(c, 2, Pn, std::vector<FineSlot>{}, probs, w, &d_slots, &d_probs, cap, 1, g));
+    /* the clouds are the "voxel clouds" of the two slots; the result goes behind them in the sort scratch */
+    uint32_t counts[2];
+    counts[ss] = n_src;
+    counts[ts] = n_tgt;
+    if (n_src) HIPCK(c, hipMemcpyAsync(w.vox + ss * Pn, src, (size_t)n_src * sizeof(bev_point_t), hipMemcpyHostToDevice, c->stream));
+    if (n_tgt) HIPCK(c, hipMemcpyAsync(w.vox + ts * Pn, tgt, (size_t)n_tgt * sizeof(bev_point_t), hipMemcpyHostToDevice, c->stream));
     HIPCK(c, hipMemcpyAsync(w.vox_n, counts, sizeof(counts), hipMemcpyHostToDevice, c->stream));
     bev_icp_result_t *d_res = reinterpret_cast<bev_icp_result_t *>(w.keys);
-    BEVCK(fine_icp(c, 2, d_probs, 1, w, nullptr, nullptr, prm, d_res));
+    BEVCK(fine_icp(c, 2, d_probs, 1, w, nullptr, nullptr, prm, d_res, g));
+    pair_grid_record(c->pair_grid_rec[0], c->reg.fine_buf, w.hdr, w.cell_off, cap ? g.l.off_words : (uint64_t)kFineCells + 1, probs, 1);
     HIPCK(c, hipMemcpyAsync(result, d_res, sizeof(bev_icp_result_t), hipMemcpyDeviceToHost, c->stream));
     HIPCK(c, hipStreamSynchronize(c->stream));
     return BEV_OK;
@@ -499,6 +595,11 @@ int bev_fine_registration_device_resident(bev_ctx_t *c, int n_frames, const bev_
         }
         return (uint32_t)slot_of[f];
     };
+    /* under a cap the targets come first: their grids are built over the slots [0, T) and no others.  Which slot a frame gets
+     * changes no result */
+    const int cap = c->pair_grid_cap[0];
+    for (int m = 0; cap && m < n_matches; ++m) slot(h_matches[m].match_idx);
+    const size_t T = slots.size();
     std::vector<FineProblem> probs((size_t)n_matches);
     for (int m = 0; m < n_matches; ++m) {
         const bev_match_t &mt = h_matches[m];
@@ -513,10 +614,49 @@ int bev_fine_registration_device_resident(bev_ctx_t *c, int n_frames, const bev_
     FineWork w;
     const FineSlot *d_slots;
     const FineProblem *d_probs;
-    BEVCK(fine_setup(c, (size_t)U, Pn, slots, probs, w, &d_slots, &d_probs));
+    PairGrid g;
+    BEVCK(fine_setup(c, (size_t)U, Pn, slots, probs, w, &d_slots, &d_probs, cap, T, g));
     BEVCK(fine_voxel(c, d_clouds, d_slots, U, w, leaf));
-    BEVCK(fine_icp(c, U, d_probs, probs.size(), w, d_coarse, d_best, prm, d_results));
+    BEVCK(fine_icp(c, U, d_probs, probs.size(), w, d_coarse, d_best, prm, d_results, g));
+    pair_grid_record(c->pair_grid_rec[0], c->reg.fine_buf, w.hdr, w.cell_off, cap ? g.l.off_words : (uint64_t)kFineCells + 1, probs, 1);
     return record_tail(c);
+}
+
+/* ---- search grids sized to the cloud (bev_pair_grid.h) ---------------------------------------------------- */
+int bev_set_pair_search_grid(bev_ctx_t *c, int fine_dim, int coarse_dim)
+{
+    static_assert(BEV_PAIR_SEARCH_GRID_MAX == bevpair::kGridCapMax, "one cap");
+    if (!c || fine_dim < 0 || fine_dim > BEV_PAIR_SEARCH_GRID_MAX || coarse_dim < 0 || coarse_dim > BEV_PAIR_SEARCH_GRID_MAX)
+        return BEV_ERR_INVALID_ARG;
+    c->pair_grid_cap[0] = fine_dim;
+    c->pair_grid_cap[1] = coarse_dim;
+    return BEV_OK;
+}
+
+int bev_debug_get_pair_grid(bev_ctx_t *c, int coarse, int first_match, int n_matches, uint32_t *out)
+{
+    if (!c || (coarse != 0 && coarse != 1) || first_match < 0 || n_matches < 0 || !out) return BEV_ERR_INVALID_ARG;
+    const PairGridRecord &r = c->pair_grid_rec[coarse];
+    if (!r.hdr || (size_t)first_match + (size_t)n_matches > r.match_slot.size()) return BEV_ERR_INVALID_ARG;
+    if (r.uses != (coarse ? c->reg.icp_buf : c->reg.fine_buf).uses) return BEV_ERR_INVALID_ARG; /* a later call laid it out anew */
+    BEVCK(begin_call(c, false));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    std::vector<uint32_t> off;
+    for (int i = 0; i < n_matches; ++i) {
+        const uint32_t slot = r.match_slot[(size_t)(first_match + i)];
+        IcpGridHdr h;
+        HIPCK(c, hipMemcpy(&h, r.hdr + slot, sizeof h, hipMemcpyDeviceToHost));
+        if (h.nx < 1 || h.ny < 1 || (uint64_t)h.nx * (uint64_t)h.ny + 1 > r.off_words) return BEV_ERR_INVALID_ARG; /* (not a grid) */
+        off.resize((size_t)h.nx * (size_t)h.ny + 1);
+        HIPCK(c, hipMemcpy(off.data(), r.cell_off + (size_t)slot * r.off_words, off.size() * 4, hipMemcpyDeviceToHost));
+        uint32_t largest = 0;
+        for (size_t k = 0; k + 1 < off.size(); ++k) largest = std::max(largest, off[k + 1] - off[k]);
+        out[4 * i] = (uint32_t)h.nx;
+        out[4 * i + 1] = (uint32_t)h.ny;
+        out[4 * i + 2] = h.n;
+        out[4 * i + 3] = largest;
+    }
+    return BEV_OK;
 }
 
 } /* extern "C" */

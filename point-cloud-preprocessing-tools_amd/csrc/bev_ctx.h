@@ -118,6 +118,7 @@ struct Downloader {
 struct DevBuf {
     void *p = nullptr;
     size_t cap = 0;
+    uint64_t uses = 0; /* calls of grow: every call that lays the buffer out anew (PairGridRecord) */
     int grow(bev_ctx *c, size_t need); /* (waits for the context's stream first: the last call's kernels may still use it) */
     void release();
 };
@@ -165,6 +166,16 @@ struct SubmapGridRecord {
     const uint32_t *cell_off = nullptr;
     std::vector<uint64_t> off0;       /* a map's first offset word behind cell_off */
     std::vector<uint64_t> cells;      /* the cells its offsets have room for */
+};
+
+/* what bev_debug_get_pair_grid reads: the search grids of the targets of the last pair call of a stage, in that stage's
+ * workspace (uses: DevBuf::uses behind the call's own grow; the record holds while no later call has laid the buffer out) */
+struct PairGridRecord {
+    uint64_t uses = 0;
+    const IcpGridHdr *hdr = nullptr;    /* [the call's slots] */
+    const uint32_t *cell_off = nullptr; /* a slot's offsets at slot * off_words */
+    uint64_t off_words = 0;
+    std::vector<uint32_t> match_slot;   /* the target slot of every match of the call */
 };
 
 } // namespace bevh
@@ -260,6 +271,9 @@ struct bev_ctx {
      * 0: the one-workgroup grids of 128 x 128 and 64 x 64 cells at most.  [0] fine, [1] coarse, as the records of the hook */
     int submap_grid_cap[2] = {0, 0};
     bevh::SubmapGridRecord submap_grid_rec[2];
+    /* bev_set_pair_search_grid: the same for the pair calls' targets; neither setter reads the other's state */
+    int pair_grid_cap[2] = {0, 0};
+    bevh::PairGridRecord pair_grid_rec[2];
     int posed_group = 0; /* BEV_POSED_GROUP=1 .. 65535: grids per launch group (tests: results do not depend on it); 0: what fits kPosedWsCap */
 
     bevh::RegState reg;

@@ -255,6 +255,9 @@ enum KernelId {
     K_SUBMAP_GRID_SCATTER, /* ... the searchable points by cell */
     K_SUBMAP_ICP_WIDE,        /* K_SUBMAP_ICP against such a grid */
     K_SUBMAP_COARSE_ICP_WIDE, /* K_SUBMAP_COARSE_ICP against such a grid, its offsets in global memory */
+    K_PAIRGRID_DESC, /* the pair calls' search grids sized to the cloud (bev_pair_grid.h): the targets' point counts */
+    K_FINE_ICP_WIDE, /* K_FINE_ICP against such a grid */
+    K_ICP_WIDE,      /* K_ICP against such a grid, its offsets in global memory */
     K_COUNT
 };
 const char *kernel_name(int id);
@@ -624,6 +627,22 @@ void launch_submap_icp_wide(const FineProblem *probs, int n, const void *maps, u
 void launch_submap_coarse_icp_wide(const float *pn, size_t stride, const uint32_t *counts, const IcpProblem *probs, int n,
                                    const void *maps, uint32_t map0, const SubmapCoarseWork &t, const uint64_t *cell0,
                                    const bev_icp_params_t &prm, bev_icp_result_t *results, hipStream_t st);
+
+/* ---- the pair calls' search grids sized to the cloud (bev_pair_grid.h, bev_pair_grid_plan.h) ----
+ * maps: the host's table of the call's targets (bevsubreg::Map: pt0 the target's first point, ent0 its slot or frame); the build
+ * is §6s's over the n targets from t0 on, w's hdr and off pointing at target t0's, w.cell0 at the table of first counters */
+/* the targets' point counts into vh: vox_n[t] (fine), or min(counts[ent0], stride) */
+void launch_pairgrid_desc(const void *maps, int n, const uint32_t *vox_n, const uint32_t *counts, size_t stride, SubvoxHdr *vh,
+                          hipStream_t st);
+/* launch_submap_grid over targets: their points are recs (32-byte records) or, recs == nullptr, PointNormal rows */
+void launch_pair_grid(int step, const void *maps, uint32_t t0, int n, uint32_t parts, uint32_t tiles, int cap, const SubvoxHdr *vh,
+                      const bev_point_t *recs, const float *rows, const SubmapGridWork &w, hipStream_t st);
+/* launch_fine_icp and launch_icp with w.cell_off the wide table: a slot's offsets at slot * off_words; launch_icp_wide reads
+ * w.sorted by FRAME */
+void launch_fine_icp_wide(const FineProblem *probs, int n, const FineWork &w, uint64_t off_words, const bev_icp_result_t *coarse,
+                          const int32_t *best, const bev_icp_params_t &prm, bev_icp_result_t *results, hipStream_t st);
+void launch_icp_wide(const float *pn, size_t stride, const uint32_t *counts, const IcpProblem *probs, int n, const IcpWork &w,
+                     uint64_t off_words, const bev_icp_params_t &prm, bev_icp_result_t *results, hipStream_t st);
 
 /* opt in to > 64 KiB of dynamic LDS for the kernels that need it */
 hipError_t configure_kernels(const Geometry &g);

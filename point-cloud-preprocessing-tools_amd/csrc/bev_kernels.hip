@@ -51,6 +51,7 @@
 #include "bev_submap_pn_vox.h"
 #include "bev_submap_top.h"
 #include "bev_submap_grid.h"
+#include "bev_pair_grid.h"
 
 using namespace bevx;
 
@@ -71,6 +72,7 @@ static const char *const kNames[K_COUNT] = {
     "k_submap_top_overflow",
     "k_subgrid_bounds", "k_subgrid_header", "k_subgrid_count", "k_subgrid_sums", "k_subgrid_scan", "k_subgrid_scatter",
     "k_submap_icp_wide", "k_submap_coarse_icp_wide",
+    "k_pairgrid_desc", "k_fine_icp_wide", "k_icp_wide",
 };
 const char *kernel_name(int id) { return (id >= 0 && id < K_COUNT) ? kNames[id] : "?"; }
 

@@ -16,6 +16,12 @@
  * "[TIME] Avg Tiempo" lines are the chain's wall time per match in ms (coarse: file reading excluded, front end and
  * coarse ICP; fine: the fine stage), not the reference's per-match stopwatch; an unreadable file ends the tool with exit
  * status 1 before anything is written to the report.
+ *
+ * BEV_PAIR_SEARCH_GRID=<fine>[,<coarse>] in the environment (both tools): the cap of cells per axis of the targets'
+ * search grids in the fine and the coarse stage, handed to bev_set_pair_search_grid before the first chunk; a single number sets
+ * both stages.  Integers 0 ... 1024; unset, empty or 0: the grids, the launches and the output as ever.  The output does not
+ * depend on it.  Anything else: exit 1 with "BEV_PAIR_SEARCH_GRID '<text>': expected <fine>[,<coarse>], integers 0 ... 1024" and
+ * the usage line, before any GPU work.
  */
 #include <cstdio>
 #include <cstdlib>
@@ -26,6 +32,7 @@
 #include "BatchMultiBevGen.h"
 #include "Registration.h"
 #include "RegistrationChain.h"
+#include "SearchGridEnv.h"
 #include "Utility.h"
 
 #ifndef BEV_WHOLE_TOOL
@@ -36,6 +43,8 @@ namespace {
 
 constexpr bool kTopPart = !BEV_WHOLE_TOOL;
 const char *const kTool = kTopPart ? "batch_top_part_registration" : "batch_whole_registration";
+
+void usage() { std::cerr << "Usage: " << kTool << " <match_list> <pcd_dir> [max_frames]\n"; }
 
 std::string cloud_path(const std::string &dir, long idx)
 {
@@ -49,9 +58,17 @@ std::string cloud_path(const std::string &dir, long idx)
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        std::cerr << "Usage: " << kTool << " <match_list> <pcd_dir> [max_frames]\n";
+        usage();
         return 1;
     }
+    int search_grid[2] = {0, 0};
+    if (const char *env = std::getenv("BEV_PAIR_SEARCH_GRID"))
+        if (*env && !parse_search_grid(env, BEV_PAIR_SEARCH_GRID_MAX, search_grid)) {
+            std::cerr << "BEV_PAIR_SEARCH_GRID '" << env << "': expected <fine>[,<coarse>], integers 0 ... " << BEV_PAIR_SEARCH_GRID_MAX
+                      << "\n";
+            usage();
+            return 1;
+        }
     const std::string match_list(argv[1]), pcd_dir(argv[2]);
     const int max_frames = argc > 3 ? std::atoi(argv[3]) : 256;
     if (max_frames < 2) {
@@ -70,6 +87,10 @@ int main(int argc, char **argv)
     sensor_params_ = getSensorParams(parseSensorType("HDL_64E"));
     const bev_icp_params_t fine_prm = kTopPart ? bev_icp_fine_defaults() : bev_icp_whole_defaults();
     regchain::Tally tally(&report, kTopPart ? regchain::ReportAgainst::ChosenCoarse : regchain::ReportAgainst::Nothing);
+    if (search_grid[0] || search_grid[1]) {
+        bev_ctx_t *ctx = bevhost_context();
+        if (!ctx || bev_set_pair_search_grid(ctx, search_grid[0], search_grid[1]) != BEV_OK) return 2;
+    }
     for (size_t m0 = 0; m0 < matches.size();) {
         /* the indices are file numbers: a window of the number alone, nothing to clip */
         const regchain::Chunk chunk =

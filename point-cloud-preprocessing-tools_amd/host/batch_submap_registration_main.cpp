@@ -59,6 +59,7 @@
 
 #include "Registration.h"
 #include "RegistrationChain.h"
+#include "SearchGridEnv.h"
 #include "SubmapWindows.h"
 
 #ifndef BEV_SUBMAP_TOP_PART
@@ -81,25 +82,6 @@ bool parse_map_leaf(const char *s, float *out)
     if (end == s || *end != '\0' || !std::isfinite(v) || v < 0.0f) return false;
     *out = v;
     return true;
-}
-
-/* "<fine>[,<coarse>]": one or two integers 0 ... BEV_SUBMAP_SEARCH_GRID_MAX and nothing else; one number sets both */
-bool parse_search_grid(const char *s, int dims[2])
-{
-    for (int k = 0; k < 2; ++k) {
-        if (*s < '0' || *s > '9') return false; /* (strtol would take a sign or blanks) */
-        char *end = nullptr;
-        const long v = std::strtol(s, &end, 10);
-        if (v > BEV_SUBMAP_SEARCH_GRID_MAX) return false;
-        dims[k] = (int)v;
-        if (*end == '\0') {
-            if (k == 0) dims[1] = dims[0];
-            return true;
-        }
-        if (*end != ',' || k == 1) return false;
-        s = end + 1;
-    }
-    return false;
 }
 
 } // namespace
@@ -131,7 +113,7 @@ int main(int argc, char **argv)
         }
     int search_grid[2] = {0, 0};
     if (const char *env = std::getenv("BEV_SUBMAP_SEARCH_GRID"))
-        if (*env && !parse_search_grid(env, search_grid)) {
+        if (*env && !parse_search_grid(env, BEV_SUBMAP_SEARCH_GRID_MAX, search_grid)) {
             std::cerr << "BEV_SUBMAP_SEARCH_GRID '" << env << "': expected <fine>[,<coarse>], integers 0 ... " << BEV_SUBMAP_SEARCH_GRID_MAX
                       << "\n";
             usage();
