@@ -113,10 +113,10 @@ void pair_grid_plan(PairGrid &g, int cap, size_t targets, size_t capacity, First
         g.cell0.push_back(bevpair::cell0(t, g.l));
     }
 }
-/* the grids of the call's targets, one build group behind the other on the context's stream: the point counts, then §6s's six
- * steps per group over zeroed counters.  hdr, sorted: the stage's own arrays; the points: recs (fine) or rows (coarse) */
+/* the grids of the call's targets, one build group behind the other on the context's stream: the point counts, then the build
+ * (search_grid_build) per group.  hdr, sorted: the stage's own arrays; the points: src's records (fine) or rows (coarse) */
 int pair_grid_build(bev_ctx *c, PairGrid &g, IcpGridHdr *hdr, float4 *sorted, const uint32_t *vox_n, const uint32_t *counts,
-                    size_t stride, const bev_point_t *recs, const float *rows)
+                    size_t stride, const SubgridSource &src)
 {
     {
         ProfScope ps(c, K_PAIRGRID_DESC, (int)g.targets);
@@ -127,25 +127,26 @@ int pair_grid_build(bev_ctx *c, PairGrid &g, IcpGridHdr *hdr, float4 *sorted, co
     for (const bevpair::Group &gr : bevpair::groups(g.targets, g.l)) {
         g.gw.hdr = hdr + gr.t0;
         g.gw.off = g.off + (size_t)gr.t0 * g.l.off_words;
-        HIPCK(c, hipMemsetAsync(g.gw.cnt, 0, (size_t)gr.n * g.l.off_words * 4, c->stream));
-        for (int step = 0; step < 6; ++step) {
-            ProfScope ps(c, K_SUBMAP_GRID_BOUNDS + step, (int)gr.n);
-            launch_pair_grid(step, g.d_maps, gr.t0, (int)gr.n, g.l.parts, g.l.tiles, g.cap, g.vh + gr.t0, recs, rows, g.gw, c->stream);
-        }
+        BEVCK(search_grid_build(c, g.d_maps, gr.t0, (int)gr.n, g.l.parts, g.l.tiles, g.cap, g.vh + gr.t0, src, g.gw,
+                                (size_t)gr.n * g.l.off_words));
     }
     return BEV_OK;
 }
-/* what bev_debug_get_pair_grid reads of a call of n_matches matches, match m's first problem being probs[m * per_match] */
+/* what bev_debug_get_pair_grid reads of a call's matches, match m's first problem being probs[m * per_match]: the grid of
+ * its target slot, whose offsets lie at slot * off_words */
 template <class Problem>
-void pair_grid_record(PairGridRecord &r, const DevBuf &buf, const IcpGridHdr *hdr, const uint32_t *cell_off, uint64_t off_words,
+void pair_grid_record(bev_ctx *c, int coarse, const IcpGridHdr *hdr, const uint32_t *cell_off, uint64_t off_words,
                       const std::vector<Problem> &probs, size_t per_match)
 {
-    r = PairGridRecord{};
-    r.uses = buf.uses;
+    GridRecord &r = c->pair_grid_rec[coarse];
+    r = GridRecord{};
+    r.uses = stage_buf(c, coarse).uses;
     r.hdr = hdr;
     r.cell_off = cell_off;
-    r.off_words = off_words;
-    for (size_t m = 0; m * per_match < probs.size(); ++m) r.match_slot.push_back(probs[m * per_match].tgt_slot);
+    for (size_t m = 0; m * per_match < probs.size(); ++m) {
+        const uint64_t slot = probs[m * per_match].tgt_slot;
+        r.items.push_back({slot, slot * off_words, off_words - 1});
+    }
 }
 
 } // namespace
@@ -159,6 +160,40 @@ int bevh::fine_voxel(bev_ctx *c, const bev_point_t *d_pts, const FineSlot *d_slo
         launch_fine_voxel(d_pts, d_slots, s0, n, w, leaf, c->stream);
     }
     HIPCK(c, hipGetLastError());
+    return BEV_OK;
+}
+
+/* ---- search grids sized to the target: the build's driver and the hooks' reader (bev_reg_host.h) ---- */
+int bevh::search_grid_build(bev_ctx *c, const void *d_maps, uint32_t t0, int n, uint32_t parts, uint32_t tiles, int cap,
+                            const SubvoxHdr *vh, const SubgridSource &src, const SubmapGridWork &w, size_t clear_words)
+{
+    HIPCK(c, hipMemsetAsync(w.cnt, 0, clear_words * 4, c->stream));
+    for (int step = 0; step < 6; ++step) {
+        ProfScope ps(c, K_SUBMAP_GRID_BOUNDS + step, n);
+        launch_subgrid(step, d_maps, t0, n, parts, tiles, cap, vh, src, w, c->stream);
+    }
+    return BEV_OK;
+}
+
+int bevh::grid_record_read(bev_ctx *c, const GridRecord &r, int first, int n, uint32_t *out)
+{
+    BEVCK(begin_call(c, false));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    std::vector<uint32_t> off;
+    for (int i = 0; i < n; ++i) {
+        const GridRecord::Item &it = r.items[(size_t)(first + i)];
+        IcpGridHdr h;
+        HIPCK(c, hipMemcpy(&h, r.hdr + it.hdr, sizeof h, hipMemcpyDeviceToHost));
+        if (h.nx < 1 || h.ny < 1 || (uint64_t)h.nx * (uint64_t)h.ny > it.cells) return BEV_ERR_INVALID_ARG; /* (not a grid) */
+        off.resize((size_t)h.nx * (size_t)h.ny + 1);
+        HIPCK(c, hipMemcpy(off.data(), r.cell_off + it.off0, off.size() * 4, hipMemcpyDeviceToHost));
+        uint32_t largest = 0;
+        for (size_t k = 0; k + 1 < off.size(); ++k) largest = std::max(largest, off[k + 1] - off[k]);
+        out[4 * i] = (uint32_t)h.nx;
+        out[4 * i + 1] = (uint32_t)h.ny;
+        out[4 * i + 2] = h.n;
+        out[4 * i + 3] = largest;
+    }
     return BEV_OK;
 }
 
@@ -346,13 +381,12 @@ int icp_launch(bev_ctx *c, const float *d_pn, size_t stride, const uint32_t *d_c
     if (cap) {
         w.cell_off = g.off;
         w.sorted = by_frame;
-        BEVCK(pair_grid_build(c, g, w.hdr, w.sorted, nullptr, d_counts, stride, nullptr, d_pn));
+        BEVCK(pair_grid_build(c, g, w.hdr, w.sorted, nullptr, d_counts, stride, SubgridSource{nullptr, nullptr, d_pn}));
     } else {
         ProfScope ps(c, K_ICP_GRID, (int)U);
         launch_icp_grid(d_pn, stride, d_counts, d_slots, (int)U, w, c->stream);
     }
-    pair_grid_record(c->pair_grid_rec[1], c->reg.icp_buf, w.hdr, w.cell_off, cap ? g.l.off_words : (uint64_t)kIcpCells + 1, probs,
-                     per_match);
+    pair_grid_record(c, 1, w.hdr, w.cell_off, cap ? g.l.off_words : (uint64_t)kIcpCells + 1, probs, per_match);
     for (size_t p0 = 0; p0 < P; p0 += kIcpProblemsPerLaunch) {
         const int n = (int)std::min((size_t)kIcpProblemsPerLaunch, P - p0);
         ProfScope ps(c, cap ? K_ICP_WIDE : K_ICP, n);
@@ -491,7 +525,7 @@ int fine_icp(bev_ctx *c, int U, const FineProblem *d_probs, size_t P, const Fine
              const int32_t *d_best, const bev_icp_params_t &prm, bev_icp_result_t *d_res, PairGrid &g)
 {
     if (g.cap) {
-        BEVCK(pair_grid_build(c, g, w.hdr, w.sorted, w.vox_n, nullptr, w.Pn, w.vox, nullptr));
+        BEVCK(pair_grid_build(c, g, w.hdr, w.sorted, w.vox_n, nullptr, w.Pn, SubgridSource{nullptr, w.vox, nullptr}));
     } else {
         ProfScope ps(c, K_FINE_GRID, U);
         launch_fine_grid(U, w, c->stream);
@@ -559,7 +593,7 @@ int bev_icp_point_to_point(bev_ctx_t *c, const bev_point_t *src, uint32_t n_src,
     HIPCK(c, hipMemcpyAsync(w.vox_n, counts, sizeof(counts), hipMemcpyHostToDevice, c->stream));
     bev_icp_result_t *d_res = reinterpret_cast<bev_icp_result_t *>(w.keys);
     BEVCK(fine_icp(c, 2, d_probs, 1, w, nullptr, nullptr, prm, d_res, g));
-    pair_grid_record(c->pair_grid_rec[0], c->reg.fine_buf, w.hdr, w.cell_off, cap ? g.l.off_words : (uint64_t)kFineCells + 1, probs, 1);
+    pair_grid_record(c, 0, w.hdr, w.cell_off, cap ? g.l.off_words : (uint64_t)kFineCells + 1, probs, 1);
     HIPCK(c, hipMemcpyAsync(result, d_res, sizeof(bev_icp_result_t), hipMemcpyDeviceToHost, c->stream));
     HIPCK(c, hipStreamSynchronize(c->stream));
     return BEV_OK;
@@ -618,7 +652,7 @@ int bev_fine_registration_device_resident(bev_ctx_t *c, int n_frames, const bev_
     BEVCK(fine_setup(c, (size_t)U, Pn, slots, probs, w, &d_slots, &d_probs, cap, T, g));
     BEVCK(fine_voxel(c, d_clouds, d_slots, U, w, leaf));
     BEVCK(fine_icp(c, U, d_probs, probs.size(), w, d_coarse, d_best, prm, d_results, g));
-    pair_grid_record(c->pair_grid_rec[0], c->reg.fine_buf, w.hdr, w.cell_off, cap ? g.l.off_words : (uint64_t)kFineCells + 1, probs, 1);
+    pair_grid_record(c, 0, w.hdr, w.cell_off, cap ? g.l.off_words : (uint64_t)kFineCells + 1, probs, 1);
     return record_tail(c);
 }
 
@@ -636,27 +670,10 @@ int bev_set_pair_search_grid(bev_ctx_t *c, int fine_dim, int coarse_dim)
 int bev_debug_get_pair_grid(bev_ctx_t *c, int coarse, int first_match, int n_matches, uint32_t *out)
 {
     if (!c || (coarse != 0 && coarse != 1) || first_match < 0 || n_matches < 0 || !out) return BEV_ERR_INVALID_ARG;
-    const PairGridRecord &r = c->pair_grid_rec[coarse];
-    if (!r.hdr || (size_t)first_match + (size_t)n_matches > r.match_slot.size()) return BEV_ERR_INVALID_ARG;
-    if (r.uses != (coarse ? c->reg.icp_buf : c->reg.fine_buf).uses) return BEV_ERR_INVALID_ARG; /* a later call laid it out anew */
-    BEVCK(begin_call(c, false));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    std::vector<uint32_t> off;
-    for (int i = 0; i < n_matches; ++i) {
-        const uint32_t slot = r.match_slot[(size_t)(first_match + i)];
-        IcpGridHdr h;
-        HIPCK(c, hipMemcpy(&h, r.hdr + slot, sizeof h, hipMemcpyDeviceToHost));
-        if (h.nx < 1 || h.ny < 1 || (uint64_t)h.nx * (uint64_t)h.ny + 1 > r.off_words) return BEV_ERR_INVALID_ARG; /* (not a grid) */
-        off.resize((size_t)h.nx * (size_t)h.ny + 1);
-        HIPCK(c, hipMemcpy(off.data(), r.cell_off + (size_t)slot * r.off_words, off.size() * 4, hipMemcpyDeviceToHost));
-        uint32_t largest = 0;
-        for (size_t k = 0; k + 1 < off.size(); ++k) largest = std::max(largest, off[k + 1] - off[k]);
-        out[4 * i] = (uint32_t)h.nx;
-        out[4 * i + 1] = (uint32_t)h.ny;
-        out[4 * i + 2] = h.n;
-        out[4 * i + 3] = largest;
-    }
-    return BEV_OK;
+    const GridRecord &r = c->pair_grid_rec[coarse];
+    if (!r.hdr || (size_t)first_match + (size_t)n_matches > r.items.size()) return BEV_ERR_INVALID_ARG;
+    if (r.uses != stage_buf(c, coarse).uses) return BEV_ERR_INVALID_ARG; /* a later call laid it out anew */
+    return grid_record_read(c, r, first_match, n_matches, out);
 }
 
 } /* extern "C" */

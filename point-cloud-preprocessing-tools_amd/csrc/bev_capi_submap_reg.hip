@@ -4,7 +4,7 @@
  * against maps thinned over their union with recomputed normals (§6q), and against the top part over the union of a map's moved
  * full clouds, thinned the same way (§6r).
  * Host-side only: the kernels are in bev_kernels.hip, the plan of a call in bev_submap_reg_plan.h; bev_reg_host.h is shared with
- * bev_capi_reg.hip, the context (bev_ctx.h) with every file of the C ABI.  What is shared and what is not: DESIGN.md §6n.
+ * bev_capi_reg.hip, the context (bev_ctx.h) with every file of the C ABI.  What is shared and what is not: DESIGN.md §6n, §6u.
  */
 #include <algorithm>
 #include <cstring>
@@ -74,38 +74,40 @@ GridPieces grid_pieces(const Plan &plan, bool wide)
     return wide ? GridPieces{C * 4, M * kSubgridParts * sizeof(float4), M * kSubgridScanParts * 4} : GridPieces{0, 0, 0};
 }
 
-/* the search grids of a group's maps by several workgroups per map: the maps' point counts are vh's n_out, their points pts
- * (float4) or, pts == nullptr, the PointNormal rows */
-int submap_grid_build(bev_ctx *c, const Plan &plan, const Group &g, int cap, const void *d_maps, const SubvoxHdr *vh,
-                      const float4 *pts, const float *rows, const SubmapGridWork &w)
+/* the search grids of a group's maps by several workgroups per map (search_grid_build, bev_reg_host.h): the maps' point counts
+ * are vh's n_out, their points src's */
+int submap_grid_build(bev_ctx *c, const Group &g, int cap, const void *d_maps, const SubvoxHdr *vh, const SubgridSource &src,
+                      const SubmapGridWork &w)
 {
-    uint64_t largest = 0;
-    for (uint32_t u = g.map0; u < g.map0 + g.n_maps; ++u) largest = std::max(largest, plan.map_cap[u]);
     /* workgroups of 2048 points of the largest map, of 4096 cells of the largest grid */
-    const uint32_t parts = (uint32_t)std::min<uint64_t>((largest + 8 * kIcpThreads - 1) / (8 * kIcpThreads), kSubgridParts);
+    const uint32_t parts = (uint32_t)std::min<uint64_t>((g.max_cap + 8 * kIcpThreads - 1) / (8 * kIcpThreads), kSubgridParts);
     const uint32_t tiles = (uint32_t)((g.max_cells + bevsubreg::kGridScanTile - 1) / bevsubreg::kGridScanTile);
-    HIPCK(c, hipMemsetAsync(w.cnt, 0, (size_t)g.cells * 4, c->stream));
-    for (int step = 0; step < 6; ++step) {
-        ProfScope ps(c, K_SUBMAP_GRID_BOUNDS + step, (int)g.n_maps);
-        launch_submap_grid(step, d_maps, g.map0, (int)g.n_maps, parts, tiles, cap, vh, pts, rows, w, c->stream);
-    }
-    return BEV_OK;
+    return search_grid_build(c, d_maps, g.map0, (int)g.n_maps, parts, tiles, cap, vh, src, w, (size_t)g.cells);
 }
 
-/* what bev_debug_get_submap_grid reads of a call: the grids of its last group */
-void submap_grid_record(bev_ctx *c, int coarse, const Plan &plan, int cap, uint32_t fixed_cells, const void *buf,
-                        const IcpGridHdr *hdr, const uint32_t *cell_off)
+/* what bev_debug_get_submap_grid reads of a stage's call: the grids of its last group, in the stage's workspace */
+void submap_grid_record(bev_ctx *c, int coarse, const Plan &plan, int cap, const IcpGridHdr *hdr, const uint32_t *cell_off)
 {
-    SubmapGridRecord &r = c->submap_grid_rec[coarse];
-    r = SubmapGridRecord{};
+    const uint64_t fixed_cells = coarse ? kIcpCells : kFineCells;
+    GridRecord &r = c->submap_grid_rec[coarse];
+    r = GridRecord{};
     if (plan.groups.empty()) return;
     const Group &g = plan.groups.back();
-    r.buf = buf;
+    r.buf = stage_buf(c, coarse).p;
     r.hdr = hdr;
     r.cell_off = cell_off;
-    for (uint32_t i = 0; i < g.n_maps; ++i) {
-        r.off0.push_back(cap ? plan.map_cell0[g.map0 + i] : (uint64_t)i * (fixed_cells + 1));
-        r.cells.push_back(cap ? bevsubreg::grid_cells(plan.map_cap[g.map0 + i], cap) : fixed_cells);
+    for (uint32_t i = 0; i < g.n_maps; ++i)
+        r.items.push_back({i, cap ? plan.map_cell0[g.map0 + i] : i * (fixed_cells + 1),
+                           cap ? bevsubreg::grid_cells(plan.map_cap[g.map0 + i], cap) : fixed_cells});
+}
+
+/* the sort of a group's key arrays as bev_submap_vox_plan.h schedules it */
+void submap_sort_keys(bev_ctx *c, const Group &g, const SubmapVoxWork &v)
+{
+    const uint32_t tiles = bevsubvox::tiles(g.max_slots);
+    for (const bevsubvox::Stage &sg : bevsubvox::schedule(g.max_slots)) {
+        ProfScope ps(c, sg.kind == bevsubvox::kStageGlobal ? K_SUBMAP_VOX_GLOBAL : K_SUBMAP_VOX_TILE, (int)g.n_maps);
+        launch_submap_vox_stage(sg.kind, sg.k, sg.j, g.map0, (int)g.n_maps, tiles, v, c->stream);
     }
 }
 
@@ -165,11 +167,12 @@ int submap_fine_begin(bev_ctx *c, const Plan &plan, const Options &opt, const be
 
 /* a group's targets in s.t.pts (the plain cloud call: in s.v.moved): the entries' voxel clouds moved and concatenated, with their
  * search grids where the call has matches; map_leaf > 0: thinned by the voxel grid over the union */
-int submap_fine_targets(bev_ctx *c, const Plan &plan, const Group &g, const Options &opt, const SubmapFine &s, float map_leaf)
+int submap_fine_targets(bev_ctx *c, const Group &g, const Options &opt, const SubmapFine &s, float map_leaf)
 {
     const int gm = (int)g.n_maps;
     const PlanDev &d = s.d;
     const bool wide = opt.grid_cap > 0 && !opt.all_maps;
+    const SubgridSource pts{s.t.pts, nullptr, nullptr};
     if (!opt.union_voxel && !opt.all_maps && !wide) {
         ProfScope ps(c, K_SUBMAP_TARGET, gm);
         launch_submap_target(d.maps, g.map0, gm, d.entries, s.w, s.ent_start, s.t, c->stream);
@@ -179,23 +182,19 @@ int submap_fine_targets(bev_ctx *c, const Plan &plan, const Group &g, const Opti
         ProfScope ps(c, K_SUBMAP_VOX_MOVE, gm);
         launch_submap_vox_move(d.maps, g.map0, gm, d.entries, s.w, s.ent_start, s.v, c->stream);
     }
-    if (!opt.union_voxel) return wide ? submap_grid_build(c, plan, g, opt.grid_cap, d.maps, s.v.vh, s.t.pts, nullptr, s.gw) : BEV_OK;
+    if (!opt.union_voxel) return wide ? submap_grid_build(c, g, opt.grid_cap, d.maps, s.v.vh, pts, s.gw) : BEV_OK;
     {
         ProfScope ps(c, K_SUBMAP_VOX_KEYS, gm);
         launch_submap_vox_keys(d.maps, g.map0, gm, s.v, map_leaf, c->stream);
     }
-    const uint32_t tiles = bevsubvox::tiles(g.max_slots);
-    for (const bevsubvox::Stage &sg : bevsubvox::schedule(g.max_slots)) {
-        ProfScope ps(c, sg.kind == bevsubvox::kStageGlobal ? K_SUBMAP_VOX_GLOBAL : K_SUBMAP_VOX_TILE, gm);
-        launch_submap_vox_stage(sg.kind, sg.k, sg.j, g.map0, gm, tiles, s.v, c->stream);
-    }
+    submap_sort_keys(c, g, s.v);
     {
         SubmapRegWork t = s.t;
         if (wide) t.sorted = nullptr, t.hdr = nullptr, t.cell_off = nullptr; /* (no grid at nullptr) */
         ProfScope ps(c, K_SUBMAP_VOX_FINISH, gm);
         launch_submap_vox_finish(d.maps, g.map0, gm, s.v, t, c->stream);
     }
-    return wide ? submap_grid_build(c, plan, g, opt.grid_cap, d.maps, s.v.vh, s.t.pts, nullptr, s.gw) : BEV_OK;
+    return wide ? submap_grid_build(c, g, opt.grid_cap, d.maps, s.v.vh, pts, s.gw) : BEV_OK;
 }
 
 /* the registration call on the context's stream, behind the entries' checks and begin_call.  map_leaf > 0: the maps are thinned
@@ -222,7 +221,7 @@ int submap_reg_frames(bev_ctx *c, const bev_point_t *d_clouds, const Call &call,
     BEVCK(submap_fine_begin(c, plan, opt, d_clouds, leaf, s, probs));
     const FineProblem *d_probs = static_cast<const FineProblem *>(s.d.probs);
     for (const Group &g : plan.groups) { /* one behind the other: the stream's order hands the maps' arrays on */
-        BEVCK(submap_fine_targets(c, plan, g, opt, s, map_leaf));
+        BEVCK(submap_fine_targets(c, g, opt, s, map_leaf));
         for (uint32_t p0 = 0; p0 < g.n_probs; p0 += kFineProblemsPerLaunch) {
             const int n = (int)std::min<uint32_t>(kFineProblemsPerLaunch, g.n_probs - p0);
             ProfScope ps(c, opt.grid_cap ? K_SUBMAP_ICP_WIDE : K_SUBMAP_ICP, n);
@@ -233,7 +232,7 @@ int submap_reg_frames(bev_ctx *c, const bev_point_t *d_clouds, const Call &call,
                 launch_submap_icp(d_probs + g.prob0 + p0, n, s.d.maps, g.map0, s.w, s.t, d_coarse, d_best, prm, d_results, c->stream);
         }
     }
-    submap_grid_record(c, 0, plan, opt.grid_cap, kFineCells, c->reg.fine_buf.p, s.t.hdr, s.t.cell_off);
+    submap_grid_record(c, 0, plan, opt.grid_cap, s.t.hdr, s.t.cell_off);
     HIPCK(c, hipGetLastError());
     return BEV_OK;
 }
@@ -329,43 +328,99 @@ Plan submap_coarse_plan(bev_ctx *c, Call &call, const Options &opt, int n_frames
     return plan;
 }
 
-/* a group's targets thinned over their union into s.t.rows: moved rows, keys, the sort, centroids, normals;
- * the search grids where the call has matches */
-int submap_coarse_thin(bev_ctx *c, const Plan &plan, const Group &g, const SubmapCoarse &s, const float *pn, size_t stride,
-                       const uint32_t *d_counts, float pn_leaf, float radius, const float vp[2])
+/* two problems per match, the guesses adjacent */
+std::vector<IcpProblem> submap_coarse_problems(const Plan &plan, const bev_match_t *h_matches)
+{
+    std::vector<IcpProblem> probs;
+    probs.reserve(2 * plan.probs.size());
+    for (const bevsubreg::Problem &pp : plan.probs)
+        for (int g = 0; g < 2; ++g) {
+            IcpProblem pb{};
+            pb.src_frame = (uint32_t)h_matches[pp.result].query_idx;
+            pb.tgt_frame = 0xffffffffu; /* (not read: the target is a map) */
+            pb.tgt_slot = pp.map;
+            pb.result = 2 * pp.result + (uint32_t)g;
+            bevx::icp_tool_guess(h_matches[pp.result].angle_guess, g, pb.guess);
+            probs.push_back(pb);
+        }
+    return probs;
+}
+
+/* how the two coarse registration calls end: the hook's record, the better guess of every match, the tail */
+int submap_coarse_end(bev_ctx *c, const Plan &plan, const SubmapCoarse &s, bev_icp_result_t *d_results, int n_matches,
+                      int32_t *d_best)
+{
+    submap_grid_record(c, 1, plan, s.grid_cap, s.t.hdr, s.t.cell_off);
+    {
+        ProfScope ps(c, K_ICP_BEST, n_matches);
+        launch_icp_best(d_results, n_matches, d_best, c->stream);
+    }
+    HIPCK(c, hipGetLastError());
+    return record_tail(c);
+}
+
+/* a group's targets out of s.p.moved (thinned: s.t.rows), as the two cloud calls write them */
+void submap_pn_out(bev_ctx *c, const Group &g, const SubmapCoarse &s, bool vox, float *d_out, uint64_t out_stride,
+                   uint32_t *d_counts_out)
+{
+    const uint32_t parts = (uint32_t)std::min<uint64_t>((3 * g.max_cap + 4 * kIcpThreads - 1) / (4 * kIcpThreads), 256);
+    ProfScope ps(c, K_SUBMAP_PN_OUT, (int)g.n_maps);
+    launch_submap_pn_out(s.d.maps, g.map0, (int)g.n_maps, parts, s.p.v.vh, vox ? s.t.rows : s.p.moved, d_out, out_stride,
+                         d_counts_out, c->stream);
+}
+
+/* a group's entries' rows moved and concatenated into s.p.moved */
+void submap_pn_move(bev_ctx *c, const Group &g, const SubmapCoarse &s, const float *pn, size_t stride, const uint32_t *d_counts)
+{
+    ProfScope ps(c, K_SUBMAP_PN_MOVE, (int)g.n_maps);
+    launch_submap_pn_move(s.d.maps, g.map0, (int)g.n_maps, s.d.entries, pn, stride, d_counts, s.ent_start, s.p, c->stream);
+}
+
+/* the rows of a group's maps in s.p.moved thinned over their union into s.t.rows: keys, the sort, centroids,
+ * (overflow: §6r's count of a top part cut short,) normals; the search grids, wide or fixed, where the call has matches */
+int submap_pn_thin(bev_ctx *c, const Group &g, const SubmapCoarse &s, bool overflow, float pn_leaf, float radius, const float vp[2])
 {
     const int gm = (int)g.n_maps;
     const PlanDev &d = s.d;
     {
-        ProfScope ps(c, K_SUBMAP_PN_MOVE, gm);
-        launch_submap_pn_move(d.maps, g.map0, gm, d.entries, pn, stride, d_counts, s.ent_start, s.p, c->stream);
-    }
-    {
         ProfScope ps(c, K_SUBMAP_PN_KEYS, gm);
         launch_submap_pn_keys(d.maps, g.map0, gm, s.p, pn_leaf, c->stream);
     }
-    const uint32_t tiles = bevsubvox::tiles(g.max_slots);
-    for (const bevsubvox::Stage &sg : bevsubvox::schedule(g.max_slots)) {
-        ProfScope ps(c, sg.kind == bevsubvox::kStageGlobal ? K_SUBMAP_VOX_GLOBAL : K_SUBMAP_VOX_TILE, gm);
-        launch_submap_vox_stage(sg.kind, sg.k, sg.j, g.map0, gm, tiles, s.p.v, c->stream);
-    }
+    submap_sort_keys(c, g, s.p.v);
     {
         ProfScope ps(c, K_SUBMAP_PN_FINISH, gm);
         launch_submap_pn_finish(d.maps, g.map0, gm, s.p, s.t.rows, c->stream);
     }
+    if (overflow) {
+        ProfScope ps(c, K_SUBMAP_TOP_OVERFLOW, gm);
+        launch_submap_top_overflow(d.maps, g.map0, gm, s.p, c->stream);
+    }
     {
-        uint64_t largest = 0;
-        for (uint32_t u = g.map0; u < g.map0 + g.n_maps; ++u) largest = std::max(largest, plan.map_cap[u]);
         ProfScope ps(c, K_SUBMAP_PN_NORMALS, gm);
-        launch_submap_pn_normals(d.maps, g.map0, gm, (uint32_t)((largest + kIcpThreads - 1) / kIcpThreads), s.p, radius, pn_leaf, vp,
+        launch_submap_pn_normals(d.maps, g.map0, gm, (uint32_t)((g.max_cap + kIcpThreads - 1) / kIcpThreads), s.p, radius, pn_leaf, vp,
                                  s.t.rows, c->stream);
     }
-    if (s.t.hdr && s.grid_cap) return submap_grid_build(c, plan, g, s.grid_cap, d.maps, s.p.v.vh, nullptr, s.t.rows, s.gw);
+    if (s.t.hdr && s.grid_cap)
+        return submap_grid_build(c, g, s.grid_cap, d.maps, s.p.v.vh, SubgridSource{nullptr, nullptr, s.t.rows}, s.gw);
     if (s.t.hdr) {
         ProfScope ps(c, K_SUBMAP_PN_GRID, gm);
         launch_submap_pn_grid(d.maps, g.map0, gm, s.p.v.vh, s.t, c->stream);
     }
     return BEV_OK;
+}
+
+/* a group's targets thinned over their union (§6q) */
+int submap_coarse_thin(bev_ctx *c, const Group &g, const SubmapCoarse &s, const float *pn, size_t stride, const uint32_t *d_counts,
+                       float pn_leaf, float radius, const float vp[2])
+{
+    submap_pn_move(c, g, s, pn, stride, d_counts);
+    return submap_pn_thin(c, g, s, false, pn_leaf, radius, vp);
+}
+/* ... as they are, under a wide grid: the concatenation is s.t.rows (submap_coarse_work) */
+int submap_coarse_wide(bev_ctx *c, const Group &g, const SubmapCoarse &s, const float *pn, size_t stride, const uint32_t *d_counts)
+{
+    submap_pn_move(c, g, s, pn, stride, d_counts);
+    return submap_grid_build(c, g, s.grid_cap, s.d.maps, s.p.v.vh, SubgridSource{nullptr, nullptr, s.t.rows}, s.gw);
 }
 
 /* ---- the top part over the union of a map's moved full clouds (§6r) ---- */
@@ -418,29 +473,17 @@ int submap_top_work(bev_ctx *c, const Plan &plan, bool icp, int grid_cap, size_t
     return BEV_OK;
 }
 
-/* the sort of a group's key arrays as bev_submap_vox_plan.h schedules it */
-void submap_sort_keys(bev_ctx *c, const Group &g, const SubmapVoxWork &v)
-{
-    const uint32_t tiles = bevsubvox::tiles(g.max_slots);
-    for (const bevsubvox::Stage &sg : bevsubvox::schedule(g.max_slots)) {
-        ProfScope ps(c, sg.kind == bevsubvox::kStageGlobal ? K_SUBMAP_VOX_GLOBAL : K_SUBMAP_VOX_TILE, (int)g.n_maps);
-        launch_submap_vox_stage(sg.kind, sg.k, sg.j, g.map0, (int)g.n_maps, tiles, v, c->stream);
-    }
-}
-
 /* a group's targets: the keys of the unions, the select, the sorted selection, the rows of top(g) in s.p.moved;
  * pn_leaf > 0: thinned with their normals into s.t.rows as §6q thins a concatenation, the search grids where the call has matches */
-int submap_top_targets(bev_ctx *c, const Plan &plan, const Group &g, const SubmapTop &w, const bev_point_t *d_clouds, float pn_leaf,
+int submap_top_targets(bev_ctx *c, const Group &g, const SubmapTop &w, const bev_point_t *d_clouds, float pn_leaf,
                        float radius, const float vp[2])
 {
     const int gm = (int)g.n_maps;
     const SubmapCoarse &s = w.s;
     const PlanDev &d = s.d;
-    uint64_t rows = 0;
-    for (uint32_t u = g.map0; u < g.map0 + g.n_maps; ++u) rows = std::max(rows, plan.map_cap[u]);
     /* workgroups of 4096 records of the largest union, of 256 rows of the largest top part */
     const uint32_t parts = (uint32_t)std::min<uint64_t>((g.max_union + 16 * kIcpThreads - 1) / (16 * kIcpThreads), 512);
-    const uint32_t row_parts = (uint32_t)std::min<uint64_t>((rows + kIcpThreads - 1) / kIcpThreads, 1024);
+    const uint32_t row_parts = (uint32_t)std::min<uint64_t>((g.max_cap + kIcpThreads - 1) / kIcpThreads, 1024);
     HIPCK(c, hipMemsetAsync(w.t.cells, 0, w.cell_stride + (size_t)gm * kTopHistWords * 4, c->stream));
     {
         ProfScope ps(c, K_SUBMAP_TOP_KEYS, gm);
@@ -467,31 +510,7 @@ int submap_top_targets(bev_ctx *c, const Plan &plan, const Group &g, const Subma
         ProfScope ps(c, K_SUBMAP_TOP_ROWS, gm);
         launch_submap_top_rows(d.maps, g.map0, gm, row_parts, d.entries, d.slots, d_clouds, w.t, s.p, c->stream);
     }
-    if (!(pn_leaf > 0.0f)) return BEV_OK;
-    {
-        ProfScope ps(c, K_SUBMAP_PN_KEYS, gm);
-        launch_submap_pn_keys(d.maps, g.map0, gm, s.p, pn_leaf, c->stream);
-    }
-    submap_sort_keys(c, g, s.p.v);
-    {
-        ProfScope ps(c, K_SUBMAP_PN_FINISH, gm);
-        launch_submap_pn_finish(d.maps, g.map0, gm, s.p, s.t.rows, c->stream);
-    }
-    {
-        ProfScope ps(c, K_SUBMAP_TOP_OVERFLOW, gm);
-        launch_submap_top_overflow(d.maps, g.map0, gm, s.p, c->stream);
-    }
-    {
-        ProfScope ps(c, K_SUBMAP_PN_NORMALS, gm);
-        launch_submap_pn_normals(d.maps, g.map0, gm, (uint32_t)((rows + kIcpThreads - 1) / kIcpThreads), s.p, radius, pn_leaf, vp,
-                                 s.t.rows, c->stream);
-    }
-    if (s.t.hdr && s.grid_cap) return submap_grid_build(c, plan, g, s.grid_cap, d.maps, s.p.v.vh, nullptr, s.t.rows, s.gw);
-    if (s.t.hdr) {
-        ProfScope ps(c, K_SUBMAP_PN_GRID, gm);
-        launch_submap_pn_grid(d.maps, g.map0, gm, s.p.v.vh, s.t, c->stream);
-    }
-    return BEV_OK;
+    return pn_leaf > 0.0f ? submap_pn_thin(c, g, s, true, pn_leaf, radius, vp) : BEV_OK;
 }
 
 } // namespace
@@ -562,10 +581,8 @@ int bev_submap_voxel_cloud_device_resident(bev_ctx_t *c, int n_frames, const bev
     SubmapFine s;
     BEVCK(submap_fine_begin(c, plan, opt, d_clouds, leaf, s));
     for (const Group &g : plan.groups) {
-        BEVCK(submap_fine_targets(c, plan, g, opt, s, map_leaf));
-        uint64_t largest = 0;
-        for (uint32_t u = g.map0; u < g.map0 + g.n_maps; ++u) largest = std::max(largest, plan.map_cap[u]);
-        const uint32_t parts = (uint32_t)std::min<uint64_t>((largest + 4 * kFineThreads - 1) / (4 * kFineThreads), 256);
+        BEVCK(submap_fine_targets(c, g, opt, s, map_leaf));
+        const uint32_t parts = (uint32_t)std::min<uint64_t>((g.max_cap + 4 * kFineThreads - 1) / (4 * kFineThreads), 256);
         ProfScope ps(c, K_SUBMAP_VOX_OUT, (int)g.n_maps);
         launch_submap_vox_out(s.d.maps, g.map0, (int)g.n_maps, parts, s.v.vh, opt.union_voxel ? s.t.pts : s.v.moved,
                               reinterpret_cast<float4 *>(d_out), out_stride, d_counts, c->stream);
@@ -643,18 +660,7 @@ int bev_submap_coarse_voxel_registration_device_resident(bev_ctx_t *c, int n_fra
     const Plan plan = submap_coarse_plan(c, call, opt, n_frames, stride);
     SubmapCoarse s;
     BEVCK(submap_coarse_work(c, plan, opt, stride, s));
-    std::vector<IcpProblem> probs; /* two problems per match, the guesses adjacent */
-    probs.reserve(2 * plan.probs.size());
-    for (const bevsubreg::Problem &pp : plan.probs)
-        for (int g = 0; g < 2; ++g) {
-            IcpProblem pb{};
-            pb.src_frame = (uint32_t)h_matches[pp.result].query_idx;
-            pb.tgt_frame = 0xffffffffu; /* (not read: the target is a map) */
-            pb.tgt_slot = pp.map;
-            pb.result = 2 * pp.result + (uint32_t)g;
-            bevx::icp_tool_guess(h_matches[pp.result].angle_guess, g, pb.guess);
-            probs.push_back(pb);
-        }
+    const std::vector<IcpProblem> probs = submap_coarse_problems(plan, h_matches);
     BEVCK(plan_up(c, c->reg.icp_tab, plan, opt, s.d, probs.data(), probs.size() * sizeof(IcpProblem)));
     s.p.v.key0 = static_cast<const uint64_t *>(s.d.key0);
     submap_coarse_grid_work(s, opt, s.d);
@@ -663,26 +669,16 @@ int bev_submap_coarse_voxel_registration_device_resident(bev_ctx_t *c, int n_fra
     const IcpProblem *d_probs = static_cast<const IcpProblem *>(s.d.probs);
     for (const Group &g : plan.groups) {
         if (vox) {
-            BEVCK(submap_coarse_thin(c, plan, g, s, pn, stride, d_counts, pn_leaf, radius, vp));
+            BEVCK(submap_coarse_thin(c, g, s, pn, stride, d_counts, pn_leaf, radius, vp));
         } else if (s.grid_cap) {
-            {
-                ProfScope ps(c, K_SUBMAP_PN_MOVE, (int)g.n_maps);
-                launch_submap_pn_move(s.d.maps, g.map0, (int)g.n_maps, s.d.entries, pn, stride, d_counts, s.ent_start, s.p, c->stream);
-            }
-            BEVCK(submap_grid_build(c, plan, g, s.grid_cap, s.d.maps, s.p.v.vh, nullptr, s.t.rows, s.gw));
+            BEVCK(submap_coarse_wide(c, g, s, pn, stride, d_counts));
         } else {
             ProfScope ps(c, K_SUBMAP_PN_TARGET, (int)g.n_maps);
             launch_submap_pn_target(s.d.maps, g.map0, (int)g.n_maps, s.d.entries, pn, stride, d_counts, s.ent_start, s.t, c->stream);
         }
         submap_coarse_icp_launches(c, g, s, pn, stride, d_counts, d_probs, prm, d_results);
     }
-    submap_grid_record(c, 1, plan, s.grid_cap, kIcpCells, c->reg.icp_buf.p, s.t.hdr, s.t.cell_off);
-    {
-        ProfScope ps(c, K_ICP_BEST, n_matches);
-        launch_icp_best(d_results, n_matches, d_best, c->stream);
-    }
-    HIPCK(c, hipGetLastError());
-    return record_tail(c);
+    return submap_coarse_end(c, plan, s, d_results, n_matches, d_best);
 }
 
 int bev_submap_coarse_registration_device_resident(bev_ctx_t *c, int n_frames, const void *d_pn, size_t stride,
@@ -728,18 +724,9 @@ int bev_submap_pn_cloud_device_resident(bev_ctx_t *c, int n_frames, const void *
     const float vp[2] = {viewpoint && vox ? viewpoint[0] : 0.0f, viewpoint && vox ? viewpoint[1] : 0.0f};
     const float *pn = static_cast<const float *>(d_pn);
     for (const Group &g : plan.groups) {
-        if (vox) {
-            BEVCK(submap_coarse_thin(c, plan, g, s, pn, stride, d_counts, pn_leaf, radius, vp));
-        } else {
-            ProfScope ps(c, K_SUBMAP_PN_MOVE, (int)g.n_maps);
-            launch_submap_pn_move(s.d.maps, g.map0, (int)g.n_maps, s.d.entries, pn, stride, d_counts, s.ent_start, s.p, c->stream);
-        }
-        uint64_t largest = 0;
-        for (uint32_t u = g.map0; u < g.map0 + g.n_maps; ++u) largest = std::max(largest, plan.map_cap[u]);
-        const uint32_t parts = (uint32_t)std::min<uint64_t>((3 * largest + 4 * kIcpThreads - 1) / (4 * kIcpThreads), 256);
-        ProfScope ps(c, K_SUBMAP_PN_OUT, (int)g.n_maps);
-        launch_submap_pn_out(s.d.maps, g.map0, (int)g.n_maps, parts, s.p.v.vh, vox ? s.t.rows : s.p.moved, d_out, out_stride,
-                             d_counts_out, c->stream);
+        if (vox) BEVCK(submap_coarse_thin(c, g, s, pn, stride, d_counts, pn_leaf, radius, vp));
+        else submap_pn_move(c, g, s, pn, stride, d_counts);
+        submap_pn_out(c, g, s, vox, d_out, out_stride, d_counts_out);
     }
     HIPCK(c, hipGetLastError());
     return record_tail(c);
@@ -777,13 +764,8 @@ int bev_submap_top_part_cloud_device_resident(bev_ctx_t *c, int n_frames, const 
     w.t.u0 = static_cast<const uint64_t *>(w.s.d.u0);
     const float vp[2] = {viewpoint && vox ? viewpoint[0] : 0.0f, viewpoint && vox ? viewpoint[1] : 0.0f};
     for (const Group &g : plan.groups) {
-        BEVCK(submap_top_targets(c, plan, g, w, d_clouds, pn_leaf, radius, vp));
-        uint64_t largest = 0;
-        for (uint32_t u = g.map0; u < g.map0 + g.n_maps; ++u) largest = std::max(largest, plan.map_cap[u]);
-        const uint32_t parts = (uint32_t)std::min<uint64_t>((3 * largest + 4 * kIcpThreads - 1) / (4 * kIcpThreads), 256);
-        ProfScope ps(c, K_SUBMAP_PN_OUT, (int)g.n_maps);
-        launch_submap_pn_out(w.s.d.maps, g.map0, (int)g.n_maps, parts, w.s.p.v.vh, vox ? w.s.t.rows : w.s.p.moved, d_out, out_stride,
-                             d_counts_out, c->stream);
+        BEVCK(submap_top_targets(c, g, w, d_clouds, pn_leaf, radius, vp));
+        submap_pn_out(c, g, w.s, vox, d_out, out_stride, d_counts_out);
     }
     HIPCK(c, hipGetLastError());
     return record_tail(c);
@@ -816,18 +798,7 @@ int bev_submap_top_part_coarse_registration_device_resident(bev_ctx_t *c, int n_
     const Plan plan = bevsubreg::plan_call(call, opt, group_cap(c));
     SubmapTop w;
     BEVCK(submap_top_work(c, plan, true, opt.grid_cap, stride, w));
-    std::vector<IcpProblem> probs; /* two problems per match, the guesses adjacent */
-    probs.reserve(2 * plan.probs.size());
-    for (const bevsubreg::Problem &pp : plan.probs)
-        for (int g = 0; g < 2; ++g) {
-            IcpProblem pb{};
-            pb.src_frame = (uint32_t)h_matches[pp.result].query_idx;
-            pb.tgt_frame = 0xffffffffu; /* (not read: the target is a map) */
-            pb.tgt_slot = pp.map;
-            pb.result = 2 * pp.result + (uint32_t)g;
-            bevx::icp_tool_guess(h_matches[pp.result].angle_guess, g, pb.guess);
-            probs.push_back(pb);
-        }
+    const std::vector<IcpProblem> probs = submap_coarse_problems(plan, h_matches);
     BEVCK(plan_up(c, c->reg.icp_tab, plan, opt, w.s.d, probs.data(), probs.size() * sizeof(IcpProblem)));
     w.s.p.v.key0 = static_cast<const uint64_t *>(w.s.d.key0);
     w.t.u0 = static_cast<const uint64_t *>(w.s.d.u0);
@@ -836,16 +807,10 @@ int bev_submap_top_part_coarse_registration_device_resident(bev_ctx_t *c, int n_
     const float *pn = static_cast<const float *>(d_pn);
     const IcpProblem *d_probs = static_cast<const IcpProblem *>(w.s.d.probs);
     for (const Group &g : plan.groups) {
-        BEVCK(submap_top_targets(c, plan, g, w, d_clouds, pn_leaf, radius, vp));
+        BEVCK(submap_top_targets(c, g, w, d_clouds, pn_leaf, radius, vp));
         submap_coarse_icp_launches(c, g, w.s, pn, stride, d_counts, d_probs, prm, d_results);
     }
-    submap_grid_record(c, 1, plan, w.s.grid_cap, kIcpCells, c->reg.icp_buf.p, w.s.t.hdr, w.s.t.cell_off);
-    {
-        ProfScope ps(c, K_ICP_BEST, n_matches);
-        launch_icp_best(d_results, n_matches, d_best, c->stream);
-    }
-    HIPCK(c, hipGetLastError());
-    return record_tail(c);
+    return submap_coarse_end(c, plan, w.s, d_results, n_matches, d_best);
 }
 
 /* ---- search grids sized to the maps (bev_submap_grid.h) ---------------------------------------------------- */
@@ -862,28 +827,10 @@ int bev_set_submap_search_grid(bev_ctx_t *c, int fine_dim, int coarse_dim)
 int bev_debug_get_submap_grid(bev_ctx_t *c, int coarse, int first_map, int n_maps, uint32_t *out)
 {
     if (!c || (coarse != 0 && coarse != 1) || first_map < 0 || n_maps < 0 || !out) return BEV_ERR_INVALID_ARG;
-    const SubmapGridRecord &r = c->submap_grid_rec[coarse];
-    if (!r.hdr || (size_t)first_map + (size_t)n_maps > r.off0.size()) return BEV_ERR_INVALID_ARG;
-    BEVCK(begin_call(c, false));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    if (r.buf != (coarse ? c->reg.icp_buf.p : c->reg.fine_buf.p)) return BEV_ERR_INVALID_ARG;
-    std::vector<IcpGridHdr> hdr((size_t)n_maps);
-    std::vector<uint32_t> off;
-    if (n_maps) HIPCK(c, hipMemcpy(hdr.data(), r.hdr + first_map, hdr.size() * sizeof(IcpGridHdr), hipMemcpyDeviceToHost));
-    for (int i = 0; i < n_maps; ++i) {
-        const IcpGridHdr &h = hdr[(size_t)i];
-        const size_t m = (size_t)(first_map + i);
-        if (h.nx < 1 || h.ny < 1 || (uint64_t)h.nx * (uint64_t)h.ny > r.cells[m]) return BEV_ERR_INVALID_ARG; /* (not a grid) */
-        off.resize((size_t)h.nx * (size_t)h.ny + 1);
-        HIPCK(c, hipMemcpy(off.data(), r.cell_off + r.off0[m], off.size() * 4, hipMemcpyDeviceToHost));
-        uint32_t largest = 0;
-        for (size_t k = 0; k + 1 < off.size(); ++k) largest = std::max(largest, off[k + 1] - off[k]);
-        out[4 * i] = (uint32_t)h.nx;
-        out[4 * i + 1] = (uint32_t)h.ny;
-        out[4 * i + 2] = h.n;
-        out[4 * i + 3] = largest;
-    }
-    return BEV_OK;
+    const GridRecord &r = c->submap_grid_rec[coarse];
+    if (!r.hdr || (size_t)first_map + (size_t)n_maps > r.items.size()) return BEV_ERR_INVALID_ARG;
+    if (r.buf != stage_buf(c, coarse).p) return BEV_ERR_INVALID_ARG; /* a later call has moved the workspace */
+    return grid_record_read(c, r, first_map, n_maps, out);
 }
 
 } /* extern "C" */

@@ -118,7 +118,7 @@ struct Downloader {
 struct DevBuf {
     void *p = nullptr;
     size_t cap = 0;
-    uint64_t uses = 0; /* calls of grow: every call that lays the buffer out anew (PairGridRecord) */
+    uint64_t uses = 0; /* calls of grow: every call that lays the buffer out anew (GridRecord) */
     int grow(bev_ctx *c, size_t need); /* (waits for the context's stream first: the last call's kernels may still use it) */
     void release();
 };
@@ -158,24 +158,21 @@ struct RegState {
     void release();
 };
 
-/* what bev_debug_get_submap_grid reads: the search grids of the last launch group of the last scan-to-map call of a stage, in
- * that stage's workspace (buf: the workspace's address then; the record holds while it has not moved) */
-struct SubmapGridRecord {
-    const void *buf = nullptr;
-    const IcpGridHdr *hdr = nullptr;  /* [the group's maps] */
+/* what bev_debug_get_submap_grid and bev_debug_get_pair_grid read (grid_record_read, bev_reg_host.h): the search grids that
+ * the last call of a stage left in the stage's workspace.  An item is a map of the call's last launch group (scan-to-map) or a
+ * match of the call (pair).  Each hook has its own rule for a record gone stale: scan-to-map holds while the workspace has not
+ * moved (buf: its address then); pair while no later call has laid the buffer out (uses: DevBuf::uses behind the call's grow) */
+struct GridRecord {
+    const IcpGridHdr *hdr = nullptr;
     const uint32_t *cell_off = nullptr;
-    std::vector<uint64_t> off0;       /* a map's first offset word behind cell_off */
-    std::vector<uint64_t> cells;      /* the cells its offsets have room for */
-};
-
-/* what bev_debug_get_pair_grid reads: the search grids of the targets of the last pair call of a stage, in that stage's
- * workspace (uses: DevBuf::uses behind the call's own grow; the record holds while no later call has laid the buffer out) */
-struct PairGridRecord {
+    struct Item {
+        uint64_t hdr;   /* its header's index behind hdr */
+        uint64_t off0;  /* its first offset word behind cell_off */
+        uint64_t cells; /* the cells its offsets have room for */
+    };
+    std::vector<Item> items;
+    const void *buf = nullptr;
     uint64_t uses = 0;
-    const IcpGridHdr *hdr = nullptr;    /* [the call's slots] */
-    const uint32_t *cell_off = nullptr; /* a slot's offsets at slot * off_words */
-    uint64_t off_words = 0;
-    std::vector<uint32_t> match_slot;   /* the target slot of every match of the call */
 };
 
 } // namespace bevh
@@ -270,10 +267,10 @@ struct bev_ctx {
     /* bev_set_submap_search_grid: the cap of cells per axis of the maps' search grids, fine and coarse stage;
      * 0: the one-workgroup grids of 128 x 128 and 64 x 64 cells at most.  [0] fine, [1] coarse, as the records of the hook */
     int submap_grid_cap[2] = {0, 0};
-    bevh::SubmapGridRecord submap_grid_rec[2];
+    bevh::GridRecord submap_grid_rec[2];
     /* bev_set_pair_search_grid: the same for the pair calls' targets; neither setter reads the other's state */
     int pair_grid_cap[2] = {0, 0};
-    bevh::PairGridRecord pair_grid_rec[2];
+    bevh::GridRecord pair_grid_rec[2];
     int posed_group = 0; /* BEV_POSED_GROUP=1 .. 65535: grids per launch group (tests: results do not depend on it); 0: what fits kPosedWsCap */
 
     bevh::RegState reg;

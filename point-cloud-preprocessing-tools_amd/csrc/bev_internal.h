@@ -603,7 +603,8 @@ void launch_submap_top_rows(const void *maps, uint32_t map0, int n_maps, uint32_
 void launch_submap_top_overflow(const void *maps, uint32_t map0, int n_maps, const SubmapPnVoxWork &p, hipStream_t st);
 
 /* ---- a map's search grid sized to the map (bev_submap_grid.h) ----
- * the maps of ONE launch group of a plan with grid_cap > 0: a map's offsets and counters at cell0[its index in the plan] */
+ * the maps of ONE launch group of a plan with grid_cap > 0: a map's offsets and counters at cell0[its index in the plan];
+ * the pair calls' targets (§6t) in the same terms */
 constexpr uint32_t kSubgridParts = 256;     /* workgroups over a map's points at most (bevsubreg::kGridParts) */
 constexpr uint32_t kSubgridScanParts = 256; /* tiles of 4096 cells of a map at most (bevsubreg::kGridScanParts) */
 struct SubmapGridWork {
@@ -615,18 +616,17 @@ struct SubmapGridWork {
     uint32_t *part_sum;     /* [the group's maps][kSubgridScanParts] */
     const uint64_t *cell0;  /* [the plan's maps]    device table */
 };
+/* where the build reads its targets' points, a target's at its pt0: exactly one of the three is set, {pts, recs, rows} */
+struct SubgridSource {
+    const float4 *pts;       /* float4 points (scan-to-map, fine) */
+    const bev_point_t *recs; /* 32-byte records (pair, fine: the slots' voxel clouds) */
+    const float *rows;       /* PointNormal rows (both coarse stages) */
+};
 /* one step of the build for the n_maps maps from map0 on: 0 bounds, 1 header, 2 count, 3 sums, 4 scan, 5 scatter.  parts:
  * workgroups over the largest map's points; tiles: over the largest map's cells; cap: the cap of cells per axis; vh: the maps'
- * point counts (n_out); the points: pts (float4, a map's at its pt0) or, pts == nullptr, PointNormal rows */
-void launch_submap_grid(int step, const void *maps, uint32_t map0, int n_maps, uint32_t parts, uint32_t tiles, int cap,
-                        const SubvoxHdr *vh, const float4 *pts, const float *rows, const SubmapGridWork &w, hipStream_t st);
-/* launch_submap_icp and launch_submap_coarse_icp with t.cell_off the group's offsets and cell0 the plan's table of bases */
-void launch_submap_icp_wide(const FineProblem *probs, int n, const void *maps, uint32_t map0, const FineWork &w,
-                            const SubmapRegWork &t, const uint64_t *cell0, const bev_icp_result_t *coarse, const int32_t *best,
-                            const bev_icp_params_t &prm, bev_icp_result_t *results, hipStream_t st);
-void launch_submap_coarse_icp_wide(const float *pn, size_t stride, const uint32_t *counts, const IcpProblem *probs, int n,
-                                   const void *maps, uint32_t map0, const SubmapCoarseWork &t, const uint64_t *cell0,
-                                   const bev_icp_params_t &prm, bev_icp_result_t *results, hipStream_t st);
+ * point counts (n_out) */
+void launch_subgrid(int step, const void *maps, uint32_t map0, int n_maps, uint32_t parts, uint32_t tiles, int cap,
+                    const SubvoxHdr *vh, const SubgridSource &src, const SubmapGridWork &w, hipStream_t st);
 
 /* ---- the pair calls' search grids sized to the cloud (bev_pair_grid.h, bev_pair_grid_plan.h) ----
  * maps: the host's table of the call's targets (bevsubreg::Map: pt0 the target's first point, ent0 its slot or frame); the build
@@ -634,9 +634,15 @@ void launch_submap_coarse_icp_wide(const float *pn, size_t stride, const uint32_
 /* the targets' point counts into vh: vox_n[t] (fine), or min(counts[ent0], stride) */
 void launch_pairgrid_desc(const void *maps, int n, const uint32_t *vox_n, const uint32_t *counts, size_t stride, SubvoxHdr *vh,
                           hipStream_t st);
-/* launch_submap_grid over targets: their points are recs (32-byte records) or, recs == nullptr, PointNormal rows */
-void launch_pair_grid(int step, const void *maps, uint32_t t0, int n, uint32_t parts, uint32_t tiles, int cap, const SubvoxHdr *vh,
-                      const bev_point_t *recs, const float *rows, const SubmapGridWork &w, hipStream_t st);
+
+/* ---- the ICP loops against a grid of either build (bev_wide_icp.h) ---- */
+/* launch_submap_icp and launch_submap_coarse_icp with t.cell_off the group's offsets and cell0 the plan's table of bases */
+void launch_submap_icp_wide(const FineProblem *probs, int n, const void *maps, uint32_t map0, const FineWork &w,
+                            const SubmapRegWork &t, const uint64_t *cell0, const bev_icp_result_t *coarse, const int32_t *best,
+                            const bev_icp_params_t &prm, bev_icp_result_t *results, hipStream_t st);
+void launch_submap_coarse_icp_wide(const float *pn, size_t stride, const uint32_t *counts, const IcpProblem *probs, int n,
+                                   const void *maps, uint32_t map0, const SubmapCoarseWork &t, const uint64_t *cell0,
+                                   const bev_icp_params_t &prm, bev_icp_result_t *results, hipStream_t st);
 /* launch_fine_icp and launch_icp with w.cell_off the wide table: a slot's offsets at slot * off_words; launch_icp_wide reads
  * w.sorted by FRAME */
 void launch_fine_icp_wide(const FineProblem *probs, int n, const FineWork &w, uint64_t off_words, const bev_icp_result_t *coarse,

@@ -50,8 +50,9 @@
 #include "bev_submap_coarse.h"
 #include "bev_submap_pn_vox.h"
 #include "bev_submap_top.h"
-#include "bev_submap_grid.h"
 #include "bev_pair_grid.h"
+#include "bev_submap_grid.h"
+#include "bev_wide_icp.h"
 
 using namespace bevx;
 

@@ -1,7 +1,8 @@
 /*
  * bev_reg_host.h — what the two registration files of the C ABI share over bev_ctx.h: bev_capi_reg.hip (the front end and the
  * pair stages) and bev_capi_submap_reg.hip (scan-to-map).  Argument checks, the frame table of a packed or
- * d_ordered buffer, upload tables laid out by carve, and the fine stage's two steps that scan-to-map runs as they are.
+ * d_ordered buffer, upload tables laid out by carve, the host driver of a search grid's build and the reader of the two grid
+ * hooks (§6u), and the fine stage's two steps that scan-to-map runs as they are.
  * Declarations and short inline functions, no state (RegState: bev_ctx.h).  Private.
  */
 #ifndef BEV_REG_HOST_H
@@ -77,6 +78,17 @@ int table_up(bev_ctx *c, UploadTable &t, const size_t (&sz)[N], const void *cons
     carve(t.dev, sz, dst);
     return BEV_OK;
 }
+
+/* ---- search grids sized to the target (bev_submap_grid.h; defined in bev_capi_reg.hip) ---- */
+/* the workspace of a stage: 0 fine, 1 coarse, as the hooks count */
+inline DevBuf &stage_buf(bev_ctx *c, int coarse) { return coarse ? c->reg.icp_buf : c->reg.fine_buf; }
+/* the grids of the n targets from t0 on of the table d_maps, on the context's stream: clear_words counters at w.cnt zeroed, then
+ * the build's six steps.  parts, tiles: the caller's launch grids over the largest target's points and cells */
+int search_grid_build(bev_ctx *c, const void *d_maps, uint32_t t0, int n, uint32_t parts, uint32_t tiles, int cap, const SubvoxHdr *vh,
+                      const SubgridSource &src, const SubmapGridWork &w, size_t clear_words);
+/* what both hooks do behind their own argument and staleness checks: the stream waited for, {nx, ny, n, largest cell} of items
+ * first .. first + n - 1 into out; BEV_ERR_INVALID_ARG for an item whose header is not a grid that fits its offsets */
+int grid_record_read(bev_ctx *c, const GridRecord &r, int first, int n, uint32_t *out);
 
 /* ---- of the fine stage (bev_capi_reg.hip) ---- */
 /* the voxel clouds of U slots, in launches of kFineVoxelGroup, on the context's stream */

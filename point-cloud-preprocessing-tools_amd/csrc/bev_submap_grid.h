@@ -16,8 +16,8 @@
  *                                        the counters turned into the cells' cursors; the last tile: offsets[nx * ny], hdr.n
  *   k_subgrid_points   per (part, map) : scattering: every finite point takes a position from its cell's cursor and goes to
  *                                        the searchable points as (x, y, z, index bits)
- * then k_submap_icp_wide / k_submap_coarse_icp_wide: the loops of k_submap_icp and k_submap_coarse_icp with a map's offsets at
- * its cell base (a plan table) and, for the coarse one, read from global memory.
+ * then the ICP loops against such a grid: bev_wide_icp.h.  The pair calls run the same six launches over their target slots
+ * (bev_pair_grid.h; §6t): one launcher, launch_subgrid, takes the points as float4, as 32-byte records or as PointNormal rows.
  * The phases meet only through the order of launches on the call's stream: no workgroup waits for another.  The order of the
  * points inside a cell depends on the atomics; icp_nn's result does not (lowest index on equal distance).  No float or double sum
  * depends on an atomic: the integer counts and cursors do.  A map's n is known on the device only: the launch grids are the
@@ -27,6 +27,7 @@
 #ifndef BEV_SUBMAP_GRID_H
 #define BEV_SUBMAP_GRID_H
 
+#include "bev_pair_grid.h" /* PairgridRecs */
 #include "bev_submap_reg_plan.h"
 
 namespace bevk {
@@ -238,92 +239,6 @@ __global__ __launch_bounds__(kRegThreads) void k_subgrid_scan(uint32_t map0, Sub
     }
 }
 
-/* ---- the ICP loops against a wide grid ---- */
-
-/* k_submap_icp (bev_submap_reg.h) with the map's cell offsets at its cell base */
-__global__ __launch_bounds__(kFineThreads) void k_submap_icp_wide(const FineProblem *probs, const bevsubreg::Map *maps,
-                                                                  uint32_t map0, FineWork w, SubmapRegWork t,
-                                                                  const uint64_t *cell0, const bev_icp_result_t *coarse,
-                                                                  const int32_t *best, bev_icp_params_t prm,
-                                                                  bev_icp_result_t *results)
-{
-    __shared__ FineShared sh;
-    const FineProblem pb = probs[blockIdx.x];
-    const uint64_t pt0 = maps[pb.tgt_slot].pt0;
-    const uint32_t g = pb.tgt_slot - map0;
-    float G[16];
-    fine_guess(pb, coarse, best, G);
-    fine_icp_problem(sh, w.vox_n[pb.src_slot], w.vox + (size_t)pb.src_slot * w.Pn, SubregPts{t.pts + pt0}, t.hdr[g],
-                     t.cell_off + cell0[pb.tgt_slot], t.sorted + pt0, w.cur + (size_t)blockIdx.x * w.Pn,
-                     w.corr + (size_t)blockIdx.x * w.Pn, G, prm, results + pb.result);
-}
-
-/* submap_coarse_problem (bev_submap_coarse.h), statement for statement, but that the cell offsets stay in global memory:
- * IcpShared::off holds 64 x 64 cells.  A COPY for the reason given there; sh.off is not used (icp_step takes an IcpShared). */
-__device__ __forceinline__ void submap_coarse_problem_wide(IcpShared &sh, uint32_t n_src, const float *src, const float *tgt,
-                                                           const float4 *tpts, const IcpGridHdr *hdr, const uint32_t *goff,
-                                                           float4 *cur, const float *guess, const bev_icp_params_t &prm,
-                                                           bev_icp_result_t *result)
-{
-    const int tid = threadIdx.x;
-    if (tid == 0) sh.hdr = *hdr;
-    __syncthreads();
-    const IcpGridHdr h = sh.hdr;
-    reg_start(sh.loop, guess, n_src, IcpRows{src}, cur);
-    __syncthreads();
-    const double D2 = prm.max_correspondence_distance * prm.max_correspondence_distance;
-    double prev = 1.7976931348623157e308; /* DBL_MAX (thread 0's copy is the one used) */
-    while (true) {
-        reg_pass<0, 28>(sh.sums, n_src, [&](uint32_t i, float *, double *t) -> bool {
-            const float4 s = cur[i];
-            if (!finite3(s.x, s.y, s.z)) return false;
-            float d;
-            uint32_t j;
-            if (!icp_nn(h, goff, tpts, s.x, s.y, s.z, D2, d, j) || !((double)d <= D2)) return false;
-            const float4 tp = *reinterpret_cast<const float4 *>(tgt + (size_t)j * 12);
-            const float4 tn = *reinterpret_cast<const float4 *>(tgt + (size_t)j * 12 + 4);
-            const float nx = tn.x, ny = tn.y, nz = tn.z;
-            if (finite3(nx, ny, nz)) {
-                const float a = nz * s.y - ny * s.z, b = nx * s.z - nz * s.x, c = ny * s.x - nx * s.y;
-                const float dd = ((((nx * tp.x + ny * tp.y) + nz * tp.z) - nx * s.x) - ny * s.y) - nz * s.z;
-                const double r[6] = {a, b, c, nx, ny, nz};
-                int k = 0;
-#pragma unroll
-                for (int u = 0; u < 6; ++u)
-#pragma unroll
-                    for (int v = u; v < 6; ++v) t[k++] = r[u] * r[v];
-#pragma unroll
-                for (int u = 0; u < 6; ++u) t[21 + u] = r[u] * (double)dd;
-            }
-            t[27] = (double)d;
-            return true;
-        });
-        if (tid == 0) {
-            if (sh.sums.cnt < 3) sh.loop.state = 5; /* NO_CORRESPONDENCES */
-            else icp_step(sh, prm, prev);
-        }
-        __syncthreads();
-        if (sh.loop.state != 0) break;
-        reg_advance(sh.loop, n_src, cur);
-    }
-    reg_finish(sh.sums, sh.loop, n_src, IcpRows{src}, h, goff, tpts, result);
-}
-
-/* k_submap_coarse_icp (bev_submap_coarse.h) with the map's cell offsets at its cell base, in global memory */
-__global__ __launch_bounds__(kIcpThreads) void k_submap_coarse_icp_wide(const float *pn, size_t stride, const uint32_t *counts,
-                                                                        const IcpProblem *probs, const bevsubreg::Map *maps,
-                                                                        uint32_t map0, SubmapCoarseWork t, const uint64_t *cell0,
-                                                                        bev_icp_params_t prm, bev_icp_result_t *results)
-{
-    __shared__ IcpShared sh;
-    const IcpProblem pb = probs[blockIdx.x];
-    const uint64_t pt0 = maps[pb.tgt_slot].pt0;
-    const uint32_t g = pb.tgt_slot - map0;
-    submap_coarse_problem_wide(sh, min(counts[pb.src_frame], (uint32_t)stride), pn + (size_t)pb.src_frame * stride * 12,
-                               t.rows + pt0 * 12, t.sorted + pt0, t.hdr + g, t.cell_off + cell0[pb.tgt_slot],
-                               t.cur + (size_t)blockIdx.x * stride, pb.guess, prm, results + pb.result);
-}
-
 /* ---- launchers ---- */
 template <class Fetch>
 static void subgrid_launches(const bevsubreg::Map *maps, uint32_t map0, int n_maps, uint32_t parts, uint32_t tiles, int cap,
@@ -340,33 +255,16 @@ static void subgrid_launches(const bevsubreg::Map *maps, uint32_t map0, int n_ma
     }
 }
 
-void launch_submap_grid(int step, const void *maps, uint32_t map0, int n_maps, uint32_t parts, uint32_t tiles, int cap,
-                        const SubvoxHdr *vh, const float4 *pts, const float *rows, const SubmapGridWork &w, hipStream_t st)
+void launch_subgrid(int step, const void *maps, uint32_t map0, int n_maps, uint32_t parts, uint32_t tiles, int cap,
+                    const SubvoxHdr *vh, const SubgridSource &src, const SubmapGridWork &w, hipStream_t st)
 {
     if (n_maps <= 0) return;
     parts = std::min(std::max(parts, 1u), kSubgridParts);
     tiles = std::min(std::max(tiles, 1u), kSubgridScanParts);
     const bevsubreg::Map *mp = static_cast<const bevsubreg::Map *>(maps);
-    if (pts) subgrid_launches(mp, map0, n_maps, parts, tiles, cap, vh, SubgridPts{pts}, w, step, st);
-    else subgrid_launches(mp, map0, n_maps, parts, tiles, cap, vh, SubgridRows{rows}, w, step, st);
-}
-
-void launch_submap_icp_wide(const FineProblem *probs, int n, const void *maps, uint32_t map0, const FineWork &w,
-                            const SubmapRegWork &t, const uint64_t *cell0, const bev_icp_result_t *coarse, const int32_t *best,
-                            const bev_icp_params_t &prm, bev_icp_result_t *results, hipStream_t st)
-{
-    if (n > 0)
-        hipLaunchKernelGGL(k_submap_icp_wide, dim3(n), dim3(kFineThreads), 0, st, probs, static_cast<const bevsubreg::Map *>(maps),
-                           map0, w, t, cell0, coarse, best, prm, results);
-}
-
-void launch_submap_coarse_icp_wide(const float *pn, size_t stride, const uint32_t *counts, const IcpProblem *probs, int n,
-                                   const void *maps, uint32_t map0, const SubmapCoarseWork &t, const uint64_t *cell0,
-                                   const bev_icp_params_t &prm, bev_icp_result_t *results, hipStream_t st)
-{
-    if (n > 0)
-        hipLaunchKernelGGL(k_submap_coarse_icp_wide, dim3(n), dim3(kIcpThreads), 0, st, pn, stride, counts, probs,
-                           static_cast<const bevsubreg::Map *>(maps), map0, t, cell0, prm, results);
+    if (src.pts) subgrid_launches(mp, map0, n_maps, parts, tiles, cap, vh, SubgridPts{src.pts}, w, step, st);
+    else if (src.recs) subgrid_launches(mp, map0, n_maps, parts, tiles, cap, vh, PairgridRecs{src.recs}, w, step, st);
+    else subgrid_launches(mp, map0, n_maps, parts, tiles, cap, vh, SubgridRows{src.rows}, w, step, st);
 }
 
 } /* namespace bevk */

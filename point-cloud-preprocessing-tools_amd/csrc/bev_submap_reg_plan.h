@@ -131,6 +131,7 @@ struct Group {
     uint32_t map0 = 0, n_maps = 0;   /* [map0, map0 + n_maps) of Plan::maps */
     uint32_t prob0 = 0, n_probs = 0; /* [prob0, prob0 + n_probs) of Plan::probs */
     uint64_t pts = 0;                /* points its maps can hold together */
+    uint64_t max_cap = 0;            /* the largest map_cap among its maps: it sizes the launches over a map's points */
     uint64_t bytes = 0;              /* sum of map_bytes over its maps */
     uint64_t keys = 0;               /* union_voxel: sort keys of its maps together (bevsubvox::key_slots of each) */
     uint64_t max_slots = 0;          /* union_voxel: the largest key array among its maps: it sizes the sort's launches */
@@ -328,6 +329,7 @@ inline Plan plan_call(const Call &call, const Options &opt, uint64_t cap_bytes)
                 g.max_cells = std::max(g.max_cells, cells);
             }
             g.pts += p.map_cap[u];
+            g.max_cap = std::max(g.max_cap, p.map_cap[u]);
             g.bytes += b;
             ++g.n_maps;
             ++u;

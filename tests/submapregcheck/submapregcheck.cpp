@@ -6,7 +6,8 @@
  *   maps      the used maps, ascending; a map's entries are the call's, IN MAP ORDER, each with its frame's slot and its
  *             matrix bit for bit; its capacity is the sum of its entries' record counts;
  *   groups    consecutive maps, all of them once; a group's bytes are within the cap unless it is one map; a map's points
- *             [pt0, pt0 + capacity) lie inside its group's points and overlap no other map's;
+ *             [pt0, pt0 + capacity) lie inside its group's points and overlap no other map's; max_cap is the largest
+ *             capacity among the group's maps;
  *   problems  every match is in exactly one group, the group of its map, with its own index as the result and its query's
  *             slot; a group's problems are contiguous.
  * Prints one "ok:" line, or "PLAN ..." lines and exits 1.  Tests only.
@@ -114,13 +115,15 @@ int main()
                 ++groups;
                 CHECK(g.map0 == next_map && g.n_maps >= 1 && g.map0 + g.n_maps <= p.maps.size(), "call %d: a group starts at map %u", call, g.map0);
                 CHECK(g.prob0 == next_prob && (size_t)g.prob0 + g.n_probs <= p.probs.size(), "call %d: a group's problems start at %u", call, g.prob0);
-                uint64_t bytes = 0, pts = 0;
+                uint64_t bytes = 0, pts = 0, largest = 0;
                 for (uint32_t u = g.map0; u < g.map0 + g.n_maps && u < p.maps.size(); ++u) {
                     CHECK(p.maps[u].pt0 == pts, "call %d: map %u lies at %llu, expected %llu", call, u, (unsigned long long)p.maps[u].pt0, (unsigned long long)pts);
                     pts += p.map_cap[u];
                     bytes += map_bytes(p.map_cap[u]);
+                    largest = std::max(largest, p.map_cap[u]);
                 }
                 CHECK(g.pts == pts && g.bytes == bytes, "call %d: a group's size", call);
+                CHECK(g.max_cap == largest, "call %d: a group's largest map holds %llu, max_cap says %llu", call, (unsigned long long)largest, (unsigned long long)g.max_cap);
                 CHECK(bytes <= cap || g.n_maps == 1, "call %d: a group of %u maps above the cap", call, g.n_maps);
                 if (bytes > cap) ++oversize;
                 /* greedy: the next map did not fit */
