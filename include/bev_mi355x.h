@@ -931,6 +931,33 @@ int bev_debug_get_code_overflow(bev_ctx_t *ctx, int first_frame, int n_frames, u
  * device for n (dx,dy,dz) triples given as HOST arrays; out[i] = 1 if GROUND. */
 int bev_debug_angle_predicate(bev_ctx_t *ctx, const float *dx, const float *dy,
                               const float *dz, uint8_t *out, size_t n);
+/* Test hook: one function of the arithmetic that host and device share (csrc/bev_exact.h, bev_libm.h, bev_libm_f64.h),
+ * named by id, evaluated on the device for n elements given as HOST arrays.  Synchronous; its allocations are its own, so
+ * it moves no workspace and leaves the other hooks' state alone.  in0..in3: element i of each array the id reads (f: float,
+ * u: uint32_t, d: double; arrays the id does not read may be NULL); params: the floats the id takes once per call (NULL
+ * where it takes none); out: one 32-bit word per element (an int, or a float's bits), two for a double (low word first),
+ * three floats for BEV_EVAL_TRANSFORM_XYZ.  BEV_ERR_INVALID_ARG, with out untouched, for a NULL context, out, needed array
+ * or needed params, an unknown id, and n above BEV_EVAL_MAX_N; n == 0 is BEV_OK.
+ *   FD_ATANF f(x) | FD_ATAN2F f(y) f(x) | KITTI_AZIMUTH f(x) f(y) | KITTI_COL f(az) | KITTI_CROSSING f(az_prev) f(az)
+ *   PROJECT_MULRAN u(k) f(x) f(y) and PROJECT_OXFORD f(x) f(y) f(z): row | col << 16
+ *   FD_SIN, FD_COS d(x) | CVTT_F32 f(v) | CVTT_F64 d(v) | FLOOR_HALF_TO_INT f(nx) | GROUND_CELL f(x) f(y)
+ *   ROUND_HALF_UP_BIN f(v) | HEIGHT_TIMES4 f(t) | BIN_IN_RANGE, BIN_OF_SHIFTED f(v) u(M): bin | in << 31
+ *   BEV_BIN f(p) f(MAX_RANGE) f(interval) | COUNT_ADVANCE f(c) u(n), c >= 0.01f finite and n < 2^24 | EXACT_RECIPROCAL f(v)
+ *   ANGLE_NODIV, ANGLE f(dx) f(dy) f(dz) | TRANSFORM_XYZ f(x) f(y) f(z), params: 12 floats of a row-major [R | t]
+ *   DEGREES_OF f(rad) | WRAP_AZIMUTH f(az) | TO_U16 f(v)
+ *   BEV_CODE f(px) f(py) f(pz), params: MAX_RANGE, interval, HEIGHT_RES, lidar_to_ground, n_layers: the code of label 1
+ *   KITTI_COL_XY f(x) f(y): KITTI_COL of KITTI_AZIMUTH */
+enum {
+    BEV_EVAL_FD_ATANF = 0, BEV_EVAL_FD_ATAN2F, BEV_EVAL_KITTI_AZIMUTH, BEV_EVAL_KITTI_COL, BEV_EVAL_KITTI_CROSSING,
+    BEV_EVAL_PROJECT_MULRAN, BEV_EVAL_PROJECT_OXFORD, BEV_EVAL_FD_SIN, BEV_EVAL_FD_COS, BEV_EVAL_CVTT_F32, BEV_EVAL_CVTT_F64,
+    BEV_EVAL_FLOOR_HALF_TO_INT, BEV_EVAL_GROUND_CELL, BEV_EVAL_ROUND_HALF_UP_BIN, BEV_EVAL_HEIGHT_TIMES4, BEV_EVAL_BIN_IN_RANGE,
+    BEV_EVAL_BIN_OF_SHIFTED, BEV_EVAL_BEV_BIN, BEV_EVAL_COUNT_ADVANCE, BEV_EVAL_EXACT_RECIPROCAL, BEV_EVAL_ANGLE_NODIV,
+    BEV_EVAL_ANGLE, BEV_EVAL_TRANSFORM_XYZ, BEV_EVAL_DEGREES_OF, BEV_EVAL_WRAP_AZIMUTH, BEV_EVAL_TO_U16, BEV_EVAL_BEV_CODE,
+    BEV_EVAL_KITTI_COL_XY, BEV_EVAL_COUNT
+};
+#define BEV_EVAL_MAX_N ((size_t)1 << 24)
+int bev_debug_exact_eval(bev_ctx_t *ctx, int id, size_t n, const void *in0, const void *in1, const void *in2,
+                         const void *in3, const float *params, void *out);
 
 /* Test hook: the search grids of the LAST launch group of the last fine (coarse == 0) or coarse (coarse == 1) scan-to-map call
  * with matches, whichever path built them.  Synchronises.  out[4 * i .. 4 * i + 3] = { nx, ny, searchable points, largest count

@@ -86,7 +86,7 @@ ABI_SYMBOLS = [
     "bev_order_cloud", "bev_mark_ground", "bev_multi_bev", "bev_single_bev",
     "bev_float_bev", "bev_float_bev_size", "bev_transform_cloud", "bev_yaw_translate_matrix", "bev_project_xyzi", "bev_project_out_points", "bev_host_alloc", "bev_host_free",
     "bev_set_lanes", "bev_set_layout_hint", "bev_profile_enable", "bev_profile_reset", "bev_profile_get",
-    "bev_debug_get_cell_avg", "bev_debug_get_frame_info", "bev_debug_get_code_overflow", "bev_debug_angle_predicate", "bev_abi_version",
+    "bev_debug_get_cell_avg", "bev_debug_get_frame_info", "bev_debug_get_code_overflow", "bev_debug_angle_predicate", "bev_debug_exact_eval", "bev_abi_version",
     "bev_top_part_flatten", "bev_voxel_grid_xyz", "bev_normals_2d", "bev_registration_front_device_resident",
     "bev_regfront_max_out",
     "bev_icp_coarse_defaults", "bev_icp_point_to_plane", "bev_coarse_registration_device_resident",
@@ -107,6 +107,23 @@ ABI_SYMBOLS = [
     "bev_set_submap_search_grid", "bev_debug_get_submap_grid",
     "bev_set_pair_search_grid", "bev_debug_get_pair_grid",
 ]
+
+# bev_debug_exact_eval (include/bev_mi355x.h, BEV_EVAL_* in id order): name -> (input kinds f / u / d, output kind, params)
+EXACT_EVAL = {
+    "fd_atanf": ("f", "f", 0), "fd_atan2f": ("ff", "f", 0), "kitti_azimuth": ("ff", "f", 0), "kitti_col": ("f", "i", 0),
+    "kitti_crossing": ("ff", "i", 0), "project_mulran": ("uff", "u", 0), "project_oxford": ("fff", "u", 0),
+    "fd_sin": ("d", "d", 0), "fd_cos": ("d", "d", 0), "cvtt_f32": ("f", "i", 0), "cvtt_f64": ("d", "i", 0),
+    "floor_half_to_int": ("f", "i", 0), "ground_cell": ("ff", "i", 0), "round_half_up_bin": ("f", "i", 0),
+    "height_times4": ("f", "i", 0), "bin_in_range": ("fu", "u", 0), "bin_of_shifted": ("fu", "u", 0),
+    "bev_bin": ("fff", "i", 0), "count_advance": ("fu", "f", 0), "exact_reciprocal": ("f", "f", 0),
+    "angle_is_ground_nodiv": ("fff", "i", 0), "angle_is_ground": ("fff", "i", 0), "transform_xyz": ("fff", "f3", 12),
+    "degrees_of": ("f", "f", 0), "wrap_azimuth": ("f", "f", 0), "to_u16": ("f", "i", 0), "bev_code": ("fff", "u", 5),
+    "kitti_col_xy": ("ff", "i", 0),
+}
+EXACT_EVAL_NAMES = list(EXACT_EVAL)
+EXACT_EVAL_MAX_N = 1 << 24  # BEV_EVAL_MAX_N
+_EVAL_IN = {"f": np.float32, "u": np.uint32, "d": np.float64}
+_EVAL_OUT = {"f": np.float32, "i": np.int32, "u": np.uint32, "d": np.float64, "f3": np.float32}
 
 # registration front end (include/bev_mi355x.h): pcl::PointXYZ, pcl::Normal, pcl::PointNormal as float rows
 XYZ_FLOATS, NORMAL_FLOATS, POINT_NORMAL_FLOATS = 4, 8, 12
@@ -198,6 +215,8 @@ def load_lib() -> C.CDLL:
     if hasattr(lib, "bev_debug_get_code_overflow"):  # (absent from older builds selected through BEV_AMD_LIB for A/B runs)
         lib.bev_debug_get_code_overflow.argtypes = [vp, i32, i32, vp]
     lib.bev_debug_angle_predicate.argtypes = [vp, vp, vp, vp, vp, sz]
+    if hasattr(lib, "bev_debug_exact_eval"):  # (absent from older builds selected through BEV_AMD_LIB)
+        lib.bev_debug_exact_eval.argtypes = [vp, i32, sz, vp, vp, vp, vp, vp, vp]
     lib.bev_abi_version.restype = i32
     if hasattr(lib, "bev_registration_front_device_resident"):  # (absent from older builds selected through BEV_AMD_LIB)
         lib.bev_top_part_flatten.argtypes = [vp, vp, u32, vp, C.POINTER(u32)]
@@ -988,6 +1007,25 @@ class BevContext:
         out = np.empty(dx.shape[0], dtype=np.uint8)
         self._check(self.lib.bev_debug_angle_predicate(self._h, _ptr(dx), _ptr(dy), _ptr(dz), _ptr(out), dx.shape[0]),
                     "bev_debug_angle_predicate")
+        return out
+
+    def exact_eval(self, fn, *inputs, params=None):
+        """bev_debug_exact_eval: function `fn` (a name of EXACT_EVAL, or its id) of the shared host/device arithmetic on
+        the device, element by element.  inputs: the arrays of EXACT_EVAL[fn] in order; returns int32, uint32, float32,
+        float64 or (n, 3) float32 as the function does."""
+        name = fn if isinstance(fn, str) else EXACT_EVAL_NAMES[fn]
+        kinds, out_kind, n_params = EXACT_EVAL[name]
+        if len(inputs) != len(kinds):
+            raise BevError(f"exact_eval({name}) takes {len(kinds)} arrays")
+        arrs = [np.ascontiguousarray(a, dtype=_EVAL_IN[k]) for a, k in zip(inputs, kinds)]
+        n = arrs[0].shape[0]
+        if any(a.shape != (n,) for a in arrs):
+            raise BevError("exact_eval: the arrays differ in length")
+        prm = None if not n_params else np.ascontiguousarray(params, dtype=np.float32).reshape(n_params)
+        out = np.zeros((n, 3) if out_kind == "f3" else n, dtype=_EVAL_OUT[out_kind])
+        ptrs = [_ptr(a) for a in arrs] + [None] * (4 - len(arrs))
+        self._check(self.lib.bev_debug_exact_eval(self._h, EXACT_EVAL_NAMES.index(name), n, *ptrs,
+                                                  _ptr(prm) if prm is not None else None, _ptr(out)), "bev_debug_exact_eval")
         return out
 
 

@@ -18,6 +18,7 @@
 
 #include "bev_ctx.h"
 #include "bev_libm.h"
+#include "bev_exact_eval.h"
 
 using namespace bevk;
 using namespace bevh;
@@ -1272,6 +1273,54 @@ int bev_debug_angle_predicate(bev_ctx_t *c, const float *dx, const float *dy, co
         ck(hipGetLastError(), __LINE__);
         ck(hipStreamSynchronize(c->stream), __LINE__);
         ck(hipMemcpy(out, o, n, hipMemcpyDeviceToHost), __LINE__);
+    }
+    (void)hipFree(d);
+    (void)hipFree(o);
+    return rc;
+}
+
+static_assert(BEV_EVAL_COUNT == bevx::kEvCount && BEV_EVAL_FD_SIN == bevx::kEvFdSin && BEV_EVAL_BEV_BIN == bevx::kEvBevBin &&
+                  BEV_EVAL_BEV_CODE == bevx::kEvBevCode && BEV_EVAL_KITTI_COL_XY == bevx::kEvKittiColXy && BEV_EVAL_MAX_N == bevx::kEvMaxN, "the header's ids are bev_exact_eval.h's");
+/* like bev_debug_angle_predicate: its own allocations, no begin_call — no workspace moves, no hook goes stale */
+int bev_debug_exact_eval(bev_ctx_t *c, int id, size_t n, const void *in0, const void *in1, const void *in2, const void *in3,
+                         const float *params, void *out)
+{
+    const bevx::ExactEvalSig sig = bevx::exact_eval_sig(id);
+    const void *const in[4] = {in0, in1, in2, in3};
+    if (!c || !out || sig.out_words == 0 || n > bevx::kEvMaxN || (sig.params && !params)) return BEV_ERR_INVALID_ARG;
+    size_t off[5] = {0, 0, 0, 0, 0}; /* the arrays back to back (the only 8-byte words are a first array's: all stay aligned) */
+    for (int k = 0; k < 4; ++k) {
+        if (sig.in[k] != bevx::kEvNone && !in[k]) return BEV_ERR_INVALID_ARG;
+        off[k + 1] = off[k] + n * bevx::exact_eval_word_bytes(sig.in[k]);
+    }
+    if (n == 0) return BEV_OK;
+    HIPCK(c, hipSetDevice(c->device));
+    char *d = nullptr;
+    uint32_t *o = nullptr;
+    const size_t out_bytes = n * sig.out_words * sizeof(uint32_t);
+    HIPCK(c, hipMalloc((void **)&d, off[4]));
+    hipError_t e = hipMalloc((void **)&o, out_bytes);
+    if (e != hipSuccess) {
+        (void)hipFree(d);
+        return hip_fail(c, e, "hipMalloc", __LINE__);
+    }
+    int rc = BEV_OK;
+    auto ck = [&](hipError_t err, int line) {
+        if (err != hipSuccess && rc == BEV_OK) rc = hip_fail(c, err, "bev_debug_exact_eval", line);
+    };
+    const void *dev[4] = {nullptr, nullptr, nullptr, nullptr};
+    for (int k = 0; k < 4; ++k) {
+        if (sig.in[k] == bevx::kEvNone) continue;
+        dev[k] = d + off[k];
+        ck(hipMemcpy(d + off[k], in[k], off[k + 1] - off[k], hipMemcpyHostToDevice), __LINE__);
+    }
+    if (rc == BEV_OK) {
+        float prm[bevx::kEvParams] = {};
+        for (int k = 0; k < sig.params; ++k) prm[k] = params[k];
+        launch_exact_eval(id, dev, prm, o, sig.out_words, n, c->stream);
+        ck(hipGetLastError(), __LINE__);
+        ck(hipStreamSynchronize(c->stream), __LINE__);
+        if (rc == BEV_OK) ck(hipMemcpy(out, o, out_bytes, hipMemcpyDeviceToHost), __LINE__);
     }
     (void)hipFree(d);
     (void)hipFree(o);

@@ -370,6 +370,8 @@ void launch_submap_splat(const bev_point_t *clouds, const void *rows, const uint
 void launch_submap_float_splat(const bev_point_t *clouds, const void *rows, const uint32_t *ent0, int nf, uint32_t blocks,
                                const void *entries, float interval, int M, bool skip_label0, float *grids, hipStream_t st);
 void launch_angle_debug(const float *dx, const float *dy, const float *dz, uint8_t *out, size_t n, hipStream_t st);
+/* element i of function `id` (bev_exact_eval.h) for i < n: in its device arrays, prm its 12 floats (nullptr: zeros), out n * out_words words */
+void launch_exact_eval(int id, const void *const in[4], const float *prm, uint32_t *out, uint32_t out_words, size_t n, hipStream_t st);
 /* ---- registration front end (bev_regfront.h; DESIGN.md "Registration front end") ---- */
 constexpr int kRfThreads = 256;
 constexpr int kRfGrid = 10;                  /* NUM_GRID_X / NUM_GRID_Y of extractTopAndFlatten (TopPartRegistration.cpp:83-84) */

@@ -341,5 +341,13 @@ void launch_angle_debug(const float *dx, const float *dy, const float *dz, uint8
     if (n == 0) return;
     hipLaunchKernelGGL(k_angle_debug, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dx, dy, dz, out, n);
 }
+void launch_exact_eval(int id, const void *const in[4], const float *prm, uint32_t *out, uint32_t out_words, size_t n, hipStream_t st)
+{
+    if (n == 0) return;
+    ExactEvalArgs a{};
+    for (int k = 0; k < 4; ++k) a.in[k] = in[k];
+    for (int k = 0; k < kEvParams; ++k) a.prm[k] = prm ? prm[k] : 0.0f;
+    hipLaunchKernelGGL(k_exact_eval, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, id, a, out, out_words, n);
+}
 
 } /* namespace bevk */

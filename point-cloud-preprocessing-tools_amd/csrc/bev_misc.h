@@ -7,6 +7,7 @@
 
 #include "bev_dev.h"
 #include "bev_libm.h"
+#include "bev_exact_eval.h"
 
 namespace bevk {
 using namespace bevx;
@@ -117,6 +118,17 @@ __global__ __launch_bounds__(256) void k_angle_debug(const float *dx, const floa
 {
     const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
     if (i < n) out[i] = angle_is_ground(dx[i], dy[i], dz[i]) ? 1 : 0;
+}
+
+/* test hook: element i of one function of the shared host/device arithmetic, named by id (bev_exact_eval.h) */
+struct ExactEvalArgs {
+    const void *in[4];
+    float prm[kEvParams];
+};
+__global__ __launch_bounds__(256) void k_exact_eval(int id, ExactEvalArgs a, uint32_t *out, uint32_t out_words, size_t n)
+{
+    const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (i < n) exact_eval_one(id, a.in, a.prm, i, out + i * out_words);
 }
 
 } /* namespace bevk */
