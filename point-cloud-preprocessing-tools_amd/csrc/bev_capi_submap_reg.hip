@@ -365,8 +365,8 @@ void submap_pn_out(bev_ctx *c, const Group &g, const SubmapCoarse &s, bool vox, 
 {
     const uint32_t parts = (uint32_t)std::min<uint64_t>((3 * g.max_cap + 4 * kIcpThreads - 1) / (4 * kIcpThreads), 256);
     ProfScope ps(c, K_SUBMAP_PN_OUT, (int)g.n_maps);
-    launch_submap_pn_out(s.d.maps, g.map0, (int)g.n_maps, parts, s.p.v.vh, vox ? s.t.rows : s.p.moved, d_out, out_stride,
-                         d_counts_out, c->stream);
+    launch_submap_out(s.d.maps, g.map0, (int)g.n_maps, parts, s.p.v.vh, vox ? s.t.rows : s.p.moved, d_out, out_stride,
+                      d_counts_out, 3, c->stream);
 }
 
 /* a group's entries' rows moved and concatenated into s.p.moved */
@@ -584,8 +584,8 @@ int bev_submap_voxel_cloud_device_resident(bev_ctx_t *c, int n_frames, const bev
         BEVCK(submap_fine_targets(c, g, opt, s, map_leaf));
         const uint32_t parts = (uint32_t)std::min<uint64_t>((g.max_cap + 4 * kFineThreads - 1) / (4 * kFineThreads), 256);
         ProfScope ps(c, K_SUBMAP_VOX_OUT, (int)g.n_maps);
-        launch_submap_vox_out(s.d.maps, g.map0, (int)g.n_maps, parts, s.v.vh, opt.union_voxel ? s.t.pts : s.v.moved,
-                              reinterpret_cast<float4 *>(d_out), out_stride, d_counts, c->stream);
+        launch_submap_out(s.d.maps, g.map0, (int)g.n_maps, parts, s.v.vh, opt.union_voxel ? s.t.pts : s.v.moved, d_out,
+                          out_stride, d_counts, 1, c->stream);
     }
     HIPCK(c, hipGetLastError());
     return record_tail(c);

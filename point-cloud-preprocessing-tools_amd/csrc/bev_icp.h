@@ -21,16 +21,6 @@
 
 namespace bevk {
 
-/* a PointNormal row's position */
-struct IcpRows {
-    const float *rows;
-    __device__ float3 operator()(uint32_t i) const
-    {
-        const float4 p = *reinterpret_cast<const float4 *>(rows + (size_t)i * 12);
-        return make_float3(p.x, p.y, p.z);
-    }
-};
-
 __global__ __launch_bounds__(kIcpThreads) void k_icp_grid(const float *pn, size_t stride, const uint32_t *counts,
                                                           const uint32_t *slot_frame, IcpWork w)
 {

@@ -522,9 +522,10 @@ void launch_submap_vox_stage(uint32_t kind, uint32_t k, uint32_t j, uint32_t map
 /* t.pts: the thinned points; t.hdr == nullptr: no search grid (the cloud call) */
 void launch_submap_vox_finish(const void *maps, uint32_t map0, int n_maps, const SubmapVoxWork &v, const SubmapRegWork &t,
                               hipStream_t st);
-/* src: the group's point array that holds the targets (moved or thinned); out, counts: the caller's, indexed by map of the plan */
-void launch_submap_vox_out(const void *maps, uint32_t map0, int n_maps, uint32_t parts, const SubvoxHdr *vh, const float4 *src,
-                           float4 *out, uint64_t stride, uint32_t *counts, hipStream_t st);
+/* the cloud calls of this section and of §6q.  src: the group's array that holds the targets (moved or thinned), rows of
+ * row_f4 float4 (points: 1, PointNormal rows: 3); out, counts: the caller's, indexed by map of the plan, stride in rows */
+void launch_submap_out(const void *maps, uint32_t map0, int n_maps, uint32_t parts, const SubvoxHdr *vh, const void *src,
+                       void *out, uint64_t stride, uint32_t *counts, uint32_t row_f4, hipStream_t st);
 
 /* ---- scan-to-map coarse ICP (bev_submap_coarse.h, bev_submap_reg_plan.h) ----
  * the maps of ONE launch group of the plan: a map's rows at its pt0, its header and cell offsets at its index in the group */
@@ -562,9 +563,6 @@ void launch_submap_pn_normals(const void *maps, uint32_t map0, int n_maps, uint3
                               float pn_leaf, const float vp[2], float *target, hipStream_t st);
 void launch_submap_pn_grid(const void *maps, uint32_t map0, int n_maps, const SubvoxHdr *vh, const SubmapCoarseWork &t,
                            hipStream_t st);
-/* src: the group's row array that holds the targets (moved or thinned); out, counts: the caller's, indexed by map of the plan */
-void launch_submap_pn_out(const void *maps, uint32_t map0, int n_maps, uint32_t parts, const SubvoxHdr *vh, const float *src,
-                          float *out, uint64_t stride, uint32_t *counts, hipStream_t st);
 
 /* ---- the top part over the union of a map's moved full clouds (bev_submap_top.h) ----
  * the maps of ONE launch group of a plan with top_union (and point_normal, union_voxel): a map's rows (SubmapPnVoxWork::moved and

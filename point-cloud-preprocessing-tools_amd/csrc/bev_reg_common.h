@@ -2,11 +2,13 @@
  * bev_reg_common.h — what the registration stages share (included by bev_kernels.hip before bev_regfront.h, bev_icp.h and
  * bev_fine.h):
  *
- *   helpers        finite3, icp_cell, icp_se3, rf_pow2, rf_bitonic
+ *   helpers        finite3, rf_canon, icp_cell, icp_se3, rf_pow2, rf_bitonic; SubregPts / IcpRows: a point's position in a
+ *                  float4 array, in PointNormal rows
  *   voxel grid     rf_voxel_bounds / rf_voxel_keys / rf_voxel_starts: the three steps of pcl::VoxelGrid that k_rf_voxel
- *                  (PointXYZ) and k_fine_voxel (PointXYZIRCT) have in common; sort buffer, centroids and outputs are theirs
+ *                  (PointXYZ), k_fine_voxel (PointXYZIRCT) and the union grids of the scan-to-map calls have in common, and
+ *                  rf_voxel_centroids, the x y z centroids of all but k_fine_voxel; sort buffer and outputs are theirs
  *   search grid    reg_grid_build<kCells>: bounds, header, counts, scan and counting sort of a target cloud (k_icp_grid,
- *                  k_fine_grid), and icp_nn, the exact 1-NN on it
+ *                  k_fine_grid and the scan-to-map targets), and icp_nn, the exact 1-NN on it
  *   ordered pass   RegSums<NF, ND> / reg_pass: the pinned summation order of every sum over a source cloud
  *   loop           RegLoop / reg_start / reg_advance / reg_converge / reg_finish: what k_icp and k_fine_icp do around
  *                  their own estimators
@@ -23,6 +25,28 @@ constexpr int kRegThreads = 256, kRegWaves = kRegThreads / 64;
 static_assert(kRfThreads == kRegThreads && kIcpThreads == kRegThreads && kFineThreads == kRegThreads, "one workgroup shape");
 
 __device__ __forceinline__ bool finite3(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
+
+/* where a cloud's positions lie, one functor per layout (bev_fine.h has the 32-byte records' FinePts): float4 points ... */
+struct SubregPts {
+    const float4 *pts;
+    __device__ float3 operator()(uint32_t i) const
+    {
+        const float4 p = pts[i];
+        return make_float3(p.x, p.y, p.z);
+    }
+};
+/* ... and PointNormal rows of 12 floats */
+struct IcpRows {
+    const float *rows;
+    __device__ float3 operator()(uint32_t i) const
+    {
+        const float4 p = *reinterpret_cast<const float4 *>(rows + (size_t)i * 12);
+        return make_float3(p.x, p.y, p.z);
+    }
+};
+
+/* every NaN as the one quiet NaN the checkers write */
+__device__ __forceinline__ float rf_canon(float f) { return isnan(f) ? __uint_as_float(0x7fc00000u) : f; }
 
 /* cell coordinate: monotone in v, so cell boundaries are ordered (the ring bound relies on that alone) */
 __device__ __forceinline__ int icp_cell(float v, float mn, float inv, int n)
@@ -177,6 +201,26 @@ __device__ uint32_t rf_voxel_starts(const uint64_t *buf, uint32_t nf, uint32_t *
     return base;
 }
 
+/* the nv centroids (AccumulatorXYZ; k_fine_voxel's loop also sums intensity and votes labels): one lane per voxel, x, y, z
+ * of point(input index) summed in key order, that is ascending input index, divided by float(count) */
+template <class Point>
+__device__ __forceinline__ void rf_voxel_centroids(const uint64_t *buf, const uint32_t *vstart, uint32_t nv, Point point,
+                                                   float4 *out)
+{
+    for (uint32_t v = threadIdx.x; v < nv; v += kRegThreads) {
+        const uint32_t a = vstart[v], b = vstart[v + 1];
+        float sx = 0.0f, sy = 0.0f, sz = 0.0f;
+        for (uint32_t q = a; q < b; ++q) {
+            const float4 s = point((uint32_t)buf[q]);
+            sx += s.x;
+            sy += s.y;
+            sz += s.z;
+        }
+        const float cf = (float)(b - a);
+        out[v] = make_float4(sx / cf, sy / cf, sz / cf, 0.0f);
+    }
+}
+
 constexpr int reg_isqrt(int n)
 {
     int r = 0;
@@ -186,9 +230,10 @@ constexpr int reg_isqrt(int n)
 
 /* ---- the 2-D search grid of a target cloud ------------------------------------------------------------------------------- */
 /* over the searchable points (finite x, y, z) of fetch(0 .. n - 1): bounds, a uniform grid of at most dim x dim square
- * cells, dim = min(sqrt(kCells), ceil(sqrt(n))), and a counting sort of the points by cell (x, y, z, index bits) */
+ * cells, dim = min(sqrt(kCells), ceil(sqrt(n))), and a counting sort of the points by cell (x, y, z, index bits).  Inlined
+ * by force: several kernels share an instantiation, and each keeps the code it had as the only caller */
 template <int kCells, class Fetch>
-__device__ void reg_grid_build(uint32_t n, Fetch fetch, IcpGridHdr *hdr_out, uint32_t *off_out, float4 *sorted_out)
+__device__ __forceinline__ void reg_grid_build(uint32_t n, Fetch fetch, IcpGridHdr *hdr_out, uint32_t *off_out, float4 *sorted_out)
 {
     constexpr int kGridMax = reg_isqrt(kCells); /* kIcpGridMax, kFineGridMax */
     static_assert(kGridMax * kGridMax == kCells && kCells % kRegThreads == 0, "a square grid, whole cells per thread");

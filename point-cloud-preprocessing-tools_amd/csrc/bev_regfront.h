@@ -8,9 +8,11 @@
  *   k_rf_top      per (cell, frame): sorts the cell's keys, writes the first round(0.2f * n) points flattened
  *                                    (:113-133)
  *   k_rf_voxel    per frame        : pcl::VoxelGrid<PointXYZ>::applyFilter — bounds, voxel index, stable sort by voxel,
- *                                    one lane sums one voxel's points in input order
+ *                                    one lane sums one voxel's points in input order (the steps are bev_reg_common.h's)
  *   k_rf_normals  per query        : Normal2dEstimation::compute in radius mode (src/Normal2dEstimation.cpp,
  *                                    src/PCA2D.cpp): the neighbours in ascending index order, closed-form 2 x 2 eigenvector
+ *                                    (Normal2d, which k_submap_pn_normals runs too)
+ * rf_top_rank, rf_top_cell and rf_z_desc_key are bev_submap_top.h's too, rf_lower_bound is bev_submap_pn_vox.h's.
  *
  * The contract every line follows (and tests/regfront/regfront_oracle.c restates) is DESIGN.md "Registration front end".
  * No float sum depends on an atomic: counts are atomics (integers), every float sum runs in one lane in a fixed order.
@@ -20,8 +22,6 @@
 #pragma once
 
 namespace bevk {
-
-__device__ __forceinline__ float rf_canon(float f) { return isnan(f) ? __uint_as_float(0x7fc00000u) : f; }
 
 /* 32-bit key whose ascending order is DESCENDING z; -0 and +0 are one value */
 __device__ __forceinline__ uint32_t rf_z_desc_key(float z)
@@ -42,6 +42,12 @@ __device__ __forceinline__ int rf_top_cell(const bev_point_t &p)
     const float gy = roundf((p.y + 100.0f) / 20.0f);
     if (!(gx >= 0.0f && gx < (float)kRfGrid && gy >= 0.0f && gy < (float)kRfGrid)) return -1;
     return (int)gx * kRfGrid + (int)gy;
+}
+
+/* points kept of a cell of n: the highest fifth, none of a cell with fewer than kRfMinCellPoints (:113-133) */
+__device__ __forceinline__ uint32_t rf_top_rank(uint32_t n)
+{
+    return n >= (uint32_t)kRfMinCellPoints ? (uint32_t)roundf(0.2f * (float)n) : 0u;
 }
 
 __device__ __forceinline__ void rf_frame(const RfIn &in, int f, const bev_point_t **p, uint32_t *n)
@@ -82,7 +88,7 @@ __global__ __launch_bounds__(kRfThreads) void k_rf_cells(RfIn in, RfWork w)
             out_off[c] = o;
             fill[c] = off;
             off += cnt[c];
-            if (cnt[c] >= (uint32_t)kRfMinCellPoints) o += (uint32_t)roundf(0.2f * (float)cnt[c]);
+            o += rf_top_rank(cnt[c]);
         }
         cell_off[kRfCells] = off;
         out_off[kRfCells] = o;
@@ -106,6 +112,7 @@ __global__ __launch_bounds__(kRfThreads) void k_rf_top(RfIn in, RfWork w)
     __shared__ uint64_t lds[kRfLdsKeys];
     const int c = (int)blockIdx.x, f = (int)blockIdx.y;
     const uint32_t n = w.cell_cnt[(size_t)f * kRfCells + c];
+    /* (rf_top_rank's rule in this kernel's own two statements, so that its code stays what it was: DESIGN.md §6w) */
     if (n < (uint32_t)kRfMinCellPoints) return;
     const uint32_t k = (uint32_t)roundf(0.2f * (float)n);
     const uint32_t off = w.cell_off[(size_t)f * (kRfCells + 1) + c];
@@ -179,22 +186,11 @@ __global__ __launch_bounds__(kRfThreads) void k_rf_voxel(RfWork w, float leaf, u
         if (counts) counts[f] = nv;
     }
     __syncthreads();
-    /* centroids: one lane per voxel, float sums in ascending input index, divided by float(count) */
-    for (uint32_t v = t; v < nv; v += blockDim.x) {
-        const uint32_t a = vstart[v], b = vstart[v + 1];
-        float sx = 0.0f, sy = 0.0f, sz = 0.0f;
-        for (uint32_t q = a; q < b; ++q) {
-            const float4 s = src[(uint32_t)buf[q]];
-            sx += s.x;
-            sy += s.y;
-            sz += s.z;
-        }
-        const float cf = (float)(b - a);
-        vpts[v] = make_float4(sx / cf, sy / cf, sz / cf, 0.0f);
-    }
+    rf_voxel_centroids(buf, vstart, nv, [src](uint32_t i) { return src[i]; }, vpts);
 }
 
 /* ---- 2-D normals ---------------------------------------------------------------------------------------------------- */
+/* the first of the n ascending voxel indices a that is >= x */
 __device__ __forceinline__ uint32_t rf_lower_bound(const uint32_t *a, uint32_t n, uint64_t x)
 {
     uint32_t lo = 0, hi = n;
@@ -206,41 +202,49 @@ __device__ __forceinline__ uint32_t rf_lower_bound(const uint32_t *a, uint32_t n
     return lo;
 }
 
-/* kPointNormal: pcl::PointNormal records (12 floats) at out + f * out_stride (the chain); else pcl::Normal records
- * (8 floats) at out + f * out_stride.  Neighbours are scanned in ascending index: over all points, or — where the points
- * are voxel centroids sorted by index i + j * div_x (meta.windowed) — over the rows j +- win, a contiguous index range. */
-template <bool kPointNormal>
-__global__ __launch_bounds__(kRfThreads) void k_rf_normals(RfWork w, float r2, uint32_t win, float vpx, float vpy,
-                                                          float *out, size_t out_stride)
-{
-    const int f = (int)blockIdx.y;
-    const RfFrameMeta meta = w.meta[f];
-    const uint32_t nv = meta.nv;
-    const float4 *pts = w.vpts + (size_t)f * w.Q;
-    const uint32_t *vidx = w.vidx + (size_t)f * w.Q;
-    for (uint32_t v = blockIdx.x * blockDim.x + threadIdx.x; v < nv; v += gridDim.x * blockDim.x) {
-        const float4 q = pts[v];
-        uint32_t lo = 0, hi = nv;
-        if (meta.windowed) {
-            const uint32_t j = vidx[v] / meta.div_x;
-            const uint32_t jl = j > win ? j - win : 0u;
-            const uint64_t jh = std::min<uint64_t>((uint64_t)j + win, (uint64_t)meta.div_y - 1u);
-            lo = rf_lower_bound(vidx, nv, (uint64_t)jl * meta.div_x);
-            hi = rf_lower_bound(vidx, nv, (jh + 1u) * meta.div_x);
+/* Normal2dEstimation::compute in radius mode for one query q (src/Normal2dEstimation.cpp, src/PCA2D.cpp), in the steps its two
+ * passes over the candidates need: first() per candidate j (position p) in ascending index; where cnt >= 3, mean() and then
+ * second() per candidate again; then the record (f64 sqrt and division, the flip towards the viewpoint).  k_rf_normals walks a
+ * window in global memory, k_submap_pn_normals (bev_submap_pn_vox.h) chunks staged in LDS. */
+struct Normal2d {
+    float4 q;
+    float r2;
+    uint32_t cnt = 0, n0 = 0, n1 = 0;
+    float sx = 0.0f, sy = 0.0f, mx = 0.0f, my = 0.0f, a = 0.0f, b = 0.0f, c = 0.0f;
+    __device__ __forceinline__ bool near(const float4 p) const
+    {
+        const float dx = p.x - q.x, dy = p.y - q.y, dz = p.z - q.z;
+        return (dx * dx + dy * dy) + dz * dz <= r2;
+    }
+    __device__ __forceinline__ void first(uint32_t j, const float4 p)
+    {
+        if (near(p)) {
+            if (cnt == 0) n0 = j;
+            if (cnt == 1) n1 = j;
+            ++cnt;
+            sx += p.x;
+            sy += p.y;
         }
-        uint32_t cnt = 0, n0 = 0, n1 = 0;
-        float sx = 0.0f, sy = 0.0f;
-        for (uint32_t j = lo; j < hi; ++j) {
-            const float4 p = pts[j];
-            const float dx = p.x - q.x, dy = p.y - q.y, dz = p.z - q.z;
-            if ((dx * dx + dy * dy) + dz * dz <= r2) {
-                if (cnt == 0) n0 = j;
-                if (cnt == 1) n1 = j;
-                ++cnt;
-                sx += p.x;
-                sy += p.y;
-            }
+    }
+    __device__ __forceinline__ void mean()
+    {
+        mx = sx / (float)cnt;
+        my = sy / (float)cnt;
+    }
+    __device__ __forceinline__ void second(const float4 p)
+    {
+        if (near(p)) {
+            const float ex = p.x - mx, ey = p.y - my;
+            a += ex * ex;
+            b += ex * ey;
+            c += ey * ey;
         }
+    }
+    /* pts: the queries' cloud (the two neighbours of the |N| = 2 branch); o: a pcl::PointNormal record (12 floats) where
+     * kPointNormal, else a pcl::Normal record (8 floats) */
+    template <bool kPointNormal>
+    __device__ __forceinline__ void write(const float4 *pts, float vpx, float vpy, float4 *o) const
+    {
         float nx = 0.0f, ny = 0.0f, nz = 0.0f, curv = 0.0f;
         if (cnt == 1) {
             nx = ny = nz = curv = __uint_as_float(0x7fc00000u);
@@ -251,18 +255,6 @@ __global__ __launch_bounds__(kRfThreads) void k_rf_normals(RfWork w, float r2, u
             nx = (float)(-vy / norm);
             ny = (float)(vx / norm);
         } else if (cnt >= 3) {
-            const float mx = sx / (float)cnt, my = sy / (float)cnt;
-            float a = 0.0f, b = 0.0f, c = 0.0f;
-            for (uint32_t j = lo; j < hi; ++j) {
-                const float4 p = pts[j];
-                const float dx = p.x - q.x, dy = p.y - q.y, dz = p.z - q.z;
-                if ((dx * dx + dy * dy) + dz * dz <= r2) {
-                    const float ex = p.x - mx, ey = p.y - my;
-                    a += ex * ex;
-                    b += ex * ey;
-                    c += ey * ey;
-                }
-            }
             double vx, vy;
             const double h = 0.5 * ((double)c - (double)a);
             const double s = sqrt(h * h + (double)b * (double)b);
@@ -290,15 +282,43 @@ __global__ __launch_bounds__(kRfThreads) void k_rf_normals(RfWork w, float r2, u
                 nz = -nz;
             }
         }
-        float4 *o = reinterpret_cast<float4 *>(out + (size_t)f * out_stride * (kPointNormal ? 12 : 8) + (size_t)v * (kPointNormal ? 12 : 8));
-        if (kPointNormal) {
-            o[0] = make_float4(q.x, q.y, q.z, 0.0f);
-            o[1] = make_float4(rf_canon(nx), rf_canon(ny), rf_canon(nz), 0.0f);
-            o[2] = make_float4(rf_canon(curv), 0.0f, 0.0f, 0.0f);
-        } else {
-            o[0] = make_float4(rf_canon(nx), rf_canon(ny), rf_canon(nz), 0.0f);
-            o[1] = make_float4(rf_canon(curv), 0.0f, 0.0f, 0.0f);
+        if (kPointNormal) *o++ = make_float4(q.x, q.y, q.z, 0.0f);
+        o[0] = make_float4(rf_canon(nx), rf_canon(ny), rf_canon(nz), 0.0f);
+        o[1] = make_float4(rf_canon(curv), 0.0f, 0.0f, 0.0f);
+    }
+};
+
+/* kPointNormal: pcl::PointNormal records (12 floats) at out + f * out_stride (the chain); else pcl::Normal records
+ * (8 floats) at out + f * out_stride.  Neighbours are scanned in ascending index: over all points, or — where the points
+ * are voxel centroids sorted by index i + j * div_x (meta.windowed) — over the rows j +- win, a contiguous index range. */
+template <bool kPointNormal>
+__global__ __launch_bounds__(kRfThreads) void k_rf_normals(RfWork w, float r2, uint32_t win, float vpx, float vpy,
+                                                          float *out, size_t out_stride)
+{
+    const int f = (int)blockIdx.y;
+    const RfFrameMeta meta = w.meta[f];
+    const uint32_t nv = meta.nv;
+    const float4 *pts = w.vpts + (size_t)f * w.Q;
+    const uint32_t *vidx = w.vidx + (size_t)f * w.Q;
+    for (uint32_t v = blockIdx.x * blockDim.x + threadIdx.x; v < nv; v += gridDim.x * blockDim.x) {
+        Normal2d nrm;
+        nrm.q = pts[v];
+        nrm.r2 = r2;
+        uint32_t lo = 0, hi = nv;
+        if (meta.windowed) {
+            const uint32_t j = vidx[v] / meta.div_x;
+            const uint32_t jl = j > win ? j - win : 0u;
+            const uint64_t jh = std::min<uint64_t>((uint64_t)j + win, (uint64_t)meta.div_y - 1u);
+            lo = rf_lower_bound(vidx, nv, (uint64_t)jl * meta.div_x);
+            hi = rf_lower_bound(vidx, nv, (jh + 1u) * meta.div_x);
         }
+        for (uint32_t j = lo; j < hi; ++j) nrm.first(j, pts[j]);
+        if (nrm.cnt >= 3) {
+            nrm.mean();
+            for (uint32_t j = lo; j < hi; ++j) nrm.second(pts[j]);
+        }
+        constexpr size_t kRow = kPointNormal ? 12 : 8;
+        nrm.write<kPointNormal>(pts, vpx, vpy, reinterpret_cast<float4 *>(out + ((size_t)f * out_stride + v) * kRow));
     }
 }
 

@@ -6,20 +6,20 @@
  *   target(g)[i] = the PointNormal record of V[i] and N[i].
  * The moved normals and curvatures of concat(g) are not used: the normals are RECOMPUTED over the union.  Per launch group of
  * the plan (bev_submap_reg_plan.h with point_normal and union_voxel), the sort as bev_submap_vox_plan.h schedules it:
- *   k_submap_pn_move     per map         : k_submap_pn_target's scan and pn_move (a copy of its first two steps, so that
- *                                          kernel stays what it is): concat(g) into the moved rows, its count
+ *   k_submap_pn_move     per map         : submap_pn_concat, k_submap_pn_target's first two steps (bev_submap_coarse.h):
+ *                                          concat(g) into the moved rows, its count
  *   k_submap_pn_keys     per map         : rf_voxel_bounds and rf_voxel_keys over the moved rows' positions: the union's
  *                                          bounds, divisions and overflow test, the keys voxel index << 32 | concatenation
  *                                          index, padded with ~0 to the map's own power of two
  *   k_submap_vox_tile, k_submap_vox_global (bev_submap_vox.h) as they are: they see key arrays and headers only
- *   k_submap_pn_finish   per map         : rf_voxel_starts (the voxel's index recorded), then one lane per voxel: x, y, z
- *                                          summed in key order (that is concatenation order) / float(n) into the position
- *                                          array; the overflow branch copies the moved rows to the target instead
- *   k_submap_pn_normals  per (part, map) : one lane per thinned point: k_rf_normals' arithmetic (bev_regfront.h) over a
- *                                          window of the union's grid in THREE dimensions, the candidates staged in LDS, see
- *                                          below; 12-float rows
+ *   k_submap_pn_finish   per map         : rf_voxel_starts (the voxel's index recorded), then rf_voxel_centroids (key order
+ *                                          is concatenation order) into the position array; the overflow branch copies the
+ *                                          moved rows to the target instead
+ *   k_submap_pn_normals  per (part, map) : one lane per thinned point: Normal2d (bev_regfront.h), k_rf_normals' arithmetic,
+ *                                          over a window of the union's grid in THREE dimensions, the candidates staged in
+ *                                          LDS, see below; 12-float rows
  *   k_submap_pn_grid     per map         : reg_grid_build<kIcpCells> over the target's positions
- *   k_submap_pn_out      per (part, map) : the cloud call: a map's rows and count into the caller's arrays
+ *   k_submap_out (bev_submap_vox.h)      : the cloud call: a map's rows and count into the caller's arrays
  * then k_submap_coarse_icp and k_icp_best as they are, the SubmapCoarseWork pointing at the thinned rows.
  * A map's point count is known on the device only: the grids are the plan's (the group's largest capacity), and a workgroup
  * beyond its map's count returns at once.  No float sum depends on an atomic or on which workgroup ran first: a centroid and
@@ -36,60 +36,25 @@ namespace bevk {
 static_assert(bevsubreg::kCoarseUnionRowBytes == 48 + 16 + 48 + 4 + 4 + 16,
               "the thinned row and its searchable copy, the moved row, a voxel start, a voxel index, a position");
 
-/* a moved row's position (the keys), a target row's position (the search grid): each reg_* template keeps one caller */
-struct SubpnMovedRows {
-    const float *rows;
-    __device__ float3 operator()(uint32_t i) const
-    {
-        const float4 p = *reinterpret_cast<const float4 *>(rows + (size_t)i * 12);
-        return make_float3(p.x, p.y, p.z);
-    }
-};
-struct SubpnTargetRows {
-    const float *rows;
-    __device__ float3 operator()(uint32_t i) const
-    {
-        const float4 p = *reinterpret_cast<const float4 *>(rows + (size_t)i * 12);
-        return make_float3(p.x, p.y, p.z);
-    }
-};
-
-/* Map map0 + blockIdx.x of the plan: the scan and the moved rows, as k_submap_pn_target's steps 1 and 2 (bev_submap_coarse.h),
- * into p.moved; the header's n and n_out (with pn_leaf == 0 the moved rows are the cloud call's target) */
+/* Map map0 + blockIdx.x of the plan: submap_pn_concat (bev_submap_coarse.h) into p.moved; the header's n and n_out (with
+ * pn_leaf == 0 the moved rows are the cloud call's target) */
 __global__ __launch_bounds__(kIcpThreads) void k_submap_pn_move(const bevsubreg::Map *maps, uint32_t map0,
                                                                 const bevsubreg::Entry *entries, const float *pn, size_t stride,
                                                                 const uint32_t *counts, uint32_t *ent_start, SubmapPnVoxWork p)
 {
     __shared__ uint32_t wave_sum[kRegWaves];
     __shared__ uint32_t s_base;
-    const int tid = (int)threadIdx.x;
     const bevsubreg::Map mp = maps[map0 + blockIdx.x];
-    float *rows = p.moved + mp.pt0 * 12;
-    const uint32_t n = submap_scan(
-        mp, [&](uint32_t e) { return min(counts[entries[mp.ent0 + e].slot], (uint32_t)stride); }, ent_start, wave_sum, s_base);
-    for (uint32_t e = 0; e < mp.n_ent; ++e) {
-        const bevsubreg::Entry &en = entries[mp.ent0 + e];
-        const uint32_t frame = en.slot, nr = min(counts[frame], (uint32_t)stride), at = ent_start[mp.ent0 + e];
-        float m[12];
-        for (int k = 0; k < 12; ++k) m[k] = en.m[k];
-        const float4 *in = reinterpret_cast<const float4 *>(pn + (size_t)frame * stride * 12);
-        float4 *out = reinterpret_cast<float4 *>(rows + (size_t)at * 12);
-        for (uint32_t i = (uint32_t)tid; i < nr; i += kRegThreads) {
-            float4 op, on, oc;
-            pn_move(m, in[(size_t)i * 3], in[(size_t)i * 3 + 1], in[(size_t)i * 3 + 2], op, on, oc);
-            out[(size_t)i * 3] = op;
-            out[(size_t)i * 3 + 1] = on;
-            out[(size_t)i * 3 + 2] = oc;
-        }
-    }
-    if (tid == 0) {
+    const uint32_t n = submap_pn_concat(mp, entries, pn, stride, counts, ent_start, p.moved + mp.pt0 * 12, wave_sum, s_base);
+    if (threadIdx.x == 0) {
         SubvoxHdr h{};
         h.n = h.n_out = n;
         p.v.vh[blockIdx.x] = h;
     }
 }
 
-/* map map0 + blockIdx.x: k_submap_vox_keys' steps on the moved rows' positions; the union grid's divisions into the header */
+/* map map0 + blockIdx.x: k_submap_vox_keys' steps (bev_submap_vox.h; a body of its own, see there) on the moved rows'
+ * positions; the union grid's divisions into the header */
 __global__ __launch_bounds__(kIcpThreads) void k_submap_pn_keys(const bevsubreg::Map *maps, uint32_t map0, SubmapPnVoxWork p,
                                                                 float pn_leaf)
 {
@@ -97,7 +62,7 @@ __global__ __launch_bounds__(kIcpThreads) void k_submap_pn_keys(const bevsubreg:
     __shared__ int s_par[8]; /* overflow, nfin, minb xyz, div xyz */
     const int g = (int)blockIdx.x, t = (int)threadIdx.x;
     const uint32_t n = p.v.vh[g].n;
-    const SubpnMovedRows fetch{p.moved + maps[map0 + g].pt0 * 12};
+    const IcpRows fetch{p.moved + maps[map0 + g].pt0 * 12};
     const float inv = 1.0f / pn_leaf;
     rf_voxel_bounds(n, fetch, inv, red, s_par);
     const uint32_t nf = (uint32_t)s_par[1];
@@ -137,114 +102,10 @@ __global__ __launch_bounds__(kIcpThreads) void k_submap_pn_finish(const bevsubre
         float4 *vpos = p.vpos + pt0;
         n_out = rf_voxel_starts(buf, h.nf, wave_cnt, vstart, [=](uint32_t v, uint32_t i) { vidx[v] = (uint32_t)(buf[i] >> 32); });
         __syncthreads();
-        /* AccumulatorXYZ: float sums in input order / float(n) */
-        for (uint32_t vx = tid; vx < n_out; vx += kRegThreads) {
-            const uint32_t a = vstart[vx], b = vstart[vx + 1];
-            float sx = 0.0f, sy = 0.0f, sz = 0.0f;
-            for (uint32_t q = a; q < b; ++q) {
-                const float4 s = moved[(size_t)(uint32_t)buf[q] * 3];
-                sx += s.x;
-                sy += s.y;
-                sz += s.z;
-            }
-            const float cf = (float)(b - a);
-            vpos[vx] = make_float4(sx / cf, sy / cf, sz / cf, 0.0f);
-        }
+        rf_voxel_centroids(buf, vstart, n_out, [moved](uint32_t i) { return moved[(size_t)i * 3]; }, vpos);
     }
     if (tid == 0) p.v.vh[g].n_out = n_out;
 }
-
-/* the first of the nv ascending voxel indices a that is >= x */
-__device__ __forceinline__ uint32_t subpn_lower_bound(const uint32_t *a, uint32_t nv, uint64_t x)
-{
-    uint32_t lo = 0, hi = nv;
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if ((uint64_t)a[mid] < x) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
-/* Normal2dEstimation::compute in radius mode for one query q, k_rf_normals' arithmetic (bev_regfront.h) statement for statement,
- * in the three steps its two passes over the candidates need: first() per candidate j (position p) in ascending index, then
- * second() per candidate again where cnt >= 3, then the record (f64 sqrt and division, the flip towards the viewpoint) */
-struct SubpnNormal {
-    float4 q;
-    float r2;
-    uint32_t cnt = 0, n0 = 0, n1 = 0;
-    float sx = 0.0f, sy = 0.0f, mx = 0.0f, my = 0.0f, a = 0.0f, b = 0.0f, c = 0.0f;
-    __device__ __forceinline__ void first(uint32_t j, const float4 p)
-    {
-        const float dx = p.x - q.x, dy = p.y - q.y, dz = p.z - q.z;
-        if ((dx * dx + dy * dy) + dz * dz <= r2) {
-            if (cnt == 0) n0 = j;
-            if (cnt == 1) n1 = j;
-            ++cnt;
-            sx += p.x;
-            sy += p.y;
-        }
-    }
-    __device__ __forceinline__ void mean()
-    {
-        mx = sx / (float)cnt;
-        my = sy / (float)cnt;
-    }
-    __device__ __forceinline__ void second(const float4 p)
-    {
-        const float dx = p.x - q.x, dy = p.y - q.y, dz = p.z - q.z;
-        if ((dx * dx + dy * dy) + dz * dz <= r2) {
-            const float ex = p.x - mx, ey = p.y - my;
-            a += ex * ex;
-            b += ex * ey;
-            c += ey * ey;
-        }
-    }
-    /* pts: the thinned positions (the two neighbours of the |N| = 2 branch); o: the PointNormal record */
-    __device__ __forceinline__ void write(const float4 *pts, float vpx, float vpy, float4 *o) const
-    {
-        float nx = 0.0f, ny = 0.0f, nz = 0.0f, curv = 0.0f;
-        if (cnt == 1) {
-            nx = ny = nz = curv = __uint_as_float(0x7fc00000u);
-        } else if (cnt == 2) {
-            const double vx = (double)(float)(pts[n0].x - pts[n1].x);
-            const double vy = (double)(float)(pts[n0].y - pts[n1].y);
-            const double norm = sqrt(vx * vx + vy * vy);
-            nx = (float)(-vy / norm);
-            ny = (float)(vx / norm);
-        } else if (cnt >= 3) {
-            double vx, vy;
-            const double hh = 0.5 * ((double)c - (double)a);
-            const double s = sqrt(hh * hh + (double)b * (double)b);
-            if (b == 0.0f) {
-                vx = a <= c ? 1.0 : 0.0;
-                vy = a <= c ? 0.0 : 1.0;
-            } else if (hh >= 0.0) {
-                vx = hh + s;
-                vy = -(double)b;
-            } else {
-                vx = (double)b;
-                vy = hh - s;
-            }
-            const double len = sqrt(vx * vx + vy * vy);
-            nx = (float)(vx / len);
-            ny = (float)(vy / len);
-            const float lx = -ny, ly = nx; /* the large eigenvector (-n.y, n.x) */
-            curv = ly / (lx + ly);
-        }
-        if (cnt >= 2) { /* flipNormalTowardsViewpoint */
-            const float cs = (float)((double)(vpx - q.x) * (double)nx + (double)(vpy - q.y) * (double)ny);
-            if (cs < 0.0f) {
-                nx = -nx;
-                ny = -ny;
-                nz = -nz;
-            }
-        }
-        o[0] = make_float4(q.x, q.y, q.z, 0.0f);
-        o[1] = make_float4(rf_canon(nx), rf_canon(ny), rf_canon(nz), 0.0f);
-        o[2] = make_float4(rf_canon(curv), 0.0f, 0.0f, 0.0f);
-    }
-};
 
 /* The 256 thinned points from blockIdx.x * 256 on of map map0 + blockIdx.y, one lane each, the candidates staged in LDS.
  * A voxel's index is i + j * div_x + k * div_x * div_y and the thinned points are sorted by it; a centroid lies in its voxel
@@ -272,7 +133,7 @@ __global__ __launch_bounds__(kIcpThreads) void k_submap_pn_normals(const bevsubr
     const uint64_t pt0 = maps[map0 + g].pt0;
     const float4 *pts = p.vpos + pt0;
     const uint32_t *vidx = p.vidx + pt0;
-    SubpnNormal nrm;
+    Normal2d nrm;
     nrm.q = active ? pts[v] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     nrm.r2 = r2;
     /* the union of the queries' windows: layers kl .. kh, in each the row ranges [rl[i], rh[i]], i < nr (all workgroup-uniform) */
@@ -303,8 +164,8 @@ __global__ __launch_bounds__(kIcpThreads) void k_submap_pn_normals(const bevsubr
         const bool mine = active && (pass == 0 || nrm.cnt >= 3);
         for (uint32_t k = kl; k <= kh; ++k)
             for (uint32_t r = 0; r < nr; ++r) {
-                const uint32_t lo = windowed ? subpn_lower_bound(vidx, nv, k * layer + (uint64_t)rl[r] * h.div[0]) : 0u;
-                const uint32_t hi = windowed ? subpn_lower_bound(vidx, nv, k * layer + ((uint64_t)rh[r] + 1u) * h.div[0]) : nv;
+                const uint32_t lo = windowed ? rf_lower_bound(vidx, nv, k * layer + (uint64_t)rl[r] * h.div[0]) : 0u;
+                const uint32_t hi = windowed ? rf_lower_bound(vidx, nv, k * layer + ((uint64_t)rh[r] + 1u) * h.div[0]) : nv;
                 for (uint32_t base = lo; base < hi; base += kSubpnStage) {
                     const uint32_t n = min(kSubpnStage, hi - base);
                     __syncthreads(); /* (the chunk before is read) */
@@ -319,7 +180,7 @@ __global__ __launch_bounds__(kIcpThreads) void k_submap_pn_normals(const bevsubr
                 }
             }
     }
-    if (active) nrm.write(pts, vpx, vpy, reinterpret_cast<float4 *>(target + (pt0 + v) * 12));
+    if (active) nrm.write<true>(pts, vpx, vpy, reinterpret_cast<float4 *>(target + (pt0 + v) * 12));
 }
 
 /* map map0 + blockIdx.x: the search grid of the target's n_out positions, as k_submap_pn_target's step 3 */
@@ -327,21 +188,8 @@ __global__ __launch_bounds__(kIcpThreads) void k_submap_pn_grid(const bevsubreg:
                                                                 SubmapCoarseWork t)
 {
     const uint64_t pt0 = maps[map0 + blockIdx.x].pt0;
-    reg_grid_build<kIcpCells>(vh[blockIdx.x].n_out, SubpnTargetRows{t.rows + pt0 * 12}, t.hdr + blockIdx.x,
+    reg_grid_build<kIcpCells>(vh[blockIdx.x].n_out, IcpRows{t.rows + pt0 * 12}, t.hdr + blockIdx.x,
                               t.cell_off + (size_t)blockIdx.x * (kIcpCells + 1), t.sorted + pt0);
-}
-
-/* the cloud call: map map0 + blockIdx.y's n_out rows (three float4 each) from src + pt0 rows to out + (map0 + blockIdx.y) *
- * stride rows, its count */
-__global__ __launch_bounds__(kIcpThreads) void k_submap_pn_out(const bevsubreg::Map *maps, uint32_t map0, const SubvoxHdr *vh,
-                                                               const float *src, float *out, uint64_t stride, uint32_t *counts)
-{
-    const uint32_t g = blockIdx.y, n = vh[g].n_out;
-    const float4 *from = reinterpret_cast<const float4 *>(src + maps[map0 + g].pt0 * 12);
-    float4 *to = reinterpret_cast<float4 *>(out + (uint64_t)(map0 + g) * stride * 12);
-    for (uint64_t i = (uint64_t)blockIdx.x * kRegThreads + threadIdx.x; i < 3ull * n; i += (uint64_t)gridDim.x * kRegThreads)
-        to[i] = from[i];
-    if (blockIdx.x == 0 && threadIdx.x == 0) counts[map0 + g] = n;
 }
 
 void launch_submap_pn_move(const void *maps, uint32_t map0, int n_maps, const void *entries, const float *pn, size_t stride,
@@ -384,14 +232,6 @@ void launch_submap_pn_grid(const void *maps, uint32_t map0, int n_maps, const Su
     if (n_maps > 0)
         hipLaunchKernelGGL(k_submap_pn_grid, dim3(n_maps), dim3(kIcpThreads), 0, st, static_cast<const bevsubreg::Map *>(maps), map0,
                            vh, t);
-}
-
-void launch_submap_pn_out(const void *maps, uint32_t map0, int n_maps, uint32_t parts, const SubvoxHdr *vh, const float *src,
-                          float *out, uint64_t stride, uint32_t *counts, hipStream_t st)
-{
-    if (n_maps > 0)
-        hipLaunchKernelGGL(k_submap_pn_out, dim3(std::max(parts, 1u), (uint32_t)n_maps), dim3(kIcpThreads), 0, st,
-                           static_cast<const bevsubreg::Map *>(maps), map0, vh, src, out, stride, counts);
 }
 
 } /* namespace bevk */

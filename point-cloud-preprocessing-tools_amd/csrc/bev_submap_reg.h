@@ -24,16 +24,6 @@ using namespace bevx;
 static_assert(bevsubreg::kGridCells == (uint32_t)kFineCells, "the plan sizes a map's cell offsets");
 static_assert(sizeof(bevsubreg::Slot) == sizeof(FineSlot), "k_fine_voxel reads the plan's slots");
 
-/* a moved point's position */
-struct SubregPts {
-    const float4 *pts;
-    __device__ float3 operator()(uint32_t i) const
-    {
-        const float4 p = pts[i];
-        return make_float3(p.x, p.y, p.z);
-    }
-};
-
 /* An exclusive scan of the row counts count_of(e) of a map's entries e = 0 .. n_ent - 1, by the whole workgroup, 256 entries at
  * a time: ent_start (one word per entry of the call) gets every entry's first target index.  Returns the map's total; the
  * workgroup is in step on return.  (k_submap_target, k_submap_vox_move: voxel counts; k_submap_pn_target, bev_submap_coarse.h:

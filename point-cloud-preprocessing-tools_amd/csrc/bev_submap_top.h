@@ -107,7 +107,7 @@ __global__ __launch_bounds__(kIcpThreads) void k_submap_top_keys(const bevsubreg
         if (cnt[c]) atomicAdd(&t.cells[g].cnt[c], cnt[c]);
 }
 
-/* map map0 + blockIdx.x: the ranks as k_rf_cells has them, the selection's size; the sort's header */
+/* map map0 + blockIdx.x: the ranks (rf_top_rank, as k_rf_cells has them), the selection's size; the sort's header */
 __global__ __launch_bounds__(kIcpThreads) void k_submap_top_cells(SubmapTopWork t, SubvoxHdr *vh)
 {
     __shared__ uint32_t s_k[kRfCells];
@@ -115,8 +115,7 @@ __global__ __launch_bounds__(kIcpThreads) void k_submap_top_cells(SubmapTopWork 
     SubtopCells &cs = t.cells[g];
     uint32_t k = 0;
     if (tid < (uint32_t)kRfCells) {
-        const uint32_t n = cs.cnt[tid];
-        if (n >= (uint32_t)kRfMinCellPoints) k = (uint32_t)roundf(0.2f * (float)n);
+        k = rf_top_rank(cs.cnt[tid]);
         cs.k[tid] = cs.rank[tid] = s_k[tid] = k;
         cs.prefix[tid] = 0;
         cs.thr[tid] = 0;

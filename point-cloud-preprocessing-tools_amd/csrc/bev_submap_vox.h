@@ -10,10 +10,11 @@
  *                                          index, padded with ~0 to the map's own power of two
  *   k_submap_vox_tile    per (tile, map) : kTile keys in LDS: all stages with k <= kTile, or the stages j < kTile of one k
  *   k_submap_vox_global  per (tile, map) : one stage (k, j >= kTile) in global memory, kTile / 2 pairs per workgroup
- *   k_submap_vox_finish  per map         : rf_voxel_starts, then one lane per voxel: x, y, z summed in key order (that is
- *                                          concatenation order) / float(n) into the thinned array; the overflow branch
- *                                          copies the moved array; then reg_grid_build over the thinned points
- *   k_submap_vox_out     per (part, map) : the cloud call: a map's points and count into the caller's arrays
+ *   k_submap_vox_finish  per map         : rf_voxel_starts, then rf_voxel_centroids (key order is concatenation order) into
+ *                                          the thinned array; the overflow branch copies the moved array; then
+ *                                          reg_grid_build over the thinned points
+ *   k_submap_out         per (part, map) : the cloud calls, this one's and §6q's: a map's points or PointNormal rows and its
+ *                                          count into the caller's arrays
  * then k_submap_icp (bev_submap_reg.h) as it is, its SubmapRegWork pointing at the thinned arrays.
  * A map's point count is known on the device only: the sort's grids are the plan's (the group's largest key array), and a
  * workgroup whose tile starts at or above its map's own power of two, or whose stage has k above it, returns at once.  No float
@@ -31,17 +32,6 @@ constexpr uint32_t kVoxTile = bevsubvox::kTile;
 static_assert(sizeof(SubvoxHdr) == 32, "the plan counts 32 bytes");
 static_assert(kVoxTile % (2 * kRegThreads) == 0 && (kVoxTile & (kVoxTile - 1)) == 0, "whole pairs per thread, a power of two");
 
-/* a thinned point's position.  SubregPts under a name of its own: reg_grid_build<kFineCells, SubregPts> keeps k_submap_target
- * as its one caller, so the compiler goes on inlining it there and that kernel's code stays what it was */
-struct SubvoxThinPts {
-    const float4 *pts;
-    __device__ float3 operator()(uint32_t i) const
-    {
-        const float4 p = pts[i];
-        return make_float3(p.x, p.y, p.z);
-    }
-};
-
 /* map map0 + blockIdx.x: concat(g) and its count (n_out too: with map_leaf == 0 the moved array is the target) */
 __global__ __launch_bounds__(kFineThreads) void k_submap_vox_move(const bevsubreg::Map *maps, uint32_t map0,
                                                                   const bevsubreg::Entry *entries, FineWork w,
@@ -58,7 +48,9 @@ __global__ __launch_bounds__(kFineThreads) void k_submap_vox_move(const bevsubre
     }
 }
 
-/* map map0 + blockIdx.x: k_fine_voxel's first steps on the moved points (np2 == 0: nothing to sort) */
+/* map map0 + blockIdx.x: k_fine_voxel's first steps on the moved points (np2 == 0: nothing to sort).  k_submap_pn_keys
+ * (bev_submap_pn_vox.h) has these steps over rows and writes SubvoxHdr::div besides; one body for both cost this kernel 16
+ * instructions and measured 1.9 - 3.5 % slower, so each keeps its own */
 __global__ __launch_bounds__(kFineThreads) void k_submap_vox_keys(const bevsubreg::Map *maps, uint32_t map0, SubmapVoxWork v,
                                                                   float map_leaf)
 {
@@ -154,35 +146,25 @@ __global__ __launch_bounds__(kFineThreads) void k_submap_vox_finish(const bevsub
         uint32_t *vstart = v.vstart + pt0 + g; /* (cap + 1 words per map) */
         n_out = rf_voxel_starts(buf, h.nf, wave_cnt, vstart, [](uint32_t, uint32_t) {});
         __syncthreads();
-        /* AccumulatorXYZ: float sums in input order / float(n) */
-        for (uint32_t vx = tid; vx < n_out; vx += kRegThreads) {
-            const uint32_t a = vstart[vx], b = vstart[vx + 1];
-            float sx = 0.0f, sy = 0.0f, sz = 0.0f;
-            for (uint32_t q = a; q < b; ++q) {
-                const float4 p = moved[(uint32_t)buf[q]];
-                sx += p.x;
-                sy += p.y;
-                sz += p.z;
-            }
-            const float cf = (float)(b - a);
-            thin[vx] = make_float4(sx / cf, sy / cf, sz / cf, 0.0f);
-        }
+        rf_voxel_centroids(buf, vstart, n_out, [moved](uint32_t i) { return moved[i]; }, thin);
     }
     if (tid == 0) v.vh[g].n_out = n_out;
     __syncthreads();
     if (t.hdr)
-        reg_grid_build<kFineCells>(n_out, SubvoxThinPts{thin}, t.hdr + g, t.cell_off + (size_t)g * (kFineCells + 1), t.sorted + pt0);
+        reg_grid_build<kFineCells>(n_out, SubregPts{thin}, t.hdr + g, t.cell_off + (size_t)g * (kFineCells + 1), t.sorted + pt0);
 }
 
-/* the cloud call: map map0 + blockIdx.y's n_out points from src + pt0 to out + (map0 + blockIdx.y) * stride, its count */
-__global__ __launch_bounds__(kFineThreads) void k_submap_vox_out(const bevsubreg::Map *maps, uint32_t map0, const SubvoxHdr *vh,
-                                                                 const float4 *src, float4 *out, uint64_t stride,
-                                                                 uint32_t *counts)
+/* the cloud calls (K_SUBMAP_VOX_OUT, K_SUBMAP_PN_OUT): map map0 + blockIdx.y's n_out rows of row_f4 float4 (a point: 1, a
+ * PointNormal row: 3) from src + pt0 rows to out + (map0 + blockIdx.y) * stride rows, its count */
+__global__ __launch_bounds__(kRegThreads) void k_submap_out(const bevsubreg::Map *maps, uint32_t map0, const SubvoxHdr *vh,
+                                                            const float4 *src, float4 *out, uint64_t stride, uint32_t *counts,
+                                                            uint32_t row_f4)
 {
     const uint32_t g = blockIdx.y, n = vh[g].n_out;
-    const float4 *from = src + maps[map0 + g].pt0;
-    float4 *to = out + (uint64_t)(map0 + g) * stride;
-    for (uint32_t i = blockIdx.x * kRegThreads + threadIdx.x; i < n; i += gridDim.x * kRegThreads) to[i] = from[i];
+    const float4 *from = src + maps[map0 + g].pt0 * row_f4;
+    float4 *to = out + (uint64_t)(map0 + g) * stride * row_f4;
+    const uint64_t n_f4 = (uint64_t)row_f4 * n, step = (uint64_t)gridDim.x * kRegThreads;
+    for (uint64_t i = (uint64_t)blockIdx.x * kRegThreads + threadIdx.x; i < n_f4; i += step) to[i] = from[i];
     if (blockIdx.x == 0 && threadIdx.x == 0) counts[map0 + g] = n;
 }
 
@@ -220,12 +202,13 @@ void launch_submap_vox_finish(const void *maps, uint32_t map0, int n_maps, const
                            static_cast<const bevsubreg::Map *>(maps), map0, v, t);
 }
 
-void launch_submap_vox_out(const void *maps, uint32_t map0, int n_maps, uint32_t parts, const SubvoxHdr *vh, const float4 *src,
-                           float4 *out, uint64_t stride, uint32_t *counts, hipStream_t st)
+void launch_submap_out(const void *maps, uint32_t map0, int n_maps, uint32_t parts, const SubvoxHdr *vh, const void *src,
+                       void *out, uint64_t stride, uint32_t *counts, uint32_t row_f4, hipStream_t st)
 {
     if (n_maps > 0)
-        hipLaunchKernelGGL(k_submap_vox_out, dim3(std::max(parts, 1u), (uint32_t)n_maps), dim3(kFineThreads), 0, st,
-                           static_cast<const bevsubreg::Map *>(maps), map0, vh, src, out, stride, counts);
+        hipLaunchKernelGGL(k_submap_out, dim3(std::max(parts, 1u), (uint32_t)n_maps), dim3(kRegThreads), 0, st,
+                           static_cast<const bevsubreg::Map *>(maps), map0, vh, static_cast<const float4 *>(src),
+                           static_cast<float4 *>(out), stride, counts, row_f4);
 }
 
 } /* namespace bevk */
