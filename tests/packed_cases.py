@@ -16,6 +16,10 @@ PATTERN = 0xA5
 # test_transform_cloud's poses (tx, ty, tz, yaw), and one that pushes most points off the grid
 POSES = [(0, 0, 0, 0), (1.5, -2.25, 0.125, 30), (-3, 4, 1, -45.5), (10, 20, -1, 180), (0.1, 0.2, 0.3, 359.9)]
 FAR = (150, 0, 0, 10)
+# a general rigid matrix, every entry far from 0 and 1: frame 1 of raster_world_cases.py's map T (12 deg of roll, -9 of pitch)
+GENERAL = np.array([0.9024916887283325, 0.41009873151779175, 0.13163472712039948, -12.794914245605469,
+                    -0.4304434359073639, 0.8694769144058228, 0.24233940243721008, 4.982234001159668,
+                    -0.015070266090333462, -0.27537062764167786, 0.9612199664115906, 1.820896863937378], dtype=np.float32)
 INVALID, UNSUPPORTED, TOO_LARGE = -1, -5, -6
 
 

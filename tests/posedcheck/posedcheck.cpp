@@ -66,6 +66,14 @@ const Pose kPoses[] = {{0, 0, 0, 0}, {1.5f, -2.25f, 0.125f, 30}, {-3, 4, 1, -45.
                        {150, 0, 0, 10},
                        {1.0f, 0, 0, 0}, {-1.0f, 0, 0, 0}, {0, 1.0f, 0, 0}, {0, -1.0f, 0, 0},
                        {0.5f, 0, 0, 0}, {-0.5f, 0, 0, 0}, {0, 0.5f, 0, 0}, {0, -0.5f, 0, 0}};
+/* two entries of map T of tests/raster_world_cases.py (frames 1 and 4 about a tilted origin): general rigid matrices, every one
+ * of the 12 entries far from 0 and 1.  The Pose list above never has m[2], m[6], m[8], m[9] != 0 */
+const float kGeneral[2][12] = {
+    {0.9024916887283325f, 0.41009873151779175f, 0.13163472712039948f, -12.794914245605469f, -0.4304434359073639f, 0.8694769144058228f,
+     0.24233940243721008f, 4.982234001159668f, -0.015070266090333462f, -0.27537062764167786f, 0.9612199664115906f, 1.820896863937378f},
+    {0.9889324307441711f, -0.09149842709302902f, 0.11679299175739288f, -0.9883042573928833f, 0.05859272927045822f, 0.9640607237815857f,
+     0.2591405510902405f, 3.9861388206481934f, -0.13630647957324982f, -0.24942927062511444f, 0.9587520956993103f, 0.1872139722108841f}};
+constexpr int kNumGeneral = 2;
 
 /* both images of the cloud under m (nullptr: raw coordinates) through posed_code */
 void host_raster(const std::vector<bev_point_t> &cloud, const float *m, const RasterParams &rp, std::vector<uint8_t> &multi,
@@ -92,8 +100,8 @@ void host_raster(const std::vector<bev_point_t> &cloud, const float *m, const Ra
 
 int main()
 {
-    int cases = 0, bad = 0;
-    size_t set_bytes = 0;
+    int cases = 0, bad = 0, general = 0;
+    size_t set_bytes = 0, general_bytes = 0;
     const char *const sensor_name[] = {"HDL_32E", "HDL_64E", "OS1_64"};
     for (int kind = 0; kind < 3; ++kind) {
         oracle_sensor_t sp;
@@ -117,11 +125,13 @@ int main()
                 const std::vector<bev_point_t> &cloud = clouds[ci];
                 std::vector<oracle_point_t> moved(cloud.size());
                 const int n_poses = (int)(sizeof kPoses / sizeof kPoses[0]);
-                for (int k = -1; k < n_poses; ++k) { /* -1: no pose */
+                for (int k = -1; k < n_poses + kNumGeneral; ++k) { /* -1: no pose; behind the poses: the general matrices */
                     float m[12];
                     const oracle_point_t *src = reinterpret_cast<const oracle_point_t *>(cloud.data());
+                    const bool is_general = k >= n_poses;
                     if (k >= 0) {
-                        oracle_yaw_translate_matrix(kPoses[k].tx, kPoses[k].ty, kPoses[k].tz, kPoses[k].yaw, m);
+                        if (is_general) memcpy(m, kGeneral[k - n_poses], sizeof m);
+                        else oracle_yaw_translate_matrix(kPoses[k].tx, kPoses[k].ty, kPoses[k].tz, kPoses[k].yaw, m);
                         oracle_transform_cloud(src, cloud.size(), m, moved.data());
                         src = moved.data();
                     }
@@ -129,8 +139,8 @@ int main()
                     oracle_multi_bev(&sp, src, cloud.size(), interval, want_multi.data());
                     oracle_single_bev(src, cloud.size(), interval, want_single.data());
                     host_raster(cloud, k >= 0 ? m : nullptr, rp, multi, single);
-                    ++cases;
-                    for (uint8_t v : want_multi) set_bytes += v != 0;
+                    ++(is_general ? general : cases);
+                    for (uint8_t v : want_multi) (is_general ? general_bytes : set_bytes) += v != 0;
                     if (multi != want_multi || single != want_single) {
                         ++bad;
                         size_t dm = 0, ds = 0;
@@ -143,10 +153,11 @@ int main()
             }
         }
     }
-    if (bad || set_bytes == 0) {
-        printf("posedcheck FAILED: %d of %d cases differ\n", bad, cases);
+    if (bad || set_bytes == 0 || general_bytes == 0) {
+        printf("posedcheck FAILED: %d of %d cases differ\n", bad, cases + general);
         return 1;
     }
-    printf("posedcheck ok: %d cases, %zu occupied bytes compared\n", cases, set_bytes);
+    printf("posedcheck ok: %d cases, %zu occupied bytes compared; %d more under general matrices, %zu occupied bytes\n", cases, set_bytes,
+           general, general_bytes);
     return 0;
 }

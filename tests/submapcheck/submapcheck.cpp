@@ -53,9 +53,28 @@ struct Pose { float tx, ty, tz, yaw; };
 const Pose kPoses[] = {{0, 0, 0, 0}, {1.5f, -2.25f, 0.125f, 30}, {-3, 4, 1, -45.5f}, {10, 20, -1, 180}, {0.1f, 0.2f, 0.3f, 359.9f},
                        {150, 0, 0, 10}, {-7.5f, 2, 0.5f, 90}};
 constexpr int kNumPoses = (int)(sizeof kPoses / sizeof kPoses[0]);
+/* two entries of map T of tests/raster_world_cases.py (frames 1 and 4 about a tilted origin): general rigid matrices, every one
+ * of the 12 entries far from 0 and 1.  The Pose list above never has m[2], m[6], m[8], m[9] != 0 */
+const float kGeneral[2][12] = {
+    {0.9024916887283325f, 0.41009873151779175f, 0.13163472712039948f, -12.794914245605469f, -0.4304434359073639f, 0.8694769144058228f,
+     0.24233940243721008f, 4.982234001159668f, -0.015070266090333462f, -0.27537062764167786f, 0.9612199664115906f, 1.820896863937378f},
+    {0.9889324307441711f, -0.09149842709302902f, 0.11679299175739288f, -0.9883042573928833f, 0.05859272927045822f, 0.9640607237815857f,
+     0.2591405510902405f, 3.9861388206481934f, -0.13630647957324982f, -0.24942927062511444f, 0.9587520956993103f, 0.1872139722108841f}};
+/* pose index kNumPoses + g names kGeneral[g]; `bump` tells the entries of a scenario apart (added to tz) */
+void pose_matrix(int index, float bump, float m[12])
+{
+    if (index < kNumPoses) {
+        const Pose &q = kPoses[index];
+        oracle_yaw_translate_matrix(q.tx, q.ty, q.tz + bump, q.yaw, m);
+        return;
+    }
+    memcpy(m, kGeneral[index - kNumPoses], 12 * sizeof(float));
+    m[11] += bump;
+}
 
 struct Scenario {
     const char *name;
+    bool general = false;                               /* counted apart: the scenarios under kGeneral */
     std::vector<uint32_t> sizes;                        /* records per frame */
     std::vector<std::vector<std::pair<int, int>>> maps; /* per map its (frame, pose) entries */
 };
@@ -178,6 +197,19 @@ Scenario shared_frame()
     }
     return s;
 }
+/* the mixed frames under the general matrices, alone and next to yaw poses: one frame twice, a map of one matrix only */
+Scenario general_matrices()
+{
+    Scenario s;
+    s.name = "general matrices";
+    s.general = true;
+    s.sizes = {0, 1, 1024, 1025, 3000, 257, 5000, 2049};
+    s.maps = {{{4, kNumPoses}, {1, kNumPoses + 1}, {4, kNumPoses + 1}, {2, 0}},
+              {{6, kNumPoses}},
+              {{3, kNumPoses + 1}, {5, 2}, {6, kNumPoses}, {7, kNumPoses + 1}, {0, kNumPoses}},
+              {}};
+    return s;
+}
 Scenario no_maps()
 {
     Scenario s;
@@ -211,9 +243,9 @@ int main()
     std::vector<bev_point_t> adv(60000);
     adv.resize(bev_synth_adversarial(&bp, 3, 60000, 1, adv.data(), adv.size()));
 
-    int cases = 0, bad_images = 0, prefix_sizes = 0;
-    size_t set_bytes = 0, groups_run = 0;
-    const Scenario scenarios[] = {mixed(), shared_frame(), no_maps(), no_frames()};
+    int cases = 0, general_cases = 0, bad_images = 0, prefix_sizes = 0;
+    size_t set_bytes = 0, groups_run = 0, general_bytes = 0, general_groups = 0;
+    const Scenario scenarios[] = {mixed(), shared_frame(), no_maps(), no_frames(), general_matrices()};
     for (const Scenario &sc : scenarios) {
         /* the frames: slices of the adversarial cloud, one after the other with a gap record between them */
         std::vector<bev_point_t> clouds;
@@ -229,9 +261,8 @@ int main()
             for (const auto &fp : map) {
                 entry_frame.push_back(fp.first);
                 float m[12];
-                const Pose &q = kPoses[fp.second];
                 /* (no two entries of a scenario share frame, map AND matrix: the entry's place tells them apart) */
-                oracle_yaw_translate_matrix(q.tx, q.ty, q.tz + 0.001f * (float)entry_frame.size(), q.yaw, m);
+                pose_matrix(fp.second, 0.001f * (float)entry_frame.size(), m);
                 entry_pose.insert(entry_pose.end(), m, m + 12);
             }
             map_offs.push_back(entry_frame.size());
@@ -282,7 +313,7 @@ int main()
                     const bevsub::GroupBytes gb = bevsub::group_bytes(g, at);
                     at = gb.end;
                     run_group(reinterpret_cast<const char *>(block.data()), gb, g, clouds.data(), rp, planes);
-                    ++groups_run;
+                    ++(sc.general ? general_groups : groups_run);
                     for (int m = 0; m < g.n_maps; ++m) {
                         const uint32_t *hmax = planes.data() + (size_t)m * 2 * cells, *mask = hmax + cells;
                         std::vector<uint8_t> multi(24 * cells), single(cells);
@@ -290,8 +321,8 @@ int main()
                             single[i] = (uint8_t)hmax[i];
                             for (int l = 0; l < 24; ++l) multi[(size_t)l * cells + i] = (mask[i] >> l) & 1u ? 255 : 0;
                         }
-                        ++cases;
-                        for (uint8_t v : multi) set_bytes += v != 0;
+                        ++(sc.general ? general_cases : cases);
+                        for (uint8_t v : multi) (sc.general ? general_bytes : set_bytes) += v != 0;
                         if (multi != want_multi[g.map0 + m] || single != want_single[g.map0 + m]) {
                             ++bad_images;
                             printf("MISMATCH %s: map %d\n", tag, g.map0 + m);
@@ -301,10 +332,11 @@ int main()
             }
         }
     }
-    if (g_bad || bad_images || set_bytes == 0 || prefix_sizes != 15) /* (frames of 0, 1, 1024 and 1025 records were rows) */ {
-        printf("submapcheck FAILED: %d plan checks, %d of %d images\n", g_bad, bad_images, cases);
+    if (g_bad || bad_images || set_bytes == 0 || general_bytes == 0 || prefix_sizes != 15) /* (frames of 0, 1, 1024 and 1025 records were rows) */ {
+        printf("submapcheck FAILED: %d plan checks, %d of %d images\n", g_bad, bad_images, cases + general_cases);
         return 1;
     }
-    printf("submapcheck ok: %d map images in %zu launch groups, %zu occupied bytes compared\n", cases, groups_run, set_bytes);
+    printf("submapcheck ok: %d map images in %zu launch groups, %zu occupied bytes compared; under general matrices %d more in %zu, %zu\n",
+           cases, groups_run, set_bytes, general_cases, general_groups, general_bytes);
     return 0;
 }

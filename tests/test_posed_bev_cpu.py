@@ -23,6 +23,8 @@ def test_posed_code_rasters_equal_the_oracle_composition():
     last = r.stdout.strip().splitlines()[-1]
     # 3 sensors x 2 intervals x 2 clouds x (14 poses + none)
     assert last.startswith("posedcheck ok: 180 cases, "), last
+    # ... and 3 sensors x 2 intervals x 2 clouds x 2 general matrices (two entries of raster_world_cases.py's map T)
+    assert "; 24 more under general matrices, " in last and not last.endswith(", 0 occupied bytes"), last
     assert "MISMATCH" not in r.stdout
 
 

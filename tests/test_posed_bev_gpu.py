@@ -12,7 +12,7 @@ import bev_amd
 import oracle_lib as orc
 import packed_cases
 from bev_amd import POINT_DTYPE, POSED_BEV_MAX_POSES, synth
-from packed_cases import (FAR, INVALID, PATTERN, POSES, TOO_LARGE, _adversarial, _dev, _marked, _matrix, _one_cell, _Out, _p,
+from packed_cases import (FAR, GENERAL, INVALID, PATTERN, POSES, TOO_LARGE, _adversarial, _dev, _marked, _matrix, _one_cell, _Out, _p,
                           _pack)
 
 pytestmark = pytest.mark.gpu
@@ -142,9 +142,11 @@ def _nonfinite_cloud():
 def test_poses():
     adv, marked = _adversarial(), _marked()
     frames = [marked[:50001], adv[:0], _nonfinite_cloud(), marked[60000:60257], adv[100:1125], marked[90000:133312]]
-    nf, n_poses = len(frames), 5
-    poses = np.stack([np.stack([_matrix((POSES + POSES)[f + k][:3] + (POSES[k][3] + f,)) for k in range(4)] + [_matrix(FAR)])
+    nf, n_poses = len(frames), 6
+    # (the last pose is a general matrix: every cloud, the non-finite one too, meets m[2], m[6], m[8], m[9] != 0)
+    poses = np.stack([np.stack([_matrix((POSES + POSES)[f + k][:3] + (POSES[k][3] + f,)) for k in range(4)] + [_matrix(FAR), GENERAL])
                       for f in range(nf)])
+    assert (np.abs(poses[:, 5]) > 0.01).all() and not (poses[:, :5, [2, 6, 8, 9]] != 0).any()
     assert poses.shape == (nf, n_poses, 12)
     p = _p()
     ctx = bev_amd.BevContext(p, device=0, max_batch=2, max_points=p.slots)

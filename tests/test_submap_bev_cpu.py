@@ -34,6 +34,8 @@ def _assert_ok(run):
     last = run.stdout.strip().splitlines()[-1]
     # (7 + 5 + 0 + 3 maps) x caps of 1, 3 and "all" x 2 intervals; (7 + 3 + 1) + (5 + 2 + 1) + 0 + (3 + 1 + 1) groups x 2
     assert last.startswith("submapcheck ok: 90 map images in 48 launch groups, "), last
+    # the scenario under general matrices: 4 maps x 3 caps x 2 intervals; (4 + 2 + 1) groups x 2
+    assert "; under general matrices 24 more in 14, " in last and not last.endswith(", 0"), last
     assert "MISMATCH" not in run.stdout and "PLAN" not in run.stdout
 
 

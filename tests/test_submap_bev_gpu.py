@@ -13,7 +13,7 @@ import bev_amd
 import oracle_lib as orc
 import packed_cases
 from bev_amd import POINT_DTYPE, SUBMAP_MAX_ENTRIES, synth
-from packed_cases import (FAR, INVALID, PATTERN, POSES, TOO_LARGE, _adversarial, _dev, _marked, _matrix, _one_cell, _Out, _p,
+from packed_cases import (FAR, GENERAL, INVALID, PATTERN, POSES, TOO_LARGE, _adversarial, _dev, _marked, _matrix, _one_cell, _Out, _p,
                           _pack)
 
 pytestmark = pytest.mark.gpu
@@ -68,10 +68,11 @@ def test_maps_over_ragged_frames():
             [(16, _matrix(POSES[2])), (17, _matrix(POSES[3]))],                                  # the two empty frames only
             [(int(f), _matrix((0.5 * f - 5, 3 - 0.25 * f, 0.01 * f, 7.0 * f))) for f in order],  # every frame once
             [(12, _matrix(POSES[1])), (12, _matrix(POSES[3])), (12, _matrix(POSES[4]))],         # one frame three times
-            [(15, _matrix(FAR)), (6, _matrix(POSES[2]))]]                                        # the full sweep, far off
+            [(15, _matrix(FAR)), (6, _matrix(POSES[2]))],                                        # the full sweep, far off
+            [(15, GENERAL), (12, GENERAL), (4, _matrix(POSES[1])), (11, GENERAL)]]               # a general matrix: m[2], m[6], m[8], m[9] != 0
     p = _p()
     want = [_want(p, frames, m) for m in maps]
-    assert not want[0][0].any() and not want[2][1].any() and want[5][1].any()
+    assert not want[0][0].any() and not want[2][1].any() and want[5][1].any() and want[6][0].any() and want[6][1].any()
     # the union really is one: map 4's image is not any single entry's
     assert want[4][1].tobytes() != _want(p, frames, maps[4][:1])[1].tobytes()
     ctx = bev_amd.BevContext(p, device=0, max_batch=4, max_points=p.slots)

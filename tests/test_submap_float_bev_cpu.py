@@ -35,6 +35,8 @@ def _assert_ok(run):
     assert [l for l in lines if l.startswith("ok:")] == lines[-1:], run.stdout
     # (7 + 5 + 0 + 3 maps) x 3 intervals x both skip values; the three scenarios that have maps are one launch group each
     assert lines[-1].startswith("ok: submapfloatcheck: 90 grids in 18 launch groups, "), lines[-1]
+    # the scenario under general matrices: 4 maps x 3 intervals x both skip values
+    assert "; under general matrices 24 more grids, " in lines[-1] and not lines[-1].endswith(" 0 non-zero floats"), lines[-1]
     assert "MISMATCH" not in run.stdout and "PLAN" not in run.stdout
 
 
