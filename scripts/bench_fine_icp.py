@@ -2,67 +2,43 @@
 
     python scripts/bench_fine_icp.py [--frames 1000] [--moved 500] [--steps 3] [--warmup 1] [--out profiles/fine_icp_bench.json]
 
-The frames are bench.py's default workload (synthetic HDL_64E sweeps, 98 % of the slots, 5,000 duplicates) plus a moved
-copy (seeded yaw within +-20 degrees, translation within +-1.5 m, by bev_transform_cloud) of each of the first --moved
-frames, run once through bev_process_device_resident, the registration front end and the coarse entry.  Two match lists:
-bench_icp.py's (frame i against (i + 1) mod N or a seeded random partner, seeded angle guesses) and the moved-copy pairs
-(frame i against its copy, the yaw within +-2 degrees as the guess).  For each list and tool setting (top-part: guesses
-from the coarse device output; whole: the yaw guess): matches/s as the median of fenced steps (launch, bev_synchronize)
-and the mean of unfenced steps, the per-kernel times of bev_profile_get over one more step, the iterations and states,
-the voxels per full cloud; and the sequential C checker's matches/s on one core (context only).  One JSON line."""
+The frames are benchlib's sweeps and moved copies, run once through bev_process_device_resident, the registration front end
+and the coarse entry (the front end's buffers are allocated before the BEV path runs, and nothing is released).  Two match
+lists: bench_icp.py's (frame i against (i + 1) mod N or a seeded random partner, seeded angle guesses) and benchlib's
+moved-copy pairs.  For each list and tool setting (top-part: guesses from the coarse device output; whole: the yaw guess):
+matches/s by benchlib.timed, the per-kernel times of bev_profile_get over one more step, the iterations and states, the voxels
+per full cloud; and the sequential C checker's matches/s on one core (context only).  One JSON line."""
 import argparse
-import json
-import socket
-import statistics
-import sys
 import time
-from concurrent.futures import ThreadPoolExecutor
-from pathlib import Path
+from types import SimpleNamespace
 
 import numpy as np
 
-REPO = Path(__file__).resolve().parent.parent
-sys.path.insert(0, str(REPO / "point-cloud-preprocessing-tools_amd"))
-sys.path.insert(0, str(REPO / "tests"))
+import benchlib as bl
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--frames", type=int, default=1000)
-    ap.add_argument("--moved", type=int, default=500)
-    ap.add_argument("--sub-batch", type=int, default=500)
-    ap.add_argument("--steps", type=int, default=3)
-    ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--cpu-matches", type=int, default=2, help="matches the C checker is timed on")
-    ap.add_argument("--out", default=str(REPO / "profiles" / "fine_icp_bench.json"))
+    bl.std_args(ap, frames=1000, moved=500, sub_batch=500, steps=3, warmup=1, out="fine_icp_bench.json")
     args = ap.parse_args()
     import torch
 
     import bev_amd
     import fineicp_lib as fl
-    from bev_amd import synth
 
     fl.build()
     p = bev_amd.params_for_sensor("HDL_64E")
     F0, M, S = args.frames, args.moved, p.slots
     dev = torch.device("cuda:0")
-    with ThreadPoolExecutor(16) as ex:
-        frames = list(ex.map(lambda i: synth.sweep(p, i, keep=0.98, n_dup=5000), range(F0)))
-    n_max = max(len(f) for f in frames)
-    ctx = bev_amd.BevContext(p, device=0, max_batch=args.sub_batch, max_points=n_max)
-    rng = np.random.default_rng(2026)
-    yaw = rng.uniform(-20, 20, M).astype(np.float32)
-    tr = rng.uniform(-1.5, 1.5, (M, 2)).astype(np.float32)
-    frames += [ctx.transform_cloud(frames[i], bev_amd.yaw_translate_matrix(float(tr[i, 0]), float(tr[i, 1]), 0.0,
-                                                                           float(yaw[i]))) for i in range(M)]
+    frames = bl.sweeps(p, F0)
+    ctx = bev_amd.BevContext(p, device=0, max_batch=args.sub_batch, max_points=max(len(f) for f in frames))
+    rng, yaw, tr = bl.world_draws(M)
+    frames += bl.moved_copies(ctx, frames, yaw, tr)
     F = len(frames)
-    offs = np.zeros(F + 1, np.uint64)
-    offs[1:] = np.cumsum([len(f) for f in frames])
-    d_in = torch.from_numpy(np.concatenate(frames).view(np.uint8).reshape(-1)).to(dev)
+    offs, d_in = bl.upload(frames, dev)
     del frames
-    d_ord = torch.empty(F * S * 32, dtype=torch.uint8, device=dev)
-    d_multi = torch.empty(F * p.n_layers * p.mat_size ** 2, dtype=torch.uint8, device=dev)
-    d_single = torch.empty(F * p.mat_size ** 2, dtype=torch.uint8, device=dev)
+    d_ord, d_multi, d_single = bl.bev_outputs(p, F, dev)
     stride = bev_amd.regfront_max_out(S)
     d_pn = torch.empty(F * stride * 12, dtype=torch.float32, device=dev)
     d_cnt = torch.empty(F, dtype=torch.int32, device=dev)
@@ -77,15 +53,10 @@ def main():
     a["match_idx"] = np.where(np.arange(F0) % 2 == 0, (np.arange(F0) + 1) % F0, rng.integers(0, F0, F0))
     a["angle_guess"] = rng.uniform(-180, 180, F0).astype(np.float32)
     lists["bench_icp"] = a
-    b = np.zeros(M, bev_amd.MATCH_DTYPE)
-    b["query_idx"] = np.arange(M)
-    b["match_idx"] = F0 + np.arange(M)
-    b["angle_guess"] = yaw + rng.uniform(-2, 2, M).astype(np.float32)
-    lists["moved_copies"] = b
+    lists["moved_copies"] = bl.moved_copy_pairs(SimpleNamespace(rng=rng, yaw=yaw, F0=F0, M=M))
     R = bev_amd.ICP_RESULT_DTYPE.itemsize
     out = {"metric": "fine_icp_matches_per_s", "sensor": "HDL_64E", "frames": F, "steps": args.steps,
            "warmup": args.warmup, "runs": {}}
-    ordered_sample = None
     for name, m in lists.items():
         n = len(m)
         d_coarse = torch.zeros(n * 2 * R, dtype=torch.uint8, device=dev)
@@ -103,37 +74,18 @@ def main():
                     ctx.fine_registration_device(F, d_ord.data_ptr(), None, m, d_res.data_ptr(),
                                                  params=bev_amd.icp_whole_defaults())
 
-            for _ in range(args.warmup):
-                step()
-            ctx.synchronize()
-            fenced = []
-            for _ in range(args.steps):
-                t = time.perf_counter()
-                step()
-                ctx.synchronize()
-                fenced.append(time.perf_counter() - t)
-            t = time.perf_counter()
-            for _ in range(args.steps):
-                step()
-            ctx.synchronize()
-            unfenced = (time.perf_counter() - t) / args.steps
-            ctx.profile_reset()
-            ctx.profile_enable(True)
-            step()
-            ctx.synchronize()
-            kernels = [k for k in ctx.profile_get() if k["name"].startswith("k_fine")]
-            ctx.profile_enable(False)
+            fenced, unfenced = bl.timed(ctx, step, args.steps, args.warmup)
+            kernels = bl.kernel_ms(ctx, step, "k_fine")
             res = d_res.cpu().numpy().view(bev_amd.ICP_RESULT_DTYPE)
             it = res["iterations"]
             out["runs"][f"{name}/{tool}"] = {
-                "matches": n, "fenced_median_ms": statistics.median(fenced) * 1e3,
-                "fenced_matches_per_s": n / statistics.median(fenced), "unfenced_mean_ms": unfenced * 1e3,
-                "unfenced_matches_per_s": n / unfenced,
+                "matches": n, "fenced_median_ms": fenced * 1e3, "fenced_matches_per_s": n / fenced,
+                "unfenced_mean_ms": unfenced * 1e3, "unfenced_matches_per_s": n / unfenced,
                 "iterations": {"mean": float(it.mean()), "p50": float(np.percentile(it, 50)),
                                "p90": float(np.percentile(it, 90)), "max": int(it.max())},
                 "states": np.bincount(res["state"], minlength=6).tolist(),
                 "success_fitness_le_1_5": int((~(res["fitness"] > 1.5)).sum()),
-                "kernels_ms_per_step": {k["name"]: k["total_ms"] for k in kernels},
+                "kernels_ms_per_step": kernels,
             }
     ordered = d_ord[: 4 * S * 32].cpu().numpy().view(bev_amd.POINT_DTYPE).reshape(4, S)
     vox = [fl.voxel_irct(o) for o in ordered]
@@ -142,13 +94,8 @@ def main():
     for k in range(args.cpu_matches):
         fl.run(vox[k], vox[(k + 1) % 4], fl.tool_guess(0.0), fl.params(**fl.WHOLE))
     out["checker_single_core_matches_per_s"] = args.cpu_matches / (time.perf_counter() - t)
-    out["device"] = torch.cuda.get_device_name(0)
-    out["host"] = socket.gethostname()
     ctx.close()
-    line = json.dumps(out)
-    print(line)
-    Path(args.out).parent.mkdir(parents=True, exist_ok=True)
-    Path(args.out).write_text(line + "\n")
+    bl.emit(out, args)
 
 
 if __name__ == "__main__":

@@ -4,9 +4,8 @@ D = 0, the fixed grids of 128 x 128 (fine) and 64 x 64 (coarse) cells at most, o
     python scripts/bench_pair_search_grid.py [--frames 1000] [--moved 500] [--matches 500] [--rounds 3] [--dims 256,512,1024]
                                              [--out profiles/pair_search_grid_bench.json]
 
-Frames, moved copies and matches are scripts/bench_submap_search_grid.py's at the same scale: bench.py's synthetic HDL_64E
-sweeps through the BEV path (marked clouds) and the front end (PointNormal rows), frame i against its moved copy under the
-tools' yaw guess.  Fine: bev_fine_registration_device_resident under the whole tool's settings (the yaw guess) and under the
+Frames, moved copies and matches (the first --matches of them) are benchlib's, at bench_submap_search_grid.py's scale: the
+marked clouds and the front end's PointNormal rows, frame i against its moved copy under the tools' yaw guess.  Fine: bev_fine_registration_device_resident under the whole tool's settings (the yaw guess) and under the
 top-part settings (from the coarse stage's own table); coarse: bev_coarse_registration_device_resident under the coarse
 defaults.  The yardstick is the D = 0 call of the same build, never an absolute figure.  Per workload: one warm-up of each call,
 then for every D of [the stage's fixed cap through the new path, --dims] --rounds alternations of [D = 0 call, D call], each
@@ -16,19 +15,12 @@ results' iteration counts, the build's time (D > 0: the point counts and the six
 k_fine_grid or k_icp_grid), and from the hook max(nx, ny) and the largest count of one cell over the matches' targets.  One
 JSON line, rewritten after every run, so that a run that is cut short leaves what it measured."""
 import argparse
-import json
-import socket
 import statistics
 import sys
-import time
-from concurrent.futures import ThreadPoolExecutor
-from pathlib import Path
 
 import numpy as np
 
-REPO = Path(__file__).resolve().parent.parent
-sys.path.insert(0, str(REPO / "point-cloud-preprocessing-tools_amd"))
-sys.path.insert(0, str(REPO / "tests"))
+import benchlib as bl
 
 GRID_KERNELS = ("k_pairgrid_desc", "k_subgrid_bounds", "k_subgrid_header", "k_subgrid_count", "k_subgrid_sums", "k_subgrid_scan",
                 "k_subgrid_scatter")
@@ -39,55 +31,20 @@ FIXED_CAP = {"fine": 128, "coarse": 64}
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--frames", type=int, default=1000)
-    ap.add_argument("--moved", type=int, default=500)
     ap.add_argument("--matches", type=int, default=500)
-    ap.add_argument("--sub-batch", type=int, default=500)
-    ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--dims", default="256,512,1024", help="the caps beside the stage's fixed one")
     ap.add_argument("--workloads", default="coarse,whole,top")
-    ap.add_argument("--out", default=str(REPO / "profiles" / "pair_search_grid_bench.json"))
+    bl.std_args(ap, frames=1000, moved=500, sub_batch=500, rounds=3, out="pair_search_grid_bench.json")
     args = ap.parse_args()
     import torch
 
     import bev_amd
-    from bev_amd import synth
 
-    p = bev_amd.params_for_sensor("HDL_64E")
-    F0, M, S = args.frames, args.moved, p.slots
-    dev = torch.device("cuda:0")
-    with ThreadPoolExecutor(16) as ex:
-        frames = list(ex.map(lambda i: synth.sweep(p, i, keep=0.98, n_dup=5000), range(F0)))
-    n_max = max(len(f) for f in frames)
-    ctx = bev_amd.BevContext(p, device=0, max_batch=args.sub_batch, max_points=n_max)
-    rng = np.random.default_rng(2026)
-    yaw = rng.uniform(-20, 20, M).astype(np.float32)
-    tr = rng.uniform(-1.5, 1.5, (M, 2)).astype(np.float32)
-    frames += [ctx.transform_cloud(frames[i], bev_amd.yaw_translate_matrix(float(tr[i, 0]), float(tr[i, 1]), 0.0,
-                                                                           float(yaw[i]))) for i in range(M)]
-    F = len(frames)
-    offs = np.zeros(F + 1, np.uint64)
-    offs[1:] = np.cumsum([len(f) for f in frames])
-    d_in = torch.from_numpy(np.concatenate(frames).view(np.uint8).reshape(-1)).to(dev)
-    del frames
-    d_ord = torch.empty(F * S * 32, dtype=torch.uint8, device=dev)
-    d_multi = torch.empty(F * p.n_layers * p.mat_size ** 2, dtype=torch.uint8, device=dev)
-    d_single = torch.empty(F * p.mat_size ** 2, dtype=torch.uint8, device=dev)
-    torch.cuda.synchronize()
-    ctx.process_device(F, d_in.data_ptr(), offs, d_ord.data_ptr(), d_multi.data_ptr(), d_single.data_ptr())
-    ctx.synchronize()
-    del d_in, d_multi, d_single
-    stride = bev_amd.regfront_max_out(S)
-    d_pn = torch.empty(F * stride * 48, dtype=torch.uint8, device=dev)
-    d_cnt = torch.zeros(F, dtype=torch.int32, device=dev)
-    ctx.registration_front_device(F, d_ord.data_ptr(), None, d_pn.data_ptr(), stride, d_cnt.data_ptr())
-    ctx.synchronize()
-
-    n = min(M, args.matches)
-    pairs = np.zeros(n, bev_amd.MATCH_DTYPE)
-    pairs["query_idx"] = np.arange(n)
-    pairs["match_idx"] = F0 + np.arange(n)
-    pairs["angle_guess"] = yaw[:n] + rng.uniform(-2, 2, n).astype(np.float32)
+    w = bl.registration_world(args)
+    ctx, d_ord, F, dev = w.ctx, w.d_ord, w.F, w.dev
+    stride, d_pn, d_cnt = bl.front_end(w)
+    n = min(w.M, args.matches)
+    pairs = bl.moved_copy_pairs(w, n)
     R = bev_amd.ICP_RESULT_DTYPE.itemsize
     whole = bev_amd.icp_whole_defaults()
     out = {"metric": "pair_search_grid_time_over_fixed_grid", "sensor": "HDL_64E", "frames": F, "matches": n, "rounds": args.rounds,
@@ -95,31 +52,13 @@ def main():
                         "coarse": "coarse defaults"},
            "every_run_byte_equal_to_its_fixed_grid_partner": True, "equal_pairs": 0, "runs": []}
 
-    def fenced(step):
-        t = time.perf_counter()
-        step()
-        ctx.synchronize()
-        return time.perf_counter() - t
-
-    def profiled(step):
-        ctx.profile_reset()
-        ctx.profile_enable(True)
-        step()
-        ctx.synchronize()
-        k = {s["name"]: s["total_ms"] for s in ctx.profile_get()}
-        ctx.profile_enable(False)
-        return k
+    fenced = lambda step: bl.fenced(ctx, step, log=False)
+    profiled = lambda step: bl.kernel_ms(ctx, step)
 
     def grids(coarse):
         g = ctx.debug_pair_grid(coarse, 0, n)
         return {"targets": n, "max_dim": int(g[:, :2].max()), "largest_cell": int(g[:, 3].max()), "searchable_mean": float(g[:, 2].mean())}
 
-    def save():
-        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
-        Path(args.out).write_text(json.dumps(out) + "\n")
-
-    out["device"] = torch.cuda.get_device_name(0)
-    out["host"] = socket.gethostname()
     # the top-part settings start from the coarse stage's table: the D = 0 coarse call's, made once
     d_table = torch.zeros(2 * n * R, dtype=torch.uint8, device=dev)
     b_table = torch.zeros(n, dtype=torch.int32, device=dev)
@@ -180,14 +119,13 @@ def main():
                    "wide_build_ms": sum(k_new.get(k, 0.0) for k in GRID_KERNELS),
                    "fixed_kernels_ms": k_old, "wide_kernels_ms": k_new, "fixed_grid": g_old, "wide_grid": g_new}
             out["runs"].append(run)
-            save()
+            bl.emit(out, args, final=False)
             print(f"{work} D {D}: fixed {med_old * 1e3:.2f} ms, wide {med_new * 1e3:.2f} ms, ratio {med_new / med_old:.3f}; icp us/it "
                   f"{run['fixed_icp_us_per_iteration_problem']:.2f} -> {run['wide_icp_us_per_iteration_problem']:.2f}; build "
                   f"{run['fixed_build_ms']:.3f} -> {run['wide_build_ms']:.3f} ms; grids {g_old} -> {g_new}", file=sys.stderr, flush=True)
     ctx.set_pair_search_grid(0, 0)
     ctx.close()
-    print(json.dumps(out))
-    save()
+    bl.emit(out, args)
 
 
 if __name__ == "__main__":

@@ -2,73 +2,32 @@
 
     python scripts/bench_posed_bev.py [--frames 1000] [--steps 20] [--warmup 5] [--no-yardsticks] [--label TEXT]
 
-One JSON line.  The frames are marked HDL_64E sweeps (ordered and ground-marked by the oracle: what
-bev_process_device_resident leaves in d_ordered), both outputs wanted.  Per n_poses of 0, 1 and 8: grids/s of one call over
-all frames as the median of fenced steps (call, bev_synchronize) and as the mean of unfenced steps (back to back, one
-synchronisation at the end), and the times of k_posed_splat and k_posed_expand from bev_profile_get over one more step.  One
-frame's images are compared with the oracle in every configuration: the numbers are of code that computes the right thing.
+One JSON line.  The frames are benchlib's marked sweeps, both outputs wanted.  Per n_poses of 0, 1 and 8: grids/s of one call
+over all frames by benchlib.timed, and the times of k_posed_splat and k_posed_expand from bev_profile_get over one more step.
+One frame's images are compared with the oracle in every configuration: the numbers are of code that computes the right thing.
 Two yardsticks in the same call (skipped with --no-yardsticks):
   (a) the per-cloud route: bev_transform_cloud + bev_multi_bev + bev_single_bev per frame over the same frames in host
       memory, one pose per frame;
-  (b) bev_float_bev_device_resident at the same pose counts (one atomic per point where this has two, and no expand pass).
-BEV_AMD_LIB selects another build of the library; --label names it in the line."""
+  (b) bev_float_bev_device_resident at the same pose counts (one atomic per point where this has two, and no expand pass)."""
 import argparse
-import json
 import os
-import socket
-import statistics
 import sys
 import time
-from pathlib import Path
 
 import numpy as np
 
-REPO = Path(__file__).resolve().parent.parent
-sys.path.insert(0, str(REPO / "point-cloud-preprocessing-tools_amd"))
-sys.path.insert(0, str(REPO / "tests"))
-
-
-def _timed(ctx, step, steps, warmup):
-    for _ in range(warmup):
-        step()
-    ctx.synchronize()
-    fenced = []
-    for _ in range(steps):
-        t = time.perf_counter()
-        step()
-        ctx.synchronize()
-        fenced.append(time.perf_counter() - t)
-    t = time.perf_counter()
-    for _ in range(steps):
-        step()
-    ctx.synchronize()
-    return statistics.median(fenced), (time.perf_counter() - t) / steps
-
-
-def _kernel_ms(ctx, step, names):
-    ctx.profile_reset()
-    ctx.profile_enable(True)
-    step()
-    ctx.synchronize()
-    got = {k["name"]: k for k in ctx.profile_get()}
-    ctx.profile_enable(False)
-    return {n: {"ms_per_step": got[n]["total_ms"], "launches": got[n]["launches"]} for n in names if n in got}
+import benchlib as bl
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--frames", type=int, default=1000)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--distinct", type=int, default=8, help="distinct sweeps the frames are tiled from")
     ap.add_argument("--no-yardsticks", action="store_true", help="only the batch call (the A/B of two builds)")
-    ap.add_argument("--label", default=None)
+    bl.std_args(ap, frames=1000, steps=20, warmup=5, distinct=8, out=None)
     args = ap.parse_args()
     import torch
 
     import bev_amd
     import oracle_lib as orc
-    from bev_amd import synth
 
     if not torch.cuda.is_available():
         sys.exit("no GPU: nothing is measured (there is no CPU path)")
@@ -79,31 +38,22 @@ def main():
     S, M, L = p.slots, p.mat_size, p.n_layers
     result = {"metric": "posed_bev_grids_per_s", "frames": F, "steps": args.steps, "warmup": args.warmup,
               "records_per_frame": S, "mat_size": M, "layers": L, "outputs": "multi and single",
-              "library": args.label or os.environ.get("BEV_AMD_LIB", "csrc/libbev_mi355x.so"),
               "posed_group_env": os.environ.get("BEV_POSED_GROUP"), "n_poses": {}}
 
-    distinct = [orc.mark_ground(sp, orc.order_cloud(sp, synth.sweep(p, s)))[0] for s in range(args.distinct)]
-    up = [torch.from_numpy(c.view(np.uint8).reshape(-1).copy()).to(dev) for c in distinct]
-    d_clouds = torch.empty(F * S * 32, dtype=torch.uint8, device=dev)
-    for f in range(F):
-        d_clouds[f * S * 32:(f + 1) * S * 32] = up[f % len(up)]
-    offs = np.arange(F + 1, dtype=np.uint64) * np.uint64(S)
+    t = bl.tiled_marked_frames(p, args.distinct, F, dev)
+    distinct, d_clouds, offs = t.clouds, t.d_clouds, t.offs
     ctx = bev_amd.BevContext(p, device=0, max_batch=8, max_points=S)
     Mf = int(ctx.lib.bev_float_bev_size(1.0))
     rng = np.random.default_rng(1)
     for n_poses in (0, 1, 8):
         G = max(1, n_poses)
-        poses = None
-        if n_poses:
-            poses = np.stack([np.stack([bev_amd.yaw_translate_matrix(rng.uniform(-5, 5), rng.uniform(-5, 5), rng.uniform(-0.5, 0.5),
-                                                                      rng.uniform(-180, 180)) for _ in range(n_poses)])
-                              for _ in range(F)])
+        poses = bl.frame_poses(rng, F, n_poses)
         d_multi = torch.empty(F * G * L * M * M, dtype=torch.uint8, device=dev)
         d_single = torch.empty(F * G * M * M, dtype=torch.uint8, device=dev)
         torch.cuda.synchronize()
         step = lambda: ctx.posed_bev_device(F, d_clouds.data_ptr(), offs, d_multi.data_ptr(), d_single.data_ptr(), poses=poses)
-        fenced, unfenced = _timed(ctx, step, args.steps, args.warmup)
-        kernels = _kernel_ms(ctx, step, ("k_posed_splat", "k_posed_expand"))
+        fenced, unfenced = bl.timed(ctx, step, args.steps, args.warmup)
+        kernels = bl.kernel_ms(ctx, step, names=("k_posed_splat", "k_posed_expand"))
         got_m = d_multi[(F - 1) * G * L * M * M:].cpu().numpy().reshape(G, L, M, M)
         got_s = d_single[(F - 1) * G * M * M:].cpu().numpy().reshape(G, M, M)
         cloud = distinct[(F - 1) % len(distinct)]
@@ -129,8 +79,8 @@ def main():
             d_out = torch.empty(F * G * Mf * Mf, dtype=torch.float32, device=dev)
             torch.cuda.synchronize()
             fstep = lambda: ctx.float_bev_device(F, d_clouds.data_ptr(), offs, d_out.data_ptr(), 1.0, True, poses=poses)
-            ff, fu = _timed(ctx, fstep, args.steps, args.warmup)
-            fk = _kernel_ms(ctx, fstep, ("k_float_bev_batch",))
+            ff, fu = bl.timed(ctx, fstep, args.steps, args.warmup)
+            fk = bl.kernel_ms(ctx, fstep, names=("k_float_bev_batch",))
             w["float_bev_yardstick"] = {"fenced_median_ms": ff * 1e3, "fenced_grids_per_s": grids / ff, "unfenced_mean_ms": fu * 1e3,
                                         "unfenced_grids_per_s": grids / fu, "kernels": fk}
             if "k_float_bev_batch" in fk and "k_posed_splat" in kernels:
@@ -149,12 +99,12 @@ def main():
         ctx.multi_bev(host[0])
         times = []
         for _ in range(2):
-            t = time.perf_counter()
+            t0 = time.perf_counter()
             for c, m in zip(host, pose1):
                 moved = ctx.transform_cloud(c, m)
                 ctx.multi_bev(moved)
                 ctx.single_bev(moved)
-            times.append(time.perf_counter() - t)
+            times.append(time.perf_counter() - t0)
         per_cloud = F / min(times)
         one = result["n_poses"]["1"]
         result["per_cloud_transform_multi_single_loop"] = {"passes_ms": [x * 1e3 for x in times], "grids_per_s": per_cloud}
@@ -162,9 +112,7 @@ def main():
         result["batch_over_per_cloud_at_8_poses"] = result["n_poses"]["8"]["unfenced_grids_per_s"] / per_cloud
         assert one["unfenced_grids_per_s"] > per_cloud, "the batch call is not faster than the per-cloud route"
     ctx.close()
-    result["device"] = torch.cuda.get_device_name(0)
-    result["host"] = socket.gethostname()
-    print(json.dumps(result))
+    bl.emit(result, args)
 
 
 if __name__ == "__main__":

@@ -3,44 +3,16 @@
     python scripts/bench_project.py [--frames 1000] [--steps 20] [--warmup 5] [--copybw PATH]
 
 One JSON line.  Per workload — MulRan sweeps of 65,536 returns, KITTI sweeps of about 120 k (projection_data.kitti_returns),
-Oxford sweeps of about 35 k, and Oxford frames of 2 M returns — frames/s of one call over all frames as the median of
-fenced steps (call, bev_synchronize) and as the mean of unfenced steps (back to back, one synchronisation at the end), the
+Oxford sweeps of about 35 k, and Oxford frames of 2 M returns — frames/s of one call over all frames by benchlib.timed, the
 per-kernel times of bev_profile_get over one more step, and the algorithmic bytes per frame (16 n read + 32 n_out written)
-over the kernel time.  --copybw: the built scripts/microbench/copybw.hip, run in the same process tree on the same box:
-its best plain-copy rate is the yardstick of the two map kernels.  Then MulRan end to end, three interleaved passes:
-project_device + process_device against process_device alone on records projected beforehand."""
+over the kernel time.  --copybw: the built scripts/microbench/copybw.hip (benchlib.copy_rate): the yardstick of the two map
+kernels.  Then MulRan end to end, three interleaved passes: project_device + process_device against process_device alone on
+records projected beforehand."""
 import argparse
-import json
-import re
-import socket
-import statistics
-import subprocess
-import sys
-import time
-from pathlib import Path
 
 import numpy as np
 
-REPO = Path(__file__).resolve().parent.parent
-sys.path.insert(0, str(REPO / "point-cloud-preprocessing-tools_amd"))
-sys.path.insert(0, str(REPO / "tests"))
-
-
-def _timed(ctx, step, steps, warmup):
-    for _ in range(warmup):
-        step()
-    ctx.synchronize()
-    fenced = []
-    for _ in range(steps):
-        t = time.perf_counter()
-        step()
-        ctx.synchronize()
-        fenced.append(time.perf_counter() - t)
-    t = time.perf_counter()
-    for _ in range(steps):
-        step()
-    ctx.synchronize()
-    return statistics.median(fenced), (time.perf_counter() - t) / steps
+import benchlib as bl
 
 
 def _tiled(torch, distinct, frames, dev):
@@ -57,12 +29,9 @@ def _tiled(torch, distinct, frames, dev):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--frames", type=int, default=1000)
     ap.add_argument("--big-frames", type=int, default=100, help="frames of the 2 M-return run")
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--sub-batch", type=int, default=500)
     ap.add_argument("--copybw", default=None, help="the built scripts/microbench/copybw.hip")
+    bl.std_args(ap, frames=1000, steps=20, warmup=5, sub_batch=500, out=None)
     args = ap.parse_args()
     import torch
 
@@ -73,14 +42,7 @@ def main():
     F = args.frames
     result = {"metric": "project_frames_per_s", "frames": F, "steps": args.steps, "warmup": args.warmup, "workloads": {}}
 
-    copy_tbs = None
-    if args.copybw:
-        out = subprocess.run([args.copybw], capture_output=True, text=True, timeout=600).stdout
-        rates = [float(m.group(1)) for m in re.finditer(r"^copy .*? ([0-9.]+) TB/s$", out, flags=re.M)]
-        copy_tbs = max(rates) if rates else None
-        result["copy_rate_GBps"] = copy_tbs * 1e3 if copy_tbs else None
-        result["copybw_lines"] = [l.strip() for l in out.splitlines() if l.startswith(("copy", "grid"))]
-
+    copy_tbs = bl.copy_rate(args.copybw, result)
     pool = [raw_returns(70000, s, nonfinite=False) for s in range(8)]
     big = np.concatenate([np.roll(pool[i % 8], 11 * i, axis=0) for i in range(29)])[:2_000_000]
     workloads = [
@@ -97,13 +59,8 @@ def main():
         torch.cuda.synchronize()
         ctx = bev_amd.BevContext(p, device=0, max_batch=8, max_points=max(p.slots, int(np.diff(offs).max())))
         step = lambda: ctx.project_device(kind, nf, d_in.data_ptr(), offs, d_out.data_ptr())
-        fenced, unfenced = _timed(ctx, step, args.steps, args.warmup)
-        ctx.profile_reset()
-        ctx.profile_enable(True)
-        step()
-        ctx.synchronize()
-        kernels = {k["name"]: k["total_ms"] for k in ctx.profile_get() if k["name"].startswith(("k_project", "k_kitti"))}
-        ctx.profile_enable(False)
+        fenced, unfenced = bl.timed(ctx, step, args.steps, args.warmup)
+        kernels = bl.kernel_ms(ctx, step, ("k_project", "k_kitti"))
         ctx.close()
         bytes_frame = (16.0 * int(offs[-1]) + 32.0 * n_out) / nf
         kernel_ms = sum(kernels.values())
@@ -122,9 +79,7 @@ def main():
     p = bev_amd.params_for_sensor("OS1_64")
     d_in, offs = _tiled(torch, [x[:65536] for x in pool], F, dev)
     d_rec = torch.empty(int(offs[-1]) * 32, dtype=torch.uint8, device=dev)
-    d_ord = torch.empty(F * p.slots * 32, dtype=torch.uint8, device=dev)
-    d_multi = torch.empty(F * p.n_layers * p.mat_size ** 2, dtype=torch.uint8, device=dev)
-    d_single = torch.empty(F * p.mat_size ** 2, dtype=torch.uint8, device=dev)
+    d_ord, d_multi, d_single = bl.bev_outputs(p, F, dev)
     torch.cuda.synchronize()
     ctx = bev_amd.BevContext(p, device=0, max_batch=args.sub_batch, max_points=65536)
     process = lambda: ctx.process_device(F, d_rec.data_ptr(), offs, d_ord.data_ptr(), d_multi.data_ptr(), d_single.data_ptr())
@@ -137,16 +92,14 @@ def main():
     ctx.synchronize()
     passes = []
     for _ in range(3):
-        a = _timed(ctx, both, args.steps, args.warmup)
-        b = _timed(ctx, process, args.steps, args.warmup)
+        a = bl.timed(ctx, both, args.steps, args.warmup)
+        b = bl.timed(ctx, process, args.steps, args.warmup)
         passes.append({"project_and_process_unfenced_frames_per_s": F / a[1], "process_alone_unfenced_frames_per_s": F / b[1],
                        "project_and_process_fenced_frames_per_s": F / a[0], "process_alone_fenced_frames_per_s": F / b[0]})
     modes = sorted(set(int(m) for m in ctx.frame_info(0, min(8, F % args.sub_batch or args.sub_batch))[:, 1]))
     ctx.close()
     result["mulran_end_to_end"] = {"passes": passes, "frame_modes_of_the_last_sub_batch": modes}
-    result["device"] = torch.cuda.get_device_name(0)
-    result["host"] = socket.gethostname()
-    print(json.dumps(result))
+    bl.emit(result, args)
 
 
 if __name__ == "__main__":

@@ -1,36 +1,27 @@
 """The copy-out launch of the two scan-to-map cloud calls (K_SUBMAP_VOX_OUT, K_SUBMAP_PN_OUT), profiled over
 batches of calls at leaf 0 (the concatenation goes out): the profiled ms per map of a launch, per batch.  One JSON line."""
-import json
-import sys
-from concurrent.futures import ThreadPoolExecutor
-from pathlib import Path
+import argparse
 
 import numpy as np
 
-REPO = Path(__file__).resolve().parent.parent
-sys.path.insert(0, str(REPO / "point-cloud-preprocessing-tools_amd"))
-sys.path.insert(0, str(REPO / "tests"))
+import benchlib as bl
 
 
 def main():
+    ap = argparse.ArgumentParser()
+    bl.std_args(ap, out=None)
+    args = ap.parse_args()
     import torch
 
     import bev_amd
-    from bev_amd import synth
 
     p = bev_amd.params_for_sensor("HDL_64E")
     F, S, W, NM, BATCHES, CALLS = 48, p.slots, 3, 16, 5, 20
     dev = torch.device("cuda:0")
-    with ThreadPoolExecutor(16) as ex:
-        frames = list(ex.map(lambda i: synth.sweep(p, i, keep=0.98, n_dup=5000), range(F)))
-    n_max = max(len(f) for f in frames)
-    ctx = bev_amd.BevContext(p, device=0, max_batch=F, max_points=n_max)
-    offs = np.zeros(F + 1, np.uint64)
-    offs[1:] = np.cumsum([len(f) for f in frames])
-    d_in = torch.from_numpy(np.concatenate(frames).view(np.uint8).reshape(-1)).to(dev)
-    d_ord = torch.empty(F * S * 32, dtype=torch.uint8, device=dev)
-    d_multi = torch.empty(F * p.n_layers * p.mat_size ** 2, dtype=torch.uint8, device=dev)
-    d_single = torch.empty(F * p.mat_size ** 2, dtype=torch.uint8, device=dev)
+    frames = bl.sweeps(p, F)
+    ctx = bev_amd.BevContext(p, device=0, max_batch=F, max_points=max(len(f) for f in frames))
+    offs, d_in = bl.upload(frames, dev)
+    d_ord, d_multi, d_single = bl.bev_outputs(p, F, dev)
     torch.cuda.synchronize()
     ctx.process_device(F, d_in.data_ptr(), offs, d_ord.data_ptr(), d_multi.data_ptr(), d_single.data_ptr())
     stride = bev_amd.regfront_max_out(S)
@@ -57,17 +48,11 @@ def main():
         rows = int(d_oc.cpu().numpy().astype(np.int64).sum())
         per = []
         for _ in range(BATCHES):
-            ctx.profile_reset()
-            ctx.profile_enable(True)
-            for _ in range(CALLS):
-                call()
-            ctx.synchronize()
-            st = [s for s in ctx.profile_get() if s["name"] == kern]
-            ctx.profile_enable(False)
-            per.append(st[0]["total_ms"] / st[0]["launches"] if st and st[0]["launches"] else None)
+            st = bl.kernel_ms(ctx, lambda: [call() for _ in range(CALLS)], names=(kern,)).get(kern)
+            per.append(st["ms_per_step"] / st["launches"] if st and st["launches"] else None)
         out[name] = {"kernel": kern, "rows_copied_per_launch": rows, "ms_per_launch_by_batch": per}
     ctx.close()
-    print(json.dumps(out))
+    bl.emit(out, args, machine=())
 
 
 if __name__ == "__main__":

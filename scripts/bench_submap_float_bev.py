@@ -2,108 +2,52 @@
 
     python scripts/bench_submap_float_bev.py [--frames 1000] [--steps 20] [--warmup 5] [--windows 1,5,21] [--out FILE] [--label TEXT]
 
-One JSON line, also written to --out (default profiles/submap_float_bev_bench.json).  The frames are marked HDL_64E sweeps
-(ordered and ground-marked by the oracle: what bev_process_device_resident leaves in d_ordered), interval 1.0, label-0 points
-skipped, all in one call.
-Workload: sliding windows of W frames at stride 1 (map i = frames i - W // 2 .. i + W // 2, clipped), frame j in map i under
-2 m along x and 1 degree of yaw per frame of distance j - i; the key frame itself under the identity.
+One JSON line, also written to --out (default profiles/submap_float_bev_bench.json).  The frames are benchlib's marked sweeps,
+the workload its sliding windows, interval 1.0, label-0 points skipped, all in one call.
 Yardstick: bev_float_bev_device_resident with the same W poses for every frame (W at most 64) in the same process: it does as
 many point-poses (a few more: its windows are not clipped at the ends) and zeroes and fills W times as many grids.  The two
-calls are timed alternately, run by run (A, B, A, B); a run is `warmup` steps, then `steps` fenced steps (call,
-bev_synchronize; the median is reported) and `steps` unfenced steps (back to back, one synchronisation; the mean).  The
-kernels' times come from bev_profile_get over five more steps of each call, alternated; the median step is reported, all five
-times beside it.  Beside them, profiled only: the yardstick's own work through the new call (F * W maps of one entry each),
-which separates what sharing grids between frames costs from what the kernel and the plan cost.
+calls are timed alternately, run by run (A, B, A, B), each run by benchlib.timed.  The kernels' times come from
+bev_profile_get over five more steps of each call, alternated; the median step is reported, all five times beside it.  Beside
+them, profiled only: the yardstick's own work through the new call (F * W maps of one entry each), which separates what
+sharing grids between frames costs from what the kernel and the plan cost.
 One full-window map's grid is compared with the oracle in every configuration: the numbers are of code that computes the
-right thing.
-BEV_AMD_LIB selects another build of the library; --label names it in the line."""
+right thing."""
 import argparse
-import json
-import os
-import statistics
 import sys
-import time
-from pathlib import Path
 
 import numpy as np
 
-REPO = Path(__file__).resolve().parent.parent
-sys.path.insert(0, str(REPO / "point-cloud-preprocessing-tools_amd"))
-sys.path.insert(0, str(REPO / "tests"))
-
-
-def _timed(ctx, step, steps, warmup):
-    for _ in range(warmup):
-        step()
-    ctx.synchronize()
-    fenced = []
-    for _ in range(steps):
-        t = time.perf_counter()
-        step()
-        ctx.synchronize()
-        fenced.append(time.perf_counter() - t)
-    t = time.perf_counter()
-    for _ in range(steps):
-        step()
-    ctx.synchronize()
-    return statistics.median(fenced), (time.perf_counter() - t) / steps
-
-
-def _kernel_ms(ctx, step, names):
-    ctx.profile_reset()
-    ctx.profile_enable(True)
-    step()
-    ctx.synchronize()
-    got = {k["name"]: k for k in ctx.profile_get()}
-    ctx.profile_enable(False)
-    return {n: {"ms_per_step": got[n]["total_ms"], "launches": got[n]["launches"]} for n in names if n in got}
+import benchlib as bl
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--frames", type=int, default=1000)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--windows", default="1,5,21")
-    ap.add_argument("--distinct", type=int, default=8, help="distinct sweeps the frames are tiled from")
-    ap.add_argument("--out", default=str(REPO / "profiles" / "submap_float_bev_bench.json"))
-    ap.add_argument("--label", default=None)
+    bl.std_args(ap, frames=1000, steps=20, warmup=5, distinct=8, out="submap_float_bev_bench.json")
     args = ap.parse_args()
     import torch
 
     import bev_amd
     import oracle_lib as orc
-    from bev_amd import synth
 
     if not torch.cuda.is_available():
         sys.exit("no GPU: nothing is measured (there is no CPU path)")
     dev = torch.device("cuda:0")
     F = args.frames
     p = bev_amd.params_for_sensor("HDL_64E")
-    sp = orc.sensor_from_params(p)
     S, M = p.slots, 201
     A, B = "k_submap_float_splat", "k_float_bev_batch"
     result = {"metric": "submap_float_bev_maps_per_s", "frames": F, "steps": args.steps, "warmup": args.warmup, "runs": "A, B, A, B",
-              "records_per_frame": S, "interval": 1.0, "skip_label0": 1, "mat_size": M,
-              "library": args.label or os.environ.get("BEV_AMD_LIB", "csrc/libbev_mi355x.so"), "windows": {}}
+              "records_per_frame": S, "interval": 1.0, "skip_label0": 1, "mat_size": M, "windows": {}}
 
-    distinct = [orc.mark_ground(sp, orc.order_cloud(sp, synth.sweep(p, s)))[0] for s in range(args.distinct)]
-    up = [torch.from_numpy(c.view(np.uint8).reshape(-1).copy()).to(dev) for c in distinct]
-    d_clouds = torch.empty(F * S * 32, dtype=torch.uint8, device=dev)
-    for f in range(F):
-        d_clouds[f * S * 32:(f + 1) * S * 32] = up[f % len(up)]
-    offs = np.arange(F + 1, dtype=np.uint64) * np.uint64(S)
+    t = bl.tiled_marked_frames(p, args.distinct, F, dev)
+    distinct, d_clouds, offs = t.clouds, t.d_clouds, t.offs
     ctx = bev_amd.BevContext(p, device=0, max_batch=8, max_points=S)
     assert int(ctx.lib.bev_float_bev_size(1.0)) == M
     for W in [int(w) for w in args.windows.split(",")]:
         h = W // 2
-        rel = {d: bev_amd.yaw_translate_matrix(2.0 * d, 0.0, 0.0, 1.0 * d) for d in range(-h, h + 1)}
-        assert np.array_equal(rel[0], np.eye(3, 4, dtype=np.float32).reshape(12))
-        windows = [range(max(0, i - h), min(F - 1, i + h) + 1) for i in range(F)]
-        map_offs = np.zeros(F + 1, dtype=np.uint64)
-        map_offs[1:] = np.cumsum([len(w) for w in windows])
-        entry_frame = np.array([j for w in windows for j in w], dtype=np.int32)
-        entry_pose = np.stack([rel[j - i] for i, w in enumerate(windows) for j in w])
+        rel = bl.relative_poses(W)
+        windows, map_offs, entry_frame, entry_pose = bl.sliding_windows(F, W, rel)
         poses = np.ascontiguousarray(np.broadcast_to(np.stack([rel[d] for d in range(-h, h + 1)]), (F, W, 12)))
         d_out = torch.empty(F * M * M, dtype=torch.float32, device=dev)
         y_out = torch.empty(F * W * M * M, dtype=torch.float32, device=dev)
@@ -114,7 +58,7 @@ def main():
         runs = {"submap": [], "float": []}
         for _ in range(2):
             for name, step in (("submap", a_step), ("float", b_step)):
-                fenced, unfenced = _timed(ctx, step, args.steps, args.warmup)
+                fenced, unfenced = bl.timed(ctx, step, args.steps, args.warmup)
                 runs[name].append({"fenced_median_ms": fenced * 1e3, "unfenced_mean_ms": unfenced * 1e3})
         # the kernels' times: five profiled steps of each call, alternated; the median step's figures are reported
         # (C: the yardstick's work through the new call — F * W maps of one entry, map f * W + k = frame f under pose k, into
@@ -125,9 +69,9 @@ def main():
         c_step = lambda: ctx.submap_float_bev_device(F, d_clouds.data_ptr(), offs, c_offs, c_frame, c_pose, y_out.data_ptr(), 1.0, True)
         pa, pb, pc = [], [], []
         for _ in range(5):
-            pa.append(_kernel_ms(ctx, a_step, (A,)))
-            pb.append(_kernel_ms(ctx, b_step, (B,)))
-            pc.append(_kernel_ms(ctx, c_step, (A,)))
+            pa.append(bl.kernel_ms(ctx, a_step, names=(A,)))
+            pb.append(bl.kernel_ms(ctx, b_step, names=(B,)))
+            pc.append(bl.kernel_ms(ctx, c_step, names=(A,)))
         ka = sorted(pa, key=lambda k: k[A]["ms_per_step"])[2]
         kb = sorted(pb, key=lambda k: k[B]["ms_per_step"])[2]
         ka[A]["ms_of_5_steps"] = [k[A]["ms_per_step"] for k in pa]
@@ -163,11 +107,7 @@ def main():
         del d_out, y_out
         torch.cuda.empty_cache()
     ctx.close()
-    result["device"] = torch.cuda.get_device_name(0)
-    line = json.dumps(result)
-    Path(args.out).parent.mkdir(parents=True, exist_ok=True)
-    Path(args.out).write_text(line + "\n")
-    print(line)
+    bl.emit(result, args, machine=("device",))
 
 
 if __name__ == "__main__":

@@ -6,13 +6,11 @@ D = 0, the fixed grids of 128 x 128 (fine) and 64 x 64 (coarse) cells at most, o
                                                [--dims 256,512,1024]
                                                [--out profiles/submap_search_grid_bench.json]
 
-Frames, moved copies, matches, windows and settings are scripts/bench_submap_voxel_registration.py's (fine: the whole tool's
-settings on the marked clouds) and scripts/bench_submap_pn_voxel_registration.py's (coarse: the coarse defaults on the front
-end's rows): bench.py's synthetic HDL_64E sweeps, frame i against a map of the moved copies i - W // 2 .. i + W // 2 (cyclic),
-the centre under the identity, the others under a seeded planar matrix within +-1 degree and +-0.3 m.  The yardstick is the
-D = 0 call of the same build, never an absolute figure.  Per stage (fine, coarse), leaf (0 and the thinning leaf) and window:
-one warm-up of each call, then for every D of [the stage's fixed cap through the new path, --dims] --rounds alternations of
-[D = 0 call, D call], each fenced (launch, bev_synchronize); the D call's results are compared byte for byte with the D = 0
+Frames, moved copies, matches and windows are benchlib's; the settings are bench_submap_voxel_registration.py's (fine: the
+whole tool's settings on the marked clouds) and bench_submap_pn_voxel_registration.py's (coarse: the coarse defaults on the
+front end's rows).  The yardstick is the D = 0 call of the same build, never an absolute figure.  Per stage (fine, coarse),
+leaf (0 and the thinning leaf) and window: one warm-up of each call, then for every D of [the stage's fixed cap through the new
+path, --dims] --rounds alternations of [D = 0 call, D call], each fenced; the D call's results are compared byte for byte with the D = 0
 call's BEFORE any of its times is recorded (a difference ends the run with status 1); then one profiled step of each: the ICP
 kernel's time over the sum of the results' iteration counts, the build's time (D > 0: the six launches of bev_submap_grid.h;
 D = 0: the kernels that hold the one-workgroup build), and from the hook max(nx, ny) and the largest count of one cell over
@@ -20,19 +18,12 @@ the maps of the last launch group.  One JSON line, rewritten after every run, so
 measured.  The fine D = 0 call on unthinned maps of 5 and 21 sweeps takes seconds per match list: --window-matches sets the fine
 stage's lists, --coarse-window-matches the coarse stage's (default: the same)."""
 import argparse
-import json
-import socket
 import statistics
 import sys
-import time
-from concurrent.futures import ThreadPoolExecutor
-from pathlib import Path
 
 import numpy as np
 
-REPO = Path(__file__).resolve().parent.parent
-sys.path.insert(0, str(REPO / "point-cloud-preprocessing-tools_amd"))
-sys.path.insert(0, str(REPO / "tests"))
+import benchlib as bl
 
 GRID_KERNELS = ("k_subgrid_bounds", "k_subgrid_header", "k_subgrid_count", "k_subgrid_sums", "k_subgrid_scan", "k_subgrid_scatter")
 # D = 0: the kernels whose one workgroup per map builds the grid (with the concatenation or the centroids, which cannot be split off)
@@ -43,79 +34,31 @@ FIXED_CAP = {"fine": 128, "coarse": 64}
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--frames", type=int, default=1000)
-    ap.add_argument("--moved", type=int, default=500)
-    ap.add_argument("--window-matches", default="1:500,5:100,21:40", help="W:n pairs: the window sizes and their matches")
     ap.add_argument("--coarse-window-matches", default=None, help="the coarse stage's W:n pairs (default: --window-matches)")
-    ap.add_argument("--sub-batch", type=int, default=500)
-    ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--map-leaf", type=float, default=0.2)
     ap.add_argument("--pn-leaf", type=float, default=0.2)
     ap.add_argument("--radius", type=float, default=2.0)
     ap.add_argument("--dims", default="256,512,1024", help="the caps beside the stage's fixed one")
     ap.add_argument("--stages", default="fine,coarse")
-    ap.add_argument("--out", default=str(REPO / "profiles" / "submap_search_grid_bench.json"))
+    bl.std_args(ap, frames=1000, moved=500, window_matches="1:500,5:100,21:40", sub_batch=500, rounds=3,
+                out="submap_search_grid_bench.json")
     args = ap.parse_args()
     import torch
 
     import bev_amd
-    from bev_amd import synth
 
-    p = bev_amd.params_for_sensor("HDL_64E")
-    F0, M, S = args.frames, args.moved, p.slots
-    dev = torch.device("cuda:0")
-    with ThreadPoolExecutor(16) as ex:
-        frames = list(ex.map(lambda i: synth.sweep(p, i, keep=0.98, n_dup=5000), range(F0)))
-    n_max = max(len(f) for f in frames)
-    ctx = bev_amd.BevContext(p, device=0, max_batch=args.sub_batch, max_points=n_max)
-    rng = np.random.default_rng(2026)
-    yaw = rng.uniform(-20, 20, M).astype(np.float32)
-    tr = rng.uniform(-1.5, 1.5, (M, 2)).astype(np.float32)
-    frames += [ctx.transform_cloud(frames[i], bev_amd.yaw_translate_matrix(float(tr[i, 0]), float(tr[i, 1]), 0.0,
-                                                                           float(yaw[i]))) for i in range(M)]
-    F = len(frames)
-    offs = np.zeros(F + 1, np.uint64)
-    offs[1:] = np.cumsum([len(f) for f in frames])
-    d_in = torch.from_numpy(np.concatenate(frames).view(np.uint8).reshape(-1)).to(dev)
-    del frames
-    d_ord = torch.empty(F * S * 32, dtype=torch.uint8, device=dev)
-    d_multi = torch.empty(F * p.n_layers * p.mat_size ** 2, dtype=torch.uint8, device=dev)
-    d_single = torch.empty(F * p.mat_size ** 2, dtype=torch.uint8, device=dev)
-    torch.cuda.synchronize()
-    ctx.process_device(F, d_in.data_ptr(), offs, d_ord.data_ptr(), d_multi.data_ptr(), d_single.data_ptr())
-    ctx.synchronize()
-    del d_in, d_multi, d_single
-    stride = bev_amd.regfront_max_out(S)
-    d_pn = torch.empty(F * stride * 48, dtype=torch.uint8, device=dev)
-    d_cnt = torch.zeros(F, dtype=torch.int32, device=dev)
-    ctx.registration_front_device(F, d_ord.data_ptr(), None, d_pn.data_ptr(), stride, d_cnt.data_ptr())
-    ctx.synchronize()
-
-    pairs = np.zeros(M, bev_amd.MATCH_DTYPE)
-    pairs["query_idx"] = np.arange(M)
-    pairs["match_idx"] = F0 + np.arange(M)
-    pairs["angle_guess"] = yaw + rng.uniform(-2, 2, M).astype(np.float32)
+    w = bl.registration_world(args)
+    ctx, d_ord, F, M, dev = w.ctx, w.d_ord, w.F, w.M, w.dev
+    stride, d_pn, d_cnt = bl.front_end(w)
+    pairs = bl.moved_copy_pairs(w)
     R = bev_amd.ICP_RESULT_DTYPE.itemsize
-    identity = np.eye(3, 4, dtype=np.float32).reshape(12)
     whole = bev_amd.icp_whole_defaults()
     out = {"metric": "submap_search_grid_time_over_fixed_grid", "sensor": "HDL_64E", "frames": F, "rounds": args.rounds,
            "map_leaf": args.map_leaf, "pn_leaf": args.pn_leaf, "settings": {"fine": "whole tool", "coarse": "coarse defaults"},
            "every_run_byte_equal_to_its_fixed_grid_partner": True, "runs": []}
 
-    def fenced(step):
-        t = time.perf_counter()
-        step()
-        ctx.synchronize()
-        return time.perf_counter() - t
-
-    def profiled(step):
-        ctx.profile_reset()
-        ctx.profile_enable(True)
-        step()
-        ctx.synchronize()
-        k = {s["name"]: s["total_ms"] for s in ctx.profile_get() if s["name"].startswith(("k_submap", "k_subgrid"))}
-        ctx.profile_enable(False)
-        return k
+    fenced = lambda step: bl.fenced(ctx, step, log=False)
+    profiled = lambda step: bl.kernel_ms(ctx, step, ("k_submap", "k_subgrid"))
 
     def grids(coarse, n_maps):
         for n in (n_maps, 1):
@@ -126,27 +69,11 @@ def main():
                 continue
         return None
 
-    def save():
-        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
-        Path(args.out).write_text(json.dumps(out) + "\n")
-
-    out["device"] = torch.cuda.get_device_name(0)
-    out["host"] = socket.gethostname()
-    lists = [(stage, int(w.split(":")[0]), min(M, int(w.split(":")[1])))
-             for stage in args.stages.split(",")
-             for w in (args.coarse_window_matches if stage == "coarse" and args.coarse_window_matches else args.window_matches).split(",")]
+    lists = [(stage, W, n) for stage in args.stages.split(",") for W, n in bl.parse_window_matches(
+        args.coarse_window_matches if stage == "coarse" and args.coarse_window_matches else args.window_matches, M)]
     for stage, W, n in sorted(lists, key=lambda l: l[1]):
-        half = W // 2
-        m_map = pairs[:n].copy()
-        m_map["match_idx"] = np.arange(n)
-        map_offs = np.arange(n + 1, dtype=np.uint64) * np.uint64(W)
-        entry_frame = np.zeros(n * W, np.int32)
-        entry_pose = np.zeros((n * W, 12), np.float32)
-        for i in range(n):
-            for k, d in enumerate(range(-half, half + 1)):
-                entry_frame[i * W + k] = F0 + (i + d) % M
-                entry_pose[i * W + k] = identity if d == 0 else bev_amd.yaw_translate_matrix(
-                    float(rng.uniform(-0.3, 0.3)), float(rng.uniform(-0.3, 0.3)), 0.0, float(rng.uniform(-1, 1)))
+        m_map = bl.map_matches(pairs, n)
+        map_offs, entry_frame, entry_pose = bl.cyclic_windows(w.rng, w.F0, M, n, W)
         coarse = stage == "coarse"
         for leaf in (0.0, args.pn_leaf if coarse else args.map_leaf):
             per = 2 if coarse else 1
@@ -177,10 +104,7 @@ def main():
                 if not same:
                     print(f"{stage} W {W} leaf {leaf} D {D}: the results differ from the D = 0 call's", file=sys.stderr)
                     sys.exit(1)
-                t_old, t_new = [], []
-                for _ in range(args.rounds):
-                    t_old.append(fenced(old))
-                    t_new.append(fenced(new))
+                t_old, t_new = bl.alternate(ctx, old, new, args.rounds, warm=False, log=False)
                 k_new = profiled(new)
                 g_new = grids(int(coarse), n)
                 assert (d_new.cpu().numpy().tobytes(), b_new.cpu().numpy().tobytes()) == ref
@@ -197,15 +121,14 @@ def main():
                        "wide_build_ms": sum(k_new.get(k, 0.0) for k in GRID_KERNELS),
                        "fixed_kernels_ms": k_old, "wide_kernels_ms": k_new, "fixed_grid": g_old, "wide_grid": g_new}
                 out["runs"].append(run)
-                save()
+                bl.emit(out, args, final=False)
                 print(f"{stage} W {W} leaf {leaf} D {D}: fixed {med_old * 1e3:.2f} ms, wide {med_new * 1e3:.2f} ms, ratio "
                       f"{med_new / med_old:.3f}; icp us/it {run['fixed_icp_us_per_iteration_problem']:.2f} -> "
                       f"{run['wide_icp_us_per_iteration_problem']:.2f}; build {run['wide_build_ms']:.3f} ms; grids {g_old} -> {g_new}",
                       file=sys.stderr, flush=True)
     ctx.set_submap_search_grid(0, 0)
     ctx.close()
-    print(json.dumps(out))
-    save()
+    bl.emit(out, args)
 
 
 if __name__ == "__main__":
