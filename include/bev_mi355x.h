@@ -973,6 +973,89 @@ int bev_debug_get_submap_grid(bev_ctx_t *ctx, int coarse, int first_map, int n_m
  * once another call (a scan-to-map one included) has used the stage's workspace. */
 int bev_debug_get_pair_grid(bev_ctx_t *ctx, int coarse, int first_match, int n_matches, uint32_t *out);
 
+/* ---- place retrieval: polar max-height descriptors and a match list -----------------------------------
+ * A rotation-searching polar descriptor in the manner of Scan Context (Kim and Kim, IROS 2018), and the brute-force search
+ * over all (query, candidate) pairs and all rotations that turns descriptors into the match list the registration calls
+ * start from.  The contract, whose arithmetic is csrc/bev_place_exact.h's on the host and on the device alike:
+ *   cell      r2 = x * x + y * y in float; ring k holds edge2[k] <= r2 < edge2[k + 1], edge2[k] = (float)(((double)max_range *
+ *             k / n_rings)^2); a point contributes iff 0 < r2 < edge2[n_rings] (not the origin's no-return records, NaN, inf)
+ *             and, with skip_label0, label != 0; sector = floorf(a * (float)n_sectors / 360.0f) clamped to n_sectors - 1, with
+ *             a = the azimuth of fd_atan2f(y, x) in degrees (degrees_of), + 360.0f where negative: counter-clockwise from +x;
+ *   value     min(127, max(0, (int)((z + lidar_to_ground) * 4))), the single-layer BEV's height code saturated at 127
+ *             (lidar_to_ground: the context's); a cell holds the maximum over its points, 0 when empty;
+ *   descriptor n_rings x n_sectors bytes, ring-major.  Of a map: that of the concatenation of bev_transform_cloud(frame, pose)
+ *             over its entries (the moved x, y, z);
+ *   columns   n2 = the sum of column s's squared values; unit[s][r] = (int)(127.0 * v / sqrt((double)n2) + 0.5) in double, 0
+ *             where n2 == 0; a column with n2 > 0 is "non-empty";
+ *   shift n   S_n = sum over j, r of unit_q[j][r] * unit_c[(j + n) % n_sectors][r]; cnt_n = the number of j with both columns
+ *             non-empty.  Score a beats score b iff S_a * cnt_b > S_b * cnt_a in 64-bit integers; cnt == 0 loses to every
+ *             cnt > 0; ties go to the lower shift.  distance = 1.0 - (double)S / (16129.0 * (double)cnt) of the pair's best
+ *             shift, 2.0 when every shift has cnt == 0 (the shift is 0 then);
+ *   yaw       angle_guess = n * (360 / n_sectors) degrees, less 360 where that is >= 180: the yaw with p_match ~
+ *             Rz(angle_guess) p_query, what the registration calls take as bev_match_t::angle_guess;
+ *   ranking   query q's candidates are 0 .. limit[q] - 1, ranked by the same comparison of their best shifts, ties to the
+ *             lower candidate index.
+ * Every output is integer work or a maximum: bit for bit whatever the launch shape. */
+typedef struct bev_place_params {
+    int32_t n_rings;     /* 4 ... 32 */
+    int32_t n_sectors;   /* 8 ... 64 */
+    float max_range;     /* finite, > 0: metres */
+    int32_t skip_label0; /* 0 or 1: as for bev_float_bev */
+} bev_place_params_t;
+typedef struct bev_place_hit { /* its first twelve bytes are a bev_match_t */
+    int32_t query_idx;
+    int32_t match_idx;  /* -1: the query has fewer candidates than top_k */
+    float angle_guess;  /* degrees, in [-180, 180) */
+    int32_t shift;      /* sectors */
+    double distance;    /* 1 - the mean cosine of the common columns; 2.0: no common column */
+} bev_place_hit_t;
+#define BEV_PLACE_MAX_TOP_K 64
+/* Host only.  The defaults: 20 rings, 60 sectors, 80.0f m, skip_label0 1.  The bytes of a descriptor, n_rings * n_sectors, and
+ * of the opaque per-descriptor record that bev_place_descriptor_device_resident writes and bev_place_match_device_resident
+ * reads (a multiple of 64); both 0 for parameters outside the admitted values (params NULL: the defaults). */
+bev_place_params_t bev_place_defaults(void);
+size_t bev_place_descriptor_bytes(const bev_place_params_t *params);
+size_t bev_place_desc_handle_bytes(const bev_place_params_t *params);
+/* The descriptors of frames or of maps over packed frames in device memory; asynchronous, on the context's stream.
+ * d_clouds, h_offsets : as for bev_float_bev_device_resident (records in the d_ordered layout).
+ * n_maps, h_map_offsets, h_entry_frame, h_entry_pose : as for bev_submap_float_bev_device_resident: descriptor g is map g's.
+ *                 All three arrays NULL with n_maps == 0: one descriptor per frame, from its RAW coordinates (not an identity
+ *                 pose, as in bev_float_bev_device_resident), n_frames descriptors.
+ * params        : NULL: the defaults.
+ * d_desc        : the descriptors, bev_place_descriptor_bytes each, one after the other; NULL: not wanted.
+ * d_units       : per descriptor one record of bev_place_desc_handle_bytes bytes, 64-byte aligned; NULL: not wanted.  Every
+ *                 byte of every record is written.
+ * Ordering      : as for bev_submap_float_bev_device_resident.
+ * Status        : that call's argument and status rules, with BEV_ERR_INVALID_ARG for parameters outside the admitted values
+ *                 (checked first, behind the context), for map arrays of which only some are NULL, for n_maps > 0 with NULL
+ *                 h_map_offsets, for both outputs NULL and for a misaligned d_units.  Nothing is launched in any of these
+ *                 cases.  No descriptors to make: BEV_OK.
+ * Workspace     : a plane of 4 bytes per cell and descriptor, and the tables of the submap calls.  Freed by bev_destroy. */
+int bev_place_descriptor_device_resident(bev_ctx_t *ctx, int n_frames, const bev_point_t *d_clouds, const uint64_t *h_offsets,
+                                         int n_maps, const uint64_t *h_map_offsets, const int32_t *h_entry_frame,
+                                         const float *h_entry_pose, const bev_place_params_t *params, uint8_t *d_desc,
+                                         void *d_units);
+/* The best top_k candidates of every query; asynchronous, on the context's stream, ordered like the call above.
+ * d_units_q, d_units_db : n_queries and n_db records of bev_place_descriptor_device_resident under the SAME params.
+ * h_limit       : n_queries values 0 ... n_db, query q's candidates being 0 .. h_limit[q] - 1; NULL: all of the database.
+ * top_k         : 1 ... BEV_PLACE_MAX_TOP_K.
+ * d_hits        : n_queries * top_k records, query q's at q * top_k in rank order; rows past the number of its candidates
+ *                 have match_idx -1, distance 2.0, shift 0 and angle_guess 0.
+ * Status        : BEV_ERR_INVALID_ARG for a NULL context, parameters outside the admitted values, negative counts, top_k
+ *                 outside its range, a limit outside 0 ... n_db, NULL d_hits or d_units_q with n_queries > 0, NULL d_units_db
+ *                 with n_db > 0.  n_queries == 0: BEV_OK.
+ * Workspace     : 8 bytes per pair of a group of queries (groups of at most 64 MiB; BEV_PLACE_QUERY_GROUP=<queries> sets the
+ *                 group, the results do not depend on it).  Freed by bev_destroy. */
+int bev_place_match_device_resident(bev_ctx_t *ctx, const bev_place_params_t *params, int n_queries, const void *d_units_q,
+                                    int n_db, const void *d_units_db, const int32_t *h_limit, int top_k,
+                                    bev_place_hit_t *d_hits);
+/* Both calls through HOST clouds, synchronous: every frame alone (raw coordinates) is a query, query q = frame q; the database
+ * is the maps (n_maps of them), or — all three map arrays NULL and n_maps == 0 — the frames themselves.  h_limit, top_k and
+ * hits (n_frames * top_k records) as above.  The frames go up through the context's input staging max_batch at a time. */
+int bev_place_retrieval_batch(bev_ctx_t *ctx, int n_frames, const bev_point_t *const *clouds, const uint32_t *n_pts, int n_maps,
+                              const uint64_t *h_map_offsets, const int32_t *h_entry_frame, const float *h_entry_pose,
+                              const bev_place_params_t *params, const int32_t *h_limit, int top_k, bev_place_hit_t *hits);
+
 int bev_abi_version(void);
 
 #ifdef __cplusplus

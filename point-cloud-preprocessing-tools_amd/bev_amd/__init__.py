@@ -106,6 +106,8 @@ ABI_SYMBOLS = [
     "bev_submap_top_part_max_out",
     "bev_set_submap_search_grid", "bev_debug_get_submap_grid",
     "bev_set_pair_search_grid", "bev_debug_get_pair_grid",
+    "bev_place_defaults", "bev_place_descriptor_bytes", "bev_place_desc_handle_bytes",
+    "bev_place_descriptor_device_resident", "bev_place_match_device_resident", "bev_place_retrieval_batch",
 ]
 
 # bev_debug_exact_eval (include/bev_mi355x.h, BEV_EVAL_* in id order): name -> (input kinds f / u / d, output kind, params)
@@ -145,6 +147,22 @@ def icp_params(max_correspondence_distance=10.0, max_iterations=10, transformati
                euclidean_fitness_epsilon=-1.7976931348623157e308) -> IcpParams:
     """The coarse defaults of the registration tools (bev_icp_coarse_defaults), any of them overridden."""
     return IcpParams(max_correspondence_distance, transformation_epsilon, euclidean_fitness_epsilon, max_iterations, 0)
+
+
+# place retrieval (include/bev_mi355x.h, DESIGN.md §6z): bev_place_hit_t, whose first twelve bytes are a MATCH_DTYPE record
+PLACE_HIT_DTYPE = np.dtype([("query_idx", "<i4"), ("match_idx", "<i4"), ("angle_guess", "<f4"), ("shift", "<i4"),
+                            ("distance", "<f8")])
+PLACE_MAX_TOP_K = 64  # BEV_PLACE_MAX_TOP_K
+
+
+class PlaceParams(C.Structure):
+    """bev_place_params_t"""
+    _fields_ = [("n_rings", C.c_int32), ("n_sectors", C.c_int32), ("max_range", C.c_float), ("skip_label0", C.c_int32)]
+
+
+def place_params(n_rings=20, n_sectors=60, max_range=80.0, skip_label0=True) -> PlaceParams:
+    """The defaults of place retrieval (bev_place_defaults), any of them overridden."""
+    return PlaceParams(n_rings, n_sectors, max_range, 1 if skip_label0 else 0)
 
 
 def load_lib() -> C.CDLL:
@@ -296,6 +314,16 @@ def load_lib() -> C.CDLL:
     if hasattr(lib, "bev_set_pair_search_grid"):
         lib.bev_set_pair_search_grid.argtypes = [vp, i32, i32]
         lib.bev_debug_get_pair_grid.argtypes = [vp, i32, i32, i32, vp]
+    if hasattr(lib, "bev_place_match_device_resident"):
+        lib.bev_place_defaults.argtypes = []
+        lib.bev_place_defaults.restype = PlaceParams
+        lib.bev_place_descriptor_bytes.argtypes = lib.bev_place_desc_handle_bytes.argtypes = [C.POINTER(PlaceParams)]
+        lib.bev_place_descriptor_bytes.restype = lib.bev_place_desc_handle_bytes.restype = sz
+        lib.bev_place_descriptor_device_resident.argtypes = [vp, i32, vp, C.POINTER(C.c_uint64), i32, vp, vp, vp,
+                                                             C.POINTER(PlaceParams), vp, vp]
+        lib.bev_place_match_device_resident.argtypes = [vp, C.POINTER(PlaceParams), i32, vp, i32, vp, vp, i32, vp]
+        lib.bev_place_retrieval_batch.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(u32), i32, vp, vp, vp,
+                                                  C.POINTER(PlaceParams), vp, i32, vp]
     _lib = lib
     return lib
 
@@ -559,6 +587,51 @@ class BevContext:
                                                  _ptr(entry_pose), _rows(out))
         self._check(rc, "bev_submap_float_bev_batch")
         return out
+
+    def place_descriptor_device(self, n_frames, d_clouds, offsets, d_desc, d_units, params: PlaceParams | None = None,
+                                map_offsets=None, entry_frame=None, entry_pose=None):
+        """bev_place_descriptor_device_resident on device pointers: frames as for float_bev_device; without map_offsets one
+        descriptor per frame from its raw coordinates, else one per map (maps and entries as for submap_bev_device).  d_desc
+        (0 or None: not wanted) receives place_descriptor_bytes(params) per descriptor, d_units (0 or None: not wanted) one
+        record of place_desc_handle_bytes(params), 64-byte aligned.  Asynchronous: synchronize() before the host reads them."""
+        offsets, offs = _offsets(offsets, n_frames)
+        prm = params if params is not None else place_params()
+        n_maps, mo, ef, ep = 0, None, None, None
+        if map_offsets is not None:
+            n_maps, mo, ef, ep = self._submap_entries(map_offsets, entry_frame, entry_pose)
+        rc = self.lib.bev_place_descriptor_device_resident(self._h, n_frames, C.c_void_p(d_clouds), offs, n_maps, _ptr(mo), _ptr(ef),
+                                                           _ptr(ep), C.byref(prm), C.c_void_p(d_desc or None),
+                                                           C.c_void_p(d_units or None))
+        self._check(rc, "bev_place_descriptor_device_resident")
+
+    def place_match_device(self, n_queries, d_units_q, n_db, d_units_db, d_hits, top_k=1, limit=None,
+                           params: PlaceParams | None = None):
+        """bev_place_match_device_resident on device pointers: the best top_k candidates of every query among candidates
+        0 .. limit[q] - 1 (None: all n_db) of the database; d_hits receives n_queries * top_k PLACE_HIT_DTYPE records, a query's
+        in rank order.  Asynchronous: synchronize() before the host reads d_hits."""
+        prm = params if params is not None else place_params()
+        lim = np.ascontiguousarray(limit, dtype=np.int32) if limit is not None else None
+        assert lim is None or lim.shape == (n_queries,)
+        rc = self.lib.bev_place_match_device_resident(self._h, C.byref(prm), n_queries, C.c_void_p(d_units_q or None), n_db,
+                                                      C.c_void_p(d_units_db or None), _ptr(lim), top_k, C.c_void_p(d_hits or None))
+        self._check(rc, "bev_place_match_device_resident")
+
+    def place_retrieval_batch(self, clouds, top_k=1, limit=None, params: PlaceParams | None = None, map_offsets=None,
+                              entry_frame=None, entry_pose=None):
+        """bev_place_retrieval_batch on host clouds: every frame a query, the database the maps (maps and entries as for
+        submap_bev_device) or, without map_offsets, the frames themselves; returns (n_frames, top_k) PLACE_HIT_DTYPE records."""
+        clouds, pts, npts = _host_clouds(clouds)
+        prm = params if params is not None else place_params()
+        n_maps, mo, ef, ep = 0, None, None, None
+        if map_offsets is not None:
+            n_maps, mo, ef, ep = self._submap_entries(map_offsets, entry_frame, entry_pose)
+        lim = np.ascontiguousarray(limit, dtype=np.int32) if limit is not None else None
+        assert lim is None or lim.shape == (len(clouds),)
+        hits = np.zeros((len(clouds), top_k), dtype=PLACE_HIT_DTYPE)
+        rc = self.lib.bev_place_retrieval_batch(self._h, len(clouds), pts, npts, n_maps, _ptr(mo), _ptr(ef), _ptr(ep),
+                                                C.byref(prm), _ptr(lim), top_k, _ptr(hits))
+        self._check(rc, "bev_place_retrieval_batch")
+        return hits
 
     def transform_cloud(self, cloud, m):
         cloud = np.ascontiguousarray(cloud, dtype=POINT_DTYPE)
@@ -1033,6 +1106,16 @@ def project_batch_out_points(kind: int, n_frames: int, offsets) -> int:
     """Records the d_out of project_device must hold (host only); 0 for an unknown kind or decreasing offsets."""
     offsets, offs = _offsets(offsets, n_frames)
     return int(load_lib().bev_project_batch_out_points(kind, n_frames, offs))
+
+
+def place_descriptor_bytes(params: PlaceParams | None = None) -> int:
+    """bev_place_descriptor_bytes: n_rings * n_sectors; 0 for parameters outside the admitted values."""
+    return int(load_lib().bev_place_descriptor_bytes(C.byref(params) if params is not None else None))
+
+
+def place_desc_handle_bytes(params: PlaceParams | None = None) -> int:
+    """bev_place_desc_handle_bytes: the opaque per-descriptor record of place_descriptor_device / place_match_device."""
+    return int(load_lib().bev_place_desc_handle_bytes(C.byref(params) if params is not None else None))
 
 
 def regfront_max_out(n: int) -> int:

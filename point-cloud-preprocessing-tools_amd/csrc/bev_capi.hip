@@ -927,6 +927,11 @@ void bev_destroy(bev_ctx_t *c)
     c->manip_grids.release();
     c->posed_tab.release();
     c->submap_tab.release();
+    c->place_tab.release();
+    c->place_lim.release();
+    c->place_planes.release();
+    c->place_pairs.release();
+    c->place_out.release();
     c->posed_ws.release();
     c->posed_imgs.release();
     for (auto &s : c->prof_pool) {

@@ -2,7 +2,7 @@
  * bev_capi_packed.hip — the batched calls over packed frames (several clouds one after the other in one buffer, described by
  * n_frames + 1 offsets) of the boundary declared extern "C" in include/bev_mi355x.h: projection of raw sweeps, float BEV,
  * posed BEVs, submap BEVs, float submap BEVs (DESIGN.md §6e – §6j).  Host-side only.  They share one path (§6h): the frame table
- * (upload_packed_table), the bracket of the device-resident calls (resident_call), the chunk loop of the host-buffer calls
+ * (upload_packed_table), the bracket of the device-resident calls (resident_call, bev_ctx.h), the chunk loop of the host-buffer calls
  * (packed_host_chunks) and the planes of a launch group (plane_pair_bytes, expand_planes).
  */
 #include "bev_ctx.h"
@@ -59,45 +59,9 @@ int upload_packed_table(bev_ctx *c, UploadTable &t, size_t min_cap, int nf, cons
     return rc != BEV_OK ? rc : t.push(c, pt->bytes);
 }
 
-/* the arguments every call over packed frames of the caller's has: BEV_OK, or what the entry point returns */
-int check_packed_frames(const bev_ctx *c, int n_frames, const uint64_t *h_offsets)
-{
-    if (!c || n_frames < 0 || !h_offsets) return BEV_ERR_INVALID_ARG;
-    const uint64_t cap = cloud_cap(c);
-    for (int f = 0; f < n_frames; ++f)
-        if (h_offsets[f + 1] < h_offsets[f]) return BEV_ERR_INVALID_ARG;
-    for (int f = 0; f < n_frames; ++f)
-        if (h_offsets[f + 1] - h_offsets[f] > cap) return BEV_ERR_TOO_LARGE;
-    return BEV_OK;
-}
-/* ... and the calls over host clouds: their arrays */
-bool host_clouds_ok(int n_frames, const bev_point_t *const *clouds, const uint32_t *n_pts)
-{
-    if (n_frames > 0 && (!clouds || !n_pts)) return false;
-    for (int f = 0; f < n_frames; ++f)
-        if (n_pts[f] && !clouds[f]) return false;
-    return true;
-}
 bool poses_ok(int n_poses, const float *h_poses, int max_poses)
 {
     return n_poses >= 0 && n_poses <= max_poses && (n_poses == 0 || h_poses);
-}
-
-/* A call on packed frames in device memory of the caller's: asynchronous, on the context's stream.  flush_pending joins the
- * stage streams into it, so a BEV call that still reads or writes the caller's buffers (a bev_process_device_resident whose
- * d_ordered this call reads, say) has launched all its stages and comes first; then whatever the caller has queued on the
- * default stream (the upload or the fill of its input, typically); then the body; and the stage streams of the next BEV call
- * wait for what record_tail records: it may read this call's output, or overwrite its input, at once. */
-template <class Body>
-int resident_call(bev_ctx *c, Body body)
-{
-    int rc = begin_call(c, false);
-    if (rc != BEV_OK) return rc;
-    rc = wait_default_stream(c);
-    if (rc != BEV_OK) return rc;
-    rc = body();
-    if (rc != BEV_OK) return rc;
-    return record_tail(c);
 }
 
 /* The host route of a batched call over packed frames (after begin_call with the staging): chunks of max_batch clouds fit the

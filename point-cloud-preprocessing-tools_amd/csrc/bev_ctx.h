@@ -1,8 +1,8 @@
 /*
- * bev_ctx.h — the context behind bev_ctx_t and what the four files of the C ABI share: bev_capi.hip (the context, the BEV
+ * bev_ctx.h — the context behind bev_ctx_t and what the five files of the C ABI share: bev_capi.hip (the context, the BEV
  * pipeline and the single-cloud entry points), bev_capi_packed.hip (the batched calls over packed frames), bev_capi_reg.hip
- * (the registration entry points, frame against frame) and bev_capi_submap_reg.hip (frames against submaps; what only these
- * two share: bev_reg_host.h) — among it the prologue of every call outside the fused pipeline (begin_call) and the bound
+ * (the registration entry points, frame against frame), bev_capi_submap_reg.hip (frames against submaps; what only these
+ * two share: bev_reg_host.h) and bev_capi_place.hip (place retrieval) — among it the prologue of every call outside the fused pipeline (begin_call) and the bound
  * on a cloud's points (cloud_cap).  Private, like bev_internal.h.  Named namespace: struct bev_ctx is one type in all of them.
  */
 #ifndef BEV_CTX_H
@@ -113,7 +113,7 @@ struct Downloader {
     }
 };
 
-/* ---- what the batched entry points keep between calls (defined in bev_capi.hip; used by all four files) ---- */
+/* ---- what the batched entry points keep between calls (defined in bev_capi.hip; used by all five files) ---- */
 /* a device buffer that grows when a call needs more */
 struct DevBuf {
     void *p = nullptr;
@@ -271,6 +271,11 @@ struct bev_ctx {
     /* bev_set_pair_search_grid: the same for the pair calls' targets; neither setter reads the other's state */
     int pair_grid_cap[2] = {0, 0};
     bevh::GridRecord pair_grid_rec[2];
+    /* place retrieval (bev_capi_place.hip): the frame table or plan and the ring edges of a descriptor call, the
+     * limits of a match call; the descriptors' planes; the pairs of a group of queries; what bev_place_retrieval_batch keeps on
+     * the device (unit records, hits); all allocated on first use and grown on demand */
+    bevh::UploadTable place_tab, place_lim;
+    bevh::DevBuf place_planes, place_pairs, place_out;
     int posed_group = 0; /* BEV_POSED_GROUP=1 .. 65535: grids per launch group (tests: results do not depend on it); 0: what fits kPosedWsCap */
 
     bevh::RegState reg;
@@ -332,6 +337,43 @@ int project_frames(bev_ctx *c, int kind, int nf, const float *d_xyzi, const uint
 /* What the submap entry points check of the maps (bev_capi_packed.hip): BEV_OK, or what the entry point returns.  The entry
  * arrays are read only when their length has passed. */
 int check_submap_entries(int n_frames, int n_maps, const uint64_t *map_offs, const int32_t *entry_frame, const float *entry_pose);
+
+/* ---- what the calls over packed frames share across files (bev_capi_packed.hip, bev_capi_place.hip) ---- */
+/* the arguments every call over packed frames of the caller's has: BEV_OK, or what the entry point returns */
+inline int check_packed_frames(const bev_ctx *c, int n_frames, const uint64_t *h_offsets)
+{
+    if (!c || n_frames < 0 || !h_offsets) return BEV_ERR_INVALID_ARG;
+    const uint64_t cap = cloud_cap(c);
+    for (int f = 0; f < n_frames; ++f)
+        if (h_offsets[f + 1] < h_offsets[f]) return BEV_ERR_INVALID_ARG;
+    for (int f = 0; f < n_frames; ++f)
+        if (h_offsets[f + 1] - h_offsets[f] > cap) return BEV_ERR_TOO_LARGE;
+    return BEV_OK;
+}
+/* ... and the calls over host clouds: their arrays */
+inline bool host_clouds_ok(int n_frames, const bev_point_t *const *clouds, const uint32_t *n_pts)
+{
+    if (n_frames > 0 && (!clouds || !n_pts)) return false;
+    for (int f = 0; f < n_frames; ++f)
+        if (n_pts[f] && !clouds[f]) return false;
+    return true;
+}
+/* A call on packed frames in device memory of the caller's: asynchronous, on the context's stream.  flush_pending joins the
+ * stage streams into it, so a BEV call that still reads or writes the caller's buffers (a bev_process_device_resident whose
+ * d_ordered this call reads, say) has launched all its stages and comes first; then whatever the caller has queued on the
+ * default stream (the upload or the fill of its input, typically); then the body; and the stage streams of the next BEV call
+ * wait for what record_tail records: it may read this call's output, or overwrite its input, at once. */
+template <class Body>
+int resident_call(bev_ctx *c, Body body)
+{
+    int rc = begin_call(c, false);
+    if (rc != BEV_OK) return rc;
+    rc = wait_default_stream(c);
+    if (rc != BEV_OK) return rc;
+    rc = body();
+    if (rc != BEV_OK) return rc;
+    return record_tail(c);
+}
 
 inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 /* one allocation in 256-byte aligned pieces: *dst[i] = the piece of sz[i] bytes (base == nullptr: nothing is written);

@@ -258,6 +258,10 @@ enum KernelId {
     K_PAIRGRID_DESC, /* the pair calls' search grids sized to the cloud (bev_pair_grid.h): the targets' point counts */
     K_FINE_ICP_WIDE, /* K_FINE_ICP against such a grid */
     K_ICP_WIDE,      /* K_ICP against such a grid, its offsets in global memory */
+    K_PLACE_SPLAT,   /* place retrieval (bev_place.h): the points of frames, or of maps' entries, into polar max-height planes */
+    K_PLACE_FINISH,  /* ... the planes into descriptor bytes, unit columns and column masks */
+    K_PLACE_PAIRS,   /* ... the best shift of every (query, candidate) pair */
+    K_PLACE_TOPK,    /* ... the best top_k candidates of every query */
     K_COUNT
 };
 const char *kernel_name(int id);
@@ -369,6 +373,33 @@ void launch_submap_splat(const bev_point_t *clouds, const void *rows, const uint
  * per map, the atomics' target, zeroed by the caller on the same stream */
 void launch_submap_float_splat(const bev_point_t *clouds, const void *rows, const uint32_t *ent0, int nf, uint32_t blocks,
                                const void *entries, float interval, int M, bool skip_label0, float *grids, hipStream_t st);
+/* ---- place retrieval: polar descriptors and the search over pairs and rotations (bev_place.h) ---- */
+struct PlaceShape { /* a descriptor's shape and what a point's value needs (the ring edges go up beside the frame table) */
+    int n_rings, n_sectors, skip_label0;
+    float lidar_to_ground;
+};
+constexpr int kPlaceWords = 8; /* words of a unit column: 32 rings, four to a word */
+constexpr int kPlaceTile = 64; /* candidates per workgroup of k_place_pairs */
+/* the opaque per-descriptor record of the C ABI (bev_place_desc_handle_bytes): unit[s] column s's unit values, ring r in byte
+ * r % 4 of word r / 4, zero past n_rings and in the columns past n_sectors; mask: bit s set where column s is not empty */
+struct alignas(64) PlaceHandle {
+    uint32_t unit[64][kPlaceWords];
+    uint64_t mask;
+    uint32_t pad[14];
+};
+static_assert(sizeof(PlaceHandle) == 2112, "the device reads this layout");
+/* rows, ent0, blocks and entries as for launch_submap_float_splat (ent0 == nullptr: no maps, row f's raw points into plane f);
+ * edge2: n_rings + 1 floats on the device; planes: n_rings * n_sectors words per descriptor, zeroed by the caller on the stream */
+void launch_place_splat(const bev_point_t *clouds, const void *rows, const uint32_t *ent0, int nf, uint32_t blocks,
+                        const void *entries, const float *edge2, const PlaceShape &ps, uint32_t *planes, hipStream_t st);
+/* n_desc planes into desc (nullptr: not wanted) and units (nullptr: not wanted) */
+void launch_place_finish(const uint32_t *planes, int n_desc, const PlaceShape &ps, uint8_t *desc, PlaceHandle *units, hipStream_t st);
+/* queries [q0, q0 + nq) of uq against candidates 0 .. limit[q] - 1 of udb (limit == nullptr: n_db; a device array indexed by
+ * q): pairs[(q - q0) * n_db + c] = the pair's best (S, cnt | shift << 16); then their top_k hits into hits + q * top_k */
+void launch_place_pairs(const PlaceHandle *uq, int q0, int nq, const PlaceHandle *udb, int n_db, const int32_t *limit,
+                        const PlaceShape &ps, uint2 *pairs, hipStream_t st);
+void launch_place_topk(const uint2 *pairs, int q0, int nq, int n_db, const int32_t *limit, const PlaceShape &ps, int top_k,
+                       bev_place_hit_t *hits, hipStream_t st);
 void launch_angle_debug(const float *dx, const float *dy, const float *dz, uint8_t *out, size_t n, hipStream_t st);
 /* element i of function `id` (bev_exact_eval.h) for i < n: in its device arrays, prm its 12 floats (nullptr: zeros), out n * out_words words */
 void launch_exact_eval(int id, const void *const in[4], const float *prm, uint32_t *out, uint32_t out_words, size_t n, hipStream_t st);

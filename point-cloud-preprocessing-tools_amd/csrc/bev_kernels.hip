@@ -53,6 +53,7 @@
 #include "bev_pair_grid.h"
 #include "bev_submap_grid.h"
 #include "bev_wide_icp.h"
+#include "bev_place.h"
 
 using namespace bevx;
 
@@ -74,6 +75,7 @@ static const char *const kNames[K_COUNT] = {
     "k_subgrid_bounds", "k_subgrid_header", "k_subgrid_count", "k_subgrid_sums", "k_subgrid_scan", "k_subgrid_scatter",
     "k_submap_icp_wide", "k_submap_coarse_icp_wide",
     "k_pairgrid_desc", "k_fine_icp_wide", "k_icp_wide",
+    "k_place_splat", "k_place_finish", "k_place_pairs", "k_place_topk",
 };
 const char *kernel_name(int id) { return (id >= 0 && id < K_COUNT) ? kNames[id] : "?"; }
 
@@ -325,6 +327,52 @@ void launch_submap_float_splat(const bev_point_t *clouds, const void *rows, cons
     hipLaunchKernelGGL(k_submap_float_splat, dim3(blocks), dim3(256), 0, st, clouds, static_cast<const ProjFrame *>(rows), ent0,
                        nf, static_cast<const bevsub::Entry *>(entries), interval, M, skip_label0 ? 1 : 0,
                        reinterpret_cast<uint32_t *>(grids));
+}
+void launch_place_splat(const bev_point_t *clouds, const void *rows, const uint32_t *ent0, int nf, uint32_t blocks,
+                        const void *entries, const float *edge2, const PlaceShape &ps, uint32_t *planes, hipStream_t st)
+{
+    if (blocks == 0 || nf == 0) return;
+    if (ent0)
+        hipLaunchKernelGGL(k_place_splat<true>, dim3(blocks), dim3(256), 0, st, clouds, static_cast<const ProjFrame *>(rows), ent0,
+                           nf, static_cast<const bevsub::Entry *>(entries), edge2, ps, planes);
+    else
+        hipLaunchKernelGGL(k_place_splat<false>, dim3(blocks), dim3(256), 0, st, clouds, static_cast<const ProjFrame *>(rows), ent0,
+                           nf, static_cast<const bevsub::Entry *>(entries), edge2, ps, planes);
+}
+void launch_place_finish(const uint32_t *planes, int n_desc, const PlaceShape &ps, uint8_t *desc, PlaceHandle *units, hipStream_t st)
+{
+    if (n_desc == 0) return;
+    hipLaunchKernelGGL(k_place_finish, dim3((unsigned)n_desc), dim3(64), 0, st, planes, ps, desc, units);
+}
+/* fn(kWords) for the words of a column that hold rings */
+template <class F>
+static void with_place_words(int n_rings, F &&fn)
+{
+    switch ((n_rings + 3) / 4) {
+    case 1: return fn(std::integral_constant<int, 1>{});
+    case 2: return fn(std::integral_constant<int, 2>{});
+    case 3: return fn(std::integral_constant<int, 3>{});
+    case 4: return fn(std::integral_constant<int, 4>{});
+    case 5: return fn(std::integral_constant<int, 5>{});
+    case 6: return fn(std::integral_constant<int, 6>{});
+    case 7: return fn(std::integral_constant<int, 7>{});
+    default: return fn(std::integral_constant<int, 8>{});
+    }
+}
+void launch_place_pairs(const PlaceHandle *uq, int q0, int nq, const PlaceHandle *udb, int n_db, const int32_t *limit,
+                        const PlaceShape &ps, uint2 *pairs, hipStream_t st)
+{
+    if (nq == 0 || n_db == 0) return;
+    const dim3 grid((unsigned)((n_db + kPlaceTile - 1) / kPlaceTile), (unsigned)nq);
+    with_place_words(ps.n_rings, [&](auto w) {
+        hipLaunchKernelGGL((k_place_pairs<decltype(w)::value>), grid, dim3(256), 0, st, uq, q0, udb, n_db, limit, ps.n_sectors, pairs);
+    });
+}
+void launch_place_topk(const uint2 *pairs, int q0, int nq, int n_db, const int32_t *limit, const PlaceShape &ps, int top_k,
+                       bev_place_hit_t *hits, hipStream_t st)
+{
+    if (nq == 0) return;
+    hipLaunchKernelGGL(k_place_topk, dim3((unsigned)nq), dim3(256), 0, st, pairs, q0, n_db, limit, ps.n_sectors, top_k, hits);
 }
 void launch_project_kitti(int step, const float *xyzi, const ProjFrame *tab, int nf, uint32_t n_max, const KittiWork &w,
                           bev_point_t *out, hipStream_t st)
