@@ -1056,6 +1056,81 @@ int bev_place_retrieval_batch(bev_ctx_t *ctx, int n_frames, const bev_point_t *c
                               const uint64_t *h_map_offsets, const int32_t *h_entry_frame, const float *h_entry_pose,
                               const bev_place_params_t *params, const int32_t *h_limit, int top_k, bev_place_hit_t *hits);
 
+/* ---- verification of registered matches: two-way inlier counts --------------------------------------------
+ * What "retrieve, register" lacks: under the transform a registration returned, how many points of each cloud have a neighbour
+ * in the other within a distance, in both directions.  bev_icp_result_t::fitness is a mean over all source points without a cap,
+ * and says nothing of how much of the target the query explains; these counts do.  The contract, for match
+ * m = (query_idx, match_idx, .) with T = d_results[m].T (rows 0 ... 2):
+ *   query cloud  : Q = bev_voxel_grid_irct(frame query_idx, leaf);
+ *   moved point  : q' = (T0 x + (T1 y + (T2 z + T3)), T4 x + (T5 y + (T6 z + T7)), T8 x + (T9 y + (T10 z + T11))): the ICP's own
+ *                  association, the very point the fitness is measured at;
+ *   target cloud : the pair call: P = bev_voxel_grid_irct(frame match_idx, leaf); the submap call: the target of
+ *                  bev_submap_voxel_registration_device_resident for (leaf, map_leaf): the concatenation in entry order, thinned
+ *                  over the union when map_leaf > 0;
+ *   searchable   : a point whose x, y and z are finite.  n_query counts the searchable q', n_target the searchable p;
+ *   distance     : d(a, B) = the minimum over searchable b of the float (dx dx + dy dy) + dz dz (the ICP's expression; the same
+ *                  float in either direction of the subtraction);
+ *   counting     : a point counts at k iff (double)d <= (double)threshold[k] * (double)threshold[k] (the form of the ICP's
+ *                  correspondence rule).  query_within[k] counts the searchable q' with d(q', P) inside the rule,
+ *                  target_within[k] the searchable p with d(p, Q') inside it;
+ *   empty cases  : every count is 0 when the other side has no searchable point or the map is empty; a NaN in T gives
+ *                  n_query = 0 and all sixteen counts 0; slots k >= n_thresholds are 0; every byte of the record is written.
+ * The outputs are integers: no float sum appears anywhere, and no output depends on an atomic's order, on the launch shape, on
+ * how a cloud is cut into slices or a match list into groups.  No inlier mean or RMSE is returned on purpose: the thresholds
+ * give the distribution. */
+#define BEV_VERIFY_MAX_THRESHOLDS 8
+typedef struct bev_verify_params {   /* 40 bytes */
+    float leaf;                      /* the voxel grid of every frame: as bev_fine_registration_device_resident's leaf */
+    int32_t n_thresholds;            /* 1 ... 8 */
+    float threshold[8];              /* metres; the first n_thresholds finite, > 0, strictly ascending; the rest 0 */
+} bev_verify_params_t;
+typedef struct bev_verify_result {   /* 72 bytes */
+    uint32_t n_query, n_target;      /* searchable points of the moved query / of the target */
+    uint32_t query_within[8];        /* moved query points whose nearest target point is within threshold[k] */
+    uint32_t target_within[8];       /* target points whose nearest moved query point is within threshold[k] */
+} bev_verify_result_t;
+/* leaf 0.2; thresholds 0.1, 0.2, 0.5, 1.0.  Host only. */
+bev_verify_params_t bev_verify_defaults(void);
+/* One problem on host clouds (synchronous), no voxel grid: params->leaf is ignored; only x, y, z are read.  T16: row-major
+ * 4 x 4, rows 0 ... 2 read (NULL: BEV_ERR_INVALID_ARG).  params NULL: the defaults.  Parameters outside the ranges above ->
+ * BEV_ERR_INVALID_ARG before anything is launched. */
+int bev_verify_clouds(bev_ctx_t *ctx, const bev_point_t *src, uint32_t n_src, const bev_point_t *tgt, uint32_t n_tgt,
+                      const float *T16, const bev_verify_params_t *params, bev_verify_result_t *result);
+/* The counts of a list of registered matches, frame against frame, device-resident.
+ * d_clouds, h_offsets : as bev_fine_registration_device_resident (h_offsets NULL: d_ordered, S records per frame)
+ * h_matches           : n_matches HOST records; angle_guess is not read
+ * d_results           : n_matches bev_icp_result_t (device); only .T is read, so bev_fine_registration_device_resident's output
+ *                       goes in as it is, with no synchronisation between the two calls
+ * d_verify            : n_matches records (device).  params NULL: the defaults.
+ * Asynchronous and ordered exactly like the fine call: it starts behind every earlier call on the context and behind the
+ * caller's default-stream work; bev_synchronize() before reading.  Everything the fine call refuses (bad offsets, match indices
+ * out of range, a leaf that is not finite and > 0) and every parameter outside its range is BEV_ERR_INVALID_ARG before anything
+ * is launched.
+ * Workspace, allocated on first use (grown when a call needs more) and freed by bev_destroy: the fine call's per frame, with U, N
+ * and K as there, U * (48 N + 4 * 16385 + 36) + min(U, 256) * (8 K + 4 N + 4) bytes, plus min(n_matches, 1024) *
+ * (32 N + 4 * 16385 + 32) bytes of moved queries and their grids, plus the tables (16 bytes per frame, 24 per match).  The call
+ * voxelises the frames itself: reusing the voxel clouds a preceding fine call left in the workspace is out of scope.  It always
+ * runs the default search grids (at most 128 x 128 cells, one workgroup's build): bev_set_pair_search_grid and
+ * bev_set_submap_search_grid are not read.  Matches run in launches of 1024 and a cloud's points in workgroups of 256
+ * (BEV_VERIFY_SLICE=<points> sets the latter); no result depends on either. */
+int bev_verify_registration_device_resident(bev_ctx_t *ctx, int n_frames, const bev_point_t *d_clouds, const uint64_t *h_offsets,
+                                            int n_matches, const bev_match_t *h_matches, const bev_icp_result_t *d_results,
+                                            const bev_verify_params_t *params, bev_verify_result_t *d_verify);
+/* The same against maps: match_idx is a MAP's index, the maps, map_leaf and the limits (BEV_SUBMAP_MAX_ENTRIES,
+ * BEV_SUBMAP_REG_MAX_TARGET) those of bev_submap_voxel_registration_device_resident, whose d_results go in as they are.  The
+ * workspace is that call's, plus the moved queries and their grids as above. */
+int bev_submap_verify_registration_device_resident(bev_ctx_t *ctx, int n_frames, const bev_point_t *d_clouds,
+                                                   const uint64_t *h_offsets, int n_maps, const uint64_t *h_map_offsets,
+                                                   const int32_t *h_entry_frame, const float *h_entry_pose, float map_leaf,
+                                                   int n_matches, const bev_match_t *h_matches,
+                                                   const bev_icp_result_t *d_results, const bev_verify_params_t *params,
+                                                   bev_verify_result_t *d_verify);
+/* The pair call through HOST buffers, synchronous: clouds / n_pts as the other _batch forms, results n_matches HOST records of
+ * which .T is read, verify n_matches HOST records. */
+int bev_verify_registration_batch(bev_ctx_t *ctx, int n_frames, const bev_point_t *const *clouds, const uint32_t *n_pts,
+                                  int n_matches, const bev_match_t *h_matches, const bev_icp_result_t *results,
+                                  const bev_verify_params_t *params, bev_verify_result_t *verify);
+
 int bev_abi_version(void);
 
 #ifdef __cplusplus

@@ -108,6 +108,8 @@ ABI_SYMBOLS = [
     "bev_set_pair_search_grid", "bev_debug_get_pair_grid",
     "bev_place_defaults", "bev_place_descriptor_bytes", "bev_place_desc_handle_bytes",
     "bev_place_descriptor_device_resident", "bev_place_match_device_resident", "bev_place_retrieval_batch",
+    "bev_verify_defaults", "bev_verify_clouds", "bev_verify_registration_device_resident",
+    "bev_submap_verify_registration_device_resident", "bev_verify_registration_batch",
 ]
 
 # bev_debug_exact_eval (include/bev_mi355x.h, BEV_EVAL_* in id order): name -> (input kinds f / u / d, output kind, params)
@@ -163,6 +165,24 @@ class PlaceParams(C.Structure):
 def place_params(n_rings=20, n_sectors=60, max_range=80.0, skip_label0=True) -> PlaceParams:
     """The defaults of place retrieval (bev_place_defaults), any of them overridden."""
     return PlaceParams(n_rings, n_sectors, max_range, 1 if skip_label0 else 0)
+
+
+# verification of registered matches (include/bev_mi355x.h, DESIGN.md §6aa): bev_verify_result_t
+VERIFY_MAX_THRESHOLDS = 8  # BEV_VERIFY_MAX_THRESHOLDS
+VERIFY_RESULT_DTYPE = np.dtype([("n_query", "<u4"), ("n_target", "<u4"), ("query_within", "<u4", (8,)),
+                                ("target_within", "<u4", (8,))])
+
+
+class VerifyParams(C.Structure):
+    """bev_verify_params_t"""
+    _fields_ = [("leaf", C.c_float), ("n_thresholds", C.c_int32), ("threshold", C.c_float * 8)]
+
+
+def verify_params(thresholds=(0.1, 0.2, 0.5, 1.0), leaf=0.2) -> VerifyParams:
+    """The defaults of the verification calls (bev_verify_defaults), either of them overridden.  More than 8 thresholds: the
+    first 8 go into the record and n_thresholds says how many were given, which the calls refuse."""
+    t = [float(v) for v in thresholds]
+    return VerifyParams(leaf, len(t), (C.c_float * 8)(*t[:8]))
 
 
 def load_lib() -> C.CDLL:
@@ -324,6 +344,17 @@ def load_lib() -> C.CDLL:
         lib.bev_place_match_device_resident.argtypes = [vp, C.POINTER(PlaceParams), i32, vp, i32, vp, vp, i32, vp]
         lib.bev_place_retrieval_batch.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(u32), i32, vp, vp, vp,
                                                   C.POINTER(PlaceParams), vp, i32, vp]
+    if hasattr(lib, "bev_verify_registration_device_resident"):
+        lib.bev_verify_defaults.argtypes = []
+        lib.bev_verify_defaults.restype = VerifyParams
+        lib.bev_verify_clouds.argtypes = [vp, vp, u32, vp, u32, vp, C.POINTER(VerifyParams), vp]
+        lib.bev_verify_registration_device_resident.argtypes = [vp, i32, vp, C.POINTER(C.c_uint64), i32, vp, vp,
+                                                                C.POINTER(VerifyParams), vp]
+        lib.bev_submap_verify_registration_device_resident.argtypes = [vp, i32, vp, C.POINTER(C.c_uint64), i32,
+                                                                       C.POINTER(C.c_uint64), vp, vp, C.c_float, i32, vp, vp,
+                                                                       C.POINTER(VerifyParams), vp]
+        lib.bev_verify_registration_batch.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(u32), i32, vp, vp,
+                                                      C.POINTER(VerifyParams), vp]
     _lib = lib
     return lib
 
@@ -993,6 +1024,60 @@ class BevContext:
             pn_leaf, radius, _ptr(vp), n_maps, map_offsets.ctypes.data_as(C.POINTER(C.c_uint64)), _ptr(entry_frame),
             _ptr(entry_pose), len(m), _ptr(m) if len(m) else None, C.byref(prm), C.c_void_p(d_results or None),
             C.c_void_p(d_best or None)), "bev_submap_top_part_coarse_registration_device_resident")
+
+    # ---- verification of registered matches: two-way inlier counts --------------------------------------
+    def verify_clouds(self, src, tgt, T, params: VerifyParams | None = None):
+        """One problem: src / tgt are POINT_DTYPE records (or (n, 3) / (n, 4) float rows: x, y, z), T a 4 x 4 whose rows
+        0 ... 2 move src; params None: the defaults (the leaf is not read: no voxel grid).  Returns one VERIFY_RESULT_DTYPE
+        record."""
+        src, tgt = as_points(src), as_points(tgt)
+        t16 = np.ascontiguousarray(np.asarray(T, dtype=np.float32).reshape(16))
+        prm = params if params is not None else verify_params()
+        out = np.zeros(1, dtype=VERIFY_RESULT_DTYPE)
+        self._check(self.lib.bev_verify_clouds(self._h, _ptr(src) if len(src) else None, len(src),
+                                               _ptr(tgt) if len(tgt) else None, len(tgt), _ptr(t16), C.byref(prm), _ptr(out)),
+                    "bev_verify_clouds")
+        return out[0]
+
+    def verify_registration_device(self, n_frames, d_clouds, offsets, matches, d_results, d_verify,
+                                   params: VerifyParams | None = None):
+        """bev_verify_registration_device_resident on device pointers: frames as for fine_registration_device, d_results its
+        output (only T is read).  Asynchronous: synchronize() before reading d_verify (one VERIFY_RESULT_DTYPE per match)."""
+        offsets, offs = _offsets(offsets, n_frames) if offsets is not None else (None, None)
+        m = np.ascontiguousarray(matches, dtype=MATCH_DTYPE)
+        prm = params if params is not None else verify_params()
+        self._check(self.lib.bev_verify_registration_device_resident(
+            self._h, n_frames, C.c_void_p(d_clouds or None), offs, len(m), _ptr(m) if len(m) else None,
+            C.c_void_p(d_results or None), C.byref(prm), C.c_void_p(d_verify or None)),
+            "bev_verify_registration_device_resident")
+
+    def submap_verify_registration_device(self, n_frames, d_clouds, offsets, map_offsets, entry_frame, entry_pose, matches,
+                                          d_results, d_verify, map_leaf=0.0, params: VerifyParams | None = None):
+        """bev_submap_verify_registration_device_resident: the same against maps; maps, entries and map_leaf as for
+        submap_voxel_registration_device, whose d_results go in as they are."""
+        offsets, offs = _offsets(offsets, n_frames) if offsets is not None else (None, None)
+        n_maps, map_offsets, entry_frame, entry_pose = self._submap_entries(map_offsets, entry_frame, entry_pose)
+        m = np.ascontiguousarray(matches, dtype=MATCH_DTYPE)
+        prm = params if params is not None else verify_params()
+        self._check(self.lib.bev_submap_verify_registration_device_resident(
+            self._h, n_frames, C.c_void_p(d_clouds or None), offs, n_maps, map_offsets.ctypes.data_as(C.POINTER(C.c_uint64)),
+            _ptr(entry_frame), _ptr(entry_pose), map_leaf, len(m), _ptr(m) if len(m) else None, C.c_void_p(d_results or None),
+            C.byref(prm), C.c_void_p(d_verify or None)), "bev_submap_verify_registration_device_resident")
+
+    def verify_registration_batch(self, clouds, matches, results, params: VerifyParams | None = None):
+        """bev_verify_registration_batch on host clouds: matches MATCH_DTYPE records or (query_idx, match_idx, angle_guess)
+        tuples, results their ICP_RESULT_DTYPE records (only T is read).  Returns (n_matches,) VERIFY_RESULT_DTYPE."""
+        clouds, pts, npts = _host_clouds(clouds)
+        m = np.array([tuple(r) for r in matches], dtype=MATCH_DTYPE) if not isinstance(matches, np.ndarray) else \
+            np.ascontiguousarray(matches, dtype=MATCH_DTYPE)
+        res = np.ascontiguousarray(results, dtype=ICP_RESULT_DTYPE).reshape(-1)
+        assert len(res) == len(m)
+        prm = params if params is not None else verify_params()
+        out = np.zeros(len(m), dtype=VERIFY_RESULT_DTYPE)
+        self._check(self.lib.bev_verify_registration_batch(
+            self._h, len(clouds), pts, npts, len(m), _ptr(m) if len(m) else None, _ptr(res) if len(m) else None,
+            C.byref(prm), _ptr(out) if len(m) else None), "bev_verify_registration_batch")
+        return out
 
     def set_layout_hint(self, layout: int):
         """LAYOUT_UNKNOWN (the library looks), LAYOUT_STRUCTURED, LAYOUT_FIRING_ORDER: include/bev_mi355x.h"""

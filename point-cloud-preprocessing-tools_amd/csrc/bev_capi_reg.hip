@@ -22,8 +22,8 @@ using namespace bevh;
 /* ---- what the entry points keep between calls (RegState, bev_ctx.h; DevBuf and UploadTable themselves: bev_capi.hip) ---- */
 void RegState::release()
 {
-    for (DevBuf *b : {&rf_buf, &icp_buf, &icp_one, &fine_buf, &fine_in, &sub_res}) b->release();
-    for (UploadTable *t : {&rf_offs, &icp_tab, &fine_tab}) t->release();
+    for (DevBuf *b : {&rf_buf, &icp_buf, &icp_one, &fine_buf, &fine_in, &sub_res, &verify_buf, &verify_io}) b->release();
+    for (UploadTable *t : {&rf_offs, &icp_tab, &fine_tab, &verify_tab}) t->release();
     if (tail_ev) (void)hipEventDestroy(tail_ev);
     tail_ev = nullptr;
     tail_pending = false;
@@ -677,3 +677,11 @@ int bev_debug_get_pair_grid(bev_ctx_t *c, int coarse, int first_match, int n_mat
 }
 
 } /* extern "C" */
+
+/* ---- the fine stage's workspace without an ICP launch's scratch (bev_reg_host.h): what the verification calls work in ---- */
+int bevh::fine_slots_setup(bev_ctx *c, size_t U, size_t Pn, const std::vector<FineSlot> &slots, FineWork &w, const FineSlot **d_slots)
+{
+    const FineProblem *d_probs;
+    PairGrid none;
+    return fine_setup(c, U, Pn, slots, std::vector<FineProblem>{}, w, d_slots, &d_probs, 0, 0, none);
+}

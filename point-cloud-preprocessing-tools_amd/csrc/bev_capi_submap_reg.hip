@@ -18,15 +18,14 @@ using namespace bevk;
 using namespace bevh;
 using bevsubreg::Call, bevsubreg::Group, bevsubreg::Options, bevsubreg::Plan;
 
-namespace {
-
+/* ---- what the verification calls run as well (bev_reg_host.h) ---- */
 /* bytes of a launch group's maps (BEV_SUBMAP_REG_GROUP): 8 GiB, of the order of the voxel clouds of a call on a thousand sweeps,
  * and hundreds of maps of full sweeps in one launch (a map is one workgroup of k_submap_target, a match one of k_submap_icp) */
 constexpr uint64_t kSubmapRegCap = (uint64_t)8 << 30;
-uint64_t group_cap(const bev_ctx *c) { return c->submap_reg_group ? (uint64_t)c->submap_reg_group : kSubmapRegCap; }
+uint64_t bevh::group_cap(const bev_ctx *c) { return c->submap_reg_group ? (uint64_t)c->submap_reg_group : kSubmapRegCap; }
 
 /* what the fine entries check behind their own arguments: BEV_OK, or what the entry returns */
-int submap_reg_check(const Call &call)
+int bevh::submap_reg_check(const Call &call)
 {
     const int n_frames = call.frames.size();
     BEVCK(check_submap_entries(n_frames, call.n_maps, call.map_offs, call.entry_frame, call.entry_pose));
@@ -37,12 +36,9 @@ int submap_reg_check(const Call &call)
     return BEV_OK;
 }
 
-/* the plan's tables in one block of tab, the device's on return: the slots (fine, top_union), the maps, the entries (64-byte
- * aligned), the caller's problems if it has any, the maps' first keys (union_voxel; else nullptr), their first union keys
- * (top_union; else nullptr), their first cells (grid_cap > 0; else nullptr) */
-struct PlanDev {
-    void *slots, *maps, *entries, *probs, *key0, *u0, *cell0;
-};
+namespace {
+
+/* the plan's tables in one block of tab, the device's on return (PlanDev, bev_reg_host.h) */
 int plan_up(bev_ctx *c, UploadTable &tab, const Plan &plan, const Options &opt, PlanDev &d, const void *probs = nullptr,
             size_t prob_bytes = 0)
 {
@@ -116,15 +112,8 @@ void submap_sort_keys(bev_ctx *c, const Group &g, const SubmapVoxWork &v)
 /* A fine call's workspace in fine_buf, and its tables: the voxel clouds of the slots (no grids: no frame is a target), the scratch
  * of a voxel launch and of an ICP launch, the entries' first indices, the maps of one launch group.  Of the group's arrays, a call
  * with matches (icp: every one but the cloud call) has t.pts and the search grids t.sorted, t.hdr, t.cell_off; the union grid
- * (vox) has v.keys, v.vstart and thins into t.pts; who concatenates into an array of its own (vox, the cloud call): v.moved, v.vh */
-struct SubmapFine {
-    FineWork w{};
-    SubmapRegWork t{};
-    SubmapVoxWork v{};
-    uint32_t *ent_start = nullptr;
-    PlanDev d{};
-    SubmapGridWork gw{}; /* grid_cap > 0: the wide grids (gw.off is t.cell_off, gw.hdr t.hdr, gw.sorted t.sorted) */
-};
+ * (vox) has v.keys, v.vstart and thins into t.pts; who concatenates into an array of its own (vox, the cloud call): v.moved, v.vh
+ * (SubmapFine: bev_reg_host.h) */
 int submap_fine_work(bev_ctx *c, const Plan &plan, const Options &opt, SubmapFine &s)
 {
     /* wide: the concatenation is k_submap_vox_move's (v.moved, v.vh) where the maps are not thinned, and t.pts points at it */
@@ -154,9 +143,11 @@ int submap_fine_work(bev_ctx *c, const Plan &plan, const Options &opt, SubmapFin
     return BEV_OK;
 }
 
+} // namespace
+
 /* the workspace, the tables and the voxel clouds of the plan's slots: frame f = frames.n[f] records at frames.off[f] of d_clouds */
-int submap_fine_begin(bev_ctx *c, const Plan &plan, const Options &opt, const bev_point_t *d_clouds, float leaf, SubmapFine &s,
-                      const std::vector<FineProblem> &probs = {})
+int bevh::submap_fine_begin(bev_ctx *c, const Plan &plan, const Options &opt, const bev_point_t *d_clouds, float leaf, SubmapFine &s,
+                            const std::vector<FineProblem> &probs)
 {
     BEVCK(submap_fine_work(c, plan, opt, s));
     BEVCK(plan_up(c, c->reg.fine_tab, plan, opt, s.d, probs.data(), probs.size() * sizeof(FineProblem)));
@@ -167,7 +158,7 @@ int submap_fine_begin(bev_ctx *c, const Plan &plan, const Options &opt, const be
 
 /* a group's targets in s.t.pts (the plain cloud call: in s.v.moved): the entries' voxel clouds moved and concatenated, with their
  * search grids where the call has matches; map_leaf > 0: thinned by the voxel grid over the union */
-int submap_fine_targets(bev_ctx *c, const Group &g, const Options &opt, const SubmapFine &s, float map_leaf)
+int bevh::submap_fine_targets(bev_ctx *c, const Group &g, const Options &opt, const SubmapFine &s, float map_leaf)
 {
     const int gm = (int)g.n_maps;
     const PlanDev &d = s.d;
@@ -196,6 +187,8 @@ int submap_fine_targets(bev_ctx *c, const Group &g, const Options &opt, const Su
     }
     return wide ? submap_grid_build(c, g, opt.grid_cap, d.maps, s.v.vh, pts, s.gw) : BEV_OK;
 }
+
+namespace {
 
 /* the registration call on the context's stream, behind the entries' checks and begin_call.  map_leaf > 0: the maps are thinned
  * (DESIGN.md §6l); 0: §6k's launches and workspace */

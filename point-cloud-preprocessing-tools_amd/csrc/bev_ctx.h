@@ -1,8 +1,8 @@
 /*
- * bev_ctx.h — the context behind bev_ctx_t and what the five files of the C ABI share: bev_capi.hip (the context, the BEV
+ * bev_ctx.h — the context behind bev_ctx_t and what the six files of the C ABI share: bev_capi.hip (the context, the BEV
  * pipeline and the single-cloud entry points), bev_capi_packed.hip (the batched calls over packed frames), bev_capi_reg.hip
  * (the registration entry points, frame against frame), bev_capi_submap_reg.hip (frames against submaps; what only these
- * two share: bev_reg_host.h) and bev_capi_place.hip (place retrieval) — among it the prologue of every call outside the fused pipeline (begin_call) and the bound
+ * two and bev_capi_verify.hip share: bev_reg_host.h), bev_capi_place.hip (place retrieval) and bev_capi_verify.hip (verification of registered matches) — among it the prologue of every call outside the fused pipeline (begin_call) and the bound
  * on a cloud's points (cloud_cap).  Private, like bev_internal.h.  Named namespace: struct bev_ctx is one type in all of them.
  */
 #ifndef BEV_CTX_H
@@ -113,7 +113,7 @@ struct Downloader {
     }
 };
 
-/* ---- what the batched entry points keep between calls (defined in bev_capi.hip; used by all five files) ---- */
+/* ---- what the batched entry points keep between calls (defined in bev_capi.hip; used by all six files) ---- */
 /* a device buffer that grows when a call needs more */
 struct DevBuf {
     void *p = nullptr;
@@ -150,6 +150,11 @@ struct RegState {
     /* scan-to-map fine ICP (bev_submap_registration_device_resident & co.) works in fine_buf and sends its plan
      * up fine_tab; sub_res: the results of bev_submap_registration_batch on the device */
     DevBuf sub_res;
+    /* verification of registered matches (bev_capi_verify.hip) voxelises and builds its targets in fine_buf like
+     * the fine calls; verify_buf: the moved queries and their grids of a launch group; verify_tab: the matches' table; verify_io:
+     * what the host-buffer forms keep on the device (the transforms going in, the records coming out) */
+    DevBuf verify_buf, verify_io;
+    UploadTable verify_tab;
     /* Recorded on the context's stream behind the last batched registration call (front end, coarse, fine): the next BEV
      * call's stage streams wait for it.  One event serves all three: they record on the same stream, so the latest record
      * covers the earlier ones. */

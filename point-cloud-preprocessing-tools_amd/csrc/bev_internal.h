@@ -262,6 +262,8 @@ enum KernelId {
     K_PLACE_FINISH,  /* ... the planes into descriptor bytes, unit columns and column masks */
     K_PLACE_PAIRS,   /* ... the best shift of every (query, candidate) pair */
     K_PLACE_TOPK,    /* ... the best top_k candidates of every query */
+    K_VERIFY_MOVE,   /* verification of registered matches (bev_verify.h): the moved query of every match and its search grid */
+    K_VERIFY_COUNT,  /* ... the inlier counts of both directions */
     K_COUNT
 };
 const char *kernel_name(int id);
@@ -680,6 +682,37 @@ void launch_fine_icp_wide(const FineProblem *probs, int n, const FineWork &w, ui
                           const int32_t *best, const bev_icp_params_t &prm, bev_icp_result_t *results, hipStream_t st);
 void launch_icp_wide(const float *pn, size_t stride, const uint32_t *counts, const IcpProblem *probs, int n, const IcpWork &w,
                      uint64_t off_words, const bev_icp_params_t &prm, bev_icp_result_t *results, hipStream_t st);
+
+/* ---- verification of registered matches: two-way inlier counts (bev_verify.h) ---- */
+constexpr int kVerifyProblemsPerLaunch = 1024; /* matches of one launch group (= moved queries and their grids in scratch) */
+constexpr uint32_t kVerifySlice = 256;         /* points of one k_verify_count workgroup (BEV_VERIFY_SLICE; no result depends on it) */
+/* a match of a launch group: its query's slot, its target's grid (the index of its header and of its kFineCells + 1 offsets) and
+ * first searchable point behind VerifyTarget's arrays, its record in the call's d_results and d_verify */
+struct VerifyProblem {
+    uint32_t src_slot, tgt_grid, result, _pad;
+    uint64_t tgt_pt0;
+};
+/* the targets' grids as their builders left them: k_fine_grid's per slot (pair), k_submap_target's or k_submap_vox_finish's per
+ * map of a launch group (scan-to-map) */
+struct VerifyTarget {
+    const IcpGridHdr *hdr;
+    const uint32_t *cell_off;
+    const float4 *sorted;
+};
+/* per match of a launch group: the moved query, its searchable points by cell, its grid's offsets and header */
+struct VerifyWork {
+    float4 *moved;     /* [kVerifyProblemsPerLaunch][Pn] */
+    float4 *qsorted;   /* [kVerifyProblemsPerLaunch][Pn] */
+    uint32_t *qoff;    /* [kVerifyProblemsPerLaunch][kFineCells + 1] */
+    IcpGridHdr *qhdr;  /* [kVerifyProblemsPerLaunch] */
+    size_t Pn;         /* FineWork's */
+};
+/* n <= kVerifyProblemsPerLaunch matches; w: the voxel clouds (vox, vox_n, Pn); results: the call's d_results (T is read) */
+void launch_verify_move(const VerifyProblem *probs, int n, const FineWork &w, const bev_icp_result_t *results, const VerifyTarget &t,
+                        const VerifyWork &v, bev_verify_result_t *out, hipStream_t st);
+/* both directions of the same matches; slices: workgroups of `slice` points over the largest cloud of either side */
+void launch_verify_count(const VerifyProblem *probs, int n, uint32_t slices, const FineWork &w, const VerifyTarget &t,
+                         const VerifyWork &v, const bev_verify_params_t &prm, uint32_t slice, bev_verify_result_t *out, hipStream_t st);
 
 /* opt in to > 64 KiB of dynamic LDS for the kernels that need it */
 hipError_t configure_kernels(const Geometry &g);

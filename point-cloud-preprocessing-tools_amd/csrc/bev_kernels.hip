@@ -54,6 +54,7 @@
 #include "bev_submap_grid.h"
 #include "bev_wide_icp.h"
 #include "bev_place.h"
+#include "bev_verify.h"
 
 using namespace bevx;
 
@@ -76,6 +77,7 @@ static const char *const kNames[K_COUNT] = {
     "k_submap_icp_wide", "k_submap_coarse_icp_wide",
     "k_pairgrid_desc", "k_fine_icp_wide", "k_icp_wide",
     "k_place_splat", "k_place_finish", "k_place_pairs", "k_place_topk",
+    "k_verify_move", "k_verify_count",
 };
 const char *kernel_name(int id) { return (id >= 0 && id < K_COUNT) ? kNames[id] : "?"; }
 

@@ -1,6 +1,7 @@
 /*
- * bev_reg_host.h — what the two registration files of the C ABI share over bev_ctx.h: bev_capi_reg.hip (the front end and the
- * pair stages) and bev_capi_submap_reg.hip (scan-to-map).  Argument checks, the frame table of a packed or
+ * bev_reg_host.h — what the registration files of the C ABI share over bev_ctx.h: bev_capi_reg.hip (the front end and the
+ * pair stages), bev_capi_submap_reg.hip (scan-to-map) and bev_capi_verify.hip (verification of their results,
+ * which runs their voxel, grid and target steps as they are; §6aa).  Argument checks, the frame table of a packed or
  * d_ordered buffer, upload tables laid out by carve, the host driver of a search grid's build and the reader of the two grid
  * hooks (§6u), and the fine stage's two steps that scan-to-map runs as they are.
  * Declarations and short inline functions, no state (RegState: bev_ctx.h).  Private.
@@ -10,6 +11,7 @@
 
 #include <cmath>
 #include <cstring>
+#include <vector>
 
 #include "bev_ctx.h"
 #include "bev_submap_reg_plan.h"
@@ -95,6 +97,35 @@ int grid_record_read(bev_ctx *c, const GridRecord &r, int first, int n, uint32_t
 int fine_voxel(bev_ctx *c, const bev_point_t *d_pts, const FineSlot *d_slots, int U, const FineWork &w, float leaf);
 /* host records -> c->reg.fine_in (grown on demand); offs[i]: where cloud i went */
 int fine_upload(bev_ctx *c, const bev_point_t *const *clouds, const uint32_t *n, int k, size_t *offs);
+/* the fine stage's workspace for U slots of at most Pn records and no problem, under the default grids (fine_setup without an
+ * ICP launch's scratch); the slot table goes up the context's stream.  What the verification calls voxelise and search in */
+int fine_slots_setup(bev_ctx *c, size_t U, size_t Pn, const std::vector<FineSlot> &slots, FineWork &w, const FineSlot **d_slots);
+
+/* ---- of the scan-to-map fine path (bev_capi_submap_reg.hip) ---- */
+/* bytes of a launch group's maps (BEV_SUBMAP_REG_GROUP) */
+uint64_t group_cap(const bev_ctx *c);
+/* what the fine entries check behind their own arguments: BEV_OK, or what the entry returns */
+int submap_reg_check(const bevsubreg::Call &call);
+/* the plan's tables in one block of tab, the device's on return: the slots (fine, top_union), the maps, the entries (64-byte
+ * aligned), the caller's problems if it has any, the maps' first keys (union_voxel; else nullptr), their first union keys
+ * (top_union; else nullptr), their first cells (grid_cap > 0; else nullptr) */
+struct PlanDev {
+    void *slots, *maps, *entries, *probs, *key0, *u0, *cell0;
+};
+/* a fine call's workspace in fine_buf and its tables (submap_fine_work, bev_capi_submap_reg.hip) */
+struct SubmapFine {
+    FineWork w{};
+    SubmapRegWork t{};
+    SubmapVoxWork v{};
+    uint32_t *ent_start = nullptr;
+    PlanDev d{};
+    SubmapGridWork gw{}; /* grid_cap > 0: the wide grids (gw.off is t.cell_off, gw.hdr t.hdr, gw.sorted t.sorted) */
+};
+/* the workspace, the tables and the voxel clouds of the plan's slots: frame f = frames.n[f] records at frames.off[f] of d_clouds */
+int submap_fine_begin(bev_ctx *c, const bevsubreg::Plan &plan, const bevsubreg::Options &opt, const bev_point_t *d_clouds, float leaf,
+                      SubmapFine &s, const std::vector<FineProblem> &probs = {});
+/* a group's targets in s.t.pts with their search grids where the call has matches; map_leaf > 0: thinned over the union */
+int submap_fine_targets(bev_ctx *c, const bevsubreg::Group &g, const bevsubreg::Options &opt, const SubmapFine &s, float map_leaf);
 
 } // namespace bevh
 #endif

@@ -46,7 +46,7 @@ void DeviceBuffer::download(void *dst, size_t bytes) const { hip_check(hipMemcpy
 
 ChunkResult runChunk(bev_ctx_t *ctx, const std::vector<Cloud> &clouds, const std::vector<uint64_t> &offs, const Chunk &chunk,
                      const std::vector<float> *entry_pose, float map_leaf, bool top_part, const bev_icp_params_t &fine_prm,
-                     float pn_leaf, bool top_union)
+                     float pn_leaf, bool top_union, const bev_verify_params_t *verify)
 {
     using clk = std::chrono::steady_clock;
     const int F = (int)clouds.size(), n = (int)chunk.matches.size();
@@ -102,6 +102,17 @@ ChunkResult runChunk(bev_ctx_t *ctx, const std::vector<Cloud> &clouds, const std
     r.ms_fine = std::chrono::duration<double, std::milli>(t2 - t1).count();
     r.fine = downloaded<bev_icp_result_t>(fine, n);
     if (top_part) r.coarse = downloaded<bev_icp_result_t>(coarse, 2 * (size_t)n), r.best = downloaded<int32_t>(best, n);
+    if (verify) { /* the fine results stay where they are: only their transforms are read */
+        DeviceBuffer counts(std::max<size_t>((size_t)n, 1) * sizeof(bev_verify_result_t));
+        if (entry_pose)
+            BEV_CALL(bev_submap_verify_registration_device_resident, F, pts.as<bev_point_t>(), offs.data(), n, map_offs, entry_frame,
+                     entry_pose->data(), map_leaf, n, cm, fine.as<bev_icp_result_t>(), verify, counts.as<bev_verify_result_t>());
+        else
+            BEV_CALL(bev_verify_registration_device_resident, F, pts.as<bev_point_t>(), offs.data(), n, cm, fine.as<bev_icp_result_t>(),
+                     verify, counts.as<bev_verify_result_t>());
+        BEV_CALL(bev_synchronize);
+        r.verify = downloaded<bev_verify_result_t>(counts, n);
+    }
     return r;
 }
 
@@ -133,7 +144,8 @@ void Tally::print(std::ostream &out, bool coarse_line, bool fine_is_both) const
 }
 
 int registerChunk(const std::vector<std::string> &paths, const Chunk &chunk, const std::vector<float> *entry_pose, float map_leaf,
-                  bool top_part, const bev_icp_params_t &fine_prm, Tally &tally, float pn_leaf, bool top_union)
+                  bool top_part, const bev_icp_params_t &fine_prm, Tally &tally, float pn_leaf, bool top_union,
+                  const bev_verify_params_t *verify, ChunkResult *result)
 {
     std::vector<Cloud> clouds(paths.size());
     std::vector<uint64_t> offs(paths.size() + 1, 0);
@@ -147,7 +159,9 @@ int registerChunk(const std::vector<std::string> &paths, const Chunk &chunk, con
     bev_ctx_t *ctx = bevhost_context();
     if (!ctx) return 2;
     try {
-        tally.add(chunk, runChunk(ctx, clouds, offs, chunk, entry_pose, map_leaf, top_part, fine_prm, pn_leaf, top_union));
+        ChunkResult r = runChunk(ctx, clouds, offs, chunk, entry_pose, map_leaf, top_part, fine_prm, pn_leaf, top_union, verify);
+        tally.add(chunk, r);
+        if (result) *result = std::move(r);
     } catch (const std::exception &e) {
         std::cerr << e.what() << "\n";
         return 2;

@@ -46,11 +46,26 @@
  * not depend on it.  Anything else: exit 1 with "BEV_SUBMAP_SEARCH_GRID '<text>': expected <fine>[,<coarse>], integers 0 ...
  * 1024" and the usage line, before any GPU work.
  *
+ * batch_verified_registration <match_result_text_file> <keyframes_root_dir> <half_window> [<chunk> [<map_leaf>]] (a third build,
+ * BEV_VERIFY_TOOL 1) is batch_submap_registration, stdout and reports included, with the third step of "retrieve,
+ * register, verify" behind every chunk: bev_submap_verify_registration_device_resident on the chunk's fine results, at leaf 0.2
+ * and one threshold.  Two values from the environment: BEV_VERIFY_THRESHOLD (metres, default 0.5) and BEV_VERIFY_MIN_OVERLAP
+ * (default 0.3), finite and > 0, the overlap at most 1; anything else: exit 1 with the usage line before any GPU work.  Both
+ * defaults are PLACEHOLDERS that nobody has tuned on real sweeps.  overlap = query_within / n_query, and at half_window 0 (a
+ * frame against a frame) the smaller of that and target_within / n_target (a map is larger than a sweep by construction, so its
+ * side says nothing); 0 where a count it divides by is 0.  A match is accepted iff converged && fitness <= 1.5 && overlap >=
+ * min_overlap.  Into the working directory go verification_detail.csv (a header, then one row per input match in input order:
+ * query, match, fitness, converged, n_query, n_target, query_within, target_within, overlap, accepted, the 12 entries of T) and
+ * verified_match_result.txt (one line "query_idx match_idx yaw" per accepted match, yaw = atan2(T[4], T[0]) in degrees: a match
+ * list that loadMatchResults reads back).
+ *
  * The chunks, the chain and the bookkeeping are the four registration tools' own (RegistrationChunks.h, RegistrationChain.h;
  * DESIGN.md §6p), the entries' matrices every submap tool's (submapwin::appendEntryPose): this file is the command line, which
  * file an index names, and the poses.
  */
+#include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <fstream>
 #include <iostream>
@@ -65,13 +80,52 @@
 #ifndef BEV_SUBMAP_TOP_PART
 #define BEV_SUBMAP_TOP_PART 0
 #endif
+#ifndef BEV_VERIFY_TOOL
+#define BEV_VERIFY_TOOL 0
+#endif
 
 namespace {
 
-constexpr bool kTopPart = BEV_SUBMAP_TOP_PART;
-const char *const kTool = kTopPart ? "batch_submap_top_part_registration" : "batch_submap_registration";
+constexpr bool kTopPart = BEV_SUBMAP_TOP_PART, kVerify = BEV_VERIFY_TOOL;
+static_assert(!(kTopPart && kVerify), "the verified tool is the whole tool's chain");
+const char *const kTool = kVerify ? "batch_verified_registration" : kTopPart ? "batch_submap_top_part_registration" : "batch_submap_registration";
 
-void usage() { std::cerr << "Usage: " << kTool << " <match_result_text_file> <keyframes_root_dir> <half_window> [<chunk> [<map_leaf>]]\n"; }
+void usage()
+{
+    std::cerr << "Usage: " << kTool << " <match_result_text_file> <keyframes_root_dir> <half_window> [<chunk> [<map_leaf>]]\n";
+    if (kVerify)
+        std::cerr << "  environment: BEV_VERIFY_THRESHOLD=<metres> (default 0.5), BEV_VERIFY_MIN_OVERLAP=<share> (default 0.3): finite, > 0,\n"
+                     "  the overlap <= 1.  Both defaults are placeholders that nobody has tuned on real sweeps.\n";
+}
+
+/* BEV_VERIFY_THRESHOLD, BEV_VERIFY_MIN_OVERLAP: unset or empty: the default; a finite number in (0, most]; else false */
+bool verify_env(const char *name, float most, float *out)
+{
+    const char *s = std::getenv(name);
+    if (!s || !*s) return true;
+    char *end = nullptr;
+    const float v = std::strtof(s, &end);
+    if (end == s || *end != '\0' || !std::isfinite(v) || !(v > 0.0f) || v > most) return false;
+    *out = v;
+    return true;
+}
+
+/* a row of verification_detail.csv, and the match's line of verified_match_result.txt where it is accepted */
+void verified_row(std::FILE *csv, std::FILE *list, const MatchResult &mt, const bev_icp_result_t &r, const bev_verify_result_t &v,
+                  bool pair, float min_overlap)
+{
+    const double fwd = v.n_query && v.query_within[0] ? (double)v.query_within[0] / (double)v.n_query : 0.0;
+    const double rev = v.n_target && v.target_within[0] ? (double)v.target_within[0] / (double)v.n_target : 0.0;
+    const double overlap = pair ? std::min(fwd, rev) : fwd;
+    const bool accepted = r.converged && r.fitness <= 1.5 && overlap >= (double)min_overlap;
+    std::fprintf(csv, "%d,%d,%.17g,%d,%u,%u,%u,%u,%.17g,%d", mt.query_idx, mt.match_idx, r.fitness, r.converged, v.n_query, v.n_target,
+                 v.query_within[0], v.target_within[0], overlap, accepted ? 1 : 0);
+    for (int k = 0; k < 12; ++k) std::fprintf(csv, ",%.9g", (double)r.T[k]);
+    std::fprintf(csv, "\n");
+    if (accepted)
+        std::fprintf(list, "%d %d %.9g\n", mt.query_idx, mt.match_idx,
+                     (double)(float)(std::atan2((double)r.T[4], (double)r.T[0]) * 180.0 / 3.14159265358979323846));
+}
 
 /* a finite number >= 0 and nothing else */
 bool parse_map_leaf(const char *s, float *out)
@@ -92,7 +146,12 @@ int main(int argc, char **argv)
         usage();
         return 1;
     }
-    float map_leaf = 0.0f, pn_leaf = 0.0f;
+    float map_leaf = 0.0f, pn_leaf = 0.0f, threshold = 0.5f, min_overlap = 0.3f;
+    if (kVerify && !(verify_env("BEV_VERIFY_THRESHOLD", INFINITY, &threshold) && verify_env("BEV_VERIFY_MIN_OVERLAP", 1.0f, &min_overlap))) {
+        std::cerr << "BEV_VERIFY_THRESHOLD / BEV_VERIFY_MIN_OVERLAP: expected finite numbers > 0, the overlap at most 1\n";
+        usage();
+        return 1;
+    }
     if (const char *env = kTopPart ? std::getenv("BEV_SUBMAP_PN_LEAF") : nullptr)
         if (*env && !parse_map_leaf(env, &pn_leaf)) {
             std::cerr << "BEV_SUBMAP_PN_LEAF '" << env << "': expected a finite number >= 0\n";
@@ -164,6 +223,19 @@ int main(int argc, char **argv)
         }
     sensor_params_ = getSensorParams(parseSensorType("HDL_64E")); /* (the context follows a sensor; packed clouds read none) */
     const bev_icp_params_t prm = kTopPart ? bev_icp_fine_defaults() : bev_icp_whole_defaults();
+    bev_verify_params_t vprm{};
+    vprm.leaf = 0.2f;
+    vprm.n_thresholds = 1;
+    vprm.threshold[0] = threshold;
+    std::FILE *csv = kVerify ? std::fopen("./verification_detail.csv", "w") : nullptr;
+    std::FILE *list = kVerify ? std::fopen("./verified_match_result.txt", "w") : nullptr;
+    if (kVerify && (!csv || !list)) {
+        std::cerr << "verification_detail.csv / verified_match_result.txt: can not be written\n";
+        return 1;
+    }
+    if (kVerify)
+        std::fprintf(csv, "query,match,fitness,converged,n_query,n_target,query_within,target_within,overlap,accepted,"
+                          "t00,t01,t02,t03,t10,t11,t12,t13,t20,t21,t22,t23\n");
     regchain::Tally tally(kTopPart ? &report : &submap_report,
                           kTopPart ? regchain::ReportAgainst::ChosenCoarse : regchain::ReportAgainst::YawGuess);
     if (search_grid[0] || search_grid[1]) {
@@ -179,11 +251,16 @@ int main(int argc, char **argv)
         for (size_t k = 0; k < chunk.matches.size(); ++k)
             for (uint64_t e = chunk.map_offs[k]; e < chunk.map_offs[k + 1]; ++e)
                 submapwin::appendEntryPose(pose, matches[m0 + k].match_idx, chunk.files[chunk.entry_frame[e]], entry_pose);
-        if (const int rc = regchain::registerChunk(paths, chunk, &entry_pose, map_leaf, kTopPart, prm, tally, pn_leaf, top_union))
+        regchain::ChunkResult res;
+        if (const int rc = regchain::registerChunk(paths, chunk, &entry_pose, map_leaf, kTopPart, prm, tally, pn_leaf, top_union,
+                                                   kVerify ? &vprm : nullptr, kVerify ? &res : nullptr))
             return rc;
+        for (size_t k = 0; kVerify && k < chunk.matches.size(); ++k)
+            verified_row(csv, list, matches[m0 + k], res.fine[k], res.verify[k], half == 0, min_overlap);
         m0 = chunk.m1;
     }
     /* batch_submap_registration's fine line is the whole visit of the device, uploads included */
     tally.print(std::cout, kTopPart, !kTopPart);
+    if (kVerify && (std::fclose(csv) != 0 || std::fclose(list) != 0)) return 1;
     return 0;
 }
