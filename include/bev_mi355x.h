@@ -1131,6 +1131,83 @@ int bev_verify_registration_batch(bev_ctx_t *ctx, int n_frames, const bev_point_
                                   int n_matches, const bev_match_t *h_matches, const bev_icp_result_t *results,
                                   const bev_verify_params_t *params, bev_verify_result_t *verify);
 
+/* ---- a translation guess for retrieved pairs: height-grid offset search ---------------------------------
+ * Place retrieval hands a pair over on a yaw alone.  This stage adds the translation in the plane: both clouds become small
+ * Cartesian height grids, the query's is rotated by the yaw hypotheses of the hit, and an exhaustive search over whole-cell
+ * shifts picks the shift with the highest correlation.  The output is the table of initial transforms that the fine calls
+ * already take as d_coarse / d_best.  The contract, whose arithmetic is csrc/bev_align_exact.h's on the host and on the
+ * device alike:
+ *   grid      G x G bytes, byte [iy * G + ix].  A point contributes iff x * x + y * y > 0 in float (not the origin's no-return
+ *             records, NaN), label != 0 where skip_label0 is set, and fx = floorf(x / cell), fy = floorf(y / cell) both satisfy
+ *             -(float)(G / 2) <= f < (float)(G / 2), compared in float before any conversion; then ix = (int)fx + G / 2, iy
+ *             likewise.  Its value is §6z's: min(127, max(0, (int)((z + lidar_to_ground) * 4))); a cell holds the maximum;
+ *   candidate of a frame: from its raw coordinates; of a map: every point moved by its entry's matrix (the moved x, y, z);
+ *   hypotheses for flip in {0, 1} and k in -K ... K: theta = angle_guess + (float)k * yaw_step in float, T = the registration
+ *             tools' initial guess of (theta, flip) (a yaw of theta, or theta + 180, degrees about z); the query's grid under
+ *             the hypothesis is the grid of its points moved by rows 0 ... 2 of T;
+ *   score     of a shift (dx, dy) in [-S, S]^2: the sum over ix, iy of q[iy][ix] * c[iy + dy][ix + dx], a candidate byte
+ *             outside the grid being 0; a 32-bit unsigned integer;
+ *   orders    among the shifts of a hypothesis: higher score, then smaller dx^2 + dy^2, then smaller dy, then smaller dx; among
+ *             the k of a flip: higher best score, then smaller |k|, then smaller k; best = 0 iff the best score of flip 0 >=
+ *             that of flip 1;
+ *   offset    per axis, only where both neighbours of the winning shift lie inside the window: in double, den = S- - 2 S0 + S+,
+ *             off = den < 0 ? 0.5 (S- - S+) / den : 0, clamped to [-0.5, 0.5];
+ *   result    [2m + flip]: T of the winning hypothesis with T[3] = (float)(((double)dx + off_x) * (double)cell) and T[7] from dy:
+ *             p_candidate ~ T p_query; fitness = 1 - S / sqrt((double)Eq * (double)Ec), Eq and Ec the grids' sums of squares,
+ *             2.0 where S == 0; converged = S > 0; iterations 0; state BEV_ICP_NOT_CONVERGED; _pad 0;
+ *   no match  a hit with match_idx < 0 reads an empty candidate: S = 0, Ec = 0, shift (0, 0), k = 0.
+ * Everything but the last few double operations is integer work or a maximum: no output depends on the launch shape, on a
+ * group's size or on an atomic's order. */
+typedef struct bev_align_params {   /* 24 bytes */
+    int32_t grid;        /* G: even, 16 ... 128 */
+    float cell;          /* finite, > 0: metres */
+    int32_t max_shift;   /* S: 1 ... 16, and 2 S <= G / 2 */
+    int32_t yaw_steps;   /* K: 0 ... 3 */
+    float yaw_step;      /* finite, >= 0: degrees */
+    int32_t skip_label0; /* 0 or 1: as for bev_float_bev */
+} bev_align_params_t;
+typedef struct bev_align_detail {   /* 36 bytes */
+    int32_t dx, dy, k, flip;        /* the winning shift and hypothesis of (hit, flip) */
+    uint32_t score, eq, ec;         /* its score and the two grids' sums of squares */
+    float off_x, off_y;             /* the sub-cell offsets, in cells */
+} bev_align_detail_t;
+/* Host only.  The defaults: G 128, cell 0.5f, S 16, K 1, yaw_step 2.0f, skip_label0 1.  The bytes of a grid, G * G; 0 for
+ * parameters outside the admitted values (params NULL: the defaults). */
+bev_align_params_t bev_align_defaults(void);
+size_t bev_align_grid_bytes(const bev_align_params_t *params);
+/* The candidate grids of frames (n_maps == 0, the three map arrays NULL) or of maps over packed frames in device memory;
+ * asynchronous, on the context's stream.  Arguments, ordering and statuses are bev_place_descriptor_device_resident's.
+ * d_grids  : bev_align_grid_bytes per grid, one after the other.
+ * d_energy : one uint32 per grid: its sum of squares.  Both are required where there is a grid to make.
+ * Workspace: a plane of 4 bytes per cell and grid, and the tables of the submap calls.  Freed by bev_destroy. */
+int bev_align_grid_device_resident(bev_ctx_t *ctx, int n_frames, const bev_point_t *d_clouds, const uint64_t *h_offsets, int n_maps,
+                                   const uint64_t *h_map_offsets, const int32_t *h_entry_frame, const float *h_entry_pose,
+                                   const bev_align_params_t *params, uint8_t *d_grids, uint32_t *d_energy);
+/* The translation guesses of a hit list; asynchronous, on the context's stream, ordered like the place calls.
+ * d_clouds, h_offsets : the queries' packed frames, as above.
+ * n_db, d_grids, d_energy : the candidates, as the call above left them under the SAME params.
+ * h_hits    : n_hits HOST records; query_idx in 0 ... n_frames - 1; match_idx in 0 ... n_db - 1, or negative (a
+ *             bev_place_hit_t that found nothing).
+ * d_results : 2 * n_hits records (device); d_best: n_hits int32 (device).  Both go into bev_fine_registration_device_resident
+ *             and bev_submap_voxel_registration_device_resident as d_coarse and d_best with no synchronisation in between.
+ * d_detail  : 2 * n_hits records (device), or NULL.  Every byte of every record of all three is written.
+ * Status    : BEV_ERR_INVALID_ARG for a NULL context, parameters outside the admitted values, bad offsets, negative counts,
+ *             an index out of range, NULL h_hits, d_results or d_best with n_hits > 0, NULL d_grids or d_energy where a hit
+ *             names a candidate, NULL d_clouds where a hit's query has records.  Nothing is launched then.  n_hits == 0: BEV_OK.
+ * Workspace : 32 bytes per hypothesis of a launch group of hits (BEV_ALIGN_GROUP=<hits> sets the group, the results do not
+ *             depend on it) and 24 bytes per hit.  Freed by bev_destroy. */
+int bev_align_hits_device_resident(bev_ctx_t *ctx, int n_frames, const bev_point_t *d_clouds, const uint64_t *h_offsets, int n_db,
+                                   const uint8_t *d_grids, const uint32_t *d_energy, int n_hits, const bev_match_t *h_hits,
+                                   const bev_align_params_t *params, bev_icp_result_t *d_results, int32_t *d_best,
+                                   bev_align_detail_t *d_detail);
+/* Both calls through HOST buffers, synchronous: the frames are the queries; the candidates are the maps (n_maps of them), or —
+ * all three map arrays NULL and n_maps == 0 — the frames themselves.  results: 2 * n_hits, best: n_hits, detail: 2 * n_hits
+ * HOST records or NULL. */
+int bev_align_batch(bev_ctx_t *ctx, int n_frames, const bev_point_t *const *clouds, const uint32_t *n_pts, int n_maps,
+                    const uint64_t *h_map_offsets, const int32_t *h_entry_frame, const float *h_entry_pose, int n_hits,
+                    const bev_match_t *h_hits, const bev_align_params_t *params, bev_icp_result_t *results, int32_t *best,
+                    bev_align_detail_t *detail);
+
 int bev_abi_version(void);
 
 #ifdef __cplusplus

@@ -110,6 +110,8 @@ ABI_SYMBOLS = [
     "bev_place_descriptor_device_resident", "bev_place_match_device_resident", "bev_place_retrieval_batch",
     "bev_verify_defaults", "bev_verify_clouds", "bev_verify_registration_device_resident",
     "bev_submap_verify_registration_device_resident", "bev_verify_registration_batch",
+    "bev_align_defaults", "bev_align_grid_bytes", "bev_align_grid_device_resident", "bev_align_hits_device_resident",
+    "bev_align_batch",
 ]
 
 # bev_debug_exact_eval (include/bev_mi355x.h, BEV_EVAL_* in id order): name -> (input kinds f / u / d, output kind, params)
@@ -183,6 +185,22 @@ def verify_params(thresholds=(0.1, 0.2, 0.5, 1.0), leaf=0.2) -> VerifyParams:
     first 8 go into the record and n_thresholds says how many were given, which the calls refuse."""
     t = [float(v) for v in thresholds]
     return VerifyParams(leaf, len(t), (C.c_float * 8)(*t[:8]))
+
+
+# translation guess of retrieved pairs (include/bev_mi355x.h, DESIGN.md §6ab): bev_align_detail_t
+ALIGN_DETAIL_DTYPE = np.dtype([("dx", "<i4"), ("dy", "<i4"), ("k", "<i4"), ("flip", "<i4"), ("score", "<u4"), ("eq", "<u4"),
+                               ("ec", "<u4"), ("off_x", "<f4"), ("off_y", "<f4")])
+
+
+class AlignParams(C.Structure):
+    """bev_align_params_t"""
+    _fields_ = [("grid", C.c_int32), ("cell", C.c_float), ("max_shift", C.c_int32), ("yaw_steps", C.c_int32),
+                ("yaw_step", C.c_float), ("skip_label0", C.c_int32)]
+
+
+def align_params(grid=128, cell=0.5, max_shift=16, yaw_steps=1, yaw_step=2.0, skip_label0=True) -> AlignParams:
+    """The defaults of the translation guess (bev_align_defaults), any of them overridden."""
+    return AlignParams(grid, cell, max_shift, yaw_steps, yaw_step, 1 if skip_label0 else 0)
 
 
 def load_lib() -> C.CDLL:
@@ -355,6 +373,17 @@ def load_lib() -> C.CDLL:
                                                                        C.POINTER(VerifyParams), vp]
         lib.bev_verify_registration_batch.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(u32), i32, vp, vp,
                                                       C.POINTER(VerifyParams), vp]
+    if hasattr(lib, "bev_align_hits_device_resident"):
+        lib.bev_align_defaults.argtypes = []
+        lib.bev_align_defaults.restype = AlignParams
+        lib.bev_align_grid_bytes.argtypes = [C.POINTER(AlignParams)]
+        lib.bev_align_grid_bytes.restype = sz
+        lib.bev_align_grid_device_resident.argtypes = [vp, i32, vp, C.POINTER(C.c_uint64), i32, vp, vp, vp,
+                                                       C.POINTER(AlignParams), vp, vp]
+        lib.bev_align_hits_device_resident.argtypes = [vp, i32, vp, C.POINTER(C.c_uint64), i32, vp, vp, i32, vp,
+                                                       C.POINTER(AlignParams), vp, vp, vp]
+        lib.bev_align_batch.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(u32), i32, vp, vp, vp, i32, vp,
+                                        C.POINTER(AlignParams), vp, vp, vp]
     _lib = lib
     return lib
 
@@ -1079,6 +1108,57 @@ class BevContext:
             C.byref(prm), _ptr(out) if len(m) else None), "bev_verify_registration_batch")
         return out
 
+    # ---- a translation guess for retrieved pairs: height-grid offset search -----------------------------
+    def align_grid_device(self, n_frames, d_clouds, offsets, d_grids, d_energy, params: AlignParams | None = None,
+                          map_offsets=None, entry_frame=None, entry_pose=None):
+        """bev_align_grid_device_resident on device pointers: frames as for float_bev_device; without map_offsets one grid per
+        frame from its raw coordinates, else one per map (maps and entries as for submap_bev_device).  d_grids receives
+        align_grid_bytes(params) per grid, d_energy one uint32 per grid.  Asynchronous: synchronize() before the host reads."""
+        offsets, offs = _offsets(offsets, n_frames)
+        prm = params if params is not None else align_params()
+        n_maps, mo, ef, ep = 0, None, None, None
+        if map_offsets is not None:
+            n_maps, mo, ef, ep = self._submap_entries(map_offsets, entry_frame, entry_pose)
+        rc = self.lib.bev_align_grid_device_resident(self._h, n_frames, C.c_void_p(d_clouds or None), offs, n_maps, _ptr(mo),
+                                                     _ptr(ef), _ptr(ep), C.byref(prm), C.c_void_p(d_grids or None),
+                                                     C.c_void_p(d_energy or None))
+        self._check(rc, "bev_align_grid_device_resident")
+
+    def align_hits_device(self, n_frames, d_clouds, offsets, n_db, d_grids, d_energy, hits, d_results, d_best, d_detail=None,
+                          params: AlignParams | None = None):
+        """bev_align_hits_device_resident on device pointers: the queries' packed frames, the n_db candidate grids of
+        align_grid_device under the same params, hits MATCH_DTYPE records (PLACE_HIT_DTYPE records are cut to their first twelve
+        bytes).  d_results receives 2 * n_hits ICP_RESULT_DTYPE, d_best n_hits int32, d_detail (0 or None: not wanted)
+        2 * n_hits ALIGN_DETAIL_DTYPE.  Asynchronous: d_results / d_best go into the fine calls as d_coarse / d_best."""
+        offsets, offs = _offsets(offsets, n_frames)
+        m = _matches(hits)
+        prm = params if params is not None else align_params()
+        rc = self.lib.bev_align_hits_device_resident(self._h, n_frames, C.c_void_p(d_clouds or None), offs, n_db,
+                                                     C.c_void_p(d_grids or None), C.c_void_p(d_energy or None), len(m),
+                                                     _ptr(m) if len(m) else None, C.byref(prm), C.c_void_p(d_results or None),
+                                                     C.c_void_p(d_best or None), C.c_void_p(d_detail or None))
+        self._check(rc, "bev_align_hits_device_resident")
+
+    def align_batch(self, clouds, hits, params: AlignParams | None = None, map_offsets=None, entry_frame=None, entry_pose=None,
+                    want_detail=True):
+        """bev_align_batch on host clouds: the frames are the queries, the candidates the maps or, without map_offsets, the
+        frames themselves.  Returns (results (n, 2) ICP_RESULT_DTYPE, best (n,) int32, detail (n, 2) ALIGN_DETAIL_DTYPE or
+        None)."""
+        clouds, pts, npts = _host_clouds(clouds)
+        m = _matches(hits)
+        prm = params if params is not None else align_params()
+        n_maps, mo, ef, ep = 0, None, None, None
+        if map_offsets is not None:
+            n_maps, mo, ef, ep = self._submap_entries(map_offsets, entry_frame, entry_pose)
+        n = len(m)
+        res, best = np.zeros((n, 2), dtype=ICP_RESULT_DTYPE), np.zeros(n, dtype=np.int32)
+        det = np.zeros((n, 2), dtype=ALIGN_DETAIL_DTYPE) if want_detail else None
+        rc = self.lib.bev_align_batch(self._h, len(clouds), pts, npts, n_maps, _ptr(mo), _ptr(ef), _ptr(ep), n,
+                                      _ptr(m) if n else None, C.byref(prm), _ptr(res) if n else None,
+                                      _ptr(best) if n else None, _ptr(det) if n and want_detail else None)
+        self._check(rc, "bev_align_batch")
+        return res, best, det
+
     def set_layout_hint(self, layout: int):
         """LAYOUT_UNKNOWN (the library looks), LAYOUT_STRUCTURED, LAYOUT_FIRING_ORDER: include/bev_mi355x.h"""
         self._check(self.lib.bev_set_layout_hint(self._h, layout), "bev_set_layout_hint")
@@ -1191,6 +1271,22 @@ def project_batch_out_points(kind: int, n_frames: int, offsets) -> int:
     """Records the d_out of project_device must hold (host only); 0 for an unknown kind or decreasing offsets."""
     offsets, offs = _offsets(offsets, n_frames)
     return int(load_lib().bev_project_batch_out_points(kind, n_frames, offs))
+
+
+def _matches(hits) -> np.ndarray:
+    """MATCH_DTYPE records of match records, hit records (their first twelve bytes) or (query_idx, match_idx, angle_guess)
+    tuples"""
+    if isinstance(hits, np.ndarray) and hits.dtype.names:
+        m = np.zeros(hits.size, dtype=MATCH_DTYPE)
+        for f in MATCH_DTYPE.names:
+            m[f] = hits.reshape(-1)[f]
+        return m
+    return np.array([tuple(r) for r in hits], dtype=MATCH_DTYPE)
+
+
+def align_grid_bytes(params: AlignParams | None = None) -> int:
+    """bev_align_grid_bytes: grid * grid; 0 for parameters outside the admitted values."""
+    return int(load_lib().bev_align_grid_bytes(C.byref(params) if params is not None else None))
 
 
 def place_descriptor_bytes(params: PlaceParams | None = None) -> int:

@@ -932,6 +932,11 @@ void bev_destroy(bev_ctx_t *c)
     c->place_planes.release();
     c->place_pairs.release();
     c->place_out.release();
+    c->align_tab.release();
+    c->align_hits.release();
+    c->align_planes.release();
+    c->align_hyp.release();
+    c->align_io.release();
     c->posed_ws.release();
     c->posed_imgs.release();
     for (auto &s : c->prof_pool) {

@@ -1,8 +1,9 @@
 /*
- * bev_ctx.h — the context behind bev_ctx_t and what the six files of the C ABI share: bev_capi.hip (the context, the BEV
+ * bev_ctx.h — the context behind bev_ctx_t and what the seven files of the C ABI share: bev_capi.hip (the context, the BEV
  * pipeline and the single-cloud entry points), bev_capi_packed.hip (the batched calls over packed frames), bev_capi_reg.hip
  * (the registration entry points, frame against frame), bev_capi_submap_reg.hip (frames against submaps; what only these
- * two and bev_capi_verify.hip share: bev_reg_host.h), bev_capi_place.hip (place retrieval) and bev_capi_verify.hip (verification of registered matches) — among it the prologue of every call outside the fused pipeline (begin_call) and the bound
+ * two and bev_capi_verify.hip share: bev_reg_host.h), bev_capi_place.hip (place retrieval), bev_capi_verify.hip (verification of
+ * registered matches) and bev_capi_align.hip (the translation guess of retrieved pairs) — among it the prologue of every call outside the fused pipeline (begin_call) and the bound
  * on a cloud's points (cloud_cap).  Private, like bev_internal.h.  Named namespace: struct bev_ctx is one type in all of them.
  */
 #ifndef BEV_CTX_H
@@ -113,7 +114,7 @@ struct Downloader {
     }
 };
 
-/* ---- what the batched entry points keep between calls (defined in bev_capi.hip; used by all six files) ---- */
+/* ---- what the batched entry points keep between calls (defined in bev_capi.hip; used by all seven files) ---- */
 /* a device buffer that grows when a call needs more */
 struct DevBuf {
     void *p = nullptr;
@@ -281,6 +282,11 @@ struct bev_ctx {
      * the device (unit records, hits); all allocated on first use and grown on demand */
     bevh::UploadTable place_tab, place_lim;
     bevh::DevBuf place_planes, place_pairs, place_out;
+    /* translation guess of retrieved pairs (bev_capi_align.hip): the frame table or plan of a grid call, the
+     * hits of a hits call; the grids' planes; the hypotheses of a launch group; what bev_align_batch keeps on the device (the
+     * clouds, the grids, the records coming out); all allocated on first use and grown on demand */
+    bevh::UploadTable align_tab, align_hits;
+    bevh::DevBuf align_planes, align_hyp, align_io;
     int posed_group = 0; /* BEV_POSED_GROUP=1 .. 65535: grids per launch group (tests: results do not depend on it); 0: what fits kPosedWsCap */
 
     bevh::RegState reg;

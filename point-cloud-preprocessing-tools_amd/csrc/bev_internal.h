@@ -264,6 +264,10 @@ enum KernelId {
     K_PLACE_TOPK,    /* ... the best top_k candidates of every query */
     K_VERIFY_MOVE,   /* verification of registered matches (bev_verify.h): the moved query of every match and its search grid */
     K_VERIFY_COUNT,  /* ... the inlier counts of both directions */
+    K_ALIGN_GRID,    /* translation guess of retrieved pairs (bev_align.h): the candidates' height grids, maxima per cell */
+    K_ALIGN_FINISH,  /* ... their bytes and sums of squares */
+    K_ALIGN_HIT,     /* ... every shift of one (hit, flip, k) hypothesis and the best of them */
+    K_ALIGN_PICK,    /* ... per hit: the order over k, the sub-cell offsets, the results, the detail and best */
     K_COUNT
 };
 const char *kernel_name(int id);
@@ -713,6 +717,43 @@ void launch_verify_move(const VerifyProblem *probs, int n, const FineWork &w, co
 /* both directions of the same matches; slices: workgroups of `slice` points over the largest cloud of either side */
 void launch_verify_count(const VerifyProblem *probs, int n, uint32_t slices, const FineWork &w, const VerifyTarget &t,
                          const VerifyWork &v, const bev_verify_params_t &prm, uint32_t slice, bev_verify_result_t *out, hipStream_t st);
+
+/* ---- translation guess of retrieved pairs: height-grid offset search (bev_align.h) ---- */
+struct AlignShape { /* bev_align_params_t as the kernels take it, and what a point's value needs */
+    int G, S, K, skip_label0;
+    float cell, yaw_step, lidar_to_ground;
+};
+/* a hit as it goes up: the query's records, the candidate's grid (-1: none, read as an empty grid) and the yaw */
+struct AlignHit {
+    uint64_t off;
+    uint32_t n;
+    int32_t cand;
+    float angle_guess;
+    uint32_t _pad;
+};
+static_assert(sizeof(AlignHit) == 24, "the device reads this layout");
+/* what k_align_hit leaves of one (hit, flip, k) hypothesis: its best shift, the query grid's sum of squares and the scores of
+ * the shift's four neighbours (0 where a neighbour lies outside the window: not read then) */
+struct AlignHyp {
+    uint32_t score;
+    int32_t dx, dy;
+    uint32_t eq, sxm, sxp, sym, syp;
+};
+static_assert(sizeof(AlignHyp) == 32, "one record per hypothesis");
+/* the words of dynamic LDS of k_align_hit for a shape: the plane of G * G words, then the packed query, the padded candidate,
+ * the table of scores and the reduction's scratch in its place */
+size_t align_hit_lds_bytes(const AlignShape &as);
+/* rows, ent0, blocks and entries as for launch_place_splat; planes: G * G words per grid, zeroed by the caller on the stream */
+void launch_align_grid(const bev_point_t *clouds, const void *rows, const uint32_t *ent0, int nf, uint32_t blocks,
+                       const void *entries, const AlignShape &as, uint32_t *planes, hipStream_t st);
+/* n_grids planes into grids (G * G bytes each) and energy (their sums of squares) */
+void launch_align_finish(const uint32_t *planes, int n_grids, const AlignShape &as, uint8_t *grids, uint32_t *energy, hipStream_t st);
+/* n hits from hits[0]: hyp[(h * 2 + flip) * (2K + 1) + (k + K)] */
+void launch_align_hit(const bev_point_t *clouds, const AlignHit *hits, int n, const uint8_t *grids, const AlignShape &as,
+                      AlignHyp *hyp, hipStream_t st);
+/* ... and their results[2h + flip], best[h] and (where wanted) detail[2h + flip] */
+void launch_align_pick(const AlignHit *hits, int n, const AlignHyp *hyp, const uint32_t *energy, const AlignShape &as,
+                       bev_icp_result_t *results, int32_t *best, bev_align_detail_t *detail, hipStream_t st);
 
 /* opt in to > 64 KiB of dynamic LDS for the kernels that need it */
 hipError_t configure_kernels(const Geometry &g);

@@ -55,6 +55,7 @@
 #include "bev_wide_icp.h"
 #include "bev_place.h"
 #include "bev_verify.h"
+#include "bev_align.h"
 
 using namespace bevx;
 
@@ -78,6 +79,7 @@ static const char *const kNames[K_COUNT] = {
     "k_pairgrid_desc", "k_fine_icp_wide", "k_icp_wide",
     "k_place_splat", "k_place_finish", "k_place_pairs", "k_place_topk",
     "k_verify_move", "k_verify_count",
+    "k_align_grid", "k_align_finish", "k_align_hit", "k_align_pick",
 };
 const char *kernel_name(int id) { return (id >= 0 && id < K_COUNT) ? kNames[id] : "?"; }
 

@@ -46,7 +46,7 @@ void DeviceBuffer::download(void *dst, size_t bytes) const { hip_check(hipMemcpy
 
 ChunkResult runChunk(bev_ctx_t *ctx, const std::vector<Cloud> &clouds, const std::vector<uint64_t> &offs, const Chunk &chunk,
                      const std::vector<float> *entry_pose, float map_leaf, bool top_part, const bev_icp_params_t &fine_prm,
-                     float pn_leaf, bool top_union, const bev_verify_params_t *verify)
+                     float pn_leaf, bool top_union, const bev_verify_params_t *verify, const bev_align_params_t *align)
 {
     using clk = std::chrono::steady_clock;
     const int F = (int)clouds.size(), n = (int)chunk.matches.size();
@@ -87,6 +87,22 @@ ChunkResult runChunk(bev_ctx_t *ctx, const std::vector<Cloud> &clouds, const std
                      coarse.as<bev_icp_result_t>(), best.as<int32_t>());
         BEV_CALL(bev_synchronize);
     }
+    DeviceBuffer grids, energy, detail; /* the translation guess's: it fills coarse and best, which the fine stage reads at once */
+    const bool aligned = align && !top_part;
+    if (aligned) {
+        const size_t n_db = entry_pose ? (size_t)n : (size_t)F, grid_bytes = bev_align_grid_bytes(align);
+        if (!grid_bytes) throw std::runtime_error("bev_align_grid_bytes: parameters outside the admitted values");
+        grids = DeviceBuffer(std::max<size_t>(n_db, 1) * grid_bytes);
+        energy = DeviceBuffer(std::max<size_t>(n_db, 1) * sizeof(uint32_t));
+        coarse = DeviceBuffer((size_t)n * 2 * sizeof(bev_icp_result_t));
+        best = DeviceBuffer((size_t)n * 4);
+        detail = DeviceBuffer((size_t)n * 2 * sizeof(bev_align_detail_t));
+        BEV_CALL(bev_align_grid_device_resident, F, pts.as<bev_point_t>(), offs.data(), entry_pose ? n : 0, entry_pose ? map_offs : nullptr,
+                 entry_pose ? entry_frame : nullptr, entry_pose ? entry_pose->data() : nullptr, align, grids.as<uint8_t>(),
+                 energy.as<uint32_t>());
+        BEV_CALL(bev_align_hits_device_resident, F, pts.as<bev_point_t>(), offs.data(), (int)n_db, grids.as<uint8_t>(),
+                 energy.as<uint32_t>(), n, cm, align, coarse.as<bev_icp_result_t>(), best.as<int32_t>(), detail.as<bev_align_detail_t>());
+    }
     const auto t1 = clk::now();
     if (entry_pose) /* with map_leaf 0 this is bev_submap_registration_device_resident, which forwards here */
         BEV_CALL(bev_submap_voxel_registration_device_resident, F, pts.as<bev_point_t>(), offs.data(), 0.2f, map_leaf, n, map_offs,
@@ -101,7 +117,8 @@ ChunkResult runChunk(bev_ctx_t *ctx, const std::vector<Cloud> &clouds, const std
     r.ms_first = std::chrono::duration<double, std::milli>(t1 - t0).count();
     r.ms_fine = std::chrono::duration<double, std::milli>(t2 - t1).count();
     r.fine = downloaded<bev_icp_result_t>(fine, n);
-    if (top_part) r.coarse = downloaded<bev_icp_result_t>(coarse, 2 * (size_t)n), r.best = downloaded<int32_t>(best, n);
+    if (top_part || aligned) r.coarse = downloaded<bev_icp_result_t>(coarse, 2 * (size_t)n), r.best = downloaded<int32_t>(best, n);
+    if (aligned) r.align = downloaded<bev_align_detail_t>(detail, 2 * (size_t)n);
     if (verify) { /* the fine results stay where they are: only their transforms are read */
         DeviceBuffer counts(std::max<size_t>((size_t)n, 1) * sizeof(bev_verify_result_t));
         if (entry_pose)
@@ -145,7 +162,7 @@ void Tally::print(std::ostream &out, bool coarse_line, bool fine_is_both) const
 
 int registerChunk(const std::vector<std::string> &paths, const Chunk &chunk, const std::vector<float> *entry_pose, float map_leaf,
                   bool top_part, const bev_icp_params_t &fine_prm, Tally &tally, float pn_leaf, bool top_union,
-                  const bev_verify_params_t *verify, ChunkResult *result)
+                  const bev_verify_params_t *verify, ChunkResult *result, const bev_align_params_t *align)
 {
     std::vector<Cloud> clouds(paths.size());
     std::vector<uint64_t> offs(paths.size() + 1, 0);
@@ -159,7 +176,7 @@ int registerChunk(const std::vector<std::string> &paths, const Chunk &chunk, con
     bev_ctx_t *ctx = bevhost_context();
     if (!ctx) return 2;
     try {
-        ChunkResult r = runChunk(ctx, clouds, offs, chunk, entry_pose, map_leaf, top_part, fine_prm, pn_leaf, top_union, verify);
+        ChunkResult r = runChunk(ctx, clouds, offs, chunk, entry_pose, map_leaf, top_part, fine_prm, pn_leaf, top_union, verify, align);
         tally.add(chunk, r);
         if (result) *result = std::move(r);
     } catch (const std::exception &e) {

@@ -47,6 +47,9 @@ struct ChunkResult {
     std::vector<bev_icp_result_t> coarse; /* top part: per match, from the guess and from the guess + 180 */
     std::vector<int32_t> best;            /* top part: which of the two the fine stage started from */
     std::vector<bev_verify_result_t> verify; /* per match, where runChunk was handed verification parameters; else empty */
+    /* where runChunk was handed alignment parameters (and not top_part): per match and flip the translation guess's detail;
+     * coarse and best are then its table, what the fine stage started from; else empty */
+    std::vector<bev_align_detail_t> align;
     double ms_first = 0.0; /* from before the first allocation to the synchronise behind coarse ICP (whole: the uploads) */
     double ms_fine = 0.0;  /* the fine stage and its synchronise */
 };
@@ -60,10 +63,13 @@ struct ChunkResult {
  * top part over the union of the entries' moved FULL clouds, thinned the same way, the front end's rows being the queries
  * (bev_submap_top_part_coarse_registration_device_resident).  verify not null: behind the fine stage and outside its
  * time, the two-way inlier counts of every match under its final transform, against the same targets; null, the
- * default: exactly the chain without them */
+ * default: exactly the chain without them.  align not null and not top_part: ahead of the fine stage, the height grids of the
+ * matches' targets (the frames, or the chunk's maps) and the translation guess of every match, whose table the
+ * fine stage starts from in place of the yaw guess, with no synchronisation in between; null, the default: the chain as ever */
 ChunkResult runChunk(bev_ctx_t *ctx, const std::vector<Cloud> &clouds, const std::vector<uint64_t> &offs, const Chunk &chunk,
                      const std::vector<float> *entry_pose, float map_leaf, bool top_part, const bev_icp_params_t &fine_prm,
-                     float pn_leaf = 0.0f, bool top_union = false, const bev_verify_params_t *verify = nullptr);
+                     float pn_leaf = 0.0f, bool top_union = false, const bev_verify_params_t *verify = nullptr,
+                     const bev_align_params_t *align = nullptr);
 
 /* what a successful match's "diff_xy diff_yaw" line compares its final transform with */
 enum class ReportAgainst { Nothing, ChosenCoarse, YawGuess };
@@ -83,11 +89,12 @@ private:
 };
 
 /* The files paths[f] as the chunk's frames, the context (after the files: an unreadable one ends the tool first), runChunk, Tally::add.  0, or the tool's exit
- * status with the reason on stderr: 1 an unreadable cloud, 2 no context or a failed call.  verify: runChunk's; result not null: it
- * gets what runChunk returned */
+ * status with the reason on stderr: 1 an unreadable cloud, 2 no context or a failed call.  verify, align: runChunk's; result not
+ * null: it gets what runChunk returned */
 int registerChunk(const std::vector<std::string> &paths, const Chunk &chunk, const std::vector<float> *entry_pose, float map_leaf,
                   bool top_part, const bev_icp_params_t &fine_prm, Tally &tally, float pn_leaf = 0.0f, bool top_union = false,
-                  const bev_verify_params_t *verify = nullptr, ChunkResult *result = nullptr);
+                  const bev_verify_params_t *verify = nullptr, ChunkResult *result = nullptr,
+                  const bev_align_params_t *align = nullptr);
 
 } // namespace regchain
 

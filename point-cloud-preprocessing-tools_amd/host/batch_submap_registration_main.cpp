@@ -2,7 +2,7 @@
  * batch_submap_registration          <match_result_text_file> <keyframes_root_dir> <half_window> [<chunk> [<map_leaf>]]
  * batch_submap_top_part_registration <match_result_text_file> <keyframes_root_dir> <half_window> [<chunk> [<map_leaf>]]
  *
- * One source, built twice (BEV_SUBMAP_TOP_PART 0 / 1).  The first tool:
+ * One source, built four times (BEV_SUBMAP_TOP_PART 0 / 1; BEV_VERIFY_TOOL, BEV_ALIGN_TOOL below).  The first tool:
  *
  * Scan-to-map registration: batch_whole_registration with a LOCAL MAP as every match's target.  The match list
  * is batch_whole_registration's ("query match yaw" per line); the indices name the sorted files of
@@ -59,6 +59,16 @@
  * verified_match_result.txt (one line "query_idx match_idx yaw" per accepted match, yaw = atan2(T[4], T[0]) in degrees: a match
  * list that loadMatchResults reads back).
  *
+ * batch_aligned_registration <match_result_text_file> <keyframes_root_dir> <half_window> [<chunk> [<map_leaf>]] (a fourth build,
+ * BEV_ALIGN_TOOL 1) is batch_submap_registration, stdout and reports included, with a translation guess ahead of
+ * the fine stage of every chunk: the height grids of the chunk's maps (bev_align_grid_device_resident), the shift search of every
+ * match (bev_align_hits_device_resident), and the fine stage from that table in place of the yaw guess.  BEV_ALIGN=<grid>,<cell>,
+ * <max_shift>,<yaw_steps>,<yaw_step> in the environment overrides the defaults (bev_align_defaults; skip_label0 stays 1); unset or
+ * empty: the defaults; anything but five numbers inside the admitted values: exit 1 with "BEV_ALIGN '<text>': expected
+ * <grid>,<cell>,<max_shift>,<yaw_steps>,<yaw_step> ..." and the usage line before any GPU work.  Into the working directory goes
+ * alignment_detail.csv: a header, then two rows per input match in input order, flip 0 and flip 1: query, match, flip, chosen (1
+ * on the row the fine stage started from), dx, dy, k, score, eq, ec, off_x, off_y, fitness, tx, ty.
+ *
  * The chunks, the chain and the bookkeeping are the four registration tools' own (RegistrationChunks.h, RegistrationChain.h;
  * DESIGN.md §6p), the entries' matrices every submap tool's (submapwin::appendEntryPose): this file is the command line, which
  * file an index names, and the poses.
@@ -67,6 +77,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <fstream>
 #include <iostream>
 #include <string>
@@ -83,12 +94,19 @@
 #ifndef BEV_VERIFY_TOOL
 #define BEV_VERIFY_TOOL 0
 #endif
+#ifndef BEV_ALIGN_TOOL
+#define BEV_ALIGN_TOOL 0
+#endif
 
 namespace {
 
-constexpr bool kTopPart = BEV_SUBMAP_TOP_PART, kVerify = BEV_VERIFY_TOOL;
+constexpr bool kTopPart = BEV_SUBMAP_TOP_PART, kVerify = BEV_VERIFY_TOOL, kAlign = BEV_ALIGN_TOOL;
 static_assert(!(kTopPart && kVerify), "the verified tool is the whole tool's chain");
-const char *const kTool = kVerify ? "batch_verified_registration" : kTopPart ? "batch_submap_top_part_registration" : "batch_submap_registration";
+static_assert(!(kAlign && (kTopPart || kVerify)), "the aligned tool is the whole tool's chain");
+const char *const kTool = kAlign    ? "batch_aligned_registration"
+                          : kVerify ? "batch_verified_registration"
+                          : kTopPart ? "batch_submap_top_part_registration"
+                                     : "batch_submap_registration";
 
 void usage()
 {
@@ -96,6 +114,34 @@ void usage()
     if (kVerify)
         std::cerr << "  environment: BEV_VERIFY_THRESHOLD=<metres> (default 0.5), BEV_VERIFY_MIN_OVERLAP=<share> (default 0.3): finite, > 0,\n"
                      "  the overlap <= 1.  Both defaults are placeholders that nobody has tuned on real sweeps.\n";
+    if (kAlign)
+        std::cerr << "  environment: BEV_ALIGN=<grid>,<cell>,<max_shift>,<yaw_steps>,<yaw_step> (default 128,0.5,16,1,2): grid even, 16 ... 128;\n"
+                     "  cell > 0; max_shift 1 ... 16 and 2 * max_shift <= grid / 2; yaw_steps 0 ... 3; yaw_step >= 0.\n";
+}
+
+/* BEV_ALIGN: five numbers and nothing else, inside the admitted values (bev_align_grid_bytes says which) */
+bool parse_align(const char *s, bev_align_params_t *out)
+{
+    bev_align_params_t p = *out;
+    int used = 0;
+    if (std::sscanf(s, "%d,%f,%d,%d,%f%n", &p.grid, &p.cell, &p.max_shift, &p.yaw_steps, &p.yaw_step, &used) != 5 || s[used] != '\0')
+        return false;
+    for (const char *c = s; *c; ++c) /* (sscanf reads "nan", "inf" and leading blanks: digits, signs, points and exponents only) */
+        if (!std::strchr("0123456789+-.,eE", *c)) return false;
+    if (bev_align_grid_bytes(&p) == 0) return false;
+    *out = p;
+    return true;
+}
+
+/* the two rows of a match in alignment_detail.csv */
+void aligned_rows(std::FILE *csv, const MatchResult &mt, const bev_icp_result_t *table, const bev_align_detail_t *detail, int best)
+{
+    for (int flip = 0; flip < 2; ++flip) {
+        const bev_align_detail_t &d = detail[flip];
+        std::fprintf(csv, "%d,%d,%d,%d,%d,%d,%d,%u,%u,%u,%.9g,%.9g,%.17g,%.9g,%.9g\n", mt.query_idx, mt.match_idx, flip,
+                     best == flip ? 1 : 0, d.dx, d.dy, d.k, d.score, d.eq, d.ec, (double)d.off_x, (double)d.off_y, table[flip].fitness,
+                     (double)table[flip].T[3], (double)table[flip].T[7]);
+    }
 }
 
 /* BEV_VERIFY_THRESHOLD, BEV_VERIFY_MIN_OVERLAP: unset or empty: the default; a finite number in (0, most]; else false */
@@ -152,6 +198,13 @@ int main(int argc, char **argv)
         usage();
         return 1;
     }
+    bev_align_params_t aprm = bev_align_defaults();
+    if (const char *env = kAlign ? std::getenv("BEV_ALIGN") : nullptr)
+        if (*env && !parse_align(env, &aprm)) {
+            std::cerr << "BEV_ALIGN '" << env << "': expected <grid>,<cell>,<max_shift>,<yaw_steps>,<yaw_step> inside the admitted values\n";
+            usage();
+            return 1;
+        }
     if (const char *env = kTopPart ? std::getenv("BEV_SUBMAP_PN_LEAF") : nullptr)
         if (*env && !parse_map_leaf(env, &pn_leaf)) {
             std::cerr << "BEV_SUBMAP_PN_LEAF '" << env << "': expected a finite number >= 0\n";
@@ -236,6 +289,12 @@ int main(int argc, char **argv)
     if (kVerify)
         std::fprintf(csv, "query,match,fitness,converged,n_query,n_target,query_within,target_within,overlap,accepted,"
                           "t00,t01,t02,t03,t10,t11,t12,t13,t20,t21,t22,t23\n");
+    std::FILE *align_csv = kAlign ? std::fopen("./alignment_detail.csv", "w") : nullptr;
+    if (kAlign && !align_csv) {
+        std::cerr << "alignment_detail.csv: can not be written\n";
+        return 1;
+    }
+    if (kAlign) std::fprintf(align_csv, "query,match,flip,chosen,dx,dy,k,score,eq,ec,off_x,off_y,fitness,tx,ty\n");
     regchain::Tally tally(kTopPart ? &report : &submap_report,
                           kTopPart ? regchain::ReportAgainst::ChosenCoarse : regchain::ReportAgainst::YawGuess);
     if (search_grid[0] || search_grid[1]) {
@@ -253,8 +312,11 @@ int main(int argc, char **argv)
                 submapwin::appendEntryPose(pose, matches[m0 + k].match_idx, chunk.files[chunk.entry_frame[e]], entry_pose);
         regchain::ChunkResult res;
         if (const int rc = regchain::registerChunk(paths, chunk, &entry_pose, map_leaf, kTopPart, prm, tally, pn_leaf, top_union,
-                                                   kVerify ? &vprm : nullptr, kVerify ? &res : nullptr))
+                                                   kVerify ? &vprm : nullptr, kVerify || kAlign ? &res : nullptr,
+                                                   kAlign ? &aprm : nullptr))
             return rc;
+        for (size_t k = 0; kAlign && k < chunk.matches.size(); ++k)
+            aligned_rows(align_csv, matches[m0 + k], &res.coarse[2 * k], &res.align[2 * k], res.best[k]);
         for (size_t k = 0; kVerify && k < chunk.matches.size(); ++k)
             verified_row(csv, list, matches[m0 + k], res.fine[k], res.verify[k], half == 0, min_overlap);
         m0 = chunk.m1;
@@ -262,5 +324,6 @@ int main(int argc, char **argv)
     /* batch_submap_registration's fine line is the whole visit of the device, uploads included */
     tally.print(std::cout, kTopPart, !kTopPart);
     if (kVerify && (std::fclose(csv) != 0 || std::fclose(list) != 0)) return 1;
+    if (kAlign && std::fclose(align_csv) != 0) return 1;
     return 0;
 }
