@@ -24,7 +24,7 @@
 namespace bevk {
 using namespace bevx;
 
-/* k_place_splat's shape over a Cartesian plane of G * G words (dynamic LDS) */
+/* lds_max_splat (bev_place.h) over a Cartesian plane of G * G words (dynamic LDS) */
 template <bool kMaps>
 __global__ __launch_bounds__(256) void k_align_grid(const bev_point_t *__restrict__ clouds, const ProjFrame *__restrict__ tab,
                                                     const uint32_t *__restrict__ ent0, int nf,
@@ -32,39 +32,8 @@ __global__ __launch_bounds__(256) void k_align_grid(const bev_point_t *__restric
                                                     uint32_t *__restrict__ planes)
 {
     extern __shared__ uint32_t align_grid_plane[];
-    uint32_t *s_cell = align_grid_plane;
-    const int cells = as.G * as.G;
-    const PackedPlace pl = packed_place(tab, nf, blockIdx.x + tab[0].blk0);
-    const uint32_t n = pl.n, k0 = pl.k0;
-    for (int i = (int)threadIdx.x; i < cells; i += 256) s_cell[i] = 0u;
-    float4 a[kProjPerThread];
-    int label[kProjPerThread];
-    load_packed_records(clouds + pl.off, n, k0, as.skip_label0 != 0, 1, a, label);
-    __syncthreads();
-    const uint32_t e0 = kMaps ? ent0[pl.f] : 0u, e1 = kMaps ? ent0[pl.f + 1] : 1u;
-    for (uint32_t e = e0; e < e1; ++e) {
-        bevsub::Entry en;
-        if (kMaps) en = entries[e];
-#pragma unroll
-        for (int j = 0; j < kProjPerThread; ++j) {
-            float x = a[j].x, y = a[j].y, z = a[j].z;
-            if (kMaps) transform_xyz(en.m, a[j].x, a[j].y, a[j].z, x, y, z);
-            int cell = align_cell(x, y, label[j], as.G, as.cell, as.skip_label0);
-            if (k0 + (uint32_t)j * 256u >= n) cell = -1;
-            const int v = place_value(z, as.lidar_to_ground);
-            if (cell >= 0 && v > 0) atomicMax(&s_cell[cell], (uint32_t)v);
-        }
-        __syncthreads();
-        uint32_t *__restrict__ plane = planes + (size_t)(kMaps ? en.grid : (uint32_t)pl.f) * (size_t)cells;
-        for (int i = (int)threadIdx.x; i < cells; i += 256) {
-            const uint32_t v = s_cell[i];
-            if (v) {
-                atomicMax(&plane[i], v);
-                s_cell[i] = 0u; /* (the thread that zeroes a cell is the one that read it) */
-            }
-        }
-        __syncthreads();
-    }
+    lds_max_splat<kMaps>(clouds, tab, ent0, nf, entries, as.skip_label0, as.lidar_to_ground, as.G * as.G, align_grid_plane, planes,
+                         [=](float x, float y, int label) { return align_cell(x, y, label, as.G, as.cell, as.skip_label0); });
 }
 
 /* the sum of a value over a workgroup of 256 threads, in thread 0 (scratch: 4 words of LDS, free on entry) */

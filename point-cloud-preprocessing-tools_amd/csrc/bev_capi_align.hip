@@ -2,14 +2,13 @@
  * bev_capi_align.hip — the translation guess of retrieved pairs of the boundary declared extern "C" in include/bev_mi355x.h
  * (DESIGN.md §6ab): Cartesian height grids of frames or of submaps over packed frames, and per hit of a match list the table of
  * initial transforms the fine registration calls take.  Host-side only; the kernels are bev_align.h's, the arithmetic
- * bev_align_exact.h's, the maps' plan bev_submap_plan.h's (§6i), the bracket of a device-resident call and the argument checks
- * bev_ctx.h's.
+ * bev_align_exact.h's, the maps' plan bev_submap_plan.h's (§6i); the prologue of the grid call and the tables on their way up
+ * are bev_packed_host.h's, shared with the submap calls and place retrieval.
  */
 #include <cstdlib>
 
-#include "bev_ctx.h"
+#include "bev_packed_host.h"
 #include "bev_align_exact.h"
-#include "bev_submap_plan.h"
 
 using namespace bevh; /* (and through it bevk) */
 using namespace bevx;
@@ -24,66 +23,28 @@ bool align_call(const bev_ctx *c, const bev_align_params_t *params, AlignShape *
     return true;
 }
 
-/* the map arrays of a call: all NULL with n_maps == 0 (no maps: the frames), or the submap calls' */
-int check_align_maps(int n_frames, int n_maps, const uint64_t *map_offs, const int32_t *entry_frame, const float *entry_pose,
-                     bool *maps)
-{
-    *maps = map_offs != nullptr;
-    if (!map_offs) return (n_maps == 0 && !entry_frame && !entry_pose) ? BEV_OK : BEV_ERR_INVALID_ARG;
-    return check_submap_entries(n_frames, n_maps, map_offs, entry_frame, entry_pose);
-}
-
 /* The grids of nf frames (map_offs == nullptr), or of n_maps maps over them, in device memory, on the context's stream
- * (arguments checked by the caller; at least one grid).  The tables go up in ONE block of align_tab: the frame table of a call
- * without maps (nf + 1 rows) or the one launch group of a plan over maps (§6i). */
+ * (arguments checked by the caller; at least one grid).  The tables go up in ONE block of align_tab (TablesUp,
+ * bev_packed_host.h): the frame table of a call without maps or the one launch group of a plan over maps (§6i). */
 int align_grids(bev_ctx *c, const AlignShape &as, int nf, const bev_point_t *d_clouds, const uint64_t *offs, int n_maps,
                 const uint64_t *map_offs, const int32_t *entry_frame, const float *entry_pose, uint8_t *d_grids, uint32_t *d_energy)
 {
-    const bool maps = map_offs != nullptr;
-    const int n_grids = maps ? n_maps : nf;
-    std::vector<bevsub::Frame> rows;
-    bevsub::Plan plan;
-    bevsub::GroupBytes at{};
-    size_t bytes = 0;
-    if (maps) {
-        if (!bevsub::plan_maps(plan, offs, map_offs, 0, n_maps, entry_frame, entry_pose, (size_t)n_maps)) return BEV_ERR_TOO_LARGE;
-        at = bevsub::group_bytes(plan.groups[0], 0);
-        bytes = at.end;
-    } else {
-        uint64_t b = 0;
-        rows.resize((size_t)nf + 1);
-        for (int f = 0; f < nf; ++f) {
-            const uint32_t n = (uint32_t)(offs[f + 1] - offs[f]);
-            rows[f] = bevsub::Frame{offs[f], n, (uint32_t)b};
-            b += (n + bevsub::kBlockPoints - 1u) / bevsub::kBlockPoints;
-            if (b > 0x7fffffffull) return BEV_ERR_TOO_LARGE;
-        }
-        rows[nf] = bevsub::Frame{offs[nf], 0u, (uint32_t)b};
-        bytes = rows.size() * sizeof(bevsub::Frame);
-    }
+    TablesUp u;
+    const int n_grids = map_offs ? n_maps : nf;
+    if (map_offs ? !bevsub::plan_maps(u.plan, offs, map_offs, 0, n_maps, entry_frame, entry_pose, (size_t)n_maps) : !u.frames(nf, offs))
+        return BEV_ERR_TOO_LARGE;
     const size_t plane_bytes = (size_t)n_grids * (size_t)as.G * (size_t)as.G * sizeof(uint32_t);
     int rc = c->align_planes.grow(c, plane_bytes); /* (a grow waits for the stream: before the tables go up) */
     if (rc != BEV_OK) return rc;
     uint32_t *planes = static_cast<uint32_t *>(c->align_planes.p);
     HIPCK(c, hipMemsetAsync(planes, 0, plane_bytes, c->stream));
-    char *h = nullptr;
-    rc = c->align_tab.begin(c, bytes, 64 * 1024, reinterpret_cast<void **>(&h));
+    rc = u.up(c, c->align_tab);
     if (rc != BEV_OK) return rc;
-    if (maps) bevsub::pack(plan, h);
-    else memcpy(h, rows.data(), bytes);
-    rc = c->align_tab.push(c, bytes);
-    if (rc != BEV_OK) return rc;
-    const char *dev = static_cast<const char *>(c->align_tab.dev);
-    const bevsub::Frame *hr = maps ? plan.rows.data() + plan.groups[0].row0 : rows.data();
-    const int nr = maps ? plan.groups[0].n_rows : nf;
-    const uint32_t blocks = hr[nr].blk0 - hr[0].blk0;
-    if (blocks) {
+    const int nr = u.plan.groups[0].n_rows;
+    const TablesUp::Slice s = u.slice(0, 0, nr);
+    if (s.blocks) {
         ProfScope ps(c, K_ALIGN_GRID, nr);
-        if (maps)
-            launch_align_grid(d_clouds, dev + at.rows, reinterpret_cast<const uint32_t *>(dev + at.ent0), nr, blocks,
-                              dev + at.entries, as, planes, c->stream);
-        else
-            launch_align_grid(d_clouds, dev, nullptr, nr, blocks, nullptr, as, planes, c->stream);
+        launch_align_grid(d_clouds, s.rows, s.ent0, nr, s.blocks, s.entries, as, planes, c->stream);
     }
     {
         ProfScope ps(c, K_ALIGN_FINISH, n_grids);
@@ -157,20 +118,8 @@ int bev_align_grid_device_resident(bev_ctx_t *c, int n_frames, const bev_point_t
 {
     AlignShape as;
     if (!c || !align_call(c, params, &as)) return BEV_ERR_INVALID_ARG;
-    const int rc = check_packed_frames(c, n_frames, h_offsets);
-    if (rc == BEV_ERR_INVALID_ARG) return rc;
-    bool maps = false;
-    const int rc_maps = check_align_maps(n_frames, n_maps, h_map_offsets, h_entry_frame, h_entry_pose, &maps);
-    if (rc_maps != BEV_OK) return rc_maps;
-    if (rc != BEV_OK) return rc; /* (a frame that is too large: behind the arguments that are wrong) */
-    if ((maps ? n_maps : n_frames) == 0) return BEV_OK;
-    if (!d_grids || !d_energy) return BEV_ERR_INVALID_ARG;
-    if (!d_clouds) { /* records to read */
-        if (!maps && h_offsets[n_frames] != h_offsets[0]) return BEV_ERR_INVALID_ARG;
-        for (uint64_t e = maps ? h_map_offsets[0] : 0; maps && e < h_map_offsets[n_maps]; ++e)
-            if (h_offsets[h_entry_frame[e] + 1] != h_offsets[h_entry_frame[e]]) return BEV_ERR_INVALID_ARG;
-    }
-    return resident_call(c, [&] {
+    const FramesAndMaps a{n_frames, d_clouds, h_offsets, n_maps, h_map_offsets, h_entry_frame, h_entry_pose};
+    return resident_maps_call(c, a, true, BEV_OK, d_grids && d_energy, [&] {
         return align_grids(c, as, n_frames, d_clouds, h_offsets, n_maps, h_map_offsets, h_entry_frame, h_entry_pose, d_grids, d_energy);
     });
 }
@@ -208,7 +157,7 @@ int bev_align_batch(bev_ctx_t *c, int n_frames, const bev_point_t *const *clouds
     AlignShape as;
     if (!c || !align_call(c, params, &as) || n_frames < 0 || !host_clouds_ok(n_frames, clouds, n_pts)) return BEV_ERR_INVALID_ARG;
     bool maps = false;
-    int rc = check_align_maps(n_frames, n_maps, h_map_offsets, h_entry_frame, h_entry_pose, &maps);
+    int rc = check_optional_maps(n_frames, n_maps, h_map_offsets, h_entry_frame, h_entry_pose, &maps);
     if (rc != BEV_OK) return rc;
     const int n_db = maps ? n_maps : n_frames;
     if (n_hits < 0 || (n_hits > 0 && (!h_hits || !results || !best)) || !hits_ok(n_frames, n_db, n_hits, h_hits))

@@ -2,12 +2,13 @@
  * bev_capi_packed.hip — the batched calls over packed frames (several clouds one after the other in one buffer, described by
  * n_frames + 1 offsets) of the boundary declared extern "C" in include/bev_mi355x.h: projection of raw sweeps, float BEV,
  * posed BEVs, submap BEVs, float submap BEVs (DESIGN.md §6e – §6j).  Host-side only.  They share one path (§6h): the frame table
- * (upload_packed_table), the bracket of the device-resident calls (resident_call, bev_ctx.h), the chunk loop of the host-buffer calls
- * (packed_host_chunks) and the planes of a launch group (plane_pair_bytes, expand_planes).
+ * (upload_packed_table over bevsub::frame_table), the bracket of the device-resident calls (resident_call, bev_ctx.h), the chunk
+ * loop of the host-buffer calls (packed_host_chunks) and the planes of a launch group (plane_pair_bytes, expand_planes).  What
+ * the calls over maps share with place retrieval and the translation guess is bev_packed_host.h's: the prologue of a
+ * device-resident call (resident_maps_call), the tables on their way up (TablesUp) and the loops of the host-buffer calls.
  */
-#include "bev_ctx.h"
+#include "bev_packed_host.h"
 #include "bev_libm.h"
-#include "bev_submap_plan.h"
 
 using namespace bevh; /* (and through it bevk) */
 
@@ -34,20 +35,12 @@ int fill_packed_table(bev_ctx *c, UploadTable &t, size_t min_cap, int nf, const 
     const int rc = t.begin(c, tab_bytes + pose_bytes, min_cap, reinterpret_cast<void **>(&h));
     if (rc != BEV_OK) return rc;
     ProjFrame *tab = reinterpret_cast<ProjFrame *>(h);
-    uint64_t b = 0;
-    uint32_t m = 0;
-    for (int f = 0; f < nf; ++f) {
-        const uint32_t n = (uint32_t)(offs[f + 1] - offs[f]);
-        tab[f] = ProjFrame{offs[f], n, (uint32_t)b};
-        b += (n + (uint32_t)kProjBlock - 1u) / (uint32_t)kProjBlock;
-        m = std::max(m, n);
-        if (b > 0x7fffffffull) return BEV_ERR_TOO_LARGE;
-    }
-    tab[nf] = ProjFrame{offs[nf], 0u, (uint32_t)b};
+    uint32_t b = 0, m = 0;
+    if (!bevsub::frame_table(reinterpret_cast<bevsub::Frame *>(tab), nf, offs, &m, &b)) return BEV_ERR_TOO_LARGE;
     if (pose_bytes) memcpy(h + tab_bytes, h_poses, pose_bytes);
     const char *d = static_cast<const char *>(t.dev); /* (begin alone sets dev; push only copies into it) */
     *pt = PackedTable{tab, reinterpret_cast<const ProjFrame *>(d), reinterpret_cast<const float *>(d + tab_bytes),
-                      tab_bytes + pose_bytes, (uint32_t)b, m};
+                      tab_bytes + pose_bytes, b, m};
     return BEV_OK;
 }
 /* ... and sends it up the context's stream.  Each call has an UploadTable of its own: a shared one would make a call wait for
@@ -64,34 +57,12 @@ bool poses_ok(int n_poses, const float *h_poses, int max_poses)
     return n_poses >= 0 && n_poses <= max_poses && (n_poses == 0 || h_poses);
 }
 
-/* The host route of a batched call over packed frames (after begin_call with the staging): chunks of max_batch clouds fit the
- * input staging whatever their sizes.  A chunk's clouds are packed into st_in, one copy per non-empty cloud;
- * body(f0, nb, off) launches the chunk's nb frames [off[f], off[f + 1]) of st_in and queues the downloads of their results;
- * all of it follows the chunk before in the order of the context's stream, and one synchronisation ends the call.  An error
- * leaves nothing in flight either: copies of earlier chunks into the caller's buffers may still be on their way. */
+/* The host route of a batched call over packed frames (after begin_call with the staging): packed_chunks' chunks
+ * (bev_packed_host.h), body queueing the downloads of a chunk's results, and the one synchronisation that ends the call. */
 template <class Body>
 int packed_host_chunks(bev_ctx *c, int n_frames, const bev_point_t *const *clouds, const uint32_t *n_pts, Body body)
 {
-    const auto chunks = [&]() -> int {
-        std::vector<uint64_t> off;
-        for (int f0 = 0; f0 < n_frames; f0 += c->max_batch) {
-            const int nb = std::min(c->max_batch, n_frames - f0);
-            off.assign((size_t)nb + 1, 0);
-            for (int f = 0; f < nb; ++f) {
-                off[f + 1] = off[f] + n_pts[f0 + f];
-                if (n_pts[f0 + f])
-                    HIPCK(c, hipMemcpyAsync(c->st_in + off[f], clouds[f0 + f], (size_t)n_pts[f0 + f] * sizeof(bev_point_t),
-                                            hipMemcpyHostToDevice, c->stream));
-            }
-            const int rc_ = body(f0, nb, off.data());
-            if (rc_ != BEV_OK) return rc_;
-        }
-        HIPCK(c, hipStreamSynchronize(c->stream));
-        return BEV_OK;
-    };
-    const int rc = chunks();
-    if (rc != BEV_OK) (void)hipDeviceSynchronize();
-    return rc;
+    return end_host_call(c, packed_chunks(c, n_frames, clouds, n_pts, body));
 }
 
 /* The float BEV of nf frames on the context's stream: frame f = records [offs[f], offs[f + 1]) of d_clouds (offsets checked by
@@ -170,64 +141,40 @@ int posed_bev_frames(bev_ctx *c, int nf, const bev_point_t *d_clouds, const uint
 }
 
 /* ---- submaps: windows of posed frames rastered into one grid per map (bev_submap_plan.h, bev_submap.h) ---- */
-/* A plan on its way to the device: the planes of its largest group in posed_ws, its tables in ONE block of submap_tab, sent up
- * the context's stream. */
-struct SubmapPlanUp {
-    bevsub::Plan plan;
-    std::vector<bevsub::GroupBytes> at; /* per group: where its tables lie in the block */
-    const char *dev = nullptr;
-    uint32_t *planes = nullptr;
-};
-/* the tables alone (the float call has no planes: its output is the accumulator) */
-int submap_tables_up(bev_ctx *c, SubmapPlanUp &u)
-{
-    size_t bytes = 0;
-    for (const bevsub::Group &g : u.plan.groups) {
-        u.at.push_back(bevsub::group_bytes(g, bytes));
-        bytes = u.at.back().end;
-    }
-    char *h = nullptr;
-    const int rc = c->submap_tab.begin(c, bytes, 64 * 1024, reinterpret_cast<void **>(&h));
-    if (rc != BEV_OK) return rc;
-    bevsub::pack(u.plan, h);
-    u.dev = static_cast<const char *>(c->submap_tab.dev);
-    return c->submap_tab.push(c, bytes);
-}
-int submap_plan_up(bev_ctx *c, SubmapPlanUp &u)
+/* the planes of a plan's largest group in posed_ws */
+int submap_planes(bev_ctx *c, const bevsub::Plan &plan, uint32_t **planes)
 {
     int most = 0;
-    for (const bevsub::Group &g : u.plan.groups) most = std::max(most, g.n_maps);
-    const int rc = c->posed_ws.grow(c, (size_t)most * plane_pair_bytes(c)); /* (a grow waits for the stream: before the table goes up) */
-    if (rc != BEV_OK) return rc;
-    u.planes = static_cast<uint32_t *>(c->posed_ws.p);
-    return submap_tables_up(c, u);
+    for (const bevsub::Group &g : plan.groups) most = std::max(most, g.n_maps);
+    const int rc = c->posed_ws.grow(c, (size_t)most * plane_pair_bytes(c));
+    *planes = static_cast<uint32_t *>(c->posed_ws.p);
+    return rc;
 }
 /* group gi of an uploaded plan on the context's stream: its rows [r0, r0 + nr) splatted from d_clouds (left out where they hold no point) */
-void submap_splat(bev_ctx *c, const SubmapPlanUp &u, size_t gi, const bev_point_t *d_clouds, int r0, int nr)
+void submap_splat(bev_ctx *c, const TablesUp &u, size_t gi, const bev_point_t *d_clouds, int r0, int nr, uint32_t *planes)
 {
-    const bevsub::Group &g = u.plan.groups[gi];
-    const bevsub::Frame *rows = u.plan.rows.data() + g.row0;
-    const uint32_t blocks = rows[r0 + nr].blk0 - rows[r0].blk0;
-    if (blocks == 0) return;
+    const TablesUp::Slice s = u.slice(gi, r0, nr);
+    if (s.blocks == 0) return;
     ProfScope ps(c, K_SUBMAP_SPLAT, nr);
-    launch_submap_splat(d_clouds, u.dev + u.at[gi].rows + (size_t)r0 * sizeof(bevsub::Frame),
-                        reinterpret_cast<const uint32_t *>(u.dev + u.at[gi].ent0) + r0, nr, blocks, u.dev + u.at[gi].entries,
-                        c->geo, u.planes, c->stream);
+    launch_submap_splat(d_clouds, s.rows, s.ent0, nr, s.blocks, s.entries, c->geo, planes, c->stream);
 }
 
 /* The images of n_maps maps over nf frames in device memory, on the context's stream (arguments checked by the caller) */
 int submap_bev_frames(bev_ctx *c, const bev_point_t *d_clouds, const uint64_t *offs, int n_maps, const uint64_t *map_offs,
                       const int32_t *entry_frame, const float *entry_pose, uint8_t *d_multi, uint8_t *d_single)
 {
-    SubmapPlanUp u;
+    TablesUp u;
     if (!bevsub::plan_maps(u.plan, offs, map_offs, 0, n_maps, entry_frame, entry_pose, posed_cap_grids(c))) return BEV_ERR_TOO_LARGE;
-    int rc = submap_plan_up(c, u);
+    uint32_t *planes = nullptr;
+    int rc = submap_planes(c, u.plan, &planes); /* (a grow waits for the stream: before the tables go up) */
+    if (rc != BEV_OK) return rc;
+    rc = u.up(c, c->submap_tab);
     if (rc != BEV_OK) return rc;
     for (size_t gi = 0; gi < u.plan.groups.size(); ++gi) {
         const bevsub::Group &g = u.plan.groups[gi];
-        HIPCK(c, hipMemsetAsync(u.planes, 0, (size_t)g.n_maps * plane_pair_bytes(c), c->stream));
-        submap_splat(c, u, gi, d_clouds, 0, g.n_rows);
-        expand_planes(c, u.planes, (size_t)g.n_maps, (size_t)g.map0, d_multi, d_single, g.n_maps);
+        HIPCK(c, hipMemsetAsync(planes, 0, (size_t)g.n_maps * plane_pair_bytes(c), c->stream));
+        submap_splat(c, u, gi, d_clouds, 0, g.n_rows, planes);
+        expand_planes(c, planes, (size_t)g.n_maps, (size_t)g.map0, d_multi, d_single, g.n_maps);
     }
     HIPCK(c, hipGetLastError());
     return BEV_OK;
@@ -240,25 +187,23 @@ struct FloatGrid {
     bool skip_label0;
 };
 /* the rows [r0, r0 + nr) of an uploaded plan's one group splatted from d_clouds into grids (left out where they hold no point) */
-void submap_float_splat(bev_ctx *c, const SubmapPlanUp &u, const bev_point_t *d_clouds, int r0, int nr, const FloatGrid &fg,
+void submap_float_splat(bev_ctx *c, const TablesUp &u, const bev_point_t *d_clouds, int r0, int nr, const FloatGrid &fg,
                         float *grids)
 {
-    const bevsub::Frame *rows = u.plan.rows.data() + u.plan.groups[0].row0;
-    const uint32_t blocks = rows[r0 + nr].blk0 - rows[r0].blk0;
-    if (blocks == 0) return;
+    const TablesUp::Slice s = u.slice(0, r0, nr);
+    if (s.blocks == 0) return;
     ProfScope ps(c, K_SUBMAP_FLOAT_SPLAT, nr);
-    launch_submap_float_splat(d_clouds, u.dev + u.at[0].rows + (size_t)r0 * sizeof(bevsub::Frame),
-                              reinterpret_cast<const uint32_t *>(u.dev + u.at[0].ent0) + r0, nr, blocks, u.dev + u.at[0].entries,
-                              fg.interval, (int)fg.M, fg.skip_label0, grids, c->stream);
+    launch_submap_float_splat(d_clouds, s.rows, s.ent0, nr, s.blocks, s.entries, fg.interval, (int)fg.M, fg.skip_label0, grids,
+                              c->stream);
 }
 /* The grids of n_maps > 0 maps over frames in device memory, on the context's stream (arguments checked by the caller): map g's
  * grid at d_out + g * M * M, zeroed here */
 int submap_float_frames(bev_ctx *c, const bev_point_t *d_clouds, const uint64_t *offs, const FloatGrid &fg, int n_maps,
                         const uint64_t *map_offs, const int32_t *entry_frame, const float *entry_pose, float *d_out)
 {
-    SubmapPlanUp u;
+    TablesUp u;
     if (!bevsub::plan_maps(u.plan, offs, map_offs, 0, n_maps, entry_frame, entry_pose, (size_t)n_maps)) return BEV_ERR_TOO_LARGE;
-    const int rc = submap_tables_up(c, u);
+    const int rc = u.up(c, c->submap_tab);
     if (rc != BEV_OK) return rc;
     HIPCK(c, hipMemsetAsync(d_out, 0, (size_t)n_maps * fg.M * fg.M * sizeof(float), c->stream));
     submap_float_splat(c, u, d_clouds, 0, u.plan.groups[0].n_rows, fg, d_out);
@@ -471,22 +416,14 @@ int bev_submap_bev_device_resident(bev_ctx_t *c, int n_frames, const bev_point_t
                                    const uint64_t *h_map_offsets, const int32_t *h_entry_frame, const float *h_entry_pose,
                                    uint8_t *d_multi, uint8_t *d_single)
 {
-    const int rc = check_packed_frames(c, n_frames, h_offsets);
-    if (rc == BEV_ERR_INVALID_ARG) return rc;
-    const int rc_maps = check_submap_entries(n_frames, n_maps, h_map_offsets, h_entry_frame, h_entry_pose);
-    if (rc_maps != BEV_OK) return rc_maps;
-    if (rc != BEV_OK) return rc; /* (a frame that is too large: behind the arguments that are wrong) */
-    if (n_maps == 0) return BEV_OK;
-    if (!d_multi && !d_single) return BEV_ERR_INVALID_ARG;
-    for (uint64_t e = h_map_offsets[0]; e < h_map_offsets[n_maps] && !d_clouds; ++e)
-        if (h_offsets[h_entry_frame[e] + 1] != h_offsets[h_entry_frame[e]]) return BEV_ERR_INVALID_ARG; /* records to read */
-    return resident_call(c, [&] {
+    const FramesAndMaps a{n_frames, d_clouds, h_offsets, n_maps, h_map_offsets, h_entry_frame, h_entry_pose};
+    return resident_maps_call(c, a, false, BEV_OK, d_multi || d_single, [&] {
         return submap_bev_frames(c, d_clouds, h_offsets, n_maps, h_map_offsets, h_entry_frame, h_entry_pose, d_multi, d_single);
     });
 }
 
-/* Maps in chunks of one launch group of at most max_batch maps; the distinct frames a chunk names go through the input
- * staging max_batch at a time, each such piece splatted into the chunk's planes before the next piece goes up. */
+/* host_map_chunks' chunks and pieces (bev_packed_host.h): a chunk's pieces are splatted into its planes, which are then
+ * expanded into the chunk's images. */
 int bev_submap_bev_batch(bev_ctx_t *c, int n_frames, const bev_point_t *const *clouds, const uint32_t *n_pts, int n_maps,
                          const uint64_t *h_map_offsets, const int32_t *h_entry_frame, const float *h_entry_pose,
                          uint8_t *const *multi_out, uint8_t *const *single_out)
@@ -508,30 +445,19 @@ int bev_submap_bev_batch(bev_ctx_t *c, int n_frames, const bev_point_t *const *c
     if (rc != BEV_OK) return rc;
     uint8_t *d_multi = multi_out ? static_cast<uint8_t *>(c->posed_imgs.p) : nullptr;
     uint8_t *d_single = single_out ? static_cast<uint8_t *>(c->posed_imgs.p) + (size_t)chunk * multi_map : nullptr;
-    const auto chunks = [&]() -> int {
-        std::vector<uint64_t> offs((size_t)n_frames + 1, 0); /* (only the counts matter: a row's offset is set per piece) */
-        for (int f = 0; f < n_frames; ++f) offs[f + 1] = offs[f] + n_pts[f];
-        for (int m0 = 0; m0 < n_maps; m0 += chunk) {
-            const int nm = std::min(chunk, n_maps - m0);
-            SubmapPlanUp u;
-            if (!bevsub::plan_maps(u.plan, offs.data(), h_map_offsets, m0, m0 + nm, h_entry_frame, h_entry_pose, (size_t)nm))
-                return BEV_ERR_TOO_LARGE;
-            const bevsub::Group &g = u.plan.groups[0];
-            bevsub::Frame *rows = u.plan.rows.data() + g.row0;
-            for (int r = 0; r < g.n_rows; ++r) /* where the row's frame will lie in the staging while its piece is there */
-                rows[r].off = r % c->max_batch ? rows[r - 1].off + rows[r - 1].n : 0;
-            const int rc_ = submap_plan_up(c, u);
-            if (rc_ != BEV_OK) return rc_;
-            HIPCK(c, hipMemsetAsync(u.planes, 0, (size_t)g.n_maps * plane_pair_bytes(c), c->stream));
-            for (int r0 = 0; r0 < g.n_rows; r0 += c->max_batch) {
-                const int nr = std::min(c->max_batch, g.n_rows - r0);
-                for (int r = r0; r < r0 + nr; ++r)
-                    if (rows[r].n)
-                        HIPCK(c, hipMemcpyAsync(c->st_in + rows[r].off, clouds[u.plan.frame[g.row0 + r]],
-                                                (size_t)rows[r].n * sizeof(bev_point_t), hipMemcpyHostToDevice, c->stream));
-                submap_splat(c, u, 0, c->st_in, r0, nr);
-            }
-            expand_planes(c, u.planes, (size_t)g.n_maps, 0, d_multi, d_single, g.n_maps);
+    rc = c->posed_ws.grow(c, (size_t)chunk * plane_pair_bytes(c));
+    if (rc != BEV_OK) return rc;
+    uint32_t *planes = static_cast<uint32_t *>(c->posed_ws.p);
+    const HostMaps a{n_frames, clouds, n_pts, n_maps, h_map_offsets, h_entry_frame, h_entry_pose, &c->submap_tab};
+    return end_host_call(c, host_map_chunks(
+        c, a, chunk,
+        [&](int, int nm) -> int {
+            HIPCK(c, hipMemsetAsync(planes, 0, (size_t)nm * plane_pair_bytes(c), c->stream));
+            return BEV_OK;
+        },
+        [&](const TablesUp &u, int r0, int nr) { submap_splat(c, u, 0, c->st_in, r0, nr, planes); },
+        [&](int m0, int nm) -> int {
+            expand_planes(c, planes, (size_t)nm, 0, d_multi, d_single, nm);
             HIPCK(c, hipGetLastError());
             for (int m = 0; m < nm; ++m) {
                 if (multi_out)
@@ -541,36 +467,23 @@ int bev_submap_bev_batch(bev_ctx_t *c, int n_frames, const bev_point_t *const *c
                     HIPCK(c, hipMemcpyAsync(single_out[m0 + m], d_single + (size_t)m * single_map, single_map,
                                             hipMemcpyDeviceToHost, c->stream));
             }
-        }
-        HIPCK(c, hipStreamSynchronize(c->stream));
-        return BEV_OK;
-    };
-    rc = chunks();
-    if (rc != BEV_OK) (void)hipDeviceSynchronize();
-    return rc;
+            return BEV_OK;
+        }));
 }
 
 int bev_submap_float_bev_device_resident(bev_ctx_t *c, int n_frames, const bev_point_t *d_clouds, const uint64_t *h_offsets,
                                          float interval, int skip_label0, int n_maps, const uint64_t *h_map_offsets,
                                          const int32_t *h_entry_frame, const float *h_entry_pose, float *d_out)
 {
-    const int rc = check_packed_frames(c, n_frames, h_offsets);
-    if (rc == BEV_ERR_INVALID_ARG) return rc;
-    const int rc_maps = check_submap_entries(n_frames, n_maps, h_map_offsets, h_entry_frame, h_entry_pose);
-    if (rc_maps != BEV_OK) return rc_maps;
     const FloatGrid fg{interval, bev_float_bev_size(interval), skip_label0 != 0};
-    if (fg.M == 0) return BEV_ERR_UNSUPPORTED;
-    if (rc != BEV_OK) return rc; /* (a frame that is too large: behind the arguments that are wrong and the interval) */
-    if (n_maps == 0) return BEV_OK;
-    if (!d_out) return BEV_ERR_INVALID_ARG;
-    for (uint64_t e = h_map_offsets[0]; e < h_map_offsets[n_maps] && !d_clouds; ++e)
-        if (h_offsets[h_entry_frame[e] + 1] != h_offsets[h_entry_frame[e]]) return BEV_ERR_INVALID_ARG; /* records to read */
-    return resident_call(c, [&] {
+    const FramesAndMaps a{n_frames, d_clouds, h_offsets, n_maps, h_map_offsets, h_entry_frame, h_entry_pose};
+    /* (a frame that is too large: behind the arguments that are wrong and the interval) */
+    return resident_maps_call(c, a, false, fg.M == 0 ? BEV_ERR_UNSUPPORTED : BEV_OK, d_out != nullptr, [&] {
         return submap_float_frames(c, d_clouds, h_offsets, fg, n_maps, h_map_offsets, h_entry_frame, h_entry_pose, d_out);
     });
 }
 
-/* bev_submap_bev_batch's chunks and pieces; the chunk's grids in the float-grid buffer of bev_float_bev_batch. */
+/* host_map_chunks' chunks and pieces; the chunk's grids in the float-grid buffer of bev_float_bev_batch. */
 int bev_submap_float_bev_batch(bev_ctx_t *c, int n_frames, const bev_point_t *const *clouds, const uint32_t *n_pts, float interval,
                                int skip_label0, int n_maps, const uint64_t *h_map_offsets, const int32_t *h_entry_frame,
                                const float *h_entry_pose, float *const *out)
@@ -593,38 +506,19 @@ int bev_submap_float_bev_batch(bev_ctx_t *c, int n_frames, const bev_point_t *co
     rc = c->manip_grids.grow(c, (size_t)chunk * per_map * sizeof(float));
     if (rc != BEV_OK) return rc;
     float *grids = static_cast<float *>(c->manip_grids.p);
-    const auto chunks = [&]() -> int {
-        std::vector<uint64_t> offs((size_t)n_frames + 1, 0); /* (only the counts matter: a row's offset is set per piece) */
-        for (int f = 0; f < n_frames; ++f) offs[f + 1] = offs[f] + n_pts[f];
-        for (int m0 = 0; m0 < n_maps; m0 += chunk) {
-            const int nm = std::min(chunk, n_maps - m0);
-            SubmapPlanUp u;
-            if (!bevsub::plan_maps(u.plan, offs.data(), h_map_offsets, m0, m0 + nm, h_entry_frame, h_entry_pose, (size_t)nm))
-                return BEV_ERR_TOO_LARGE;
-            const bevsub::Group &g = u.plan.groups[0];
-            bevsub::Frame *rows = u.plan.rows.data() + g.row0;
-            for (int r = 0; r < g.n_rows; ++r) /* where the row's frame will lie in the staging while its piece is there */
-                rows[r].off = r % c->max_batch ? rows[r - 1].off + rows[r - 1].n : 0;
-            const int rc_ = submap_tables_up(c, u);
-            if (rc_ != BEV_OK) return rc_;
+    const HostMaps a{n_frames, clouds, n_pts, n_maps, h_map_offsets, h_entry_frame, h_entry_pose, &c->submap_tab};
+    return end_host_call(c, host_map_chunks(
+        c, a, chunk,
+        [&](int, int nm) -> int {
             HIPCK(c, hipMemsetAsync(grids, 0, (size_t)nm * per_map * sizeof(float), c->stream));
-            for (int r0 = 0; r0 < g.n_rows; r0 += c->max_batch) {
-                const int nr = std::min(c->max_batch, g.n_rows - r0);
-                for (int r = r0; r < r0 + nr; ++r)
-                    if (rows[r].n)
-                        HIPCK(c, hipMemcpyAsync(c->st_in + rows[r].off, clouds[u.plan.frame[g.row0 + r]],
-                                                (size_t)rows[r].n * sizeof(bev_point_t), hipMemcpyHostToDevice, c->stream));
-                submap_float_splat(c, u, c->st_in, r0, nr, fg, grids);
-            }
+            return BEV_OK;
+        },
+        [&](const TablesUp &u, int r0, int nr) { submap_float_splat(c, u, c->st_in, r0, nr, fg, grids); },
+        [&](int m0, int nm) -> int {
             HIPCK(c, hipGetLastError());
             for (int m = 0; m < nm; ++m)
                 HIPCK(c, hipMemcpyAsync(out[m0 + m], grids + (size_t)m * per_map, per_map * sizeof(float), hipMemcpyDeviceToHost,
                                         c->stream));
-        }
-        HIPCK(c, hipStreamSynchronize(c->stream));
-        return BEV_OK;
-    };
-    rc = chunks();
-    if (rc != BEV_OK) (void)hipDeviceSynchronize();
-    return rc;
+            return BEV_OK;
+        }));
 }

@@ -1,14 +1,14 @@
 /*
  * bev_capi_place.hip — place retrieval of the boundary declared extern "C" in include/bev_mi355x.h: polar
  * max-height descriptors of frames or of submaps over packed frames, and the match list of queries against a database.
- * Host-side only; the kernels are bev_place.h's, the arithmetic bev_place_exact.h's, the maps' plan bev_submap_plan.h's (§6i),
- * the bracket of a device-resident call and the argument checks bev_ctx.h's.
+ * Host-side only; the kernels are bev_place.h's, the arithmetic bev_place_exact.h's, the maps' plan bev_submap_plan.h's (§6i);
+ * the prologue of the descriptor call, the tables on their way up and both loops of bev_place_retrieval_batch are
+ * bev_packed_host.h's, shared with the submap calls and the translation guess.
  */
 #include <cstdlib>
 
-#include "bev_ctx.h"
+#include "bev_packed_host.h"
 #include "bev_place_exact.h"
-#include "bev_submap_plan.h"
 
 using namespace bevh; /* (and through it bevk) */
 using namespace bevx;
@@ -33,65 +33,15 @@ bool place_call(const bev_ctx *c, const bev_place_params_t *params, PlaceCall *p
 
 constexpr size_t kEdgeBytes = 256; /* the ring edges lead the block that goes up; the tables follow, 64-byte aligned */
 
-/* The tables of a descriptor call on their way to the device, in ONE block of place_tab: the ring edges, then either the frame
- * table of a call without maps (rows: nf + 1 ProjFrame) or the one launch group of a plan over maps (§6i). */
-struct PlaceUp {
-    bool maps = false;
-    std::vector<bevsub::Frame> rows; /* without maps */
-    bevsub::Plan plan;               /* with maps: groups[0] */
-    bevsub::GroupBytes at{};
-    const char *dev = nullptr;
-    const bevsub::Frame *host_rows() const { return maps ? plan.rows.data() + plan.groups[0].row0 : rows.data(); }
-    int n_rows() const { return maps ? plan.groups[0].n_rows : (int)rows.size() - 1; }
-};
-/* the frame table of nf frames [offs[f], offs[f + 1]): false for more workgroups than a launch can have */
-bool place_rows(PlaceUp &u, int nf, const uint64_t *offs)
+/* rows [r0, r0 + nr) of the tables that went up behind the ring edges (TablesUp, bev_packed_host.h; the one launch group of a
+ * plan over maps, or the frame table) splatted from d_clouds into planes (left out where they hold no point) */
+void place_splat(bev_ctx *c, const TablesUp &u, const PlaceCall &pc, const bev_point_t *d_clouds, int r0, int nr, uint32_t *planes)
 {
-    uint64_t b = 0;
-    u.rows.resize((size_t)nf + 1);
-    for (int f = 0; f < nf; ++f) {
-        const uint32_t n = (uint32_t)(offs[f + 1] - offs[f]);
-        u.rows[f] = bevsub::Frame{offs[f], n, (uint32_t)b};
-        b += (n + bevsub::kBlockPoints - 1u) / bevsub::kBlockPoints;
-        if (b > 0x7fffffffull) return false;
-    }
-    u.rows[nf] = bevsub::Frame{offs[nf], 0u, (uint32_t)b};
-    return true;
-}
-int place_tables_up(bev_ctx *c, PlaceUp &u, const PlaceCall &pc)
-{
-    size_t bytes = kEdgeBytes;
-    if (u.maps) {
-        u.at = bevsub::group_bytes(u.plan.groups[0], kEdgeBytes);
-        bytes = u.at.end;
-    } else {
-        bytes += u.rows.size() * sizeof(bevsub::Frame);
-    }
-    char *h = nullptr;
-    const int rc = c->place_tab.begin(c, bytes, 64 * 1024, reinterpret_cast<void **>(&h));
-    if (rc != BEV_OK) return rc;
-    memset(h, 0, kEdgeBytes);
-    memcpy(h, pc.edge2, sizeof pc.edge2);
-    if (u.maps) bevsub::pack(u.plan, h + kEdgeBytes);
-    else memcpy(h + kEdgeBytes, u.rows.data(), u.rows.size() * sizeof(bevsub::Frame));
-    u.dev = static_cast<const char *>(c->place_tab.dev);
-    return c->place_tab.push(c, bytes);
-}
-/* rows [r0, r0 + nr) of the uploaded tables splatted from d_clouds into planes (left out where they hold no point) */
-void place_splat(bev_ctx *c, const PlaceUp &u, const PlaceCall &pc, const bev_point_t *d_clouds, int r0, int nr, uint32_t *planes)
-{
-    const bevsub::Frame *rows = u.host_rows();
-    const uint32_t blocks = rows[r0 + nr].blk0 - rows[r0].blk0;
-    if (blocks == 0) return;
-    const float *d_edge = reinterpret_cast<const float *>(u.dev);
+    const TablesUp::Slice s = u.slice(0, r0, nr);
+    if (s.blocks == 0) return;
     ProfScope ps(c, K_PLACE_SPLAT, nr);
-    if (u.maps)
-        launch_place_splat(d_clouds, u.dev + u.at.rows + (size_t)r0 * sizeof(bevsub::Frame),
-                           reinterpret_cast<const uint32_t *>(u.dev + u.at.ent0) + r0, nr, blocks, u.dev + u.at.entries, d_edge,
-                           pc.ps, planes, c->stream);
-    else
-        launch_place_splat(d_clouds, u.dev + kEdgeBytes + (size_t)r0 * sizeof(bevsub::Frame), nullptr, nr, blocks, nullptr, d_edge,
-                           pc.ps, planes, c->stream);
+    launch_place_splat(d_clouds, s.rows, s.ent0, nr, s.blocks, s.entries, reinterpret_cast<const float *>(u.dev), pc.ps, planes,
+                       c->stream);
 }
 void place_finish(bev_ctx *c, const PlaceCall &pc, const uint32_t *planes, int n_desc, uint8_t *d_desc, void *d_units)
 {
@@ -114,18 +64,16 @@ int place_planes(bev_ctx *c, const PlaceCall &pc, int n_desc, uint32_t **planes)
 int place_descriptors(bev_ctx *c, const PlaceCall &pc, int nf, const bev_point_t *d_clouds, const uint64_t *offs, int n_maps,
                       const uint64_t *map_offs, const int32_t *entry_frame, const float *entry_pose, uint8_t *d_desc, void *d_units)
 {
-    PlaceUp u;
-    u.maps = map_offs != nullptr;
-    const int n_desc = u.maps ? n_maps : nf;
-    if (u.maps ? !bevsub::plan_maps(u.plan, offs, map_offs, 0, n_maps, entry_frame, entry_pose, (size_t)n_maps)
-               : !place_rows(u, nf, offs))
+    TablesUp u;
+    const int n_desc = map_offs ? n_maps : nf;
+    if (map_offs ? !bevsub::plan_maps(u.plan, offs, map_offs, 0, n_maps, entry_frame, entry_pose, (size_t)n_maps) : !u.frames(nf, offs))
         return BEV_ERR_TOO_LARGE;
     uint32_t *planes = nullptr;
     int rc = place_planes(c, pc, n_desc, &planes); /* (a grow waits for the stream: before the tables go up) */
     if (rc != BEV_OK) return rc;
-    rc = place_tables_up(c, u, pc);
+    rc = u.up(c, c->place_tab, kEdgeBytes, pc.edge2, sizeof pc.edge2);
     if (rc != BEV_OK) return rc;
-    place_splat(c, u, pc, d_clouds, 0, u.n_rows(), planes);
+    place_splat(c, u, pc, d_clouds, 0, u.plan.groups[0].n_rows, planes);
     place_finish(c, pc, planes, n_desc, d_desc, d_units);
     HIPCK(c, hipGetLastError());
     return BEV_OK;
@@ -175,15 +123,6 @@ int place_match(bev_ctx *c, const PlaceCall &pc, int n_queries, const void *d_un
     return BEV_OK;
 }
 
-/* the map arrays of a place call: all NULL with n_maps == 0 (no maps: the frames), or the submap calls' */
-int check_place_maps(int n_frames, int n_maps, const uint64_t *map_offs, const int32_t *entry_frame, const float *entry_pose,
-                     bool *maps)
-{
-    *maps = map_offs != nullptr;
-    if (!map_offs) return (n_maps == 0 && !entry_frame && !entry_pose) ? BEV_OK : BEV_ERR_INVALID_ARG;
-    return check_submap_entries(n_frames, n_maps, map_offs, entry_frame, entry_pose);
-}
-
 } // namespace
 
 extern "C" {
@@ -209,20 +148,9 @@ int bev_place_descriptor_device_resident(bev_ctx_t *c, int n_frames, const bev_p
 {
     PlaceCall pc;
     if (!c || !place_call(c, params, &pc)) return BEV_ERR_INVALID_ARG;
-    const int rc = check_packed_frames(c, n_frames, h_offsets);
-    if (rc == BEV_ERR_INVALID_ARG) return rc;
-    bool maps = false;
-    const int rc_maps = check_place_maps(n_frames, n_maps, h_map_offsets, h_entry_frame, h_entry_pose, &maps);
-    if (rc_maps != BEV_OK) return rc_maps;
-    if (rc != BEV_OK) return rc; /* (a frame that is too large: behind the arguments that are wrong) */
-    if ((maps ? n_maps : n_frames) == 0) return BEV_OK;
-    if ((!d_desc && !d_units) || reinterpret_cast<uintptr_t>(d_units) % 64 != 0) return BEV_ERR_INVALID_ARG;
-    if (!d_clouds) { /* records to read */
-        if (!maps && h_offsets[n_frames] != h_offsets[0]) return BEV_ERR_INVALID_ARG;
-        for (uint64_t e = maps ? h_map_offsets[0] : 0; maps && e < h_map_offsets[n_maps]; ++e)
-            if (h_offsets[h_entry_frame[e] + 1] != h_offsets[h_entry_frame[e]]) return BEV_ERR_INVALID_ARG;
-    }
-    return resident_call(c, [&] {
+    const FramesAndMaps a{n_frames, d_clouds, h_offsets, n_maps, h_map_offsets, h_entry_frame, h_entry_pose};
+    const bool outputs_ok = (d_desc || d_units) && reinterpret_cast<uintptr_t>(d_units) % 64 == 0;
+    return resident_maps_call(c, a, true, BEV_OK, outputs_ok, [&] {
         return place_descriptors(c, pc, n_frames, d_clouds, h_offsets, n_maps, h_map_offsets, h_entry_frame, h_entry_pose, d_desc,
                                  d_units);
     });
@@ -250,7 +178,7 @@ int bev_place_retrieval_batch(bev_ctx_t *c, int n_frames, const bev_point_t *con
     PlaceCall pc;
     if (!c || !place_call(c, params, &pc) || n_frames < 0 || !host_clouds_ok(n_frames, clouds, n_pts)) return BEV_ERR_INVALID_ARG;
     bool maps = false;
-    int rc = check_place_maps(n_frames, n_maps, h_map_offsets, h_entry_frame, h_entry_pose, &maps);
+    int rc = check_optional_maps(n_frames, n_maps, h_map_offsets, h_entry_frame, h_entry_pose, &maps);
     if (rc != BEV_OK) return rc;
     const int n_db = maps ? n_maps : n_frames;
     if (top_k < 1 || top_k > BEV_PLACE_MAX_TOP_K || !limits_ok(n_frames, n_db, h_limit) || (n_frames > 0 && !hits))
@@ -266,58 +194,31 @@ int bev_place_retrieval_batch(bev_ctx_t *c, int n_frames, const bev_point_t *con
     if (rc != BEV_OK) return rc;
     PlaceHandle *units_q = static_cast<PlaceHandle *>(c->place_out.p), *units_db = maps ? units_q + n_frames : units_q;
     bev_place_hit_t *d_hits = reinterpret_cast<bev_place_hit_t *>(static_cast<char *>(c->place_out.p) + unit_bytes);
-    const auto chunks = [&]() -> int {
-        std::vector<uint64_t> off;
-        for (int f0 = 0; f0 < n_frames; f0 += c->max_batch) {
-            const int nb = std::min(c->max_batch, n_frames - f0);
-            off.assign((size_t)nb + 1, 0);
-            for (int f = 0; f < nb; ++f) {
-                off[f + 1] = off[f] + n_pts[f0 + f];
-                if (n_pts[f0 + f])
-                    HIPCK(c, hipMemcpyAsync(c->st_in + off[f], clouds[f0 + f], (size_t)n_pts[f0 + f] * sizeof(bev_point_t),
-                                            hipMemcpyHostToDevice, c->stream));
-            }
-            const int rc_ = place_descriptors(c, pc, nb, c->st_in, off.data(), 0, nullptr, nullptr, nullptr, nullptr, units_q + f0);
-            if (rc_ != BEV_OK) return rc_;
-        }
-        std::vector<uint64_t> offs((size_t)n_frames + 1, 0); /* (only the counts matter: a row's offset is set per piece) */
-        for (int f = 0; f < n_frames; ++f) offs[f + 1] = offs[f] + n_pts[f];
-        const int chunk = std::min(std::max(n_maps, 1), c->max_batch);
-        for (int m0 = 0; maps && m0 < n_maps; m0 += chunk) {
-            const int nm = std::min(chunk, n_maps - m0);
-            PlaceUp u;
-            u.maps = true;
-            if (!bevsub::plan_maps(u.plan, offs.data(), h_map_offsets, m0, m0 + nm, h_entry_frame, h_entry_pose, (size_t)nm))
-                return BEV_ERR_TOO_LARGE;
-            const bevsub::Group &g = u.plan.groups[0];
-            bevsub::Frame *rows = u.plan.rows.data() + g.row0;
-            for (int r = 0; r < g.n_rows; ++r) /* where the row's frame will lie in the staging while its piece is there */
-                rows[r].off = r % c->max_batch ? rows[r - 1].off + rows[r - 1].n : 0;
+    const auto body = [&]() -> int {
+        int rc_ = packed_chunks(c, n_frames, clouds, n_pts, [&](int f0, int nb, const uint64_t *off) {
+            return place_descriptors(c, pc, nb, c->st_in, off, 0, nullptr, nullptr, nullptr, nullptr, units_q + f0);
+        });
+        if (rc_ != BEV_OK) return rc_;
+        if (maps) {
             uint32_t *planes = nullptr;
-            int rc_ = place_planes(c, pc, nm, &planes);
+            const HostMaps a{n_frames, clouds, n_pts, n_maps, h_map_offsets, h_entry_frame, h_entry_pose, &c->place_tab,
+                             kEdgeBytes, pc.edge2, sizeof pc.edge2};
+            rc_ = host_map_chunks(
+                c, a, std::min(std::max(n_maps, 1), c->max_batch), [&](int, int nm) { return place_planes(c, pc, nm, &planes); },
+                [&](const TablesUp &u, int r0, int nr) { place_splat(c, u, pc, c->st_in, r0, nr, planes); },
+                [&](int m0, int nm) -> int {
+                    place_finish(c, pc, planes, nm, nullptr, units_db + m0);
+                    HIPCK(c, hipGetLastError());
+                    return BEV_OK;
+                });
             if (rc_ != BEV_OK) return rc_;
-            rc_ = place_tables_up(c, u, pc);
-            if (rc_ != BEV_OK) return rc_;
-            for (int r0 = 0; r0 < g.n_rows; r0 += c->max_batch) {
-                const int nr = std::min(c->max_batch, g.n_rows - r0);
-                for (int r = r0; r < r0 + nr; ++r)
-                    if (rows[r].n)
-                        HIPCK(c, hipMemcpyAsync(c->st_in + rows[r].off, clouds[u.plan.frame[g.row0 + r]],
-                                                (size_t)rows[r].n * sizeof(bev_point_t), hipMemcpyHostToDevice, c->stream));
-                place_splat(c, u, pc, c->st_in, r0, nr, planes);
-            }
-            place_finish(c, pc, planes, nm, nullptr, units_db + m0);
-            HIPCK(c, hipGetLastError());
         }
-        const int rc_ = place_match(c, pc, n_frames, units_q, n_db, units_db, h_limit, top_k, d_hits);
+        rc_ = place_match(c, pc, n_frames, units_q, n_db, units_db, h_limit, top_k, d_hits);
         if (rc_ != BEV_OK) return rc_;
         HIPCK(c, hipMemcpyAsync(hits, d_hits, hit_bytes, hipMemcpyDeviceToHost, c->stream));
-        HIPCK(c, hipStreamSynchronize(c->stream));
         return BEV_OK;
     };
-    rc = chunks();
-    if (rc != BEV_OK) (void)hipDeviceSynchronize();
-    return rc;
+    return end_host_call(c, body());
 }
 
 } /* extern "C" */

@@ -3,8 +3,9 @@
  * pipeline and the single-cloud entry points), bev_capi_packed.hip (the batched calls over packed frames), bev_capi_reg.hip
  * (the registration entry points, frame against frame), bev_capi_submap_reg.hip (frames against submaps; what only these
  * two and bev_capi_verify.hip share: bev_reg_host.h), bev_capi_place.hip (place retrieval), bev_capi_verify.hip (verification of
- * registered matches) and bev_capi_align.hip (the translation guess of retrieved pairs) — among it the prologue of every call outside the fused pipeline (begin_call) and the bound
- * on a cloud's points (cloud_cap).  Private, like bev_internal.h.  Named namespace: struct bev_ctx is one type in all of them.
+ * registered matches) and bev_capi_align.hip (the translation guess of retrieved pairs; what it, bev_capi_place.hip and
+ * bev_capi_packed.hip share over maps: bev_packed_host.h) — among it the prologue of every call outside the fused pipeline
+ * (begin_call) and the bound on a cloud's points (cloud_cap).  Private, like bev_internal.h.  Named namespace: struct bev_ctx is one type in all of them.
  */
 #ifndef BEV_CTX_H
 #define BEV_CTX_H
@@ -265,7 +266,7 @@ struct bev_ctx {
      * grown on demand */
     bevh::UploadTable posed_tab;
     bevh::DevBuf posed_ws, posed_imgs;
-    /* ... of submaps (submap_plan_up & co., bev_capi_packed.hip): the plan of a call; the planes are posed_ws, the images of
+    /* ... of submaps (TablesUp, bev_packed_host.h; bev_capi_packed.hip): the plan of a call; the planes are posed_ws, the images of
      * bev_submap_bev_batch's chunks posed_imgs (both host-buffer calls are synchronous).  The float submap calls
      * (submap_float_frames) send their plan up the same table and have no planes: their output is the accumulator */
     bevh::UploadTable submap_tab;
@@ -349,7 +350,7 @@ int project_frames(bev_ctx *c, int kind, int nf, const float *d_xyzi, const uint
  * arrays are read only when their length has passed. */
 int check_submap_entries(int n_frames, int n_maps, const uint64_t *map_offs, const int32_t *entry_frame, const float *entry_pose);
 
-/* ---- what the calls over packed frames share across files (bev_capi_packed.hip, bev_capi_place.hip) ---- */
+/* ---- what the calls over packed frames share across files (more of it, over maps: bev_packed_host.h) ---- */
 /* the arguments every call over packed frames of the caller's has: BEV_OK, or what the entry point returns */
 inline int check_packed_frames(const bev_ctx *c, int n_frames, const uint64_t *h_offsets)
 {

@@ -21,25 +21,23 @@
 namespace bevk {
 using namespace bevx;
 
-/* A workgroup is kProjBlock points of one row's frame (k_submap_float_splat's shape).  kMaps: per entry of the row (a uniform
- * loop), the moved points into the entry's descriptor; else the raw coordinates into descriptor pl.f (NOT an identity pose).
- * The LDS plane takes the workgroup's maxima, and only its non-zero cells go out: a cell's value is 0 ... 127, 0 is "empty". */
-template <bool kMaps>
-__global__ __launch_bounds__(256) void k_place_splat(const bev_point_t *__restrict__ clouds, const ProjFrame *__restrict__ tab,
-                                                     const uint32_t *__restrict__ ent0, int nf,
-                                                     const bevsub::Entry *__restrict__ entries,
-                                                     const float *__restrict__ edge2, PlaceShape ps, uint32_t *__restrict__ planes)
+/* The max-height splat of a workgroup of 256 threads over a plane of `cells` words of LDS at s_cell (free on entry; what else
+ * of LDS cell_of reads is written by the caller, before the call).  The workgroup is kProjBlock points of one row's frame
+ * (k_submap_float_splat's shape).  kMaps: per entry of the row (a uniform loop), the moved points into the entry's plane; else
+ * the raw coordinates into plane pl.f (NOT an identity pose).  cell_of(x, y, label): the point's cell, or -1.  The LDS plane
+ * takes the workgroup's maxima, and only its non-zero cells go out: a cell's value is 0 ... 127, 0 is "empty". */
+template <bool kMaps, class Cell>
+__device__ __forceinline__ void lds_max_splat(const bev_point_t *__restrict__ clouds, const ProjFrame *__restrict__ tab,
+                                              const uint32_t *__restrict__ ent0, int nf, const bevsub::Entry *__restrict__ entries,
+                                              int skip_label0, float lidar_to_ground, int cells, uint32_t *s_cell,
+                                              uint32_t *__restrict__ planes, Cell cell_of)
 {
-    __shared__ float s_edge[kPlaceMaxRings + 1];
-    __shared__ uint32_t s_cell[kPlaceMaxRings * kPlaceMaxSectors];
-    const int cells = ps.n_rings * ps.n_sectors;
     const PackedPlace pl = packed_place(tab, nf, blockIdx.x + tab[0].blk0);
     const uint32_t n = pl.n, k0 = pl.k0;
-    if ((int)threadIdx.x <= ps.n_rings) s_edge[threadIdx.x] = edge2[threadIdx.x];
     for (int i = (int)threadIdx.x; i < cells; i += 256) s_cell[i] = 0u;
     float4 a[kProjPerThread];
     int label[kProjPerThread];
-    load_packed_records(clouds + pl.off, n, k0, ps.skip_label0 != 0, 1, a, label);
+    load_packed_records(clouds + pl.off, n, k0, skip_label0 != 0, 1, a, label);
     __syncthreads();
     const uint32_t e0 = kMaps ? ent0[pl.f] : 0u, e1 = kMaps ? ent0[pl.f + 1] : 1u;
     for (uint32_t e = e0; e < e1; ++e) {
@@ -49,9 +47,9 @@ __global__ __launch_bounds__(256) void k_place_splat(const bev_point_t *__restri
         for (int j = 0; j < kProjPerThread; ++j) {
             float x = a[j].x, y = a[j].y, z = a[j].z;
             if (kMaps) transform_xyz(en.m, a[j].x, a[j].y, a[j].z, x, y, z);
-            int cell = place_cell(s_edge, ps.n_rings, ps.n_sectors, x, y, label[j], ps.skip_label0);
+            int cell = cell_of(x, y, label[j]);
             if (k0 + (uint32_t)j * 256u >= n) cell = -1;
-            const int v = place_value(z, ps.lidar_to_ground);
+            const int v = place_value(z, lidar_to_ground);
             if (cell >= 0 && v > 0) atomicMax(&s_cell[cell], (uint32_t)v);
         }
         __syncthreads();
@@ -65,6 +63,20 @@ __global__ __launch_bounds__(256) void k_place_splat(const bev_point_t *__restri
         }
         __syncthreads();
     }
+}
+
+/* lds_max_splat over the polar cells of a descriptor; the ring edges lie in LDS beside the plane */
+template <bool kMaps>
+__global__ __launch_bounds__(256) void k_place_splat(const bev_point_t *__restrict__ clouds, const ProjFrame *__restrict__ tab,
+                                                     const uint32_t *__restrict__ ent0, int nf,
+                                                     const bevsub::Entry *__restrict__ entries,
+                                                     const float *__restrict__ edge2, PlaceShape ps, uint32_t *__restrict__ planes)
+{
+    __shared__ float s_edge[kPlaceMaxRings + 1];
+    __shared__ uint32_t s_cell[kPlaceMaxRings * kPlaceMaxSectors];
+    if ((int)threadIdx.x <= ps.n_rings) s_edge[threadIdx.x] = edge2[threadIdx.x];
+    lds_max_splat<kMaps>(clouds, tab, ent0, nf, entries, ps.skip_label0, ps.lidar_to_ground, ps.n_rings * ps.n_sectors, s_cell, planes,
+                         [=](float x, float y, int label) { return place_cell(s_edge, ps.n_rings, ps.n_sectors, x, y, label, ps.skip_label0); });
 }
 
 /* One wave per descriptor, lane s its sector s: the column's bytes, its squared length, its unit values padded to

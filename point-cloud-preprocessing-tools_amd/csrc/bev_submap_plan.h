@@ -1,7 +1,8 @@
 /*
  * bev_submap_plan.h — the host plan of a submap call (bev_submap_bev_device_resident, bev_submap_bev_batch):
- * which (frame, pose) entry goes into which grid of which launch group.  Plain C++, no HIP: bev_capi.hip builds and uploads
- * the plan, tests/submapcheck builds it, runs it on the host and checks its invariants.
+ * which (frame, pose) entry goes into which grid of which launch group; and the packed-frame table of a call without maps
+ * (frame_table), whose rows a group's rows are.  Plain C++, no HIP: the C ABI files build and upload the plan (TablesUp,
+ * bev_packed_host.h), tests/submapcheck builds it, runs it on the host and checks its invariants.
  *
  * A call is cut into launch groups of at most `cap` consecutive maps; a map is a grid of its group.  Per group:
  *   rows     the distinct frames that have entries in the group's maps, ascending by frame index, as a packed-frame table
@@ -34,6 +35,27 @@ struct alignas(64) Entry { /* one aligned 64-byte line per entry: the splat read
     uint32_t pad[3];
 };
 static_assert(sizeof(Frame) == 16 && sizeof(Entry) == 64, "the device reads these layouts");
+
+/* The packed-frame table of nf frames, frame f = records [offs[f], offs[f + 1]) (offsets checked by the caller), in
+ * rows[0 .. nf]: per frame its offset, its count and the workgroups before it, row nf closing the table with the workgroups of
+ * a launch over all frames (*blocks) at offs[nf]; *n_max: the longest frame.  false: more workgroups than a launch can have
+ * (2^31 - 1), the rows then unfinished. */
+inline bool frame_table(Frame *rows, int nf, const uint64_t *offs, uint32_t *n_max, uint32_t *blocks)
+{
+    uint64_t b = 0;
+    uint32_t m = 0;
+    for (int f = 0; f < nf; ++f) {
+        const uint32_t n = (uint32_t)(offs[f + 1] - offs[f]);
+        rows[f] = Frame{offs[f], n, (uint32_t)b};
+        b += ((uint64_t)n + kBlockPoints - 1u) / kBlockPoints; /* (in 64 bits: a count near 2^32 must not wrap to no workgroup) */
+        m = std::max(m, n);
+        if (b > 0x7fffffffull) return false;
+    }
+    rows[nf] = Frame{offs[nf], 0u, (uint32_t)b};
+    *n_max = m;
+    *blocks = (uint32_t)b;
+    return true;
+}
 
 struct Group {
     int map0 = 0, n_maps = 0; /* maps [map0, map0 + n_maps) of the call: grids 0 .. n_maps - 1 */

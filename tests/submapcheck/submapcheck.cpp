@@ -6,7 +6,8 @@
  * frame table (packed_place's binary search), the workgroup's 1024 points, per entry of the row posed_code (csrc/bev_exact.h)
  * into the two planes of the entry's grid.  The planes are expanded as tests/posedcheck does and every byte of both images of
  * every map is compared with oracle_multi_bev / oracle_single_bev of the concatenated oracle_transform_cloud outputs.  The
- * plan's invariants are asserted on the way.  A stand-alone program: exit status 0 and a last line "submapcheck ok: ..." when
+ * plan's invariants are asserted on the way.  The packed-frame table that the calls without maps send up instead of a plan
+ * (bevsub::frame_table) is checked from offsets alone: its rows, its closing row and the limit of a launch.  A stand-alone program: exit status 0 and a last line "submapcheck ok: ..." when
  * every case agrees, 1 and the failing cases otherwise.
  */
 #include <algorithm>
@@ -172,6 +173,56 @@ void run_group(const char *block, const bevsub::GroupBytes &at, const bevsub::Gr
     }
 }
 
+/* bevsub::frame_table from offsets alone (no clouds): every row, the closing row, the longest frame, and the limit of a launch;
+ * returns the tables checked */
+int check_frame_tables()
+{
+    int tables = 0;
+    const auto run = [&](const std::vector<uint32_t> &sizes, bool want_ok, const char *tag) {
+        const int nf = (int)sizes.size();
+        std::vector<uint64_t> offs(1, 7); /* (a table need not start at record 0) */
+        uint64_t want_blocks = 0;
+        uint32_t want_max = 0;
+        for (uint32_t n : sizes) {
+            offs.push_back(offs.back() + n);
+            want_blocks += ((uint64_t)n + 1023u) / 1024u;
+            want_max = std::max(want_max, n);
+        }
+        const bevsub::Frame untouched{~0ull, ~0u, ~0u};
+        std::vector<bevsub::Frame> rows((size_t)nf + 2, untouched); /* (one row behind the closing row: a guard) */
+        uint32_t n_max = 12345u, blocks = 12345u;
+        const bool ok = bevsub::frame_table(rows.data(), nf, offs.data(), &n_max, &blocks);
+        ++tables;
+        CHECK(ok == want_ok, "frame table %s: %s, %llu workgroups", tag, ok ? "accepted" : "refused", (unsigned long long)want_blocks);
+        CHECK(rows[(size_t)nf + 1].off == untouched.off && rows[(size_t)nf + 1].n == untouched.n, "frame table %s: a row behind the table was written", tag);
+        if (!ok || !want_ok) return;
+        CHECK(n_max == want_max && blocks == want_blocks, "frame table %s: longest %u (%u), workgroups %u (%llu)", tag, n_max, want_max,
+              blocks, (unsigned long long)want_blocks);
+        uint64_t b = 0;
+        for (int f = 0; f < nf; ++f) {
+            CHECK(rows[f].off == offs[f] && rows[f].n == sizes[f] && rows[f].blk0 == b, "frame table %s: row %d", tag, f);
+            b += ((uint64_t)sizes[f] + 1023u) / 1024u;
+        }
+        CHECK(rows[nf].off == offs[nf] && rows[nf].n == 0u && rows[nf].blk0 == want_blocks, "frame table %s: the closing row", tag);
+    };
+    run({}, true, "empty");
+    run({0}, true, "0");
+    run({1}, true, "1");
+    run({1023}, true, "1023");
+    run({1024}, true, "1024");
+    run({1025}, true, "1025");
+    run({0, 1, 1023, 1024, 1025, 0, 5000, 1}, true, "mixed"); /* 0 + 1 + 1 + 1 + 2 + 0 + 5 + 1 workgroups */
+    /* a frame of 0xffffffff records is 4194304 workgroups: 511 of them are 2143289344 <= 2^31 - 1, 512 are exactly 2^31 */
+    run(std::vector<uint32_t>(511, 0xffffffffu), true, "511 frames of 2^32 - 1");
+    run(std::vector<uint32_t>(512, 0xffffffffu), false, "512 frames of 2^32 - 1");
+    std::vector<uint32_t> edge(511, 0xffffffffu);
+    edge.push_back(4194303u * 1024u); /* 2143289344 + 4194303 = 2^31 - 1 exactly: the most a launch can have */
+    run(edge, true, "2^31 - 1 workgroups");
+    edge.push_back(1u);
+    run(edge, false, "2^31 workgroups");
+    return tables;
+}
+
 Scenario mixed()
 {
     Scenario s;
@@ -332,6 +383,8 @@ int main()
             }
         }
     }
+    const int bad_before = g_bad, tables = check_frame_tables();
+    printf("frame tables: %d checked, %d failed checks\n", tables, g_bad - bad_before);
     if (g_bad || bad_images || set_bytes == 0 || general_bytes == 0 || prefix_sizes != 15) /* (frames of 0, 1, 1024 and 1025 records were rows) */ {
         printf("submapcheck FAILED: %d plan checks, %d of %d images\n", g_bad, bad_images, cases + general_cases);
         return 1;

@@ -45,6 +45,17 @@ def test_plans_run_on_the_host_equal_the_oracle_composition():
     _assert_ok(run)
 
 
+def test_frame_table_rows_closing_row_and_the_limit_of_a_launch():
+    """bevsub::frame_table, from offsets alone: frames of 0, 1, 1023, 1024, 1025 records and an empty table; the closing row's
+    blk0 is the sum of ceil(n / 1024) and the longest frame is reported; 511 frames of 0xffffffff records (2143289344
+    workgroups) are accepted, 512 (2^31) are refused, and so is one workgroup past 2^31 - 1"""
+    built, run = _build_and_run()
+    assert built.returncode == 0, built.stdout
+    assert run.returncode == 0, run.stdout + run.stderr
+    assert "frame tables: 11 checked, 0 failed checks" in run.stdout.splitlines(), run.stdout
+    assert "PLAN frame table" not in run.stdout
+
+
 def test_the_same_under_the_address_and_undefined_behaviour_sanitizers(tmp_path):
     probe = tmp_path / "probe.c"
     probe.write_text("int main(void) { return 0; }\n")
